@@ -19,7 +19,16 @@ Inputs (the other BASELINE configs, same JSON contract):
   --emulate-rank r/P                    ONE GPU runs rank r of a P-rank job (exchange = no-op on resident slabs):
                                         the shard shapes that 2/4/8 GPUs run, with a roofline object per launch group
 
-Extra objects in the JSON line:
+A plain run sets up, warms up, times the K steps and prints the line: what the headline `value` / `ms_per_step` need and
+nothing else.  The other figures and checks below run only with --full:
+  --full                                the roofline (HIP events around the dominant kernel inside the timed region, plus a
+                                        per-kernel split after it), the halo launch groups and the exchange probe, the
+                                        cpu_baseline, the first-contact self-test of an N > 1 job and, at N > 1, the
+                                        replays of a captured HIP graph (--graph auto)
+  --dump-outputs DIR                    after the timed steps: what the last one computed, as DIR/<name>.npy (see
+                                        dump_outputs) -- the inputs are seeded, so two builds compare output for output
+
+Extra objects in the JSON line (--full):
   roofline     dominant kernel = the local-block SpMM A_loc.H, ONE launch group: spmm_tasks_kernel (XCD-sliced
                gather part) + spmm_strip_kernel (512 x 128 LDS-staged strip tiles) + spmm_dense_kernel (fp32-MFMA
                tiles) (+ spmm_core_kernel, the 128 x 128 LDS core, on small blocks) + the fix-up that adds their
@@ -51,6 +60,8 @@ sys.path.insert(0, ROOT)
 PKG = "scalable-graph-convolutional-network-training-on-distributed-memory-systems_amd"
 
 HBM_PEAK = 8.0e12  # B/s, MI355X_MICROARCH.md (6.29e12 measured copy ceiling)
+DUMP_ROWS = 16384  # --dump-outputs: rows of each n x f output written (a fixed sample; the whole Reddit-shaped output is 119 MB)
+DUMP_MAX_BYTES = 64 << 20
 
 
 def pkg(sub):
@@ -615,6 +626,40 @@ def graph_replay(model, make_model, H, labels, n, P, steps, dev, eager_ms, world
         return {"captured": False, "error": repr(e)[:300]}
 
 
+def dump_outputs(path, part, n, loss, out, H, model):
+    """--dump-outputs: what the last timed step computed, as .npy files under `path` (float32 unless said; DUMP_MAX_BYTES at most):
+      loss                  the step's loss
+      vertex_ids            the global ids of the sampled rows below, ascending (float64: exact)
+      output                the model's output on those rows (a fixed seeded sample of the vertices, DUMP_ROWS of them)
+      input_grad            the gradient that reached the input features on those rows -- summed over the warm-up and timed
+                            steps, as the step leaves it (H is not a parameter: nothing zeroes its gradient)
+      param.<name>          every parameter after the step's optimizer update
+      grad.<name>           its gradient of that step (N > 1: after the all-reduce)
+    N > 1: this rank's rows of the sample."""
+    arrays = {"loss": np.array([loss.detach().item()], np.float32)}
+    for name, p in model.named_parameters():
+        arrays["param." + name] = p.detach()
+        if p.grad is not None:
+            arrays["grad." + name] = p.grad
+    fixed = sum(4 * (a.numel() if torch.is_tensor(a) else a.size) for a in arrays.values())
+    if fixed > DUMP_MAX_BYTES:
+        sys.exit("--dump-outputs: the parameters and their gradients alone are %d bytes (limit %d)" % (fixed, DUMP_MAX_BYTES))
+    width = out.shape[1] + (H.shape[1] if H.grad is not None else 0)
+    k = int(min(n, DUMP_ROWS, max(0, (DUMP_MAX_BYTES - fixed) // (4 * width + 8))))
+    own = part.owned.cpu().numpy()
+    local = np.nonzero(np.isin(own, np.random.default_rng(0).choice(n, size=k, replace=False)))[0]
+    local = local[np.argsort(own[local], kind="stable")]
+    rows = torch.from_numpy(local).to(out.device)
+    arrays["vertex_ids"] = own[local].astype(np.float64)
+    arrays["output"] = out.detach()[rows]
+    if H.grad is not None:
+        arrays["input_grad"] = H.grad[rows]
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        a = a.float().cpu().numpy() if torch.is_tensor(a) else a
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 class GatKernelTimer:
     """HIP events around every launch of the dominant GAT kernel: the fused transposed product + edge gradient
     (pgcn_spmm_heads_grad_f32), or -- shapes it does not cover -- the stand-alone edge gradient."""
@@ -694,19 +739,23 @@ def bench_gat(args, rank, world, dev, backend, stage):
         loss.backward()
         G.sum_gradients(model)
         opt.step()
+        if args.dump_outputs:
+            last["out"] = logits
         return loss
 
-    timer = GatKernelTimer(K, dev)
+    last = {}
+    timer = GatKernelTimer(K, dev) if args.full else None
     for _ in range(args.warmup):
         loss = step()
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
-    timer.on = not args.no_kernel_timing
+    if timer is not None:
+        timer.on = not args.no_kernel_timing
     xprobe = None
     paced = bool(emul and args.pace_exchange > 0)
-    if (world > 1 or paced) and not args.no_kernel_timing and (paced or not emul):      # what the exchange costs, what of it is exposed (r06)
+    if (world > 1 or paced) and args.full and not args.no_kernel_timing and (paced or not emul):      # what the exchange costs, what of it is exposed (r06)
         xprobe = eng.probe = pkg("engine").ExchangeProbe(dev)
         xprobe.on = True
     t0 = time.perf_counter()
@@ -717,7 +766,8 @@ def bench_gat(args, rank, world, dev, backend, stage):
         dist.barrier()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
-    timer.on = False
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, part, n, loss, last["out"], H, model)
     exchange_report = None
     if xprobe is not None:
         xprobe.on = False
@@ -729,7 +779,10 @@ def bench_gat(args, rank, world, dev, backend, stage):
         elapsed = float(t)
     ms = 1e3 * elapsed / args.steps
     roofline = None
-    kname, avg, launches = timer.mean_ms()
+    kname, avg, launches = (None, None, 0)
+    if timer is not None:
+        timer.on = False
+        kname, avg, launches = timer.mean_ms()
     if avg:
         n_r, n_c = part.n_local, part.n_local + part.n_halo
         if kname == "spmm_heads_grad":
@@ -815,6 +868,11 @@ def main():
     ap.add_argument("--workload", default="reddit")
     ap.add_argument("--features", type=int, default=None)
     ap.add_argument("--layers", type=int, default=None)
+    ap.add_argument("--full", action="store_true",
+                    help="also what the headline does not need: roofline, halo groups, exchange probe, cpu_baseline, the N > 1 "
+                         "self-test and (--graph auto) the N > 1 graph replays")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last one computed to DIR/<name>.npy (float32, <= 64 MB; N > 1: rank 0)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-budget", type=float, default=12.0, help="seconds of host time per cpu_baseline leg")
     ap.add_argument("--no-kernel-timing", action="store_true")
@@ -830,11 +888,11 @@ def main():
     ap.add_argument("--mtx", default=None, help="a MatrixMarket adjacency file (like PGCN.py -a) instead of the synthetic graph")
     ap.add_argument("--real", action="store_true", help="label the --shards / --mtx input as real data in the JSON line")
     ap.add_argument("--no-selftest", action="store_true",
-                    help="N > 1: skip the small-graph check of the multi-rank path that runs before the timed region")
+                    help="N > 1 with --full: skip the small-graph check of the multi-rank path that runs before the timed region")
     ap.add_argument("--graph", nargs="?", const="on", default="auto", choices=("on", "off", "auto"),
                     help="after the timed (eager) region: capture ONE training step in a HIP graph -- the RCCL calls of an "
                          "N > 1 run included -- and time its replays (reported as `graph_replay`; all ranks or none).  auto "
-                         "(default): on for N > 1, where the host-side enqueue of ~150 launches per step is 13 %% of a rank's "
+                         "(default): on for N > 1 with --full, where the host-side enqueue of ~150 launches per step is 13 %% of a rank's "
                          "step (r04: 3.06 ms eager, 2.71 replayed on rank 0 of 8), off for N = 1 (device-bound: 10.66 vs 10.64 ms)")
     ap.add_argument("--emulate-rank", default=None, metavar="r/P",
                     help="one GPU runs rank r of a P-rank job with a no-op exchange (per-rank compute of 2/4/8 GPUs)")
@@ -842,6 +900,8 @@ def main():
                     help="with --emulate-rank: every exchange round occupies the comm stream as long as its largest peer segment takes at "
                          "this rate per link (153 = one xGMI link) -- prices the overlap, reported under `exchange`")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -906,7 +966,7 @@ def main():
         eng._slab("halo", eng.n_halo, f).uniform_()
         eng._slab("send", eng.n_send, f).uniform_()
     selftest = None
-    if world > 1 and not args.no_selftest:        # first contact: the multi-rank path on a small graph, before anything is timed
+    if world > 1 and args.full and not args.no_selftest:        # first contact: the multi-rank path on a small graph, before anything is timed
         selftest = multirank_selftest(rank, world, dev, K, exch)
         stage("multi-rank self-test passed")
     P._engine_current = eng           # gradient all-reduce rides the exchange's communicator and stream
@@ -935,9 +995,12 @@ def main():
         loss.backward()
         P.average_gradients(model)
         opt.step()
+        if args.dump_outputs:
+            last["out"] = logits
         return loss
 
-    timer = KernelTimer(K, dev)
+    last = {}
+    timer = KernelTimer(K, dev) if args.full else None
     for _ in range(args.warmup):
         loss = step()
         stage("warm-up step done")
@@ -945,12 +1008,13 @@ def main():
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
-    timer.on = not args.no_kernel_timing
+    if timer is not None:
+        timer.on = not args.no_kernel_timing
     # N > 1: what the boundary exchange costs and how much of it the compute stream sees (engine.ExchangeProbe: HIP events on the comm
     # stream around every round, on the compute stream around every wait for one, and around the fused gradient all-reduce)
     xprobe = None
     paced = bool(args.emulate_rank and part.size > 1 and args.pace_exchange > 0)
-    if (world > 1 or paced) and not args.no_kernel_timing and (paced or not (args.emulate_rank and part.size > 1)):
+    if (world > 1 or paced) and args.full and not args.no_kernel_timing and (paced or not (args.emulate_rank and part.size > 1)):
         xprobe = eng.probe = engine.ExchangeProbe(dev)
         xprobe.on = True
     t0 = time.perf_counter()
@@ -961,7 +1025,8 @@ def main():
         dist.barrier()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
-    timer.on = False
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, part, n, loss, last["out"], H, model)
     exchange_report = None
     if xprobe is not None:
         xprobe.on = False
@@ -980,7 +1045,10 @@ def main():
 
     # ---- roofline of the dominant kernel (local-block forward SpMM) -----------------
     roofline = None
-    avg_ms, launches = timer.summary(id(eng.A_loc), f)
+    avg_ms, launches = (None, 0)
+    if timer is not None:
+        timer.on = False
+        avg_ms, launches = timer.summary(id(eng.A_loc), f)
     if avg_ms:
         alg = eng.A_loc.alg_bytes(f)
         achieved = alg / (avg_ms * 1e-3)
@@ -1033,7 +1101,7 @@ def main():
             K.lib, K.single_lane = real_lib, real_lane
             eng.A_loc.launch_cache.clear()
     halo_groups = None
-    if part.size > 1:       # the halo launch groups of this rank (A_halo[r] . slab, one per exchange round)
+    if part.size > 1 and timer is not None:       # the halo launch groups of this rank (A_halo[r] . slab, one per exchange round)
         halo_groups = []
         for r, Ah in enumerate(eng.A_halo):
             havg, hl = timer.summary(id(Ah), f)
@@ -1097,7 +1165,7 @@ def main():
     if exchange_report is not None:
         out["exchange"] = exchange_report
     out["config"]["timed_region"] = "%d eagerly launched training steps" % args.steps
-    if args.graph == "on" or (args.graph == "auto" and world > 1 and dev.type == "cuda"):
+    if args.graph == "on" or (args.graph == "auto" and args.full and world > 1 and dev.type == "cuda"):
         # LAST thing that touches the device: the eager line above is complete.  A replay whose collectives never finish cannot be
         # recovered from, but it must not cost the eager line either: on a deadline every rank leaves, rank 0 with its line printed.
         def bail(what):
@@ -1119,7 +1187,7 @@ def main():
             # N > 1 a rank's step is ~150 launches of ~20 us and the host-side enqueue is 11-13 % of it, which the replay removes.
             gr["value"] = 2 * L * nnz_job / (gr["ms_per_step"] * 1e-3)
             gr["unit"] = out["unit"]
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not emul:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline and not emul:
         try:
             out["cpu_baseline"] = cpu_baseline(part, f, L, args.cpu_budget)
         except Exception as e:                     # the host-side comparison leg must never cost the GPU line

@@ -126,7 +126,8 @@ def test_real_file_is_picked_up_from_data_dir(tmp_path, monkeypatch):
 @pytest.mark.skipif(torch.cuda.is_available(), reason="flag parsing on a box without a GPU")
 def test_new_flags_parse_and_fail_loudly_without_gpu(tmp_path):
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--shards", str(tmp_path / "x"), "--emulate-rank", "0/8",
-                          "--mtx", str(tmp_path / "y.mtx"), "--real", "--steps", "1", "--warmup", "0"],
+                          "--mtx", str(tmp_path / "y.mtx"), "--real", "--steps", "1", "--warmup", "0",
+                          "--full", "--dump-outputs", str(tmp_path / "out")],
                          capture_output=True, text=True, timeout=600)
     assert out.returncode == 1 and "needs an MI355X" in out.stderr and "unrecognized" not in out.stderr
 

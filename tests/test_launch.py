@@ -55,7 +55,7 @@ def test_smoke_entry_point():
 @pytest.mark.gpu
 def test_bench_single_gpu_line_small_workload():
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--workload", "cora",
-                          "--steps", "3", "--warmup", "1", "--cpu-budget", "1"], env=_env(),
+                          "--steps", "3", "--warmup", "1", "--cpu-budget", "1", "--full"], env=_env(),
                          capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-3000:]
     rec = _json_line(out.stdout)
@@ -67,12 +67,43 @@ def test_bench_single_gpu_line_small_workload():
 
 
 @pytest.mark.gpu
+def test_bench_plain_line_and_dumped_outputs(tmp_path):
+    """Without --full the line carries the headline only; --dump-outputs writes what the last timed step computed (float32
+    .npy files, 64 MB at most, a fixed sample of the rows), and a second run with the same arguments computes the same."""
+    from conftest import rel_err
+    runs = []
+    for k in range(2):
+        d = tmp_path / ("out%d" % k)
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--workload", "mid",
+                              "--steps", "3", "--warmup", "1", "--dump-outputs", str(d)], env=_env(),
+                             capture_output=True, text=True, timeout=900)
+        assert out.returncode == 0, out.stderr[-3000:]
+        rec = _json_line(out.stdout)
+        assert rec["steps"] == 3 and rec["warmup"] == 1 and rec["ms_per_step"] > 0 and rec["value"] > 0
+        assert rec["roofline"] is None and rec["cpu_baseline"] is None and "graph_replay" not in rec
+        assert sum(p.stat().st_size for p in d.iterdir()) <= 64 << 20
+        got = {p.name[:-4]: np.load(p) for p in d.iterdir()}
+        assert all(a.dtype in (np.float32, np.float64) and np.isfinite(a).all() for a in got.values())
+        assert abs(float(got["loss"][0]) - rec["loss"]) <= 1e-6 * max(1.0, abs(rec["loss"]))
+        runs.append(got)
+    a, b = runs
+    n, f, L = rec["config"]["n"], rec["config"]["f"], rec["config"]["layers"]
+    ids = a["vertex_ids"].astype(np.int64)
+    assert len(ids) == 16384 and np.all(np.diff(ids) > 0) and 0 <= ids[0] and ids[-1] < n
+    assert a["output"].shape == a["input_grad"].shape == (len(ids), f)
+    assert len([k for k in a if k.startswith("param.")]) == len([k for k in a if k.startswith("grad.")]) == L
+    assert set(a) == set(b)
+    for k in a:
+        assert rel_err(b[k], a[k]) <= 1e-5, k
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("N", [2, 4])
 def test_bench_self_launch_n_ranks_share_the_gpu(N):
     """The exact command form the driver uses for N = 1, with N > 1 and nothing else: the ranks are started by
     bench.py itself (here they share the one GPU and talk over gloo; real kernels, comm-stream overlap on)."""
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(N), "--workload", "cora",
-                          "--steps", "3", "--warmup", "1"], env=_env(PGCN_BENCH_BACKEND="gloo"),
+                          "--steps", "3", "--warmup", "1", "--full"], env=_env(PGCN_BENCH_BACKEND="gloo"),
                          capture_output=True, text=True, timeout=1200)
     assert out.returncode == 0, out.stderr[-3000:]
     rec = _json_line(out.stdout)
@@ -193,7 +224,7 @@ def test_bench_with_reference_hypergraph_part_vector():
 @pytest.mark.gpu
 def test_bench_sbm_generator_line():
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--workload", "mid", "--generator", "sbm",
-                          "--steps", "2", "--warmup", "1", "--no-cpu-baseline"], env=_env(),
+                          "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--full"], env=_env(),
                          capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-3000:]
     rec = _json_line(out.stdout)
@@ -220,7 +251,7 @@ def test_bench_from_binary_shards_papers_shape_two_ranks(tmp_path):
     assert mk.returncode == 0, mk.stderr[-3000:]
     assert os.path.exists(prefix + ".0.pgcsr") and os.path.exists(prefix + ".1.pgcsr")
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--shards", prefix, "--partvec", pv,
-                          "--features", "64", "--layers", "2", "--steps", "2", "--warmup", "1"],
+                          "--features", "64", "--layers", "2", "--steps", "2", "--warmup", "1", "--full"],
                          env=_env(PGCN_BENCH_BACKEND="gloo"), capture_output=True, text=True, timeout=1800)
     assert out.returncode == 0, out.stderr[-3000:]
     rec = _json_line(out.stdout)
@@ -239,7 +270,7 @@ def test_bench_gat_two_ranks_share_the_gpu():
     """BASELINE config 5 is a multi-GPU GAT: `bench.py --workload reddit-gat --gpus 2` (ranks share the GPU over gloo,
     real attention kernels, Reddit-sized shards) prints the same kind of line as the GCN bench."""
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--workload", "reddit-gat",
-                          "--steps", "2", "--warmup", "1"], env=_env(PGCN_BENCH_BACKEND="gloo"),
+                          "--steps", "2", "--warmup", "1", "--full"], env=_env(PGCN_BENCH_BACKEND="gloo"),
                          capture_output=True, text=True, timeout=1800)
     assert out.returncode == 0, out.stderr[-3000:]
     rec = _json_line(out.stdout)
@@ -259,7 +290,7 @@ def test_bench_emulated_rank_line():
     """`--emulate-rank r/P`: one GPU runs the compute of rank r of a P-rank job (the shard shapes 2/4/8 GPUs run),
     with a roofline object for the local block and one per halo launch group."""
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "mid", "--emulate-rank", "1/4",
-                          "--steps", "3", "--warmup", "1"], env=_env(), capture_output=True, text=True, timeout=900)
+                          "--steps", "3", "--warmup", "1", "--full"], env=_env(), capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-3000:]
     rec = _json_line(out.stdout)
     assert rec["n_gpus"] == 1 and rec["config"]["emulated_rank"] == "1/4" and rec["cpu_baseline"] is None

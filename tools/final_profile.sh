@@ -52,27 +52,27 @@ python tools/make_pmc_traffic.py $out/pmc_summary_gat_r4.txt $out/pmc_traffic.js
 rm -rf $out/pmc_gat_r4
 cp $out/pmc_traffic.json profiles/pmc_traffic.json      # (bench.py reads it from there for the lines below)
 else python tools/make_shards.py --workload papers --ranks 8 --only-rank 0 --device cuda --out /tmp/papers > $out/papers_make_shards.txt 2>&1; fi
-python bench.py > $out/bench.json 2> $out/bench.err; tail -c 1200 $out/bench.json; echo
+python bench.py --full > $out/bench.json 2> $out/bench.err; tail -c 1200 $out/bench.json; echo
 rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof -o bench -- python bench.py --steps 10 --warmup 2 --no-cpu-baseline > $out/prof_stdout.log 2> $out/prof_stderr.log
 rm -f $out/prof/*kernel_trace.csv $out/prof/*/*kernel_trace.csv
-python bench.py --workload products --steps 5 --warmup 2 --no-cpu-baseline > $out/bench_products.json 2>/dev/null
-python bench.py --generator sbm --steps 10 --warmup 2 --no-cpu-baseline > $out/bench_sbm.json 2>/dev/null
-python bench.py --workload mid --steps 10 --warmup 2 > $out/bench_mid.json 2>/dev/null
-python bench.py --workload reddit-gat --steps 5 --warmup 2 > $out/bench_gat.json 2>/dev/null
-PGCN_TUNING=gat_blocks=0 python bench.py --workload reddit-gat --steps 5 --warmup 2 --no-cpu-baseline > $out/bench_gat_noblocks.json 2>/dev/null   # (the same line with every entry in the gather kernels)
+python bench.py --full --workload products --steps 5 --warmup 2 --no-cpu-baseline > $out/bench_products.json 2>/dev/null
+python bench.py --full --generator sbm --steps 10 --warmup 2 --no-cpu-baseline > $out/bench_sbm.json 2>/dev/null
+python bench.py --full --workload mid --steps 10 --warmup 2 > $out/bench_mid.json 2>/dev/null
+python bench.py --full --workload reddit-gat --steps 5 --warmup 2 > $out/bench_gat.json 2>/dev/null
+PGCN_TUNING=gat_blocks=0 python bench.py --full --workload reddit-gat --steps 5 --warmup 2 --no-cpu-baseline > $out/bench_gat_noblocks.json 2>/dev/null   # (the same line with every entry in the gather kernels)
 rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof_gat -o gat -- python bench.py --workload reddit-gat --steps 4 --warmup 1 --no-cpu-baseline --no-kernel-timing > $out/prof_gat_stdout.log 2> $out/prof_gat_stderr.log
 rm -f $out/prof_gat/*kernel_trace.csv $out/prof_gat/*/*kernel_trace.csv
-python bench.py --workload papers --emulate-rank 0/8 --shards /tmp/papers --partvec block --features 64 --layers 2 --steps 5 --warmup 2 --no-cpu-baseline > $out/bench_papers_full_rank_0_8.json 2>/dev/null
+python bench.py --full --workload papers --emulate-rank 0/8 --shards /tmp/papers --partvec block --features 64 --layers 2 --steps 5 --warmup 2 --no-cpu-baseline > $out/bench_papers_full_rank_0_8.json 2>/dev/null
 python tools/shard_rank_check.py --shards /tmp/papers --rank 0 --ranks 8 --features 64 > $out/papers_full_rank_0_8_check.json 2>/dev/null
 for rp in 0/8 3/8 7/8 0/4 0/2; do t=$(echo $rp | tr '/' '_')
-  python bench.py --emulate-rank $rp --graph --steps 10 --warmup 2 --no-cpu-baseline > $out/bench_rank_$t.json 2>/dev/null
+  python bench.py --full --emulate-rank $rp --graph --steps 10 --warmup 2 --no-cpu-baseline > $out/bench_rank_$t.json 2>/dev/null
 done
-python bench.py --workload reddit-gat --emulate-rank 0/4 --steps 5 --warmup 2 > $out/bench_gat_rank_0_4.json 2>/dev/null
-python bench.py --workload reddit-gat --emulate-rank 0/4 --pace-exchange 153 --steps 5 --warmup 2 --no-cpu-baseline > $out/bench_gat_rank_0_4_paced.json 2>/dev/null   # (exchange priced at the xGMI link rate)
+python bench.py --full --workload reddit-gat --emulate-rank 0/4 --steps 5 --warmup 2 > $out/bench_gat_rank_0_4.json 2>/dev/null
+python bench.py --full --workload reddit-gat --emulate-rank 0/4 --pace-exchange 153 --steps 5 --warmup 2 --no-cpu-baseline > $out/bench_gat_rank_0_4_paced.json 2>/dev/null   # (exchange priced at the xGMI link rate)
 if [ -f "$HP" ]; then
   for r in 0 3; do
-    python bench.py --workload $W3 --generator sbm --partvec $HP --emulate-rank $r/8 --steps 5 --warmup 2 --no-cpu-baseline > $out/bench_${W3}_sbm_hp_rank_${r}_8.json 2>/dev/null
-    python bench.py --workload $W3 --generator sbm --emulate-rank $r/8 --steps 5 --warmup 2 --no-cpu-baseline > $out/bench_${W3}_sbm_rp_rank_${r}_8.json 2>/dev/null
+    python bench.py --full --workload $W3 --generator sbm --partvec $HP --emulate-rank $r/8 --steps 5 --warmup 2 --no-cpu-baseline > $out/bench_${W3}_sbm_hp_rank_${r}_8.json 2>/dev/null
+    python bench.py --full --workload $W3 --generator sbm --emulate-rank $r/8 --steps 5 --warmup 2 --no-cpu-baseline > $out/bench_${W3}_sbm_rp_rank_${r}_8.json 2>/dev/null
   done
 fi
 for f in $out/bench*.json; do python - <<PY
