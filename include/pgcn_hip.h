@@ -239,6 +239,20 @@ int pgcn_spmm_dense_bf16x3_f32(const int32_t *work, int64_t nwork, const int32_t
                                int32_t f, void *image_ws, int64_t image_ws_bytes, float *partial_ws,
                                int64_t partial_ws_elems, int64_t nslots_total, pgcn_stream_t stream);
 
+/* The same blocks without values (pattern / degree-normalised adjacencies): block b's entries are r_i P_ij c_j with P its 0/1 pattern.
+ * bits: [nblocks][8 waves][64 lanes][4 words], 16-byte aligned -- byte u = 2 ks + rb of a lane's 16 bytes, bit 4 h + e: position
+ *   (row 64 w + 32 rb + lane % 32, column 16 ks + 8 (lane / 32) + 4 h + e) of the block (the layout of pgcn_gat_blocks_forward_f32).
+ * piece_row0[nwork]: first matrix row of every piece's 512-row partial block.  row_scale (NULL = all ones): r of the matrix rows,
+ *   readable at rows piece_row0 + 0 .. 511 of every piece (the caller pads it past the last row).  col_scale (NULL = all ones): c of the
+ *   rows of B, ncols entries.  work / blk_img / panel_list / image_ws / partial_ws / nslots_total: as pgcn_spmm_dense_bf16x3_f32, and
+ *   the same result bit for bit on an all-ones block with NULL scales.  A panel holding Inf / NaN takes an exact path that adds
+ *   c_j B_j only where the bit is set, then scales by r_i.                                                                        */
+int pgcn_spmm_dense_pat_bf16x3_f32(const int32_t *work, int64_t nwork, const int32_t *blk_img, const int32_t *bits,
+                                   const int32_t *piece_row0, const float *row_scale, const float *col_scale,
+                                   const int32_t *panel_list, int64_t npanels, const float *B, int64_t ldb, int64_t ncols, int32_t f,
+                                   void *image_ws, int64_t image_ws_bytes, float *partial_ws, int64_t partial_ws_elems,
+                                   int64_t nslots_total, pgcn_stream_t stream);
+
 /* C[row] (+)= sum of the partial-sum slots listed for the row, in list order.
  * fix: 4 x int32 per row {row, begin, count, 0}; slot_ids (optional): the row's slots are
  * slot_ids[begin .. begin+count), or begin .. begin+count when slot_ids is NULL.        */

@@ -71,8 +71,11 @@ __device__ __forceinline__ void static_for(F &&f) {
 // (8 bf16: k = 32 q + 8 kg + j), i.e. a lane's B operand of v_mfma_f32_32x32x16_bf16 is one 16-byte slot and the 32 lanes of a half
 // wave read 512 contiguous bytes.  grid (panels in the list, feature blocks of 128); thread t: column n = t & 127, k groups
 // 8 (t >> 7) .. + 8.  panel_list holds the FIRST ROW of every panel (any row: a grid aligned to the vertex order's bands).
-static __global__ __launch_bounds__(kSplitThreads) void spmm_split_panels_kernel(const int32_t *__restrict__ panel_list, const float *__restrict__ B,
-                                                                            int64_t ldb, int64_t ncols, int32_t f, u32x4 *__restrict__ image) {
+// SCALE (pgcn_spmm_dense_pat_bf16x3_f32): row r of B is multiplied by col_scale[r] before the split (the column scale of a factored
+// block, A = diag(r) P diag(c)); the plain kernel below is the SCALE = false body.
+template <bool SCALE>
+__device__ __forceinline__ void split_panels_body(const int32_t *__restrict__ panel_list, const float *__restrict__ B, int64_t ldb,
+                                                  int64_t ncols, int32_t f, const float *__restrict__ col_scale, u32x4 *__restrict__ image) {
     const int64_t r0 = (int64_t)panel_list[blockIdx.x];
     const int fcol0 = blockIdx.y * kT;
     const int n = threadIdx.x & (kT - 1);
@@ -88,6 +91,7 @@ static __global__ __launch_bounds__(kSplitThreads) void spmm_split_panels_kernel
         for (int j = 0; j < 8; ++j) {
             const int64_t r = r0 + 8 * kga + j;
             x[j] = (n_ok && r < ncols) ? col[r * ldb] : 0.f;
+            if constexpr (SCALE) x[j] = r < ncols ? __fmul_rn(x[j], col_scale[r]) : 0.f;
         }
         u32x4 p1, p2, p3;
 #pragma unroll
@@ -102,6 +106,16 @@ static __global__ __launch_bounds__(kSplitThreads) void spmm_split_panels_kernel
         dst[4 * kT] = p2;
         dst[8 * kT] = p3;
     }
+}
+static __global__ __launch_bounds__(kSplitThreads) void spmm_split_panels_kernel(const int32_t *__restrict__ panel_list, const float *__restrict__ B,
+                                                                            int64_t ldb, int64_t ncols, int32_t f, u32x4 *__restrict__ image) {
+    split_panels_body<false>(panel_list, B, ldb, ncols, f, nullptr, image);
+}
+static __global__ __launch_bounds__(kSplitThreads) void spmm_split_panels_scaled_kernel(const int32_t *__restrict__ panel_list,
+                                                                                   const float *__restrict__ B, int64_t ldb, int64_t ncols,
+                                                                                   int32_t f, const float *__restrict__ col_scale,
+                                                                                   u32x4 *__restrict__ image) {
+    split_panels_body<true>(panel_list, B, ldb, ncols, f, col_scale, image);
 }
 
 }  // namespace pgcn_bf16x3

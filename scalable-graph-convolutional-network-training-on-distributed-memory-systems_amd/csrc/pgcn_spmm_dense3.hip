@@ -349,6 +349,204 @@ __global__ __launch_bounds__(kThreads, 2) void spmm_dense3_kernel(
         }
 }
 
+
+// ---- value-free blocks (pgcn_spmm_dense_pat_bf16x3_f32) --------------------------------------------------------------------------
+// A block of a PATTERN structure (every value 1) or of a FACTORED one (a_ij = r_i c_j: D_r^-1/2 P D_c^-1/2) is its pattern P, one bit
+// per position (16 bytes per lane and block instead of the 2 KB x 16 units of vals3).  The bits become bf16 1.0 / 0.0 operands in
+// registers -- a1 = P, a2 = a3 = 0 -- so three of the six products are exact zeros and go: a1 h3, a1 h2, a1 h1 remain, on the same
+// accumulator chain and in the order of mma_step (an all-ones block gives the six-product kernel's sums bit for bit).  c_j scales
+// panel row j before the split (spmm_split_panels_scaled_kernel), r_i the accumulator before the slot write.  No A ring: the LDS holds
+// the two quarter images of B only.
+constexpr size_t kSmemPat = 2 * (size_t)kQBytes;
+
+// pair D (0..3) of unit U of a pattern word (byte U, bits 2 D and 2 D + 1) as two packed bf16 numbers 1.0 / 0.0 (bf16(1) = 0x3f80)
+template <int U, int D>
+__device__ __forceinline__ uint32_t expand_pair(uint32_t word) {
+    const uint32_t x = __builtin_amdgcn_ubfe(word, 8 * U + 2 * D, 2);
+    return ((x | (x << 15)) & 0x10001u) * 0x3f80u;
+}
+
+// the three MFMAs of one (k step, row block, column block): the a1 terms of mma_step, smallest first
+template <int NBLK, int RB, int NB>
+__device__ __forceinline__ void mma_step_pat(f32x16 (&acc)[2][NBLK], const u32x4 &a, const u32x4 (&bb)[3]) {
+    acc[RB][NB] = mma(a, bb[2], acc[RB][NB]);
+    acc[RB][NB] = mma(a, bb[1], acc[RB][NB]);
+    acc[RB][NB] = mma(a, bb[0], acc[RB][NB]);
+}
+
+// One quarter (32 k) of one block: four units u = 2 s + rb of NBLK steps of three MFMAs.  wq / wn: this lane's pattern word of this
+// quarter / of the next one (byte u = unit u).  The operand of unit u + 1 is expanded under the steps of unit u, one pair per step,
+// between the chains; the B operands of step t + 1 are in flight under the MFMAs of step t.
+template <int NBLK>
+__device__ __forceinline__ void compute_quarter_pat(f32x16 (&acc)[2][NBLK], u32x4 (&ap)[2], uint32_t base, uint32_t wq, uint32_t wn) {
+    constexpr int NT = 4 * NBLK;
+    u32x4 b[2][3];
+    read_step<NBLK, 0>(b[0], base);
+    static_for<0, NT>([&](auto tc) {
+        constexpr int t = decltype(tc)::value;
+        constexpr int u = t / NBLK, nb = t % NBLK, rb = u % 2;
+        if constexpr (t + 1 < NT) {
+            constexpr int u1 = (t + 1) / NBLK, nb1 = (t + 1) % NBLK;
+            read_step<NBLK, (u1 / 2) * NBLK + nb1>(b[(t + 1) & 1], base);
+            lds_wait<3>(b[t & 1]);
+        } else {
+            lds_wait<0>(b[t & 1]);
+        }
+        static_for<nb, (nb == NBLK - 1 ? 4 : nb + 1)>([&](auto dc) {
+            constexpr int D = decltype(dc)::value;
+            ap[(u + 1) & 1][D] = u < 3 ? expand_pair<(u + 1) & 3, D>(wq) : expand_pair<0, D>(wn);
+        });
+        __builtin_amdgcn_sched_barrier(0);
+        mma_step_pat<NBLK, rb, nb>(acc, ap[u & 1], b[t & 1]);
+        __builtin_amdgcn_sched_barrier(0);
+    });
+}
+
+__device__ __forceinline__ uint32_t word_of(const u32x4 &v, int i) { return i == 0 ? v.x : i == 1 ? v.y : i == 2 ? v.z : v.w; }
+
+template <int NBLK>
+__device__ __forceinline__ void dense_pat_piece(const int4 wk, const int32_t *__restrict__ blk_img, const u32x4 *__restrict__ bits,
+                                                const char *__restrict__ image, int nfb, int fb, char *smem, f32x16 (&acc)[2][NBLK]) {
+    const int lane = threadIdx.x & 63;
+    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int hi = lane >> 5, lo = lane & 31;
+    const uint32_t lds0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) char *)smem;
+    const uint32_t rbase = lds0 + hi * 2048 + lo * 16;
+    const int nq = wk.z * 4;
+    auto img_of = [&](int qi) -> const char * {          // quarter qi of the piece (clamped, as in dense3_piece)
+        qi = qi < nq ? qi : nq - 1;
+        const int64_t pi = blk_img[(int64_t)wk.y + (qi >> 2)];
+        return image + (pi * nfb + fb) * (int64_t)kImgBytes + (qi & 3) * kQBytes;
+    };
+    auto bits_of = [&](int bi) -> u32x4 {                // this lane's 16 pattern bytes of block bi of the piece (clamped)
+        bi = bi < wk.z ? bi : wk.z - 1;
+        return bits[(((int64_t)wk.y + bi) * 8 + w) * 64 + lane];
+    };
+    // in flight at the top of quarter q: B(q) (3 copies) and the pattern of the block after the current one (bn); the counted wait
+    // takes bn as an operand, so that the compiler adds no wait of its own for it
+    u32x4 bn = bits_of(0), bc;
+    issue_quarter(img_of(0), smem, 0, w);
+    asm volatile("s_waitcnt vmcnt(0)" : "+v"(bn)::"memory");
+    u32x4 ap[2];
+    static_for<0, 4>([&](auto dc) { ap[0][decltype(dc)::value] = expand_pair<0, decltype(dc)::value>(bn.x); });
+    for (int q = 0; q < nq; ++q) {
+        asm volatile("s_waitcnt vmcnt(0)" : "+v"(bn)::"memory");   // B(q) and the next block's pattern have landed
+        __syncthreads();                                            // ... everybody's; nobody reads the other buffer any more
+        const int qq = q & 3;
+        const uint32_t wb = bn.x;                                   // (read before the reload: after it the compiler would wait for it)
+        if (qq == 0) {
+            bc = bn;
+            bn = bits_of((q >> 2) + 1);
+        }
+        const uint32_t wq = word_of(bc, qq), wn = qq == 3 ? wb : word_of(bc, qq + 1);
+        issue_quarter(img_of(q + 1), smem, (q + 1) & 1, w);
+        compute_quarter_pat<NBLK>(acc, ap, rbase + (q & 1) * kQBytes, wq, wn);
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");              // (the redundant last fetches must not outlive the workgroup's LDS)
+}
+
+// Exact redo of a piece: c_j h_j added only where the bit is set, k ascending, operands from global memory (the row scale is applied
+// by the caller, as on the fast path).
+template <int NBLK>
+__device__ __noinline__ void dense_pat_piece_exact(const int4 wk, const int32_t *__restrict__ blk_img,
+                                                   const int32_t *__restrict__ panel_list, const uint32_t *__restrict__ bits,
+                                                   const float *__restrict__ col_scale, const float *__restrict__ B, int64_t ldb,
+                                                   int64_t ncols, int fcol0, int fw, f32x16 (&acc)[2][NBLK]) {
+    const int lane = threadIdx.x & 63;
+    const int w = threadIdx.x >> 6;
+    const int hi = lane >> 5, lo = lane & 31;
+    for (int t = 0; t < wk.z; ++t) {
+        const int64_t bi = (int64_t)wk.y + t;
+        const int64_t prow0 = (int64_t)panel_list[blk_img[bi]];
+        for (int k = 0; k < kT; ++k) {
+            const int ks = k >> 4, hk = (k >> 3) & 1, bit = k & 7;
+            float b[NBLK];
+            const bool k_ok = prow0 + k < ncols;
+            const float cs = (col_scale && k_ok) ? col_scale[prow0 + k] : 1.f;
+#pragma unroll
+            for (int nb = 0; nb < NBLK; ++nb) {
+                const int colj = nb * 32 + lo;
+                const float x = (k_ok && colj < fw) ? B[(prow0 + k) * ldb + fcol0 + colj] : 0.f;
+                b[nb] = col_scale ? __fmul_rn(x, cs) : x;
+            }
+#pragma unroll
+            for (int rb = 0; rb < 2; ++rb) {
+                const int u = 2 * ks + rb;
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int il = (r & 3) + 8 * (r >> 2) + 4 * hi;
+                    const uint32_t wd = bits[((bi * 8 + w) * 64 + hk * 32 + il) * 4 + (u >> 2)];
+                    const bool set = (wd >> (8 * (u & 3) + bit)) & 1u;
+#pragma unroll
+                    for (int nb = 0; nb < NBLK; ++nb) acc[rb][nb][r] = set ? __fadd_rn(acc[rb][nb][r], b[nb]) : acc[rb][nb][r];
+                }
+            }
+        }
+    }
+}
+
+// work: int4 {block row, first block, number of blocks, first slot}; piece_row0[piece]: first matrix row of the piece's partial block
+template <int NBLK>
+__global__ __launch_bounds__(kThreads, 2) void spmm_dense_pat_kernel(
+    const int4 *__restrict__ work, const int32_t *__restrict__ blk_img, const int32_t *__restrict__ piece_row0,
+    const uint32_t *__restrict__ bits, const float *__restrict__ row_scale, const float *__restrict__ col_scale,
+    const int32_t *__restrict__ panel_list, const char *__restrict__ image, const float *__restrict__ B, int64_t ldb, int64_t ncols,
+    int32_t f, float *__restrict__ partial) {
+    extern __shared__ __attribute__((aligned(16))) char smem_pat[];
+    int4 wk = work[blockIdx.x];
+    wk.y = __builtin_amdgcn_readfirstlane(wk.y); wk.z = __builtin_amdgcn_readfirstlane(wk.z);
+    const int fb = blockIdx.y, nfb = gridDim.y;
+    const int fcol0 = fb * kT;
+    const int fw = min(kT, f - fcol0);
+    const int lane = threadIdx.x & 63;
+    const int w = threadIdx.x >> 6;
+    const int hi = lane >> 5, lo = lane & 31;
+    f32x16 acc[2][NBLK];
+#pragma unroll
+    for (int rb = 0; rb < 2; ++rb)
+#pragma unroll
+        for (int nb = 0; nb < NBLK; ++nb)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[rb][nb][r] = 0.f;
+    dense_pat_piece<NBLK>(wk, blk_img, reinterpret_cast<const u32x4 *>(bits), image, nfb, fb, smem_pat, acc);
+    bool bad = false;
+#pragma unroll
+    for (int rb = 0; rb < 2; ++rb)
+#pragma unroll
+        for (int nb = 0; nb < NBLK; ++nb)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) bad = bad || !(fabsf(acc[rb][nb][r]) <= 3.402823466e+38f);
+    if (__syncthreads_or(bad)) {
+        f32x16 exact[2][NBLK];   // (its own array: the address of `acc` must not escape)
+#pragma unroll
+        for (int rb = 0; rb < 2; ++rb)
+#pragma unroll
+            for (int nb = 0; nb < NBLK; ++nb)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) exact[rb][nb][r] = 0.f;
+        dense_pat_piece_exact<NBLK>(wk, blk_img, panel_list, bits, col_scale, B, ldb, ncols, fcol0, fw, exact);
+#pragma unroll
+        for (int rb = 0; rb < 2; ++rb)
+#pragma unroll
+            for (int nb = 0; nb < NBLK; ++nb) acc[rb][nb] = exact[rb][nb];
+    }
+    const int64_t row0 = (int64_t)piece_row0[blockIdx.x] + 64 * w;
+#pragma unroll
+    for (int rb = 0; rb < 2; ++rb)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int il = (r & 3) + 8 * (r >> 2) + 4 * hi;
+            const float rs = row_scale ? row_scale[row0 + 32 * rb + il] : 1.f;   // (the caller pads row_scale to the last partial block)
+#pragma unroll
+            for (int nb = 0; nb < NBLK; ++nb) {
+                const int colj = nb * 32 + lo;
+                if (colj < fw)
+                    partial[((int64_t)wk.w + 64 * w + 32 * rb + il) * f + fcol0 + colj] = row_scale ? __fmul_rn(acc[rb][nb][r], rs)
+                                                                                                      : acc[rb][nb][r];
+            }
+        }
+}
+
 }  // namespace
 
 extern "C" int64_t pgcn_dense_bf16x3_image_bytes(int64_t npanels, int32_t f) {
@@ -395,6 +593,50 @@ extern "C" int pgcn_spmm_dense_bf16x3_f32(const int32_t *work, int64_t nwork, co
         case 2: hipLaunchKernelGGL(spmm_dense3_kernel<2>, grid, block, kSmem3, s, w4, blk_img, panel_list, vals3, img, B, ldb, ncols, f, partial_ws); break;
         case 3: hipLaunchKernelGGL(spmm_dense3_kernel<3>, grid, block, kSmem3, s, w4, blk_img, panel_list, vals3, img, B, ldb, ncols, f, partial_ws); break;
         default: hipLaunchKernelGGL(spmm_dense3_kernel<4>, grid, block, kSmem3, s, w4, blk_img, panel_list, vals3, img, B, ldb, ncols, f, partial_ws); break;
+    }
+    PGCN_HIP_CHECK(hipGetLastError());
+    return PGCN_OK;
+}
+
+// Value-free blocks (pattern / factored): the block structure and work-space of pgcn_spmm_dense_bf16x3_f32, bits instead of vals3.
+// GPU/PGCN.py:171 reads a pattern matrix (mmread: all values 1); the normalised adjacency the products of GPU/PGCN.py:127 (forward,
+// torch.sparse.mm(A, H)) and :132 (backward, A.t()) run on is D^-1/2 P D^-1/2 -- a pattern scaled by a row and a column vector.
+extern "C" int pgcn_spmm_dense_pat_bf16x3_f32(const int32_t *work, int64_t nwork, const int32_t *blk_img, const int32_t *bits,
+                                              const int32_t *piece_row0, const float *row_scale, const float *col_scale,
+                                              const int32_t *panel_list, int64_t npanels, const float *B, int64_t ldb, int64_t ncols,
+                                              int32_t f, void *image_ws, int64_t image_ws_bytes, float *partial_ws,
+                                              int64_t partial_ws_elems, int64_t nslots_total, pgcn_stream_t stream) {
+    if (nwork < 0 || npanels < 0 || f <= 0 || ldb < f || ncols < 0)
+        return pgcn_set_error(PGCN_EINVAL, "pgcn_spmm_dense_pat_bf16x3_f32: bad sizes");
+    if (nwork == 0) return PGCN_OK;
+    if (!work || !blk_img || !bits || !piece_row0 || !panel_list || !B || !image_ws || !partial_ws || npanels == 0)
+        return pgcn_set_error(PGCN_EINVAL, "pgcn_spmm_dense_pat_bf16x3_f32: null pointer");
+    if ((uintptr_t)bits % 16 || (uintptr_t)image_ws % 16 || (uintptr_t)work % 16)
+        return pgcn_set_error(PGCN_EINVAL, "pgcn_spmm_dense_pat_bf16x3_f32: work / bits / image_ws must be 16-byte aligned");
+    if (image_ws_bytes < pgcn_dense_bf16x3_image_bytes(npanels, f))
+        return pgcn_set_error(PGCN_ENOMEM, "pgcn_spmm_dense_pat_bf16x3_f32: panel image work-space too small");
+    if (partial_ws_elems < nslots_total * (int64_t)f)
+        return pgcn_set_error(PGCN_ENOMEM, "pgcn_spmm_dense_pat_bf16x3_f32: partial work-space too small");
+    if (nwork > 0x7fffffffLL || npanels > 0x7fffffffLL)
+        return pgcn_set_error(PGCN_EINVAL, "pgcn_spmm_dense_pat_bf16x3_f32: work / panel list too long");
+    hipStream_t s = (hipStream_t)stream;
+    const unsigned nfb = (unsigned)((f + kT - 1) / kT);
+    if (col_scale)
+        hipLaunchKernelGGL(spmm_split_panels_scaled_kernel, dim3((unsigned)npanels, nfb), dim3(kSplitThreads), 0, s, panel_list, B, ldb, ncols,
+                           f, col_scale, reinterpret_cast<u32x4 *>(image_ws));
+    else
+        hipLaunchKernelGGL(spmm_split_panels_kernel, dim3((unsigned)npanels, nfb), dim3(kSplitThreads), 0, s, panel_list, B, ldb, ncols, f,
+                           reinterpret_cast<u32x4 *>(image_ws));
+    PGCN_HIP_CHECK(hipGetLastError());
+    const int4 *w4 = reinterpret_cast<const int4 *>(work);
+    const char *img = reinterpret_cast<const char *>(image_ws);
+    const uint32_t *bt = reinterpret_cast<const uint32_t *>(bits);
+    const dim3 grid((unsigned)nwork, nfb), block(kThreads);
+    switch (((f < kT ? f : kT) + 31) / 32) {
+        case 1: hipLaunchKernelGGL(spmm_dense_pat_kernel<1>, grid, block, kSmemPat, s, w4, blk_img, piece_row0, bt, row_scale, col_scale, panel_list, img, B, ldb, ncols, f, partial_ws); break;
+        case 2: hipLaunchKernelGGL(spmm_dense_pat_kernel<2>, grid, block, kSmemPat, s, w4, blk_img, piece_row0, bt, row_scale, col_scale, panel_list, img, B, ldb, ncols, f, partial_ws); break;
+        case 3: hipLaunchKernelGGL(spmm_dense_pat_kernel<3>, grid, block, kSmemPat, s, w4, blk_img, piece_row0, bt, row_scale, col_scale, panel_list, img, B, ldb, ncols, f, partial_ws); break;
+        default: hipLaunchKernelGGL(spmm_dense_pat_kernel<4>, grid, block, kSmemPat, s, w4, blk_img, piece_row0, bt, row_scale, col_scale, panel_list, img, B, ldb, ncols, f, partial_ws); break;
     }
     PGCN_HIP_CHECK(hipGetLastError());
     return PGCN_OK;

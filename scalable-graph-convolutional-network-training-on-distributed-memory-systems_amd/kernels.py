@@ -77,11 +77,15 @@ class DeviceCSR:
 class DeviceDense3:
     work: torch.Tensor
     blk_img: torch.Tensor
-    vals3: torch.Tensor
+    vals3: Optional[torch.Tensor]               # None: value-free blocks (bits, pgcn_spmm_dense_pat_bf16x3_f32)
     panel_list: torch.Tensor
     npieces: int
     npanels: int
     nnz: int
+    bits: Optional[torch.Tensor] = None         # int32 [nblocks, 8, 64, 4] pattern of value-free blocks
+    piece_row0: Optional[torch.Tensor] = None   # int32 [npieces] first row of every piece (value-free blocks)
+    row_scale: Optional[torch.Tensor] = None    # fp32, padded to the last piece's 512 rows (factored blocks)
+    col_scale: Optional[torch.Tensor] = None    # fp32 [ncols]
     image: Optional[torch.Tensor] = None      # uint8 work-space of the split panels (grown on demand, per width)
     retired: list = field(default_factory=list)   # outgrown images: a HIP graph captured earlier still launches into them
 
@@ -238,7 +242,7 @@ class HipKernels:
     def _attach_core(self, d: DeviceCSR, csr: HostCSR, fix_rem: Optional[np.ndarray]) -> None:
         """Upload the tiled parts (LDS core, MFMA tiles) and build the per-row slot lists: a row's
         partial sums are its core pieces (in work order), its dense pieces, then its gather-kernel slots."""
-        from .partition import CORE_TR, STRIP_TR
+        from .partition import CORE_TR, DENSE3_BR, STRIP_TR
         dev = self.device
         hc, hs, h3 = csr.core, csr.strip, csr.dense3
         ns_rem = d.nslots
@@ -264,8 +268,19 @@ class HipKernels:
         if h3 is not None:
             work = h3.work.clone()
             work[:, 3] += ns_rem + ns_strip + ns_core              # ... and the bf16 blocks last
-            d.dense3 = DeviceDense3(work.to(dev).contiguous(), h3.blk_img.to(dev).contiguous(), h3.vals3.to(dev).contiguous(),
+            d.dense3 = DeviceDense3(work.to(dev).contiguous(), h3.blk_img.to(dev).contiguous(),
+                                    None if h3.vals3 is None else h3.vals3.to(dev).contiguous(),
                                     h3.panel_list.to(dev).contiguous(), h3.npieces, int(h3.panel_list.numel()), h3.nnz)
+            if h3.bits is not None:             # value-free blocks: the pattern, the pieces' first rows and the scales
+                d3 = d.dense3
+                d3.bits = h3.bits.to(dev, torch.int32).contiguous()
+                d3.piece_row0 = h3.piece_row0.to(dev, torch.int32).contiguous()
+                if h3.row_scale is not None:    # (the kernel reads all 512 rows of a piece's partial block: padded with zeros)
+                    rs = torch.zeros(max(h3.nrows, int(h3.piece_row0.max()) + DENSE3_BR), dtype=torch.float32, device=dev)
+                    rs[:h3.nrows] = h3.row_scale.to(dev, torch.float32)
+                    d3.row_scale = rs
+                if h3.col_scale is not None:
+                    d3.col_scale = h3.col_scale.to(dev, torch.float32).contiguous()
             w64 = work.cpu().to(torch.int64)
             # (a block may start at any row and its band may end inside it: the piece's own first row and row count)
             pieces.append(torch.stack([h3.piece_row0.cpu().to(torch.int64), h3.piece_rows.cpu().to(torch.int64), w64[:, 3]], 1))
@@ -380,8 +395,9 @@ class HipKernels:
                     d3.retired.append(d3.image)   # (scratch of one launch group: a stale binding stays correct, it only must not dangle)
                 d3.image = torch.empty(need3, dtype=torch.uint8, device=self.device)
                 A.launch_cache.clear()          # other bindings hold the old work-space pointer
-            w3, n3, bi3, v3, pl3, np3, img3, imgb3 = (d3.work.data_ptr(), d3.npieces, d3.blk_img.data_ptr(), d3.vals3.data_ptr(),
+            w3, n3, bi3, v3, pl3, np3, img3, imgb3 = (d3.work.data_ptr(), d3.npieces, d3.blk_img.data_ptr(), _ptr(d3.vals3),
                                                       d3.panel_list.data_ptr(), d3.npanels, d3.image.data_ptr(), d3.image.numel())
+            pat3, pr3, rs3, cs3 = _ptr(d3.bits), _ptr(d3.piece_row0), _ptr(d3.row_scale), _ptr(d3.col_scale)
         if st is not None:
             sw, sn, srec, spairs = st.work.data_ptr(), st.npieces, st.rec.data_ptr(), st.pairs.data_ptr()
         if co is not None:
@@ -415,6 +431,9 @@ class HipKernels:
                                                  c, ldc, f, ws, ws_n, nslots, gflags, s), "pgcn_spmm_csr_plan_f32")
             elif name == "strip":
                 check(lib.pgcn_spmm_strip_f32(sw, sn, srec, spairs, b, ldb, ncols, f, ws, ws_n, nst, s), "pgcn_spmm_strip_f32")
+            elif pat3 is not None:
+                check(lib.pgcn_spmm_dense_pat_bf16x3_f32(w3, n3, bi3, pat3, pr3, rs3, cs3, pl3, np3, b, ldb, ncols, f, img3, imgb3, ws,
+                                                         ws_n, nst, s), "pgcn_spmm_dense_pat_bf16x3_f32")
             else:
                 check(lib.pgcn_spmm_dense_bf16x3_f32(w3, n3, bi3, v3, pl3, np3, b, ldb, ncols, f, img3, imgb3, ws, ws_n, nst, s),
                       "pgcn_spmm_dense_bf16x3_f32")
@@ -630,6 +649,8 @@ class HipKernels:
     def gat_block_bits(h3) -> torch.Tensor:
         """The pattern of ``HostDense3`` blocks as bits: [nblocks, 8 waves, 64 lanes, 4 words] int32 -- byte u = 2 ks + rb of a lane's
         16 bytes, bit 4 h + e, the A-operand order of ``partition.dense3_index`` (include/pgcn_hip.h, pgcn_gat_blocks_forward_f32)."""
+        if h3.vals3 is None:                                                            # value-free blocks carry their bits
+            return h3.bits
         nb = h3.vals3.shape[0]
         nz = (h3.vals3 != 0).view(nb, 8, 16, 2, 64, 4)                                  # [block][w][unit][h][lane][e]
         wgt = (1 << (4 * torch.arange(2, device=nz.device).view(2, 1, 1) + torch.arange(4, device=nz.device).view(1, 1, 4))).to(torch.int64)

@@ -142,6 +142,8 @@ DENSE3_ON = _T.dense_bf16x3
 DENSE3_TAU = _T.dense3_tau
 DENSE3_PIECE = _T.dense3_piece
 DENSE3_MIN_BLOCKS = _T.dense3_min_blocks
+DENSE3_VALUES = _T.dense3_values          # stored | pattern | factored: what the blocks of a structure may drop (classify_values)
+DENSE3_TAU_IMPLICIT = _T.dense3_tau_implicit
 DENSE3_BR = 512    # rows per block (= STRIP_TR: the two tall-tile paths share the row blocking and the 512-row slot blocks)
 
 
@@ -180,13 +182,15 @@ def dense3_index(i, k):
 class HostDense3:
     """The densest 512 x 128 blocks, stored DENSE in fp32 in the A-operand order of the bf16 MFMA (``dense3_index``);
     the kernel splits the values into three bf16 planes in registers and the panels of the dense operand once per
-    SpMM into a work-space (one 96 KB image per entry of ``panel_list`` and 128 features)."""
+    SpMM into a work-space (one 96 KB image per entry of ``panel_list`` and 128 features).
+    Value-free blocks (``values`` pattern / factored, ``classify_values``): ``vals3`` is None and ``bits`` holds the pattern,
+    8 KB per block (``dense3_bits``); the values are 1, or r_i c_j with ``row_scale`` / ``col_scale`` in the structure's numbering."""
     nrows: int
     ncols: int
     work: torch.Tensor        # int32 [npieces, 4] {block row id, first block, number of blocks, first slot (local)}
     blk_row: torch.Tensor     # int32 [nblocks] block row id (blocks of one id share their 512 rows: they may share a piece)
     blk_panel: torch.Tensor   # int32 [nblocks] panel id
-    vals3: torch.Tensor       # fp32 [nblocks, 512 * 128]
+    vals3: Optional[torch.Tensor]   # fp32 [nblocks, 512 * 128] (None: value-free blocks)
     panel_list: torch.Tensor  # int32 [npanels] FIRST ROW (of the dense operand) of the distinct panels of the blocks, ascending
     blk_img: torch.Tensor     # int32 [nblocks] position of a block's panel in panel_list
     coo: tuple                # (row, col, val) of the stored entries (host-side bookkeeping / checker)
@@ -194,6 +198,10 @@ class HostDense3:
     blk_col0: torch.Tensor = None    # int32 [nblocks] first matrix column   aligned to the communities of the vertex order)
     piece_row0: torch.Tensor = None  # int32 [npieces] first matrix row of a piece's 512-row partial block (the order of ``work``)
     piece_rows: torch.Tensor = None  # int32 [npieces] rows of it that belong to the piece (the band may end inside the block)
+    bits: torch.Tensor = None        # int32 [nblocks, 8, 64, 4] the pattern of value-free blocks (dense3_bits)
+    row_scale: torch.Tensor = None   # fp32 [nrows] r of a factored structure (None: all ones)
+    col_scale: torch.Tensor = None   # fp32 [ncols] c of a factored structure
+    values: str = "stored"           # stored | pattern | factored
 
     @property
     def nnz(self) -> int:
@@ -208,10 +216,67 @@ class HostDense3:
         return self.npieces * DENSE3_BR
 
 
+def _ulp32(a: torch.Tensor) -> torch.Tensor:
+    """Spacing of the fp32 numbers at |a| (float64)."""
+    x = a.to(torch.float32).abs()
+    return (torch.nextafter(x, torch.full_like(x, float("inf"))) - x).to(torch.float64)
+
+
+def classify_values(r: torch.Tensor, c: torch.Tensor, v: torch.Tensor, nrows: int, ncols: int, mode: Optional[str] = None,
+                    scales=None):
+    """What the bf16 blocks of a WHOLE structure may drop: ('stored' | 'pattern' | 'factored', row_scale, col_scale).
+    Duplicates are merged by summing (a duplicated pattern entry is 2, not a pattern).  pattern: every merged value is exactly 1;
+    factored (mode 'factored' with candidate ``scales`` = (r [nrows], c [ncols]) in the structure's numbering): every merged a_ij is
+    within 2 ulp of fl32(r_i) fl32(c_j).  Anything else -- and every structure under mode 'stored' -- keeps its stored values."""
+    mode = DENSE3_VALUES if mode is None else mode
+    if mode not in ("stored", "pattern", "factored"):
+        raise ValueError("dense3_values must be stored, pattern or factored, got %r" % (mode,))
+    if mode == "stored" or r.numel() == 0:
+        return "stored", None, None
+    r64, c64 = r.to(torch.int64), c.to(torch.int64)
+    uk, inv = torch.unique(r64 * max(ncols, 1) + c64, return_inverse=True)
+    merged = torch.zeros(uk.numel(), dtype=torch.float32, device=r.device).index_add_(0, inv, v.to(torch.float32))
+    if bool((merged == 1.0).all()):
+        return "pattern", None, None
+    if mode != "factored" or scales is None or scales[0] is None:
+        return "stored", None, None
+    rs = torch.as_tensor(scales[0]).to(device=r.device, dtype=torch.float32).contiguous()
+    cs = torch.as_tensor(scales[1]).to(device=r.device, dtype=torch.float32).contiguous()
+    if rs.numel() < nrows or cs.numel() < ncols or not bool(torch.isfinite(rs[:nrows]).all() and torch.isfinite(cs[:ncols]).all()):
+        return "stored", None, None
+    ur, uc = uk // max(ncols, 1), uk % max(ncols, 1)
+    err = (merged.to(torch.float64) - rs[ur].to(torch.float64) * cs[uc].to(torch.float64)).abs()
+    if bool((err <= 2.0 * _ulp32(merged)).all()):
+        return "factored", rs[:nrows], cs[:ncols]
+    return "stored", None, None
+
+
+def degree_scales(count: torch.Tensor) -> torch.Tensor:
+    """fl32(d^-1/2) of a count vector (the candidate scales of D^-1/2 P D^-1/2; 1 where the count is 0)."""
+    d = count.to(torch.float64)
+    return torch.where(d > 0, 1.0 / torch.sqrt(torch.clamp(d, min=1.0)), torch.ones_like(d)).to(torch.float32)
+
+
+def dense3_bits(i: torch.Tensor, k: torch.Tensor, bl: torch.Tensor, nblocks: int) -> torch.Tensor:
+    """The pattern of value-free blocks from block-local coordinates (row i of 512, column k of 128, block bl), by a scatter-OR:
+    int32 [nblocks, 8 waves, 64 lanes, 4 words], byte u = 2 ks + rb of a lane's 16 bytes, bit 4 h + e -- the A-operand order of
+    ``dense3_index`` (include/pgcn_hip.h pgcn_spmm_dense_pat_bf16x3_f32; the layout of ``HipKernels.gat_block_bits``)."""
+    i, k, bl = i.to(torch.int64), k.to(torch.int64), bl.to(torch.int64)
+    w, rb, il = i // 64, (i // 32) % 2, i % 32
+    ks, hk, h, e = k // 16, (k // 8) % 2, (k // 4) % 2, k % 4
+    u = 2 * ks + rb
+    word = ((bl * 8 + w) * 64 + hk * 32 + il) * 4 + u // 4
+    key = torch.unique(word * 32 + 8 * (u % 4) + 4 * h + e)                      # (a position set twice is one bit)
+    words = torch.zeros(nblocks * 8 * 64 * 4, dtype=torch.int64, device=i.device).index_add_(0, key // 32, 1 << (key % 32))
+    words = torch.where(words >= (1 << 31), words - (1 << 32), words)
+    return words.to(torch.int32).view(nblocks, 8, 64, 4)
+
+
 def build_dense3(r64, c64, v, bkey_local, nblocks, blk_row, blk_panel, nrows, ncols, piece: int = None,
-                 blk_row0=None, blk_col0=None, blk_rows=None) -> HostDense3:
+                 blk_row0=None, blk_col0=None, blk_rows=None, values: str = "stored", scales=None) -> HostDense3:
     """``bkey_local`` numbers the blocks 0..nblocks-1 in (block row id, panel id) order; ``blk_row0 / blk_col0`` are their origins
-    (default: the global 512 x 128 grid) and ``blk_rows`` the rows of a block that lie inside its band."""
+    (default: the global 512 x 128 grid) and ``blk_rows`` the rows of a block that lie inside its band.  ``values`` pattern /
+    factored (``classify_values``): the blocks keep their pattern as bits and no fp32 values; ``scales`` = (row, col) of factored."""
     import numpy as np
     BR, TC = DENSE3_BR, CORE_TC
     piece = DENSE3_PIECE if piece is None else piece
@@ -225,9 +290,14 @@ def build_dense3(r64, c64, v, bkey_local, nblocks, blk_row, blk_panel, nrows, nc
         blk_row0, blk_col0 = blk_row.to(torch.int64) * BR, blk_panel.to(torch.int64) * TC
         blk_rows = torch.clamp(nrows - blk_row0, max=BR)
     blk_row0, blk_col0, blk_rows = blk_row0.to(torch.int64), blk_col0.to(torch.int64), blk_rows.to(torch.int64)
-    vals = torch.zeros(nblocks * BR * TC, dtype=torch.float32, device=dev)
-    vals.index_add_(0, bkey_local * (BR * TC) + dense3_index(r64 - blk_row0[bkey_local], c64 - blk_col0[bkey_local]),
-                    v.to(torch.float32))                                                             # duplicates add
+    if values == "stored":
+        vals = torch.zeros(nblocks * BR * TC, dtype=torch.float32, device=dev)
+        vals.index_add_(0, bkey_local * (BR * TC) + dense3_index(r64 - blk_row0[bkey_local], c64 - blk_col0[bkey_local]),
+                        v.to(torch.float32))                                                         # duplicates add
+        vals, bits = vals.view(nblocks, BR * TC), None
+    else:
+        vals, bits = None, dense3_bits(r64 - blk_row0[bkey_local], c64 - blk_col0[bkey_local], bkey_local, nblocks)
+    rs, cs = (None, None) if values != "factored" else scales
     brw = blk_row.cpu().numpy()
     run_start = np.r_[True, brw[1:] != brw[:-1]]
     pos_in_run = np.arange(nblocks) - np.maximum.accumulate(np.where(run_start, np.arange(nblocks), 0))
@@ -238,9 +308,10 @@ def build_dense3(r64, c64, v, bkey_local, nblocks, blk_row, blk_panel, nrows, nc
     work = np.stack([brw[kbeg][lpt], kbeg[lpt], kcnt[lpt], np.arange(len(kbeg)) * BR], 1).astype(np.int32)
     first = torch.from_numpy(kbeg[lpt]).to(dev)
     plist, bimg = torch.unique(blk_col0, return_inverse=True)              # (a panel id has one origin: unique origins = unique panels)
-    return HostDense3(nrows, ncols, torch.from_numpy(work).to(dev), blk_row, blk_panel, vals.view(nblocks, BR * TC),
+    return HostDense3(nrows, ncols, torch.from_numpy(work).to(dev), blk_row, blk_panel, vals,
                       plist.to(torch.int32), bimg.to(torch.int32), (r64, c64, v.to(torch.float32)),
-                      blk_row0.to(torch.int32), blk_col0.to(torch.int32), blk_row0[first].to(torch.int32), blk_rows[first].to(torch.int32))
+                      blk_row0.to(torch.int32), blk_col0.to(torch.int32), blk_row0[first].to(torch.int32), blk_rows[first].to(torch.int32),
+                      bits, rs, cs, values)
 
 
 def band_grid(x64: torch.Tensor, size: int, unit: int, bands: Optional[torch.Tensor]):
@@ -259,15 +330,21 @@ def band_grid(x64: torch.Tensor, size: int, unit: int, bands: Optional[torch.Ten
 
 
 def split_dense3(r: torch.Tensor, c: torch.Tensor, v: torch.Tensor, nrows: int, ncols: int, tau: float = None,
-                 row_bands: Optional[torch.Tensor] = None, col_bands: Optional[torch.Tensor] = None, piece: Optional[int] = None):
+                 row_bands: Optional[torch.Tensor] = None, col_bands: Optional[torch.Tensor] = None, piece: Optional[int] = None,
+                 values: str = "stored", scales=None):
     """Separate the entries of 512 x 128 blocks at least ``tau`` full.  Returns (keep_mask or None, HostDense3 or None).
     With the default ``tau`` a matrix with fewer than DENSE3_MIN_BLOCKS such blocks keeps them for the other paths.
     ``row_bands / col_bands`` (r06): starts of the bands the block grid restarts at -- the communities of the vertex order, so
     that a community's diagonal block is tiled from ITS first vertex instead of wherever the global grid happens to cut it (the
-    planted-partition stand-in: 65 % of the entries sit inside communities at ~23 % fill, the global grid caught 20 %)."""
+    planted-partition stand-in: 65 % of the entries sit inside communities at ~23 % fill, the global grid caught 20 %).
+    ``values`` / ``scales``: the class of the whole structure (``classify_values``); value-free structures take the default threshold
+    DENSE3_TAU_IMPLICIT (at most the stored one of their grid: a block without values costs less)."""
     min_blocks = DENSE3_MIN_BLOCKS if tau is None else 0
     banded = (row_bands is not None and row_bands.numel() > 1) or (col_bands is not None and col_bands.numel() > 1)
-    tau = (DENSE3_TAU_BANDED if banded else DENSE3_TAU) if tau is None else tau
+    if tau is None:
+        tau = DENSE3_TAU_BANDED if banded else DENSE3_TAU
+        if values != "stored":
+            tau = min(tau, DENSE3_TAU_IMPLICIT)
     if r.numel() == 0 or tau > 1.0:
         return None, None
     BR, TC = DENSE3_BR, CORE_TC
@@ -289,7 +366,7 @@ def split_dense3(r: torch.Tensor, c: torch.Tensor, v: torch.Tensor, nrows: int, 
     blk_c0 = torch.zeros(nb, dtype=torch.int64, device=r64.device).index_copy_(0, bl, c0[is3])
     blk_rows = torch.clamp(torch.zeros(nb, dtype=torch.int64, device=r64.device).index_copy_(0, bl, rend[is3]) - blk_r0, max=BR)
     h3 = build_dense3(r64[is3], c64[is3], v[is3], bl, nb, (bk // ncp).to(torch.int32), (bk % ncp).to(torch.int32),
-                      nrows, ncols, piece, blk_r0, blk_c0, blk_rows)
+                      nrows, ncols, piece, blk_r0, blk_c0, blk_rows, values, scales)
     return ~is3, h3
 
 
@@ -549,13 +626,15 @@ def csr_from_coo(r: torch.Tensor, c: torch.Tensor, v: torch.Tensor, nrows: int, 
                  tau: float = None, emax: int = None, ngroups: Optional[int] = None,
                  slice_bounds: Optional[torch.Tensor] = None,
                  strip: Optional[bool] = None, strip_min: Optional[int] = None, dense3_tau: Optional[float] = None,
-                 row_bands: Optional[torch.Tensor] = None, col_bands: Optional[torch.Tensor] = None) -> HostCSR:
+                 row_bands: Optional[torch.Tensor] = None, col_bands: Optional[torch.Tensor] = None,
+                 scales=None, dense3_values: Optional[str] = None) -> HostCSR:
     """Sort by (row, slice, col) and build CSR.  Duplicate entries are kept as
     separate stored entries (an uncoalesced COO sums them, PGCN.py:63).  With ``core``
     the entries of dense 128 x 128 tiles are split off into a HostCore (LDS-tiled kernel).
     slice of a column = col % nslices, or -- with ``slice_bounds`` (nslices+1 ascending column
     bounds) -- the RANGE it falls in: then the rows of the dense operand that one XCD gathers are
-    contiguous in memory instead of 4 KB apart."""
+    contiguous in memory instead of 4 KB apart.  ``scales`` = (row [nrows], col [ncols]): candidate factors of the values in this
+    structure's numbering and ``dense3_values`` the mode (default tuning.dense3_values): ``classify_values``."""
     dev = r.device
     if slice_bounds is not None:
         slice_bounds = torch.as_tensor(slice_bounds, dtype=torch.int64, device=dev)
@@ -577,7 +656,8 @@ def csr_from_coo(r: torch.Tensor, c: torch.Tensor, v: torch.Tensor, nrows: int, 
         # the bf16 three-plane blocks (512 x 128); dense3_tau > 1 switches them off
         use3 = DENSE3_ON if dense3_tau is None else dense3_tau <= 1.0
         if use3 and ncols >= CORE_TC:
-            keep3, hdense3 = split_dense3(r, c, v, nrows, ncols, dense3_tau, row_bands, col_bands)
+            vmode, rs, cs = classify_values(r, c, v, nrows, ncols, dense3_values, scales)
+            keep3, hdense3 = split_dense3(r, c, v, nrows, ncols, dense3_tau, row_bands, col_bands, values=vmode, scales=(rs, cs))
             if keep3 is not None:
                 r, c, v = r[keep3], c[keep3], v[keep3]
         keep, hcore = split_core(r, c, v, nrows, ncols, 2.0 if use_strip else tau, emax)
@@ -645,14 +725,15 @@ def csr_from_coo(r: torch.Tensor, c: torch.Tensor, v: torch.Tensor, nrows: int, 
 
 def csr_from_scipy(A, nslices: Optional[int] = None, core: bool = False, tau: float = None,
                    emax: int = None, ngroups: Optional[int] = None,
-                   strip: Optional[bool] = None, strip_min: Optional[int] = None, dense3_tau: Optional[float] = None) -> HostCSR:
+                   strip: Optional[bool] = None, strip_min: Optional[int] = None, dense3_tau: Optional[float] = None,
+                   scales=None, dense3_values: Optional[str] = None) -> HostCSR:
     """Convenience for tests / tools: a scipy sparse matrix -> HostCSR (optionally sliced)."""
     import numpy as np
     A = A.tocoo()
     return csr_from_coo(torch.from_numpy(A.row.astype(np.int64)), torch.from_numpy(A.col.astype(np.int64)),
                         torch.from_numpy(A.data.astype(np.float32)), A.shape[0], A.shape[1],
                         nslices=nslices, core=core, tau=tau, emax=emax, ngroups=ngroups,
-                        strip=strip, strip_min=strip_min, dense3_tau=dense3_tau)
+                        strip=strip, strip_min=strip_min, dense3_tau=dense3_tau, scales=scales, dense3_values=dense3_values)
 
 
 @dataclass
@@ -773,11 +854,13 @@ def _offsets(owner: torch.Tensor, size: int) -> List[int]:
 def build_partition(row: torch.Tensor, col: torch.Tensor, val: torch.Tensor, n: int,
                     partvec: torch.Tensor, rank: int, size: int,
                     with_transpose: bool = True, rounds: Optional[int] = None,
-                    degree_sort: Optional[bool] = None) -> Partition:
+                    degree_sort: Optional[bool] = None, scales=None) -> Partition:
     """Build rank ``rank``'s pieces from the GLOBAL COO (row, col, val) of A.
 
     Mirrors the reference, where every rank parses the whole matrix (PGCN.py:171)
-    and filters its rows (:55-59) and boundary sets (:41-45)."""
+    and filters its rows (:55-59) and boundary sets (:41-45).
+    ``scales`` = (r, c), global n-vectors: candidate factors a_ij = r_i c_j of the values (tuning.dense3_values=factored); by
+    default there the inverse square roots of the global row and column counts (D^-1/2 P D^-1/2)."""
     dev = row.device
     row = row.to(torch.int64)
     col = col.to(torch.int64)
@@ -798,8 +881,10 @@ def build_partition(row: torch.Tensor, col: torch.Tensor, val: torch.Tensor, n: 
     # rows of mine that other ranks need: (target rank, degree rank) keys, unique and sorted
     theirs = (pcol == rank) & (prow != rank)
     suniq = torch.unique(prow[theirs] * n + grank[col[theirs]])
+    if scales is None and DENSE3_VALUES == "factored":
+        scales = (degree_scales(torch.bincount(row, minlength=n)), degree_scales(torch.bincount(col, minlength=n)))
     p = _finish_partition(row[mine], col[mine], val[mine], n, part, rank, size, gorder, grank, suniq,
-                          int(row.numel()), with_transpose, rounds, order_info.get("_bands"))
+                          int(row.numel()), with_transpose, rounds, order_info.get("_bands"), scales)
     p.order_info = order_info
     return p
 
@@ -807,7 +892,7 @@ def build_partition(row: torch.Tensor, col: torch.Tensor, val: torch.Tensor, n: 
 def build_partition_local(row: torch.Tensor, col: torch.Tensor, val: torch.Tensor, n: int,
                           partvec: torch.Tensor, rank: int, size: int, group=None,
                           with_transpose: bool = True, rounds: Optional[int] = None,
-                          degree_sort: Optional[bool] = None, emulate: Optional[dict] = None) -> Partition:
+                          degree_sort: Optional[bool] = None, emulate: Optional[dict] = None, scales=None) -> Partition:
     """The same Partition from rank ``rank``'s OWN ROWS only (global coordinates, e.g.
     ``ingest.load_partition``): no rank ever holds the whole matrix.  Two small collectives over
     ``torch.distributed`` replace the global scan: an all-reduce of the n-vector of degrees (for
@@ -818,7 +903,9 @@ def build_partition_local(row: torch.Tensor, col: torch.Tensor, val: torch.Tenso
     ``emulate`` (one process stands in for rank ``rank`` of ``size``, bench.py --emulate-rank with --shards): the two
     collectives are replaced by what the caller knows -- ``emulate["gdeg"]``, the global n-vector of (row count + column
     count) degrees, and ``emulate["nnz_global"]``; the rows the peers need from this rank are derived from this
-    rank's own entries, which is exact for a SYMMETRIC pattern (peer q holds (c, r) for every (r, c) held here)."""
+    rank's own entries, which is exact for a SYMMETRIC pattern (peer q holds (c, r) for every (r, c) held here).
+    ``scales``: as in ``build_partition``; the default candidates (factored mode) come from the global degrees: (gdeg / 2)^-1/2, the
+    row count of a symmetric pattern."""
     import torch.distributed as dist
     dev = row.device
     row = row.to(torch.int64)
@@ -833,6 +920,8 @@ def build_partition_local(row: torch.Tensor, col: torch.Tensor, val: torch.Tenso
         if row64.numel() and not bool((part_[row64] == rank).all()):
             raise ValueError("build_partition_local takes the rows owned by this rank only")
         gdeg = torch.as_tensor(emulate["gdeg"]).to(device=dev, dtype=torch.int64)
+        if scales is None and DENSE3_VALUES == "factored":
+            scales = (degree_scales(gdeg // 2),) * 2
         if not (DEGREE_SORT if degree_sort is None else degree_sort) or n <= 1:
             gdeg = None
         gorder, grank = _degree_order(gdeg, n, dev)
@@ -840,7 +929,7 @@ def build_partition_local(row: torch.Tensor, col: torch.Tensor, val: torch.Tenso
         away = pcol != rank
         suniq = torch.unique(pcol[away] * n + grank[row64[away]])            # (requesting rank, degree rank of MY row)
         return _finish_partition(row64, col64, val, n, part_, rank, size, gorder, grank, suniq,
-                                 int(emulate.get("nnz_global", row64.numel())), with_transpose, rounds)
+                                 int(emulate.get("nnz_global", row64.numel())), with_transpose, rounds, scales=scales)
     gloo = size > 1 and dist.get_backend(group) == "gloo"
 
     def to_wire(t):            # gloo moves host tensors; nccl (= RCCL) device tensors
@@ -873,8 +962,10 @@ def build_partition_local(row: torch.Tensor, col: torch.Tensor, val: torch.Tenso
         dist.all_to_all_single(recv_ids, send_ids, output_split_sizes=in_list, input_split_sizes=out_list, group=group)
         src = torch.repeat_interleave(torch.arange(size, dtype=torch.int64), torch.tensor(in_list)).to(dev)
         suniq = torch.unique(src * n + recv_ids.to(dev))                              # (requesting rank, degree rank)
+    if scales is None and DENSE3_VALUES == "factored" and gdeg is not None:
+        scales = (degree_scales(gdeg // 2),) * 2
     return _finish_partition(row, col, val, n, part, rank, size, gorder, grank, suniq, int(nnz_global),
-                             with_transpose, rounds)
+                             with_transpose, rounds, scales=scales)
 
 
 def _check_partvec(partvec, n: int, size: int, dev) -> torch.Tensor:
@@ -1003,9 +1094,10 @@ def _coo_is_symmetric(r: torch.Tensor, c: torch.Tensor, v: torch.Tensor, n: int)
 
 def _finish_partition(row_m: torch.Tensor, col_m: torch.Tensor, val_m: torch.Tensor, n: int, part: torch.Tensor,
                       rank: int, size: int, gorder: torch.Tensor, grank: torch.Tensor, suniq: torch.Tensor,
-                      nnz_global: int, with_transpose: bool, rounds: Optional[int], bands_global=None) -> Partition:
+                      nnz_global: int, with_transpose: bool, rounds: Optional[int], bands_global=None, scales=None) -> Partition:
     """Everything after the two global facts (degree ranking, who needs which of my rows):
-    ``row_m/col_m/val_m`` are this rank's entries in GLOBAL coordinates."""
+    ``row_m/col_m/val_m`` are this rank's entries in GLOBAL coordinates; ``scales`` = (r, c) global candidate factors of the values,
+    handed to every structure in its own numbering (a transpose swaps them)."""
     dev = row_m.device
     owned = torch.nonzero(part == rank).reshape(-1)
     n_p = int(owned.numel())
@@ -1029,7 +1121,13 @@ def _finish_partition(row_m: torch.Tensor, col_m: torch.Tensor, val_m: torch.Ten
             lbands = torch.cat([torch.zeros(1, dtype=torch.int64, device=dev), lbands])
         if lbands.numel() <= 1:
             lbands = None
-    A_loc = csr_from_coo(r[loc], g2l[c[loc]], v[loc], n_p, n_p, core=CORE_ON, row_bands=lbands, col_bands=lbands)
+    rg = cg = None
+    if scales is not None:
+        rg, cg = (torch.as_tensor(x).to(device=dev, dtype=torch.float32) for x in scales)
+    def sc(rv, rix, cv, cix):      # (row scale, col scale) of a structure: global vectors picked by its row / column numbering
+        return None if rg is None else (rv[rix], cv[cix])
+    A_loc = csr_from_coo(r[loc], g2l[c[loc]], v[loc], n_p, n_p, core=CORE_ON, row_bands=lbands, col_bands=lbands,
+                         scales=sc(rg, owned, cg, owned))
     R = max(1, (EXCHANGE_ROUNDS if rounds is None else rounds)) if size > 1 else 1
     # halo columns: per owner the reference's recv_map[q] as a SET (PGCN.py:44-48), ordered
     # (round, owner, degree rank)
@@ -1051,10 +1149,11 @@ def _finish_partition(row_m: torch.Tensor, col_m: torch.Tensor, val_m: torch.Ten
     for k in range(R if size > 1 else 0):
         sel = ecol_round == k
         A_halo.append(csr_from_coo(rr[sel], hcol[sel], vv[sel], n_p, n_halo, compact_rows=not halo_core,
-                                   core=halo_core))
+                                   core=halo_core, scales=sc(rg, owned, cg, halo_global)))
         if with_transpose:
             base, end = round_recv_off[k][0], round_recv_off[k][size]
-            A_halo_T.append(csr_from_coo(hcol[sel] - base, rr[sel], vv[sel], end - base, n_p, core=halo_core))
+            A_halo_T.append(csr_from_coo(hcol[sel] - base, rr[sel], vv[sel], end - base, n_p, core=halo_core,
+                                         scales=sc(cg, halo_global[base:end], rg, owned)))
 
     A_loc_T = None
     if with_transpose:
@@ -1064,7 +1163,8 @@ def _finish_partition(row_m: torch.Tensor, col_m: torch.Tensor, val_m: torch.Ten
             # the block -- half the structure memory and half of the "partition built" stage (r06)
             A_loc_T = A_loc
         else:
-            A_loc_T = csr_from_coo(cl, rl, vl, n_p, n_p, core=CORE_ON, row_bands=lbands, col_bands=lbands)
+            A_loc_T = csr_from_coo(cl, rl, vl, n_p, n_p, core=CORE_ON, row_bands=lbands, col_bands=lbands,
+                                   scales=sc(cg, owned, rg, owned))
 
     # rows of mine that other ranks need, in the peers' slab order (round, target rank, degree rank)
     s_order, _, round_send_off = _round_major(suniq // n, size, R)

@@ -46,6 +46,12 @@ class Tuning:
     dense3_tau_banded: float = 0.12  # ... under a grid aligned to the communities of the vertex order (tuning.order_band_min): the blocks of a community
                                      # are evenly ~23 % full on the planted-partition stand-in and the next cluster sits at ~13 % (r06, SBM line: global
                                      # grid 18.0-18.2 ms / epoch, bands at 0.20 17.5-17.6, bands at 0.12 16.9-17.0: profiles/r06_bands_sbm.txt)
+    dense3_values: str = "stored"    # what the blocks hold: stored (fp32 values, six products) | pattern (structures whose merged values are all 1:
+                                     # one bit per position, three products) | factored (also structures with a_ij = fl32(r_i) fl32(c_j) within
+                                     # 2 ulp, e.g. D^-1/2 P D^-1/2: the bits plus a row and a column scale).  Verified per structure; the rest stays stored
+    dense3_tau_implicit: float = 0.08  # block fill threshold of the value-free structures (at most the stored threshold of their grid): no value
+                                     # stream and three MFMAs per step move the break-even down.  Sweep, factored, ms per epoch: R-MAT 0.20 9.82,
+                                     # 0.12 9.70, 0.08 9.60 (stored blocks 10.13-10.18); SBM (banded) 0.12 16.64, 0.08 16.58, 0.05 16.99 (stored 17.04-17.08)
     dense3_piece: int = 0            # blocks per piece (0 = adaptive: one round of 256 pieces, between 1 and 8 blocks)
     dense3_min_blocks: int = 400     # matrices with fewer such blocks leave their entries to the strips / the LDS core (a shard of an
                                      # 8-way run: two more launches and 512-row partial blocks for a few dozen blocks: rank 0 of 8,
@@ -124,7 +130,12 @@ def _parse(spec: str, base: Tuning) -> Tuning:
         else:
             val = v
         setattr(out, k, val)
+    if out.dense3_values not in DENSE3_VALUES:
+        raise ValueError("PGCN_TUNING: dense3_values must be one of %s, got %r" % ("|".join(DENSE3_VALUES), out.dense3_values))
     return out
+
+
+DENSE3_VALUES = ("stored", "pattern", "factored")
 
 
 # what else the package reads from the environment: transports, ingest path, seeds, a cache path, a deadline -- no kernel shape
