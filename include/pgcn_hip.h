@@ -134,6 +134,26 @@ int pgcn_spmm_csr_plan_f32(const int64_t *rowptr, const int32_t *col, const floa
                            int64_t ldc, int32_t f, float *partial_ws, int64_t partial_ws_elems,
                            int64_t nslots, uint32_t flags, pgcn_stream_t stream);
 
+/* Value-free structures (a 0/1 pattern P with a row and a column scale, e.g. the GCN adjacency
+ * D_r^-1/2 (A + I) D_c^-1/2 normalised on the fly): C (+)= diag(row_scale) P diag(col_scale) . B,
+ * no value array.  Replaces torch.sparse.mm(A, H) / torch.sparse.mm(A.t(), grad) at GPU/PGCN.py:127,132
+ * for such A (pass the pattern of A^T with the scales swapped for the second).  The weight of an entry
+ * is col_scale[col] (ncols entries); every task multiplies its sum by row_scale[row] (CSR row, before
+ * row_map) before it writes a partial slot or a row of C and before the PGCN_SPMM_ACCUMULATE add, so
+ * the fix-up adds rows that are already scaled.  Both scales NULL = the pattern product (as val NULL
+ * above); row_scale needs col_scale.  slot_row[nslots]: the CSR row of every partial slot (required
+ * with row_scale when nslots > 0).  Everything else as pgcn_spmm_csr_f32 / pgcn_spmm_csr_plan_f32. */
+int pgcn_spmm_csr_scaled_f32(const int64_t *rowptr, const int32_t *col, const float *row_scale,
+                             const float *col_scale, int64_t nrows, const float *B, int64_t ldb, float *C,
+                             int64_t ldc, int32_t f, uint32_t flags, pgcn_stream_t stream);
+int pgcn_spmm_csr_plan_scaled_f32(const int64_t *rowptr, const int32_t *col, const float *row_scale,
+                                  const float *col_scale, const int32_t *slot_row,
+                                  const int32_t *tasks, int64_t ntasks, const int64_t *seg,
+                                  int32_t nslices, const int32_t *fix, int64_t nfix,
+                                  const int32_t *row_map, const float *B, int64_t ldb, float *C,
+                                  int64_t ldc, int32_t f, float *partial_ws, int64_t partial_ws_elems,
+                                  int64_t nslots, uint32_t flags, pgcn_stream_t stream);
+
 /* Host-side plan builder (pure CPU, no HIP).  rowptr_host: nrows+1 entries;
  * slice_cnt: nrows x (nslices*ngroups) entry counts per (row, slice, column group), index
  *        s*ngroups + g, or NULL when nslices*ngroups == 1.  ngroups > 1 additionally orders
@@ -218,6 +238,17 @@ int pgcn_spmm_heads_f32(const int64_t *rowptr, const int32_t *col, const float *
 int pgcn_spmm_strip_f32(const int32_t *work, int64_t nwork, const int32_t *recs, const int32_t *pairs,
                         const float *B, int64_t ldb, int64_t ncols, int32_t f, float *partial_ws,
                         int64_t partial_ws_elems, int64_t nslots_total, pgcn_stream_t stream);
+
+/* Value-free strip records (structures with no values: diag(row_scale) P diag(col_scale), P a 0/1 pattern).  offs: int32
+ * [nrec][1024], the offset slots of pgcn_spmm_strip_f32's pairs without the values (4 KB per record), 16-byte aligned.  The
+ * staged panel row j is multiplied by col_scale[j] once (NULL = ones) and every partial row i by row_scale[i] at its slot write
+ * (NULL = ones; readable at rows 512 * tile row + 0 .. 511 of every piece: the caller pads it).  work / recs / partial_ws /
+ * nslots_total: as pgcn_spmm_strip_f32, and the same sums bit for bit on all-ones records with NULL scales.  Part of
+ * torch.sparse.mm at GPU/PGCN.py:127,132 for such A.                                                                    */
+int pgcn_spmm_strip_vf_f32(const int32_t *work, int64_t nwork, const int32_t *recs, const int32_t *offs,
+                           const float *row_scale, const float *col_scale, const float *B, int64_t ldb, int64_t ncols,
+                           int32_t f, float *partial_ws, int64_t partial_ws_elems, int64_t nslots_total,
+                           pgcn_stream_t stream);
 
 
 /* The densest 512 x 128 BLOCKS through the bf16 matrix cores at fp32 accuracy (v_mfma_f32_32x32x16_bf16; every fp32

@@ -84,41 +84,42 @@ def _partvec_fingerprint(partvec):
     return (int(pv.size), int(pv.sum()), int((pv * (np.arange(pv.size, dtype=np.int64) % 1000003 + 1)).sum()))
 
 
-def _get_partition(A, partvec, rank, size):
+def _get_partition(A, partvec, rank, size, normalize=None):
     """One-entry cache (compute_communication_maps and get_partitiont_of_adjacency_matrix are called back
     to back on the same matrix, PGCN.py:178-179).  The entry HOLDS the matrix it was built from and is
     matched by identity plus a fingerprint of the part vector, so a recycled id() or a new part vector
-    can never return a stale partition."""
-    key = (rank, size, tuple(A.shape), int(A.nnz), _partvec_fingerprint(partvec))
+    can never return a stale partition.  ``normalize``: partition.build_partition's (None = train on A's values)."""
+    key = (rank, size, tuple(A.shape), int(A.nnz), _partvec_fingerprint(partvec), normalize)
     ent = _partition_cache.get("entry")
     if ent is not None and ent[0] is A and ent[1] == key:
         return ent[2]
     row, col, val = _coo_tensors(A)
     p = _partition.build_partition(row, col, val, A.shape[0],
-                                   torch.as_tensor(partvec, dtype=torch.int64), rank, size)
+                                   torch.as_tensor(partvec, dtype=torch.int64), rank, size, normalize=normalize)
     _partition_cache["entry"] = (A, key, p)
     return p
 
 
-def _seed_partition_cache(A, partvec, rank, size, p):
-    _partition_cache["entry"] = (A, (rank, size, tuple(A.shape), int(A.nnz), _partvec_fingerprint(partvec)), p)
+def _seed_partition_cache(A, partvec, rank, size, p, normalize=None):
+    _partition_cache["entry"] = (A, (rank, size, tuple(A.shape), int(A.nnz), _partvec_fingerprint(partvec), normalize), p)
 
 
-def compute_communication_maps(A, partvec, rank, size):
+def compute_communication_maps(A, partvec, rank, size, normalize=None):
     """PGCN.py:37-51.  Returns (send_map, recv_map): peer -> sorted LongTensor of GLOBAL ids
-    (own rank absent).  O(nnz) tensor ops instead of the reference's Python loop."""
-    p = _get_partition(A, partvec, rank, size)
+    (own rank absent).  O(nnz) tensor ops instead of the reference's Python loop.  ``normalize="sym"``: the maps of
+    A + I (partition.build_partition)."""
+    p = _get_partition(A, partvec, rank, size, normalize)
     dev = device if device is not None else torch.device("cpu")
     return ({q: t.to(dev) for q, t in p.send_map().items()},
             {q: t.to(dev) for q, t in p.recv_map().items()})
 
 
-def get_partitiont_of_adjacency_matrix(A, partvec, rank):
+def get_partitiont_of_adjacency_matrix(A, partvec, rank, normalize=None):
     """PGCN.py:53-64.  Returns the aggregation engine of this rank's row block (the
     object PSpMM / PGCN take as ``A``) instead of an n x n COO tensor."""
     global _engine_current, _exchanger
     size = world_size if world_size else 1
-    p = _get_partition(A, partvec, rank, size)
+    p = _get_partition(A, partvec, rank, size, normalize)
     exch = None
     if size > 1:
         if _exchanger is None:
@@ -755,8 +756,9 @@ def local_loss(logits, labels, n_global):
     return (nll_sum + missing * math.log(f)) / n_global
 
 
-def run(rank, size, nlayers, nfeatures, path_A, path_partvec, backend):
-    """PGCN.py:162-238."""
+def run(rank, size, nlayers, nfeatures, path_A, path_partvec, backend, normalize=None):
+    """PGCN.py:162-238.  ``normalize="sym"``: train on D_r^-1/2 (A + I) D_c^-1/2 of the pattern of ``path_A``, built on the fly
+    (partition.build_partition) instead of by the offline pass preprocess/GrB-GNN-IDG.py."""
     global myrank, world_size, send_map, recv_map, device, X, recv_buffers, send_buffers, stats
     myrank = rank
     world_size = size
@@ -787,7 +789,8 @@ def run(rank, size, nlayers, nfeatures, path_A, path_partvec, backend):
         row, col, val = _coo_tensors(A)
         build = _partition.build_partition_local if size > 1 else _partition.build_partition
         _seed_partition_cache(A, partvec, rank, size, build(row, col, val, A.shape[0],
-                                                            torch.as_tensor(partvec, dtype=torch.int64), rank, size))
+                                                            torch.as_tensor(partvec, dtype=torch.int64), rank, size,
+                                                            normalize=normalize), normalize)
     elif os.environ.get("PGCN_INGEST", "rows") == "rows" and size > 1:
         # every rank keeps ONLY its rows (pgcn_load_mtx_partition) and the partition is completed by two
         # small collectives instead of a scan of the whole matrix on every rank (PGCN.py:37-64).  Default since
@@ -795,13 +798,13 @@ def run(rank, size, nlayers, nfeatures, path_A, path_partvec, backend):
         A = _ingest.load_partition(path_A, partvec, rank)
         row, col, val = _coo_tensors(A)
         _seed_partition_cache(A, partvec, rank, size, _partition.build_partition_local(
-            row, col, val, A.shape[0], torch.as_tensor(partvec, dtype=torch.int64), rank, size))
+            row, col, val, A.shape[0], torch.as_tensor(partvec, dtype=torch.int64), rank, size, normalize=normalize), normalize)
     else:
         A = _ingest.mmread(path_A)      # C++ multi-threaded reader, same result as scipy's mmread
     n = A.shape[0]
 
-    send_map, recv_map = compute_communication_maps(A, partvec, rank, size)
-    A = get_partitiont_of_adjacency_matrix(A, partvec, rank)
+    send_map, recv_map = compute_communication_maps(A, partvec, rank, size, normalize)
+    A = get_partitiont_of_adjacency_matrix(A, partvec, rank, normalize)
     _partition_cache.clear()              # the engine owns the pieces now; let the host matrix go
     send_buffers, recv_buffers = {}, {}   # persistent slabs live inside the engine
 
@@ -867,7 +870,7 @@ def run(rank, size, nlayers, nfeatures, path_A, path_partvec, backend):
     return model
 
 
-def init_process(rank, size, fn, nlayers, nfeatures, path_A, path_partvec, backend):
+def init_process(rank, size, fn, nlayers, nfeatures, path_A, path_partvec, backend, normalize=None):
     """PGCN.py:241-253."""
     global _exchanger
     dist.init_process_group(backend, rank=rank, world_size=size)
@@ -878,7 +881,10 @@ def init_process(rank, size, fn, nlayers, nfeatures, path_A, path_partvec, backe
     }
     print(f"[{os.getpid()}] Initializing process group with: {env_dict}", flush=True)
 
-    fn(rank, size, nlayers, nfeatures, path_A, path_partvec, backend)
+    if normalize is None:
+        fn(rank, size, nlayers, nfeatures, path_A, path_partvec, backend)
+    else:
+        fn(rank, size, nlayers, nfeatures, path_A, path_partvec, backend, normalize=normalize)
 
     if _exchanger is not None:
         _exchanger.close()
@@ -895,14 +901,19 @@ def main(argv):
     os.environ["RANK"] = str(rank)
     os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
     os.environ.setdefault("MASTER_PORT", "29500")
-    backend, nlayers, nfeatures = "nccl", 3, 128
+    backend, nlayers, nfeatures, normalize = "nccl", 3, 128, None
     try:
-        opts, args = getopt.getopt(argv, "a:p:b:s:l:f:", [])
+        opts, args = getopt.getopt(argv, "a:p:b:s:l:f:", ["normalize="])
     except getopt.GetoptError:
         print("a:p:b:", flush=True)
         sys.exit(2)
     for opt, arg in opts:
-        if opt == '-a':
+        if opt == '--normalize':       # train on D^-1/2 (A + I) D^-1/2 of the input's pattern (partition.build_partition)
+            if arg not in _partition.NORMALIZE:
+                print("--normalize takes %s, got %r" % ("|".join(_partition.NORMALIZE), arg), flush=True)
+                sys.exit(2)
+            normalize = arg
+        elif opt == '-a':
             path_A = arg
         elif opt == '-p':
             path_partvec = arg
@@ -917,7 +928,7 @@ def main(argv):
     os.environ.setdefault("WORLD_SIZE", str(size))
 
     mp.set_start_method("spawn", force=True)
-    p = mp.Process(target=init_process, args=(rank, size, run, nlayers, nfeatures, path_A, path_partvec, backend))
+    p = mp.Process(target=init_process, args=(rank, size, run, nlayers, nfeatures, path_A, path_partvec, backend, normalize))
     p.start()
     p.join()
     if p.exitcode != 0:

@@ -44,15 +44,18 @@ __device__ __forceinline__ int64_t swizzle_block(int64_t b, int64_t nb, bool on)
 
 struct SliceSeg { int64_t v[PGCN_MAX_SLICES + 1]; };
 
+// value-free structures (pgcn_spmm_csr_plan_scaled_f32): column / row scales and the CSR row of every partial slot
+struct Scales { const float *col; const float *row; const int32_t *slot_row; };
+
 // tasks: int4 {kbeg low 32, kbeg high 32, length, dst}; kbeg = absolute offset of the task's
 // first entry in col/val; dst >= 0: partial-sum slot, dst < 0: write row ~dst of C directly.
-template <int LPR, int VEC, bool HAS_VAL, bool OFF32>
+template <int LPR, int VEC, bool HAS_VAL, bool OFF32, bool SCALED>
 __global__ __launch_bounds__(kThreads, 6) void spmm_tasks_kernel(
     const int64_t *__restrict__ rowptr, const int32_t *__restrict__ col,
     const float *__restrict__ val, const int4 *__restrict__ tasks, int64_t ntasks,
     const int32_t *__restrict__ row_map, const float *__restrict__ B, int64_t ldb,
     float *__restrict__ C, int64_t ldc, int32_t f, float *__restrict__ partial,
-    int64_t nblocks, uint32_t flags, int32_t nslices, SliceSeg seg) {
+    int64_t nblocks, uint32_t flags, int32_t nslices, SliceSeg seg, Scales sc) {
     constexpr int G = 64 / LPR;
     const int lane = threadIdx.x & 63;
     const int wave = threadIdx.x >> 6;
@@ -93,8 +96,9 @@ __global__ __launch_bounds__(kThreads, 6) void spmm_tasks_kernel(
             dst = ~(int32_t)tid;
         }
     }
-    pgcn_bodies::gather_task_body<LPR, VEC, HAS_VAL, OFF32>(tact, kbeg, len, dst, rowptr, col, val, row_map, B, ldb,
-                                                          C, ldc, f, partial, flags, fcol, meta_lds[wave]);
+    pgcn_bodies::gather_task_body<LPR, VEC, HAS_VAL, OFF32, SCALED>(tact, kbeg, len, dst, rowptr, col, val, row_map, B, ldb,
+                                                                  C, ldc, f, partial, flags, fcol, meta_lds[wave],
+                                                                  sc.col, sc.row, sc.slot_row);
 }
 
 // fix: int4 {row, first slot, #segments, unused}; sums the segments of a split
@@ -152,14 +156,14 @@ Shape pick_shape(int32_t f, const void *B, int64_t ldb, const void *C, int64_t l
     return {lpr, vec};
 }
 
-template <int LPR, int VEC, bool HAS_VAL, bool OFF32>
+template <int LPR, int VEC, bool HAS_VAL, bool OFF32, bool SCALED>
 int launch_tasks(const int64_t *rowptr, const int32_t *col, const float *val, const int4 *tasks,
                  int64_t ntasks, const int32_t *row_map, const float *B, int64_t ldb, float *C,
                  int64_t ldc, int32_t f, float *partial, int64_t grid, int ntiles, uint32_t flags,
-                 int nslices, const SliceSeg &seg, hipStream_t s) {
-    hipLaunchKernelGGL((spmm_tasks_kernel<LPR, VEC, HAS_VAL, OFF32>), dim3((unsigned)grid, ntiles),
+                 int nslices, const SliceSeg &seg, const Scales &sc, hipStream_t s) {
+    hipLaunchKernelGGL((spmm_tasks_kernel<LPR, VEC, HAS_VAL, OFF32, SCALED>), dim3((unsigned)grid, ntiles),
                        dim3(kThreads), 0, s, rowptr, col, val, tasks, ntasks, row_map, B, ldb, C, ldc,
-                       f, partial, grid, flags, nslices, seg);
+                       f, partial, grid, flags, nslices, seg, sc);
     PGCN_HIP_CHECK(hipGetLastError());
     return PGCN_OK;
 }
@@ -169,7 +173,7 @@ int launch(const int64_t *rowptr, const int32_t *col, const float *val, const in
            int64_t ntasks, const int64_t *seg_host, int nslices, const int32_t *fix, int64_t nfix,
            const int32_t *row_map,
            const float *B, int64_t ldb, float *C, int64_t ldc, int32_t f, float *partial,
-           uint32_t flags, hipStream_t s) {
+           uint32_t flags, const Scales &sc, hipStream_t s) {
     constexpr int G = 64 / LPR;
     const int ntiles = (f + LPR * VEC - 1) / (LPR * VEC);
     if (ntasks > 0) {
@@ -191,11 +195,12 @@ int launch(const int64_t *rowptr, const int32_t *col, const float *val, const in
         const int4 *t4 = reinterpret_cast<const int4 *>(tasks);
         const bool off32 = (flags & PGCN_SPMM_OFFSETS32) != 0;
         int rc;
-#define PGCN_LT(HV, O32)                                                                        \
-    rc = launch_tasks<LPR, VEC, HV, O32>(rowptr, col, val, t4, ntasks, row_map, B, ldb, C, ldc, f, \
-                                         partial, grid, ntiles, flags, nslices, seg, s)
-        if (val) { if (off32) PGCN_LT(true, true); else PGCN_LT(true, false); }
-        else     { if (off32) PGCN_LT(false, true); else PGCN_LT(false, false); }
+#define PGCN_LT(HV, O32, SC)                                                                        \
+    rc = launch_tasks<LPR, VEC, HV, O32, SC>(rowptr, col, val, t4, ntasks, row_map, B, ldb, C, ldc, f, \
+                                             partial, grid, ntiles, flags, nslices, seg, sc, s)
+        if (val)         { if (off32) PGCN_LT(true, true, false); else PGCN_LT(true, false, false); }
+        else if (sc.col) { if (off32) PGCN_LT(false, true, true); else PGCN_LT(false, false, true); }
+        else             { if (off32) PGCN_LT(false, true, false); else PGCN_LT(false, false, false); }
 #undef PGCN_LT
         if (rc != PGCN_OK) return rc;
     }
@@ -214,7 +219,7 @@ int dispatch(const int64_t *rowptr, const int32_t *col, const float *val, const 
              int64_t ntasks, const int64_t *seg, int nslices, const int32_t *fix, int64_t nfix,
              const int32_t *row_map,
              const float *B, int64_t ldb, float *C, int64_t ldc, int32_t f, float *partial,
-             uint32_t flags, hipStream_t s) {
+             uint32_t flags, hipStream_t s, const Scales &sc = Scales{nullptr, nullptr, nullptr}) {
     Shape sh = pick_shape(f, B, ldb, C, ldc, partial);
     // feature passes: fewer lanes per task -> the grid's y dimension walks the features 64 at a time (pass-major
     // dispatch order), so the rows of B one pass touches are 256 B each and a pass's working set is half the panel
@@ -223,7 +228,7 @@ int dispatch(const int64_t *rowptr, const int32_t *col, const float *val, const 
 #define PGCN_CASE(L, V)                                                                       \
     if (sh.lpr == L && sh.vec == V)                                                           \
         return launch<L, V>(rowptr, col, val, tasks, ntasks, seg, nslices, fix, nfix, row_map, \
-                            B, ldb, C, ldc, f, partial, flags, s);
+                            B, ldb, C, ldc, f, partial, flags, sc, s);
     PGCN_CASE(1, 4) PGCN_CASE(2, 4) PGCN_CASE(4, 4) PGCN_CASE(8, 4) PGCN_CASE(16, 4)
     PGCN_CASE(32, 4) PGCN_CASE(64, 4)
     PGCN_CASE(1, 1) PGCN_CASE(2, 1) PGCN_CASE(4, 1) PGCN_CASE(8, 1) PGCN_CASE(16, 1)
@@ -267,4 +272,44 @@ extern "C" int pgcn_spmm_csr_plan_f32(const int64_t *rowptr, const int32_t *col,
         return pgcn_set_error(PGCN_ENOMEM, "pgcn_spmm_csr_plan_f32: partial work-space too small");
     return dispatch(rowptr, col, val, tasks, ntasks, seg, nslices, fix, nfix, row_map, B, ldb, C,
                     ldc, f, partial_ws, flags, (hipStream_t)stream);
+}
+
+// Value-free structures (partition.csr_from_coo, value-free): C (+)= diag(r) P diag(c) . B.  The weight of an entry is
+// col_scale[col] -- one lookup into an n-vector that stays in L2 instead of the non-temporal value stream -- and every task
+// multiplies its sum by row_scale[row] before it writes a slot or a row of C (and before the ACCUMULATE add).
+extern "C" int pgcn_spmm_csr_scaled_f32(const int64_t *rowptr, const int32_t *col, const float *row_scale,
+                                        const float *col_scale, int64_t nrows, const float *B, int64_t ldb, float *C,
+                                        int64_t ldc, int32_t f, uint32_t flags, pgcn_stream_t stream) {
+    if (nrows < 0 || f <= 0 || ldb < f || ldc < f)
+        return pgcn_set_error(PGCN_EINVAL, "pgcn_spmm_csr_scaled_f32: bad sizes");
+    if (nrows == 0) return PGCN_OK;
+    if (!rowptr || !col || !B || !C || (row_scale && !col_scale))
+        return pgcn_set_error(PGCN_EINVAL, "pgcn_spmm_csr_scaled_f32: null pointer");
+    if (nrows > 0x7fffffffLL) return pgcn_set_error(PGCN_EINVAL, "pgcn_spmm_csr_scaled_f32: nrows >= 2^31");
+    return dispatch(rowptr, col, nullptr, nullptr, nrows, nullptr, 1, nullptr, 0, nullptr, B, ldb, C,
+                    ldc, f, nullptr, flags, (hipStream_t)stream, Scales{col_scale, row_scale, nullptr});
+}
+
+extern "C" int pgcn_spmm_csr_plan_scaled_f32(const int64_t *rowptr, const int32_t *col, const float *row_scale,
+                                             const float *col_scale, const int32_t *slot_row,
+                                             const int32_t *tasks, int64_t ntasks, const int64_t *seg,
+                                             int32_t nslices, const int32_t *fix, int64_t nfix,
+                                             const int32_t *row_map, const float *B, int64_t ldb,
+                                             float *C, int64_t ldc, int32_t f, float *partial_ws,
+                                             int64_t partial_ws_elems, int64_t nslots, uint32_t flags,
+                                             pgcn_stream_t stream) {
+    if (ntasks < 0 || nfix < 0 || f <= 0 || ldb < f || ldc < f || nslices < 1 ||
+        nslices > PGCN_MAX_SLICES || (nslices > 1 && !seg))
+        return pgcn_set_error(PGCN_EINVAL, "pgcn_spmm_csr_plan_scaled_f32: bad sizes");
+    if (nslices > 1 && (seg[0] != 0 || seg[nslices] != ntasks))
+        return pgcn_set_error(PGCN_EINVAL, "pgcn_spmm_csr_plan_scaled_f32: seg does not cover the task list");
+    if (ntasks == 0) return PGCN_OK;
+    const bool own_fixup = nfix > 0 && !(flags & PGCN_SPMM_NO_FIXUP);
+    if (!rowptr || !col || !B || !C || !tasks || (own_fixup && !fix) || (nslots > 0 && !partial_ws) ||
+        (row_scale && !col_scale) || (row_scale && nslots > 0 && !slot_row))
+        return pgcn_set_error(PGCN_EINVAL, "pgcn_spmm_csr_plan_scaled_f32: null pointer");
+    if (nslots < 0 || (nslots > 0 && partial_ws_elems < nslots * (int64_t)f))
+        return pgcn_set_error(PGCN_ENOMEM, "pgcn_spmm_csr_plan_scaled_f32: partial work-space too small");
+    return dispatch(rowptr, col, nullptr, tasks, ntasks, seg, nslices, fix, nfix, row_map, B, ldb, C,
+                    ldc, f, partial_ws, flags, (hipStream_t)stream, Scales{col_scale, row_scale, slot_row});
 }

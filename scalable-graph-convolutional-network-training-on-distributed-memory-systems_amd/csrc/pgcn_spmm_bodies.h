@@ -54,13 +54,18 @@ __device__ __forceinline__ void load_row(float (&x)[VEC], const float *B, uint32
 // Gather task: one group of LPR lanes accumulates `len` stored entries starting at kbeg into its
 // VEC features and writes a partial-sum slot (dst >= 0) or row ~dst of C.  `mrow` = 64 float2 of
 // LDS owned by the calling wave.  See pgcn_spmm.hip for the design notes.
-template <int LPR, int VEC, bool HAS_VAL, bool OFF32>
+// SCALED (value-free structures, HAS_VAL false): the weight of an entry is col_scale[col] (an n-vector that stays in
+// L2) instead of a streamed value, and the sum is multiplied by row_scale[row] (if given) before it is written or
+// accumulated -- row = ~dst, or slot_row[dst] for a partial slot, so the fix-up adds rows that are already scaled.
+template <int LPR, int VEC, bool HAS_VAL, bool OFF32, bool SCALED = false>
 __device__ __forceinline__ void gather_task_body(
     const bool tact, const int64_t kbeg, const int32_t len, const int32_t dst,
     const int64_t *__restrict__ rowptr, const int32_t *__restrict__ col, const float *__restrict__ val,
     const int32_t *__restrict__ row_map, const float *__restrict__ B, const int64_t ldb,
     float *__restrict__ C, const int64_t ldc, const int32_t f, float *__restrict__ partial,
-    const uint32_t flags, const int fcol, float2 *mrow) {
+    const uint32_t flags, const int fcol, float2 *mrow, const float *__restrict__ col_scale = nullptr,
+    const float *__restrict__ row_scale = nullptr, const int32_t *__restrict__ slot_row = nullptr) {
+    static_assert(!(HAS_VAL && SCALED), "a structure has stored values or scales, not both");
     constexpr int U = (LPR < kUnroll) ? LPR : kUnroll;   // gathers in flight per batch
     const int lane = threadIdx.x & 63;
     const int sub = lane % LPR;
@@ -84,6 +89,7 @@ __device__ __forceinline__ void gather_task_body(
         const int e = (sub < last) ? sub : last;
         nc = __builtin_nontemporal_load(cp + e);
         if constexpr (HAS_VAL) nv = __builtin_nontemporal_load(vp + e);
+        if constexpr (SCALED) nv = (len > 0) ? col_scale[nc] : 1.f;   // (an empty group's nc is not a column)
     }
     // The wave's current LPR-batch of pairs lives in LDS (512 B per wave): a group
     // broadcasts entry k to its lanes with ONE ds_read_b128 per two entries (all lanes of
@@ -100,6 +106,7 @@ __device__ __forceinline__ void gather_task_body(
             e = (e < last) ? e : last;
             nc = __builtin_nontemporal_load(cp + e);
             if constexpr (HAS_VAL) nv = __builtin_nontemporal_load(vp + e);
+            if constexpr (SCALED) nv = (len > 0) ? col_scale[nc] : 1.f;
         }
         const int cnt = len - base;  // entries left for this group (may be <= 0)
         const float2 *mg = mrow + gbase;
@@ -144,6 +151,13 @@ __device__ __forceinline__ void gather_task_body(
     }
 
     if (tact && fact) {
+        if constexpr (SCALED) {
+            if (row_scale) {
+                const float rs = row_scale[dst >= 0 ? slot_row[dst] : ~dst];
+#pragma unroll
+                for (int v = 0; v < VEC; ++v) acc[v] *= rs;
+            }
+        }
         if (dst >= 0) {
             vstore<VEC>(partial + (int64_t)dst * f + fcol, acc);
         } else {

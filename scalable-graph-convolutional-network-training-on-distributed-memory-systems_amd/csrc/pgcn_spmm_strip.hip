@@ -334,6 +334,241 @@ __global__ __launch_bounds__(kThreads, 1) void spmm_strip_kernel(
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// Value-free records (structures with no values: a 0/1 pattern P, or diag(r) P diag(c)).  A record keeps only the 4-byte
+// offset slots: 1 024 x 4 B = 4 KB, same row order, unused slots point at the zero row.  c_j reaches the FMAs through the
+// staged panel: every thread multiplies the four 16-byte chunks IT copied by the c of their rows after its own copies have
+// landed and BEFORE the one barrier of the panel change (nobody else touches those bytes, so no second barrier), i.e. once per
+// staged row instead of once per entry, and the compute phase is the stored kernel's with weight 1 (an all-ones structure
+// gives the stored kernel's sums bit for bit).  r_i is applied at the partial-row write; the fix-up is unchanged.
+constexpr int kWaveRecVF = TRS * SB * 4 / (kThreads / 64);   // 256 B: the offsets of one wave's four groups
+constexpr int kSlotBytesVF = kWaveRecVF + 16;
+constexpr int kGroupVF = RW * SB * 4;                          // 64 B per group and record
+constexpr int kSmemVF = kOffRing + (kThreads / 64) * kRing * kSlotBytesVF;
+
+__device__ __forceinline__ void issue_offs(const int32_t *__restrict__ offs, const int4 *__restrict__ recs, int64_t k, int64_t k1,
+                                           int slot, char *smem, int wave, int lane) {
+    if (lane <= 16) {
+        const int32_t *src = lane < 16 ? offs + k * (int64_t)(TRS * SB) + wave * (kWaveRecVF / 4) + lane * 4
+                                       : reinterpret_cast<const int32_t *>(recs + (k + 1 < k1 ? k + 1 : k));
+        __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)(smem + kOffRing + (wave * kRing + slot) * kSlotBytesVF), 16, 0, 0);
+    }
+}
+
+__device__ __forceinline__ void lds_wait0_q(f32x4 &a, f32x4 &b, f32x4 &c, f32x4 &d, f32x4 &q, f32x4 &h) {
+    asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(a), "+v"(b), "+v"(c), "+v"(d), "+v"(q), "+v"(h));
+}
+
+// One value-free record: the offsets of row slots 2m and 2m + 1 arrive in one ds_read_b128 (Q_m); the rows of slot J + 1 and
+// the offsets two slots ahead go out before the FMAs of slot J, as in compute_record.
+__device__ __forceinline__ void compute_record_vf(const int ISSUE, f32x2 (&acc)[RW][2][2], const uint32_t pa, const uint32_t rowbase,
+                                                  f32x4 &hn, uint32_t gq64, int next_panel, uint32_t lds0, int pbn,
+                                                  const float *__restrict__ B, int64_t ldb, int64_t ncols, int fcol0, uint32_t lane_off,
+                                                  int wave) {
+    f32x4 qa, qb, xa0, xa1, xa2, xa3, xb0, xb1, xb2, xb3;
+    qb = f32x4{0.f, 0.f, 0.f, 0.f};
+    lds_read_b128<0>(qa, pa);
+    lds_wait1(qa);
+    asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(qa));
+    {
+        const uint32_t a0 = rowbase + (uint32_t)__float_as_int(qa.x), a1 = rowbase + (uint32_t)__float_as_int(qa.y);
+        lds_read_b128<0>(xa0, a0);
+        lds_read_b128<256>(xa1, a0);
+        lds_read_b128<0>(xa2, a1);
+        lds_read_b128<256>(xa3, a1);
+    }
+    // step J: X = rows of slot J (landed at the wait), NQ = the register holding slot J + 1's offsets (.xy for odd J + 1, .zw for
+    // even), FQ = the register Q_(J/2+1) is read into (even J).  The last even step reads the next record's header instead.
+#define PGCN_STRIP_VF_STEP(J, NQ, FQ, XA0, XA1, XA2, XA3, XB0, XB1, XB2, XB3)                                      \
+    {                                                                                                             \
+        lds_wait0_q(XA0, XA1, XA2, XA3, NQ, hn);                                                                  \
+        if ((J) + 1 < RW) {                                                                                       \
+            const uint32_t a0 = rowbase + (uint32_t)__float_as_int(((J) & 1) ? NQ.x : NQ.z);                      \
+            const uint32_t a1 = rowbase + (uint32_t)__float_as_int(((J) & 1) ? NQ.y : NQ.w);                      \
+            lds_read_b128<0>(XB0, a0);                                                                            \
+            lds_read_b128<256>(XB1, a0);                                                                          \
+            lds_read_b128<0>(XB2, a1);                                                                            \
+            lds_read_b128<256>(XB3, a1);                                                                          \
+            if (((J) & 1) == 0) {                                                                                 \
+                if ((J) + 2 < RW) { lds_read_b128<(((J) / 2 + 1) * 16)>(FQ, pa); }                                \
+                else { lds_read_b128<kWaveRecVF>(hn, pa - gq64); }                                                \
+            }                                                                                                     \
+        }                                                                                                         \
+        if (((J) & 1) == 0)                                                                                       \
+            issue_panel_if<(J) / 2>(ISSUE, next_panel, lds0, pbn, B, ldb, ncols, fcol0, lane_off, wave);         \
+        __builtin_amdgcn_sched_barrier(0);                                                                        \
+        fma_chunk(acc[(J)][0], 1.f, XA0);                                                                         \
+        fma_chunk(acc[(J)][1], 1.f, XA1);                                                                         \
+        fma_chunk(acc[(J)][0], 1.f, XA2);                                                                         \
+        fma_chunk(acc[(J)][1], 1.f, XA3);                                                                         \
+        __builtin_amdgcn_sched_barrier(0);                                                                        \
+    }
+    PGCN_STRIP_VF_STEP(0, qa, qb, xa0, xa1, xa2, xa3, xb0, xb1, xb2, xb3)
+    PGCN_STRIP_VF_STEP(1, qb, qa, xb0, xb1, xb2, xb3, xa0, xa1, xa2, xa3)
+    PGCN_STRIP_VF_STEP(2, qb, qa, xa0, xa1, xa2, xa3, xb0, xb1, xb2, xb3)
+    PGCN_STRIP_VF_STEP(3, qa, qb, xb0, xb1, xb2, xb3, xa0, xa1, xa2, xa3)
+    PGCN_STRIP_VF_STEP(4, qa, qb, xa0, xa1, xa2, xa3, xb0, xb1, xb2, xb3)
+    PGCN_STRIP_VF_STEP(5, qb, qa, xb0, xb1, xb2, xb3, xa0, xa1, xa2, xa3)
+    PGCN_STRIP_VF_STEP(6, qb, qa, xa0, xa1, xa2, xa3, xb0, xb1, xb2, xb3)
+    PGCN_STRIP_VF_STEP(7, qa, qb, xb0, xb1, xb2, xb3, xa0, xa1, xa2, xa3)
+#undef PGCN_STRIP_VF_STEP
+}
+
+// The thread's four chunks of the panel in buffer `pb` (copied by issue_panel*: row q * 32 + t / 32) times c of their rows.
+__device__ __forceinline__ void scale_own_panel(char *smem, int pb, int panel, const float *__restrict__ col_scale, int64_t ncols) {
+    int64_t col0 = (int64_t)panel * TC;
+    col0 = col0 + TC <= ncols ? col0 : ncols - TC;
+    float s[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) s[q] = col_scale[col0 + q * 32 + (threadIdx.x >> 5)];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        float4 *p = reinterpret_cast<float4 *>(smem + pb * kPanelBytes + (q * kThreads + threadIdx.x) * 16);
+        float4 x = *p;
+        x.x *= s[q]; x.y *= s[q]; x.z *= s[q]; x.w *= s[q];
+        *p = x;
+    }
+}
+
+// work / recs: as spmm_strip_kernel; offs: int32 [nrec][1024] value-free records; col_scale (NULL: ones) [ncols];
+// row_scale (NULL: ones): r of the matrix rows, readable at rows 512 * tile row + 0 .. 511 of every piece.
+__global__ __launch_bounds__(kThreads, 1) void spmm_strip_vf_kernel(
+    const int4 *__restrict__ work, const int4 *__restrict__ recs, const int32_t *__restrict__ offs,
+    const float *__restrict__ row_scale, const float *__restrict__ col_scale,
+    const float *__restrict__ B, int64_t ldb, int64_t ncols, int32_t f, float *__restrict__ partial) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    int4 wk = work[blockIdx.x];
+    wk.x = __builtin_amdgcn_readfirstlane(wk.x); wk.y = __builtin_amdgcn_readfirstlane(wk.y);
+    wk.z = __builtin_amdgcn_readfirstlane(wk.z); wk.w = __builtin_amdgcn_readfirstlane(wk.w);
+    const int fcol0 = blockIdx.y * 128;
+    const int fw = min(128, f - fcol0);
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int s = lane & 15;
+    const int gq = (lane >> 4);
+    const int g = wave * 4 + gq;
+    const uint32_t lds0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) char *)smem;
+    const int c4s = min((int)(threadIdx.x & 31), (fw >> 2) - 1);
+    const uint32_t lane_off = (uint32_t)(((int64_t)(threadIdx.x >> 5) * ldb + c4s * 4) * 4);
+
+    f32x2 acc[RW][2][2];
+#pragma unroll
+    for (int j = 0; j < RW; ++j) acc[j][0][0] = acc[j][0][1] = acc[j][1][0] = acc[j][1][1] = f32x2{0.f, 0.f};
+    if (threadIdx.x < 64)
+        *reinterpret_cast<float4 *>(smem + (threadIdx.x >> 5) * kPanelBytes + kPadOff + (threadIdx.x & 31) * 16) =
+            make_float4(0.f, 0.f, 0.f, 0.f);
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+
+    const int k0 = wk.y, k1 = wk.z;
+    int4 rc = recs[k0];
+    rc.x = __builtin_amdgcn_readfirstlane(rc.x); rc.y = __builtin_amdgcn_readfirstlane(rc.y);
+    rc.z = __builtin_amdgcn_readfirstlane(rc.z);
+    int pb = 0, pbn = 0;
+    issue_panel<0, 4>(rc.x, lds0, 0, B, ldb, ncols, fcol0, lane_off, wave);
+    issue_offs(offs, recs, k0, k1, 0, smem, wave, lane);
+    bool have_next = k0 + 1 < k1;
+    if (have_next) issue_offs(offs, recs, k0 + 1, k1, 1, smem, wave, lane);
+    int after_panel = have_next ? 2 : 1;
+    bool issued1 = false, issued2 = false;
+    int slot = 0, in_run = 0;
+    for (int k = k0; k < k1; ++k) {
+        int nafter = (issued2 ? 4 : 0) + (issued1 ? 4 : 0) + (k + 1 < k1 ? 1 : 0);
+        if (k + 2 < k1) {
+            int s2 = slot + 2; s2 = s2 >= kRing ? s2 - kRing : s2;
+            issue_offs(offs, recs, k + 2, k1, s2, smem, wave, lane);
+            after_panel = after_panel < 2 ? after_panel + 1 : 2;
+            ++nafter;
+        }
+        wait_vm_dyn(nafter);
+        if (!(rc.y & 1)) in_run = 0;
+        switch (in_run) {
+            case 0: __builtin_amdgcn_s_setprio(3); break;
+            case 1: __builtin_amdgcn_s_setprio(2); break;
+            case 2: __builtin_amdgcn_s_setprio(1); break;
+            default: __builtin_amdgcn_s_setprio(0); break;
+        }
+        ++in_run;
+        bool cur_issued = false;
+        if (!(rc.y & 1)) {
+            wait_vm_dyn(after_panel);      // this thread's copies of the panel have landed ...
+            if (col_scale) {               // ... it scales exactly those bytes, then the one barrier publishes them
+                scale_own_panel(smem, pbn, rc.x, col_scale, ncols);
+                asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+            }
+            __builtin_amdgcn_s_barrier();
+            pb = pbn;
+            if (rc.z >= 0) {
+                pbn = pb ^ 1;
+                cur_issued = true;
+                after_panel = 0;
+            }
+        }
+        const uint32_t pa = lds0 + kOffRing + (wave * kRing + slot) * kSlotBytesVF + gq * kGroupVF;
+        const uint32_t rowbase = lds0 + pb * kPanelBytes + s * 16;
+        f32x4 hn = f32x4{0.f, 0.f, 0.f, 0.f};
+        compute_record_vf(cur_issued ? 1 : 0, acc, pa, rowbase, hn, gq * kGroupVF, rc.z, lds0, pbn, B, ldb, ncols, fcol0, lane_off, wave);
+        rc.x = __builtin_amdgcn_readfirstlane(__float_as_int(hn.x));
+        rc.y = __builtin_amdgcn_readfirstlane(__float_as_int(hn.y));
+        rc.z = __builtin_amdgcn_readfirstlane(__float_as_int(hn.z));
+        issued2 = issued1;
+        issued1 = cur_issued;
+        slot = slot + 1 >= kRing ? 0 : slot + 1;
+    }
+    __builtin_amdgcn_s_setprio(0);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+#pragma unroll
+    for (int j = 0; j < RW; ++j) {
+        const float r = row_scale ? row_scale[(int64_t)wk.x * TRS + j * NG + g] : 1.f;
+        float *o = partial + ((int64_t)wk.w + j * NG + g) * f + fcol0 + s * 4;
+        const float4 lo = make_float4(acc[j][0][0].x * r, acc[j][0][0].y * r, acc[j][0][1].x * r, acc[j][0][1].y * r);
+        const float4 hi = make_float4(acc[j][1][0].x * r, acc[j][1][0].y * r, acc[j][1][1].x * r, acc[j][1][1].y * r);
+        if (s * 4 < fw) *reinterpret_cast<float4 *>(o) = lo;
+        if (64 + s * 4 < fw) *reinterpret_cast<float4 *>(o + 64) = hi;
+    }
+}
+
+// Any width / alignment, value-free records: operands read straight from global memory (correctness path).
+__global__ __launch_bounds__(kThreads, 1) void spmm_strip_vf_generic_kernel(
+    const int4 *__restrict__ work, const int4 *__restrict__ recs, const int32_t *__restrict__ offs,
+    const float *__restrict__ row_scale, const float *__restrict__ col_scale,
+    const float *__restrict__ B, int64_t ldb, int64_t ncols, int32_t f, float *__restrict__ partial) {
+    const int4 wk = work[blockIdx.x];
+    const int sub = threadIdx.x & 31;
+    const int g32 = threadIdx.x >> 5;
+    const int fcol = blockIdx.y * 32 + sub;
+    const bool fact = fcol < f;
+    float acc[16];
+#pragma unroll
+    for (int i = 0; i < 16; ++i) acc[i] = 0.f;
+    for (int k = wk.y; k < wk.z; ++k) {
+        int64_t col0 = (int64_t)recs[k].x * TC;
+        col0 = col0 + TC <= ncols ? col0 : ncols - TC;
+        const int32_t *pr = offs + (int64_t)k * TRS * SB;
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+            const int row = i * 32 + g32;
+            const int32_t *pp = pr + ((row % NG) * RW + row / NG) * SB;
+#pragma unroll
+            for (int u = 0; u < SB; ++u) {
+                const int32_t off = pp[u];
+                if (off != kPadOff && fact) {
+                    const int64_t c = col0 + (off >> 9);
+                    const float x = col_scale ? B[c * ldb + fcol] * col_scale[c] : B[c * ldb + fcol];
+                    acc[i] = fmaf(1.f, x, acc[i]);
+                }
+            }
+        }
+    }
+    if (fact) {
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+            const int row = i * 32 + g32;
+            const float r = row_scale ? row_scale[(int64_t)wk.x * TRS + row] : 1.f;
+            partial[((int64_t)wk.w + row) * f + fcol] = acc[i] * r;
+        }
+    }
+}
+
 // Any width / alignment: same records, operands read straight from global memory, one feature per
 // lane (blockIdx.y walks the features 32 at a time).  Correctness path, not a fast path.
 __global__ __launch_bounds__(kThreads, 1) void spmm_strip_generic_kernel(
@@ -413,6 +648,40 @@ extern "C" int pgcn_spmm_strip_f32(const int32_t *work, int64_t nwork, const int
     } else {
         hipLaunchKernelGGL(spmm_strip_generic_kernel, dim3((unsigned)nwork, (unsigned)((f + 31) / 32)), dim3(kThreads), 0, s,
                            w4, r4, pairs, B, ldb, ncols, f, partial_ws);
+    }
+    PGCN_HIP_CHECK(hipGetLastError());
+    return PGCN_OK;
+}
+
+extern "C" int pgcn_spmm_strip_vf_f32(const int32_t *work, int64_t nwork, const int32_t *recs, const int32_t *offs,
+                                       const float *row_scale, const float *col_scale, const float *B, int64_t ldb, int64_t ncols,
+                                       int32_t f, float *partial_ws, int64_t partial_ws_elems, int64_t nslots_total,
+                                       pgcn_stream_t stream) {
+    if (nwork < 0 || f <= 0 || ldb < f || ncols < TC) return pgcn_set_error(PGCN_EINVAL, "pgcn_spmm_strip_vf_f32: bad sizes (a panel is 128 rows of B)");
+    if (nwork == 0) return PGCN_OK;
+    if (!work || !recs || !offs || !B || !partial_ws)
+        return pgcn_set_error(PGCN_EINVAL, "pgcn_spmm_strip_vf_f32: null pointer");
+    if (partial_ws_elems < nslots_total * (int64_t)f)
+        return pgcn_set_error(PGCN_ENOMEM, "pgcn_spmm_strip_vf_f32: partial work-space too small");
+    if (nwork > 0x7fffffffLL) return pgcn_set_error(PGCN_EINVAL, "pgcn_spmm_strip_vf_f32: work list too long");
+    if ((uintptr_t)offs % 16 || (uintptr_t)recs % 16 || (uintptr_t)work % 16)
+        return pgcn_set_error(PGCN_EINVAL, "pgcn_spmm_strip_vf_f32: work / recs / offs must be 16-byte aligned");
+    hipStream_t s = (hipStream_t)stream;
+    const int4 *w4 = reinterpret_cast<const int4 *>(work);
+    const int4 *r4 = reinterpret_cast<const int4 *>(recs);
+    const bool vec = f % 4 == 0 && ldb % 4 == 0 && (uintptr_t)B % 16 == 0 && (uintptr_t)partial_ws % 16 == 0;
+    if (vec) {
+        static PgcnPerDeviceOnce once;
+        if (int rc = once.run([&]() -> int {
+                PGCN_HIP_CHECK(hipFuncSetAttribute((const void *)spmm_strip_vf_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, kSmemVF));
+                return PGCN_OK;
+            }))
+            return rc;
+        hipLaunchKernelGGL(spmm_strip_vf_kernel, dim3((unsigned)nwork, (unsigned)((f + 127) / 128)), dim3(kThreads), kSmemVF, s,
+                           w4, r4, offs, row_scale, col_scale, B, ldb, ncols, f, partial_ws);
+    } else {
+        hipLaunchKernelGGL(spmm_strip_vf_generic_kernel, dim3((unsigned)nwork, (unsigned)((f + 31) / 32)), dim3(kThreads), 0, s,
+                           w4, r4, offs, row_scale, col_scale, B, ldb, ncols, f, partial_ws);
     }
     PGCN_HIP_CHECK(hipGetLastError());
     return PGCN_OK;

@@ -60,6 +60,10 @@ class DeviceCSR:
     slice_off: Optional[torch.Tensor] = None   # int32 [nrows, 9] offsets of a row's 8 col % 8 slices (XCD-sliced storage)
     rows_all: Optional[torch.Tensor] = None    # int32 all rows, longest first
     launch_cache: dict = None                 # bound C-ABI calls per (ldb, ldc, f, accumulate)
+    values: str = "stored"                    # stored | pattern | factored (value-free: val is None, partition.HostCSR.value_free)
+    row_scale: Optional[torch.Tensor] = None  # fp32 [nrows] r of a factored structure (CSR row numbering)
+    col_scale: Optional[torch.Tensor] = None  # fp32 [ncols] c of it
+    slot_row: Optional[torch.Tensor] = None   # int32 [nslots] CSR row of every gather slot (the row scale of a partial sum)
 
     def __post_init__(self):
         if self.launch_cache is None:
@@ -115,9 +119,12 @@ class DeviceGatBlocks:
 class DeviceStrip:
     work: torch.Tensor
     rec: torch.Tensor
-    pairs: torch.Tensor
+    pairs: Optional[torch.Tensor]               # None: value-free records (offs, pgcn_spmm_strip_vf_f32)
     npieces: int
     nnz: int
+    offs: Optional[torch.Tensor] = None         # int32 [nrec, 1024] offset slots of value-free records
+    row_scale: Optional[torch.Tensor] = None    # fp32, padded to the last tile's 512 rows (factored structures)
+    col_scale: Optional[torch.Tensor] = None    # fp32 [ncols]
 
 
 @dataclass
@@ -227,13 +234,27 @@ class HipKernels:
             nrows=csr.nrows, ncols=csr.ncols, nnz=csr.nnz,
             rowptr=csr.rowptr.to(dev, torch.int64).contiguous(),
             col=csr.col.to(dev, torch.int32).contiguous(),
-            val=None if pattern_only else csr.val.to(dev, torch.float32).contiguous(),
+            val=None if (pattern_only or csr.val is None) else csr.val.to(dev, torch.float32).contiguous(),
             row_map=None if csr.row_map is None else csr.row_map.to(dev, torch.int32).contiguous())
+        if csr.val is None and not pattern_only:        # value-free: a pattern, or a pattern with a row and a column scale
+            d.values = "pattern" if csr.row_scale is None else "factored"
+            if csr.row_scale is not None:
+                d.row_scale = csr.row_scale.to(dev, torch.float32).contiguous()
+                d.col_scale = csr.col_scale.to(dev, torch.float32).contiguous()
         if tasks is not None:
             d.tasks = torch.from_numpy(tasks).to(dev)
             d.fix = torch.from_numpy(fix).to(dev) if fix.shape[0] else None
             d.ntasks, d.nfix, d.nslots = tasks.shape[0], fix.shape[0], nslots
             d.nslices, d.seg = csr.nslices if sc is not None else 1, seg
+            if d.row_scale is not None and nslots > 0:   # the row of every slot: a task scales its partial sum before writing it
+                fx = torch.from_numpy(np.ascontiguousarray(fix)).to(torch.int64)
+                srow = torch.zeros(nslots, dtype=torch.int32)
+                if fx.shape[0]:
+                    cnt = fx[:, 2]
+                    start = torch.repeat_interleave(torch.cumsum(cnt, 0) - cnt, cnt)
+                    pos = torch.repeat_interleave(fx[:, 1], cnt) + torch.arange(int(cnt.sum()), dtype=torch.int64) - start
+                    srow[pos] = torch.repeat_interleave(fx[:, 0], cnt).to(torch.int32)
+                d.slot_row = srow.to(dev)
         d.nslots_total = d.nslots
         if csr.core is not None or csr.strip is not None or csr.dense3 is not None:
             self._attach_core(d, csr, fix if tasks is not None else None)
@@ -251,8 +272,15 @@ class HipKernels:
         if hs is not None:
             work = hs.work.clone()
             work[:, 3] += ns_rem                                   # strip slots live behind the gather slots
-            d.strip = DeviceStrip(work.to(dev).contiguous(), hs.rec.to(dev).contiguous(), hs.pairs.to(dev).contiguous(),
-                                  hs.npieces, hs.nnz)
+            d.strip = DeviceStrip(work.to(dev).contiguous(), hs.rec.to(dev).contiguous(),
+                                  None if hs.pairs is None else hs.pairs.to(dev).contiguous(), hs.npieces, hs.nnz)
+            if hs.pairs is None:                # value-free records: the offsets and the structure's scales
+                d.strip.offs = hs.offs.to(dev, torch.int32).contiguous()
+                if csr.row_scale is not None:   # (the kernel scales all 512 rows of a tile's partial block: padded with zeros)
+                    rs = torch.zeros(max(csr.nrows, (int(hs.work[:, 0].max()) + 1) * STRIP_TR), dtype=torch.float32, device=dev)
+                    rs[:csr.nrows] = csr.row_scale.to(dev, torch.float32)
+                    d.strip.row_scale = rs
+                    d.strip.col_scale = csr.col_scale.to(dev, torch.float32).contiguous()
             w64 = work.cpu().to(torch.int64)
             pieces.append(torch.stack([w64[:, 0] * STRIP_TR, torch.full_like(w64[:, 0], STRIP_TR), w64[:, 3]], 1))
             ns_strip = hs.nslots
@@ -364,8 +392,15 @@ class HipKernels:
             rows = A.row_map.long()
             return lambda B, C: C.index_fill_(0, rows, 0.0)
         rowptr, col, val, rmap = A.rowptr.data_ptr(), A.col.data_ptr(), _ptr(A.val), _ptr(A.row_map)
+        # factored value-free structures: the scaled gather entry points (weights col_scale[col], rows scaled by r_i where written)
+        rsc, csc, srow = _ptr(A.row_scale), _ptr(A.col_scale), _ptr(A.slot_row)
         if A.tasks is None and A.row_map is None and A.core is None and A.strip is None and A.dense3 is None:
             nrows = A.nrows
+            if csc is not None:
+                def simple_scaled(B, C):
+                    check(lib.pgcn_spmm_csr_scaled_f32(rowptr, col, rsc, csc, nrows, B.data_ptr(), ldb, C.data_ptr(), ldc, f,
+                                                       flags, stream()), "pgcn_spmm_csr_scaled_f32")
+                return simple_scaled
             def simple(B, C):
                 check(lib.pgcn_spmm_csr_f32(rowptr, col, val, nrows, B.data_ptr(), ldb, C.data_ptr(), ldc, f,
                                             flags, stream()), "pgcn_spmm_csr_f32")
@@ -381,6 +416,12 @@ class HipKernels:
         nslots = A.nslots
         if A.core is None and A.strip is None and A.dense3 is None:
             fix, nfix = _ptr(A.fix), A.nfix
+            if csc is not None:
+                def planned_scaled(B, C):
+                    check(lib.pgcn_spmm_csr_plan_scaled_f32(rowptr, col, rsc, csc, srow, tasks, ntasks, seg, nslices, fix, nfix, rmap,
+                                                            B.data_ptr(), ldb, C.data_ptr(), ldc, f, ws, ws_n, nslots, flags,
+                                                            stream()), "pgcn_spmm_csr_plan_scaled_f32")
+                return planned_scaled
             def planned(B, C):
                 check(lib.pgcn_spmm_csr_plan_f32(rowptr, col, val, tasks, ntasks, seg, nslices, fix, nfix, rmap,
                                                  B.data_ptr(), ldb, C.data_ptr(), ldc, f, ws, ws_n, nslots, flags,
@@ -399,7 +440,8 @@ class HipKernels:
                                                       d3.panel_list.data_ptr(), d3.npanels, d3.image.data_ptr(), d3.image.numel())
             pat3, pr3, rs3, cs3 = _ptr(d3.bits), _ptr(d3.piece_row0), _ptr(d3.row_scale), _ptr(d3.col_scale)
         if st is not None:
-            sw, sn, srec, spairs = st.work.data_ptr(), st.npieces, st.rec.data_ptr(), st.pairs.data_ptr()
+            sw, sn, srec, spairs = st.work.data_ptr(), st.npieces, st.rec.data_ptr(), _ptr(st.pairs)
+            soffs, srs, scs = _ptr(st.offs), _ptr(st.row_scale), _ptr(st.col_scale)
         if co is not None:
             cw, cn, ctp, ctb, cso, ccol, cval = (co.work.data_ptr(), co.npieces, co.tile_panel.data_ptr(),
                                                  co.tile_base.data_ptr(), co.seg_off.data_ptr(), co.ccol.data_ptr(),
@@ -426,9 +468,15 @@ class HipKernels:
         dev, nside = self.device, len(lanes) - 1
 
         def launch(name, b, c, s):
-            if name == "gather":
+            if name == "gather" and csc is not None:
+                check(lib.pgcn_spmm_csr_plan_scaled_f32(rowptr, col, rsc, csc, srow, tasks, ntasks, seg, nslices, None, 0, rmap, b,
+                                                        ldb, c, ldc, f, ws, ws_n, nslots, gflags, s), "pgcn_spmm_csr_plan_scaled_f32")
+            elif name == "gather":
                 check(lib.pgcn_spmm_csr_plan_f32(rowptr, col, val, tasks, ntasks, seg, nslices, None, 0, rmap, b, ldb,
                                                  c, ldc, f, ws, ws_n, nslots, gflags, s), "pgcn_spmm_csr_plan_f32")
+            elif name == "strip" and soffs is not None:
+                check(lib.pgcn_spmm_strip_vf_f32(sw, sn, srec, soffs, srs, scs, b, ldb, ncols, f, ws, ws_n, nst, s),
+                      "pgcn_spmm_strip_vf_f32")
             elif name == "strip":
                 check(lib.pgcn_spmm_strip_f32(sw, sn, srec, spairs, b, ldb, ncols, f, ws, ws_n, nst, s), "pgcn_spmm_strip_f32")
             elif pat3 is not None:

@@ -32,12 +32,14 @@ from .tuning import T as _T       # every tunable below comes from tuning.Tuning
 
 @dataclass
 class HostCSR:
-    """A CSR block as torch tensors (any device): int64 rowptr, int32 col, fp32 val."""
+    """A CSR block as torch tensors (any device): int64 rowptr, int32 col, fp32 val.
+    Value-free blocks (``val`` None: tuning.value_free or build_partition*(normalize=)): entry (i, j) is row_scale[i] col_scale[j]
+    (both None: a 0/1 pattern), i in CSR row numbering (before row_map); no fp32 value array at any level."""
     nrows: int
     ncols: int
     rowptr: torch.Tensor
     col: torch.Tensor
-    val: torch.Tensor
+    val: Optional[torch.Tensor]
     row_map: Optional[torch.Tensor] = None  # compact row r -> output row row_map[r] (int32)
     nslices: int = 1                          # entries of a row are grouped by col % nslices ...
     slice_cnt: Optional[torch.Tensor] = None  # int32 [nrows, nslices*ngroups] entries per (row, slice, group)
@@ -46,6 +48,18 @@ class HostCSR:
     row_flags: Optional[torch.Tensor] = None  # uint8 [nrows]: row also receives core partial sums
     strip: Optional["HostStrip"] = None       # entries of 512 x 128 strip tiles (LDS-staged, async pipeline)
     dense3: Optional["HostDense3"] = None     # the densest 512 x 128 blocks, stored dense for the bf16 matrix cores (three planes)
+    row_scale: Optional[torch.Tensor] = None  # fp32 [nrows] r of a value-free factored block (CSR row numbering)
+    col_scale: Optional[torch.Tensor] = None  # fp32 [ncols] c of it
+
+    @property
+    def value_free(self) -> bool:
+        return self.val is None
+
+    def values_at(self, r: torch.Tensor, c: torch.Tensor) -> torch.Tensor:
+        """fp32 values of a value-free block at CSR rows ``r`` / columns ``c``: fl32(r_i c_j), 1 for a pattern."""
+        if self.row_scale is None:
+            return torch.ones(r.numel(), dtype=torch.float32, device=r.device)
+        return self.row_scale[r.to(torch.int64)] * self.col_scale[c.to(torch.int64)]
 
     @property
     def nnz(self) -> int:
@@ -58,17 +72,23 @@ class HostCSR:
         """(row, col, val) of the whole block, core included (tests / checker only)."""
         counts = self.rowptr[1:] - self.rowptr[:-1]
         r = torch.repeat_interleave(torch.arange(self.nrows, device=self.col.device), counts)
+        c, v = self.col.to(torch.int64), self.val
+        if v is None:
+            v = self.values_at(r, c)
         if self.row_map is not None:
             r = self.row_map.to(torch.int64)[r]
-        c, v = self.col.to(torch.int64), self.val
         if self.core is not None:
             cr, cc, cv = self.core.to_coo()
             r, c, v = torch.cat([r, cr]), torch.cat([c, cc]), torch.cat([v, cv])
         if self.strip is not None:
             sr, sc, sv = self.strip.to_coo()
+            if self.val is None:              # (strips exist only without row compaction)
+                sv = self.values_at(sr, sc)
             r, c, v = torch.cat([r, sr]), torch.cat([c, sc]), torch.cat([v, sv])
         if self.dense3 is not None:
             dr, dc, dv = self.dense3.coo
+            if self.val is None:              # (blocks exist only without row compaction: dr is the CSR row)
+                dv = self.values_at(dr, dc)
             r, c, v = torch.cat([r, dr]), torch.cat([c, dc]), torch.cat([v, dv])
         return r, c, v
 
@@ -144,6 +164,8 @@ DENSE3_PIECE = _T.dense3_piece
 DENSE3_MIN_BLOCKS = _T.dense3_min_blocks
 DENSE3_VALUES = _T.dense3_values          # stored | pattern | factored: what the blocks of a structure may drop (classify_values)
 DENSE3_TAU_IMPLICIT = _T.dense3_tau_implicit
+VALUE_FREE = _T.value_free                 # pattern / factored structures keep no value array (HostCSR.val None)
+NORMALIZE = ("sym",)                      # build_partition*(normalize=): on-the-fly normalisations of a pattern input
 DENSE3_BR = 512    # rows per block (= STRIP_TR: the two tall-tile paths share the row blocking and the 512-row slot blocks)
 
 
@@ -255,6 +277,28 @@ def degree_scales(count: torch.Tensor) -> torch.Tensor:
     """fl32(d^-1/2) of a count vector (the candidate scales of D^-1/2 P D^-1/2; 1 where the count is 0)."""
     d = count.to(torch.float64)
     return torch.where(d > 0, 1.0 / torch.sqrt(torch.clamp(d, min=1.0)), torch.ones_like(d)).to(torch.float32)
+
+
+def _check_normalize(normalize: Optional[str]) -> None:
+    if normalize is not None and normalize not in NORMALIZE:
+        raise ValueError("normalize must be one of %s or None, got %r" % ("|".join(NORMALIZE), normalize))
+
+
+def sym_pattern(row: torch.Tensor, col: torch.Tensor, val: Optional[torch.Tensor], n: int, rows: Optional[torch.Tensor] = None):
+    """(row, col) int64 of the pattern of A + I that preprocess/GrB-GNN-IDG.py:45-55 builds from a 0/1 input: the distinct stored
+    positions, stored diagonal entries dropped, the diagonal of ``rows`` (default: all n) added; sorted by (row, col).  The input must
+    be a pattern: a stored value other than 1 raises ValueError instead of being silently reinterpreted."""
+    if val is not None and val.numel():
+        bad = int((val.to(torch.float32) != 1.0).sum())
+        if bad:
+            raise ValueError("normalize='sym' normalises a 0/1 pattern, but %d of the %d stored values are not 1 (a weighted input "
+                             "is not reinterpreted: normalise it offline or pass it without normalize=)" % (bad, val.numel()))
+    row, col = row.to(torch.int64), col.to(torch.int64)
+    keys = torch.unique(row * n + col)
+    keys = keys[keys // n != keys % n]
+    d = torch.arange(n, dtype=torch.int64, device=row.device) if rows is None else rows.to(device=row.device, dtype=torch.int64)
+    keys = torch.unique(torch.cat([keys, d * n + d]))
+    return keys // n, keys % n
 
 
 def dense3_bits(i: torch.Tensor, k: torch.Tensor, bl: torch.Tensor, nblocks: int) -> torch.Tensor:
@@ -408,10 +452,16 @@ class HostStrip:
     work: torch.Tensor      # int32 [npieces, 4] {tile row, first record, one-past-last record, first slot (local)}
     rec: torch.Tensor       # int32 [nrec, 4]    {panel, flags (1 = panel of the previous record), panel of the piece's
     #                         NEXT run of records (-1: none; only on records that start a run), layer}
-    pairs: torch.Tensor     # int32 [nrec, STRIP_REC, 2]
+    pairs: Optional[torch.Tensor]  # int32 [nrec, STRIP_REC, 2] (None: value-free records, ``offs``)
     rec_tile_row: torch.Tensor   # int32 [nrec] (host bookkeeping)
     rec_nnz: torch.Tensor        # int32 [nrec] stored entries per record (host bookkeeping)
     nnz_: int
+    offs: Optional[torch.Tensor] = None   # int32 [nrec, STRIP_REC] the offset slots alone (value-free structures, pgcn_spmm_strip_vf_f32)
+
+    def drop_values(self) -> None:
+        """Value-free records: keep the offset slots (4 KB per record), drop the values."""
+        self.offs = self.pairs[:, :, 0].contiguous()
+        self.pairs = None
 
     @property
     def nnz(self) -> int:
@@ -427,15 +477,18 @@ class HostStrip:
 
     def to_coo(self):
         """(row, col, val) of the stored entries, decoded from the device layout (tests / checker)."""
-        dev = self.pairs.device
+        offs = self.pairs[:, :, 0] if self.pairs is not None else self.offs
+        dev = offs.device
         nrec = int(self.rec.shape[0])
-        off = self.pairs[:, :, 0].reshape(-1).to(torch.int64)
+        off = offs.reshape(-1).to(torch.int64)
         real = off != STRIP_PAD_OFF
         pos = torch.arange(nrec * STRIP_REC, device=dev)[real]
         rec_id, inrec = pos // STRIP_REC, pos % STRIP_REC
         g, j = inrec // (STRIP_RW * STRIP_B), (inrec // STRIP_B) % STRIP_RW
         rows = self.rec_tile_row.to(torch.int64)[rec_id] * STRIP_TR + j * STRIP_NG + g
         cols = strip_panel_base(self.rec[:, 0].to(torch.int64)[rec_id], self.ncols) + off[real] // 512
+        if self.pairs is None:
+            return rows, cols, torch.ones(rows.numel(), dtype=torch.float32, device=dev)
         vals = self.pairs[:, :, 1].reshape(-1)[real].contiguous().view(torch.float32)
         return rows, cols, vals
 
@@ -627,15 +680,33 @@ def csr_from_coo(r: torch.Tensor, c: torch.Tensor, v: torch.Tensor, nrows: int, 
                  slice_bounds: Optional[torch.Tensor] = None,
                  strip: Optional[bool] = None, strip_min: Optional[int] = None, dense3_tau: Optional[float] = None,
                  row_bands: Optional[torch.Tensor] = None, col_bands: Optional[torch.Tensor] = None,
-                 scales=None, dense3_values: Optional[str] = None) -> HostCSR:
+                 scales=None, dense3_values: Optional[str] = None, values: Optional[str] = None,
+                 value_free: Optional[bool] = None) -> HostCSR:
     """Sort by (row, slice, col) and build CSR.  Duplicate entries are kept as
     separate stored entries (an uncoalesced COO sums them, PGCN.py:63).  With ``core``
     the entries of dense 128 x 128 tiles are split off into a HostCore (LDS-tiled kernel).
     slice of a column = col % nslices, or -- with ``slice_bounds`` (nslices+1 ascending column
     bounds) -- the RANGE it falls in: then the rows of the dense operand that one XCD gathers are
     contiguous in memory instead of 4 KB apart.  ``scales`` = (row [nrows], col [ncols]): candidate factors of the values in this
-    structure's numbering and ``dense3_values`` the mode (default tuning.dense3_values): ``classify_values``."""
+    structure's numbering and ``dense3_values`` the mode (default tuning.dense3_values): ``classify_values``.
+    ``value_free`` (default tuning.value_free): a structure classified pattern / factored keeps no values (``HostCSR.val`` None,
+    duplicate positions merged) and sends its strip and LDS-core entries to the gather tasks.  ``values`` ('pattern' | 'factored'
+    with ``scales``): the class is known by construction (build_partition*(normalize=)) -- value-free, no classification."""
     dev = r.device
+    vclass = None                        # (class, row scale, col scale) of the whole structure, classified at most once
+    if values is not None:
+        if values not in ("pattern", "factored") or (values == "factored" and (scales is None or scales[0] is None)):
+            raise ValueError("values must be pattern, or factored with scales, got %r" % (values,))
+        vclass = (values, None, None) if values == "pattern" else \
+            (values, scales[0].to(device=dev, dtype=torch.float32)[:nrows].contiguous(),
+             scales[1].to(device=dev, dtype=torch.float32)[:ncols].contiguous())
+    elif (VALUE_FREE if value_free is None else value_free) and r.numel():
+        vclass = classify_values(r, c, v, nrows, ncols, dense3_values, scales)
+    vfree = vclass is not None and vclass[0] != "stored"
+    if vfree and r.numel():              # one entry per position: the value of a position is r_i c_j, whatever was stored there
+        key = torch.unique(r.to(torch.int64) * max(ncols, 1) + c.to(torch.int64))
+        r, c = key // max(ncols, 1), key % max(ncols, 1)
+        v = torch.ones(key.numel(), dtype=torch.float32, device=dev)
     if slice_bounds is not None:
         slice_bounds = torch.as_tensor(slice_bounds, dtype=torch.int64, device=dev)
         nslices = int(slice_bounds.numel()) - 1
@@ -656,11 +727,11 @@ def csr_from_coo(r: torch.Tensor, c: torch.Tensor, v: torch.Tensor, nrows: int, 
         # the bf16 three-plane blocks (512 x 128); dense3_tau > 1 switches them off
         use3 = DENSE3_ON if dense3_tau is None else dense3_tau <= 1.0
         if use3 and ncols >= CORE_TC:
-            vmode, rs, cs = classify_values(r, c, v, nrows, ncols, dense3_values, scales)
+            vmode, rs, cs = vclass if vclass is not None else classify_values(r, c, v, nrows, ncols, dense3_values, scales)
             keep3, hdense3 = split_dense3(r, c, v, nrows, ncols, dense3_tau, row_bands, col_bands, values=vmode, scales=(rs, cs))
             if keep3 is not None:
                 r, c, v = r[keep3], c[keep3], v[keep3]
-        keep, hcore = split_core(r, c, v, nrows, ncols, 2.0 if use_strip else tau, emax)
+        keep, hcore = (None, None) if (vfree and not use_strip) else split_core(r, c, v, nrows, ncols, 2.0 if use_strip else tau, emax)
         if keep is not None:
             r, c, v = r[keep], c[keep], v[keep]
         if use_strip:
@@ -668,13 +739,16 @@ def csr_from_coo(r: torch.Tensor, c: torch.Tensor, v: torch.Tensor, nrows: int, 
             if hstrip is not None and strip_min is None and hstrip.rec.shape[0] < STRIP_MIN_RECORDS:
                 # a small block (a rank's shard of an 8-way run): too few records to fill 256 one-workgroup CUs with
                 # pieces long enough to amortise their 512-row partial block -- the finer-grained 128 x 128 LDS core
-                # (two workgroups per CU, 128-row pieces) serves it better (measured: tools/rank_probe.py, r02)
+                # (two workgroups per CU, 128-row pieces) serves it better (measured: tools/rank_probe.py, r02).
+                # (Value-free structures have no LDS-core variant: those entries stay with the gather tasks.)
                 skeep = hstrip = None
-                ckeep, hcore = split_core(r, c, v, nrows, ncols, tau, emax)
+                ckeep, hcore = (None, None) if vfree else split_core(r, c, v, nrows, ncols, tau, emax)
                 if ckeep is not None and hcore is not None:
                     r, c, v = r[ckeep], c[ckeep], v[ckeep]
             if skeep is not None:
                 r, c, v = r[skeep], c[skeep], v[skeep]
+            if hstrip is not None and vfree:
+                hstrip.drop_values()     # 4-byte offset slots, 4 KB per record (pgcn_spmm_strip_vf_f32)
         tiled = sum(h.nnz for h in (hcore, hstrip, hdense3) if h is not None)
         if tiled and tau is None and strip_min is None and dense3_tau is None and \
                 (tiled < CORE_MIN_NNZ or tiled < CORE_MIN_FRAC * r0.numel()):
@@ -699,10 +773,13 @@ def csr_from_coo(r: torch.Tensor, c: torch.Tensor, v: torch.Tensor, nrows: int, 
         order = torch.argsort(key, stable=True)
         r, c, v = r[order], c[order], v[order]
     row_map = None
+    rscale, cscale = (vclass[1], vclass[2]) if vfree else (None, None)
     if compact_rows:
         rows_u, r = torch.unique(r, return_inverse=True)  # sorted
         row_map = rows_u.to(torch.int32)
         nrows = int(rows_u.numel())
+        if rscale is not None:
+            rscale = rscale[rows_u].contiguous()
     counts = torch.bincount(r.to(torch.int64), minlength=nrows) if r.numel() else \
         torch.zeros(nrows, dtype=torch.int64, device=dev)
     rowptr = torch.zeros(nrows + 1, dtype=torch.int64, device=dev)
@@ -720,20 +797,23 @@ def csr_from_coo(r: torch.Tensor, c: torch.Tensor, v: torch.Tensor, nrows: int, 
     else:
         G = 1
     return HostCSR(nrows, ncols, rowptr, c.to(torch.int32).contiguous(),
-                   v.to(torch.float32).contiguous(), row_map, S, slice_cnt, G, hcore, row_flags, hstrip, hdense3)
+                   None if vfree else v.to(torch.float32).contiguous(), row_map, S, slice_cnt, G, hcore, row_flags, hstrip, hdense3,
+                   rscale, cscale)
 
 
 def csr_from_scipy(A, nslices: Optional[int] = None, core: bool = False, tau: float = None,
                    emax: int = None, ngroups: Optional[int] = None,
                    strip: Optional[bool] = None, strip_min: Optional[int] = None, dense3_tau: Optional[float] = None,
-                   scales=None, dense3_values: Optional[str] = None) -> HostCSR:
+                   scales=None, dense3_values: Optional[str] = None, values: Optional[str] = None,
+                   value_free: Optional[bool] = None) -> HostCSR:
     """Convenience for tests / tools: a scipy sparse matrix -> HostCSR (optionally sliced)."""
     import numpy as np
     A = A.tocoo()
     return csr_from_coo(torch.from_numpy(A.row.astype(np.int64)), torch.from_numpy(A.col.astype(np.int64)),
                         torch.from_numpy(A.data.astype(np.float32)), A.shape[0], A.shape[1],
                         nslices=nslices, core=core, tau=tau, emax=emax, ngroups=ngroups,
-                        strip=strip, strip_min=strip_min, dense3_tau=dense3_tau, scales=scales, dense3_values=dense3_values)
+                        strip=strip, strip_min=strip_min, dense3_tau=dense3_tau, scales=scales, dense3_values=dense3_values,
+                        values=values, value_free=value_free)
 
 
 @dataclass
@@ -854,17 +934,27 @@ def _offsets(owner: torch.Tensor, size: int) -> List[int]:
 def build_partition(row: torch.Tensor, col: torch.Tensor, val: torch.Tensor, n: int,
                     partvec: torch.Tensor, rank: int, size: int,
                     with_transpose: bool = True, rounds: Optional[int] = None,
-                    degree_sort: Optional[bool] = None, scales=None) -> Partition:
+                    degree_sort: Optional[bool] = None, scales=None, normalize: Optional[str] = None) -> Partition:
     """Build rank ``rank``'s pieces from the GLOBAL COO (row, col, val) of A.
 
     Mirrors the reference, where every rank parses the whole matrix (PGCN.py:171)
     and filters its rows (:55-59) and boundary sets (:41-45).
     ``scales`` = (r, c), global n-vectors: candidate factors a_ij = r_i c_j of the values (tuning.dense3_values=factored); by
-    default there the inverse square roots of the global row and column counts (D^-1/2 P D^-1/2)."""
+    default there the inverse square roots of the global row and column counts (D^-1/2 P D^-1/2).
+    ``normalize="sym"``: train on A_hat = D_r^-1/2 (A + I) D_c^-1/2 of the PATTERN (row, col) -- the arithmetic of
+    preprocess/GrB-GNN-IDG.py:45-68 (``sym_pattern``; r_i, c_j = fl32 of the row / column counts of A + I to the -1/2,
+    ``degree_scales``) without its offline pass; every structure is value-free (``scales`` is ignored)."""
     dev = row.device
+    _check_normalize(normalize)
     row = row.to(torch.int64)
     col = col.to(torch.int64)
     part = _check_partvec(partvec, n, size, dev)
+    values = None
+    if normalize is not None:
+        row, col = sym_pattern(row, col, val, n)
+        val = torch.ones(row.numel(), dtype=torch.float32, device=dev)
+        scales = (degree_scales(torch.bincount(row, minlength=n)), degree_scales(torch.bincount(col, minlength=n)))
+        values = "factored"
     # One global degree ranking, identical on every rank (every rank scans the whole COO, as in
     # the reference): grank[v] = position of vertex v in the order (degree descending, id
     # ascending).  It numbers the local rows AND orders the boundary-row slabs, so that the
@@ -884,7 +974,7 @@ def build_partition(row: torch.Tensor, col: torch.Tensor, val: torch.Tensor, n: 
     if scales is None and DENSE3_VALUES == "factored":
         scales = (degree_scales(torch.bincount(row, minlength=n)), degree_scales(torch.bincount(col, minlength=n)))
     p = _finish_partition(row[mine], col[mine], val[mine], n, part, rank, size, gorder, grank, suniq,
-                          int(row.numel()), with_transpose, rounds, order_info.get("_bands"), scales)
+                          int(row.numel()), with_transpose, rounds, order_info.get("_bands"), scales, values)
     p.order_info = order_info
     return p
 
@@ -892,7 +982,8 @@ def build_partition(row: torch.Tensor, col: torch.Tensor, val: torch.Tensor, n: 
 def build_partition_local(row: torch.Tensor, col: torch.Tensor, val: torch.Tensor, n: int,
                           partvec: torch.Tensor, rank: int, size: int, group=None,
                           with_transpose: bool = True, rounds: Optional[int] = None,
-                          degree_sort: Optional[bool] = None, emulate: Optional[dict] = None, scales=None) -> Partition:
+                          degree_sort: Optional[bool] = None, emulate: Optional[dict] = None, scales=None,
+                          normalize: Optional[str] = None) -> Partition:
     """The same Partition from rank ``rank``'s OWN ROWS only (global coordinates, e.g.
     ``ingest.load_partition``): no rank ever holds the whole matrix.  Two small collectives over
     ``torch.distributed`` replace the global scan: an all-reduce of the n-vector of degrees (for
@@ -905,14 +996,35 @@ def build_partition_local(row: torch.Tensor, col: torch.Tensor, val: torch.Tenso
     count) degrees, and ``emulate["nnz_global"]``; the rows the peers need from this rank are derived from this
     rank's own entries, which is exact for a SYMMETRIC pattern (peer q holds (c, r) for every (r, c) held here).
     ``scales``: as in ``build_partition``; the default candidates (factored mode) come from the global degrees: (gdeg / 2)^-1/2, the
-    row count of a symmetric pattern."""
+    row count of a symmetric pattern.
+    ``normalize="sym"``: as in ``build_partition``.  Every rank turns its own rows into rows of A + I; the row counts are local and the
+    global column counts come from one more all-reduce of an n-vector (under ``emulate``: ``emulate["col_count"]``, the column counts
+    of A + I, default ``gdeg // 2`` = those of a symmetric pattern; ``gdeg`` and ``nnz_global`` are then those of A + I too)."""
     import torch.distributed as dist
     dev = row.device
+    _check_normalize(normalize)
     row = row.to(torch.int64)
     col = col.to(torch.int64)
     part = _check_partvec(partvec, n, size, dev)
     if row.numel() and not bool((part[row] == rank).all()):
         raise ValueError("build_partition_local takes the rows owned by this rank only")
+    values = None
+    if normalize is not None:
+        if emulate is None and size > 1:
+            # every rank learns whether ANY rank holds a weighted entry and raises together: a rank that raised alone would leave
+            # its peers waiting in the collectives below
+            bad = torch.tensor([int((val.to(torch.float32) != 1.0).sum()) if val.numel() else 0], dtype=torch.int64)
+            if dist.get_backend(group) != "gloo":
+                bad = bad.to(dev)
+            dist.all_reduce(bad, group=group)
+            if int(bad.item()):
+                raise ValueError("normalize='sym' normalises a 0/1 pattern, but %d stored values (over all ranks) are not 1 (a "
+                                 "weighted input is not reinterpreted: normalise it offline or pass it without normalize=)"
+                                 % int(bad.item()))
+        row, col = sym_pattern(row, col, val, n, rows=torch.nonzero(part == rank).reshape(-1))
+        val = torch.ones(row.numel(), dtype=torch.float32, device=dev)
+        values = "factored"
+        rscale = degree_scales(torch.bincount(row, minlength=n))             # a row's entries all live on its owner
 
     if emulate is not None:
         part_ = _check_partvec(partvec, n, size, dev)
@@ -920,7 +1032,11 @@ def build_partition_local(row: torch.Tensor, col: torch.Tensor, val: torch.Tenso
         if row64.numel() and not bool((part_[row64] == rank).all()):
             raise ValueError("build_partition_local takes the rows owned by this rank only")
         gdeg = torch.as_tensor(emulate["gdeg"]).to(device=dev, dtype=torch.int64)
-        if scales is None and DENSE3_VALUES == "factored":
+        if normalize is not None:
+            ccount = emulate.get("col_count")
+            ccount = gdeg // 2 if ccount is None else torch.as_tensor(ccount).to(device=dev, dtype=torch.int64)
+            scales = (rscale, degree_scales(ccount))
+        elif scales is None and DENSE3_VALUES == "factored":
             scales = (degree_scales(gdeg // 2),) * 2
         if not (DEGREE_SORT if degree_sort is None else degree_sort) or n <= 1:
             gdeg = None
@@ -929,7 +1045,7 @@ def build_partition_local(row: torch.Tensor, col: torch.Tensor, val: torch.Tenso
         away = pcol != rank
         suniq = torch.unique(pcol[away] * n + grank[row64[away]])            # (requesting rank, degree rank of MY row)
         return _finish_partition(row64, col64, val, n, part_, rank, size, gorder, grank, suniq,
-                                 int(emulate.get("nnz_global", row64.numel())), with_transpose, rounds, scales=scales)
+                                 int(emulate.get("nnz_global", row64.numel())), with_transpose, rounds, scales=scales, values=values)
     gloo = size > 1 and dist.get_backend(group) == "gloo"
 
     def to_wire(t):            # gloo moves host tensors; nccl (= RCCL) device tensors
@@ -947,6 +1063,13 @@ def build_partition_local(row: torch.Tensor, col: torch.Tensor, val: torch.Tenso
             w = to_wire(gdeg)
             dist.all_reduce(w, group=group)
             gdeg = w.to(dev)
+    if normalize is not None:
+        ccount = torch.bincount(col, minlength=n)
+        if size > 1:
+            w = to_wire(ccount)
+            dist.all_reduce(w, group=group)
+            ccount = w.to(dev)
+        scales = (rscale, degree_scales(ccount))
     gorder, grank = _degree_order(gdeg, n, dev)
     # what I need from every owner (my halo sets), as degree ranks; the owners receive the lists
     pcol = part[col]
@@ -965,7 +1088,7 @@ def build_partition_local(row: torch.Tensor, col: torch.Tensor, val: torch.Tenso
     if scales is None and DENSE3_VALUES == "factored" and gdeg is not None:
         scales = (degree_scales(gdeg // 2),) * 2
     return _finish_partition(row, col, val, n, part, rank, size, gorder, grank, suniq, int(nnz_global),
-                             with_transpose, rounds, scales=scales)
+                             with_transpose, rounds, scales=scales, values=values)
 
 
 def _check_partvec(partvec, n: int, size: int, dev) -> torch.Tensor:
@@ -1094,10 +1217,12 @@ def _coo_is_symmetric(r: torch.Tensor, c: torch.Tensor, v: torch.Tensor, n: int)
 
 def _finish_partition(row_m: torch.Tensor, col_m: torch.Tensor, val_m: torch.Tensor, n: int, part: torch.Tensor,
                       rank: int, size: int, gorder: torch.Tensor, grank: torch.Tensor, suniq: torch.Tensor,
-                      nnz_global: int, with_transpose: bool, rounds: Optional[int], bands_global=None, scales=None) -> Partition:
+                      nnz_global: int, with_transpose: bool, rounds: Optional[int], bands_global=None, scales=None,
+                      values: Optional[str] = None) -> Partition:
     """Everything after the two global facts (degree ranking, who needs which of my rows):
     ``row_m/col_m/val_m`` are this rank's entries in GLOBAL coordinates; ``scales`` = (r, c) global candidate factors of the values,
-    handed to every structure in its own numbering (a transpose swaps them)."""
+    handed to every structure in its own numbering (a transpose swaps them: diag(c) P^T diag(r)).  ``values`` ('factored': the
+    normalised pattern of ``normalize=``): every structure but the unpack pattern is value-free by construction."""
     dev = row_m.device
     owned = torch.nonzero(part == rank).reshape(-1)
     n_p = int(owned.numel())
@@ -1127,7 +1252,7 @@ def _finish_partition(row_m: torch.Tensor, col_m: torch.Tensor, val_m: torch.Ten
     def sc(rv, rix, cv, cix):      # (row scale, col scale) of a structure: global vectors picked by its row / column numbering
         return None if rg is None else (rv[rix], cv[cix])
     A_loc = csr_from_coo(r[loc], g2l[c[loc]], v[loc], n_p, n_p, core=CORE_ON, row_bands=lbands, col_bands=lbands,
-                         scales=sc(rg, owned, cg, owned))
+                         scales=sc(rg, owned, cg, owned), values=values)
     R = max(1, (EXCHANGE_ROUNDS if rounds is None else rounds)) if size > 1 else 1
     # halo columns: per owner the reference's recv_map[q] as a SET (PGCN.py:44-48), ordered
     # (round, owner, degree rank)
@@ -1149,22 +1274,23 @@ def _finish_partition(row_m: torch.Tensor, col_m: torch.Tensor, val_m: torch.Ten
     for k in range(R if size > 1 else 0):
         sel = ecol_round == k
         A_halo.append(csr_from_coo(rr[sel], hcol[sel], vv[sel], n_p, n_halo, compact_rows=not halo_core,
-                                   core=halo_core, scales=sc(rg, owned, cg, halo_global)))
+                                   core=halo_core, scales=sc(rg, owned, cg, halo_global), values=values))
         if with_transpose:
             base, end = round_recv_off[k][0], round_recv_off[k][size]
             A_halo_T.append(csr_from_coo(hcol[sel] - base, rr[sel], vv[sel], end - base, n_p, core=halo_core,
-                                         scales=sc(cg, halo_global[base:end], rg, owned)))
+                                         scales=sc(cg, halo_global[base:end], rg, owned), values=values))
 
     A_loc_T = None
     if with_transpose:
         rl, cl, vl = r[loc], g2l[c[loc]], v[loc]
-        if size == 1 and _coo_is_symmetric(rl, cl, vl, n_p):
+        if size == 1 and _coo_is_symmetric(rl, cl, vl, n_p) and \
+                (A_loc.row_scale is None or torch.equal(A_loc.row_scale, A_loc.col_scale)):
             # one rank, A = A^T entry for entry (every A_hat of `preprocess`; checked bit for bit, not assumed): the transposed block IS
             # the block -- half the structure memory and half of the "partition built" stage (r06)
             A_loc_T = A_loc
         else:
             A_loc_T = csr_from_coo(cl, rl, vl, n_p, n_p, core=CORE_ON, row_bands=lbands, col_bands=lbands,
-                                   scales=sc(cg, owned, rg, owned))
+                                   scales=sc(cg, owned, rg, owned), values=values)
 
     # rows of mine that other ranks need, in the peers' slab order (round, target rank, degree rank)
     s_order, _, round_send_off = _round_major(suniq // n, size, R)
@@ -1180,7 +1306,7 @@ def _finish_partition(row_m: torch.Tensor, col_m: torch.Tensor, val_m: torch.Ten
         a, b = round_send_off[k][0], round_send_off[k][size]
         unpack.append(csr_from_coo(send_idx[a:b].to(torch.int64), pos_all[a:b],
                                    torch.ones(b - a, dtype=torch.float32, device=dev), n_p,
-                                   int(send_idx.numel()), compact_rows=True, nslices=1))
+                                   int(send_idx.numel()), compact_rows=True, nslices=1, value_free=False))
 
     return Partition(n=n, rank=rank, size=size, owned=owned, A_loc=A_loc, A_halo=A_halo,
                      A_loc_T=A_loc_T, A_halo_T=A_halo_T, send_idx=send_idx.contiguous(), unpack=unpack,

@@ -52,6 +52,10 @@ class Tuning:
     dense3_tau_implicit: float = 0.08  # block fill threshold of the value-free structures (at most the stored threshold of their grid): no value
                                      # stream and three MFMAs per step move the break-even down.  Sweep, factored, ms per epoch: R-MAT 0.20 9.82,
                                      # 0.12 9.70, 0.08 9.60 (stored blocks 10.13-10.18); SBM (banded) 0.12 16.64, 0.08 16.58, 0.05 16.99 (stored 17.04-17.08)
+    value_free: bool = False         # structures that dense3_values classifies as pattern / factored keep NO fp32 value array at any
+                                     # level: the gather tasks weigh an entry by col_scale[col] and scale their rows by r_i, the blocks keep
+                                     # their bits, and their strip / LDS-core entries go to the gather tasks (partition.csr_from_coo).
+                                     # Structures built with build_partition*(normalize="sym") are value-free whatever this says
     dense3_piece: int = 0            # blocks per piece (0 = adaptive: one round of 256 pieces, between 1 and 8 blocks)
     dense3_min_blocks: int = 400     # matrices with fewer such blocks leave their entries to the strips / the LDS core (a shard of an
                                      # 8-way run: two more launches and 512-row partial blocks for a few dozen blocks: rank 0 of 8,
