@@ -60,6 +60,42 @@ int64_t pgcn_linear_weight_grad_ws_elems(void);
 int pgcn_linear_weight_grad_f32(const float *Gm, int64_t ldg, const float *X, int64_t ldx, int64_t n, int32_t fout, int32_t fin,
                                 float *dW, int64_t lddw, float *ws, int64_t ws_elems, void *stream);
 
+/* ---- dropout fused into the same kernels (source: <package>/gemm/pgcn_dense.hip; the keep function: <package>/gemm/pgcn_dropout.h,
+ * restated in integer numpy by <package>/dropout.py) --------------------------------------------------------------------------------
+ * Beyond the reference (which has no dropout); opt-in through PGCN(dropout=...) / `--dropout P`, selected by tuning.dropout_fused.
+ * Whether element (row, column) of a layer's output survives is a PURE FUNCTION of (seed, step, layer, global row id, column), all
+ * arithmetic modulo 2^64 / 2^32:
+ *   mix64(z):  z += 0x9E3779B97F4A7C15; z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9; z = (z ^ z >> 27) * 0x94D049BB133111EB; return z ^ z >> 31
+ *   key   = mix64(mix64(seed) ^ (step * 0x9E3779B97F4A7C15) ^ ((2 layer + 1) * 0xD6E8FEB86659FD93))
+ *   fmix32(h): h ^= h >> 16; h *= 0x85EBCA6B; h ^= h >> 13; h *= 0xC2B2AE35; h ^= h >> 16
+ *   a = fmix32(col ^ lo32(key));  b = fmix32(a ^ lo32(row id) ^ hi32(key));  u = row id < 2^32 ? b : fmix32(b ^ (row id >> 32))
+ *   keep  = u >= thr,  thr = min(floor(p 2^32 + 1/2), 2^32 - 1) for a drop probability p in [0, 1)
+ *   scale = (float)(1.0 / (1.0 - thr / 2^32))      (double division, rounded to float once)
+ * so P ranks under any part vector draw the masks of one rank, element for element.  `step` is a DEVICE pointer to one int64, read when
+ * the kernel starts: a captured graph that also increments it draws new masks at every replay.  row_ids: the global id of every row
+ * (int64, n of them, 8-byte aligned), or NULL: the row index.  Conventions as above: 0; -2 refused, nothing launched; -1 errors
+ * (pgcn_dense_last_error()); never allocate, never synchronise. */
+
+/* 1: the pgcn_dropout_* entry points below exist (a binding checks this before it resolves them) */
+int pgcn_dropout_abi_version(void);
+
+/* Y (n x fout, ldy) = keep ? max(X . W^T, 0) * scale : 0;  mask (optional, n x ceil(fout / 32) words): bit = (Y > 0) = sign AND keep --
+ * all the backward needs.  The product and its operands as pgcn_linear_relu_f32 (bit-identical where kept, before the scaling). */
+int pgcn_dropout_linear_relu_f32(const float *X, int64_t ldx, int64_t n, int32_t fin, const float *W, int64_t ldw, int32_t fout,
+                                 float *Y, int64_t ldy, uint32_t *mask, const int64_t *row_ids, uint64_t seed, const int64_t *step,
+                                 uint32_t layer, uint32_t thr, void *stream);
+
+/* Gm = mask ? G * scale : 0 (written when Gm != NULL; Gm == G allowed; mask NULL: Gm = G * scale),  dX (n x fin, lddx) = Gm . W.
+ * Operands as pgcn_linear_relu_grad_input_f32; nothing is regenerated: the mask of the forward above already holds the keep bits.
+ * The weight gradient takes Gm unchanged (pgcn_linear_weight_grad_f32). */
+int pgcn_dropout_grad_input_f32(const float *G, int64_t ldg, const uint32_t *mask, float scale, float *Gm, int64_t ldgm, int64_t n,
+                                int32_t fout, const float *W, int64_t ldw, int32_t fin, float *dX, int64_t lddx, void *stream);
+
+/* words (n x ceil(N / 32)) = the keep bits alone in the sign-mask layout (bits of columns >= N are 0): for layers whose product
+ * stays a library GEMM (widths above 128, unaligned operands) */
+int pgcn_dropout_keep_words_u32(const int64_t *row_ids, int64_t n, int32_t N, uint64_t seed, const int64_t *step, uint32_t layer,
+                                uint32_t thr, uint32_t *words, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

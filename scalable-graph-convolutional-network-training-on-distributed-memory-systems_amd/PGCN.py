@@ -34,6 +34,7 @@ import torch.multiprocessing as mp
 import torch.nn as nn
 import torch.nn.functional as F
 
+from . import dropout as _dropout
 from . import engine as _engine
 from . import ingest as _ingest
 from . import kernels as _kernels
@@ -313,6 +314,21 @@ def bind_dense_library(path):
         L.pgcn_linear_weight_grad_ws_elems.restype = ctypes.c_int64
         L.pgcn_linear_weight_grad_ws_elems.argtypes = []
         L.pgcn_wgrad_last_error.restype = ctypes.c_char_p
+    # dropout fused into the same kernels: only a library that vouches for them (an older build, or the host emulation, has neither
+    # the version function nor the entry points -- the layers then take the unfused route)
+    L.pgcn_has_dropout = False
+    if hasattr(L, "pgcn_dropout_abi_version"):
+        L.pgcn_dropout_abi_version.restype = ctypes.c_int
+        L.pgcn_dropout_abi_version.argtypes = []
+        if L.pgcn_dropout_abi_version() == 1:
+            u32, u64, f32 = ctypes.c_uint32, ctypes.c_uint64, ctypes.c_float
+            L.pgcn_dropout_linear_relu_f32.restype = ctypes.c_int
+            L.pgcn_dropout_linear_relu_f32.argtypes = [ptr, i64, i64, i32, ptr, i64, i32, ptr, i64, ptr, ptr, u64, ptr, u32, u32, ptr]
+            L.pgcn_dropout_grad_input_f32.restype = ctypes.c_int
+            L.pgcn_dropout_grad_input_f32.argtypes = [ptr, i64, ptr, f32, ptr, i64, i64, i32, ptr, i64, i32, ptr, i64, ptr]
+            L.pgcn_dropout_keep_words_u32.restype = ctypes.c_int
+            L.pgcn_dropout_keep_words_u32.argtypes = [ptr, i64, i32, u64, ptr, u32, u32, ptr, ptr]
+            L.pgcn_has_dropout = True
     return L
 
 
@@ -418,6 +434,81 @@ def weight_grad_call(L, gm, x, stream):
     if rc != 0:
         raise RuntimeError("pgcn_linear_weight_grad_f32: %s" % L.pgcn_wgrad_last_error().decode())
     return dw
+
+
+def _row_ids_ok(row_ids, n):
+    return row_ids is None or (row_ids.dtype is torch.int64 and row_ids.dim() == 1 and row_ids.shape[0] == n and row_ids.is_contiguous())
+
+
+def dropout_linear_relu_call(L, x, weight, row_ids, seed, step, layer, thr, stream):
+    """(y, mask) = (keep ? relu(x . weight^T) * scale : 0, sign AND keep words) through pgcn_dropout_linear_relu_f32 of `L`, or None when
+    the library has no such entry point / does not take the operands (-2).  row_ids: int64 [n] global ids (None: the row index);
+    step: one-element int64 tensor on x's device, read by the kernel."""
+    if not getattr(L, "pgcn_has_dropout", False) or x.dim() != 2 or weight.dim() != 2 or x.shape[1] != weight.shape[1] or \
+            x.stride(1) != 1 or weight.stride(1) != 1 or not (x.dtype is weight.dtype is torch.float32) or \
+            not _row_ids_ok(row_ids, x.shape[0]) or step.dtype is not torch.int64 or step.numel() != 1:
+        return None
+    y = torch.empty((x.shape[0], weight.shape[0]), dtype=torch.float32, device=x.device)
+    mask = torch.empty((x.shape[0], mask_words(weight.shape[0])), dtype=torch.int32, device=x.device)
+    rc = L.pgcn_dropout_linear_relu_f32(x.data_ptr(), x.stride(0), x.shape[0], x.shape[1], weight.data_ptr(), weight.stride(0),
+                                        weight.shape[0], y.data_ptr(), y.stride(0), mask.data_ptr(),
+                                        row_ids.data_ptr() if row_ids is not None else None, int(seed), step.data_ptr(), int(layer),
+                                        int(thr), stream)
+    if rc == -2:
+        return None
+    if rc != 0:
+        raise RuntimeError("pgcn_dropout_linear_relu_f32: %s" % L.pgcn_dense_last_error().decode())
+    return y, mask
+
+
+def dropout_grad_input_call(L, g, mask, scale, weight, stream, gm=None):
+    """(gm, gx) = (mask ? g * scale : 0, gm . weight) through pgcn_dropout_grad_input_f32 of `L`, or None.  gm: where to write it
+    (g itself is allowed), default a new tensor."""
+    if not getattr(L, "pgcn_has_dropout", False) or g.dim() != 2 or weight.dim() != 2 or g.shape[1] != weight.shape[0] or \
+            g.stride(1) != 1 or weight.stride(1) != 1 or not (g.dtype is weight.dtype is torch.float32):
+        return None
+    if mask is not None and (mask.shape != (g.shape[0], mask_words(g.shape[1])) or mask.dtype is not torch.int32 or
+                             not mask.is_contiguous()):
+        return None
+    if gm is None:
+        gm = torch.empty_like(g, memory_format=torch.contiguous_format)
+    gx = torch.empty((g.shape[0], weight.shape[1]), dtype=torch.float32, device=g.device)
+    rc = L.pgcn_dropout_grad_input_f32(g.data_ptr(), g.stride(0), mask.data_ptr() if mask is not None else None, float(scale),
+                                       gm.data_ptr(), gm.stride(0), g.shape[0], g.shape[1], weight.data_ptr(), weight.stride(0),
+                                       weight.shape[1], gx.data_ptr(), gx.stride(0), stream)
+    if rc == -2:
+        return None
+    if rc != 0:
+        raise RuntimeError("pgcn_dropout_grad_input_f32: %s" % L.pgcn_dense_last_error().decode())
+    return gm, gx
+
+
+def dropout_keep_words_call(L, row_ids, n, width, seed, step, layer, thr, stream):
+    """The keep bits alone as int32 words in the sign-mask layout (pgcn_dropout_keep_words_u32), on step's device."""
+    if not getattr(L, "pgcn_has_dropout", False):
+        raise RuntimeError("libpgcn_gemm.so has no pgcn_dropout_* entry points: rebuild it (gemm/build.sh)")
+    if not _row_ids_ok(row_ids, n):
+        raise ValueError("row_ids: contiguous int64 [n]")
+    words = torch.empty((n, mask_words(width)), dtype=torch.int32, device=step.device)
+    rc = L.pgcn_dropout_keep_words_u32(row_ids.data_ptr() if row_ids is not None else None, n, width, int(seed), step.data_ptr(),
+                                       int(layer), int(thr), words.data_ptr(), stream)
+    if rc != 0:
+        raise RuntimeError("pgcn_dropout_keep_words_u32: %s" % L.pgcn_dense_last_error().decode())
+    return words
+
+
+def dropout_linear_relu_fused(x, weight, row_ids, seed, step, layer, thr):
+    """relu(x . weight^T) with dropout in the kernel's epilogue on the current stream -> (y, sign AND keep words), or None."""
+    if not _dense_operand_ok(x, weight):
+        return None
+    return dropout_linear_relu_call(_dense_lib(), x, weight, row_ids, seed, step, layer, thr, _dense_stream(x))
+
+
+def dropout_grad_input_fused(g, mask, scale, weight):
+    """(mask ? g * scale : 0, that . weight) in one pass, or None."""
+    if not _dense_operand_ok(g, weight):
+        return None
+    return dropout_grad_input_call(_dense_lib(), g, mask, scale, weight, _dense_stream(g))
 
 
 def linear_relu_fused(x, weight, relu=True, want_mask=False):
@@ -532,6 +623,60 @@ class _LinearReluNoBias(torch.autograd.Function):
             if gw is None:
                 gw = _LinearNoBias.weight_grad(g, x)
         return gx, gw
+
+
+class _LinearReluDropoutNoBias(torch.autograd.Function):
+    """dropout(relu(x . W^T)) as one autograd node: y = keep ? relu(x . W^T) / (1 - p) : 0 with keep a pure function of
+    (seed, step, layer, GLOBAL row id, column) (dropout.py, gemm/pgcn_dropout.h).  Fused (tuning.dropout_fused, tuning.dense_fused >= 2):
+    ONE forward kernel that leaves y and the words sign AND keep, the backward reads nothing but those words.  Otherwise (CPU
+    tensors, widths above 128, unaligned rows, a library without the entry points): the library product + clamp + the keep words
+    (kernel on the GPU, dropout.keep_mask on the CPU) + torch.where -- the same results up to the product's rounding."""
+
+    @staticmethod
+    def forward(ctx, x, weight, row_ids, state, layer, thr, scale):
+        from .tuning import T as _T
+        level = _dense_fused_level()
+        out = None
+        if int(_T.dropout_fused) and level >= 2:
+            out = dropout_linear_relu_fused(x, weight, row_ids, state.seed, state.step, layer, thr)
+        if out is not None:
+            y, mask = out
+        else:
+            y = mm_nt(x, weight).clamp_min_(0.0)
+            if y.is_cuda:
+                words = dropout_keep_words_call(_dense_lib(), row_ids, y.shape[0], y.shape[1], state.seed, state.step, layer, thr,
+                                                _dense_stream(y))
+                keep = unpack_sign_mask(words, y.shape[1])
+            else:
+                ids = row_ids if row_ids is not None else torch.arange(y.shape[0])
+                keep = _dropout.keep_mask(state.seed, state.host_step(), layer, ids, y.shape[1], thr)
+            y = torch.where(keep, y * scale, torch.zeros((), dtype=y.dtype, device=y.device))
+            # (y is zero where dropped: its sign mask is sign AND keep)
+            mask = sign_mask_call(_dense_lib(), y, _dense_stream(y)) if y.is_cuda else _dropout.pack_words(y > 0)
+        ctx.scale = scale
+        ctx.save_for_backward(x, weight, mask)
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        from .tuning import T as _T
+        x, weight, mask = ctx.saved_tensors
+        gx = gw = None
+        level = _dense_fused_level()
+        both = None
+        if int(_T.dropout_fused) and level >= 2:
+            both = dropout_grad_input_fused(g.contiguous(), mask, ctx.scale, weight)
+        if both is not None:
+            g, gx = both
+        else:
+            g = torch.where(unpack_sign_mask(mask, g.shape[1]), g * ctx.scale, torch.zeros((), dtype=g.dtype, device=g.device))
+            if ctx.needs_input_grad[0]:
+                gx = mm_nn(g, weight)
+        if ctx.needs_input_grad[1]:
+            gw = weight_grad_fused(g, x) if level >= 3 else None
+            if gw is None:
+                gw = _LinearNoBias.weight_grad(g, x)
+        return gx, gw, None, None, None, None, None
 
 
 _gemm_tuned_shapes = set()
@@ -656,17 +801,36 @@ def tune_dense_gemms(n_rows, f, dev, fout=None):
 
 
 class PGCN(nn.Module):
-    """PGCN.py:136-148."""
+    """PGCN.py:136-148.
 
-    def __init__(self, A, in_features, out_features):
+    ``dropout`` (beyond the reference, opt-in): in training mode the layer's OUTPUT is dropped with this probability and the
+    survivors scaled by 1 / (1 - p), inside the dense kernel.  A model drops the output of every layer except the last --
+    equivalently the input of layers 2 .. L: Kipf & Welling's placement minus the raw input features (``run`` builds it that
+    way).  ``layer``: the layer's index, part of the hash; ``state``: the dropout.DropoutState the model's layers share (seed,
+    device-resident step).  The keep bit of an element depends on the GLOBAL id of its row (``A.part.owned``), so P ranks
+    under any part vector reproduce one rank.  ``eval()`` or ``dropout=0``: the path without dropout, bit for bit."""
+
+    def __init__(self, A, in_features, out_features, dropout=0.0, layer=0, state=None):
         super(PGCN, self).__init__()
         self.linear = nn.Linear(in_features, out_features, bias=False)
         self.A = A
         self.send_map = send_map
         self.recv_map = recv_map
+        self.dropout = float(dropout)
+        self.dropout_thr, self.dropout_scale = _dropout.threshold(dropout)
+        self.layer = int(layer)
+        self.state = state
+        self._row_ids = None
 
     def forward(self, H):
         H = PSpMM.apply(self.A, H)
+        if self.training and self.dropout > 0.0:
+            if self.state is None:
+                self.state = _dropout.DropoutState(0, H.device)
+            if self._row_ids is None or self._row_ids.device != H.device:      # global ids in local row order, once
+                self._row_ids = self.A.part.owned.to(device=H.device, dtype=torch.int64).contiguous()
+            return _LinearReluDropoutNoBias.apply(H, self.linear.weight, self._row_ids, self.state, self.layer, self.dropout_thr,
+                                                  self.dropout_scale)
         return _LinearReluNoBias.apply(H, self.linear.weight)      # == F.relu(self.linear(H)), PGCN.py:146-147
 
 
@@ -756,9 +920,11 @@ def local_loss(logits, labels, n_global):
     return (nll_sum + missing * math.log(f)) / n_global
 
 
-def run(rank, size, nlayers, nfeatures, path_A, path_partvec, backend, normalize=None):
+def run(rank, size, nlayers, nfeatures, path_A, path_partvec, backend, normalize=None, dropout=0.0, dropout_seed=0):
     """PGCN.py:162-238.  ``normalize="sym"``: train on D_r^-1/2 (A + I) D_c^-1/2 of the pattern of ``path_A``, built on the fly
-    (partition.build_partition) instead of by the offline pass preprocess/GrB-GNN-IDG.py."""
+    (partition.build_partition) instead of by the offline pass preprocess/GrB-GNN-IDG.py.  ``dropout`` > 0: the output of every
+    layer but the last is dropped with that probability (class PGCN), masks from (``dropout_seed``, step, layer, global row,
+    column); the step advances once per training step on every rank alike."""
     global myrank, world_size, send_map, recv_map, device, X, recv_buffers, send_buffers, stats
     myrank = rank
     world_size = size
@@ -817,7 +983,14 @@ def run(rank, size, nlayers, nfeatures, path_A, path_partvec, backend, normalize
     labels = owned % nfeatures            # PGCN.py:192
 
     tune_dense_gemms(A.part.n_local, nfeatures, device)
-    model = nn.Sequential(*[PGCN(A, nfeatures, nfeatures) for _ in range(nlayers)])
+    _dropout.threshold(dropout)
+    if dropout > 0.0:
+        state = _dropout.DropoutState(dropout_seed, device)
+        model = nn.Sequential(*[PGCN(A, nfeatures, nfeatures, dropout=dropout if i < nlayers - 1 else 0.0, layer=i, state=state)
+                                for i in range(nlayers)])
+    else:
+        state = None
+        model = nn.Sequential(*[PGCN(A, nfeatures, nfeatures) for _ in range(nlayers)])
     model = model.to(device)
     initiliaze_parameters(model)
     optimizer = torch.optim.Adam(model.parameters(), lr=1e-3)
@@ -829,6 +1002,8 @@ def run(rank, size, nlayers, nfeatures, path_A, path_partvec, backend, normalize
         loss.backward()
         average_gradients(model)
         optimizer.step()
+        if state is not None:
+            state.advance()
 
     if device.type == "cuda":
         torch.cuda.synchronize(device)
@@ -841,6 +1016,8 @@ def run(rank, size, nlayers, nfeatures, path_A, path_partvec, backend, normalize
         loss.backward()
         average_gradients(model)
         optimizer.step()
+        if state is not None:
+            state.advance()
 
         if myrank == 0:
             print("Epoch {:05d} | Loss {:.4f}".format(epoch, loss), flush=True)
@@ -870,7 +1047,7 @@ def run(rank, size, nlayers, nfeatures, path_A, path_partvec, backend, normalize
     return model
 
 
-def init_process(rank, size, fn, nlayers, nfeatures, path_A, path_partvec, backend, normalize=None):
+def init_process(rank, size, fn, nlayers, nfeatures, path_A, path_partvec, backend, normalize=None, dropout=0.0, dropout_seed=0):
     """PGCN.py:241-253."""
     global _exchanger
     dist.init_process_group(backend, rank=rank, world_size=size)
@@ -881,10 +1058,12 @@ def init_process(rank, size, fn, nlayers, nfeatures, path_A, path_partvec, backe
     }
     print(f"[{os.getpid()}] Initializing process group with: {env_dict}", flush=True)
 
-    if normalize is None:
-        fn(rank, size, nlayers, nfeatures, path_A, path_partvec, backend)
-    else:
-        fn(rank, size, nlayers, nfeatures, path_A, path_partvec, backend, normalize=normalize)
+    kw = {}
+    if normalize is not None:
+        kw["normalize"] = normalize
+    if dropout > 0.0:
+        kw["dropout"], kw["dropout_seed"] = dropout, dropout_seed
+    fn(rank, size, nlayers, nfeatures, path_A, path_partvec, backend, **kw)     # (no option given: today's call)
 
     if _exchanger is not None:
         _exchanger.close()
@@ -901,9 +1080,9 @@ def main(argv):
     os.environ["RANK"] = str(rank)
     os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
     os.environ.setdefault("MASTER_PORT", "29500")
-    backend, nlayers, nfeatures, normalize = "nccl", 3, 128, None
+    backend, nlayers, nfeatures, normalize, dropout, dropout_seed = "nccl", 3, 128, None, 0.0, 0
     try:
-        opts, args = getopt.getopt(argv, "a:p:b:s:l:f:", ["normalize="])
+        opts, args = getopt.getopt(argv, "a:p:b:s:l:f:", ["normalize=", "dropout=", "dropout-seed="])
     except getopt.GetoptError:
         print("a:p:b:", flush=True)
         sys.exit(2)
@@ -913,6 +1092,19 @@ def main(argv):
                 print("--normalize takes %s, got %r" % ("|".join(_partition.NORMALIZE), arg), flush=True)
                 sys.exit(2)
             normalize = arg
+        elif opt == '--dropout':       # drop the output of every layer but the last with this probability (class PGCN)
+            try:
+                dropout = float(arg)
+                _dropout.threshold(dropout)
+            except ValueError:
+                print("--dropout takes a probability in [0, 1), got %r" % arg, flush=True)
+                sys.exit(2)
+        elif opt == '--dropout-seed':
+            try:
+                dropout_seed = int(arg)
+            except ValueError:
+                print("--dropout-seed takes an integer, got %r" % arg, flush=True)
+                sys.exit(2)
         elif opt == '-a':
             path_A = arg
         elif opt == '-p':
@@ -928,7 +1120,8 @@ def main(argv):
     os.environ.setdefault("WORLD_SIZE", str(size))
 
     mp.set_start_method("spawn", force=True)
-    p = mp.Process(target=init_process, args=(rank, size, run, nlayers, nfeatures, path_A, path_partvec, backend, normalize))
+    p = mp.Process(target=init_process, args=(rank, size, run, nlayers, nfeatures, path_A, path_partvec, backend, normalize) +
+                   ((dropout, dropout_seed) if dropout > 0.0 else ()))
     p.start()
     p.join()
     if p.exitcode != 0:

@@ -53,6 +53,8 @@
 namespace pgcn_dense {
 
 #include "pgcn_dense_tile.h"
+#define PG_DROPOUT_FN __host__ __device__ __forceinline__
+#include "pgcn_dropout.h"
 
 using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
 
@@ -100,11 +102,25 @@ struct Args {
     float *C;
     int64_t ldc;
     int relu;
+    // dropout (the DROP instantiations only; pgcn_dropout.h has the keep function)
+    const int64_t *row_ids;    // forward: the GLOBAL id of every row of A (n), or NULL: the row index
+    const int64_t *step;       // forward: the training step, read from device memory at kernel start (a replayed graph draws new masks)
+    uint64_t seed;
+    uint32_t layer, thr;       // keep = u >= thr
+    float scale;               // 1 / (1 - p): forward Y = keep ? relu(.) * scale : 0; input gradient Gm = mask ? G * scale : 0
+};
+
+// the global ids of a tile's 32 rows as the hash takes them, row L of the tile in lanes L and 32 + L
+struct RowIds {
+    uint32_t term, hi;         // dropout_row(key, id); id >> 32
+    bool any_hi;               // (wave-uniform) some id of the tile is 2^32 or above: the second round of the hash is needed
 };
 
 // C (n x N) = op(A) (n x K) . Bm (K x N).  MODE 0: op(A) = A, C = relu ? max(C, 0) : C, mask_out = sign mask of the product;
 // MODE 1: op(A) = A where mask_in says so (all of A when mask_in == NULL), written out as Gm when asked for.
-template <int NKS, int NBLK, int MODE, bool RAGGED>
+// DROP (the pgcn_dropout_* entry points): MODE 0 stores keep ? relu(C) * scale : 0 and the mask sign AND keep, the keep bit hashed in
+// the epilogue from (seed, *step, layer, row id, column); MODE 1 multiplies the masked gradient by scale.
+template <int NKS, int NBLK, int MODE, bool RAGGED, bool DROP = false>
 __global__ __launch_bounds__(kThreads, 2) void dense_kernel(const Args a) {
     extern __shared__ __attribute__((aligned(16))) char image[];
     {
@@ -166,10 +182,51 @@ __global__ __launch_bounds__(kThreads, 2) void dense_kernel(const Args a) {
     auto consume = [&](window_t wgm, int ks) {
         if constexpr (MODE == 1) {
 #pragma unroll
-            for (int h = 0; h < 2; ++h) raw[ks][h] = mask4_bits(raw[ks][h], mwn[ks >> 1], ks, h, lane);
+            for (int h = 0; h < 2; ++h) {
+                raw[ks][h] = mask4_bits(raw[ks][h], mwn[ks >> 1], ks, h, lane);
+                if constexpr (DROP) {
+                    raw[ks][h].x *= a.scale; raw[ks][h].y *= a.scale; raw[ks][h].z *= a.scale; raw[ks][h].w *= a.scale;
+                }
+            }
             store_piece<RAGGED>(raw[ks], wgm, gm_off, ks, K, lane);
         }
         split8(raw[ks][0], raw[ks][1], ap[ks]);
+    };
+
+    // dropout (forward): the key once, the column's share of the hash once per column block, the row ids of the tiles whose blocks are
+    // being stored: the current one (requested at the top of its trip, first used a column block later) and the one before
+    uint32_t dcol = 0;                                        // the column's share, of the block being stored
+    uint64_t key = 0;
+    uint32_t key_hi = 0;
+    RowIds ids_prev{0u, 0u, false}, ids_cur{0u, 0u, false};
+    auto load_ids = [&](int64_t t, RowIds &ids) {
+        if constexpr (DROP && MODE == 0) {
+            const window_t wi = tile_window(a.row_ids, 1, a.row_ids ? n : 0, t * kRows, 1, 8);
+            const uint32_t lo = win_load4u(wi, (uint32_t)(8 * (lane & 31)), 0), hi = win_load4u(wi, (uint32_t)(8 * (lane & 31) + 4), 0);
+            const uint64_t own = (uint64_t)(t * kRows) + (uint64_t)(lane & 31);          // (no ids passed: the row index)
+            ids.term = (a.row_ids ? lo : (uint32_t)own) ^ key_hi;
+            ids.hi = a.row_ids ? hi : (uint32_t)(own >> 32);
+        }
+    };
+    auto settle_ids = [&](RowIds &ids) {                      // (after the load has landed)
+        if constexpr (DROP && MODE == 0) ids.any_hi = __builtin_amdgcn_ballot_w64(ids.hi != 0u) != 0ull;
+    };
+    if constexpr (DROP && MODE == 0) {
+        key = dropout_key(a.seed, (uint64_t)*a.step, a.layer);
+        key_hi = (uint32_t)(key >> 32);
+    }
+    // register r of the lane: tile row (r & 3) + 8 (r >> 2) + 4 hi -- the row's id from the lane that holds it
+    auto drop_reg = [&](float x, auto rc, const RowIds &ids) {
+        constexpr int r = decltype(rc)::value, R0 = (r & 3) + 8 * (r >> 2);
+        const bool up = lane >= 32;
+        const uint32_t t0 = (uint32_t)__builtin_amdgcn_readlane((int)ids.term, R0), t1 = (uint32_t)__builtin_amdgcn_readlane((int)ids.term, R0 + 4);
+        uint32_t u = dropout_fmix32(dcol ^ (up ? t1 : t0));
+        if (ids.any_hi) {                                     // (uniform; ids of 2^32 and above only)
+            const uint32_t h0 = (uint32_t)__builtin_amdgcn_readlane((int)ids.hi, R0), h1 = (uint32_t)__builtin_amdgcn_readlane((int)ids.hi, R0 + 4);
+            const uint32_t h = up ? h1 : h0;
+            u = h ? dropout_fmix32(u ^ h) : u;
+        }
+        return u >= a.thr ? x * a.scale : 0.f;
     };
 
     // prologue: the first tile through the same path, nothing to overlap it with yet
@@ -192,8 +249,12 @@ __global__ __launch_bounds__(kThreads, 2) void dense_kernel(const Args a) {
     uint32_t mword = 0;                                       // the mask word this lane collects for the block being stored
 
     // registers [kChunk c, kChunk c + kChunk) of column block nb of tile t: their stores and their share of the sign mask
-    auto store_chunk = [&](const f32x16 &x, auto cc, int nb, window_t wc, window_t wmo) {
+    auto store_chunk = [&](f32x16 &x, auto cc, int nb, window_t wc, window_t wmo, const RowIds &ids) {
         constexpr int c = decltype(cc)::value;
+        if constexpr (DROP && MODE == 0) {                    // (the block is finished: dropped in place, so that the stores and the mask see it)
+            if constexpr (c == 0) dcol = dropout_col(key, (uint32_t)(32 * nb + (lane & 31)));
+            static_for<kChunk * c, kChunk * (c + 1)>([&](auto rc) { x[decltype(rc)::value] = drop_reg(x[decltype(rc)::value], rc, ids); });
+        }
         store_regs<RAGGED>(x, kChunk * c, kChunk, nb, wc, c_off, c_row, N, lane, a.relu);
         if constexpr (MODE == 0) {
             static_for<kChunk * c, kChunk * (c + 1)>([&](auto rc) {
@@ -213,6 +274,7 @@ __global__ __launch_bounds__(kThreads, 2) void dense_kernel(const Args a) {
         const bool has_next = tn < ntiles;
         // the windows of this trip, once (scalar work): C and the mask of the current tile, Gm of the next, A and the mask of the one after
         const window_t wc = win_c(tile), wmo = win_mo(tile), wgm = win_gm(tn), wa2 = win_a(tn2), wmi2 = win_mi(tn2);
+        load_ids(tile, ids_cur);
         static_for<0, T>([&](auto tc) {
             constexpr int t = decltype(tc)::value;
             constexpr int nb = t / NKS, ks = t % NKS, P = nb & 1;
@@ -230,8 +292,9 @@ __global__ __launch_bounds__(kThreads, 2) void dense_kernel(const Args a) {
             }
             __builtin_amdgcn_sched_barrier(0);
             // between the chains: the stores of the block that was finished one pass ago ...
-            if constexpr (nb > 0) store_chunk(acc[P ^ 1], std::integral_constant<int, ks>{}, nb - 1, wc, wmo);
-            else store_chunk(acc[1], std::integral_constant<int, ks>{}, NBLK - 1, wc_prev, wmo_prev);
+            if constexpr (nb == 1 && ks == 0) settle_ids(ids_cur);
+            if constexpr (nb > 0) store_chunk(acc[P ^ 1], std::integral_constant<int, ks>{}, nb - 1, wc, wmo, ids_cur);
+            else store_chunk(acc[1], std::integral_constant<int, ks>{}, NBLK - 1, wc_prev, wmo_prev, ids_prev);
             // ... and, in the last pass, the next tile's piece ks - 1 (its plane registers are free now) and the load behind it
             if constexpr (nb == NBLK - 1 && ks >= 1) {
                 consume(wgm, ks - 1);
@@ -244,12 +307,13 @@ __global__ __launch_bounds__(kThreads, 2) void dense_kernel(const Args a) {
         load_mask_words(wmi2);
         wc_prev = wc;
         wmo_prev = wmo;
+        ids_prev = ids_cur;
         if (!has_next) break;
         tile = tn;
         tn = tn2;
     }
     // the last block of the wave's last tile
-    static_for<0, NKS>([&](auto cc) { store_chunk(acc[1], cc, NBLK - 1, wc_prev, wmo_prev); });
+    static_for<0, NKS>([&](auto cc) { store_chunk(acc[1], cc, NBLK - 1, wc_prev, wmo_prev, ids_prev); });
 }
 
 // ---- the sign mask of an existing matrix (callers that hold Y but not the forward's mask: tests, the library-GEMM route) ---------------
@@ -267,9 +331,27 @@ __global__ __launch_bounds__(256) void sign_mask_kernel(const float *__restrict_
     mask[word] = bits;
 }
 
-template <int NKS, int NBLK, int MODE, bool RAGGED>
+// ---- the keep bits alone, in the sign-mask layout (layers whose product stays a library GEMM) --------------------------------------------
+__global__ __launch_bounds__(256) void keep_words_kernel(const int64_t *__restrict__ row_ids, int64_t n, int N, uint64_t seed,
+                                                         const int64_t *__restrict__ step, uint32_t layer, uint32_t thr,
+                                                         uint32_t *__restrict__ words) {
+    const int mw = (N + 31) / 32;
+    const int64_t word = (int64_t)blockIdx.x * 256 + threadIdx.x;          // one thread per word
+    if (word >= n * mw) return;
+    const int64_t row = word / mw;
+    const int w = (int)(word % mw);
+    const uint64_t key = dropout_key(seed, (uint64_t)*step, layer), grow = row_ids ? (uint64_t)row_ids[row] : (uint64_t)row;
+    uint32_t bits = 0;
+    for (int bidx = 0; bidx < 32; ++bidx) {
+        const int c = 32 * w + bidx;
+        if (c < N && dropout_keep(key, grow, (uint32_t)c, thr)) bits |= 1u << bidx;
+    }
+    words[word] = bits;
+}
+
+template <int NKS, int NBLK, int MODE, bool RAGGED, bool DROP = false>
 int launch(const Args &a, int workgroups, hipStream_t s) {
-    auto kern = dense_kernel<NKS, NBLK, MODE, RAGGED>;
+    auto kern = dense_kernel<NKS, NBLK, MODE, RAGGED, DROP>;
     static bool attr_set[64] = {false};
     static std::mutex attr_mu;
     int dev = 0;
@@ -286,7 +368,7 @@ int launch(const Args &a, int workgroups, hipStream_t s) {
     return hipGetLastError() == hipSuccess ? 0 : fail(-1, "kernel launch");
 }
 
-template <int MODE>
+template <int MODE, bool DROP = false>
 int dispatch(Args a, hipStream_t s) {
     int dev = 0, cus = 0;
     if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
@@ -299,8 +381,8 @@ int dispatch(Args a, hipStream_t s) {
     a.wvec = slot_vec_ok(a.W, a.ldw, a.transposed, a.K) ? 1 : 0;
 #define PGCN_DENSE_CASE(KS, NB)                                                                                              \
     if (nks <= KS && nblk <= NB) {                                                                                           \
-        if (a.K == 16 * KS && a.N == 32 * NB) return launch<KS, NB, MODE, false>(a, wgs, s);                                  \
-        return launch<KS, NB, MODE, true>(a, wgs, s);                                                                        \
+        if (a.K == 16 * KS && a.N == 32 * NB) return launch<KS, NB, MODE, false, DROP>(a, wgs, s);                                  \
+        return launch<KS, NB, MODE, true, DROP>(a, wgs, s);                                                                       \
     }
     PGCN_DENSE_CASE(4, 2)
     PGCN_DENSE_CASE(4, 4)
@@ -353,4 +435,57 @@ extern "C" int pgcn_sign_mask_f32(const float *Y, int64_t ldy, int64_t n, int32_
     const int64_t words = n * ((N + 31) / 32);
     hipLaunchKernelGGL(sign_mask_kernel, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, (hipStream_t)stream, Y, ldy, n, N, mask);
     return hipGetLastError() == hipSuccess ? 0 : fail(-1, "kernel launch (sign_mask_kernel)");
+}
+
+// ---- dropout fused into the same kernels (include/pgcn_gemm.h has the contract; pgcn_dropout.h the keep function) ------------------------
+extern "C" int pgcn_dropout_abi_version(void) { return 1; }      // 1: the pgcn_dropout_* entry points below exist
+
+namespace pgcn_dense {
+inline int check_dropout(uint32_t thr, const int64_t *step, const int64_t *row_ids) {
+    (void)thr;
+    if (!step) return fail(-1, "pgcn_dropout: the step must be a device pointer");
+    if (row_ids && (uintptr_t)row_ids % 8) return fail(-2, "pgcn_dropout: row_ids must be 8-byte aligned");
+    return 0;
+}
+}  // namespace pgcn_dense
+
+// Y = keep ? relu(X . W^T) * scale : 0, mask (optional) = sign AND keep;  keep = u(seed, *step, layer, row id, column) >= thr
+extern "C" int pgcn_dropout_linear_relu_f32(const float *X, int64_t ldx, int64_t n, int32_t fin, const float *W, int64_t ldw, int32_t fout,
+                                            float *Y, int64_t ldy, uint32_t *mask, const int64_t *row_ids, uint64_t seed,
+                                            const int64_t *step, uint32_t layer, uint32_t thr, void *stream) {
+    using namespace pgcn_dense;
+    if (int rc = check(X, ldx, n, fin, fout, W, ldw, fout, fin, Y, ldy)) return rc;
+    if (int rc = check_dropout(thr, step, row_ids)) return rc;
+    if (n == 0) return 0;
+    Args a{};
+    a.A = X; a.lda = ldx; a.mask_out = mask; a.n = n; a.K = fin; a.N = fout; a.W = W; a.ldw = ldw; a.transposed = 1; a.C = Y; a.ldc = ldy;
+    a.relu = 1;
+    a.row_ids = row_ids; a.step = step; a.seed = seed; a.layer = layer; a.thr = thr; a.scale = dropout_scale(thr);
+    return dispatch<0, true>(a, (hipStream_t)stream);
+}
+
+// Gm = mask ? G * scale : 0 (mask: the forward's sign AND keep words; NULL: Gm = G * scale),  dX = Gm . W
+extern "C" int pgcn_dropout_grad_input_f32(const float *G, int64_t ldg, const uint32_t *mask, float scale, float *Gm, int64_t ldgm, int64_t n,
+                                           int32_t fout, const float *W, int64_t ldw, int32_t fin, float *dX, int64_t lddx, void *stream) {
+    using namespace pgcn_dense;
+    if (int rc = check(G, ldg, n, fout, fin, W, ldw, fout, fin, dX, lddx)) return rc;
+    if (Gm && (ldgm % 4 || (uintptr_t)Gm % 16 || ldgm < fout)) return fail(-2, "pgcn_dense: rows of Gm must be 16-byte pieces");
+    if (n == 0) return 0;
+    Args a{};
+    a.A = G; a.lda = ldg; a.mask_in = mask; a.Gm = Gm; a.ldgm = ldgm; a.n = n; a.K = fout; a.N = fin; a.W = W; a.ldw = ldw; a.transposed = 0;
+    a.C = dX; a.ldc = lddx; a.relu = 0; a.scale = scale;
+    return dispatch<1, true>(a, (hipStream_t)stream);
+}
+
+// words (n x ceil(N / 32)) = the keep bits alone, in the sign-mask layout
+extern "C" int pgcn_dropout_keep_words_u32(const int64_t *row_ids, int64_t n, int32_t N, uint64_t seed, const int64_t *step, uint32_t layer,
+                                           uint32_t thr, uint32_t *words, void *stream) {
+    using namespace pgcn_dense;
+    if (n < 0 || N <= 0 || !step || (n > 0 && !words)) return fail(-1, "pgcn_dropout_keep_words_u32: bad argument");
+    if (n == 0) return 0;
+    const int64_t nw = n * ((N + 31) / 32);
+    if ((nw + 255) / 256 > 0x7fffffffLL) return fail(-2, "pgcn_dropout_keep_words_u32: too many words for one launch");
+    hipLaunchKernelGGL(keep_words_kernel, dim3((unsigned)((nw + 255) / 256)), dim3(256), 0, (hipStream_t)stream, row_ids, n, (int)N, seed, step,
+                       layer, thr, words);
+    return hipGetLastError() == hipSuccess ? 0 : fail(-1, "kernel launch (keep_words_kernel)");
 }

@@ -97,6 +97,11 @@ class Tuning:
                                      # 0 = the library route.  r05 on the MI355X at n = 232 965, f = 128: forward 63.3 us against 85 + 35 us
                                      # of rocBLAS + clamp, input gradient 116.8 us against 50 + 86 us; epochs 10.52 / 10.48 / 10.45 ms off,
                                      # 10.37 / 10.36 / 10.34 at level 2 (profiles/r05_dense_fused_epochs.txt); r06: DESIGN.md section 4
+    dropout_fused: int = 1           # dropout of a layer's output (PGCN(dropout=...)) in the epilogue of the dense kernels (one forward kernel leaves
+                                     # y and the words sign AND keep; the backward scales by them) instead of library product + keep-words kernel
+                                     # + element-wise passes; 0 = always the unfused route (same masks, same results up to the product's rounding)
+                                     # MI355X, n = 232 965, f = 128: forward 82 us fused against 63 plain and 856 unfused, input gradient 84 / 86 / 368
+                                     # (profiles/dropout_dense_times.json, HISTORY.md section 14)
     # ---- GAT path -------------------------------------------------------------------------------------------
     gat_long_row: int = 1024         # rows above this get a 256-thread workgroup in the attention kernels
     gat_small_row: int = 192         # gather plan of the attention structures (r05): a partial row there is heads x d = 1 KB wide, twice the GCN
