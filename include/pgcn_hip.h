@@ -462,6 +462,36 @@ int pgcn_nll_rows_backward_f32(const float *X, int64_t ldx, const int64_t *label
                                const float *gscale_dev, float scale, int64_t nrows, int32_t f, float *dX,
                                int64_t lddx, pgcn_stream_t stream);
 
+/* ---- masked loss and accuracy of node classification (one pass each way) -------------------------------
+ * split[i] (one byte per local row): 0 = in no set, 1 = train, 2 = val, 3 = test (a code above 3 reads as 0).
+ * pgcn_masked_nll_f32 reads the nrows x C logits once and writes lse_rows[i] = logsumexp_j X[i,j] for EVERY row and the
+ * record *stats (device memory, 8-byte aligned), per set k in {1, 2, 3}:
+ *   loss_sum[k] = sum over the set's rows of lse_i - X[i, labels[i]]        (added in double)
+ *   correct[k]  = rows whose arg-max equals the label; arg-max = the LOWEST index among equal maxima (numpy.argmax)
+ *   rows[k]     = rows of the set;                     slot 0: loss_sum = 0, correct = 0, rows = rows in no set.
+ * Labels of rows in no set are never read (-1 = "unlabelled" is fine there).  A label outside [0, C) on a row of a set
+ * makes THAT set's loss_sum NaN and counts the row as wrong; nothing is read through it.  Rows may hold -inf; an all -inf
+ * row behaves as in pgcn_nll_rows_f32.  A block owns 64 rows and writes one partial record to `ws`
+ * (pgcn_masked_nll_ws_bytes(nrows) bytes, 8-byte aligned); a second one-block launch adds them in block order: no
+ * floating-point atomics, the same input gives the same bits.  nrows == 0 writes an all-zero record.
+ * pgcn_masked_nll_backward_f32 overwrites the whole nrows x C block dX:
+ *   dX[i,j] = gscale_dev[0] * scale * (exp(X[i,j] - lse_rows[i]) - [j == labels[i]])  on train rows (split 1),
+ *   exact zeros on every other row (their logits and labels are not read).            (gscale_dev NULL = 1)
+ * Both: raw pointers + a stream, no allocation, no synchronisation (graph-capturable), PGCN_EUNSUPPORTED above 1024
+ * columns; a float4 path for C % 4 == 0 with 16-byte aligned rows, a wave-per-row path for every other width.      */
+typedef struct {
+    double loss_sum[4];
+    int64_t correct[4];
+    int64_t rows[4];
+} pgcn_masked_nll_stats;
+int64_t pgcn_masked_nll_ws_bytes(int64_t nrows);
+int pgcn_masked_nll_f32(const float *X, int64_t ldx, const int64_t *labels, const uint8_t *split, int64_t nrows,
+                        int32_t C, float *lse_rows, pgcn_masked_nll_stats *stats, void *ws, int64_t ws_bytes,
+                        pgcn_stream_t stream);
+int pgcn_masked_nll_backward_f32(const float *X, int64_t ldx, const int64_t *labels, const uint8_t *split,
+                                 const float *lse_rows, const float *gscale_dev, float scale, int64_t nrows, int32_t C,
+                                 float *dX, int64_t lddx, pgcn_stream_t stream);
+
 /* ---- boundary-row pack / unpack -------------------------------------------
  * out[r,:] = H[idx[r],:]                      replaces H[indices]   GPU/PGCN.py:104
  * H[idx[r],:] (+)= in[r,:]                    replaces X[indices] = buf   :115

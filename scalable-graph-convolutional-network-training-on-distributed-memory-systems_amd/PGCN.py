@@ -38,6 +38,7 @@ from . import dropout as _dropout
 from . import engine as _engine
 from . import ingest as _ingest
 from . import kernels as _kernels
+from . import nodedata as _nodedata
 from . import partition as _partition
 
 # module-level state, same names as PGCN.py:23-35
@@ -808,9 +809,12 @@ class PGCN(nn.Module):
     equivalently the input of layers 2 .. L: Kipf & Welling's placement minus the raw input features (``run`` builds it that
     way).  ``layer``: the layer's index, part of the hash; ``state``: the dropout.DropoutState the model's layers share (seed,
     device-resident step).  The keep bit of an element depends on the GLOBAL id of its row (``A.part.owned``), so P ranks
-    under any part vector reproduce one rank.  ``eval()`` or ``dropout=0``: the path without dropout, bit for bit."""
+    under any part vector reproduce one rank.  ``eval()`` or ``dropout=0``: the path without dropout, bit for bit.
 
-    def __init__(self, A, in_features, out_features, dropout=0.0, layer=0, state=None):
+    ``relu=False`` (the output layer of a classifier): the aggregation followed by the plain product x . W^T -- no ReLU in front
+    of the softmax, no dropout.  The default is the reference's layer."""
+
+    def __init__(self, A, in_features, out_features, dropout=0.0, layer=0, state=None, relu=True):
         super(PGCN, self).__init__()
         self.linear = nn.Linear(in_features, out_features, bias=False)
         self.A = A
@@ -821,9 +825,12 @@ class PGCN(nn.Module):
         self.layer = int(layer)
         self.state = state
         self._row_ids = None
+        self.relu = bool(relu)
 
     def forward(self, H):
         H = PSpMM.apply(self.A, H)
+        if not self.relu:
+            return _LinearNoBias.apply(H, self.linear.weight)
         if self.training and self.dropout > 0.0:
             if self.state is None:
                 self.state = _dropout.DropoutState(0, H.device)
@@ -858,14 +865,16 @@ def _reduce_sum(t):
     return t
 
 
-def average_gradients(model):
-    """PGCN.py:150-154, as ONE fused all-reduce of all layers' gradients."""
+def average_gradients(model, average=True):
+    """PGCN.py:150-154, as ONE fused all-reduce of all layers' gradients.  ``average=False``: the ranks' sum (the gradient of a
+    loss whose rank-local parts add up to the whole, ``masked_loss``)."""
     if world_size <= 1:
         return
     grads = [p.grad.data for p in model.parameters()]
     flat = torch.cat([g.reshape(-1) for g in grads])
     _reduce_sum(flat)
-    flat /= world_size
+    if average:
+        flat /= world_size
     o = 0
     for g in grads:
         g.copy_(flat[o:o + g.numel()].view_as(g))
@@ -920,14 +929,184 @@ def local_loss(logits, labels, n_global):
     return (nll_sum + missing * math.log(f)) / n_global
 
 
-def run(rank, size, nlayers, nfeatures, path_A, path_partvec, backend, normalize=None, dropout=0.0, dropout_seed=0):
+def _masked_kernels(logits, labels, split):
+    """The provider whose masked_nll takes these operands, or None (CPU tensors, a provider without the kernel such as the
+    checker-backed one of the tests, another dtype or layout)."""
+    k = _kernel_provider if _kernel_provider is not None else getattr(_engine_current, "k", None)
+    if (k is not None and hasattr(k, "masked_nll") and logits.is_cuda and logits.dim() == 2 and logits.dtype is torch.float32
+            and logits.stride(1) == 1 and labels.dtype is torch.int64 and labels.is_contiguous()
+            and split.dtype is torch.uint8 and split.is_contiguous()):
+        return k
+    return None
+
+
+def masked_stats_composed(logits, labels, split):
+    """(lse_rows, MaskedStats) from framework operations: the same numbers as pgcn_masked_nll_f32 (row losses in the logits'
+    precision, sums in float64, arg-max = the first of equal maxima, NaN for a label outside [0, C) on a row of a set)."""
+    C = logits.shape[1]
+    lse = torch.logsumexp(logits, 1)
+    valid = (labels >= 0) & (labels < C)
+    picked = logits.gather(1, labels.clamp(0, C - 1).unsqueeze(1)).squeeze(1)
+    nll = torch.where(valid, lse - picked, torch.full((), float("nan"), dtype=logits.dtype, device=logits.device)).double()
+    hit = valid & (logits.argmax(1) == labels)
+    zero = torch.zeros((), dtype=torch.float64, device=logits.device)
+    sets = [split == k for k in range(4)]
+    loss_sum = torch.stack([zero] + [torch.where(m, nll, zero).sum() for m in sets[1:]])
+    correct = torch.stack([torch.zeros((), dtype=torch.int64, device=logits.device)] + [(m & hit).sum() for m in sets[1:]])
+    rows = torch.stack([(m if k else (split == 0) | (split > 3)).sum() for k, m in enumerate(sets)])
+    return lse, _kernels.MaskedStats(loss_sum, correct, rows)
+
+
+def masked_stats(logits, labels, split):
+    """(lse_rows, MaskedStats) of one pass over the logits: pgcn_masked_nll_f32 where a provider has it, else the composition."""
+    k = _masked_kernels(logits, labels, split)
+    out = k.masked_nll(logits, labels, split) if k is not None else None       # (None: a shape the kernel refuses)
+    return out if out is not None else masked_stats_composed(logits, labels, split)
+
+
+class _MaskedNLL(torch.autograd.Function):
+    """loss_sum[train] * scale through pgcn_masked_nll_f32 / _backward_f32; the record of all three sets rides along."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, split, scale):
+        lse, st = masked_stats(logits, labels, split)
+        ctx.scale = float(scale)
+        ctx.save_for_backward(logits, labels, split, lse)
+        ctx.mark_non_differentiable(st.loss_sum, st.correct, st.rows)
+        return (st.loss_sum[1] * ctx.scale).to(logits.dtype), st.loss_sum, st.correct, st.rows
+
+    @staticmethod
+    def backward(ctx, g, *_):
+        logits, labels, split, lse = ctx.saved_tensors
+        k = _masked_kernels(logits, labels, split)
+        dX = k.masked_nll_backward(logits, labels, split, lse, g, ctx.scale) if k is not None else None
+        if dX is None:
+            onehot = torch.arange(logits.shape[1], device=logits.device).unsqueeze(0) == labels.unsqueeze(1)
+            dX = torch.where((split == 1).unsqueeze(1),
+                             (g.to(logits.dtype) * ctx.scale) * (torch.exp(logits - lse.unsqueeze(1)) - onehot.to(logits.dtype)),
+                             torch.zeros((), dtype=logits.dtype, device=logits.device))
+        return dX, None, None, None
+
+
+def masked_loss(logits, labels, split, n_train_global):
+    """(loss, stats): the cross entropy of the TRAIN rows this rank owns over the global number of train rows -- the ranks'
+    losses add up to the mean over the train set, their gradients to its gradient (``average_gradients(model, average=False)``)
+    -- and the per-set record of the same pass (kernels.MaskedStats: loss sums, correct counts, row counts by split code).
+    ``split``: uint8 per owned row, 0 no set / 1 train / 2 val / 3 test.  No ``missing . log f`` term: that quirk belongs to
+    the synthetic loop (``local_loss``)."""
+    loss, loss_sum, correct, rows = _MaskedNLL.apply(logits, labels, split, 1.0 / float(n_train_global))
+    return loss, _kernels.MaskedStats(loss_sum, correct, rows)
+
+
+def _global_stats(st):
+    """The nine numbers of a record summed over the ranks in one float64 all-reduce (counts are exact below 2^53):
+    {"loss": {set: mean loss}, "acc": {set: accuracy}, "correct": {set: rows predicted right}, "rows": {set: rows}} as Python
+    numbers, sets "train" / "val" / "test"."""
+    nine = torch.cat([st.loss_sum[1:], st.correct[1:].double(), st.rows[1:].double()])
+    if world_size > 1:
+        _all_reduce(nine)
+    v = nine.tolist()
+    out = {"loss": {}, "acc": {}, "correct": {}, "rows": {}}
+    for j, name in enumerate(_nodedata.SPLIT_NAMES[1:]):
+        r = v[6 + j]
+        out["rows"][name], out["correct"][name] = int(r), int(v[3 + j])
+        out["loss"][name] = v[j] / r if r else float("nan")
+        out["acc"][name] = v[3 + j] / r if r else float("nan")
+    return out
+
+
+def evaluate(model, H, labels, split):
+    """One eval-mode forward without autograd, one pass of the masked kernel, one all-reduce: {"loss": {set: mean loss},
+    "acc": {set: accuracy}, "correct": {set: count}, "rows": {set: rows}} over ALL ranks' rows, sets "train" / "val" / "test".
+    Collective."""
+    was_training = model.training
+    model.eval()
+    try:
+        with torch.no_grad():
+            _, st = masked_stats(model(H), labels, split)
+    finally:
+        model.train(was_training)
+    return _global_stats(st)
+
+
+def _train_on_data(A, n, nlayers, nfeatures, features, labels, split, hidden, epochs, lr, eval_every, dropout, dropout_seed):
+    """The loop of ``run`` on real inputs: widths fin -> hidden -> ... -> C, no ReLU on the last layer, constant features (the
+    first layer's backward aggregation is skipped), Adam, the masked loss over the train rows.  Reports every ``eval_every``
+    epochs: without dropout from the record of the training step's own pass (the logits BEFORE that step's update), with
+    dropout from ``evaluate`` after the update."""
+    data = _nodedata.load(features, labels, split, A.part.owned, n, device=device)
+    hidden = int(nfeatures if hidden is None else hidden)
+    epochs = int(4 if epochs is None else epochs)
+    lr = float(1e-3 if lr is None else lr)
+    eval_every = max(1, int(1 if eval_every is None else eval_every))
+    n_train = data.counts[1]
+    if n_train < 1:
+        raise ValueError("split %r: no train rows" % (split,))
+    widths = [data.fin] + [hidden] * (nlayers - 1) + [data.classes]
+    for a, b in zip(widths, widths[1:]):
+        tune_dense_gemms(A.part.n_local, a, device, b)
+    _dropout.threshold(dropout)
+    state = _dropout.DropoutState(dropout_seed, device) if dropout > 0.0 else None
+    model = nn.Sequential(*[PGCN(A, widths[i], widths[i + 1], dropout=dropout if i < nlayers - 1 else 0.0, layer=i, state=state,
+                                 relu=i < nlayers - 1) for i in range(nlayers)]).to(device)
+    initiliaze_parameters(model)
+    optimizer = torch.optim.Adam(model.parameters(), lr=lr)
+    H, y, s = data.features, data.labels, data.split           # (H needs no gradient)
+
+    history, best = [], None
+    if device.type == "cuda":
+        torch.cuda.synchronize(device)
+    start = time.time()
+    for epoch in range(epochs):
+        model.train()
+        loss, st = masked_loss(model(H), y, s, n_train)
+        optimizer.zero_grad()
+        loss.backward()
+        average_gradients(model, average=False)
+        optimizer.step()
+        if state is not None:
+            state.advance()
+        if epoch % eval_every == 0 or epoch == epochs - 1:
+            ev = evaluate(model, H, y, s) if state is not None else _global_stats(st)
+            l, acc = ev["loss"], ev["acc"]
+            history.append({"epoch": epoch, "loss": l["train"], "train": acc["train"], "val": acc["val"], "test": acc["test"],
+                            "losses": l, "correct": ev["correct"], "rows": ev["rows"]})
+            if best is None or acc["val"] > best["val"]:           # (the first epoch of the best validation accuracy)
+                best = history[-1]
+            if myrank == 0:
+                print("Epoch {:05d} | Loss {:.4f} | Train {:.4f} | Val {:.4f} | Test {:.4f}".format(
+                    epoch, l["train"], acc["train"], acc["val"], acc["test"]), flush=True)
+    if device.type == "cuda":
+        torch.cuda.synchronize(device)
+    elapsed = torch.tensor([time.time() - start], device=device)
+    if world_size > 1:
+        _all_reduce(elapsed, dist.ReduceOp.MAX)
+    _sync_stats(A)
+    if best is None:
+        best = {"epoch": -1, "val": float("nan"), "test": float("nan")}
+    if myrank == 0:
+        print("Elapsed time {:.4f}  ms/epoch: {:.3f}".format(elapsed.item(), 1e3 * elapsed.item() / max(epochs, 1)), flush=True)
+        print("Best Val {:.4f} at epoch {:05d} | Test {:.4f}".format(best["val"], best["epoch"], best["test"]), flush=True)
+    model.history, model.best, model.widths = history, best, widths
+    return model
+
+
+def run(rank, size, nlayers, nfeatures, path_A, path_partvec, backend, normalize=None, dropout=0.0, dropout_seed=0,
+        features=None, labels=None, split=None, hidden=None, epochs=None, lr=None, eval_every=None):
     """PGCN.py:162-238.  ``normalize="sym"``: train on D_r^-1/2 (A + I) D_c^-1/2 of the pattern of ``path_A``, built on the fly
     (partition.build_partition) instead of by the offline pass preprocess/GrB-GNN-IDG.py.  ``dropout`` > 0: the output of every
     layer but the last is dropped with that probability (class PGCN), masks from (``dropout_seed``, step, layer, global row,
-    column); the step advances once per training step on every rank alike."""
+    column); the step advances once per training step on every rank alike.
+
+    ``features`` / ``labels`` / ``split`` (.npy files in global vertex order, nodedata.py; all three or none): train a node
+    classifier on them instead of the synthetic loop -- ``_train_on_data``; ``hidden`` (default ``nfeatures``), ``epochs`` (4),
+    ``lr`` (1e-3), ``eval_every`` (1).  The returned model carries ``history`` (the reported epochs) and ``best``."""
     global myrank, world_size, send_map, recv_map, device, X, recv_buffers, send_buffers, stats
     myrank = rank
     world_size = size
+    given = [v is not None for v in (features, labels, split)]
+    if any(given) and not all(given):
+        raise ValueError("features, labels and split go together: got features=%r labels=%r split=%r" % (features, labels, split))
     if torch.cuda.is_available():
         device = torch.device(f'cuda:{myrank % torch.cuda.device_count()}')
         torch.cuda.set_device(device)
@@ -938,6 +1117,8 @@ def run(rank, size, nlayers, nfeatures, path_A, path_partvec, backend, normalize
                                       "backend=%s only selects the transport" % backend)
 
     partvec = _partition.read_partvec(path_partvec)       # first line: n part ids (PGCN.py:172-173); .gz accepted
+    if all(given):         # reads the files alone: every rank raises alike, before any collective
+        _nodedata.open_checked(features, labels, split, len(partvec))
     _partition_cache.clear()
     if _ingest.is_shard_prefix(path_A, rank):
         # binary CSR shards written ahead of time (ingest.write_shards / tools/make_shards.py): this rank reads
@@ -975,6 +1156,10 @@ def run(rank, size, nlayers, nfeatures, path_A, path_partvec, backend, normalize
     send_buffers, recv_buffers = {}, {}   # persistent slabs live inside the engine
 
     init_stats()
+
+    if all(given):
+        return _train_on_data(A, n, nlayers, nfeatures, features, labels, split, hidden, epochs, lr, eval_every, dropout,
+                              dropout_seed)
 
     owned = A.part.owned.to(device)
     # PGCN.py:186-188 synthetic features H[i,:] = i, owned rows only
@@ -1047,7 +1232,8 @@ def run(rank, size, nlayers, nfeatures, path_A, path_partvec, backend, normalize
     return model
 
 
-def init_process(rank, size, fn, nlayers, nfeatures, path_A, path_partvec, backend, normalize=None, dropout=0.0, dropout_seed=0):
+def init_process(rank, size, fn, nlayers, nfeatures, path_A, path_partvec, backend, normalize=None, dropout=0.0, dropout_seed=0,
+                 features=None, labels=None, split=None, hidden=None, epochs=None, lr=None, eval_every=None):
     """PGCN.py:241-253."""
     global _exchanger
     dist.init_process_group(backend, rank=rank, world_size=size)
@@ -1063,6 +1249,10 @@ def init_process(rank, size, fn, nlayers, nfeatures, path_A, path_partvec, backe
         kw["normalize"] = normalize
     if dropout > 0.0:
         kw["dropout"], kw["dropout_seed"] = dropout, dropout_seed
+    for name, v in (("features", features), ("labels", labels), ("split", split), ("hidden", hidden), ("epochs", epochs), ("lr", lr),
+                    ("eval_every", eval_every)):
+        if v is not None:
+            kw[name] = v
     fn(rank, size, nlayers, nfeatures, path_A, path_partvec, backend, **kw)     # (no option given: today's call)
 
     if _exchanger is not None:
@@ -1081,8 +1271,10 @@ def main(argv):
     os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
     os.environ.setdefault("MASTER_PORT", "29500")
     backend, nlayers, nfeatures, normalize, dropout, dropout_seed = "nccl", 3, 128, None, 0.0, 0
+    data = {}          # the node-classification options that were given (run's keyword arguments)
     try:
-        opts, args = getopt.getopt(argv, "a:p:b:s:l:f:", ["normalize=", "dropout=", "dropout-seed="])
+        opts, args = getopt.getopt(argv, "a:p:b:s:l:f:", ["normalize=", "dropout=", "dropout-seed=", "features=", "labels=", "split=",
+                                                          "hidden=", "epochs=", "lr=", "eval-every="])
     except getopt.GetoptError:
         print("a:p:b:", flush=True)
         sys.exit(2)
@@ -1105,6 +1297,24 @@ def main(argv):
             except ValueError:
                 print("--dropout-seed takes an integer, got %r" % arg, flush=True)
                 sys.exit(2)
+        elif opt in ('--features', '--labels', '--split'):       # .npy files in global vertex order (nodedata.py)
+            data[opt[2:]] = arg
+        elif opt in ('--hidden', '--epochs', '--eval-every'):
+            try:
+                data[opt[2:].replace("-", "_")] = int(arg)
+                if int(arg) < (0 if opt == '--epochs' else 1):
+                    raise ValueError
+            except ValueError:
+                print("%s takes a positive integer, got %r" % (opt, arg), flush=True)
+                sys.exit(2)
+        elif opt == '--lr':
+            try:
+                data["lr"] = float(arg)
+                if not (data["lr"] > 0.0 and math.isfinite(data["lr"])):
+                    raise ValueError
+            except ValueError:
+                print("--lr takes a positive number, got %r" % arg, flush=True)
+                sys.exit(2)
         elif opt == '-a':
             path_A = arg
         elif opt == '-p':
@@ -1118,10 +1328,23 @@ def main(argv):
         elif opt == '-f':
             nfeatures = int(arg)
     os.environ.setdefault("WORLD_SIZE", str(size))
+    files = [k for k in ("features", "labels", "split") if k in data]
+    if data and len(files) != 3:
+        print("--features, --labels and --split go together (and --hidden, --epochs, --lr, --eval-every need them); got %s"
+              % ", ".join("--" + k.replace("_", "-") for k in sorted(data)), flush=True)
+        sys.exit(2)
+    for k in files:
+        if not os.path.exists(data[k]):
+            print("--%s: no such file %r" % (k, data[k]), flush=True)
+            sys.exit(2)
 
     mp.set_start_method("spawn", force=True)
-    p = mp.Process(target=init_process, args=(rank, size, run, nlayers, nfeatures, path_A, path_partvec, backend, normalize) +
-                   ((dropout, dropout_seed) if dropout > 0.0 else ()))
+    args = (rank, size, run, nlayers, nfeatures, path_A, path_partvec, backend, normalize)
+    if dropout > 0.0 or data:
+        args += (dropout, dropout_seed)
+    if data:
+        args += tuple(data.get(k) for k in ("features", "labels", "split", "hidden", "epochs", "lr", "eval_every"))
+    p = mp.Process(target=init_process, args=args)
     p.start()
     p.join()
     if p.exitcode != 0:

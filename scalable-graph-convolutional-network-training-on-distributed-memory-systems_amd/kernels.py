@@ -16,7 +16,7 @@ from __future__ import annotations
 import ctypes
 import dataclasses
 from dataclasses import dataclass, field
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import numpy as np
 import torch
@@ -179,6 +179,17 @@ def build_plan(rowptr_host: np.ndarray, chunk: int, slice_cnt: Optional[np.ndarr
 
 def _ptr(t: Optional[torch.Tensor]) -> Optional[int]:
     return None if t is None else t.data_ptr()
+
+
+class MaskedStats(NamedTuple):
+    """pgcn_masked_nll_stats as three views of one 96-byte device record, indexed by the split code (slot 0: rows in no set)."""
+    loss_sum: torch.Tensor      # float64 [4]
+    correct: torch.Tensor       # int64 [4]
+    rows: torch.Tensor          # int64 [4]
+
+
+def masked_stats_views(record: torch.Tensor) -> MaskedStats:
+    return MaskedStats(record[0:4].view(torch.float64), record[4:8], record[8:12])
 
 
 class HipKernels:
@@ -986,6 +997,43 @@ class HipKernels:
         _lib.check(self.lib.pgcn_nll_rows_backward_f32(X.data_ptr(), X.stride(0), labels.data_ptr(), lse.data_ptr(),
                                                        g.data_ptr(), scale, n, f, dX.data_ptr(), dX.stride(0),
                                                        self._stream()), "pgcn_nll_rows_backward_f32")
+        return dX
+
+    @staticmethod
+    def _masked_ok(X: torch.Tensor, labels: torch.Tensor, split: torch.Tensor) -> bool:
+        return (X.dim() == 2 and 0 < X.shape[1] <= 1024 and X.stride(1) == 1 and X.dtype is torch.float32 and
+                labels.dtype is torch.int64 and labels.is_contiguous() and split.dtype is torch.uint8 and split.is_contiguous())
+
+    def masked_nll(self, X: torch.Tensor, labels: torch.Tensor, split: torch.Tensor):
+        """(lse_rows, MaskedStats) of pgcn_masked_nll_f32: the per-set loss sums, correct counts and row counts of one pass
+        over the logits (split: uint8 per row, 0 no set / 1 train / 2 val / 3 test), or None when the shape is not covered."""
+        if not self._masked_ok(X, labels, split):
+            return None
+        n, C = X.shape
+        if labels.numel() != n or split.numel() != n:
+            raise _lib.PgcnError("masked_nll: %d rows of logits for %d labels, %d split codes" % (n, labels.numel(), split.numel()))
+        self._check_dense(X, n, "X")
+        lse = torch.empty(n, dtype=torch.float32, device=self.device)
+        record = torch.empty(12, dtype=torch.int64, device=self.device)
+        ws_bytes = int(self.lib.pgcn_masked_nll_ws_bytes(n))
+        ws = torch.empty(ws_bytes // 8, dtype=torch.int64, device=self.device)
+        _lib.check(self.lib.pgcn_masked_nll_f32(X.data_ptr(), X.stride(0), labels.data_ptr(), split.data_ptr(), n, C, lse.data_ptr(),
+                                                record.data_ptr(), ws.data_ptr(), ws_bytes, self._stream()), "pgcn_masked_nll_f32")
+        return lse, masked_stats_views(record)
+
+    def masked_nll_backward(self, X: torch.Tensor, labels: torch.Tensor, split: torch.Tensor, lse: torch.Tensor,
+                            gscale: torch.Tensor, scale: float):
+        """dX = gscale * scale * (softmax(X) - onehot) on train rows, exact zeros elsewhere (pgcn_masked_nll_backward_f32), or None."""
+        if not self._masked_ok(X, labels, split):
+            return None
+        n, C = X.shape
+        if labels.numel() != n or split.numel() != n or lse.numel() != n:
+            raise _lib.PgcnError("masked_nll_backward: %d rows of logits for %d labels" % (n, labels.numel()))
+        dX = torch.empty((n, C), dtype=torch.float32, device=self.device)
+        g = gscale.reshape(1).to(torch.float32).contiguous()
+        _lib.check(self.lib.pgcn_masked_nll_backward_f32(X.data_ptr(), X.stride(0), labels.data_ptr(), split.data_ptr(),
+                                                         lse.data_ptr(), g.data_ptr(), scale, n, C, dX.data_ptr(), dX.stride(0),
+                                                         self._stream()), "pgcn_masked_nll_backward_f32")
         return dX
 
     def gather_rows(self, H: torch.Tensor, idx: torch.Tensor, out: torch.Tensor) -> torch.Tensor:

@@ -124,6 +124,36 @@ def rmat_undirected(n: int, nnz_directed: int, seed: int = 0, device="cpu", port
     return torch.sort(full).values
 
 
+def _sbm_blocks(n: int, community: int, gen, device):
+    """(sizes, cstart, comm) of sbm_undirected's communities: consecutive blocks of an internal numbering, sizes proportional
+    to 1 + 3 u^2 (1x .. 4x); the first draw of the generator's stream."""
+    nc = max(1, n // max(community, 1))
+    u = gen.rand(nc)
+    raw = (1.0 + 3.0 * u * u)
+    sizes = torch.clamp((raw * (n / float(raw.sum().item()))).floor().long(), min=1)
+    short = n - int(sizes.sum())
+    sizes[-1] += short
+    if int(sizes[-1]) < 1:
+        sizes = torch.full((nc,), n // nc, dtype=torch.int64, device=device)
+        sizes[-1] += n - int(sizes.sum())
+    cstart = torch.cumsum(sizes, 0) - sizes
+    comm = torch.repeat_interleave(torch.arange(nc, device=device), sizes)
+    return sizes, cstart, comm
+
+
+def sbm_communities(n: int, seed: int = 0, device="cpu", community: int = 2048) -> torch.Tensor:
+    """The planted community of every vertex of ``sbm_undirected(n, ..., seed, community=community)`` in the graph's own
+    (permuted) numbering: int64 [n].  Replays the head of the generator's stream (block sizes, degree weights, permutation)."""
+    device = torch.device(device)
+    gen = PortableRng(seed + 7919, device)
+    _, _, comm = _sbm_blocks(n, community, gen, device)
+    gen.rand(n)                                                # (the degree weights: drawn between the blocks and the permutation)
+    perm = gen.randperm(n)
+    out = torch.empty(n, dtype=torch.int64, device=device)
+    out[perm] = comm
+    return out
+
+
 def sbm_undirected(n: int, nnz_directed: int, seed: int = 0, device="cpu", community: int = 2048,
                    p_in: float = 0.7) -> torch.Tensor:
     """Degree-corrected planted-partition graph (the second stand-in): communities of
@@ -139,18 +169,7 @@ def sbm_undirected(n: int, nnz_directed: int, seed: int = 0, device="cpu", commu
     target = nnz_directed // 2
     if target > n * (n - 1) // 2:
         raise ValueError("graph denser than complete")
-    # communities: consecutive blocks of an internal numbering, sizes proportional to 1 + 3 u^2 (1x .. 4x)
-    nc = max(1, n // max(community, 1))
-    u = gen.rand(nc)
-    raw = (1.0 + 3.0 * u * u)
-    sizes = torch.clamp((raw * (n / float(raw.sum().item()))).floor().long(), min=1)
-    short = n - int(sizes.sum())
-    sizes[-1] += short
-    if int(sizes[-1]) < 1:
-        sizes = torch.full((nc,), n // nc, dtype=torch.int64, device=device)
-        sizes[-1] += n - int(sizes.sum())
-    cstart = torch.cumsum(sizes, 0) - sizes
-    comm = torch.repeat_interleave(torch.arange(nc, device=device), sizes)
+    sizes, cstart, comm = _sbm_blocks(n, community, gen, device)
     # expected degrees: Pareto(alpha = 2) tail, w = 1 / sqrt(1 - u), truncated; integer weights (x 1024)
     w = torch.clamp(1.0 / torch.sqrt(1.0 - gen.rand(n)), max=float(max(n // 40, 2)))
     wi = torch.clamp((w * 1024.0).floor().long(), min=1)
