@@ -492,6 +492,37 @@ int pgcn_masked_nll_backward_f32(const float *X, int64_t ldx, const int64_t *lab
                                  const float *lse_rows, const float *gscale_dev, float scale, int64_t nrows, int32_t C,
                                  float *dX, int64_t lddx, pgcn_stream_t stream);
 
+/* ---- masked binary cross entropy and micro-F1 counts of multi-label node classification (one pass each way) ----
+ * labels: nrows x ceil(C / 32) uint32 words, contiguous, in the sign-mask layout: bit b of word [i][w] is 1 when row i has
+ * label 32 w + b; bits at or above C in the last word are ignored.  split: as for pgcn_masked_nll_f32.
+ * pgcn_masked_bce_f32 reads the logits of the rows that are in a set once and writes the record *stats (device memory,
+ * 8-byte aligned), per set k in {1, 2, 3}:
+ *   loss_sum[k] = sum over the set's rows and all C columns of  y ? softplus(-x) : softplus(x),
+ *                 softplus(t) = max(t, 0) + log1p(exp(-|t|))    (+-inf give 0 or +inf, never inf - inf; per row in fp32,
+ *                 across rows in double) = BCEWithLogitsLoss(reduction="sum") over the set
+ *   tp / fp / fn[k] = elements of the set with prediction x > 0 (x == 0 and NaN predict negative) against the label bit
+ *   rows[k]     = rows of the set;                     slot 0: rows = rows in no set, everything else 0.
+ * Logits and labels of rows in no set are never read.  A NaN logit in a set makes THAT set's loss_sum NaN.  A block owns
+ * 64 rows and writes one partial record to `ws` (pgcn_masked_bce_ws_bytes(nrows) bytes, 8-byte aligned); a second one-block
+ * launch adds them in block order: no floating-point atomics, the same input gives the same bits.  nrows == 0 writes an
+ * all-zero record.
+ * pgcn_masked_bce_backward_f32 overwrites the whole nrows x C block dX:
+ *   dX[i,j] = gscale_dev[0] * scale * (sigmoid(X[i,j]) - y[i,j])  on train rows (split 1; sigmoid(+-inf) = 1 / 0 exactly),
+ *   exact zeros on every other row (their logits and labels are not read).            (gscale_dev NULL = 1)
+ * Both: raw pointers + a stream, no allocation, no synchronisation (graph-capturable), PGCN_EUNSUPPORTED above 1024
+ * columns, every C from 1 upward; a float4 path for C % 4 == 0 with 16-byte aligned rows (16 lanes per row), a
+ * wave-per-row path for every other width; a row's label words are loaded once by the lanes that own the row.      */
+typedef struct {
+    double loss_sum[4];
+    int64_t tp[4], fp[4], fn[4], rows[4];
+} pgcn_masked_bce_stats; /* 160 bytes */
+int64_t pgcn_masked_bce_ws_bytes(int64_t nrows);
+int pgcn_masked_bce_f32(const float *X, int64_t ldx, const uint32_t *labels, const uint8_t *split, int64_t nrows, int32_t C,
+                        pgcn_masked_bce_stats *stats, void *ws, int64_t ws_bytes, pgcn_stream_t stream);
+int pgcn_masked_bce_backward_f32(const float *X, int64_t ldx, const uint32_t *labels, const uint8_t *split,
+                                 const float *gscale_dev, float scale, int64_t nrows, int32_t C, float *dX, int64_t lddx,
+                                 pgcn_stream_t stream);
+
 /* ---- boundary-row pack / unpack -------------------------------------------
  * out[r,:] = H[idx[r],:]                      replaces H[indices]   GPU/PGCN.py:104
  * H[idx[r],:] (+)= in[r,:]                    replaces X[indices] = buf   :115

@@ -1029,12 +1029,124 @@ def evaluate(model, H, labels, split):
     return _global_stats(st)
 
 
-def _train_on_data(A, n, nlayers, nfeatures, features, labels, split, hidden, epochs, lr, eval_every, dropout, dropout_seed):
+# ---- multi-label tasks: masked binary cross entropy with logits, micro-F1 ---------------------------------------------------------
+
+def _masked_bce_kernels(logits, labels_words, split):
+    """The provider whose masked_bce takes these operands, or None (CPU tensors, a provider without the kernel, another dtype
+    or layout, more than 1024 columns)."""
+    k = _kernel_provider if _kernel_provider is not None else getattr(_engine_current, "k", None)
+    if (k is not None and hasattr(k, "masked_bce") and logits.is_cuda and logits.dim() == 2 and logits.dtype is torch.float32
+            and logits.stride(1) == 1 and labels_words.dtype is torch.int32 and labels_words.is_contiguous()
+            and split.dtype is torch.uint8 and split.is_contiguous()):
+        return k
+    return None
+
+
+def unpack_label_bits(labels_words, C):
+    """bool [n, C] from the packed label words (int32 [n, ceil(C / 32)], nodedata.pack_label_words); bits at or above C are
+    dropped."""
+    shifts = torch.arange(32, dtype=torch.int32, device=labels_words.device)
+    bits = (labels_words.unsqueeze(2) >> shifts) & 1          # (arithmetic shift: the bit that arrives at position 0 is the same)
+    return bits.reshape(labels_words.shape[0], 32 * labels_words.shape[1])[:, :C].bool()
+
+
+def masked_bce_stats_composed(logits, labels_words, split):
+    """kernels.MaskedBCEStats from framework operations: the same numbers as pgcn_masked_bce_f32 (element losses
+    y ? softplus(-x) : softplus(x) with softplus(t) = max(t, 0) + log1p(exp(-|t|)), row sums in the logits' precision, sums
+    over rows in float64; prediction x > 0; selects, so a NaN stays in its own set and rows in no set count for nothing)."""
+    y = unpack_label_bits(labels_words, logits.shape[1])
+    t = torch.where(y, -logits, logits)
+    row = (t.clamp_min(0) + torch.log1p(torch.exp(-logits.abs()))).sum(1).double()
+    pred = logits > 0
+    tp, fp, fn = (pred & y).sum(1), (pred & ~y).sum(1), (~pred & y).sum(1)
+    zero = torch.zeros((), dtype=torch.float64, device=logits.device)
+    izero = torch.zeros((), dtype=torch.int64, device=logits.device)
+    sets = [split == k for k in (1, 2, 3)]
+    loss_sum = torch.stack([zero] + [torch.where(m, row, zero).sum() for m in sets])
+    counts = [torch.stack([izero] + [torch.where(m, c, izero).sum() for m in sets]) for c in (tp, fp, fn)]
+    rows = torch.stack([((split == 0) | (split > 3)).sum()] + [m.sum() for m in sets])
+    return _kernels.MaskedBCEStats(loss_sum, counts[0], counts[1], counts[2], rows)
+
+
+def masked_bce_stats(logits, labels_words, split):
+    """kernels.MaskedBCEStats of one pass over the logits: pgcn_masked_bce_f32 where a provider has it, else the composition."""
+    k = _masked_bce_kernels(logits, labels_words, split)
+    out = k.masked_bce(logits, labels_words, split) if k is not None else None       # (None: a shape the kernel refuses)
+    return out if out is not None else masked_bce_stats_composed(logits, labels_words, split)
+
+
+class _MaskedBCE(torch.autograd.Function):
+    """loss_sum[train] * scale through pgcn_masked_bce_f32 / _backward_f32; the record of all three sets rides along."""
+
+    @staticmethod
+    def forward(ctx, logits, labels_words, split, scale):
+        st = masked_bce_stats(logits, labels_words, split)
+        ctx.scale = float(scale)
+        ctx.save_for_backward(logits, labels_words, split)
+        ctx.mark_non_differentiable(*st)
+        return ((st.loss_sum[1] * ctx.scale).to(logits.dtype),) + tuple(st)
+
+    @staticmethod
+    def backward(ctx, g, *_):
+        logits, labels_words, split = ctx.saved_tensors
+        k = _masked_bce_kernels(logits, labels_words, split)
+        dX = k.masked_bce_backward(logits, labels_words, split, g, ctx.scale) if k is not None else None
+        if dX is None:
+            y = unpack_label_bits(labels_words, logits.shape[1]).to(logits.dtype)
+            dX = torch.where((split == 1).unsqueeze(1), (g.to(logits.dtype) * ctx.scale) * (torch.sigmoid(logits) - y),
+                             torch.zeros((), dtype=logits.dtype, device=logits.device))
+        return dX, None, None, None
+
+
+def masked_bce_loss(logits, labels_words, split, n_train_global):
+    """(loss, stats) of a multi-label task: the binary cross entropy with logits of the TRAIN rows this rank owns over
+    ``n_train_global * C`` elements -- the ranks' losses add up to ``BCEWithLogitsLoss(reduction="mean")`` over the global train
+    rows, their gradients to its gradient (``average_gradients(model, average=False)``) -- and the per-set record of the same
+    pass (kernels.MaskedBCEStats).  ``labels_words``: int32 [n_local, ceil(C / 32)] (nodedata.pack_label_words)."""
+    out = _MaskedBCE.apply(logits, labels_words, split, 1.0 / (float(n_train_global) * logits.shape[1]))
+    return out[0], _kernels.MaskedBCEStats(*out[1:])
+
+
+def _global_stats_multilabel(st, C):
+    """The fifteen numbers of a multi-label record summed over the ranks in one float64 all-reduce (counts are exact below
+    2^53): {"loss": {set: mean loss per element}, "micro_f1": {set: 2 tp / (2 tp + fp + fn), NaN when that is 0 / 0},
+    "tp" / "fp" / "fn" / "rows": {set: count}} as Python numbers, sets "train" / "val" / "test"."""
+    v = torch.cat([st.loss_sum[1:], st.tp[1:].double(), st.fp[1:].double(), st.fn[1:].double(), st.rows[1:].double()])
+    if world_size > 1:
+        _all_reduce(v)
+    v = v.tolist()
+    out = {"loss": {}, "micro_f1": {}, "tp": {}, "fp": {}, "fn": {}, "rows": {}}
+    for j, name in enumerate(_nodedata.SPLIT_NAMES[1:]):
+        tp, fp, fn, r = (int(v[3 * q + j]) for q in (1, 2, 3, 4))
+        out["tp"][name], out["fp"][name], out["fn"][name], out["rows"][name] = tp, fp, fn, r
+        out["loss"][name] = v[j] / (r * C) if r else float("nan")
+        out["micro_f1"][name] = 2 * tp / (2 * tp + fp + fn) if 2 * tp + fp + fn else float("nan")
+    return out
+
+
+def evaluate_multilabel(model, H, labels_words, split):
+    """``evaluate`` for a multi-label task (``evaluate`` itself keeps single-label int64 vectors): one eval-mode forward without
+    autograd, one pass of the masked BCE kernel, one all-reduce; the dictionary of ``_global_stats_multilabel``.  Collective."""
+    was_training = model.training
+    model.eval()
+    try:
+        with torch.no_grad():
+            logits = model(H)
+            st = masked_bce_stats(logits, labels_words, split)
+    finally:
+        model.train(was_training)
+    return _global_stats_multilabel(st, logits.shape[1])
+
+
+def _train_on_data(A, n, nlayers, nfeatures, features, labels, split, hidden, epochs, lr, eval_every, dropout, dropout_seed,
+                   multilabel=False):
     """The loop of ``run`` on real inputs: widths fin -> hidden -> ... -> C, no ReLU on the last layer, constant features (the
     first layer's backward aggregation is skipped), Adam, the masked loss over the train rows.  Reports every ``eval_every``
     epochs: without dropout from the record of the training step's own pass (the logits BEFORE that step's update), with
-    dropout from ``evaluate`` after the update."""
-    data = _nodedata.load(features, labels, split, A.part.owned, n, device=device)
+    dropout from ``evaluate`` after the update.  ``multilabel``: the labels are an n x C 0 / 1 matrix, the loss is the masked
+    binary cross entropy with logits and the reported score the micro-F1 (``masked_bce_loss`` / ``evaluate_multilabel``)."""
+    load = _nodedata.load_multilabel if multilabel else _nodedata.load
+    data = load(features, labels, split, A.part.owned, n, device=device)
     hidden = int(nfeatures if hidden is None else hidden)
     epochs = int(4 if epochs is None else epochs)
     lr = float(1e-3 if lr is None else lr)
@@ -1059,14 +1171,24 @@ def _train_on_data(A, n, nlayers, nfeatures, features, labels, split, hidden, ep
     start = time.time()
     for epoch in range(epochs):
         model.train()
-        loss, st = masked_loss(model(H), y, s, n_train)
+        loss, st = (masked_bce_loss if multilabel else masked_loss)(model(H), y, s, n_train)
         optimizer.zero_grad()
         loss.backward()
         average_gradients(model, average=False)
         optimizer.step()
         if state is not None:
             state.advance()
-        if epoch % eval_every == 0 or epoch == epochs - 1:
+        if multilabel and (epoch % eval_every == 0 or epoch == epochs - 1):
+            ev = evaluate_multilabel(model, H, y, s) if state is not None else _global_stats_multilabel(st, data.classes)
+            l, f1 = ev["loss"], ev["micro_f1"]
+            history.append({"epoch": epoch, "loss": l["train"], "train": f1["train"], "val": f1["val"], "test": f1["test"],
+                            "losses": l, "micro_f1": f1, "tp": ev["tp"], "fp": ev["fp"], "fn": ev["fn"], "rows": ev["rows"]})
+            if best is None or f1["val"] > best["val"]:            # (the first epoch of the best validation micro-F1)
+                best = history[-1]
+            if myrank == 0:
+                print("Epoch {:05d} | Loss {:.4f} | Train F1 {:.4f} | Val F1 {:.4f} | Test F1 {:.4f}".format(
+                    epoch, l["train"], f1["train"], f1["val"], f1["test"]), flush=True)
+        elif epoch % eval_every == 0 or epoch == epochs - 1:
             ev = evaluate(model, H, y, s) if state is not None else _global_stats(st)
             l, acc = ev["loss"], ev["acc"]
             history.append({"epoch": epoch, "loss": l["train"], "train": acc["train"], "val": acc["val"], "test": acc["test"],
@@ -1086,13 +1208,17 @@ def _train_on_data(A, n, nlayers, nfeatures, features, labels, split, hidden, ep
         best = {"epoch": -1, "val": float("nan"), "test": float("nan")}
     if myrank == 0:
         print("Elapsed time {:.4f}  ms/epoch: {:.3f}".format(elapsed.item(), 1e3 * elapsed.item() / max(epochs, 1)), flush=True)
-        print("Best Val {:.4f} at epoch {:05d} | Test {:.4f}".format(best["val"], best["epoch"], best["test"]), flush=True)
+        print(("Best Val F1 {:.4f} at epoch {:05d} | Test F1 {:.4f}" if multilabel else "Best Val {:.4f} at epoch {:05d} | Test {:.4f}")
+              .format(best["val"], best["epoch"], best["test"]), flush=True)
     model.history, model.best, model.widths = history, best, widths
     return model
 
 
+TASKS = ("single", "multilabel")       # --task / run(task=...): one class per vertex (the default) or a 0 / 1 label matrix
+
+
 def run(rank, size, nlayers, nfeatures, path_A, path_partvec, backend, normalize=None, dropout=0.0, dropout_seed=0,
-        features=None, labels=None, split=None, hidden=None, epochs=None, lr=None, eval_every=None):
+        features=None, labels=None, split=None, hidden=None, epochs=None, lr=None, eval_every=None, task=None):
     """PGCN.py:162-238.  ``normalize="sym"``: train on D_r^-1/2 (A + I) D_c^-1/2 of the pattern of ``path_A``, built on the fly
     (partition.build_partition) instead of by the offline pass preprocess/GrB-GNN-IDG.py.  ``dropout`` > 0: the output of every
     layer but the last is dropped with that probability (class PGCN), masks from (``dropout_seed``, step, layer, global row,
@@ -1100,13 +1226,20 @@ def run(rank, size, nlayers, nfeatures, path_A, path_partvec, backend, normalize
 
     ``features`` / ``labels`` / ``split`` (.npy files in global vertex order, nodedata.py; all three or none): train a node
     classifier on them instead of the synthetic loop -- ``_train_on_data``; ``hidden`` (default ``nfeatures``), ``epochs`` (4),
-    ``lr`` (1e-3), ``eval_every`` (1).  The returned model carries ``history`` (the reported epochs) and ``best``."""
+    ``lr`` (1e-3), ``eval_every`` (1).  The returned model carries ``history`` (the reported epochs) and ``best``.
+    ``task`` (needs the three files): None or "single" = one class per vertex (int64 label vector, softmax loss, accuracy);
+    "multilabel" = an n x C uint8 matrix of 0 / 1, the masked binary cross entropy with logits, micro-F1."""
     global myrank, world_size, send_map, recv_map, device, X, recv_buffers, send_buffers, stats
     myrank = rank
     world_size = size
     given = [v is not None for v in (features, labels, split)]
     if any(given) and not all(given):
         raise ValueError("features, labels and split go together: got features=%r labels=%r split=%r" % (features, labels, split))
+    if task not in TASKS + (None,):
+        raise ValueError("task takes %s, got %r" % (" | ".join(TASKS), task))
+    if task is not None and not all(given):
+        raise ValueError("task=%r needs features, labels and split" % (task,))
+    multilabel = task == "multilabel"
     if torch.cuda.is_available():
         device = torch.device(f'cuda:{myrank % torch.cuda.device_count()}')
         torch.cuda.set_device(device)
@@ -1118,7 +1251,7 @@ def run(rank, size, nlayers, nfeatures, path_A, path_partvec, backend, normalize
 
     partvec = _partition.read_partvec(path_partvec)       # first line: n part ids (PGCN.py:172-173); .gz accepted
     if all(given):         # reads the files alone: every rank raises alike, before any collective
-        _nodedata.open_checked(features, labels, split, len(partvec))
+        (_nodedata.open_checked_multilabel if multilabel else _nodedata.open_checked)(features, labels, split, len(partvec))
     _partition_cache.clear()
     if _ingest.is_shard_prefix(path_A, rank):
         # binary CSR shards written ahead of time (ingest.write_shards / tools/make_shards.py): this rank reads
@@ -1159,7 +1292,7 @@ def run(rank, size, nlayers, nfeatures, path_A, path_partvec, backend, normalize
 
     if all(given):
         return _train_on_data(A, n, nlayers, nfeatures, features, labels, split, hidden, epochs, lr, eval_every, dropout,
-                              dropout_seed)
+                              dropout_seed, multilabel)
 
     owned = A.part.owned.to(device)
     # PGCN.py:186-188 synthetic features H[i,:] = i, owned rows only
@@ -1233,7 +1366,7 @@ def run(rank, size, nlayers, nfeatures, path_A, path_partvec, backend, normalize
 
 
 def init_process(rank, size, fn, nlayers, nfeatures, path_A, path_partvec, backend, normalize=None, dropout=0.0, dropout_seed=0,
-                 features=None, labels=None, split=None, hidden=None, epochs=None, lr=None, eval_every=None):
+                 features=None, labels=None, split=None, hidden=None, epochs=None, lr=None, eval_every=None, task=None):
     """PGCN.py:241-253."""
     global _exchanger
     dist.init_process_group(backend, rank=rank, world_size=size)
@@ -1250,7 +1383,7 @@ def init_process(rank, size, fn, nlayers, nfeatures, path_A, path_partvec, backe
     if dropout > 0.0:
         kw["dropout"], kw["dropout_seed"] = dropout, dropout_seed
     for name, v in (("features", features), ("labels", labels), ("split", split), ("hidden", hidden), ("epochs", epochs), ("lr", lr),
-                    ("eval_every", eval_every)):
+                    ("eval_every", eval_every), ("task", task)):
         if v is not None:
             kw[name] = v
     fn(rank, size, nlayers, nfeatures, path_A, path_partvec, backend, **kw)     # (no option given: today's call)
@@ -1274,7 +1407,7 @@ def main(argv):
     data = {}          # the node-classification options that were given (run's keyword arguments)
     try:
         opts, args = getopt.getopt(argv, "a:p:b:s:l:f:", ["normalize=", "dropout=", "dropout-seed=", "features=", "labels=", "split=",
-                                                          "hidden=", "epochs=", "lr=", "eval-every="])
+                                                          "hidden=", "epochs=", "lr=", "eval-every=", "task="])
     except getopt.GetoptError:
         print("a:p:b:", flush=True)
         sys.exit(2)
@@ -1307,6 +1440,11 @@ def main(argv):
             except ValueError:
                 print("%s takes a positive integer, got %r" % (opt, arg), flush=True)
                 sys.exit(2)
+        elif opt == '--task':          # single (one class per vertex, the default) | multilabel (n x C 0 / 1 labels, BCE, micro-F1)
+            if arg not in TASKS:
+                print("--task takes %s, got %r" % ("|".join(TASKS), arg), flush=True)
+                sys.exit(2)
+            data["task"] = arg
         elif opt == '--lr':
             try:
                 data["lr"] = float(arg)
@@ -1330,7 +1468,7 @@ def main(argv):
     os.environ.setdefault("WORLD_SIZE", str(size))
     files = [k for k in ("features", "labels", "split") if k in data]
     if data and len(files) != 3:
-        print("--features, --labels and --split go together (and --hidden, --epochs, --lr, --eval-every need them); got %s"
+        print("--features, --labels and --split go together (and --hidden, --epochs, --lr, --eval-every, --task need them); got %s"
               % ", ".join("--" + k.replace("_", "-") for k in sorted(data)), flush=True)
         sys.exit(2)
     for k in files:
@@ -1343,7 +1481,7 @@ def main(argv):
     if dropout > 0.0 or data:
         args += (dropout, dropout_seed)
     if data:
-        args += tuple(data.get(k) for k in ("features", "labels", "split", "hidden", "epochs", "lr", "eval_every"))
+        args += tuple(data.get(k) for k in ("features", "labels", "split", "hidden", "epochs", "lr", "eval_every", "task"))
     p = mp.Process(target=init_process, args=args)
     p.start()
     p.join()

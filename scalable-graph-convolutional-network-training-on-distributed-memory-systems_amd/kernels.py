@@ -192,6 +192,19 @@ def masked_stats_views(record: torch.Tensor) -> MaskedStats:
     return MaskedStats(record[0:4].view(torch.float64), record[4:8], record[8:12])
 
 
+class MaskedBCEStats(NamedTuple):
+    """pgcn_masked_bce_stats as five views of one 160-byte device record, indexed by the split code (slot 0: rows in no set)."""
+    loss_sum: torch.Tensor      # float64 [4]
+    tp: torch.Tensor            # int64 [4]
+    fp: torch.Tensor            # int64 [4]
+    fn: torch.Tensor            # int64 [4]
+    rows: torch.Tensor          # int64 [4]
+
+
+def masked_bce_stats_views(record: torch.Tensor) -> MaskedBCEStats:
+    return MaskedBCEStats(record[0:4].view(torch.float64), record[4:8], record[8:12], record[12:16], record[16:20])
+
+
 class HipKernels:
     """libpgcn_hip.so on one MI355X.  Fails loudly when the device or library is missing."""
 
@@ -1034,6 +1047,47 @@ class HipKernels:
         _lib.check(self.lib.pgcn_masked_nll_backward_f32(X.data_ptr(), X.stride(0), labels.data_ptr(), split.data_ptr(),
                                                          lse.data_ptr(), g.data_ptr(), scale, n, C, dX.data_ptr(), dX.stride(0),
                                                          self._stream()), "pgcn_masked_nll_backward_f32")
+        return dX
+
+    def _masked_bce_ok(self, X: torch.Tensor, words: torch.Tensor, split: torch.Tensor) -> bool:
+        return (X.dim() == 2 and 0 < X.shape[1] <= 1024 and X.stride(1) == 1 and X.dtype is torch.float32 and
+                words.dtype is torch.int32 and words.dim() == 2 and words.is_contiguous() and split.dtype is torch.uint8 and
+                split.is_contiguous() and getattr(self.lib, "pgcn_masked_bce_f32", None) is not None)
+
+    def masked_bce(self, X: torch.Tensor, labels_words: torch.Tensor, split: torch.Tensor):
+        """MaskedBCEStats of pgcn_masked_bce_f32: the per-set sums of the element-wise binary cross entropy with logits, the
+        true-positive / false-positive / false-negative counts of the prediction x > 0 and the row counts of one pass over the
+        logits.  labels_words: int32 [n, ceil(C / 32)], the bit-packed labels (nodedata.pack_label_words; the uint32 words
+        viewed as int32); split: uint8 per row, 0 no set / 1 train / 2 val / 3 test.  None when the shape is not covered
+        (more than 1024 columns, another dtype or layout) or the library has no such entry point."""
+        if not self._masked_bce_ok(X, labels_words, split):
+            return None
+        n, C = X.shape
+        if tuple(labels_words.shape) != (n, (C + 31) // 32) or split.numel() != n:
+            raise _lib.PgcnError("masked_bce: %d x %d logits for label words %s, %d split codes"
+                                 % (n, C, tuple(labels_words.shape), split.numel()))
+        self._check_dense(X, n, "X")
+        record = torch.empty(20, dtype=torch.int64, device=self.device)
+        ws_bytes = int(self.lib.pgcn_masked_bce_ws_bytes(n))
+        ws = torch.empty(ws_bytes // 8, dtype=torch.int64, device=self.device)
+        _lib.check(self.lib.pgcn_masked_bce_f32(X.data_ptr(), X.stride(0), labels_words.data_ptr(), split.data_ptr(), n, C,
+                                                record.data_ptr(), ws.data_ptr(), ws_bytes, self._stream()), "pgcn_masked_bce_f32")
+        return masked_bce_stats_views(record)
+
+    def masked_bce_backward(self, X: torch.Tensor, labels_words: torch.Tensor, split: torch.Tensor, gscale: torch.Tensor,
+                            scale: float):
+        """dX = gscale * scale * (sigmoid(X) - y) on train rows, exact zeros elsewhere (pgcn_masked_bce_backward_f32), or None."""
+        if not self._masked_bce_ok(X, labels_words, split):
+            return None
+        n, C = X.shape
+        if tuple(labels_words.shape) != (n, (C + 31) // 32) or split.numel() != n:
+            raise _lib.PgcnError("masked_bce_backward: %d x %d logits for label words %s, %d split codes"
+                                 % (n, C, tuple(labels_words.shape), split.numel()))
+        dX = torch.empty((n, C), dtype=torch.float32, device=self.device)
+        g = gscale.reshape(1).to(torch.float32).contiguous()
+        _lib.check(self.lib.pgcn_masked_bce_backward_f32(X.data_ptr(), X.stride(0), labels_words.data_ptr(), split.data_ptr(),
+                                                         g.data_ptr(), scale, n, C, dX.data_ptr(), dX.stride(0),
+                                                         self._stream()), "pgcn_masked_bce_backward_f32")
         return dX
 
     def gather_rows(self, H: torch.Tensor, idx: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
