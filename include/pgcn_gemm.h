@@ -32,9 +32,11 @@ void pgcn_gemm_set_atomics(int32_t allowed);
  * class of an fp32 dot product), fused with the element-wise passes either side.  Replaces `F.relu(self.linear(AH))`
  * (GPU/PGCN.py:146-147) and the autograd of those two lines -- all three products since r06.  Row-major operands, fp32, leading
  * dimensions in elements; widths (fin, fout) up to 128; the streamed operands (X; G, Gm) need 16-byte aligned bases, leading
- * dimensions that are multiples of 4 and a width that is a multiple of 4.  Return 0; -2 for operands outside that (nothing was
- * launched: the caller runs the library product); -1 for errors (pgcn_dense_last_error() / pgcn_wgrad_last_error()).  Never
- * allocate, never synchronise.  Binding: <package>/PGCN.py (linear_relu_fused, linear_relu_grad_input_fused, weight_grad_fused),
+ * dimensions that are multiples of 4 and a width that is a multiple of 4.  Every leading dimension of a streamed operand or
+ * result (ldx, ldy; ldg, ldgm, lddx) must be below 2^25 elements (16 * ld * 4 < 2^31): the kernels address a tile's rows by
+ * 32-bit lane offsets inside a window of at most 0xfffff000 bytes; a wider stride is answered -2.  Return 0; -2 for operands
+ * outside that (nothing was launched: the caller runs the library product); -1 for errors (pgcn_dense_last_error() /
+ * pgcn_wgrad_last_error()).  Never allocate, never synchronise.  Binding: <package>/PGCN.py (linear_relu_fused, linear_relu_grad_input_fused, weight_grad_fused),
  * selected by tuning.dense_fused. */
 const char *pgcn_dense_last_error(void);
 

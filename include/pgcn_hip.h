@@ -234,7 +234,10 @@ int pgcn_spmm_heads_f32(const int64_t *rowptr, const int32_t *col, const float *
  * relative to the window; ncols >= 128 required).
  * A piece leaves 512 partial rows in slots [first slot, first slot + 512) of partial_ws for
  * pgcn_spmm_fixup_f32.  All three arrays 16-byte aligned.  f % 4 == 0 with 16-byte aligned B /
- * partial_ws takes the LDS pipeline (128 features per workgroup); anything else a plain kernel. */
+ * partial_ws takes the LDS pipeline (128 features per workgroup); anything else a plain kernel.
+ * ldb <= 34 636 829 floats: the panel copies add one 32-bit per-lane byte offset, (31 * ldb + 124) * 4,
+ * to a 64-bit base; a wider operand is refused with PGCN_EINVAL (pgcn_spmm_strip_vf_f32 likewise),
+ * whatever nwork is. */
 int pgcn_spmm_strip_f32(const int32_t *work, int64_t nwork, const int32_t *recs, const int32_t *pairs,
                         const float *B, int64_t ldb, int64_t ncols, int32_t f, float *partial_ws,
                         int64_t partial_ws_elems, int64_t nslots_total, pgcn_stream_t stream);

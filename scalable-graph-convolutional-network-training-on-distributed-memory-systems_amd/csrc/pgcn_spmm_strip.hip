@@ -59,6 +59,12 @@ constexpr int kSlotBytes = kWaveRec + 16;             // ... each followed by th
 constexpr int kOffRing = 2 * kPanelBytes;
 constexpr int kSmem = kOffRing + (kThreads / 64) * kRing * kSlotBytes;
 static_assert(kSmem <= 160 * 1024, "LDS budget of one CU");
+// The panel copies add ONE 32-bit per-lane byte offset to a 64-bit wave-uniform base: lane_off = ((tid >> 5) * ldb + c4s * 4) * 4
+// with tid >> 5 <= kThreads / 32 - 1 = 31 and c4s <= 31.  It fits 32 bits while 31 * ldb + 124 <= 2^30 - 1, i.e. ldb <= 34 636 829
+// floats; the entry points refuse a wider operand (both kernels and the generic ones, so the answer does not depend on alignment).
+constexpr int64_t kMaxLdb = ((int64_t{1} << 30) - 1 - 31 * 4) / (kThreads / 32 - 1);
+static_assert((((int64_t)(kThreads / 32 - 1) * kMaxLdb + 31 * 4) * 4) <= 0xffffffffLL &&
+              (((int64_t)(kThreads / 32 - 1) * (kMaxLdb + 1) + 31 * 4) * 4) > 0xffffffffLL, "largest ldb whose lane offset fits 32 bits");
 
 typedef __attribute__((address_space(1))) const void *gptr_t;
 typedef __attribute__((address_space(3))) void *lptr_t;
@@ -610,6 +616,8 @@ extern "C" int pgcn_spmm_strip_f32(const int32_t *work, int64_t nwork, const int
                                     const float *B, int64_t ldb, int64_t ncols, int32_t f, float *partial_ws,
                                     int64_t partial_ws_elems, int64_t nslots_total, pgcn_stream_t stream) {
     if (nwork < 0 || f <= 0 || ldb < f || ncols < TC) return pgcn_set_error(PGCN_EINVAL, "pgcn_spmm_strip_f32: bad sizes (a panel is 128 rows of B)");
+    if (ldb > kMaxLdb)
+        return pgcn_set_error(PGCN_EINVAL, "pgcn_spmm_strip_f32: leading dimension ldb too large for the 32-bit lane offsets of the panel copies (at most 34636829 floats)");
     if (nwork == 0) return PGCN_OK;
     if (!work || !recs || !pairs || !B || !partial_ws)
         return pgcn_set_error(PGCN_EINVAL, "pgcn_spmm_strip_f32: null pointer");
@@ -658,6 +666,8 @@ extern "C" int pgcn_spmm_strip_vf_f32(const int32_t *work, int64_t nwork, const 
                                        int32_t f, float *partial_ws, int64_t partial_ws_elems, int64_t nslots_total,
                                        pgcn_stream_t stream) {
     if (nwork < 0 || f <= 0 || ldb < f || ncols < TC) return pgcn_set_error(PGCN_EINVAL, "pgcn_spmm_strip_vf_f32: bad sizes (a panel is 128 rows of B)");
+    if (ldb > kMaxLdb)
+        return pgcn_set_error(PGCN_EINVAL, "pgcn_spmm_strip_vf_f32: leading dimension ldb too large for the 32-bit lane offsets of the panel copies (at most 34636829 floats)");
     if (nwork == 0) return PGCN_OK;
     if (!work || !recs || !offs || !B || !partial_ws)
         return pgcn_set_error(PGCN_EINVAL, "pgcn_spmm_strip_vf_f32: null pointer");

@@ -419,6 +419,7 @@ extern "C" int pgcn_linear_relu_grad_input_f32(const float *G, int64_t ldg, cons
     using namespace pgcn_dense;
     if (int rc = check(G, ldg, n, fout, fin, W, ldw, fout, fin, dX, lddx)) return rc;
     if (Gm && (ldgm % 4 || (uintptr_t)Gm % 16 || ldgm < fout)) return fail(-2, "pgcn_dense: rows of Gm must be 16-byte pieces");
+    if (Gm) if (int rc = check_ld(ldgm)) return rc;
     if (n == 0) return 0;
     Args a{};
     a.A = G; a.lda = ldg; a.mask_in = mask; a.Gm = Gm; a.ldgm = ldgm; a.n = n; a.K = fout; a.N = fin; a.W = W; a.ldw = ldw; a.transposed = 0;
@@ -470,6 +471,7 @@ extern "C" int pgcn_dropout_grad_input_f32(const float *G, int64_t ldg, const ui
     using namespace pgcn_dense;
     if (int rc = check(G, ldg, n, fout, fin, W, ldw, fout, fin, dX, lddx)) return rc;
     if (Gm && (ldgm % 4 || (uintptr_t)Gm % 16 || ldgm < fout)) return fail(-2, "pgcn_dense: rows of Gm must be 16-byte pieces");
+    if (Gm) if (int rc = check_ld(ldgm)) return rc;
     if (n == 0) return 0;
     Args a{};
     a.A = G; a.lda = ldg; a.mask_in = mask; a.Gm = Gm; a.ldgm = ldgm; a.n = n; a.K = fout; a.N = fin; a.W = W; a.ldw = ldw; a.transposed = 0;

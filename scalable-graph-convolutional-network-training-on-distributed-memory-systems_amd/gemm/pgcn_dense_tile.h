@@ -216,6 +216,14 @@ inline int fail(int code, const char *what) {
     return code;
 }
 
+// The lane and accumulator offsets inside a tile's window (piece_lane_offset, acc_lane_offset + 27 rows of c_row) are 32-bit and a
+// window is clamped at 0xfffff000 bytes: a tile's 32 rows, (31 ld + 128) * 4 bytes, must stay below both.  The same rule as
+// pgcn_wgrad.hip's check: 16 ld * 4 < 2^31, i.e. ld < 2^25 floats.  -2: the caller takes the library product.
+inline int check_ld(int64_t ld) {
+    if (16 * ld * 4 >= ((int64_t)1 << 31)) return fail(-2, "pgcn_dense: leading dimension too large for 32-bit lane offsets");
+    return 0;
+}
+
 inline int check(const void *A, int64_t lda, int64_t n, int K, int N, const void *W, int64_t ldw, int wrows, int wcols,
                  const void *C, int64_t ldc) {
     if (n < 0 || K <= 0 || N <= 0 || !W || (n > 0 && (!A || !C))) return fail(-1, "pgcn_dense: bad argument");
@@ -223,5 +231,6 @@ inline int check(const void *A, int64_t lda, int64_t n, int K, int N, const void
     if (K % 4 || lda % 4 || (uintptr_t)A % 16) return fail(-2, "pgcn_dense: rows of the left operand must be 16-byte pieces");
     if (lda < K || ldc < N || ldw < wcols || wrows <= 0) return fail(-1, "pgcn_dense: leading dimension below the width");
     if (n > ((int64_t)1 << 40)) return fail(-1, "pgcn_dense: n out of range");
-    return 0;
+    if (int rc = check_ld(lda)) return rc;
+    return check_ld(ldc);
 }

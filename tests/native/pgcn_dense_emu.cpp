@@ -164,6 +164,7 @@ extern "C" int pgcn_linear_relu_grad_input_f32(const float *G, int64_t ldg, cons
                                                int32_t fout, const float *W, int64_t ldw, int32_t fin, float *dX, int64_t lddx, void *) {
     if (int rc = check(G, ldg, n, fout, fin, W, ldw, fout, fin, dX, lddx)) return rc;
     if (Gm && (ldgm % 4 || (uintptr_t)Gm % 16 || ldgm < fout)) return fail(-2, "pgcn_dense: rows of Gm must be 16-byte pieces");
+    if (Gm) if (int rc = check_ld(ldgm)) return rc;
     if (n == 0) return 0;
     EmuArgs a{};
     a.A = G; a.lda = ldg; a.mask_in = mask; a.Gm = Gm; a.ldgm = ldgm; a.n = n; a.K = fout; a.N = fin; a.W = W; a.ldw = ldw; a.transposed = 0;

@@ -134,6 +134,24 @@ def test_error_reporting_without_gpu():
     assert L.pgcn_gather_rows_f32(None, 8, None, 3, None, 8, 8, None) == -1
 
 
+def test_strip_entry_points_refuse_a_leading_dimension_beyond_their_32_bit_lane_offsets():
+    """The panel copies of pgcn_spmm_strip_f32 / _vf_f32 add one 32-bit per-lane byte offset, ((tid >> 5) * ldb + 4 * chunk) * 4 with
+    tid >> 5 <= 31 and chunk <= 31, to a 64-bit base: it fits while ldb <= (2^30 - 1 - 124) / 31 = 34 636 829 floats.  A wider operand
+    is refused in the size check, before the nwork == 0 return (nothing launches with nwork = 0: no GPU needed)."""
+    L = pkg("_lib").lib()
+    limit = (2 ** 30 - 1 - 124) // 31
+    assert (31 * limit + 124) * 4 < 2 ** 32 <= (31 * (limit + 1) + 124) * 4
+    for ldb, want in ((2 ** 26, -1), (limit + 1, -1), (limit, 0), (2 ** 20, 0)):
+        assert L.pgcn_spmm_strip_f32(None, 0, None, None, None, ldb, 128, 128, None, 0, 0, None) == want, ldb
+        if want:
+            msg = L.pgcn_last_error()
+            assert b"pgcn_spmm_strip_f32" in msg and b"leading dimension" in msg and b"ldb" in msg, msg
+        assert L.pgcn_spmm_strip_vf_f32(None, 0, None, None, None, None, None, ldb, 128, 128, None, 0, 0, None) == want, ldb
+        if want:
+            msg = L.pgcn_last_error()
+            assert b"pgcn_spmm_strip_vf_f32" in msg and b"leading dimension" in msg and b"ldb" in msg, msg
+
+
 def test_product_refuses_to_run_without_a_hip_device():
     import torch
     if torch.cuda.is_available():

@@ -149,6 +149,63 @@ def test_refusals_are_minus_two_and_errors_minus_one(emu):
     assert emu.pgcn_linear_relu_f32(y.data_ptr(), 2, 4, 4, y.data_ptr(), 4, 4, y.data_ptr(), 4, 1, None, None) != 0   # ld below the width
 
 
+def test_leading_dimensions_beyond_the_32_bit_lane_offsets_are_refused(emu, monkeypatch):
+    """The lane and accumulator offsets inside a tile's window are 32-bit and a window holds at most 0xfffff000 bytes: a leading
+    dimension of 2^25 floats or more (16 ld 4 >= 2^31, the rule of pgcn_linear_weight_grad_f32) on X / Y, G / Gm / dX is answered -2
+    before anything runs (n = 0 and a stride that no allocation backs), the largest one below is taken, and the layer falls back to
+    the library product."""
+    P, tuning = pkg("PGCN"), pkg("tuning")
+    big, ok = 2 ** 25, 2 ** 25 - 4
+    w = torch.randn(8, 8)
+    base = torch.zeros(16).data_ptr()
+    base -= base % 16
+    for ldx, ldy, want in ((big, 8, -2), (8, big, -2), (ok, ok, 0), (2 ** 40, 8, -2)):
+        assert emu.pgcn_linear_relu_f32(base, ldx, 0, 8, w.data_ptr(), 8, 8, base, ldy, 1, None, None) == want, (ldx, ldy)
+        if want:
+            assert b"leading dimension too large" in emu.pgcn_dense_last_error()
+    for ldg, ldgm, lddx, want in ((big, 8, 8, -2), (8, big, 8, -2), (8, 8, big, -2), (ok, ok, ok, 0)):
+        assert emu.pgcn_linear_relu_grad_input_f32(base, ldg, None, base, ldgm, 0, 8, w.data_ptr(), 8, 8, base, lddx, None) == want
+        if want:
+            assert b"leading dimension too large" in emu.pgcn_dense_last_error()
+    assert emu.pgcn_linear_relu_grad_input_f32(base, 8, None, None, big, 0, 8, w.data_ptr(), 8, 8, base, 8, None) == 0   # no Gm: ldgm unused
+    # two rows 2^25 floats apart (128 MiB of untouched address space between them): the entry point answers -2 inside the autograd
+    # node too, which then takes the library product for the forward and, in the backward, for a gradient of that stride
+    calls = []
+
+    class Counting:
+        def __getattr__(self, name):
+            fn = getattr(emu, name)
+            if not name.startswith("pgcn_linear_relu"):
+                return fn
+
+            def call(*a):
+                rc = fn(*a)
+                calls.append((name, rc))
+                return rc
+            return call
+    monkeypatch.setattr(P, "_dense_operand_ok", lambda *ts: all(t.dim() == 2 and t.stride(1) == 1 for t in ts))
+    monkeypatch.setattr(P, "_dense_stream", lambda t: None)
+    monkeypatch.setattr(P, "_dense_lib", lambda: Counting())
+    monkeypatch.setattr(tuning.T, "dense_fused", 2)
+    x0 = torch.randn(2, 8)
+    x = torch.empty(big + 8).as_strided((2, 8), (big, 1))
+    x.copy_(x0)
+    assert x.stride(0) == big and P.linear_relu_fused(x, w) is None and calls == [("pgcn_linear_relu_f32", -2)]
+    assert P.linear_relu_fused(x0, w) is not None and calls[-1] == ("pgcn_linear_relu_f32", 0)
+    assert P.linear_relu_grad_input_fused(x, None, w) is None and calls[-1] == ("pgcn_linear_relu_grad_input_f32", -2)
+    del calls[:]
+    xs, wr = x.detach().requires_grad_(True), w.clone().requires_grad_(True)
+    y = P._LinearReluNoBias.apply(xs, wr)
+    assert calls == [("pgcn_linear_relu_f32", -2)]                  # refused inside the node: the library product made y
+    xc, wc = x0.clone().requires_grad_(True), w.clone().requires_grad_(True)
+    yc = (xc @ wc.t()).clamp_min(0)
+    assert torch.allclose(y, yc, atol=1e-5)
+    coef = torch.arange(16.0).reshape(2, 8)
+    (y * coef).sum().backward()
+    (yc * coef).sum().backward()
+    assert torch.allclose(xs.grad, xc.grad, atol=1e-5) and torch.allclose(wr.grad, wc.grad, atol=1e-5)
+
+
 def test_autograd_node_through_the_host_build(emu, monkeypatch):
     """PGCN._LinearReluNoBias with tuning.dense_fused >= 2 takes both entry points (here: the host build on CPU tensors), the
     sign mask travelling from the forward to the backward instead of y, and agrees with the stock route; level 0 never touches them."""
