@@ -526,6 +526,24 @@ int pgcn_masked_bce_backward_f32(const float *X, int64_t ldx, const uint32_t *la
                                  const float *gscale_dev, float scale, int64_t nrows, int32_t C, float *dX, int64_t lddx,
                                  pgcn_stream_t stream);
 
+/* ---- the optimiser step: Adam / AdamW over a flat fp32 arena in one launch (optim.py: FlatAdam) ----------------
+ * p, g, m, v: n floats each (parameters, gradients, first and second moments), four arrays that do not overlap.
+ * step: DEVICE pointer to one int64, the number of updates already made -- the kernel uses t = *step + 1 and never writes it
+ * (the caller adds 1 on the device after the launch), so a replayed graph applies the bias correction of its own replay.
+ * Per element, in the order of operations of torch.optim.Adam / AdamW (amsgrad and maximize off), scalars rounded to fp32
+ * where torch's fp32 kernels round theirs:
+ *   gi = g * grad_scale;   decoupled == 0: gi += weight_decay * p (when weight_decay != 0);   else: p *= 1 - lr * weight_decay
+ *   m += (gi - m) * (1 - beta1);   v = beta2 * v + (1 - beta2) * gi * gi
+ *   p -= (lr / (1 - beta1^t)) * (m / (sqrt(v) / sqrt(1 - beta2^t) + eps));   zero_grad != 0: g = 0 after it was read
+ * An element with p = g = m = v = 0 stays all zero when eps > 0 (padding between the segments of an arena).
+ * One float4 per lane and array when all four bases are 16-byte aligned (n % 4 elements in a scalar tail), element by element
+ * otherwise; a grid-stride loop over at most 256 blocks.  n == 0: PGCN_OK, nothing launched.  PGCN_EINVAL, nothing launched:
+ * n < 0, a null pointer, lr / beta1 / beta2 / eps / weight_decay non-finite or negative, a beta >= 1, a non-finite
+ * grad_scale.  Raw pointers + a stream, no allocation, no synchronisation, no atomics (graph-capturable).               */
+int pgcn_adam_step_f32(float *p, float *g, float *m, float *v, int64_t n, double lr, double beta1, double beta2, double eps,
+                       double weight_decay, int32_t decoupled, float grad_scale, int32_t zero_grad, const int64_t *step,
+                       pgcn_stream_t stream);
+
 /* ---- boundary-row pack / unpack -------------------------------------------
  * out[r,:] = H[idx[r],:]                      replaces H[indices]   GPU/PGCN.py:104
  * H[idx[r],:] (+)= in[r,:]                    replaces X[indices] = buf   :115

@@ -39,6 +39,7 @@ from . import engine as _engine
 from . import ingest as _ingest
 from . import kernels as _kernels
 from . import nodedata as _nodedata
+from . import optim as _optim
 from . import partition as _partition
 
 # module-level state, same names as PGCN.py:23-35
@@ -1138,13 +1139,19 @@ def evaluate_multilabel(model, H, labels_words, split):
     return _global_stats_multilabel(st, logits.shape[1])
 
 
+OPTIMIZERS = ("torch", "fused")       # --optimizer / run(optimizer=...): torch.optim.Adam[W] (the default) or optim.FlatAdam
+
+
 def _train_on_data(A, n, nlayers, nfeatures, features, labels, split, hidden, epochs, lr, eval_every, dropout, dropout_seed,
-                   multilabel=False):
+                   multilabel=False, weight_decay=0.0, decoupled_decay=False, optimizer="torch"):
     """The loop of ``run`` on real inputs: widths fin -> hidden -> ... -> C, no ReLU on the last layer, constant features (the
     first layer's backward aggregation is skipped), Adam, the masked loss over the train rows.  Reports every ``eval_every``
     epochs: without dropout from the record of the training step's own pass (the logits BEFORE that step's update), with
     dropout from ``evaluate`` after the update.  ``multilabel``: the labels are an n x C 0 / 1 matrix, the loss is the masked
-    binary cross entropy with logits and the reported score the micro-F1 (``masked_bce_loss`` / ``evaluate_multilabel``)."""
+    binary cross entropy with logits and the reported score the micro-F1 (``masked_bce_loss`` / ``evaluate_multilabel``).
+    ``weight_decay``: Adam's L2 term, or with ``decoupled_decay`` AdamW's decay.  ``optimizer="fused"``: optim.FlatAdam -- the
+    gradients accumulate in a flat arena, the step ends with one in-place all-reduce and one kernel launch that also clears them;
+    "torch" keeps ``zero_grad`` / ``average_gradients`` / torch's optimiser."""
     load = _nodedata.load_multilabel if multilabel else _nodedata.load
     data = load(features, labels, split, A.part.owned, n, device=device)
     hidden = int(nfeatures if hidden is None else hidden)
@@ -1162,7 +1169,15 @@ def _train_on_data(A, n, nlayers, nfeatures, features, labels, split, hidden, ep
     model = nn.Sequential(*[PGCN(A, widths[i], widths[i + 1], dropout=dropout if i < nlayers - 1 else 0.0, layer=i, state=state,
                                  relu=i < nlayers - 1) for i in range(nlayers)]).to(device)
     initiliaze_parameters(model)
-    optimizer = torch.optim.Adam(model.parameters(), lr=lr)
+    fused = None
+    if optimizer == "fused":
+        fused = _optim.FlatAdam(model.parameters(), lr=lr, weight_decay=weight_decay, decoupled=decoupled_decay)
+    elif decoupled_decay:
+        opt = torch.optim.AdamW(model.parameters(), lr=lr, weight_decay=weight_decay)
+    elif weight_decay:
+        opt = torch.optim.Adam(model.parameters(), lr=lr, weight_decay=weight_decay)
+    else:
+        opt = torch.optim.Adam(model.parameters(), lr=lr)
     H, y, s = data.features, data.labels, data.split           # (H needs no gradient)
 
     history, best = [], None
@@ -1172,10 +1187,15 @@ def _train_on_data(A, n, nlayers, nfeatures, features, labels, split, hidden, ep
     for epoch in range(epochs):
         model.train()
         loss, st = (masked_bce_loss if multilabel else masked_loss)(model(H), y, s, n_train)
-        optimizer.zero_grad()
-        loss.backward()
-        average_gradients(model, average=False)
-        optimizer.step()
+        if fused is not None:
+            loss.backward()
+            fused.reduce_gradients(average=False)
+            fused.step()
+        else:
+            opt.zero_grad()
+            loss.backward()
+            average_gradients(model, average=False)
+            opt.step()
         if state is not None:
             state.advance()
         if multilabel and (epoch % eval_every == 0 or epoch == epochs - 1):
@@ -1218,7 +1238,8 @@ TASKS = ("single", "multilabel")       # --task / run(task=...): one class per v
 
 
 def run(rank, size, nlayers, nfeatures, path_A, path_partvec, backend, normalize=None, dropout=0.0, dropout_seed=0,
-        features=None, labels=None, split=None, hidden=None, epochs=None, lr=None, eval_every=None, task=None):
+        features=None, labels=None, split=None, hidden=None, epochs=None, lr=None, eval_every=None, task=None,
+        weight_decay=None, decoupled_decay=None, optimizer=None):
     """PGCN.py:162-238.  ``normalize="sym"``: train on D_r^-1/2 (A + I) D_c^-1/2 of the pattern of ``path_A``, built on the fly
     (partition.build_partition) instead of by the offline pass preprocess/GrB-GNN-IDG.py.  ``dropout`` > 0: the output of every
     layer but the last is dropped with that probability (class PGCN), masks from (``dropout_seed``, step, layer, global row,
@@ -1228,7 +1249,9 @@ def run(rank, size, nlayers, nfeatures, path_A, path_partvec, backend, normalize
     classifier on them instead of the synthetic loop -- ``_train_on_data``; ``hidden`` (default ``nfeatures``), ``epochs`` (4),
     ``lr`` (1e-3), ``eval_every`` (1).  The returned model carries ``history`` (the reported epochs) and ``best``.
     ``task`` (needs the three files): None or "single" = one class per vertex (int64 label vector, softmax loss, accuracy);
-    "multilabel" = an n x C uint8 matrix of 0 / 1, the masked binary cross entropy with logits, micro-F1."""
+    "multilabel" = an n x C uint8 matrix of 0 / 1, the masked binary cross entropy with logits, micro-F1.
+    ``weight_decay`` (a float >= 0), ``decoupled_decay`` (True: AdamW's decay instead of an L2 term) and ``optimizer`` ("torch",
+    the default, or "fused" = optim.FlatAdam) need the three files too."""
     global myrank, world_size, send_map, recv_map, device, X, recv_buffers, send_buffers, stats
     myrank = rank
     world_size = size
@@ -1240,6 +1263,12 @@ def run(rank, size, nlayers, nfeatures, path_A, path_partvec, backend, normalize
     if task is not None and not all(given):
         raise ValueError("task=%r needs features, labels and split" % (task,))
     multilabel = task == "multilabel"
+    if optimizer not in OPTIMIZERS + (None,):
+        raise ValueError("optimizer takes %s, got %r" % (" | ".join(OPTIMIZERS), optimizer))
+    if weight_decay is not None and not (math.isfinite(float(weight_decay)) and float(weight_decay) >= 0.0):
+        raise ValueError("weight_decay must be a finite number >= 0, got %r" % (weight_decay,))
+    if not all(given) and (weight_decay is not None or decoupled_decay is not None or optimizer is not None):
+        raise ValueError("weight_decay, decoupled_decay and optimizer need features, labels and split")
     if torch.cuda.is_available():
         device = torch.device(f'cuda:{myrank % torch.cuda.device_count()}')
         torch.cuda.set_device(device)
@@ -1292,7 +1321,7 @@ def run(rank, size, nlayers, nfeatures, path_A, path_partvec, backend, normalize
 
     if all(given):
         return _train_on_data(A, n, nlayers, nfeatures, features, labels, split, hidden, epochs, lr, eval_every, dropout,
-                              dropout_seed, multilabel)
+                              dropout_seed, multilabel, float(weight_decay or 0.0), bool(decoupled_decay), optimizer or "torch")
 
     owned = A.part.owned.to(device)
     # PGCN.py:186-188 synthetic features H[i,:] = i, owned rows only
@@ -1366,7 +1395,8 @@ def run(rank, size, nlayers, nfeatures, path_A, path_partvec, backend, normalize
 
 
 def init_process(rank, size, fn, nlayers, nfeatures, path_A, path_partvec, backend, normalize=None, dropout=0.0, dropout_seed=0,
-                 features=None, labels=None, split=None, hidden=None, epochs=None, lr=None, eval_every=None, task=None):
+                 features=None, labels=None, split=None, hidden=None, epochs=None, lr=None, eval_every=None, task=None,
+                 weight_decay=None, decoupled_decay=None, optimizer=None):
     """PGCN.py:241-253."""
     global _exchanger
     dist.init_process_group(backend, rank=rank, world_size=size)
@@ -1383,7 +1413,8 @@ def init_process(rank, size, fn, nlayers, nfeatures, path_A, path_partvec, backe
     if dropout > 0.0:
         kw["dropout"], kw["dropout_seed"] = dropout, dropout_seed
     for name, v in (("features", features), ("labels", labels), ("split", split), ("hidden", hidden), ("epochs", epochs), ("lr", lr),
-                    ("eval_every", eval_every), ("task", task)):
+                    ("eval_every", eval_every), ("task", task), ("weight_decay", weight_decay), ("decoupled_decay", decoupled_decay),
+                    ("optimizer", optimizer)):
         if v is not None:
             kw[name] = v
     fn(rank, size, nlayers, nfeatures, path_A, path_partvec, backend, **kw)     # (no option given: today's call)
@@ -1407,7 +1438,8 @@ def main(argv):
     data = {}          # the node-classification options that were given (run's keyword arguments)
     try:
         opts, args = getopt.getopt(argv, "a:p:b:s:l:f:", ["normalize=", "dropout=", "dropout-seed=", "features=", "labels=", "split=",
-                                                          "hidden=", "epochs=", "lr=", "eval-every=", "task="])
+                                                          "hidden=", "epochs=", "lr=", "eval-every=", "task=", "weight-decay=", "adamw",
+                                                          "optimizer="])
     except getopt.GetoptError:
         print("a:p:b:", flush=True)
         sys.exit(2)
@@ -1445,6 +1477,21 @@ def main(argv):
                 print("--task takes %s, got %r" % ("|".join(TASKS), arg), flush=True)
                 sys.exit(2)
             data["task"] = arg
+        elif opt == '--weight-decay':  # Adam's L2 term; with --adamw the decoupled decay of AdamW
+            try:
+                data["weight_decay"] = float(arg)
+                if not (data["weight_decay"] >= 0.0 and math.isfinite(data["weight_decay"])):
+                    raise ValueError
+            except ValueError:
+                print("--weight-decay takes a number >= 0, got %r" % arg, flush=True)
+                sys.exit(2)
+        elif opt == '--adamw':
+            data["decoupled_decay"] = True
+        elif opt == '--optimizer':     # torch (torch.optim.Adam / AdamW, the default) | fused (optim.FlatAdam: one launch per step)
+            if arg not in OPTIMIZERS:
+                print("--optimizer takes %s, got %r" % ("|".join(OPTIMIZERS), arg), flush=True)
+                sys.exit(2)
+            data["optimizer"] = arg
         elif opt == '--lr':
             try:
                 data["lr"] = float(arg)
@@ -1468,8 +1515,8 @@ def main(argv):
     os.environ.setdefault("WORLD_SIZE", str(size))
     files = [k for k in ("features", "labels", "split") if k in data]
     if data and len(files) != 3:
-        print("--features, --labels and --split go together (and --hidden, --epochs, --lr, --eval-every, --task need them); got %s"
-              % ", ".join("--" + k.replace("_", "-") for k in sorted(data)), flush=True)
+        print("--features, --labels and --split go together (and --hidden, --epochs, --lr, --eval-every, --task, --weight-decay, --adamw, --optimizer need them); got %s"
+              % ", ".join("--" + {"decoupled_decay": "adamw"}.get(k, k.replace("_", "-")) for k in sorted(data)), flush=True)
         sys.exit(2)
     for k in files:
         if not os.path.exists(data[k]):
@@ -1482,6 +1529,9 @@ def main(argv):
         args += (dropout, dropout_seed)
     if data:
         args += tuple(data.get(k) for k in ("features", "labels", "split", "hidden", "epochs", "lr", "eval_every", "task"))
+        extra = tuple(data.get(k) for k in ("weight_decay", "decoupled_decay", "optimizer"))
+        if any(v is not None for v in extra):      # (none of the three given: the argument tuple of before)
+            args += extra
     p = mp.Process(target=init_process, args=args)
     p.start()
     p.join()

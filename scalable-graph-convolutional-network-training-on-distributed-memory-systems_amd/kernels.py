@@ -1090,6 +1090,24 @@ class HipKernels:
                                                          self._stream()), "pgcn_masked_bce_backward_f32")
         return dX
 
+    def adam_step(self, p: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: torch.Tensor, step: torch.Tensor, lr: float, betas,
+                  eps: float, weight_decay: float, decoupled: bool, grad_scale: float, zero_grad: bool):
+        """One Adam / AdamW update of the flat fp32 arrays p, m, v from g in ONE launch (pgcn_adam_step_f32; optim.FlatAdam), in
+        place; ``step``: one int64 on the device, the updates already made (read, never written: the caller adds 1).  Returns
+        True, or None for what the kernel does not cover (another dtype, non-contiguous tensors, tensors of different devices or
+        lengths, a CPU tensor): the caller takes the composition."""
+        ts = (p, g, m, v)
+        if not all(t.is_cuda and t.device == p.device and t.dtype is torch.float32 and t.is_contiguous() and t.numel() == p.numel()
+                   for t in ts):
+            return None
+        if not (step.device == p.device == self.device and step.dtype is torch.int64 and step.numel() == 1):
+            return None
+        _lib.check(self.lib.pgcn_adam_step_f32(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel(), float(lr),
+                                               float(betas[0]), float(betas[1]), float(eps), float(weight_decay),
+                                               1 if decoupled else 0, float(grad_scale), 1 if zero_grad else 0, step.data_ptr(),
+                                               self._stream()), "pgcn_adam_step_f32")
+        return True
+
     def gather_rows(self, H: torch.Tensor, idx: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
         n = idx.numel()
         if n == 0:
