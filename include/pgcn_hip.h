@@ -544,6 +544,54 @@ int pgcn_adam_step_f32(float *p, float *g, float *m, float *v, int64_t n, double
                        double weight_decay, int32_t decoupled, float grad_scale, int32_t zero_grad, const int64_t *step,
                        pgcn_stream_t stream);
 
+/* ---- batch normalisation over all vertices, fused with ReLU and dropout (PGCN.py: _BatchNormReluDropout) ----------
+ * The layer y = drop(relu(BN(x))) of an nrows x f block of OWNED rows whose statistics are those of ALL ranks' rows:
+ *   forward   pgcn_bn_colstats_f32  ->  [one float64 all-reduce of 2 f + 1 numbers]  ->  pgcn_bn_prepare_f32  ->  pgcn_bn_relu_apply_f32
+ *   backward  pgcn_bn_backward_stats_f32  ->  [one float64 all-reduce of 2 f numbers]  ->  pgcn_bn_relu_backward_f32
+ * pgcn_bn_colstats_f32: sums[0 .. f) = sum_i X[i,j], sums[f .. 2 f) = sum_i X[i,j]^2, sums[2 f] = nrows -- all doubles,
+ *   added in double.  A block owns 512 consecutive rows and writes one partial record [2][f] to `ws`
+ *   (pgcn_bn_colstats_ws_bytes(nrows, f) bytes, 8-byte aligned; -1 for sizes the kernels refuse); a second launch, 32 of the
+ *   2 f outputs per block, adds the records in a fixed order: no floating-point atomics, the same input gives the same bits.
+ *   nrows == 0: zero sums (and the count 0), nothing else written.
+ * pgcn_bn_prepare_f32 (one block; reads the sums from DEVICE memory: no host wait between the all-reduce and the apply):
+ *   training != 0:  N = sums[2 f];  mean = sums[j] / N;  var = max(sums[f + j] / N - mean^2, 0)  (biased, in double);
+ *     invstd = 1 / sqrt(var + eps);  mean[j], invstd[j] rounded to fp32 (the saved tensors of the backward);
+ *     running_mean = (1 - momentum) running_mean + momentum mean,  running_var likewise with var N / (N - 1) (var when N = 1),
+ *     formed in double, in place, on EVERY call (a replayed graph updates them at every replay); either may be NULL (no record);
+ *     N < 1 (no vertex anywhere): mean 0, invstd 1 / sqrt(eps), no update.
+ *   training == 0:  mean = running_mean, invstd = 1 / sqrt(running_var + eps); sums is not read and may be NULL.
+ * pgcn_bn_relu_apply_f32:  Y[i,j] = keep ? max(0, fma(gamma[j] invstd[j], X[i,j] - mean[j], beta[j])) * scale : 0.
+ *   step == NULL or thr == 0: keep is true and scale 1.  Otherwise keep / scale are those of gemm/pgcn_dropout.h with the key
+ *   (seed, *step, layer, row_ids[i] (NULL: i), j): the masks the fused dense kernel draws for that layer; *step is read from
+ *   device memory, the column's share of the hash is formed once per column.
+ * pgcn_bn_backward_stats_f32: with g' = Y > 0 ? G * scale : 0 (the saved output is its own mask: Y > 0 exactly where the
+ *   element was kept and its pre-activation positive) and xh = (X - mean) invstd:
+ *   sums[0 .. f) = sum_i g'[i,j], sums[f .. 2 f) = sum_i g'[i,j] xh[i,j] (doubles), and from THESE rank-local sums
+ *   dbeta[j] = float(sums[j]), dgamma[j] = float(sums[f + j]) (either may be NULL) -- written here, by the second-level launch,
+ *   before the all-reduce makes the sums global: the training loop adds the ranks' parameter gradients itself.
+ * pgcn_bn_relu_backward_f32: dX[i,j] = gamma[j] invstd[j] (g' - S1[j] / N - xh S2[j] / N) with the GLOBAL sums (S1 = sums[0 .. f),
+ *   S2 = sums[f .. 2 f), read from device memory) and the global vertex count N.
+ * All: row-major with leading dimensions in elements; every f from 1 to 1024 (PGCN_EUNSUPPORTED above); a thread owns four
+ * consecutive columns -- one float4 when f % 4 == 0 and every base and leading dimension keeps rows 16-byte aligned, four
+ * guarded scalars otherwise, the same additions in the same order either way (the same bits).  PGCN_EINVAL, nothing launched:
+ * a null pointer, nrows < 0, f < 1, a leading dimension below f, eps non-finite or <= 0, momentum outside [0, 1], N < 1, a
+ * scale that is not finite and positive, a misaligned sums / ws / step / row_ids; PGCN_ENOMEM: ws_bytes too small.  A NaN or inf
+ * stays in its own column.  Raw pointers + a stream, no allocation, no synchronisation (graph-capturable).                */
+int64_t pgcn_bn_colstats_ws_bytes(int64_t nrows, int32_t f);
+int pgcn_bn_colstats_f32(const float *X, int64_t ldx, int64_t nrows, int32_t f, double *sums, void *ws, int64_t ws_bytes,
+                         pgcn_stream_t stream);
+int pgcn_bn_prepare_f32(const double *sums, int32_t f, double eps, double momentum, int32_t training, float *running_mean,
+                        float *running_var, float *mean, float *invstd, pgcn_stream_t stream);
+int pgcn_bn_relu_apply_f32(const float *X, int64_t ldx, int64_t nrows, int32_t f, const float *mean, const float *invstd,
+                           const float *gamma, const float *beta, const int64_t *row_ids, uint64_t seed, const int64_t *step,
+                           uint32_t layer, uint32_t thr, float *Y, int64_t ldy, pgcn_stream_t stream);
+int pgcn_bn_backward_stats_f32(const float *G, int64_t ldg, const float *Y, int64_t ldy, const float *X, int64_t ldx, int64_t nrows,
+                               int32_t f, const float *mean, const float *invstd, float scale, double *sums, float *dgamma,
+                               float *dbeta, void *ws, int64_t ws_bytes, pgcn_stream_t stream);
+int pgcn_bn_relu_backward_f32(const float *G, int64_t ldg, const float *Y, int64_t ldy, const float *X, int64_t ldx, int64_t nrows,
+                              int32_t f, const float *mean, const float *invstd, const float *gamma, const double *sums, int64_t N,
+                              float scale, float *dX, int64_t lddx, pgcn_stream_t stream);
+
 /* ---- boundary-row pack / unpack -------------------------------------------
  * out[r,:] = H[idx[r],:]                      replaces H[indices]   GPU/PGCN.py:104
  * H[idx[r],:] (+)= in[r,:]                    replaces X[indices] = buf   :115

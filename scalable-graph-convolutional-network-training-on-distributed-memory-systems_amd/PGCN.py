@@ -681,6 +681,145 @@ class _LinearReluDropoutNoBias(torch.autograd.Function):
         return gx, gw, None, None, None, None, None
 
 
+# ---- batch normalisation over ALL vertices of the graph, fused with ReLU and dropout (csrc/pgcn_norm.hip) -------------------------
+NORMS = ("none", "batch")       # --norm / run(norm=...): "none" (the default) is the layer of before
+
+
+def _bn_keep(X, row_ids, state, layer, thr):
+    """bool [n, f]: the keep bits of dropout.py for this layer and step (CPU: the host statement; GPU: the words kernel)."""
+    n, f = X.shape
+    if X.is_cuda:
+        words = dropout_keep_words_call(_dense_lib(), row_ids, n, f, state.seed, state.step, layer, thr, _dense_stream(X))
+        return unpack_sign_mask(words, f)
+    ids = row_ids if row_ids is not None else torch.arange(n)
+    return _dropout.keep_mask(state.seed, state.host_step(), layer, ids, f, thr)
+
+
+def batchnorm_relu_composed(X, gamma, beta, running_mean=None, running_var=None, training=True, momentum=0.1, eps=1e-5,
+                            row_ids=None, state=None, layer=0, thr=0, scale=1.0):
+    """(Y, mean, invstd) of drop(relu(BN(X))) from framework operations, the definitions of csrc/pgcn_norm.hip: column sums of
+    X and X^2 over THIS rank's rows in float64, ONE float64 all-reduce of those 2 f numbers and the row count (``_all_reduce``;
+    none on one rank), mean / biased variance / invstd in float64 and rounded to X's precision, the running statistics updated in
+    place (unbiased variance, torch's rule), Y = keep ? max(0, gamma invstd (X - mean) + beta) * scale : 0.  ``training=False``:
+    the running statistics, no reduction, no dropout.  For CPU tensors, the checker-backed provider of the tests and f > 1024."""
+    n, f = X.shape
+    if training:
+        Xd = X.detach().double()
+        sums = torch.cat([Xd.sum(0), (Xd * Xd).sum(0), torch.full((1,), float(n), dtype=torch.float64, device=X.device)])
+        if world_size > 1:
+            _all_reduce(sums)
+        N = sums[2 * f]
+        Nc = N.clamp_min(1.0)
+        m = sums[:f] / Nc
+        var = sums[f:2 * f] / Nc - m * m
+        var = torch.where(var < 0, torch.zeros_like(var), var)                      # (NaN stays NaN)
+        mean, invstd = m.to(X.dtype), torch.rsqrt(var + eps).to(X.dtype)
+        with torch.no_grad():
+            has = (N >= 1.0)
+            if running_mean is not None:
+                new = ((1.0 - momentum) * running_mean.double() + momentum * m).to(running_mean.dtype)
+                running_mean.copy_(torch.where(has, new, running_mean))
+            if running_var is not None:
+                unbiased = torch.where(N > 1.0, var * (N / (N - 1.0).clamp_min(1.0)), var)
+                new = ((1.0 - momentum) * running_var.double() + momentum * unbiased).to(running_var.dtype)
+                running_var.copy_(torch.where(has, new, running_var))
+    else:
+        mean, invstd = running_mean.to(X.dtype), torch.rsqrt(running_var.double() + eps).to(X.dtype)
+    a = gamma.detach() * invstd
+    Y = torch.addcmul(beta.detach(), X.detach() - mean, a).clamp_min(0.0)
+    if training and state is not None and thr > 0:
+        Y = torch.where(_bn_keep(X, row_ids, state, layer, thr), Y * scale, torch.zeros((), dtype=Y.dtype, device=Y.device))
+    return Y, mean, invstd
+
+
+def batchnorm_relu_backward_composed(G, Y, X, mean, invstd, gamma, n_global, scale=1.0, training=True):
+    """(dX, dgamma, dbeta) of the same layer: g' = Y > 0 ? G scale : 0 (the saved output is its own mask), xh = (X - mean) invstd,
+    S1 = sum g', S2 = sum g' xh in float64 -- dbeta and dgamma are THIS rank's sums (the training loop adds the ranks' parameter
+    gradients itself), ONE float64 all-reduce makes them global for dX = gamma invstd (g' - S1 / N - xh S2 / N).
+    ``training=False``: mean and invstd were constants, dX = gamma invstd g', no reduction."""
+    gm = torch.where(Y > 0, G * scale, torch.zeros((), dtype=G.dtype, device=G.device))
+    xh = (X - mean) * invstd
+    xhd = (X.double() - mean.double()) * invstd.double()        # (in double for the sum: S2 cancels, xh's fp32 rounding would not)
+    sums = torch.cat([gm.double().sum(0), (gm.double() * torch.where(Y > 0, xhd, torch.zeros_like(xhd))).sum(0)])
+    f = X.shape[1]
+    dbeta, dgamma = sums[:f].to(X.dtype), sums[f:].to(X.dtype)
+    a = gamma.detach() * invstd
+    if not training:
+        return a * gm, dgamma, dbeta
+    if world_size > 1:
+        _all_reduce(sums)
+    c1, c2 = (sums[:f] / float(n_global)).to(X.dtype), (sums[f:] / float(n_global)).to(X.dtype)
+    return a * ((gm - c1) - xh * c2), dgamma, dbeta
+
+
+def _bn_kernels(X, vectors=(), row_ids=None):
+    """The provider whose batch-norm kernels take X and the per-column vectors, or None (CPU tensors, the checker-backed provider of
+    the tests, more than 1024 columns, another dtype or layout).  Decided BEFORE the first launch: a step never changes route
+    between its collectives."""
+    k = _kernel_provider if _kernel_provider is not None else getattr(_engine_current, "k", None)
+    if k is None or not hasattr(k, "bn_colstats") or not (X.is_cuda and X.dim() == 2 and X.dtype is torch.float32 and 0 < X.shape[1] <= _kernels.BN_MAX_F
+                                                          and (X.stride(1) == 1 or X.shape[1] == 1 or X.shape[0] == 0)):
+        return None
+    if not all(v.is_cuda and v.device == X.device and v.dtype is torch.float32 and v.is_contiguous() and v.numel() == X.shape[1]
+               for v in vectors):
+        return None
+    return k if _row_ids_ok(row_ids, X.shape[0]) and (row_ids is None or row_ids.device == X.device) else None
+
+
+def _bn_must(out, what):
+    if out is None:
+        raise RuntimeError("%s refused operands that _bn_kernels accepted" % what)
+    return out
+
+
+class _BatchNormReluDropout(torch.autograd.Function):
+    """drop(relu(BN(X))) as ONE autograd node whose statistics are those of all ranks' rows.  Forward on a HIP device: column sums
+    (two launches) -> one float64 all-reduce of 2 f + 1 numbers -> a one-block kernel that leaves mean / invstd and updates the
+    running statistics from device memory -> one pass that writes Y.  Backward: column sums of g' and g' xh (their second launch also
+    writes dgamma and dbeta from the LOCAL sums) -> one float64 all-reduce of 2 f numbers -> one pass that writes dX.  Saved: X, Y,
+    mean, invstd -- no mask tensor: Y > 0 exactly where the element was kept and its pre-activation positive.  ``stats``: the tuple
+    (running_mean, running_var) -- buffers, updated in place in training mode, read in eval mode.  Anything the kernels do not
+    cover (CPU tensors, f > 1024, the checker-backed provider) takes ``batchnorm_relu_composed``: the same definitions."""
+
+    @staticmethod
+    def forward(ctx, X, gamma, beta, stats, training, momentum, eps, n_global, row_ids, state, layer, thr, scale):
+        rm, rv = stats
+        drop = bool(training and state is not None and thr > 0)
+        k = _bn_kernels(X, (gamma, beta, rm, rv), row_ids if drop else None)
+        if k is not None:
+            sums = None
+            if training:
+                sums = _bn_must(k.bn_colstats(X), "bn_colstats")
+                if world_size > 1:
+                    _all_reduce(sums)
+            mean, invstd = _bn_must(k.bn_prepare(sums, X.shape[1], eps, momentum, training, rm, rv), "bn_prepare")
+            Y = _bn_must(k.bn_relu_apply(X, mean, invstd, gamma.detach(), beta.detach(), row_ids if drop else None,
+                                         state.seed if drop else 0, state.step if drop else None, layer, thr if drop else 0),
+                         "bn_relu_apply")
+        else:
+            Y, mean, invstd = batchnorm_relu_composed(X, gamma, beta, rm, rv, training, momentum, eps, row_ids,
+                                                      state if drop else None, layer, thr if drop else 0, scale)
+        ctx.training, ctx.n_global, ctx.scale = bool(training), int(n_global), float(scale) if drop else 1.0
+        ctx.save_for_backward(X, Y, gamma, mean, invstd)
+        return Y
+
+    @staticmethod
+    def backward(ctx, G):
+        X, Y, gamma, mean, invstd = ctx.saved_tensors
+        if G.stride(1) != 1 or (G.shape[0] > 1 and G.stride(0) < G.shape[1]):
+            G = G.contiguous()
+        k = _bn_kernels(X, (gamma, mean, invstd)) if (ctx.training and G.is_cuda and G.dtype is torch.float32) else None
+        if k is not None:
+            sums, dgamma, dbeta = _bn_must(k.bn_backward_stats(G, Y, X, mean, invstd, ctx.scale), "bn_backward_stats")
+            if world_size > 1:
+                _all_reduce(sums)
+            dX = _bn_must(k.bn_relu_backward(G, Y, X, mean, invstd, gamma.detach(), sums, ctx.n_global, ctx.scale), "bn_relu_backward")
+            out = (dX, dgamma, dbeta)
+        else:
+            out = batchnorm_relu_backward_composed(G, Y, X, mean, invstd, gamma, ctx.n_global, ctx.scale, ctx.training)
+        return out + (None,) * 10
+
+
 _gemm_tuned_shapes = set()
 # GEMM choices that ship with the package: TunableOp result files (PyTorch's own CSV format, validated by it against the
 # PyTorch / ROCm / rocBLAS / hipBLASLt versions and the GPU architecture: a file from another stack is ignored and the
@@ -813,9 +952,15 @@ class PGCN(nn.Module):
     under any part vector reproduce one rank.  ``eval()`` or ``dropout=0``: the path without dropout, bit for bit.
 
     ``relu=False`` (the output layer of a classifier): the aggregation followed by the plain product x . W^T -- no ReLU in front
-    of the softmax, no dropout.  The default is the reference's layer."""
+    of the softmax, no dropout.  The default is the reference's layer.
 
-    def __init__(self, A, in_features, out_features, dropout=0.0, layer=0, state=None, relu=True):
+    ``norm="batch"`` (opt-in; needs ``relu=True``): drop(relu(BN(A H W^T))) -- the aggregation, the plain product ``_LinearNoBias``
+    and the node ``_BatchNormReluDropout``, whose statistics are those of ALL vertices of the graph whatever the part vector.  The
+    layer then owns ``bn_weight`` (ones) and ``bn_bias`` (zeros), ordinary parameters, and the buffers ``running_mean`` (zeros)
+    and ``running_var`` (ones), updated in training mode with ``bn_momentum`` = 0.1 and used instead of the graph's statistics by
+    ``eval()``; ``bn_eps`` = 1e-5 (torch's defaults).  ``norm=None`` or "none": none of these exist and nothing changes."""
+
+    def __init__(self, A, in_features, out_features, dropout=0.0, layer=0, state=None, relu=True, norm=None):
         super(PGCN, self).__init__()
         self.linear = nn.Linear(in_features, out_features, bias=False)
         self.A = A
@@ -827,11 +972,35 @@ class PGCN(nn.Module):
         self.state = state
         self._row_ids = None
         self.relu = bool(relu)
+        if norm not in NORMS + (None,):
+            raise ValueError("norm takes %s, got %r" % (" | ".join(NORMS), norm))
+        self.norm = None if norm in (None, "none") else norm
+        if self.norm is not None:
+            if not self.relu:
+                raise ValueError("norm=%r needs relu=True: the output layer of a classifier is not normalised" % (norm,))
+            self.bn_weight = nn.Parameter(torch.ones(out_features))
+            self.bn_bias = nn.Parameter(torch.zeros(out_features))
+            self.register_buffer("running_mean", torch.zeros(out_features))
+            self.register_buffer("running_var", torch.ones(out_features))
+            self.bn_momentum, self.bn_eps = 0.1, 1e-5
+
+    def _global_row_ids(self, H):
+        if self._row_ids is None or self._row_ids.device != H.device:      # global ids in local row order, once
+            self._row_ids = self.A.part.owned.to(device=H.device, dtype=torch.int64).contiguous()
+        return self._row_ids
 
     def forward(self, H):
         H = PSpMM.apply(self.A, H)
         if not self.relu:
             return _LinearNoBias.apply(H, self.linear.weight)
+        if self.norm is not None:
+            drop = self.training and self.dropout > 0.0
+            if drop and self.state is None:
+                self.state = _dropout.DropoutState(0, H.device)
+            return _BatchNormReluDropout.apply(_LinearNoBias.apply(H, self.linear.weight), self.bn_weight, self.bn_bias,
+                                               (self.running_mean, self.running_var), self.training, self.bn_momentum, self.bn_eps,
+                                               int(self.A.part.n), self._global_row_ids(H) if drop else None,
+                                               self.state if drop else None, self.layer, self.dropout_thr, self.dropout_scale)
         if self.training and self.dropout > 0.0:
             if self.state is None:
                 self.state = _dropout.DropoutState(0, H.device)
@@ -1143,7 +1312,7 @@ OPTIMIZERS = ("torch", "fused")       # --optimizer / run(optimizer=...): torch.
 
 
 def _train_on_data(A, n, nlayers, nfeatures, features, labels, split, hidden, epochs, lr, eval_every, dropout, dropout_seed,
-                   multilabel=False, weight_decay=0.0, decoupled_decay=False, optimizer="torch"):
+                   multilabel=False, weight_decay=0.0, decoupled_decay=False, optimizer="torch", norm=None):
     """The loop of ``run`` on real inputs: widths fin -> hidden -> ... -> C, no ReLU on the last layer, constant features (the
     first layer's backward aggregation is skipped), Adam, the masked loss over the train rows.  Reports every ``eval_every``
     epochs: without dropout from the record of the training step's own pass (the logits BEFORE that step's update), with
@@ -1151,7 +1320,10 @@ def _train_on_data(A, n, nlayers, nfeatures, features, labels, split, hidden, ep
     binary cross entropy with logits and the reported score the micro-F1 (``masked_bce_loss`` / ``evaluate_multilabel``).
     ``weight_decay``: Adam's L2 term, or with ``decoupled_decay`` AdamW's decay.  ``optimizer="fused"``: optim.FlatAdam -- the
     gradients accumulate in a flat arena, the step ends with one in-place all-reduce and one kernel launch that also clears them;
-    "torch" keeps ``zero_grad`` / ``average_gradients`` / torch's optimiser."""
+    "torch" keeps ``zero_grad`` / ``average_gradients`` / torch's optimiser.  ``norm="batch"``: every layer but the last normalises
+    its product over all vertices of the graph (class PGCN); its scale and shift are parameters like the weights -- initialised,
+    reduced, decayed and stepped with them.  The reporting rule is unchanged: without dropout the record is the training step's
+    own (the graph's statistics), with dropout ``evaluate`` runs in eval mode (the running statistics)."""
     load = _nodedata.load_multilabel if multilabel else _nodedata.load
     data = load(features, labels, split, A.part.owned, n, device=device)
     hidden = int(nfeatures if hidden is None else hidden)
@@ -1167,7 +1339,8 @@ def _train_on_data(A, n, nlayers, nfeatures, features, labels, split, hidden, ep
     _dropout.threshold(dropout)
     state = _dropout.DropoutState(dropout_seed, device) if dropout > 0.0 else None
     model = nn.Sequential(*[PGCN(A, widths[i], widths[i + 1], dropout=dropout if i < nlayers - 1 else 0.0, layer=i, state=state,
-                                 relu=i < nlayers - 1) for i in range(nlayers)]).to(device)
+                                 relu=i < nlayers - 1, **({"norm": norm} if norm not in (None, "none") and i < nlayers - 1 else {}))
+                            for i in range(nlayers)]).to(device)
     initiliaze_parameters(model)
     fused = None
     if optimizer == "fused":
@@ -1239,7 +1412,7 @@ TASKS = ("single", "multilabel")       # --task / run(task=...): one class per v
 
 def run(rank, size, nlayers, nfeatures, path_A, path_partvec, backend, normalize=None, dropout=0.0, dropout_seed=0,
         features=None, labels=None, split=None, hidden=None, epochs=None, lr=None, eval_every=None, task=None,
-        weight_decay=None, decoupled_decay=None, optimizer=None):
+        weight_decay=None, decoupled_decay=None, optimizer=None, norm=None):
     """PGCN.py:162-238.  ``normalize="sym"``: train on D_r^-1/2 (A + I) D_c^-1/2 of the pattern of ``path_A``, built on the fly
     (partition.build_partition) instead of by the offline pass preprocess/GrB-GNN-IDG.py.  ``dropout`` > 0: the output of every
     layer but the last is dropped with that probability (class PGCN), masks from (``dropout_seed``, step, layer, global row,
@@ -1251,7 +1424,9 @@ def run(rank, size, nlayers, nfeatures, path_A, path_partvec, backend, normalize
     ``task`` (needs the three files): None or "single" = one class per vertex (int64 label vector, softmax loss, accuracy);
     "multilabel" = an n x C uint8 matrix of 0 / 1, the masked binary cross entropy with logits, micro-F1.
     ``weight_decay`` (a float >= 0), ``decoupled_decay`` (True: AdamW's decay instead of an L2 term) and ``optimizer`` ("torch",
-    the default, or "fused" = optim.FlatAdam) need the three files too."""
+    the default, or "fused" = optim.FlatAdam) need the three files too.  ``norm`` ("none", the default, or "batch": batch
+    normalisation over all vertices of the graph between the product and the ReLU of every layer but the last; needs the three
+    files)."""
     global myrank, world_size, send_map, recv_map, device, X, recv_buffers, send_buffers, stats
     myrank = rank
     world_size = size
@@ -1269,6 +1444,10 @@ def run(rank, size, nlayers, nfeatures, path_A, path_partvec, backend, normalize
         raise ValueError("weight_decay must be a finite number >= 0, got %r" % (weight_decay,))
     if not all(given) and (weight_decay is not None or decoupled_decay is not None or optimizer is not None):
         raise ValueError("weight_decay, decoupled_decay and optimizer need features, labels and split")
+    if norm not in NORMS + (None,):
+        raise ValueError("norm takes %s, got %r" % (" | ".join(NORMS), norm))
+    if norm is not None and not all(given):
+        raise ValueError("norm=%r needs features, labels and split" % (norm,))
     if torch.cuda.is_available():
         device = torch.device(f'cuda:{myrank % torch.cuda.device_count()}')
         torch.cuda.set_device(device)
@@ -1321,7 +1500,8 @@ def run(rank, size, nlayers, nfeatures, path_A, path_partvec, backend, normalize
 
     if all(given):
         return _train_on_data(A, n, nlayers, nfeatures, features, labels, split, hidden, epochs, lr, eval_every, dropout,
-                              dropout_seed, multilabel, float(weight_decay or 0.0), bool(decoupled_decay), optimizer or "torch")
+                              dropout_seed, multilabel, float(weight_decay or 0.0), bool(decoupled_decay), optimizer or "torch",
+                              **({"norm": norm} if norm not in (None, "none") else {}))
 
     owned = A.part.owned.to(device)
     # PGCN.py:186-188 synthetic features H[i,:] = i, owned rows only
@@ -1396,7 +1576,7 @@ def run(rank, size, nlayers, nfeatures, path_A, path_partvec, backend, normalize
 
 def init_process(rank, size, fn, nlayers, nfeatures, path_A, path_partvec, backend, normalize=None, dropout=0.0, dropout_seed=0,
                  features=None, labels=None, split=None, hidden=None, epochs=None, lr=None, eval_every=None, task=None,
-                 weight_decay=None, decoupled_decay=None, optimizer=None):
+                 weight_decay=None, decoupled_decay=None, optimizer=None, norm=None):
     """PGCN.py:241-253."""
     global _exchanger
     dist.init_process_group(backend, rank=rank, world_size=size)
@@ -1414,7 +1594,7 @@ def init_process(rank, size, fn, nlayers, nfeatures, path_A, path_partvec, backe
         kw["dropout"], kw["dropout_seed"] = dropout, dropout_seed
     for name, v in (("features", features), ("labels", labels), ("split", split), ("hidden", hidden), ("epochs", epochs), ("lr", lr),
                     ("eval_every", eval_every), ("task", task), ("weight_decay", weight_decay), ("decoupled_decay", decoupled_decay),
-                    ("optimizer", optimizer)):
+                    ("optimizer", optimizer), ("norm", norm)):
         if v is not None:
             kw[name] = v
     fn(rank, size, nlayers, nfeatures, path_A, path_partvec, backend, **kw)     # (no option given: today's call)
@@ -1439,7 +1619,7 @@ def main(argv):
     try:
         opts, args = getopt.getopt(argv, "a:p:b:s:l:f:", ["normalize=", "dropout=", "dropout-seed=", "features=", "labels=", "split=",
                                                           "hidden=", "epochs=", "lr=", "eval-every=", "task=", "weight-decay=", "adamw",
-                                                          "optimizer="])
+                                                          "optimizer=", "norm="])
     except getopt.GetoptError:
         print("a:p:b:", flush=True)
         sys.exit(2)
@@ -1492,6 +1672,12 @@ def main(argv):
                 print("--optimizer takes %s, got %r" % ("|".join(OPTIMIZERS), arg), flush=True)
                 sys.exit(2)
             data["optimizer"] = arg
+        elif opt == '--norm':          # none (the default) | batch (batch normalisation over all vertices, every layer but the last)
+            if arg not in NORMS:
+                print("--norm takes %s, got %r" % ("|".join(NORMS), arg), flush=True)
+                sys.exit(2)
+            if arg != "none" or "norm" in data:
+                data["norm"] = arg
         elif opt == '--lr':
             try:
                 data["lr"] = float(arg)
@@ -1515,7 +1701,7 @@ def main(argv):
     os.environ.setdefault("WORLD_SIZE", str(size))
     files = [k for k in ("features", "labels", "split") if k in data]
     if data and len(files) != 3:
-        print("--features, --labels and --split go together (and --hidden, --epochs, --lr, --eval-every, --task, --weight-decay, --adamw, --optimizer need them); got %s"
+        print("--features, --labels and --split go together (and --hidden, --epochs, --lr, --eval-every, --task, --weight-decay, --adamw, --optimizer, --norm need them); got %s"
               % ", ".join("--" + {"decoupled_decay": "adamw"}.get(k, k.replace("_", "-")) for k in sorted(data)), flush=True)
         sys.exit(2)
     for k in files:
@@ -1530,8 +1716,10 @@ def main(argv):
     if data:
         args += tuple(data.get(k) for k in ("features", "labels", "split", "hidden", "epochs", "lr", "eval_every", "task"))
         extra = tuple(data.get(k) for k in ("weight_decay", "decoupled_decay", "optimizer"))
-        if any(v is not None for v in extra):      # (none of the three given: the argument tuple of before)
+        if any(v is not None for v in extra) or data.get("norm") is not None:      # (none given: the argument tuple of before)
             args += extra
+        if data.get("norm") is not None:
+            args += (data["norm"],)
     p = mp.Process(target=init_process, args=args)
     p.start()
     p.join()

@@ -105,6 +105,15 @@ SIGNATURES = {
     "pgcn_masked_bce_backward_f32": (ctypes.c_int, [_vp, _i64, _vp, _vp, _vp, ctypes.c_float, _i64, _i32, _vp, _i64, _vp]),
     "pgcn_adam_step_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, ctypes.c_double, ctypes.c_double, ctypes.c_double,
                                           ctypes.c_double, ctypes.c_double, _i32, ctypes.c_float, _i32, _vp, _vp]),
+    "pgcn_bn_colstats_ws_bytes": (_i64, [_i64, _i32]),
+    "pgcn_bn_colstats_f32": (ctypes.c_int, [_vp, _i64, _i64, _i32, _vp, _vp, _i64, _vp]),
+    "pgcn_bn_prepare_f32": (ctypes.c_int, [_vp, _i32, ctypes.c_double, ctypes.c_double, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "pgcn_bn_relu_apply_f32": (ctypes.c_int, [_vp, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _vp, ctypes.c_uint64, _vp, _u32, _u32, _vp,
+                                              _i64, _vp]),
+    "pgcn_bn_backward_stats_f32": (ctypes.c_int, [_vp, _i64, _vp, _i64, _vp, _i64, _i64, _i32, _vp, _vp, ctypes.c_float, _vp, _vp, _vp,
+                                                  _vp, _i64, _vp]),
+    "pgcn_bn_relu_backward_f32": (ctypes.c_int, [_vp, _i64, _vp, _i64, _vp, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _i64, ctypes.c_float,
+                                                 _vp, _i64, _vp]),
     "pgcn_gather_rows_f32": (ctypes.c_int, [_vp, _i64, _vp, _i64, _vp, _i64, _i32, _vp]),
     "pgcn_scatter_rows_f32": (ctypes.c_int, [_vp, _i64, _vp, _i64, _vp, _i64, _i32, _i32, _vp]),
     "pgcn_comm_unique_id": (ctypes.c_int, [_vp]),

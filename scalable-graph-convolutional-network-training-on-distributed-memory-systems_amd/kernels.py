@@ -205,6 +205,10 @@ def masked_bce_stats_views(record: torch.Tensor) -> MaskedBCEStats:
     return MaskedBCEStats(record[0:4].view(torch.float64), record[4:8], record[8:12], record[12:16], record[16:20])
 
 
+BN_MAX_F = 1024          # widest block the batch-norm kernels take (csrc/pgcn_norm.hip: 256 threads x 4 columns)
+BN_STAT_ROWS = 512       # rows of a band of its column-sum kernels (kStatRows; pgcn_bn_colstats_ws_bytes counts one record per band)
+
+
 class HipKernels:
     """libpgcn_hip.so on one MI355X.  Fails loudly when the device or library is missing."""
 
@@ -1107,6 +1111,110 @@ class HipKernels:
                                                1 if decoupled else 0, float(grad_scale), 1 if zero_grad else 0, step.data_ptr(),
                                                self._stream()), "pgcn_adam_step_f32")
         return True
+
+    # -- batch normalisation over all vertices, fused with ReLU and dropout (csrc/pgcn_norm.hip) --------------------
+    def _bn_mat_ok(self, *ts: torch.Tensor) -> bool:
+        X = ts[0]
+        # (the stride of a dimension of size 1, and every stride of an empty matrix, is never used: torch leaves them arbitrary)
+        return all(t.is_cuda and t.device == self.device and t.dim() == 2 and t.dtype is torch.float32 and t.shape == X.shape and
+                   (t.stride(1) == 1 or t.shape[1] == 1 or t.shape[0] == 0) and (t.shape[0] <= 1 or t.stride(0) >= t.shape[1])
+                   for t in ts) and 0 < X.shape[1] <= BN_MAX_F
+
+    def _bn_vec_ok(self, f: int, dtype, *ts: Optional[torch.Tensor]) -> bool:
+        return all(t is None or (t.is_cuda and t.device == self.device and t.dtype is dtype and t.is_contiguous() and t.numel() >= f)
+                   for t in ts)
+
+    @staticmethod
+    def _ld(t: torch.Tensor) -> int:
+        return max(t.stride(0), t.shape[1]) if t.shape[0] > 1 else t.shape[1]
+
+    def _bn_ws(self, n: int, f: int):
+        ws_bytes = int(self.lib.pgcn_bn_colstats_ws_bytes(n, f))
+        return torch.empty(ws_bytes // 8, dtype=torch.float64, device=self.device), ws_bytes
+
+    def bn_colstats(self, X: torch.Tensor, sums: Optional[torch.Tensor] = None):
+        """float64 [2 f + 1] on the device: the column sums of X, of X^2, and the row count (pgcn_bn_colstats_f32) -- what ONE
+        float64 all-reduce turns into the statistics of all ranks' rows.  None when the shape is not covered (more than 1024
+        columns, another dtype or layout)."""
+        if not self._bn_mat_ok(X):
+            return None
+        n, f = X.shape
+        if sums is None:
+            sums = torch.empty(2 * f + 1, dtype=torch.float64, device=self.device)
+        elif not (self._bn_vec_ok(2 * f + 1, torch.float64, sums)):
+            return None
+        ws, ws_bytes = self._bn_ws(n, f)
+        _lib.check(self.lib.pgcn_bn_colstats_f32(X.data_ptr(), self._ld(X), n, f, sums.data_ptr(), ws.data_ptr(), ws_bytes,
+                                                 self._stream()), "pgcn_bn_colstats_f32")
+        return sums
+
+    def bn_prepare(self, sums: Optional[torch.Tensor], f: int, eps: float, momentum: float, training: bool,
+                   running_mean: Optional[torch.Tensor], running_var: Optional[torch.Tensor]):
+        """(mean, invstd), fp32 [f] each: from the reduced sums in train mode (the running statistics are updated in place, on
+        the device, from device memory), from the running statistics in eval mode (pgcn_bn_prepare_f32).  None when not covered."""
+        if not (0 < f <= BN_MAX_F) or not self._bn_vec_ok(f, torch.float32, running_mean, running_var) or \
+                not self._bn_vec_ok(2 * f + 1, torch.float64, sums) or (training and sums is None) or \
+                (not training and (running_mean is None or running_var is None)):
+            return None
+        mean = torch.empty(f, dtype=torch.float32, device=self.device)
+        invstd = torch.empty(f, dtype=torch.float32, device=self.device)
+        _lib.check(self.lib.pgcn_bn_prepare_f32(_ptr(sums), f, float(eps), float(momentum), 1 if training else 0, _ptr(running_mean),
+                                                _ptr(running_var), mean.data_ptr(), invstd.data_ptr(), self._stream()),
+                   "pgcn_bn_prepare_f32")
+        return mean, invstd
+
+    def bn_relu_apply(self, X: torch.Tensor, mean: torch.Tensor, invstd: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor,
+                      row_ids: Optional[torch.Tensor] = None, seed: int = 0, step: Optional[torch.Tensor] = None, layer: int = 0,
+                      thr: int = 0, out: Optional[torch.Tensor] = None):
+        """Y = keep ? max(0, gamma (X - mean) invstd + beta) * scale : 0 in one pass (pgcn_bn_relu_apply_f32); ``step`` None or
+        ``thr`` 0: no dropout.  ``step``: one int64 on the device, read by the kernel; ``row_ids``: int64 [n] global ids (None: the
+        row index).  None when the shape is not covered."""
+        if not self._bn_mat_ok(X) or (out is not None and not self._bn_mat_ok(X, out)):
+            return None
+        n, f = X.shape
+        if not self._bn_vec_ok(f, torch.float32, mean, invstd, gamma, beta) or not self._bn_vec_ok(n, torch.int64, row_ids) or \
+                not self._bn_vec_ok(1, torch.int64, step):
+            return None
+        Y = out if out is not None else torch.empty((n, f), dtype=torch.float32, device=self.device)
+        _lib.check(self.lib.pgcn_bn_relu_apply_f32(X.data_ptr(), self._ld(X), n, f, mean.data_ptr(), invstd.data_ptr(), gamma.data_ptr(),
+                                                   beta.data_ptr(), _ptr(row_ids), int(seed) & ((1 << 64) - 1), _ptr(step), int(layer),
+                                                   int(thr), Y.data_ptr(), self._ld(Y), self._stream()), "pgcn_bn_relu_apply_f32")
+        return Y
+
+    def bn_backward_stats(self, G: torch.Tensor, Y: torch.Tensor, X: torch.Tensor, mean: torch.Tensor, invstd: torch.Tensor,
+                          scale: float):
+        """(sums, dgamma, dbeta): float64 [2 f] = the column sums of g' and of g' xh over THIS rank's rows (g' = Y > 0 ? G scale
+        : 0, xh = (X - mean) invstd) and the parameter gradients rounded from them (pgcn_bn_backward_stats_f32; its second-level
+        launch writes all three).  The caller all-reduces ``sums``.  None when the shape is not covered."""
+        if not self._bn_mat_ok(X, G, Y):
+            return None
+        n, f = X.shape
+        if not self._bn_vec_ok(f, torch.float32, mean, invstd):
+            return None
+        sums = torch.empty(2 * f, dtype=torch.float64, device=self.device)
+        dgamma = torch.empty(f, dtype=torch.float32, device=self.device)
+        dbeta = torch.empty(f, dtype=torch.float32, device=self.device)
+        ws, ws_bytes = self._bn_ws(n, f)
+        _lib.check(self.lib.pgcn_bn_backward_stats_f32(G.data_ptr(), self._ld(G), Y.data_ptr(), self._ld(Y), X.data_ptr(), self._ld(X), n, f,
+                                                       mean.data_ptr(), invstd.data_ptr(), float(scale), sums.data_ptr(),
+                                                       dgamma.data_ptr(), dbeta.data_ptr(), ws.data_ptr(), ws_bytes, self._stream()),
+                   "pgcn_bn_backward_stats_f32")
+        return sums, dgamma, dbeta
+
+    def bn_relu_backward(self, G: torch.Tensor, Y: torch.Tensor, X: torch.Tensor, mean: torch.Tensor, invstd: torch.Tensor,
+                         gamma: torch.Tensor, sums: torch.Tensor, n_global: int, scale: float, out: Optional[torch.Tensor] = None):
+        """dX = gamma invstd (g' - S1 / N - xh S2 / N) in one pass from the GLOBAL sums (pgcn_bn_relu_backward_f32), or None."""
+        if not self._bn_mat_ok(X, G, Y) or (out is not None and not self._bn_mat_ok(X, out)):
+            return None
+        n, f = X.shape
+        if not self._bn_vec_ok(f, torch.float32, mean, invstd, gamma) or not self._bn_vec_ok(2 * f, torch.float64, sums):
+            return None
+        dX = out if out is not None else torch.empty((n, f), dtype=torch.float32, device=self.device)
+        _lib.check(self.lib.pgcn_bn_relu_backward_f32(G.data_ptr(), self._ld(G), Y.data_ptr(), self._ld(Y), X.data_ptr(), self._ld(X), n, f,
+                                                      mean.data_ptr(), invstd.data_ptr(), gamma.data_ptr(), sums.data_ptr(),
+                                                      int(n_global), float(scale), dX.data_ptr(), self._ld(dX), self._stream()),
+                   "pgcn_bn_relu_backward_f32")
+        return dX
 
     def gather_rows(self, H: torch.Tensor, idx: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
         n = idx.numel()
