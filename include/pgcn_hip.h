@@ -592,6 +592,37 @@ int pgcn_bn_relu_backward_f32(const float *G, int64_t ldg, const float *Y, int64
                               int32_t f, const float *mean, const float *invstd, const float *gamma, const double *sums, int64_t N,
                               float scale, float *dX, int64_t lddx, pgcn_stream_t stream);
 
+/* ---- root weight and bias, fused with ReLU and dropout (PGCN.py: _CombineBiasReluDropout) -------------------------
+ * The tail of a GraphSAGE-style layer act((A H) W_n^T + H W_r^T + b) on an nrows x f block of OWNED rows: Z1 is the neighbour
+ * product, Z2 the root product, both made by the dense path; these two entry points are everything else.
+ * pgcn_combine_forward_f32:  t = (Z1[i,j] + Z2[i,j]) + bias[j], the two additions in that order, each rounded to fp32 (no
+ *   contraction);  relu == 0: Y[i,j] = t;  otherwise Y[i,j] = keep ? max(0, t) * scale : 0.  Z2 == NULL or bias == NULL: that term
+ *   is ABSENT (not added as 0.0f: a -0.0 survives).  step == NULL or thr == 0 (or relu == 0): keep is true and scale 1.  Otherwise
+ *   keep / scale are those of gemm/pgcn_dropout.h with the key (seed, *step, layer, row_ids[i] (NULL: i), j): the masks the fused
+ *   dense kernel draws for that layer; *step is read from device memory, the column's share of the hash is formed once per
+ *   thread.  Y == Z1 with ldy == ldz1 is allowed (in place): the backward needs neither Z.  One launch; nrows == 0: none.
+ * pgcn_combine_backward_f32:  relu != 0: Gm[i,j] = Y[i,j] > 0 ? G[i,j] * scale : 0 (the saved output is its own mask: no mask
+ *   tensor, nothing regenerated);  relu == 0: Gm[i,j] = G[i,j] (Y is not read and may be NULL).  Gm is the operand of BOTH
+ *   products' backward.  In the same pass dbias[j] = float(sum_i Gm[i,j]), added in double: a block owns 512 consecutive rows,
+ *   folds its row groups through LDS by a fixed tree and writes one partial record [f] of doubles to `ws`
+ *   (pgcn_combine_ws_bytes(nrows, f) bytes, 8-byte aligned; -1 for sizes the kernels refuse); a second launch, 32 columns per
+ *   block, adds the records in a fixed order -- no floating-point atomics, the same input gives the same bits.  dbias is the
+ *   RANK-LOCAL sum: the training loop adds the ranks' parameter gradients itself.  Gm == NULL: sums only (relu == 0, where Gm is
+ *   G).  dbias == NULL: no sums, ws is not read, one launch.  nrows == 0: dbias is zeroed, nothing else is written.
+ * Both: row-major with leading dimensions in elements, 64-bit row offsets; every f from 1 to 1024 (PGCN_EUNSUPPORTED above);
+ * a thread owns four consecutive columns -- one float4 when f % 4 == 0 and every base and leading dimension keeps rows 16-byte
+ * aligned, four guarded scalars otherwise, the same bits either way.  PGCN_EINVAL, nothing launched: a null required pointer,
+ * nrows < 0, f < 1, a leading dimension below f, a scale that is not finite and positive, a misaligned ws / step / row_ids, in
+ * place with differing leading dimensions; PGCN_ENOMEM: ws_bytes too small.  A NaN or inf stays in its own column.  Raw
+ * pointers + a stream, no allocation, no synchronisation (graph-capturable).                                              */
+int64_t pgcn_combine_ws_bytes(int64_t nrows, int32_t f);
+int pgcn_combine_forward_f32(const float *Z1, int64_t ldz1, const float *Z2, int64_t ldz2, const float *bias, int64_t nrows,
+                             int32_t f, int32_t relu, const int64_t *row_ids, uint64_t seed, const int64_t *step, uint32_t layer,
+                             uint32_t thr, float *Y, int64_t ldy, pgcn_stream_t stream);
+int pgcn_combine_backward_f32(const float *G, int64_t ldg, const float *Y, int64_t ldy, int64_t nrows, int32_t f, int32_t relu,
+                              float scale, float *Gm, int64_t ldgm, float *dbias, void *ws, int64_t ws_bytes,
+                              pgcn_stream_t stream);
+
 /* ---- boundary-row pack / unpack -------------------------------------------
  * out[r,:] = H[idx[r],:]                      replaces H[indices]   GPU/PGCN.py:104
  * H[idx[r],:] (+)= in[r,:]                    replaces X[indices] = buf   :115

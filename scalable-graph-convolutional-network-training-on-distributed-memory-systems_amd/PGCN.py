@@ -820,6 +820,94 @@ class _BatchNormReluDropout(torch.autograd.Function):
         return out + (None,) * 10
 
 
+# ---- root weight and bias, fused with ReLU and dropout (csrc/pgcn_combine.hip) -----------------------------------------------------
+def combine_composed(Z1, Z2=None, bias=None, relu=True, row_ids=None, state=None, layer=0, thr=0, scale=1.0):
+    """Y of the layer tail from framework operations, the definitions of csrc/pgcn_combine.hip: t = (Z1 + Z2) + bias, the two fp32
+    additions in that order (a term that is None is absent), then with ``relu`` Y = keep ? max(0, t) * scale : 0 -- keep the bits of
+    dropout.py under (seed, step, layer, global row id, column); ``state`` None or ``thr`` 0: no dropout.  For CPU tensors, the
+    checker-backed provider of the tests and f > 1024."""
+    t = Z1.detach()
+    if Z2 is not None:
+        t = t + Z2.detach()
+    if bias is not None:
+        t = t + bias.detach()
+    if not relu:
+        return t.clone() if Z2 is None and bias is None else t
+    zero = torch.zeros((), dtype=t.dtype, device=t.device)
+    Y = torch.where(t < 0, zero, t)                                                  # (NaN stays NaN, as in the kernel)
+    if state is not None and thr > 0:
+        Y = torch.where(_bn_keep(Z1, row_ids, state, layer, thr), Y * scale, zero)
+    return Y
+
+
+def combine_backward_composed(G, Y=None, relu=True, scale=1.0, want_dbias=True):
+    """(Gm, dbias) of the same tail: Gm = Y > 0 ? G * scale : 0 with ``relu`` (the saved output is its own mask), G itself without;
+    dbias = THIS rank's column sums of Gm, added in float64 and rounded once (None unless ``want_dbias``): the training loop adds the
+    ranks' parameter gradients itself."""
+    Gm = torch.where(Y > 0, G * scale, torch.zeros((), dtype=G.dtype, device=G.device)) if relu else G
+    return Gm, (Gm.double().sum(0).to(G.dtype) if want_dbias else None)
+
+
+def _combine_kernels(Z1, Z2=None, bias=None, row_ids=None):
+    """The provider whose combine kernels take these operands, or None (CPU tensors, the checker-backed provider of the tests, more than
+    1024 columns, another dtype or layout).  Decided BEFORE the first launch."""
+    k = _kernel_provider if _kernel_provider is not None else getattr(_engine_current, "k", None)
+    if k is None or not hasattr(k, "combine_forward") or not hasattr(k, "combine_backward"):
+        return None
+    for t in (Z1, Z2):
+        if t is not None and not (t.is_cuda and t.dim() == 2 and t.dtype is torch.float32 and t.shape == Z1.shape and t.device == Z1.device
+                                  and 0 < t.shape[1] <= _kernels.COMBINE_MAX_F and (t.stride(1) == 1 or t.shape[1] == 1 or t.shape[0] == 0)
+                                  and (t.shape[0] <= 1 or t.stride(0) >= t.shape[1])):
+            return None
+    if bias is not None and not (bias.is_cuda and bias.device == Z1.device and bias.dtype is torch.float32 and bias.is_contiguous()
+                                 and bias.numel() == Z1.shape[1]):
+        return None
+    return k if _row_ids_ok(row_ids, Z1.shape[0]) and (row_ids is None or row_ids.device == Z1.device) else None
+
+
+class _CombineBiasReluDropout(torch.autograd.Function):
+    """drop(relu((Z1 + Z2) + bias)) -- or the plain sum with ``relu=False`` -- as ONE autograd node: Z1 = (A H) W_n^T is the neighbour
+    product, Z2 = H W_r^T the root product (None: absent), ``bias`` a vector per column (None: absent).  On a HIP device one launch
+    forward (pgcn_combine_forward_f32, the dropout keep function of the fused dense kernel in its epilogue) and one pass backward
+    (pgcn_combine_backward_f32): Gm = Y > 0 ? G * scale : 0 written ONCE and handed to both products' backward, the bias gradient
+    summed in double in the same pass.  Saved: Y alone (its own mask), and only with ``relu``.  Without ``relu`` the backward passes G
+    through to both products (no launch unless the bias wants its sums).  dbias is THIS rank's sum.  Anything the kernels do not cover
+    (CPU tensors, f > 1024, the checker-backed provider) takes ``combine_composed``: the same definitions."""
+
+    @staticmethod
+    def forward(ctx, Z1, Z2, bias, relu, row_ids, state, layer, thr, scale):
+        drop = bool(relu and state is not None and thr > 0)
+        k = _combine_kernels(Z1, Z2, bias, row_ids if drop else None)
+        if k is not None:
+            Y = _bn_must(k.combine_forward(Z1, Z2, bias.detach() if bias is not None else None, relu, row_ids if drop else None,
+                                           state.seed if drop else 0, state.step if drop else None, layer, thr if drop else 0),
+                         "combine_forward")
+        else:
+            Y = combine_composed(Z1, Z2, bias, relu, row_ids, state if drop else None, layer, thr if drop else 0, scale)
+        ctx.relu, ctx.scale, ctx.has_z2, ctx.has_bias = bool(relu), float(scale) if drop else 1.0, Z2 is not None, bias is not None
+        if relu:
+            ctx.save_for_backward(Y)
+        return Y
+
+    @staticmethod
+    def backward(ctx, G):
+        Y = ctx.saved_tensors[0] if ctx.relu else None
+        want_dbias = ctx.has_bias and ctx.needs_input_grad[2]
+        if not ctx.relu and not want_dbias:
+            Gm, dbias = G, None
+        else:
+            if G.stride(1) != 1 or (G.shape[0] > 1 and G.stride(0) < G.shape[1]):
+                G = G.contiguous()
+            k = _combine_kernels(G, Y)
+            if k is not None:
+                Gm, dbias = _bn_must(k.combine_backward(G, Y, ctx.relu, ctx.scale, want_gm=ctx.relu, want_dbias=want_dbias), "combine_backward")
+                if not ctx.relu:
+                    Gm = G
+            else:
+                Gm, dbias = combine_backward_composed(G, Y, ctx.relu, ctx.scale, want_dbias)
+        return (Gm, Gm if ctx.has_z2 else None, dbias) + (None,) * 6
+
+
 _gemm_tuned_shapes = set()
 # GEMM choices that ship with the package: TunableOp result files (PyTorch's own CSV format, validated by it against the
 # PyTorch / ROCm / rocBLAS / hipBLASLt versions and the GPU architecture: a file from another stack is ignored and the
@@ -958,9 +1046,19 @@ class PGCN(nn.Module):
     and the node ``_BatchNormReluDropout``, whose statistics are those of ALL vertices of the graph whatever the part vector.  The
     layer then owns ``bn_weight`` (ones) and ``bn_bias`` (zeros), ordinary parameters, and the buffers ``running_mean`` (zeros)
     and ``running_var`` (ones), updated in training mode with ``bn_momentum`` = 0.1 and used instead of the graph's statistics by
-    ``eval()``; ``bn_eps`` = 1e-5 (torch's defaults).  ``norm=None`` or "none": none of these exist and nothing changes."""
+    ``eval()``; ``bn_eps`` = 1e-5 (torch's defaults).  ``norm=None`` or "none": none of these exist and nothing changes.
 
-    def __init__(self, A, in_features, out_features, dropout=0.0, layer=0, state=None, relu=True, norm=None):
+    ``root_weight=True`` / ``bias=True`` (opt-in, the GraphSAGE-style layer): act((A H) W_n^T + H W_r^T + b).  The layer then owns a
+    second ``nn.Linear(in_features, out_features, bias=False)`` named ``root`` -- a vertex's own features get their own weights instead
+    of sharing the neighbours' through the self-loop -- and / or a parameter ``bias`` of ``out_features`` zeros.  Both products are
+    ``_LinearNoBias``; the node ``_CombineBiasReluDropout`` adds them and the bias, applies the ReLU and draws the dropout masks under
+    this layer's key (the masks the fused dense kernel would draw for it).  With ``relu=False`` the output is the plain sum
+    (Z1 + Z2) + b.  With ``norm="batch"`` the plain sum Z1 + Z2 feeds ``_BatchNormReluDropout`` and the layer owns NO ``bias`` even
+    when asked for one: ``bn_bias`` is the shift, a second one in front of the normalisation would be removed by the mean.  Ordinary
+    parameters, both: initialised, reduced, decayed and stepped with the rest.  With both flags false none of this exists and
+    ``forward`` takes the branches of before."""
+
+    def __init__(self, A, in_features, out_features, dropout=0.0, layer=0, state=None, relu=True, norm=None, root_weight=False, bias=False):
         super(PGCN, self).__init__()
         self.linear = nn.Linear(in_features, out_features, bias=False)
         self.A = A
@@ -983,13 +1081,37 @@ class PGCN(nn.Module):
             self.register_buffer("running_mean", torch.zeros(out_features))
             self.register_buffer("running_var", torch.ones(out_features))
             self.bn_momentum, self.bn_eps = 0.1, 1e-5
+        self.root_weight = bool(root_weight)
+        self.has_bias = bool(bias) and self.norm is None
+        if self.root_weight:
+            self.root = nn.Linear(in_features, out_features, bias=False)
+        if self.has_bias:
+            self.bias = nn.Parameter(torch.zeros(out_features))
 
     def _global_row_ids(self, H):
         if self._row_ids is None or self._row_ids.device != H.device:      # global ids in local row order, once
             self._row_ids = self.A.part.owned.to(device=H.device, dtype=torch.int64).contiguous()
         return self._row_ids
 
+    def _forward_combined(self, H, AH):
+        """The layer with a root weight and / or a bias: H the layer's input (owned rows), AH its aggregation."""
+        Z1 = _LinearNoBias.apply(AH, self.linear.weight)
+        Z2 = _LinearNoBias.apply(H, self.root.weight) if self.root_weight else None
+        drop = self.relu and self.training and self.dropout > 0.0
+        if drop and self.state is None:
+            self.state = _dropout.DropoutState(0, H.device)
+        if self.norm is not None:
+            X = _CombineBiasReluDropout.apply(Z1, Z2, None, False, None, None, self.layer, 0, 1.0) if Z2 is not None else Z1
+            return _BatchNormReluDropout.apply(X, self.bn_weight, self.bn_bias, (self.running_mean, self.running_var), self.training,
+                                               self.bn_momentum, self.bn_eps, int(self.A.part.n), self._global_row_ids(H) if drop else None,
+                                               self.state if drop else None, self.layer, self.dropout_thr, self.dropout_scale)
+        return _CombineBiasReluDropout.apply(Z1, Z2, self.bias if self.has_bias else None, self.relu,
+                                             self._global_row_ids(H) if drop else None, self.state if drop else None, self.layer,
+                                             self.dropout_thr if drop else 0, self.dropout_scale if drop else 1.0)
+
     def forward(self, H):
+        if self.root_weight or self.has_bias:
+            return self._forward_combined(H, PSpMM.apply(self.A, H))
         H = PSpMM.apply(self.A, H)
         if not self.relu:
             return _LinearNoBias.apply(H, self.linear.weight)
@@ -1312,7 +1434,7 @@ OPTIMIZERS = ("torch", "fused")       # --optimizer / run(optimizer=...): torch.
 
 
 def _train_on_data(A, n, nlayers, nfeatures, features, labels, split, hidden, epochs, lr, eval_every, dropout, dropout_seed,
-                   multilabel=False, weight_decay=0.0, decoupled_decay=False, optimizer="torch", norm=None):
+                   multilabel=False, weight_decay=0.0, decoupled_decay=False, optimizer="torch", norm=None, root_weight=None, bias=None):
     """The loop of ``run`` on real inputs: widths fin -> hidden -> ... -> C, no ReLU on the last layer, constant features (the
     first layer's backward aggregation is skipped), Adam, the masked loss over the train rows.  Reports every ``eval_every``
     epochs: without dropout from the record of the training step's own pass (the logits BEFORE that step's update), with
@@ -1323,7 +1445,8 @@ def _train_on_data(A, n, nlayers, nfeatures, features, labels, split, hidden, ep
     "torch" keeps ``zero_grad`` / ``average_gradients`` / torch's optimiser.  ``norm="batch"``: every layer but the last normalises
     its product over all vertices of the graph (class PGCN); its scale and shift are parameters like the weights -- initialised,
     reduced, decayed and stepped with them.  The reporting rule is unchanged: without dropout the record is the training step's
-    own (the graph's statistics), with dropout ``evaluate`` runs in eval mode (the running statistics)."""
+    own (the graph's statistics), with dropout ``evaluate`` runs in eval mode (the running statistics).  ``root_weight`` / ``bias``:
+    every layer gets a root weight / a bias (class PGCN; a normalised layer owns no bias) -- parameters like the rest."""
     load = _nodedata.load_multilabel if multilabel else _nodedata.load
     data = load(features, labels, split, A.part.owned, n, device=device)
     hidden = int(nfeatures if hidden is None else hidden)
@@ -1338,8 +1461,10 @@ def _train_on_data(A, n, nlayers, nfeatures, features, labels, split, hidden, ep
         tune_dense_gemms(A.part.n_local, a, device, b)
     _dropout.threshold(dropout)
     state = _dropout.DropoutState(dropout_seed, device) if dropout > 0.0 else None
+    extra = dict(({"root_weight": True} if root_weight else {}), **({"bias": True} if bias else {}))       # (neither: the call of before)
     model = nn.Sequential(*[PGCN(A, widths[i], widths[i + 1], dropout=dropout if i < nlayers - 1 else 0.0, layer=i, state=state,
-                                 relu=i < nlayers - 1, **({"norm": norm} if norm not in (None, "none") and i < nlayers - 1 else {}))
+                                 relu=i < nlayers - 1, **({"norm": norm} if norm not in (None, "none") and i < nlayers - 1 else {}),
+                                 **extra)
                             for i in range(nlayers)]).to(device)
     initiliaze_parameters(model)
     fused = None
@@ -1412,7 +1537,7 @@ TASKS = ("single", "multilabel")       # --task / run(task=...): one class per v
 
 def run(rank, size, nlayers, nfeatures, path_A, path_partvec, backend, normalize=None, dropout=0.0, dropout_seed=0,
         features=None, labels=None, split=None, hidden=None, epochs=None, lr=None, eval_every=None, task=None,
-        weight_decay=None, decoupled_decay=None, optimizer=None, norm=None):
+        weight_decay=None, decoupled_decay=None, optimizer=None, norm=None, root_weight=None, bias=None):
     """PGCN.py:162-238.  ``normalize="sym"``: train on D_r^-1/2 (A + I) D_c^-1/2 of the pattern of ``path_A``, built on the fly
     (partition.build_partition) instead of by the offline pass preprocess/GrB-GNN-IDG.py.  ``dropout`` > 0: the output of every
     layer but the last is dropped with that probability (class PGCN), masks from (``dropout_seed``, step, layer, global row,
@@ -1426,7 +1551,8 @@ def run(rank, size, nlayers, nfeatures, path_A, path_partvec, backend, normalize
     ``weight_decay`` (a float >= 0), ``decoupled_decay`` (True: AdamW's decay instead of an L2 term) and ``optimizer`` ("torch",
     the default, or "fused" = optim.FlatAdam) need the three files too.  ``norm`` ("none", the default, or "batch": batch
     normalisation over all vertices of the graph between the product and the ReLU of every layer but the last; needs the three
-    files)."""
+    files).  ``root_weight`` / ``bias`` (True; need the three files): every layer is the GraphSAGE-style
+    act((A H) W_n^T + H W_r^T + b) of class PGCN instead of act((A H) W^T)."""
     global myrank, world_size, send_map, recv_map, device, X, recv_buffers, send_buffers, stats
     myrank = rank
     world_size = size
@@ -1448,6 +1574,8 @@ def run(rank, size, nlayers, nfeatures, path_A, path_partvec, backend, normalize
         raise ValueError("norm takes %s, got %r" % (" | ".join(NORMS), norm))
     if norm is not None and not all(given):
         raise ValueError("norm=%r needs features, labels and split" % (norm,))
+    if (root_weight is not None or bias is not None) and not all(given):
+        raise ValueError("root_weight and bias need features, labels and split")
     if torch.cuda.is_available():
         device = torch.device(f'cuda:{myrank % torch.cuda.device_count()}')
         torch.cuda.set_device(device)
@@ -1501,7 +1629,8 @@ def run(rank, size, nlayers, nfeatures, path_A, path_partvec, backend, normalize
     if all(given):
         return _train_on_data(A, n, nlayers, nfeatures, features, labels, split, hidden, epochs, lr, eval_every, dropout,
                               dropout_seed, multilabel, float(weight_decay or 0.0), bool(decoupled_decay), optimizer or "torch",
-                              **({"norm": norm} if norm not in (None, "none") else {}))
+                              **({"norm": norm} if norm not in (None, "none") else {}),
+                              **({"root_weight": True} if root_weight else {}), **({"bias": True} if bias else {}))
 
     owned = A.part.owned.to(device)
     # PGCN.py:186-188 synthetic features H[i,:] = i, owned rows only
@@ -1576,7 +1705,7 @@ def run(rank, size, nlayers, nfeatures, path_A, path_partvec, backend, normalize
 
 def init_process(rank, size, fn, nlayers, nfeatures, path_A, path_partvec, backend, normalize=None, dropout=0.0, dropout_seed=0,
                  features=None, labels=None, split=None, hidden=None, epochs=None, lr=None, eval_every=None, task=None,
-                 weight_decay=None, decoupled_decay=None, optimizer=None, norm=None):
+                 weight_decay=None, decoupled_decay=None, optimizer=None, norm=None, root_weight=None, bias=None):
     """PGCN.py:241-253."""
     global _exchanger
     dist.init_process_group(backend, rank=rank, world_size=size)
@@ -1594,7 +1723,7 @@ def init_process(rank, size, fn, nlayers, nfeatures, path_A, path_partvec, backe
         kw["dropout"], kw["dropout_seed"] = dropout, dropout_seed
     for name, v in (("features", features), ("labels", labels), ("split", split), ("hidden", hidden), ("epochs", epochs), ("lr", lr),
                     ("eval_every", eval_every), ("task", task), ("weight_decay", weight_decay), ("decoupled_decay", decoupled_decay),
-                    ("optimizer", optimizer), ("norm", norm)):
+                    ("optimizer", optimizer), ("norm", norm), ("root_weight", root_weight), ("bias", bias)):
         if v is not None:
             kw[name] = v
     fn(rank, size, nlayers, nfeatures, path_A, path_partvec, backend, **kw)     # (no option given: today's call)
@@ -1619,7 +1748,7 @@ def main(argv):
     try:
         opts, args = getopt.getopt(argv, "a:p:b:s:l:f:", ["normalize=", "dropout=", "dropout-seed=", "features=", "labels=", "split=",
                                                           "hidden=", "epochs=", "lr=", "eval-every=", "task=", "weight-decay=", "adamw",
-                                                          "optimizer=", "norm="])
+                                                          "optimizer=", "norm=", "root-weight", "bias"])
     except getopt.GetoptError:
         print("a:p:b:", flush=True)
         sys.exit(2)
@@ -1678,6 +1807,10 @@ def main(argv):
                 sys.exit(2)
             if arg != "none" or "norm" in data:
                 data["norm"] = arg
+        elif opt == '--root-weight':   # every layer adds H . W_r^T: a vertex's own features get their own weights (class PGCN)
+            data["root_weight"] = True
+        elif opt == '--bias':          # every layer adds a bias (a normalised layer keeps bn_bias alone)
+            data["bias"] = True
         elif opt == '--lr':
             try:
                 data["lr"] = float(arg)
@@ -1701,7 +1834,7 @@ def main(argv):
     os.environ.setdefault("WORLD_SIZE", str(size))
     files = [k for k in ("features", "labels", "split") if k in data]
     if data and len(files) != 3:
-        print("--features, --labels and --split go together (and --hidden, --epochs, --lr, --eval-every, --task, --weight-decay, --adamw, --optimizer, --norm need them); got %s"
+        print("--features, --labels and --split go together (and --hidden, --epochs, --lr, --eval-every, --task, --weight-decay, --adamw, --optimizer, --norm, --root-weight, --bias need them); got %s"
               % ", ".join("--" + {"decoupled_decay": "adamw"}.get(k, k.replace("_", "-")) for k in sorted(data)), flush=True)
         sys.exit(2)
     for k in files:
@@ -1716,10 +1849,14 @@ def main(argv):
     if data:
         args += tuple(data.get(k) for k in ("features", "labels", "split", "hidden", "epochs", "lr", "eval_every", "task"))
         extra = tuple(data.get(k) for k in ("weight_decay", "decoupled_decay", "optimizer"))
-        if any(v is not None for v in extra) or data.get("norm") is not None:      # (none given: the argument tuple of before)
+        layer_opts = tuple(data.get(k) for k in ("root_weight", "bias"))
+        has_layer_opts = any(v is not None for v in layer_opts)
+        if any(v is not None for v in extra) or data.get("norm") is not None or has_layer_opts:      # (none given: the argument tuple of before)
             args += extra
-        if data.get("norm") is not None:
-            args += (data["norm"],)
+        if data.get("norm") is not None or has_layer_opts:
+            args += (data.get("norm"),)
+        if has_layer_opts:
+            args += layer_opts
     p = mp.Process(target=init_process, args=args)
     p.start()
     p.join()

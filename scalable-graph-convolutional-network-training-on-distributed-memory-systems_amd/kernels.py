@@ -207,6 +207,8 @@ def masked_bce_stats_views(record: torch.Tensor) -> MaskedBCEStats:
 
 BN_MAX_F = 1024          # widest block the batch-norm kernels take (csrc/pgcn_norm.hip: 256 threads x 4 columns)
 BN_STAT_ROWS = 512       # rows of a band of its column-sum kernels (kStatRows; pgcn_bn_colstats_ws_bytes counts one record per band)
+COMBINE_MAX_F = 1024     # widest block the combine kernels take (csrc/pgcn_combine.hip: the same layout)
+COMBINE_SUM_ROWS = 512   # rows of a block of its backward (kSumRows; pgcn_combine_ws_bytes counts one record per block)
 
 
 class HipKernels:
@@ -1215,6 +1217,50 @@ class HipKernels:
                                                       int(n_global), float(scale), dX.data_ptr(), self._ld(dX), self._stream()),
                    "pgcn_bn_relu_backward_f32")
         return dX
+
+    # -- root weight and bias, fused with ReLU and dropout (csrc/pgcn_combine.hip) -----------------------------------
+    def combine_forward(self, Z1: torch.Tensor, Z2: Optional[torch.Tensor], bias: Optional[torch.Tensor], relu: bool,
+                        row_ids: Optional[torch.Tensor] = None, seed: int = 0, step: Optional[torch.Tensor] = None, layer: int = 0,
+                        thr: int = 0, out: Optional[torch.Tensor] = None):
+        """Y = (Z1 + Z2) + bias, with ``relu`` keep ? max(0, .) * scale : 0, in one pass (pgcn_combine_forward_f32).  ``Z2`` /
+        ``bias`` None: that term is absent.  ``step`` None or ``thr`` 0: no dropout; ``step``: one int64 on the device, read by the
+        kernel; ``row_ids``: int64 [n] global ids (None: the row index).  ``out`` may be Z1 itself.  None when the shape is not
+        covered."""
+        mats = (Z1,) + ((Z2,) if Z2 is not None else ()) + ((out,) if out is not None else ())
+        if not self._bn_mat_ok(*mats):
+            return None
+        n, f = Z1.shape
+        if not self._bn_vec_ok(f, torch.float32, bias) or not self._bn_vec_ok(n, torch.int64, row_ids) or \
+                not self._bn_vec_ok(1, torch.int64, step):
+            return None
+        Y = out if out is not None else torch.empty((n, f), dtype=torch.float32, device=self.device)
+        _lib.check(self.lib.pgcn_combine_forward_f32(Z1.data_ptr(), self._ld(Z1), _ptr(Z2), self._ld(Z2) if Z2 is not None else 0, _ptr(bias),
+                                                     n, f, 1 if relu else 0, _ptr(row_ids), int(seed) & ((1 << 64) - 1), _ptr(step),
+                                                     int(layer), int(thr), Y.data_ptr(), self._ld(Y), self._stream()),
+                   "pgcn_combine_forward_f32")
+        return Y
+
+    def combine_backward(self, G: torch.Tensor, Y: Optional[torch.Tensor], relu: bool, scale: float = 1.0, want_gm: bool = True,
+                         want_dbias: bool = True, out: Optional[torch.Tensor] = None):
+        """(Gm, dbias): Gm = Y > 0 ? G * scale : 0 with ``relu`` (G itself without), dbias = fp32 [f], THIS rank's column sums of
+        Gm added in double (pgcn_combine_backward_f32; one pass + the second level of the sums).  ``want_gm`` False: Gm is None
+        (sums only); ``want_dbias`` False: dbias is None (one launch).  None when the shape is not covered."""
+        mats = (G,) + ((Y,) if relu else ()) + ((out,) if out is not None else ())
+        if (relu and Y is None) or not self._bn_mat_ok(*mats):
+            return None
+        n, f = G.shape
+        Gm = dbias = ws = None
+        ws_bytes = 0
+        if want_gm:
+            Gm = out if out is not None else torch.empty((n, f), dtype=torch.float32, device=self.device)
+        if want_dbias:
+            dbias = torch.empty(f, dtype=torch.float32, device=self.device)
+            ws_bytes = int(self.lib.pgcn_combine_ws_bytes(n, f))
+            ws = torch.empty(ws_bytes // 8, dtype=torch.float64, device=self.device)
+        _lib.check(self.lib.pgcn_combine_backward_f32(G.data_ptr(), self._ld(G), Y.data_ptr() if relu else None, self._ld(Y) if relu else 0,
+                                                      n, f, 1 if relu else 0, float(scale), _ptr(Gm), self._ld(Gm) if want_gm else 0,
+                                                      _ptr(dbias), _ptr(ws), ws_bytes, self._stream()), "pgcn_combine_backward_f32")
+        return Gm, dbias
 
     def gather_rows(self, H: torch.Tensor, idx: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
         n = idx.numel()
