@@ -62,6 +62,9 @@ int64_t pgcn_linear_weight_grad_ws_elems(void);
 int pgcn_linear_weight_grad_f32(const float *Gm, int64_t ldg, const float *X, int64_t ldx, int64_t n, int32_t fout, int32_t fin,
                                 float *dW, int64_t lddw, float *ws, int64_t ws_elems, void *stream);
 
+/* The same product on the raw gradient and the forward's sign mask, Gm formed in registers (pgcn_linear_weight_grad_masked_f32 and the
+ * version function a binding checks first): include/pgcn_wgrad_masked.h. */
+
 /* ---- dropout fused into the same kernels (source: <package>/gemm/pgcn_dense.hip; the keep function: <package>/gemm/pgcn_dropout.h,
  * restated in integer numpy by <package>/dropout.py) --------------------------------------------------------------------------------
  * Beyond the reference (which has no dropout); opt-in through PGCN(dropout=...) / `--dropout P`, selected by tuning.dropout_fused.

@@ -183,7 +183,13 @@ class PSpMM(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad_output):
-        return None, ctx.A.backward(grad_output)
+        dH = ctx.A.backward(grad_output)
+        # the weight gradient that the dense backward of this layer left running on the engine's side stream (tuning.wgrad_lane) has had
+        # this launch group to overlap with: the current stream waits for it here
+        join = getattr(ctx.A, "join_wgrad", None)
+        if join is not None:
+            join()
+        return None, dH
 
 
 # ---- the dense products by rocBLAS solution index (gemm/pgcn_gemm.cpp) ---------------------------------------------------
@@ -316,6 +322,15 @@ def bind_dense_library(path):
         L.pgcn_linear_weight_grad_ws_elems.restype = ctypes.c_int64
         L.pgcn_linear_weight_grad_ws_elems.argtypes = []
         L.pgcn_wgrad_last_error.restype = ctypes.c_char_p
+    # the weight gradient on the raw gradient + the sign mask (no Gm in memory): only a library that vouches for the entry point
+    L.pgcn_has_wgrad_masked = False
+    if hasattr(L, "pgcn_wgrad_masked_abi_version"):
+        L.pgcn_wgrad_masked_abi_version.restype = ctypes.c_int
+        L.pgcn_wgrad_masked_abi_version.argtypes = []
+        if L.pgcn_wgrad_masked_abi_version() == 1:
+            L.pgcn_linear_weight_grad_masked_f32.restype = ctypes.c_int
+            L.pgcn_linear_weight_grad_masked_f32.argtypes = [ptr, i64, ptr, ctypes.c_float, ptr, i64, i64, i32, i32, ptr, i64, ptr, i64, ptr]
+            L.pgcn_has_wgrad_masked = True
     # dropout fused into the same kernels: only a library that vouches for them (an older build, or the host emulation, has neither
     # the version function nor the entry points -- the layers then take the unfused route)
     L.pgcn_has_dropout = False
@@ -419,15 +434,20 @@ def linear_relu_grad_input_call(L, g, mask, weight, stream, want_gm=True):
 _wgrad_ws = {}
 
 
+def _wgrad_work_space(L, device, stream):
+    key = (device, stream)
+    ws = _wgrad_ws.get(key)
+    if ws is None:        # one work-space per (device, stream): partial matrices of one product (64 MB; set-up, not a training step)
+        ws = _wgrad_ws[key] = torch.empty(int(L.pgcn_linear_weight_grad_ws_elems()), dtype=torch.float32, device=device)
+    return ws
+
+
 def weight_grad_call(L, gm, x, stream):
     """gm^T . x (fout x fin) through pgcn_linear_weight_grad_f32 of `L`, or None (-2 / no such entry point).  gm: n x fout, x: n x fin."""
     if not hasattr(L, "pgcn_linear_weight_grad_f32") or gm.dim() != 2 or x.dim() != 2 or gm.shape[0] != x.shape[0] or \
             gm.stride(1) != 1 or x.stride(1) != 1 or not (gm.dtype is x.dtype is torch.float32):
         return None
-    key = (gm.device, stream)
-    ws = _wgrad_ws.get(key)
-    if ws is None:        # one work-space per (device, stream): partial matrices of one product (64 MB; set-up, not a training step)
-        ws = _wgrad_ws[key] = torch.empty(int(L.pgcn_linear_weight_grad_ws_elems()), dtype=torch.float32, device=gm.device)
+    ws = _wgrad_work_space(L, gm.device, stream)
     dw = torch.empty((gm.shape[1], x.shape[1]), dtype=torch.float32, device=gm.device)
     rc = L.pgcn_linear_weight_grad_f32(gm.data_ptr(), gm.stride(0), x.data_ptr(), x.stride(0), gm.shape[0], gm.shape[1], x.shape[1],
                                        dw.data_ptr(), dw.stride(0), ws.data_ptr(), ws.numel(), stream)
@@ -435,6 +455,28 @@ def weight_grad_call(L, gm, x, stream):
         return None
     if rc != 0:
         raise RuntimeError("pgcn_linear_weight_grad_f32: %s" % L.pgcn_wgrad_last_error().decode())
+    return dw
+
+
+def weight_grad_masked_call(L, g, mask, scale, x, stream):
+    """gm^T . x with gm = mask ? g * scale : 0 formed in the kernel's registers (pgcn_linear_weight_grad_masked_f32 of `L`), or None (-2 /
+    a library without the entry point).  g: n x fout, x: n x fin, mask: the forward's sign mask (n x ceil(fout / 32) int32) or None
+    (every bit set).  Bit-identical to weight_grad_call on the gm that the input-gradient kernels write."""
+    if not getattr(L, "pgcn_has_wgrad_masked", False) or g.dim() != 2 or x.dim() != 2 or g.shape[0] != x.shape[0] or \
+            g.stride(1) != 1 or x.stride(1) != 1 or not (g.dtype is x.dtype is torch.float32):
+        return None
+    if mask is not None and (mask.shape != (g.shape[0], mask_words(g.shape[1])) or mask.dtype is not torch.int32 or
+                             not mask.is_contiguous() or mask.device != g.device):
+        return None
+    ws = _wgrad_work_space(L, g.device, stream)
+    dw = torch.empty((g.shape[1], x.shape[1]), dtype=torch.float32, device=g.device)
+    rc = L.pgcn_linear_weight_grad_masked_f32(g.data_ptr(), g.stride(0), mask.data_ptr() if mask is not None else None, float(scale),
+                                              x.data_ptr(), x.stride(0), g.shape[0], g.shape[1], x.shape[1], dw.data_ptr(), dw.stride(0),
+                                              ws.data_ptr(), ws.numel(), stream)
+    if rc == -2:
+        return None
+    if rc != 0:
+        raise RuntimeError("pgcn_linear_weight_grad_masked_f32: %s" % L.pgcn_wgrad_last_error().decode())
     return dw
 
 
@@ -463,20 +505,23 @@ def dropout_linear_relu_call(L, x, weight, row_ids, seed, step, layer, thr, stre
     return y, mask
 
 
-def dropout_grad_input_call(L, g, mask, scale, weight, stream, gm=None):
+def dropout_grad_input_call(L, g, mask, scale, weight, stream, gm=None, want_gm=True):
     """(gm, gx) = (mask ? g * scale : 0, gm . weight) through pgcn_dropout_grad_input_f32 of `L`, or None.  gm: where to write it
-    (g itself is allowed), default a new tensor."""
+    (g itself is allowed), default a new tensor; want_gm=False: gm is not written at all (returned as None)."""
     if not getattr(L, "pgcn_has_dropout", False) or g.dim() != 2 or weight.dim() != 2 or g.shape[1] != weight.shape[0] or \
             g.stride(1) != 1 or weight.stride(1) != 1 or not (g.dtype is weight.dtype is torch.float32):
         return None
     if mask is not None and (mask.shape != (g.shape[0], mask_words(g.shape[1])) or mask.dtype is not torch.int32 or
                              not mask.is_contiguous()):
         return None
-    if gm is None:
+    if not want_gm:
+        gm = None
+    elif gm is None:
         gm = torch.empty_like(g, memory_format=torch.contiguous_format)
     gx = torch.empty((g.shape[0], weight.shape[1]), dtype=torch.float32, device=g.device)
     rc = L.pgcn_dropout_grad_input_f32(g.data_ptr(), g.stride(0), mask.data_ptr() if mask is not None else None, float(scale),
-                                       gm.data_ptr(), gm.stride(0), g.shape[0], g.shape[1], weight.data_ptr(), weight.stride(0),
+                                       gm.data_ptr() if gm is not None else None, gm.stride(0) if gm is not None else 0,
+                                       g.shape[0], g.shape[1], weight.data_ptr(), weight.stride(0),
                                        weight.shape[1], gx.data_ptr(), gx.stride(0), stream)
     if rc == -2:
         return None
@@ -506,11 +551,11 @@ def dropout_linear_relu_fused(x, weight, row_ids, seed, step, layer, thr):
     return dropout_linear_relu_call(_dense_lib(), x, weight, row_ids, seed, step, layer, thr, _dense_stream(x))
 
 
-def dropout_grad_input_fused(g, mask, scale, weight):
+def dropout_grad_input_fused(g, mask, scale, weight, want_gm=True):
     """(mask ? g * scale : 0, that . weight) in one pass, or None."""
     if not _dense_operand_ok(g, weight):
         return None
-    return dropout_grad_input_call(_dense_lib(), g, mask, scale, weight, _dense_stream(g))
+    return dropout_grad_input_call(_dense_lib(), g, mask, scale, weight, _dense_stream(g), want_gm=want_gm)
 
 
 def linear_relu_fused(x, weight, relu=True, want_mask=False):
@@ -522,11 +567,11 @@ def linear_relu_fused(x, weight, relu=True, want_mask=False):
     return linear_relu_call(_dense_lib(), x, weight, relu, _dense_stream(x), want_mask)
 
 
-def linear_relu_grad_input_fused(g, mask, weight):
+def linear_relu_grad_input_fused(g, mask, weight, want_gm=True):
     """(g where mask, that . weight): the ReLU mask and the input gradient of relu(x . weight^T) in one pass, or None."""
     if not _dense_operand_ok(g, weight):
         return None
-    return linear_relu_grad_input_call(_dense_lib(), g, mask, weight, _dense_stream(g))
+    return linear_relu_grad_input_call(_dense_lib(), g, mask, weight, _dense_stream(g), want_gm)
 
 
 def weight_grad_fused(gm, x):
@@ -539,6 +584,37 @@ def weight_grad_fused(gm, x):
 def _dense_fused_level():
     from .tuning import T as _T
     return int(_T.dense_fused)
+
+
+def _wgrad_masked_route(g, mask, x, level):
+    """Whether the backward of a fused layer may leave Gm unwritten: the fused route runs (level 3), a mask exists, the operands are
+    the kernels' and the library vouches for pgcn_linear_weight_grad_masked_f32."""
+    return level >= 3 and mask is not None and _dense_operand_ok(g, x) and mask.is_cuda and \
+        getattr(_dense_lib(), "pgcn_has_wgrad_masked", False)
+
+
+def _weight_grad_masked(g, mask, scale, x, weight, eng, joined_later):
+    """dW = (mask ? g * scale : 0)^T . x without that matrix in memory, or None when the kernel refuses the operands.
+
+    tuning.wgrad_lane and an engine (the layer's aggregation engine, handed down by PGCN.forward): the product runs on the engine's
+    side stream behind the input gradient and is joined by PSpMM.backward of the same layer, AFTER that has issued its launch group
+    -- nothing reads dW before the optimizer or the gradient all-reduce.  `joined_later`: that PSpMM.backward will run (the layer's
+    input needs a gradient).  The join happens at once instead when it will not, or when autograd would touch dW before it: a
+    gradient to accumulate into (weight.grad exists: AccumulateGrad adds on the current stream instead of adopting the tensor), a
+    backward under grad mode, hooks on the weight.
+
+    A backward that does not reach that PSpMM.backward after all (torch.autograd.grad for a later layer's weight alone leaves
+    needs_input_grad[0] true and stops there) is covered by a callback at the end of the backward pass, queued with every deferred
+    product: the caller's stream has waited for dW before backward() / grad() returns.  It finds nothing parked in the usual case."""
+    from .tuning import T as _T
+    L = _dense_lib()
+    if eng is None or not int(_T.wgrad_lane) or not hasattr(eng, "wgrad_lane") or torch.device(eng.device) != g.device:
+        return weight_grad_masked_call(L, g, mask, scale, x, _dense_stream(g))
+    later = joined_later and weight.grad is None and not torch.is_grad_enabled() and not weight._backward_hooks and \
+        not getattr(weight, "_post_accumulate_grad_hooks", None)
+    if later:
+        torch.autograd.Variable._execution_engine.queue_callback(eng.join_wgrad)
+    return eng.wgrad_lane(lambda stream: weight_grad_masked_call(L, g, mask, scale, x, stream), (g, x, mask), join_now=not later)
 
 
 class _LinearNoBias(torch.autograd.Function):
@@ -586,7 +662,9 @@ class _LinearReluNoBias(torch.autograd.Function):
     only; 2 + input gradient; 3 + weight gradient.  Same arithmetic class, relu'(0) = 0."""
 
     @staticmethod
-    def forward(ctx, x, weight):
+    def forward(ctx, x, weight, eng=None):
+        # eng: the aggregation engine whose PSpMM produced x (PGCN.forward) -- its backward joins the weight gradient's side stream
+        ctx.eng = eng
         level = _dense_fused_level()
         out = linear_relu_fused(x, weight, True, want_mask=level >= 2) if level >= 1 else None   # (None: not CUDA / not its shapes)
         mask = None
@@ -610,7 +688,23 @@ class _LinearReluNoBias(torch.autograd.Function):
         both = None
         level = _dense_fused_level()
         if ctx.has_mask and level >= 2:
-            both = linear_relu_grad_input_fused(g.contiguous(), ym, weight)       # the mask and g . W in one pass
+            g = g.contiguous()
+            # (the weight gradient masks g in its registers: Gm, whose only reader it was, is not written)
+            masked = ctx.needs_input_grad[1] and _wgrad_masked_route(g, ym, x, level)
+            if masked and not ctx.needs_input_grad[0]:
+                # (a first layer on features without gradient: with Gm gone nothing is left for the input-gradient kernel to write)
+                gw = _weight_grad_masked(g, ym, 1.0, x, weight, ctx.eng, False)
+                if gw is not None:
+                    return None, gw, None
+                masked = False
+            both = linear_relu_grad_input_fused(g, ym, weight, want_gm=not masked)       # the mask and g . W in one pass
+            if both is not None and masked:
+                gx = both[1]
+                gw = _weight_grad_masked(g, ym, 1.0, x, weight, ctx.eng, ctx.needs_input_grad[0])
+                if gw is not None:
+                    return gx, gw, None
+                # (the weight gradient refused operands the input gradient took: Gm after all, for the routes below)
+                both = (torch.where(unpack_sign_mask(ym, g.shape[1]), g, torch.zeros((), dtype=g.dtype, device=g.device)), gx)
         if both is not None:
             g, gx = both
         else:
@@ -624,7 +718,7 @@ class _LinearReluNoBias(torch.autograd.Function):
             gw = weight_grad_fused(g, x) if level >= 3 else None
             if gw is None:
                 gw = _LinearNoBias.weight_grad(g, x)
-        return gx, gw
+        return gx, gw, None
 
 
 class _LinearReluDropoutNoBias(torch.autograd.Function):
@@ -635,8 +729,9 @@ class _LinearReluDropoutNoBias(torch.autograd.Function):
     (kernel on the GPU, dropout.keep_mask on the CPU) + torch.where -- the same results up to the product's rounding."""
 
     @staticmethod
-    def forward(ctx, x, weight, row_ids, state, layer, thr, scale):
+    def forward(ctx, x, weight, row_ids, state, layer, thr, scale, eng=None):
         from .tuning import T as _T
+        ctx.eng = eng                          # (as _LinearReluNoBias: the engine whose PSpMM.backward joins the weight gradient)
         level = _dense_fused_level()
         out = None
         if int(_T.dropout_fused) and level >= 2:
@@ -667,7 +762,20 @@ class _LinearReluDropoutNoBias(torch.autograd.Function):
         level = _dense_fused_level()
         both = None
         if int(_T.dropout_fused) and level >= 2:
-            both = dropout_grad_input_fused(g.contiguous(), mask, ctx.scale, weight)
+            g = g.contiguous()
+            masked = ctx.needs_input_grad[1] and _wgrad_masked_route(g, mask, x, level)     # (as _LinearReluNoBias: Gm is not written)
+            if masked and not ctx.needs_input_grad[0]:         # (... and no input-gradient kernel where nothing reads gx)
+                gw = _weight_grad_masked(g, mask, ctx.scale, x, weight, ctx.eng, False)
+                if gw is not None:
+                    return None, gw, None, None, None, None, None, None
+                masked = False
+            both = dropout_grad_input_fused(g, mask, ctx.scale, weight, want_gm=not masked)
+            if both is not None and masked:
+                gx = both[1]
+                gw = _weight_grad_masked(g, mask, ctx.scale, x, weight, ctx.eng, ctx.needs_input_grad[0])
+                if gw is not None:
+                    return gx, gw, None, None, None, None, None, None
+                both = (torch.where(unpack_sign_mask(mask, g.shape[1]), g * ctx.scale, torch.zeros((), dtype=g.dtype, device=g.device)), gx)
         if both is not None:
             g, gx = both
         else:
@@ -678,7 +786,7 @@ class _LinearReluDropoutNoBias(torch.autograd.Function):
             gw = weight_grad_fused(g, x) if level >= 3 else None
             if gw is None:
                 gw = _LinearNoBias.weight_grad(g, x)
-        return gx, gw, None, None, None, None, None
+        return gx, gw, None, None, None, None, None, None
 
 
 # ---- batch normalisation over ALL vertices of the graph, fused with ReLU and dropout (csrc/pgcn_norm.hip) -------------------------
@@ -1129,8 +1237,8 @@ class PGCN(nn.Module):
             if self._row_ids is None or self._row_ids.device != H.device:      # global ids in local row order, once
                 self._row_ids = self.A.part.owned.to(device=H.device, dtype=torch.int64).contiguous()
             return _LinearReluDropoutNoBias.apply(H, self.linear.weight, self._row_ids, self.state, self.layer, self.dropout_thr,
-                                                  self.dropout_scale)
-        return _LinearReluNoBias.apply(H, self.linear.weight)      # == F.relu(self.linear(H)), PGCN.py:146-147
+                                                  self.dropout_scale, self.A)
+        return _LinearReluNoBias.apply(H, self.linear.weight, self.A)      # == F.relu(self.linear(H)), PGCN.py:146-147
 
 
 def _all_reduce(t, op=dist.ReduceOp.SUM):
@@ -1157,9 +1265,19 @@ def _reduce_sum(t):
     return t
 
 
+def _join_weight_gradients(model):
+    """The current stream waits for every weight gradient still on a side stream (tuning.wgrad_lane) of the engines `model` uses.
+    PSpMM.backward or the end of the backward pass has normally joined them already: then nothing is parked and nothing happens
+    (join_wgrad twice on one engine is harmless, so engines shared by several layers are not sorted out)."""
+    for eng in [_engine_current] + [getattr(m, "A", None) for m in model.modules()]:
+        if hasattr(eng, "join_wgrad"):
+            eng.join_wgrad()
+
+
 def average_gradients(model, average=True):
     """PGCN.py:150-154, as ONE fused all-reduce of all layers' gradients.  ``average=False``: the ranks' sum (the gradient of a
     loss whose rank-local parts add up to the whole, ``masked_loss``)."""
+    _join_weight_gradients(model)
     if world_size <= 1:
         return
     grads = [p.grad.data for p in model.parameters()]

@@ -455,8 +455,56 @@ class AggregationEngine(BoundaryExchange):
         else:
             self.A_loc_T = kernels.prepare(part.A_loc_T) if part.A_loc_T is not None else None
         self.A_halo_T = [kernels.prepare(a) for a in part.A_halo_T]
+        self._wgrad_stream = None       # side stream of the weight gradients (tuning.wgrad_lane), made on first use
+        self._wgrad_parked = []         # [(event after a weight gradient on that stream, tensors it reads)] not yet joined
 
     # ------------------------------------------------------------------
+    def wgrad_lane(self, launch, reads, join_now=False):
+        """Run ``launch(stream handle)`` -- a weight gradient; returns its result tensor, allocated on the current stream, or None --
+        on this engine's side stream behind everything issued so far on the current one, and park an event behind it for
+        ``join_wgrad``.  ``reads``: the tensors it reads, kept alive until the join (they belong to the current stream's allocator,
+        which may hand their memory out again as soon as they are freed); the result is marked as used on the side stream instead,
+        because a reference held here would make autograd copy it rather than adopt it.  Events on streams only: legal inside a
+        HIP-graph capture as long as the join lies inside it too."""
+        main = torch.cuda.current_stream(self.device)
+        # not one of the launch lanes of the aggregation, nor the exchange's stream, nor the current one.  Checked at every use, not
+        # only at the first: the kernels object makes its lane streams when a launch group first needs them, which may be later.
+        # (Events parked on a stream given up here stay valid.)
+        taken = {s.cuda_stream for s in getattr(self.k, "sides", [])} | {main.cuda_stream}
+        if self.comm_stream is not None:
+            taken.add(self.comm_stream.cuda_stream)
+        if self._wgrad_stream is None or self._wgrad_stream.cuda_stream in taken:
+            # torch.cuda.Stream() hands out the streams of a fixed per-device pool in turn, so a new object may wrap a handle that
+            # is already in use: ask again until it is a free one (the pool holds 32; 64 tries cover it twice)
+            for _ in range(64):
+                side = torch.cuda.Stream(device=self.device)
+                if side.cuda_stream not in taken:
+                    break
+            else:
+                raise RuntimeError("no free stream for the weight-gradient lane")
+            self._wgrad_stream = side
+        side = self._wgrad_stream
+        ready = torch.cuda.Event()
+        ready.record(main)
+        side.wait_event(ready)
+        out = launch(side.cuda_stream)
+        if out is not None:
+            out.record_stream(side)
+        done = torch.cuda.Event()
+        done.record(side)
+        self._wgrad_parked.append((done, reads))
+        if join_now:
+            self.join_wgrad()
+        return out
+
+    def join_wgrad(self) -> None:
+        """The current stream waits for every weight gradient parked by ``wgrad_lane`` (none: nothing happens)."""
+        if self._wgrad_parked:
+            main = torch.cuda.current_stream(self.device)
+            for done, _ in self._wgrad_parked:
+                main.wait_event(done)
+            self._wgrad_parked = []
+
     def forward(self, H: torch.Tensor) -> torch.Tensor:
         """AH = A_p . [H ; halo]   (H: n_local x f, owned rows only)."""
         if H.shape[0] != self.n_local:

@@ -22,6 +22,21 @@
 //
 // Arithmetic: x = x1 + x2 + x3 exactly (bf16 planes), the six partial products that matter smallest first, fp32 accumulation
 // inside the MFMA -- the error class of an fp32 dot product (tests hold it to 1e-6 of sum |g||x|).
+//
+// Masked form (MASKED; pgcn_linear_weight_grad_masked_f32): the operand is the raw gradient G and the sign mask of the forward
+// (n x ceil(fout / 32) words, bit b of word [row][w] = column 32 w + b); Gm = bit ? G * scale : +0 is formed in registers when a
+// step's operand blocks are taken up, before the three-plane split -- Gm never exists in memory.  A lane holds ONE column and
+// eight rows, so the bits it needs sit in sixteen different words (8 rows x the two blocks of its tile) and every word serves
+// the 32 lanes of a half wave.  Taken naively that is 16 more loads and 16 more registers per lane, step and set in flight
+// (233 VGPRs are in use without them).  Instead the 32 words of a step (16 rows x 2 blocks) are ONE dword load: lane l & 31 reads
+// word (row l & 15, block l >> 4), one register per set in flight.  For register j of block b the 64 select bits of the wave
+// are exactly word (row j, b) for lanes 0-31 and word (row 8 + j, b) for lanes 32-63: two v_readlane put them into a scalar
+// pair, and the select is one v_cndmask on that pair as the lane mask -- no per-lane bit arithmetic at all (32 v_readlane + 16
+// v_cndmask + 16 v_mul per 24 MFMAs).  The words go through a buffer descriptor like the operands, not through LDS: a wave's
+// rows are its own (waves of a half that share rows read different words, or the same 128 bytes once), so LDS would buy no
+// re-use and cost a barrier between waves that otherwise never meet before the end; the descriptor gives rows beyond n as zero
+// words for free, which is the cleared bit that the zero rows of G want.  A select, not a product: a NaN or Inf of G under a
+// cleared bit contributes +0.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -55,6 +70,7 @@ inline int fail(int code, const char *what) {
 
 struct StepRaw {                          // the 32 values of one lane and step: operand blocks (a0, a1 of Gm; b0, b1 of X) x 8 rows
     float a[2][8], b[2][8];
+    uint32_t m;                           // MASKED: mask word (row l & 15 of the step, block l >> 4 of the tile) of lane l & 31
 };
 
 // ---- loads: one buffer descriptor per matrix and wave (its row range; rows beyond the matrix read as zero by the hardware's bounds
@@ -64,9 +80,10 @@ using rsrc_t = __amdgpu_buffer_rsrc_t;
 PG_HD float buf_load(rsrc_t r, uint32_t voff, uint32_t soff) {
     return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, (int)voff, (int)soff, 0));
 }
-template <bool A1, bool B1, bool WGUARD>
+template <bool A1, bool B1, bool WGUARD, bool MASKED>
 PG_HD void load_step(StepRaw &s, rsrc_t g, rsrc_t x, uint32_t soff_g, uint32_t soff_x, const uint32_t (&goff)[8], const uint32_t (&xoff)[8],
-                     bool a0_ok, bool a1_ok, bool b0_ok, bool b1_ok) {
+                     bool a0_ok, bool a1_ok, bool b0_ok, bool b1_ok, rsrc_t m, uint32_t moff, uint32_t soff_m) {
+    if constexpr (MASKED) s.m = __builtin_bit_cast(uint32_t, buf_load(m, moff, soff_m));
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
         s.a[0][j] = buf_load(g, goff[j], soff_g);
@@ -80,6 +97,20 @@ PG_HD void load_step(StepRaw &s, rsrc_t g, rsrc_t x, uint32_t soff_g, uint32_t s
             s.b[1][j] = b1_ok ? s.b[1][j] : 0.f;
         }
     }
+}
+
+// Gm of one step in place: a[b][j] = bit ? a[b][j] * scale : +0, the 64 bits of register j and block b as one scalar lane mask
+// (lanes 0-31: the word of row j, lanes 32-63: the word of row 8 + j).  all_set: no mask was passed (every bit set).
+template <bool A1>
+PG_HD void mask_step(StepRaw &s, float scale, uint32_t all_set) {
+    const uint32_t w = s.m | all_set;
+#pragma unroll
+    for (int b = 0; b < (A1 ? 2 : 1); ++b)
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)w, 16 * b + j), hi = (uint32_t)__builtin_amdgcn_readlane((int)w, 16 * b + 8 + j);
+            s.a[b][j] = __builtin_amdgcn_inverse_ballot_w64(((uint64_t)hi << 32) | lo) ? s.a[b][j] * scale : 0.f;
+        }
 }
 
 PG_HD void planes_of(const float (&v)[8], u32x4 (&p)[3]) {
@@ -150,9 +181,11 @@ PG_HD void steps_of_range(int64_t nsteps, int ranges, int g, int64_t &s0, int64_
 
 // partial[range][FO x FI] (FO = 64 TO, FI = 64 TK) += this wave's tile.  TO x TK tiles of 64 x 64 per half; a half of four waves
 // holds 4 / (TO TK) row ranges; halves h = 0, 1 of a workgroup take different row ranges and are added through LDS.
-template <int TO, int TK, bool A1, bool B1, bool F32, bool WGUARD>
+// MASKED: Gm is the raw gradient G, masked and scaled in registers (header); mask == NULL: every bit set.
+template <int TO, int TK, bool A1, bool B1, bool F32, bool WGUARD, bool MASKED>
 __global__ __launch_bounds__(kThreads, 2) void wgrad_kernel(const float *__restrict__ Gm, int64_t ldg, const float *__restrict__ X,
-                                                            int64_t ldx, int64_t n, int fout, int fin, float *__restrict__ partial) {
+                                                            int64_t ldx, int64_t n, int fout, int fin, float *__restrict__ partial,
+                                                            const uint32_t *__restrict__ mask, float scale) {
     constexpr int kDepth = F32 ? kDepthF32 : kDepthBf16;         // register sets of operands in flight
     constexpr int kTiles = TO * TK, kSub = 4 / kTiles;            // tiles of dW, row ranges of a half
     constexpr int FI = 64 * TK, FO = 64 * TO;
@@ -204,28 +237,43 @@ __global__ __launch_bounds__(kThreads, 2) void wgrad_kernel(const float *__restr
     };
     const rsrc_t gr = descriptor(Gm, ldg, gstep), xr = descriptor(X, ldx, xstep);
     const uint32_t gs = (uint32_t)gstep, xs = (uint32_t)xstep;
+    // the mask words of the range as a third buffer of mw words per row (empty without a mask: zero words, OR-ed with all_set);
+    // a tile's second block may lie wholly beyond the width (its values are dropped by the guard): its word is clamped into the row
+    const int mw = (fout + 31) >> 5;
+    const rsrc_t mr = MASKED ? descriptor(reinterpret_cast<const float *>(mask), mask ? mw : 0, (int64_t)kStepRows * mw * 4) : gr;
+    const uint32_t ms = MASKED ? (uint32_t)(kStepRows * mw * 4) : 0u, all_set = mask ? 0u : ~0u;
+    uint32_t moff = 0;
+    if constexpr (MASKED) {
+        const int word = 2 * to + ((lane >> 4) & 1);
+        moff = (uint32_t)(((lane & 15) * mw + (word < mw ? word : mw - 1)) * 4);
+    }
     const int nst = __builtin_amdgcn_readfirstlane((int)(s1 - s0));          // steps of this wave (the last one may be ragged: zeros)
     {
         // kDepth register sets, the set consumed in iteration i is refilled with step i + kDepth
         StepRaw raw[kDepth];
 #pragma unroll
         for (int d = 0; d < kDepth; ++d)
-            if (d < nst) load_step<A1, B1, WGUARD>(raw[d], gr, xr, d * gs, d * xs, goff, xoff, a0_ok, a1_ok, b0_ok, b1_ok);
+            if (d < nst) load_step<A1, B1, WGUARD, MASKED>(raw[d], gr, xr, d * gs, d * xs, goff, xoff, a0_ok, a1_ok, b0_ok, b1_ok, mr, moff, d * ms);
         int t = 0;
-        uint32_t og = kDepth * gs, ox = kDepth * xs;                 // byte offsets of step t + kDepth
+        uint32_t og = kDepth * gs, ox = kDepth * xs, om = kDepth * ms;   // byte offsets of step t + kDepth
         while (t + kDepth <= nst) {                                  // kDepth steps per trip, every set refilled right after its use
 #pragma unroll
             for (int d = 0; d < kDepth; ++d) {
+                if constexpr (MASKED) mask_step<A1>(raw[d], scale, all_set);
                 step_any<A1, B1, F32>(raw[d], acc);
-                if (t + d + kDepth < nst) load_step<A1, B1, WGUARD>(raw[d], gr, xr, og + d * gs, ox + d * xs, goff, xoff, a0_ok, a1_ok, b0_ok, b1_ok);
+                if (t + d + kDepth < nst) load_step<A1, B1, WGUARD, MASKED>(raw[d], gr, xr, og + d * gs, ox + d * xs, goff, xoff, a0_ok, a1_ok, b0_ok, b1_ok, mr, moff, om + d * ms);
             }
             t += kDepth;
             og += kDepth * gs;
             ox += kDepth * xs;
+            om += kDepth * ms;
         }
 #pragma unroll
         for (int d = 0; d < kDepth; ++d)                             // the last nst - t < kDepth steps (already loaded)
-            if (t + d < nst) step_any<A1, B1, F32>(raw[d], acc);
+            if (t + d < nst) {
+                if constexpr (MASKED) mask_step<A1>(raw[d], scale, all_set);
+                step_any<A1, B1, F32>(raw[d], acc);
+            }
     }
     // the two halves of the workgroup: half 1 hands its accumulators over through LDS
     if (half == 1) {
@@ -339,9 +387,10 @@ extern "C" const char *pgcn_wgrad_last_error(void) { return pgcn_wgrad::g_err; }
 extern "C" int64_t pgcn_linear_weight_grad_ws_elems(void) { return (int64_t)1024 * 128 * 128; }
 
 namespace pgcn_wgrad {
-template <bool F32>
+// MASKED: Gm is the raw gradient, `mask` (may be NULL: every bit set) and `scale` make Gm in registers
+template <bool F32, bool MASKED>
 int run(const float *Gm, int64_t ldg, const float *X, int64_t ldx, int64_t n, int32_t fout, int32_t fin, float *dW, int64_t lddw,
-        float *ws, int64_t ws_elems, void *stream) {
+        float *ws, int64_t ws_elems, void *stream, const uint32_t *mask = nullptr, float scale = 1.0f) {
     int dev = 0, cus = 0;
     if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
         cus <= 0)
@@ -365,10 +414,10 @@ int run(const float *Gm, int64_t ldg, const float *X, int64_t ldx, int64_t n, in
     }
 #define PGCN_WGRAD_CASE(TO_, TK_, A1_, B1_)                                                                                   \
     if (sh.TO == TO_ && sh.TK == TK_ && sh.A1 == A1_ && sh.B1 == B1_) {                                                        \
-        if (ragged) hipLaunchKernelGGL((wgrad_kernel<TO_, TK_, A1_, B1_, F32, true>), dim3((unsigned)wgs), dim3(kThreads), 0, s, Gm, ldg, X, \
-                           ldx, n, fout, fin, ws);                                                                           \
-        else hipLaunchKernelGGL((wgrad_kernel<TO_, TK_, A1_, B1_, F32, false>), dim3((unsigned)wgs), dim3(kThreads), 0, s, Gm, ldg, X,    \
-                           ldx, n, fout, fin, ws);                                                                                    \
+        if (ragged) hipLaunchKernelGGL((wgrad_kernel<TO_, TK_, A1_, B1_, F32, true, MASKED>), dim3((unsigned)wgs), dim3(kThreads), 0, s, Gm, \
+                           ldg, X, ldx, n, fout, fin, ws, mask, scale);                                                                \
+        else hipLaunchKernelGGL((wgrad_kernel<TO_, TK_, A1_, B1_, F32, false, MASKED>), dim3((unsigned)wgs), dim3(kThreads), 0, s, Gm, ldg,  \
+                           X, ldx, n, fout, fin, ws, mask, scale);                                                                     \
     } else
     PGCN_WGRAD_CASE(2, 2, true, true)
     PGCN_WGRAD_CASE(2, 1, true, true)
@@ -393,12 +442,30 @@ int run(const float *Gm, int64_t ldg, const float *X, int64_t ldx, int64_t n, in
 // library product); -1: errors (pgcn_wgrad_last_error()).  Never allocates, never synchronises: two launches on `stream`.
 extern "C" int pgcn_linear_weight_grad_f32(const float *Gm, int64_t ldg, const float *X, int64_t ldx, int64_t n, int32_t fout,
                                            int32_t fin, float *dW, int64_t lddw, float *ws, int64_t ws_elems, void *stream) {
-    return pgcn_wgrad::run<PGCN_WGRAD_F32MFMA != 0>(Gm, ldg, X, ldx, n, fout, fin, dW, lddw, ws, ws_elems, stream);
+    return pgcn_wgrad::run<PGCN_WGRAD_F32MFMA != 0, false>(Gm, ldg, X, ldx, n, fout, fin, dW, lddw, ws, ws_elems, stream);
+}
+
+// 1: pgcn_linear_weight_grad_masked_f32 below exists (a binding checks this before it resolves the entry point)
+extern "C" int pgcn_wgrad_masked_abi_version(void) { return 1; }
+
+// dW (fout x fin, lddw) = Gm^T . X with Gm[i][c] = bit c of the mask's row i ? G[i][c] * scale : +0, formed in registers: the product
+// of pgcn_linear_weight_grad_f32 on the Gm that pgcn_linear_relu_grad_input_f32 / pgcn_dropout_grad_input_f32 would have written,
+// bit for bit, without that matrix.  mask: n x ceil(fout / 32) words in the sign-mask layout of pgcn_linear_relu_f32, 4-byte
+// aligned, or NULL (every bit set); a select, not a product (NaN / Inf of G under a cleared bit contribute +0).  mask == NULL and
+// scale == 1 is the kernel of pgcn_linear_weight_grad_f32.  Everything else (operands, work-space, return codes) as above.
+extern "C" int pgcn_linear_weight_grad_masked_f32(const float *G, int64_t ldg, const int32_t *mask, float scale, const float *X,
+                                                  int64_t ldx, int64_t n, int32_t fout, int32_t fin, float *dW, int64_t lddw, float *ws,
+                                                  int64_t ws_elems, void *stream) {
+    if (!mask && scale == 1.0f)
+        return pgcn_wgrad::run<PGCN_WGRAD_F32MFMA != 0, false>(G, ldg, X, ldx, n, fout, fin, dW, lddw, ws, ws_elems, stream);
+    if ((uintptr_t)mask % 4) return pgcn_wgrad::fail(-2, "pgcn_linear_weight_grad_masked_f32: the mask words must be 4-byte aligned");
+    return pgcn_wgrad::run<PGCN_WGRAD_F32MFMA != 0, true>(G, ldg, X, ldx, n, fout, fin, dW, lddw, ws, ws_elems, stream,
+                                                          reinterpret_cast<const uint32_t *>(mask), scale);
 }
 #ifdef PGCN_WGRAD_PROBES
 // measurement build (tools/micro/dense_fused_bench): the same kernel on the fp32 matrix cores
 extern "C" int pgcn_linear_weight_grad_f32mfma_f32(const float *Gm, int64_t ldg, const float *X, int64_t ldx, int64_t n, int32_t fout,
                                                    int32_t fin, float *dW, int64_t lddw, float *ws, int64_t ws_elems, void *stream) {
-    return pgcn_wgrad::run<true>(Gm, ldg, X, ldx, n, fout, fin, dW, lddw, ws, ws_elems, stream);
+    return pgcn_wgrad::run<true, false>(Gm, ldg, X, ldx, n, fout, fin, dW, lddw, ws, ws_elems, stream);
 }
 #endif

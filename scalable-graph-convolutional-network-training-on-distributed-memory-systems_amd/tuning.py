@@ -97,6 +97,15 @@ class Tuning:
                                      # 0 = the library route.  r05 on the MI355X at n = 232 965, f = 128: forward 63.3 us against 85 + 35 us
                                      # of rocBLAS + clamp, input gradient 116.8 us against 50 + 86 us; epochs 10.52 / 10.48 / 10.45 ms off,
                                      # 10.37 / 10.36 / 10.34 at level 2 (profiles/r05_dense_fused_epochs.txt); r06: DESIGN.md section 4
+    wgrad_lane: int = 0              # 1 = the weight gradient of a fused layer (dense_fused 3, a sign mask: it then masks the raw gradient itself and Gm
+                                     # is never written) on a side stream of the engine, behind the input gradient and BESIDE the transposed
+                                     # aggregation of the same layer, whose PSpMM.backward joins it after issuing its launch group; nothing reads dW
+                                     # before the optimizer / the gradient all-reduce.  0 = on the current stream, between the two.  Same bits either
+                                     # way.  OFF because it loses: four alternating runs on one MI355X, parent 10.08-10.14 ms per epoch, lane off
+                                     # 9.95-10.00, lane on 10.00-10.02 (every lane-on run slower than every lane-off run; the mid workload 0.62 ->
+                                     # 0.87 ms).  The trace shows the kernel running beside the launch group as intended -- stretched from 53 to
+                                     # 800 us -- and the group 30-45 us longer for it: the two share the memory system that bounds the group, and
+                                     # the overlap buys back less than it costs.  HISTORY.md section 21
     dropout_fused: int = 1           # dropout of a layer's output (PGCN(dropout=...)) in the epilogue of the dense kernels (one forward kernel leaves
                                      # y and the words sign AND keep; the backward scales by them) instead of library product + keep-words kernel
                                      # + element-wise passes; 0 = always the unfused route (same masks, same results up to the product's rounding)
