@@ -623,6 +623,43 @@ int pgcn_combine_backward_f32(const float *G, int64_t ldg, const float *Y, int64
                               float scale, float *Gm, int64_t ldgm, float *dbias, void *ws, int64_t ws_bytes,
                               pgcn_stream_t stream);
 
+/* ---- layer normalisation of a vertex over its features + residual link, fused with ReLU and dropout (PGCN.py: _LayerNormReluDropout)
+ * The layer y = R + drop(relu(LN(x))) of an nrows x f block of OWNED rows.  Row-local: no collective, and a row's results depend on
+ * that row alone -- not on its position, the block that met it, nrows or the rank.
+ * pgcn_ln_relu_forward_f32:  mean_i = sum_j X[i,j] / f;  var_i = sum_j (X[i,j] - mean_i)^2 / f (biased, two passes in registers, not
+ *   E[x^2] - mean^2);  rstd_i = 1 / sqrt(var_i + float(eps)) -- fp32 sums: a thread adds its four columns in a fixed order, then a
+ *   fixed tree of depth <= log2(TPR) + 1 over the TPR threads of the row.  xh = (X[i,j] - mean_i) rstd_i;  t = fma(gamma[j], xh,
+ *   beta[j]);  d = keep ? max(0, t) * scale : 0;  Y[i,j] = R ? R[i,j] + d : d (R == NULL: nothing is added).  step == NULL or
+ *   thr == 0: keep is true and scale 1.  Otherwise keep / scale are those of gemm/pgcn_dropout.h with the key (seed, *step, layer,
+ *   row_ids[i] (NULL: i), j): the masks every other layer kind draws for that layer; *step is read from device memory.
+ *   mean, rstd: nrows floats, the fp32 values the kernel itself used.  mask: nrows x ceil(f / 32) int32 words, contiguous, the
+ *   sign-mask layout of include/pgcn_gemm.h: bit b of word w of a row is 1 iff element 32 w + b was kept and t > 0; bits at and
+ *   beyond f are 0.  With R added Y > 0 no longer says that, so the backward takes the bits and not Y.  mean, rstd and mask may all
+ *   three be NULL (inference: nothing is saved).  Y == R with ldy == ldr is allowed (in place).  One launch; nrows == 0: none.
+ * pgcn_ln_relu_backward_f32:  g' = bit ? G[i,j] * scale : 0;  gh = g' gamma[j];  xh as in the forward, from X, mean, rstd;
+ *   c1 = sum_j gh / f, c2 = sum_j gh xh / f (one tree for both);  dX[i,j] = rstd_i ((gh - c1) - xh c2).  In the same pass
+ *   dbeta[j] = float(sum_i g'), dgamma[j] = float(sum_i g' xh), added in double: a block owns 512 consecutive rows, folds its row
+ *   groups through LDS by a fixed tree and writes one partial record [2][f] of doubles to `ws` (pgcn_ln_ws_bytes(nrows, f) bytes,
+ *   8-byte aligned, at least one record; -1 for sizes the kernels refuse); a second launch, 32 of the 2 f outputs per block, adds
+ *   the records in a fixed order -- no floating-point atomics, the same input gives the same bits.  dgamma / dbeta are RANK-LOCAL
+ *   sums: the training loop adds the ranks' parameter gradients itself.  Both NULL: no sums, ws is not read, one launch.
+ *   nrows == 0: they are zeroed, nothing else is written.  The residual's gradient is G itself: no kernel.
+ * Both: row-major with leading dimensions in elements, 64-bit row offsets; every f from 1 to 1024 (PGCN_EUNSUPPORTED above); a
+ * thread owns four consecutive columns -- one float4 when f % 4 == 0 and every base and leading dimension keeps rows 16-byte
+ * aligned, four guarded scalars otherwise, the same bits either way (the file is built with -ffp-contract=off: the one fused
+ * operation is the written fma).  PGCN_EINVAL, nothing launched: a null required pointer,
+ * nrows < 0, f < 1, a leading dimension below f, eps non-finite or <= 0, a scale that is not finite and positive, a misaligned ws /
+ * step / row_ids / mask, in place with differing leading dimensions, only some of mean / rstd / mask (or of dgamma / dbeta) given;
+ * PGCN_ENOMEM: ws_bytes too small.  A NaN or inf in a row stays in that row's outputs, and in the dgamma / dbeta columns whose bit
+ * that row has set.  Raw pointers + a stream, no allocation, no synchronisation (graph-capturable).                        */
+int64_t pgcn_ln_ws_bytes(int64_t nrows, int32_t f);
+int pgcn_ln_relu_forward_f32(const float *X, int64_t ldx, int64_t nrows, int32_t f, const float *gamma, const float *beta, double eps,
+                             const float *R, int64_t ldr, const int64_t *row_ids, uint64_t seed, const int64_t *step, uint32_t layer,
+                             uint32_t thr, float *Y, int64_t ldy, float *mean, float *rstd, int32_t *mask, pgcn_stream_t stream);
+int pgcn_ln_relu_backward_f32(const float *G, int64_t ldg, const float *X, int64_t ldx, int64_t nrows, int32_t f, const float *mean,
+                              const float *rstd, const float *gamma, const int32_t *mask, float scale, float *dX, int64_t lddx,
+                              float *dgamma, float *dbeta, void *ws, int64_t ws_bytes, pgcn_stream_t stream);
+
 /* ---- boundary-row pack / unpack -------------------------------------------
  * out[r,:] = H[idx[r],:]                      replaces H[indices]   GPU/PGCN.py:104
  * H[idx[r],:] (+)= in[r,:]                    replaces X[indices] = buf   :115

@@ -790,7 +790,8 @@ class _LinearReluDropoutNoBias(torch.autograd.Function):
 
 
 # ---- batch normalisation over ALL vertices of the graph, fused with ReLU and dropout (csrc/pgcn_norm.hip) -------------------------
-NORMS = ("none", "batch")       # --norm / run(norm=...): "none" (the default) is the layer of before
+NORMS = ("none", "batch", "node")       # --norm / run(norm=...): "none" (the default) is the layer of before; "node" = layer
+#                                         normalisation of one vertex over its features (PyG's mode="node"; "layer" stays refused)
 
 
 def _bn_keep(X, row_ids, state, layer, thr):
@@ -874,9 +875,9 @@ def _bn_kernels(X, vectors=(), row_ids=None):
     return k if _row_ids_ok(row_ids, X.shape[0]) and (row_ids is None or row_ids.device == X.device) else None
 
 
-def _bn_must(out, what):
+def _bn_must(out, what, gate="_bn_kernels"):
     if out is None:
-        raise RuntimeError("%s refused operands that _bn_kernels accepted" % what)
+        raise RuntimeError("%s refused operands that %s accepted" % (what, gate))
     return out
 
 
@@ -926,6 +927,114 @@ class _BatchNormReluDropout(torch.autograd.Function):
         else:
             out = batchnorm_relu_backward_composed(G, Y, X, mean, invstd, gamma, ctx.n_global, ctx.scale, ctx.training)
         return out + (None,) * 10
+
+
+# ---- layer normalisation of a vertex over its features + residual link, fused with ReLU and dropout (csrc/pgcn_layernorm.hip) --------
+def layernorm_relu_composed(X, gamma, beta, R=None, eps=1e-5, row_ids=None, state=None, layer=0, thr=0, scale=1.0):
+    """(Y, mean, rstd, bits) of R + drop(relu(LN(X))) from framework operations, the definitions of csrc/pgcn_layernorm.hip: per ROW
+    mean = sum x / f, var = sum (x - mean)^2 / f (biased, two passes), rstd = 1 / sqrt(var + eps), all in X's precision;
+    t = gamma (x - mean) rstd + beta;  Y = R + (keep ? max(0, t) * scale : 0) -- keep the bits of dropout.py under (seed, step, layer,
+    global row id, column); ``state`` None or ``thr`` 0: no dropout; ``R`` None: nothing is added.  ``bits``: bool [n, f], kept and
+    t > 0 -- the mask the backward takes instead of Y (with R added Y > 0 says nothing).  No collective: a row's results are its own.
+    For CPU tensors, the checker-backed provider of the tests and f > 1024."""
+    f = X.shape[1]
+    Xd = X.detach()
+    mean = Xd.sum(1) / f
+    e = Xd - mean.unsqueeze(1)
+    rstd = 1.0 / torch.sqrt((e * e).sum(1) / f + eps)
+    t = torch.addcmul(beta.detach(), gamma.detach(), e * rstd.unsqueeze(1))
+    zero = torch.zeros((), dtype=t.dtype, device=t.device)
+    Y = torch.where(t < 0, zero, t)                                                  # (NaN stays NaN, as in the kernel)
+    bits = t > 0
+    if state is not None and thr > 0:
+        keep = _bn_keep(X, row_ids, state, layer, thr)
+        Y = torch.where(keep, Y * scale, zero)
+        bits = bits & keep
+    if R is not None:
+        Y = R.detach() + Y
+    return Y, mean, rstd, bits
+
+
+def layernorm_relu_backward_composed(G, X, mean, rstd, gamma, bits, scale=1.0):
+    """(dX, dgamma, dbeta) of the same layer: g' = bit ? G scale : 0, gh = g' gamma, xh = (X - mean) rstd, c1 = sum_j gh / f,
+    c2 = sum_j gh xh / f, dX = rstd ((gh - c1) - xh c2);  dbeta = sum_i g' and dgamma = sum_i g' xh are THIS rank's column sums, added
+    in float64 and rounded once (a masked-out element adds exact zeros whatever its x): the training loop adds the ranks' parameter
+    gradients itself.  The residual's gradient is G itself."""
+    f = X.shape[1]
+    gm = torch.where(bits, G * scale, torch.zeros((), dtype=G.dtype, device=G.device))
+    gh = gm * gamma.detach()
+    xh = (X - mean.unsqueeze(1)) * rstd.unsqueeze(1)
+    c1, c2 = gh.sum(1, keepdim=True) / f, (gh * xh).sum(1, keepdim=True) / f
+    dX = rstd.unsqueeze(1) * ((gh - c1) - xh * c2)
+    gd = gm.double()
+    dgamma = torch.where(bits, gd * xh.double(), torch.zeros((), dtype=torch.float64, device=G.device)).sum(0).to(X.dtype)
+    return dX, dgamma, gd.sum(0).to(X.dtype)
+
+
+def _ln_kernels(X, vectors=(), R=None, row_ids=None, step=None):
+    """The provider whose layer-norm kernels take X, the per-column vectors and the residual, or None (CPU tensors, the checker-backed
+    provider of the tests, more than 1024 columns, another dtype or layout).  Decided BEFORE the first launch, as ``_bn_kernels``."""
+    k = _kernel_provider if _kernel_provider is not None else getattr(_engine_current, "k", None)
+    if k is None or not hasattr(k, "ln_relu_forward") or not hasattr(k, "ln_relu_backward"):
+        return None
+    for t in (X, R):
+        if t is not None and not (t.is_cuda and t.dim() == 2 and t.dtype is torch.float32 and t.shape == X.shape and t.device == X.device
+                                  and 0 < t.shape[1] <= _kernels.LN_MAX_F and (t.stride(1) == 1 or t.shape[1] == 1 or t.shape[0] == 0)
+                                  and (t.shape[0] <= 1 or t.stride(0) >= t.shape[1])):
+            return None
+    if not all(v.is_cuda and v.device == X.device and v.dtype is torch.float32 and v.is_contiguous() and v.numel() == X.shape[1]
+               for v in vectors):
+        return None
+    if step is not None and not (step.is_cuda and step.device == X.device and step.dtype is torch.int64 and step.numel() == 1):
+        return None
+    return k if _row_ids_ok(row_ids, X.shape[0]) and (row_ids is None or row_ids.device == X.device) else None
+
+
+class _LayerNormReluDropout(torch.autograd.Function):
+    """R + drop(relu(LN(X))) as ONE autograd node, LN over each vertex's own features: no collective, the same results under any part
+    vector.  On a HIP device one launch forward (pgcn_ln_relu_forward_f32: the row statistics in registers, the dropout keep function
+    of the fused dense kernel, the residual's addition, and 1 bit per element: kept and pre-activation positive) and one pass backward
+    (pgcn_ln_relu_backward_f32: reads G, X and the bits, writes dX, adds dgamma / dbeta in double in the same pass).  Saved: X,
+    gamma, mean, rstd and the bits -- no Y: with R added Y > 0 no longer says which elements survived.  R's gradient is G itself.
+    dgamma / dbeta are THIS rank's sums.  ``training=False``: the same statistics (they are the row's own) without dropout.  Anything
+    the kernels do not cover (CPU tensors, f > 1024, the checker-backed provider) takes ``layernorm_relu_composed``: the same
+    definitions, the bits as a bool tensor."""
+
+    @staticmethod
+    def forward(ctx, X, gamma, beta, R, training, eps, row_ids, state, layer, thr, scale):
+        drop = bool(training and state is not None and thr > 0)
+        save = any(ctx.needs_input_grad[:3])           # (only R wants a gradient: that is G itself, nothing to save)
+        k = _ln_kernels(X, (gamma, beta), R, row_ids if drop else None, state.step if drop else None)
+        if k is not None:
+            Y, mean, rstd, mask = _bn_must(k.ln_relu_forward(X, gamma.detach(), beta.detach(), eps, R.detach() if R is not None else None,
+                                                             row_ids if drop else None, state.seed if drop else 0,
+                                                             state.step if drop else None, layer, thr if drop else 0, save=save),
+                                           "ln_relu_forward", "_ln_kernels")
+        else:
+            Y, mean, rstd, mask = layernorm_relu_composed(X, gamma, beta, R, eps, row_ids, state if drop else None, layer,
+                                                          thr if drop else 0, scale)
+        ctx.scale, ctx.saved = float(scale) if drop else 1.0, save
+        if save:
+            ctx.save_for_backward(X, gamma, mean, rstd, mask)
+        return Y
+
+    @staticmethod
+    def backward(ctx, G):
+        Gr = G if ctx.needs_input_grad[3] else None                                  # (the residual's gradient: G itself, no kernel)
+        if not ctx.saved:
+            return (None, None, None, Gr) + (None,) * 7
+        X, gamma, mean, rstd, mask = ctx.saved_tensors
+        if G.stride(1) != 1 or (G.shape[0] > 1 and G.stride(0) < G.shape[1]):
+            G = G.contiguous()
+        want_sums = ctx.needs_input_grad[1] or ctx.needs_input_grad[2]
+        k = _ln_kernels(X, (gamma,)) if (G.is_cuda and G.dtype is torch.float32 and mask.dtype is torch.int32) else None
+        if k is not None:
+            dX, dgamma, dbeta = _bn_must(k.ln_relu_backward(G, X, mean, rstd, gamma.detach(), mask, ctx.scale, want_sums=want_sums),
+                                         "ln_relu_backward", "_ln_kernels")
+        else:
+            bits = unpack_sign_mask(mask, X.shape[1]) if mask.dtype is torch.int32 else mask
+            dX, dgamma, dbeta = layernorm_relu_backward_composed(G, X, mean, rstd, gamma, bits, ctx.scale)
+        return (dX, dgamma, dbeta, Gr) + (None,) * 7
 
 
 # ---- root weight and bias, fused with ReLU and dropout (csrc/pgcn_combine.hip) -----------------------------------------------------
@@ -1164,9 +1273,22 @@ class PGCN(nn.Module):
     (Z1 + Z2) + b.  With ``norm="batch"`` the plain sum Z1 + Z2 feeds ``_BatchNormReluDropout`` and the layer owns NO ``bias`` even
     when asked for one: ``bn_bias`` is the shift, a second one in front of the normalisation would be removed by the mean.  Ordinary
     parameters, both: initialised, reduced, decayed and stepped with the rest.  With both flags false none of this exists and
-    ``forward`` takes the branches of before."""
+    ``forward`` takes the branches of before.
 
-    def __init__(self, A, in_features, out_features, dropout=0.0, layer=0, state=None, relu=True, norm=None, root_weight=False, bias=False):
+    ``norm="node"`` (opt-in; needs ``relu=True``): drop(relu(LN(A H W^T))) with LN the layer normalisation of ONE vertex over its own
+    features (PyG's ``mode="node"``) -- the aggregation, the plain product ``_LinearNoBias`` and the node ``_LayerNormReluDropout``.
+    Row-local: no collective, the same results under any part vector.  The layer then owns ``ln_weight`` (ones) and ``ln_bias``
+    (zeros), ordinary parameters, and no buffers; ``ln_eps`` = 1e-5.  ``eval()`` uses the same statistics (they are the vertex's own)
+    without dropout.  As with ``norm="batch"`` a normalised layer owns no ``bias``, and with ``root_weight`` the plain sum Z1 + Z2
+    feeds the node.
+
+    ``residual=True`` (opt-in; needs ``relu=True`` and ``in_features == out_features``): the output is H + layer(H).  With
+    ``norm="node"`` the addition happens inside the node's kernel (its operand R, one extra read); with every other layer kind
+    (plain, dropout, batch norm, root weight / bias) it is a framework addition AFTER the existing node -- one more pass over the
+    output, no new kernel.  Off by default: ``forward`` then takes the branches of before."""
+
+    def __init__(self, A, in_features, out_features, dropout=0.0, layer=0, state=None, relu=True, norm=None, root_weight=False, bias=False,
+                 residual=False):
         super(PGCN, self).__init__()
         self.linear = nn.Linear(in_features, out_features, bias=False)
         self.A = A
@@ -1184,11 +1306,20 @@ class PGCN(nn.Module):
         if self.norm is not None:
             if not self.relu:
                 raise ValueError("norm=%r needs relu=True: the output layer of a classifier is not normalised" % (norm,))
+        if self.norm == "node":
+            self.ln_weight = nn.Parameter(torch.ones(out_features))
+            self.ln_bias = nn.Parameter(torch.zeros(out_features))
+            self.ln_eps = 1e-5
+        elif self.norm is not None:
             self.bn_weight = nn.Parameter(torch.ones(out_features))
             self.bn_bias = nn.Parameter(torch.zeros(out_features))
             self.register_buffer("running_mean", torch.zeros(out_features))
             self.register_buffer("running_var", torch.ones(out_features))
             self.bn_momentum, self.bn_eps = 0.1, 1e-5
+        self.residual = bool(residual)
+        if self.residual and not (self.relu and int(in_features) == int(out_features)):
+            raise ValueError("residual=True needs relu=True and in_features == out_features, got relu=%r, %d -> %d"
+                             % (self.relu, in_features, out_features))
         self.root_weight = bool(root_weight)
         self.has_bias = bool(bias) and self.norm is None
         if self.root_weight:
@@ -1201,7 +1332,16 @@ class PGCN(nn.Module):
             self._row_ids = self.A.part.owned.to(device=H.device, dtype=torch.int64).contiguous()
         return self._row_ids
 
-    def _forward_combined(self, H, AH):
+    def _node_norm(self, X, H, R):
+        """R + drop(relu(LN(X))) of the layer's product X (``norm="node"``); H: the layer's input (its device and rows)."""
+        drop = self.training and self.dropout > 0.0
+        if drop and self.state is None:
+            self.state = _dropout.DropoutState(0, H.device)
+        return _LayerNormReluDropout.apply(X, self.ln_weight, self.ln_bias, R, self.training, self.ln_eps,
+                                           self._global_row_ids(H) if drop else None, self.state if drop else None, self.layer,
+                                           self.dropout_thr, self.dropout_scale)
+
+    def _forward_combined(self, H, AH, R=None):
         """The layer with a root weight and / or a bias: H the layer's input (owned rows), AH its aggregation."""
         Z1 = _LinearNoBias.apply(AH, self.linear.weight)
         Z2 = _LinearNoBias.apply(H, self.root.weight) if self.root_weight else None
@@ -1210,6 +1350,8 @@ class PGCN(nn.Module):
             self.state = _dropout.DropoutState(0, H.device)
         if self.norm is not None:
             X = _CombineBiasReluDropout.apply(Z1, Z2, None, False, None, None, self.layer, 0, 1.0) if Z2 is not None else Z1
+            if self.norm == "node":
+                return self._node_norm(X, H, R)
             return _BatchNormReluDropout.apply(X, self.bn_weight, self.bn_bias, (self.running_mean, self.running_var), self.training,
                                                self.bn_momentum, self.bn_eps, int(self.A.part.n), self._global_row_ids(H) if drop else None,
                                                self.state if drop else None, self.layer, self.dropout_thr, self.dropout_scale)
@@ -1218,8 +1360,16 @@ class PGCN(nn.Module):
                                              self.dropout_thr if drop else 0, self.dropout_scale if drop else 1.0)
 
     def forward(self, H):
+        if self.residual:
+            # H + layer(H): with norm="node" the addition is the kernel's R; every other layer kind adds in the framework, after its node
+            return self._layer(H, H) if self.norm == "node" else H + self._layer(H)
+        return self._layer(H)
+
+    def _layer(self, H, R=None):
         if self.root_weight or self.has_bias:
-            return self._forward_combined(H, PSpMM.apply(self.A, H))
+            return self._forward_combined(H, PSpMM.apply(self.A, H), R)
+        if self.norm == "node":
+            return self._node_norm(_LinearNoBias.apply(PSpMM.apply(self.A, H), self.linear.weight), H, R)
         H = PSpMM.apply(self.A, H)
         if not self.relu:
             return _LinearNoBias.apply(H, self.linear.weight)
@@ -1552,7 +1702,8 @@ OPTIMIZERS = ("torch", "fused")       # --optimizer / run(optimizer=...): torch.
 
 
 def _train_on_data(A, n, nlayers, nfeatures, features, labels, split, hidden, epochs, lr, eval_every, dropout, dropout_seed,
-                   multilabel=False, weight_decay=0.0, decoupled_decay=False, optimizer="torch", norm=None, root_weight=None, bias=None):
+                   multilabel=False, weight_decay=0.0, decoupled_decay=False, optimizer="torch", norm=None, root_weight=None, bias=None,
+                   residual=None):
     """The loop of ``run`` on real inputs: widths fin -> hidden -> ... -> C, no ReLU on the last layer, constant features (the
     first layer's backward aggregation is skipped), Adam, the masked loss over the train rows.  Reports every ``eval_every``
     epochs: without dropout from the record of the training step's own pass (the logits BEFORE that step's update), with
@@ -1564,7 +1715,9 @@ def _train_on_data(A, n, nlayers, nfeatures, features, labels, split, hidden, ep
     its product over all vertices of the graph (class PGCN); its scale and shift are parameters like the weights -- initialised,
     reduced, decayed and stepped with them.  The reporting rule is unchanged: without dropout the record is the training step's
     own (the graph's statistics), with dropout ``evaluate`` runs in eval mode (the running statistics).  ``root_weight`` / ``bias``:
-    every layer gets a root weight / a bias (class PGCN; a normalised layer owns no bias) -- parameters like the rest."""
+    every layer gets a root weight / a bias (class PGCN; a normalised layer owns no bias) -- parameters like the rest.
+    ``norm="node"``: every layer but the last normalises each vertex's product over its own features (no collective, no buffers).
+    ``residual``: every layer but the last whose two widths are equal adds its input to its output (class PGCN)."""
     load = _nodedata.load_multilabel if multilabel else _nodedata.load
     data = load(features, labels, split, A.part.owned, n, device=device)
     hidden = int(nfeatures if hidden is None else hidden)
@@ -1582,7 +1735,7 @@ def _train_on_data(A, n, nlayers, nfeatures, features, labels, split, hidden, ep
     extra = dict(({"root_weight": True} if root_weight else {}), **({"bias": True} if bias else {}))       # (neither: the call of before)
     model = nn.Sequential(*[PGCN(A, widths[i], widths[i + 1], dropout=dropout if i < nlayers - 1 else 0.0, layer=i, state=state,
                                  relu=i < nlayers - 1, **({"norm": norm} if norm not in (None, "none") and i < nlayers - 1 else {}),
-                                 **extra)
+                                 **extra, **({"residual": True} if residual and i < nlayers - 1 and widths[i] == widths[i + 1] else {}))
                             for i in range(nlayers)]).to(device)
     initiliaze_parameters(model)
     fused = None
@@ -1655,7 +1808,7 @@ TASKS = ("single", "multilabel")       # --task / run(task=...): one class per v
 
 def run(rank, size, nlayers, nfeatures, path_A, path_partvec, backend, normalize=None, dropout=0.0, dropout_seed=0,
         features=None, labels=None, split=None, hidden=None, epochs=None, lr=None, eval_every=None, task=None,
-        weight_decay=None, decoupled_decay=None, optimizer=None, norm=None, root_weight=None, bias=None):
+        weight_decay=None, decoupled_decay=None, optimizer=None, norm=None, root_weight=None, bias=None, residual=None):
     """PGCN.py:162-238.  ``normalize="sym"``: train on D_r^-1/2 (A + I) D_c^-1/2 of the pattern of ``path_A``, built on the fly
     (partition.build_partition) instead of by the offline pass preprocess/GrB-GNN-IDG.py.  ``dropout`` > 0: the output of every
     layer but the last is dropped with that probability (class PGCN), masks from (``dropout_seed``, step, layer, global row,
@@ -1670,7 +1823,9 @@ def run(rank, size, nlayers, nfeatures, path_A, path_partvec, backend, normalize
     the default, or "fused" = optim.FlatAdam) need the three files too.  ``norm`` ("none", the default, or "batch": batch
     normalisation over all vertices of the graph between the product and the ReLU of every layer but the last; needs the three
     files).  ``root_weight`` / ``bias`` (True; need the three files): every layer is the GraphSAGE-style
-    act((A H) W_n^T + H W_r^T + b) of class PGCN instead of act((A H) W^T)."""
+    act((A H) W_n^T + H W_r^T + b) of class PGCN instead of act((A H) W^T).  ``norm="node"``: layer normalisation of every vertex
+    over its own features instead (row-local: no collective).  ``residual`` (True; needs the three files): every layer but the last
+    whose two widths are equal returns H + layer(H)."""
     global myrank, world_size, send_map, recv_map, device, X, recv_buffers, send_buffers, stats
     myrank = rank
     world_size = size
@@ -1694,6 +1849,8 @@ def run(rank, size, nlayers, nfeatures, path_A, path_partvec, backend, normalize
         raise ValueError("norm=%r needs features, labels and split" % (norm,))
     if (root_weight is not None or bias is not None) and not all(given):
         raise ValueError("root_weight and bias need features, labels and split")
+    if residual is not None and not all(given):
+        raise ValueError("residual needs features, labels and split")
     if torch.cuda.is_available():
         device = torch.device(f'cuda:{myrank % torch.cuda.device_count()}')
         torch.cuda.set_device(device)
@@ -1748,7 +1905,8 @@ def run(rank, size, nlayers, nfeatures, path_A, path_partvec, backend, normalize
         return _train_on_data(A, n, nlayers, nfeatures, features, labels, split, hidden, epochs, lr, eval_every, dropout,
                               dropout_seed, multilabel, float(weight_decay or 0.0), bool(decoupled_decay), optimizer or "torch",
                               **({"norm": norm} if norm not in (None, "none") else {}),
-                              **({"root_weight": True} if root_weight else {}), **({"bias": True} if bias else {}))
+                              **({"root_weight": True} if root_weight else {}), **({"bias": True} if bias else {}),
+                              **({"residual": True} if residual else {}))
 
     owned = A.part.owned.to(device)
     # PGCN.py:186-188 synthetic features H[i,:] = i, owned rows only
@@ -1823,7 +1981,7 @@ def run(rank, size, nlayers, nfeatures, path_A, path_partvec, backend, normalize
 
 def init_process(rank, size, fn, nlayers, nfeatures, path_A, path_partvec, backend, normalize=None, dropout=0.0, dropout_seed=0,
                  features=None, labels=None, split=None, hidden=None, epochs=None, lr=None, eval_every=None, task=None,
-                 weight_decay=None, decoupled_decay=None, optimizer=None, norm=None, root_weight=None, bias=None):
+                 weight_decay=None, decoupled_decay=None, optimizer=None, norm=None, root_weight=None, bias=None, residual=None):
     """PGCN.py:241-253."""
     global _exchanger
     dist.init_process_group(backend, rank=rank, world_size=size)
@@ -1841,7 +1999,8 @@ def init_process(rank, size, fn, nlayers, nfeatures, path_A, path_partvec, backe
         kw["dropout"], kw["dropout_seed"] = dropout, dropout_seed
     for name, v in (("features", features), ("labels", labels), ("split", split), ("hidden", hidden), ("epochs", epochs), ("lr", lr),
                     ("eval_every", eval_every), ("task", task), ("weight_decay", weight_decay), ("decoupled_decay", decoupled_decay),
-                    ("optimizer", optimizer), ("norm", norm), ("root_weight", root_weight), ("bias", bias)):
+                    ("optimizer", optimizer), ("norm", norm), ("root_weight", root_weight), ("bias", bias),
+                    ("residual", residual)):
         if v is not None:
             kw[name] = v
     fn(rank, size, nlayers, nfeatures, path_A, path_partvec, backend, **kw)     # (no option given: today's call)
@@ -1866,7 +2025,7 @@ def main(argv):
     try:
         opts, args = getopt.getopt(argv, "a:p:b:s:l:f:", ["normalize=", "dropout=", "dropout-seed=", "features=", "labels=", "split=",
                                                           "hidden=", "epochs=", "lr=", "eval-every=", "task=", "weight-decay=", "adamw",
-                                                          "optimizer=", "norm=", "root-weight", "bias"])
+                                                          "optimizer=", "norm=", "root-weight", "bias", "residual"])
     except getopt.GetoptError:
         print("a:p:b:", flush=True)
         sys.exit(2)
@@ -1919,7 +2078,8 @@ def main(argv):
                 print("--optimizer takes %s, got %r" % ("|".join(OPTIMIZERS), arg), flush=True)
                 sys.exit(2)
             data["optimizer"] = arg
-        elif opt == '--norm':          # none (the default) | batch (batch normalisation over all vertices, every layer but the last)
+        elif opt == '--norm':          # none (the default) | batch (batch normalisation over all vertices) | node (layer normalisation of
+            #                                every vertex over its features) -- every layer but the last
             if arg not in NORMS:
                 print("--norm takes %s, got %r" % ("|".join(NORMS), arg), flush=True)
                 sys.exit(2)
@@ -1929,6 +2089,8 @@ def main(argv):
             data["root_weight"] = True
         elif opt == '--bias':          # every layer adds a bias (a normalised layer keeps bn_bias alone)
             data["bias"] = True
+        elif opt == '--residual':      # every layer but the last whose widths are equal returns H + layer(H) (class PGCN)
+            data["residual"] = True
         elif opt == '--lr':
             try:
                 data["lr"] = float(arg)
@@ -1952,7 +2114,7 @@ def main(argv):
     os.environ.setdefault("WORLD_SIZE", str(size))
     files = [k for k in ("features", "labels", "split") if k in data]
     if data and len(files) != 3:
-        print("--features, --labels and --split go together (and --hidden, --epochs, --lr, --eval-every, --task, --weight-decay, --adamw, --optimizer, --norm, --root-weight, --bias need them); got %s"
+        print("--features, --labels and --split go together (and --hidden, --epochs, --lr, --eval-every, --task, --weight-decay, --adamw, --optimizer, --norm, --residual, --root-weight, --bias need them); got %s"
               % ", ".join("--" + {"decoupled_decay": "adamw"}.get(k, k.replace("_", "-")) for k in sorted(data)), flush=True)
         sys.exit(2)
     for k in files:
@@ -1968,13 +2130,16 @@ def main(argv):
         args += tuple(data.get(k) for k in ("features", "labels", "split", "hidden", "epochs", "lr", "eval_every", "task"))
         extra = tuple(data.get(k) for k in ("weight_decay", "decoupled_decay", "optimizer"))
         layer_opts = tuple(data.get(k) for k in ("root_weight", "bias"))
-        has_layer_opts = any(v is not None for v in layer_opts)
+        has_residual = data.get("residual") is not None
+        has_layer_opts = any(v is not None for v in layer_opts) or has_residual
         if any(v is not None for v in extra) or data.get("norm") is not None or has_layer_opts:      # (none given: the argument tuple of before)
             args += extra
         if data.get("norm") is not None or has_layer_opts:
             args += (data.get("norm"),)
         if has_layer_opts:
             args += layer_opts
+        if has_residual:                   # (the tuple grows only when --residual is given)
+            args += (True,)
     p = mp.Process(target=init_process, args=args)
     p.start()
     p.join()

@@ -209,6 +209,8 @@ BN_MAX_F = 1024          # widest block the batch-norm kernels take (csrc/pgcn_n
 BN_STAT_ROWS = 512       # rows of a band of its column-sum kernels (kStatRows; pgcn_bn_colstats_ws_bytes counts one record per band)
 COMBINE_MAX_F = 1024     # widest block the combine kernels take (csrc/pgcn_combine.hip: the same layout)
 COMBINE_SUM_ROWS = 512   # rows of a block of its backward (kSumRows; pgcn_combine_ws_bytes counts one record per block)
+LN_MAX_F = 1024          # widest block the layer-norm kernels take (csrc/pgcn_layernorm.hip: the same layout)
+LN_STAT_ROWS = 512       # rows of a block of its backward (kBandRows; pgcn_ln_ws_bytes counts one record per block)
 
 
 class HipKernels:
@@ -1261,6 +1263,61 @@ class HipKernels:
                                                       n, f, 1 if relu else 0, float(scale), _ptr(Gm), self._ld(Gm) if want_gm else 0,
                                                       _ptr(dbias), _ptr(ws), ws_bytes, self._stream()), "pgcn_combine_backward_f32")
         return Gm, dbias
+
+    # -- layer normalisation of a vertex over its features + residual link, fused with ReLU and dropout (csrc/pgcn_layernorm.hip)
+    def ln_relu_forward(self, X: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: float, R: Optional[torch.Tensor] = None,
+                        row_ids: Optional[torch.Tensor] = None, seed: int = 0, step: Optional[torch.Tensor] = None, layer: int = 0,
+                        thr: int = 0, save: bool = True, out: Optional[torch.Tensor] = None):
+        """(Y, mean, rstd, mask) of Y = R + (keep ? max(0, fma(gamma, (X - mean_i) rstd_i, beta)) * scale : 0) in one launch
+        (pgcn_ln_relu_forward_f32): mean / rstd fp32 [n], the row statistics the kernel used; mask int32 [n, ceil(f / 32)], bit =
+        kept and pre-activation > 0.  ``R`` None: nothing is added; ``out`` may be R itself.  ``step`` None or ``thr`` 0: no dropout;
+        ``step``: one int64 on the device, read by the kernel; ``row_ids``: int64 [n] global ids (None: the row index).  ``save``
+        False (inference): the three are None and not written.  None when the shape is not covered."""
+        mats = (X,) + ((R,) if R is not None else ()) + ((out,) if out is not None else ())
+        if not self._bn_mat_ok(*mats) or X.shape[1] > LN_MAX_F:
+            return None
+        n, f = X.shape
+        if not self._bn_vec_ok(f, torch.float32, gamma, beta) or not self._bn_vec_ok(n, torch.int64, row_ids) or \
+                not self._bn_vec_ok(1, torch.int64, step):
+            return None
+        Y = out if out is not None else torch.empty((n, f), dtype=torch.float32, device=self.device)
+        mean = rstd = mask = None
+        if save:
+            mean = torch.empty(n, dtype=torch.float32, device=self.device)
+            rstd = torch.empty(n, dtype=torch.float32, device=self.device)
+            mask = torch.empty((n, (f + 31) // 32), dtype=torch.int32, device=self.device)
+        _lib.check(self.lib.pgcn_ln_relu_forward_f32(X.data_ptr(), self._ld(X), n, f, gamma.data_ptr(), beta.data_ptr(), float(eps), _ptr(R),
+                                                     self._ld(R) if R is not None else 0, _ptr(row_ids), int(seed) & ((1 << 64) - 1),
+                                                     _ptr(step), int(layer), int(thr), Y.data_ptr(), self._ld(Y), _ptr(mean), _ptr(rstd),
+                                                     _ptr(mask), self._stream()), "pgcn_ln_relu_forward_f32")
+        return Y, mean, rstd, mask
+
+    def ln_relu_backward(self, G: torch.Tensor, X: torch.Tensor, mean: torch.Tensor, rstd: torch.Tensor, gamma: torch.Tensor,
+                         mask: torch.Tensor, scale: float = 1.0, want_sums: bool = True, out: Optional[torch.Tensor] = None):
+        """(dX, dgamma, dbeta) of the same layer from G, X and the forward's bits (pgcn_ln_relu_backward_f32; one pass + the second
+        level of the column sums): dgamma / dbeta fp32 [f], THIS rank's sums added in double; ``want_sums`` False: both None, one
+        launch.  None when the shape is not covered."""
+        if not self._bn_mat_ok(X, G) or (out is not None and not self._bn_mat_ok(X, out)) or X.shape[1] > LN_MAX_F:
+            return None
+        n, f = X.shape
+        if not self._bn_vec_ok(f, torch.float32, gamma) or not self._bn_vec_ok(n, torch.float32, mean, rstd) or mean is None or rstd is None:
+            return None
+        if not (mask is not None and mask.is_cuda and mask.device == self.device and mask.dtype is torch.int32 and mask.is_contiguous()
+                and mask.shape == (n, (f + 31) // 32)):
+            return None
+        dX = out if out is not None else torch.empty((n, f), dtype=torch.float32, device=self.device)
+        dgamma = dbeta = ws = None
+        ws_bytes = 0
+        if want_sums:
+            dgamma = torch.empty(f, dtype=torch.float32, device=self.device)
+            dbeta = torch.empty(f, dtype=torch.float32, device=self.device)
+            ws_bytes = int(self.lib.pgcn_ln_ws_bytes(n, f))
+            ws = torch.empty(ws_bytes // 8, dtype=torch.float64, device=self.device)
+        _lib.check(self.lib.pgcn_ln_relu_backward_f32(G.data_ptr(), self._ld(G), X.data_ptr(), self._ld(X), n, f, mean.data_ptr(),
+                                                      rstd.data_ptr(), gamma.data_ptr(), mask.data_ptr(), float(scale), dX.data_ptr(),
+                                                      self._ld(dX), _ptr(dgamma), _ptr(dbeta), _ptr(ws), ws_bytes, self._stream()),
+                   "pgcn_ln_relu_backward_f32")
+        return dX, dgamma, dbeta
 
     def gather_rows(self, H: torch.Tensor, idx: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
         n = idx.numel()
