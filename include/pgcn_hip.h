@@ -623,6 +623,42 @@ int pgcn_combine_backward_f32(const float *G, int64_t ldg, const float *Y, int64
                               float scale, float *Gm, int64_t ldgm, float *dbias, void *ws, int64_t ws_bytes,
                               pgcn_stream_t stream);
 
+/* ---- the tail of a GAT layer: head mean, bias, ELU and dropout (PGAT.py: _GatTail) ------------------------------------
+ * A GAT layer ends with drop(act(reduce_heads(X) + b)); X is the nrows x heads * d output of the aggregation on OWNED rows, the
+ * heads side by side.  The output width is fout = mean ? d : heads * d.
+ * pgcn_gat_tail_forward_f32:  mean == 0: r = X[i,j];  mean != 0: r = (((X[i,j] + X[i,d+j]) + X[i,2d+j]) + ...) * (1.0f / heads),
+ *   the heads added in index order, every step rounded to fp32 (no contraction); heads == 1 skips the product.  t = r + bias[j]
+ *   (bias == NULL: the term is ABSENT, not added as 0.0f: a -0.0 survives).  act == 0: a = t;  act == 1 (ELU, alpha = 1):
+ *   a = t > 0 ? t : expm1f(t).  Y[i,j] = keep ? a * scale : 0.  step == NULL or thr == 0: keep is true and scale 1.  Otherwise
+ *   keep / scale are those of gemm/pgcn_dropout.h with the key (seed, *step, layer, row_ids[i] (NULL: i), j), j the OUTPUT column:
+ *   the masks every other layer kind draws for that layer; *step is read from device memory, the column's share of the hash is
+ *   formed once per thread.  Y == X with ldy == ldx is allowed when mean == 0 (in place).  One launch; nrows == 0: none.
+ * pgcn_gat_tail_backward_f32:  from G and the saved Y; the keep bits are formed AGAIN from the same key (Y == 0 does not tell a
+ *   dropped element from a == 0, and X is not kept).  deriv = (act == 0 || Y[i,j] > 0) ? 1 : Y[i,j] * (1.0f / scale) + 1.0f (for
+ *   t <= 0, ELU' = elu(t) + 1);  Gm = keep ? (G[i,j] * scale) * deriv : 0;  dX[i, k d + j] = mean ? Gm * (1.0f / heads) : Gm for
+ *   every head k (heads == 1 skips the product).  act == 0: Y is not read and may be NULL.  In the same pass dbias[j] =
+ *   float(sum_i Gm[i,j]), added in double: a block owns 512 consecutive rows, folds its row groups through LDS by a fixed tree and
+ *   writes one partial record [fout] of doubles to `ws` (pgcn_gat_tail_ws_bytes(nrows, fout) bytes, 8-byte aligned; -1 for sizes
+ *   the kernels refuse); a second launch, 32 columns per block, adds the records in a fixed order -- no floating-point atomics, the
+ *   same input gives the same bits.  dbias is the RANK-LOCAL sum: the training loop adds the ranks' parameter gradients itself.
+ *   dX == NULL: sums only.  dbias == NULL: no sums, ws is not read, one launch.  dX == G with lddx == ldg is allowed when
+ *   mean == 0.  nrows == 0: dbias is zeroed, nothing else is written.
+ * Both: row-major with leading dimensions in elements, 64-bit row offsets; every fout from 1 to 1024 and heads * d <= 8192
+ * (PGCN_EUNSUPPORTED above); a thread owns four consecutive output columns -- one float4 when fout % 4 == 0 and every base and
+ * leading dimension keeps rows 16-byte aligned, four guarded scalars otherwise, the same bits either way.  PGCN_EINVAL, nothing
+ * launched: a null required pointer, nrows < 0, heads < 1, d < 1, act other than 0 / 1, a leading dimension below its width, a
+ * misaligned ws / step / row_ids, in place with mean != 0 or differing leading dimensions; PGCN_ENOMEM: ws_bytes too small.  A NaN
+ * or inf stays in its own output element (forward), its own head copies and dbias column (backward).  Raw pointers + a stream,
+ * no allocation, no synchronisation (graph-capturable).                                                                   */
+int64_t pgcn_gat_tail_ws_bytes(int64_t nrows, int32_t fout);
+int pgcn_gat_tail_forward_f32(const float *X, int64_t ldx, int64_t nrows, int32_t heads, int32_t d, int32_t mean,
+                              const float *bias, int32_t act, const int64_t *row_ids, uint64_t seed, const int64_t *step,
+                              uint32_t layer, uint32_t thr, float *Y, int64_t ldy, pgcn_stream_t stream);
+int pgcn_gat_tail_backward_f32(const float *G, int64_t ldg, const float *Y, int64_t ldy, int64_t nrows, int32_t heads, int32_t d,
+                               int32_t mean, int32_t act, const int64_t *row_ids, uint64_t seed, const int64_t *step,
+                               uint32_t layer, uint32_t thr, float *dX, int64_t lddx, float *dbias, void *ws, int64_t ws_bytes,
+                               pgcn_stream_t stream);
+
 /* ---- layer normalisation of a vertex over its features + residual link, fused with ReLU and dropout (PGCN.py: _LayerNormReluDropout)
  * The layer y = R + drop(relu(LN(x))) of an nrows x f block of OWNED rows.  Row-local: no collective, and a row's results depend on
  * that row alone -- not on its position, the block that met it, nrows or the rank.

@@ -22,21 +22,27 @@ What changed underneath:
 """
 from __future__ import annotations
 
+import contextlib
 import getopt
+import math
 import os
 import sys
 import time
 
+import numpy as np
 import torch
 import torch.distributed as dist
 import torch.multiprocessing as mp
 import torch.nn as nn
 
 from . import PGCN as _pgcn
+from . import dropout as _dropout
 from . import engine as _engine
 from . import gat as _gat
 from . import ingest as _ingest
 from . import kernels as _kernels
+from . import nodedata as _nodedata
+from . import optim as _optim
 from . import partition as _partition
 
 # module-level state, same names as PGAT.py:23-35
@@ -154,11 +160,122 @@ class Comm(torch.autograd.Function):
         return dH
 
 
+# ---- the tail of a layer: head mean, bias, ELU and dropout (csrc/pgcn_gat_tail.hip) -------------------------------------------------
+ACTIVATIONS = (None, "elu")
+
+
+def _f32_inv(x):
+    """1.0f / x as the kernels form it: one fp32 division."""
+    return float(np.float32(1.0) / np.float32(x))
+
+
+def gat_tail_composed(X, heads, d, mean=False, bias=None, act=0, row_ids=None, state=None, layer=0, thr=0, scale=1.0):
+    """Y of the layer tail from framework operations, the definitions of csrc/pgcn_gat_tail.hip: ``mean`` -- the heads added in index
+    order, then one product with 1.0f / heads (none for one head); t = r + bias (None: absent); ``act`` 1: ELU, t > 0 ? t : expm1(t);
+    Y = keep ? a * scale : 0 -- keep the bits of dropout.py under (seed, step, layer, global row id, OUTPUT column); ``state`` None
+    or ``thr`` 0: no dropout.  For CPU tensors, the checker-backed provider of the tests and widths the kernels refuse."""
+    X = X.detach()
+    r = X
+    if mean:
+        r = X[:, :d]
+        for k in range(1, heads):
+            r = r + X[:, k * d:(k + 1) * d]
+        if heads > 1:
+            r = r * _f32_inv(heads)
+    t = r + bias.detach() if bias is not None else r
+    a = torch.where(t > 0, t, torch.expm1(t)) if act else t
+    if state is not None and thr > 0:
+        a = torch.where(_pgcn._bn_keep(a, row_ids, state, layer, thr).to(a.device), a * scale, torch.zeros((), dtype=a.dtype, device=a.device))
+    return a.clone() if a is X else a
+
+
+def gat_tail_backward_composed(G, Y, heads, d, mean=False, act=0, row_ids=None, state=None, layer=0, thr=0, scale=1.0, want_dbias=True):
+    """(dX, dbias) of the same tail from G and the saved Y (read with ELU only): deriv = Y > 0 ? 1 : Y * (1.0f / scale) + 1.0f,
+    Gm = keep ? (G * scale) * deriv : 0 with the keep bits formed again (``state`` at the step of the forward), dX = Gm (times
+    1.0f / heads with ``mean``) for every head; dbias = THIS rank's column sums of Gm, added in float64 and rounded once (None unless
+    ``want_dbias``)."""
+    drop = state is not None and thr > 0
+    gm = G * scale if drop else G
+    if act:
+        e = Y * _f32_inv(scale) if drop else Y
+        gm = torch.where(Y > 0, gm, gm * (e + 1.0))
+    if drop:
+        gm = torch.where(_pgcn._bn_keep(G, row_ids, state, layer, thr).to(G.device), gm, torch.zeros((), dtype=G.dtype, device=G.device))
+    dX = gm
+    if mean:
+        dX = (gm * _f32_inv(heads) if heads > 1 else gm).repeat(1, heads)
+    return dX, (gm.double().sum(0).to(G.dtype) if want_dbias else None)
+
+
+def _tail_kernels(X, width, bias=None, row_ids=None):
+    """The provider whose tail kernels take these operands, or None (CPU tensors, the checker-backed provider of the tests, widths
+    above the kernels', another dtype or layout).  Decided BEFORE the first launch."""
+    k = _kernel_provider if _kernel_provider is not None else getattr(_engine_current, "k", None)
+    if k is None or not hasattr(k, "gat_tail_forward") or not hasattr(k, "gat_tail_backward"):
+        return None
+    if not (X.is_cuda and X.dim() == 2 and X.dtype is torch.float32 and 0 < X.shape[1] <= _kernels.GAT_TAIL_MAX_IN
+            and 0 < width <= _kernels.GAT_TAIL_MAX_F and (X.stride(1) == 1 or X.shape[1] == 1 or X.shape[0] == 0)
+            and (X.shape[0] <= 1 or X.stride(0) >= X.shape[1])):
+        return None
+    if bias is not None and not (bias.is_cuda and bias.device == X.device and bias.dtype is torch.float32 and bias.is_contiguous()
+                                 and bias.numel() == width):
+        return None
+    return k if _pgcn._row_ids_ok(row_ids, X.shape[0]) and (row_ids is None or row_ids.device == X.device) else None
+
+
+class _GatTail(torch.autograd.Function):
+    """drop(act(reduce_heads(X) + bias)) as ONE autograd node.  On a HIP device one launch forward (pgcn_gat_tail_forward_f32) and
+    one pass backward (pgcn_gat_tail_backward_f32; the bias gradient summed in double in the same pass).  Saved: Y, and only with
+    ELU (ELU' = Y / scale + 1 where Y <= 0); the keep bits are formed again from the key, so the step must not advance between
+    forward and backward.  dbias is THIS rank's sum.  Anything the kernels do not cover takes ``gat_tail_composed``."""
+
+    @staticmethod
+    def forward(ctx, X, bias, heads, d, mean, act, row_ids, state, layer, thr, scale):
+        drop = bool(state is not None and thr > 0)
+        fout = d if mean else heads * d
+        k = _tail_kernels(X, fout, bias, row_ids if drop else None)
+        if k is not None:
+            Y = _pgcn._bn_must(k.gat_tail_forward(X, heads, d, mean, bias.detach() if bias is not None else None, act,
+                                                  row_ids if drop else None, state.seed if drop else 0, state.step if drop else None,
+                                                  layer, thr if drop else 0), "gat_tail_forward", "_tail_kernels")
+        else:
+            Y = gat_tail_composed(X, heads, d, mean, bias, act, row_ids, state if drop else None, layer, thr if drop else 0, scale)
+        ctx.cfg = (int(heads), int(d), bool(mean), int(act), row_ids if drop else None, state if drop else None, int(layer),
+                   int(thr) if drop else 0, float(scale) if drop else 1.0, bias is not None)
+        if act:
+            ctx.save_for_backward(Y)
+        return Y
+
+    @staticmethod
+    def backward(ctx, G):
+        heads, d, mean, act, row_ids, state, layer, thr, scale, has_bias = ctx.cfg
+        Y = ctx.saved_tensors[0] if act else None
+        want_dx, want_dbias = ctx.needs_input_grad[0], has_bias and ctx.needs_input_grad[1]
+        if G.stride(1) != 1 or (G.shape[0] > 1 and G.stride(0) < G.shape[1]):
+            G = G.contiguous()
+        k = _tail_kernels(G, G.shape[1], None, row_ids)
+        if k is not None:
+            dX, dbias = _pgcn._bn_must(k.gat_tail_backward(G, Y, heads, d, mean, act, row_ids, state.seed if state is not None else 0,
+                                                           state.step if state is not None else None, layer, thr, want_dx=want_dx,
+                                                           want_dbias=want_dbias), "gat_tail_backward", "_tail_kernels")
+        else:
+            dX, dbias = gat_tail_backward_composed(G, Y, heads, d, mean, act, row_ids, state, layer, thr, scale, want_dbias)
+        return (dX if want_dx else None, dbias) + (None,) * 9
+
+
 class PGAT(nn.Module):
     """PGAT.py:120-151.  ``out_features`` is the total width; with K heads each head has
-    out_features / K columns and its own attention vector (column k of ``attention``)."""
+    out_features / K columns and its own attention vector (column k of ``attention``).
 
-    def __init__(self, A, in_features, out_features, heads=None):
+    The tail of the layer, all off by default (then the layer owns the parameters and takes the path it always did):
+    ``bias`` adds a vector per output column (zeros at first); ``activation`` takes None | "elu"; ``concat=False`` returns the MEAN
+    of the heads, out_features / K columns (the output layer of the GAT paper) -- ``out_features`` stays the projected width;
+    ``dropout`` drops the layer's output in training mode, masks from ``state`` (a dropout.DropoutState the model's layers share),
+    ``layer`` and the GLOBAL row ids, so P ranks under any part vector draw the masks of one rank.  One kernel each way
+    (``_GatTail``).  Not here: dropout on the attention coefficients, norms, residual links."""
+
+    def __init__(self, A, in_features, out_features, heads=None, bias=False, activation=None, concat=True, dropout=0.0, layer=0,
+                 state=None):
         super(PGAT, self).__init__()
         K = globals()["heads"] if heads is None else heads
         if out_features % K:
@@ -174,6 +291,19 @@ class PGAT(nn.Module):
         self.linear = nn.Linear(in_features, out_features, bias=False)
         self.attention = nn.Parameter(torch.empty(size=(2 * out_features // K, K)))   # (2F, 1) for one head, :127
         self._state = None
+        if activation not in ACTIVATIONS:
+            raise ValueError("activation takes None | 'elu', got %r" % (activation,))
+        self.activation, self.concat, self.has_bias = activation, bool(concat), bool(bias)
+        self.dropout = float(dropout)
+        self.dropout_thr, self.dropout_scale = _dropout.threshold(dropout)
+        self.layer, self.state, self._row_ids = int(layer), state, None
+        if self.dropout > 0.0 and state is None:
+            raise ValueError("dropout=%r needs state=dropout.DropoutState(...) shared by the model's layers" % (dropout,))
+        self._has_tail = self.has_bias or activation is not None or not self.concat or self.dropout > 0.0
+        if self._has_tail and A is not None and getattr(A, "mode", "standard") == "reference":
+            raise ValueError("the reference layer has no bias, activation, head mean or dropout")
+        if self.has_bias:
+            self.bias = nn.Parameter(torch.zeros(out_features if self.concat else out_features // K))
         self.reset_parameters()
 
     def reset_parameters(self):
@@ -197,7 +327,16 @@ class PGAT(nn.Module):
         st = self._state
         if st is None or st.busy or (st.heads, st.d) != (K, d):
             st = self._state = self.A.new_layer_state(K, d)
-        return _gat.GatAggregatePacked.apply(self.A, st, ZS)            # :144-149 on the stored entries
+        out = _gat.GatAggregatePacked.apply(self.A, st, ZS)             # :144-149 on the stored entries
+        if not self._has_tail:
+            return out
+        # (its own output: GatEngine.backward reads the state's `out` buffer, so the tail never runs in place here)
+        drop = self.training and self.dropout > 0.0
+        if drop and (self._row_ids is None or self._row_ids.device != out.device):      # global ids in local row order, once
+            self._row_ids = self.A.part.owned.to(device=out.device, dtype=torch.int64).contiguous()
+        return _GatTail.apply(out, self.bias if self.has_bias else None, K, d, not self.concat, 1 if self.activation == "elu" else 0,
+                              self._row_ids if drop else None, self.state if drop else None, self.layer,
+                              self.dropout_thr if drop else 0, self.dropout_scale if drop else 1.0)
 
 
 _all_reduce = _pgcn._all_reduce
@@ -255,9 +394,183 @@ def local_loss(logits, labels, n_global):
     return (torch.logsumexp(logits, 1) - picked).sum() / n_global
 
 
-def run(rank, size, nlayers, nfeatures, path_A, path_partvec, backend, epochs=50):
-    """PGAT.py:165-233."""
+@contextlib.contextmanager
+def pgcn_state():
+    """PGCN's loss, evaluation and statistics functions read PGCN's module state (device, rank, world size, provider): inside this
+    context they read PGAT's.  What was there before comes back on exit."""
+    names = ("device", "myrank", "world_size", "_kernel_provider")
+    saved = [getattr(_pgcn, a) for a in names]
+    k = _kernel_provider if _kernel_provider is not None else getattr(_engine_current, "k", None)
+    _pgcn.device, _pgcn.myrank, _pgcn.world_size, _pgcn._kernel_provider = device, myrank, world_size, k
+    try:
+        yield
+    finally:
+        for a, v in zip(names, saved):
+            setattr(_pgcn, a, v)
+
+
+def masked_loss(logits, labels, split, n_train_global):
+    """PGCN.masked_loss on this module's provider (call ``backward`` inside ``pgcn_state()`` as well: it picks its kernel then)."""
+    with pgcn_state():
+        return _pgcn.masked_loss(logits, labels, split, n_train_global)
+
+
+def masked_bce_loss(logits, labels_words, split, n_train_global):
+    with pgcn_state():
+        return _pgcn.masked_bce_loss(logits, labels_words, split, n_train_global)
+
+
+def evaluate(model, H, labels, split):
+    """PGCN.evaluate for a model of PGAT layers.  Collective."""
+    with pgcn_state():
+        return _pgcn.evaluate(model, H, labels, split)
+
+
+def evaluate_multilabel(model, H, labels_words, split):
+    with pgcn_state():
+        return _pgcn.evaluate_multilabel(model, H, labels_words, split)
+
+
+def _global_stats(st):
+    with pgcn_state():
+        return _pgcn._global_stats(st)
+
+
+def _global_stats_multilabel(st, C):
+    with pgcn_state():
+        return _pgcn._global_stats_multilabel(st, C)
+
+
+TASKS = _pgcn.TASKS
+OPTIMIZERS = _pgcn.OPTIMIZERS
+
+
+def build_classifier(A, fin, classes, nlayers, hidden, K, out_heads=1, dropout=0.0, bias=False, state=None):
+    """The model of the GAT paper on the engine ``A``: layers 0 .. L-2 are K concatenated heads of hidden / K columns, ELU, dropout
+    on their output; the last layer averages ``out_heads`` heads of ``classes`` columns.  ``widths``: the layers' input widths and
+    the class count."""
+    if hidden % K:
+        raise ValueError("hidden (%d) must be divisible by the number of heads (%d)" % (hidden, K))
+    widths = [fin] + [hidden] * (nlayers - 1) + [classes]
+    extra = {"bias": True} if bias else {}
+    layers = [PGAT(A, widths[i], hidden, heads=K, activation="elu", dropout=dropout, layer=i, state=state, **extra)
+              for i in range(nlayers - 1)]
+    layers.append(PGAT(A, widths[nlayers - 1], out_heads * classes, heads=out_heads, concat=False, **extra))
+    return nn.Sequential(*layers), widths
+
+
+def _train_on_data(A, n, nlayers, features, labels, split, task=None, hidden=None, out_heads=None, epochs=None, lr=None,
+                   eval_every=None, dropout=0.0, dropout_seed=0, bias=None, weight_decay=None, decoupled_decay=None, optimizer=None):
+    """The loop of ``run`` on real inputs, the scheme of PGCN._train_on_data: constant features, Adam, the masked loss over the train
+    rows (``task="multilabel"``: the masked binary cross entropy and micro-F1).  Reports every ``eval_every`` epochs: without
+    dropout from the record of the training step's own pass (the logits BEFORE that step's update), with dropout from ``evaluate``
+    after the update.  ``optimizer="fused"``: optim.FlatAdam, the gradients reduced in place in its arena.  The initial parameters
+    are drawn under ``dropout_seed`` on every rank alike (the caller's generator is left as it was), so a run is a function of its
+    arguments and not of the number of ranks."""
+    multilabel = task == "multilabel"
+    load = _nodedata.load_multilabel if multilabel else _nodedata.load
+    data = load(features, labels, split, A.part.owned, n, device=device)
+    K = heads
+    hidden = int(8 * K if hidden is None else hidden)
+    out_heads = int(1 if out_heads is None else out_heads)
+    epochs = int(4 if epochs is None else epochs)
+    lr = float(1e-3 if lr is None else lr)
+    eval_every = max(1, int(1 if eval_every is None else eval_every))
+    weight_decay = float(weight_decay or 0.0)
+    n_train = data.counts[1]
+    if n_train < 1:
+        raise ValueError("split %r: no train rows" % (split,))
+    _dropout.threshold(dropout)
+    state = _dropout.DropoutState(dropout_seed, device) if dropout > 0.0 else None
+    with torch.random.fork_rng(devices=[]):        # every rank draws the SAME initial parameters, from the seed of the command line:
+        torch.manual_seed(int(dropout_seed))       # -s 1 and -s P then train one model (the ranks' mean of equal draws is that draw)
+        model, widths = build_classifier(A, data.fin, data.classes, nlayers, hidden, K, out_heads, dropout, bool(bias), state)
+    for i, m in enumerate(model):
+        _pgcn.tune_dense_gemms(A.part.n_local, widths[i], device, m.out_features + 2 * m.heads)
+    model = model.to(device)
+    initiliaze_parameters(model)
+    fused = None
+    if optimizer == "fused":
+        fused = _optim.FlatAdam(model.parameters(), lr=lr, weight_decay=weight_decay, decoupled=bool(decoupled_decay),
+                                kernels=_kernel_provider if _kernel_provider is not None else A.k)
+    elif decoupled_decay:
+        opt = torch.optim.AdamW(model.parameters(), lr=lr, weight_decay=weight_decay)
+    elif weight_decay:
+        opt = torch.optim.Adam(model.parameters(), lr=lr, weight_decay=weight_decay)
+    else:
+        opt = torch.optim.Adam(model.parameters(), lr=lr)
+    H, y, s = data.features, data.labels, data.split           # (H needs no gradient)
+
+    history, best = [], None
+    if device.type == "cuda":
+        torch.cuda.synchronize(device)
+    start = time.time()
+    with pgcn_state():
+        for epoch in range(epochs):
+            model.train()
+            loss, st = (_pgcn.masked_bce_loss if multilabel else _pgcn.masked_loss)(model(H), y, s, n_train)
+            if fused is not None:
+                loss.backward()
+                if world_size > 1:
+                    _reduce_sum(fused.flat_g)                      # (the ranks' SUM: the loss is split over the owned rows)
+                fused.grad_scale = 1.0
+                fused.step()
+            else:
+                opt.zero_grad()
+                loss.backward()
+                sum_gradients(model)
+                opt.step()
+            if state is not None:
+                state.advance()
+            if not (epoch % eval_every == 0 or epoch == epochs - 1):
+                continue
+            if multilabel:
+                ev = _pgcn.evaluate_multilabel(model, H, y, s) if state is not None else _pgcn._global_stats_multilabel(st, data.classes)
+                l, f1 = ev["loss"], ev["micro_f1"]
+                history.append({"epoch": epoch, "loss": l["train"], "train": f1["train"], "val": f1["val"], "test": f1["test"],
+                                "losses": l, "micro_f1": f1, "tp": ev["tp"], "fp": ev["fp"], "fn": ev["fn"], "rows": ev["rows"]})
+                fmt = "Epoch {:05d} | Loss {:.4f} | Train F1 {:.4f} | Val F1 {:.4f} | Test F1 {:.4f}"
+            else:
+                ev = _pgcn.evaluate(model, H, y, s) if state is not None else _pgcn._global_stats(st)
+                l, acc = ev["loss"], ev["acc"]
+                history.append({"epoch": epoch, "loss": l["train"], "train": acc["train"], "val": acc["val"], "test": acc["test"],
+                                "losses": l, "correct": ev["correct"], "rows": ev["rows"]})
+                fmt = "Epoch {:05d} | Loss {:.4f} | Train {:.4f} | Val {:.4f} | Test {:.4f}"
+            h = history[-1]
+            if best is None or h["val"] > best["val"]:             # (the first epoch of the best validation score)
+                best = h
+            if myrank == 0:
+                print(fmt.format(epoch, h["loss"], h["train"], h["val"], h["test"]), flush=True)
+    if device.type == "cuda":
+        torch.cuda.synchronize(device)
+    elapsed = torch.tensor([time.time() - start], device=device)
+    if world_size > 1:
+        _all_reduce(elapsed, dist.ReduceOp.MAX)
+    if best is None:
+        best = {"epoch": -1, "val": float("nan"), "test": float("nan")}
+    if myrank == 0:
+        print("Elapsed time {:.4f}  ms/epoch: {:.3f}".format(elapsed.item(), 1e3 * elapsed.item() / max(epochs, 1)), flush=True)
+        print(("Best Val F1 {:.4f} at epoch {:05d} | Test F1 {:.4f}" if multilabel else "Best Val {:.4f} at epoch {:05d} | Test {:.4f}")
+              .format(best["val"], best["epoch"], best["test"]), flush=True)
+    model.history, model.best, model.widths = history, best, widths
+    return model
+
+
+def run(rank, size, nlayers, nfeatures, path_A, path_partvec, backend, epochs=None, features=None, labels=None, split=None, **data):
+    """PGAT.py:165-233.  ``features`` / ``labels`` / ``split`` (.npy files in global vertex order, nodedata.py; all three or none):
+    train the classifier of ``build_classifier`` on them instead of the synthetic loop (``_train_on_data`` takes the other keyword
+    arguments: task, hidden, out_heads, lr, eval_every, dropout, dropout_seed, bias, weight_decay, decoupled_decay, optimizer); the
+    returned model carries ``history``, ``best`` and ``widths``."""
     global myrank, world_size, send_map, recv_map, device, X, recv_buffers, send_buffers
+    files = [v for v in (features, labels, split) if v is not None]
+    if len(files) not in (0, 3) or (data and not files):
+        raise ValueError("features, labels and split go together, and the other options need them")
+    if data.get("task") not in (None,) + TASKS:
+        raise ValueError("task takes %s, got %r" % (" | ".join(TASKS), data.get("task")))
+    if data.get("optimizer") not in (None,) + OPTIMIZERS:
+        raise ValueError("optimizer takes %s, got %r" % (" | ".join(OPTIMIZERS), data.get("optimizer")))
+    if files and mode == "reference":
+        raise ValueError("the reference layer has no bias, activation, head mean or dropout: train on data in standard mode")
     myrank = rank
     world_size = size
     if torch.cuda.is_available():
@@ -277,6 +590,9 @@ def run(rank, size, nlayers, nfeatures, path_A, path_partvec, backend, epochs=50
     send_map, recv_map = compute_communication_maps(A, partvec, rank, size)
     A = get_partitiont_of_adjacency_matrix(A, partvec, rank)
     send_buffers, recv_buffers = {}, {}
+    if files:
+        return _train_on_data(A, n, nlayers, features, labels, split, epochs=epochs, **data)
+    epochs = 50 if epochs is None else epochs
 
     owned = A.part.owned.to(device)
     H = owned.to(torch.float32).unsqueeze(1).repeat(1, nfeatures).contiguous().requires_grad_(True)   # :196-198
@@ -318,23 +634,23 @@ def run(rank, size, nlayers, nfeatures, path_A, path_partvec, backend, epochs=50
     return model
 
 
-def init_process(rank, size, fn, nlayers, nfeatures, path_A, path_partvec, backend):
-    """PGAT.py:236-240."""
+def init_process(rank, size, fn, nlayers, nfeatures, path_A, path_partvec, backend, data=None):
+    """PGAT.py:236-240.  ``data``: the keyword arguments of ``run`` on real inputs (None: today's call)."""
     global _exchanger
     os.environ.setdefault('MASTER_ADDR', '127.0.0.1')
     os.environ.setdefault('MASTER_PORT', '29500')
     dist.init_process_group(backend, rank=rank, world_size=size)
-    fn(rank, size, nlayers, nfeatures, path_A, path_partvec, backend)
+    fn(rank, size, nlayers, nfeatures, path_A, path_partvec, backend, **(data or {}))
     if _exchanger is not None:
         _exchanger.close()
         _exchanger = None
     dist.destroy_process_group()
 
 
-def _child(rank, size, nlayers, nfeatures, a, p, backend, mode_, heads_):
+def _child(rank, size, nlayers, nfeatures, a, p, backend, mode_, heads_, data=None):
     global mode, heads
     mode, heads = mode_, heads_
-    init_process(rank, size, run, nlayers, nfeatures, a, p, backend)
+    init_process(rank, size, run, nlayers, nfeatures, a, p, backend, data)
 
 
 def main(argv):
@@ -342,13 +658,67 @@ def main(argv):
     on this node like the reference does; under torchrun / SLURM each process runs its own rank."""
     global path_A, path_partvec, mode, heads
     backend, size, nlayers, nfeatures = "nccl", 1, 1, 4
+    data = {}          # the node-classification options that were given (run's keyword arguments)
+
+    def refuse(text):
+        print(text, flush=True)
+        sys.exit(2)
+
     try:
-        opts, args = getopt.getopt(argv, "a:p:b:s:l:f:", ["mode=", "heads="])
+        opts, args = getopt.getopt(argv, "a:p:b:s:l:f:", ["mode=", "heads=", "features=", "labels=", "split=", "task=", "hidden=",
+                                                          "out-heads=", "epochs=", "lr=", "eval-every=", "dropout=", "dropout-seed=",
+                                                          "bias", "weight-decay=", "adamw", "optimizer="])
     except getopt.GetoptError:
         print("a:p:b:", flush=True)
         sys.exit(2)
     for opt, arg in opts:
-        if opt == '-a':
+        if opt in ('--features', '--labels', '--split'):       # .npy files in global vertex order (nodedata.py)
+            data[opt[2:]] = arg
+        elif opt in ('--hidden', '--out-heads', '--epochs', '--eval-every'):
+            try:
+                data[opt[2:].replace("-", "_")] = int(arg)
+                if int(arg) < (0 if opt == '--epochs' else 1):
+                    raise ValueError
+            except ValueError:
+                refuse("%s takes a positive integer, got %r" % (opt, arg))
+        elif opt == '--task':          # single (one class per vertex, the default) | multilabel (n x C 0 / 1 labels, BCE, micro-F1)
+            if arg not in TASKS:
+                refuse("--task takes %s, got %r" % ("|".join(TASKS), arg))
+            data["task"] = arg
+        elif opt == '--dropout':       # drop the output of every layer but the last with this probability (class PGAT)
+            try:
+                data["dropout"] = float(arg)
+                _dropout.threshold(data["dropout"])
+            except ValueError:
+                refuse("--dropout takes a probability in [0, 1), got %r" % arg)
+        elif opt == '--dropout-seed':
+            try:
+                data["dropout_seed"] = int(arg)
+            except ValueError:
+                refuse("--dropout-seed takes an integer, got %r" % arg)
+        elif opt == '--bias':          # every layer adds a bias
+            data["bias"] = True
+        elif opt == '--weight-decay':  # Adam's L2 term; with --adamw the decoupled decay of AdamW
+            try:
+                data["weight_decay"] = float(arg)
+                if not (data["weight_decay"] >= 0.0 and math.isfinite(data["weight_decay"])):
+                    raise ValueError
+            except ValueError:
+                refuse("--weight-decay takes a number >= 0, got %r" % arg)
+        elif opt == '--adamw':
+            data["decoupled_decay"] = True
+        elif opt == '--optimizer':     # torch (torch.optim.Adam / AdamW, the default) | fused (optim.FlatAdam: one launch per step)
+            if arg not in OPTIMIZERS:
+                refuse("--optimizer takes %s, got %r" % ("|".join(OPTIMIZERS), arg))
+            data["optimizer"] = arg
+        elif opt == '--lr':
+            try:
+                data["lr"] = float(arg)
+                if not (data["lr"] > 0.0 and math.isfinite(data["lr"])):
+                    raise ValueError
+            except ValueError:
+                refuse("--lr takes a positive number, got %r" % arg)
+        elif opt == '-a':
             path_A = arg
         elif opt == '-p':
             path_partvec = arg
@@ -364,6 +734,18 @@ def main(argv):
             mode = arg
         elif opt == '--heads':
             heads = int(arg)
+    files = [k for k in ("features", "labels", "split") if k in data]
+    if data and len(files) != 3:
+        refuse("--features, --labels and --split go together (and --task, --hidden, --out-heads, --epochs, --lr, --eval-every, --dropout, "
+               "--dropout-seed, --bias, --weight-decay, --adamw, --optimizer need them); got %s"
+               % ", ".join("--" + {"decoupled_decay": "adamw"}.get(k, k.replace("_", "-")) for k in sorted(data)))
+    for k in files:
+        if not os.path.exists(data[k]):
+            refuse("--%s: no such file %r" % (k, data[k]))
+    if data and mode == "reference":
+        refuse("--mode reference has no bias, activation, head mean or dropout: --features needs --mode standard")
+    if data and heads >= 1 and data.get("hidden", 8 * heads) % heads:
+        refuse("--hidden takes a multiple of --heads (%d), got %r" % (heads, str(data["hidden"])))
     env_rank = os.environ.get("SLURM_PROCID", os.environ.get("RANK"))
     mp.set_start_method("spawn", force=True)
     if env_rank is not None:
@@ -373,7 +755,8 @@ def main(argv):
         ranks = list(range(size))
     processes = []
     for rank in ranks:
-        p = mp.Process(target=_child, args=(rank, size, nlayers, nfeatures, path_A, path_partvec, backend, mode, heads))
+        # (no data option given: the argument tuple of before)
+        p = mp.Process(target=_child, args=(rank, size, nlayers, nfeatures, path_A, path_partvec, backend, mode, heads) + ((data,) if data else ()))
         p.start()
         processes.append(p)
     code = 0

@@ -118,6 +118,11 @@ SIGNATURES = {
     "pgcn_combine_forward_f32": (ctypes.c_int, [_vp, _i64, _vp, _i64, _vp, _i64, _i32, _i32, _vp, ctypes.c_uint64, _vp, _u32, _u32, _vp,
                                                 _i64, _vp]),
     "pgcn_combine_backward_f32": (ctypes.c_int, [_vp, _i64, _vp, _i64, _i64, _i32, _i32, ctypes.c_float, _vp, _i64, _vp, _vp, _i64, _vp]),
+    "pgcn_gat_tail_ws_bytes": (_i64, [_i64, _i32]),
+    "pgcn_gat_tail_forward_f32": (ctypes.c_int, [_vp, _i64, _i64, _i32, _i32, _i32, _vp, _i32, _vp, ctypes.c_uint64, _vp, _u32, _u32, _vp,
+                                                 _i64, _vp]),
+    "pgcn_gat_tail_backward_f32": (ctypes.c_int, [_vp, _i64, _vp, _i64, _i64, _i32, _i32, _i32, _i32, _vp, ctypes.c_uint64, _vp, _u32, _u32,
+                                                  _vp, _i64, _vp, _vp, _i64, _vp]),
     "pgcn_ln_ws_bytes": (_i64, [_i64, _i32]),
     "pgcn_ln_relu_forward_f32": (ctypes.c_int, [_vp, _i64, _i64, _i32, _vp, _vp, ctypes.c_double, _vp, _i64, _vp, ctypes.c_uint64, _vp, _u32,
                                                 _u32, _vp, _i64, _vp, _vp, _vp, _vp]),

@@ -209,6 +209,9 @@ BN_MAX_F = 1024          # widest block the batch-norm kernels take (csrc/pgcn_n
 BN_STAT_ROWS = 512       # rows of a band of its column-sum kernels (kStatRows; pgcn_bn_colstats_ws_bytes counts one record per band)
 COMBINE_MAX_F = 1024     # widest block the combine kernels take (csrc/pgcn_combine.hip: the same layout)
 COMBINE_SUM_ROWS = 512   # rows of a block of its backward (kSumRows; pgcn_combine_ws_bytes counts one record per block)
+GAT_TAIL_MAX_F = 1024    # widest output of the GAT tail kernels (csrc/pgcn_gat_tail.hip: the same layout)
+GAT_TAIL_MAX_IN = 8192   # widest input (heads * d) they read
+GAT_TAIL_SUM_ROWS = 512  # rows of a block of their backward (kSumRows; pgcn_gat_tail_ws_bytes counts one record per block)
 LN_MAX_F = 1024          # widest block the layer-norm kernels take (csrc/pgcn_layernorm.hip: the same layout)
 LN_STAT_ROWS = 512       # rows of a block of its backward (kBandRows; pgcn_ln_ws_bytes counts one record per block)
 
@@ -1263,6 +1266,66 @@ class HipKernels:
                                                       n, f, 1 if relu else 0, float(scale), _ptr(Gm), self._ld(Gm) if want_gm else 0,
                                                       _ptr(dbias), _ptr(ws), ws_bytes, self._stream()), "pgcn_combine_backward_f32")
         return Gm, dbias
+
+    # -- the tail of a GAT layer: head mean, bias, ELU and dropout (csrc/pgcn_gat_tail.hip) -------------------------------
+    def _tail_mat_ok(self, t: Optional[torch.Tensor], n: int, width: int) -> bool:
+        return t is None or (t.is_cuda and t.device == self.device and t.dim() == 2 and t.dtype is torch.float32 and
+                             tuple(t.shape) == (n, width) and (t.stride(1) == 1 or width == 1 or n == 0) and
+                             (n <= 1 or t.stride(0) >= width))
+
+    def gat_tail_forward(self, X: torch.Tensor, heads: int, d: int, mean: bool, bias: Optional[torch.Tensor], act: int,
+                         row_ids: Optional[torch.Tensor] = None, seed: int = 0, step: Optional[torch.Tensor] = None, layer: int = 0,
+                         thr: int = 0, out: Optional[torch.Tensor] = None):
+        """Y = drop(act(reduce_heads(X) + bias)) in one pass (pgcn_gat_tail_forward_f32): X is n x heads * d, Y n x fout with fout = d
+        (``mean``: the heads averaged) or heads * d.  ``bias`` None: absent; ``act`` 0: none, 1: ELU.  ``step`` None or ``thr`` 0: no
+        dropout; ``step``: one int64 on the device, read by the kernel; ``row_ids``: int64 [n] global ids (None: the row index).
+        ``out`` may be X itself when ``mean`` is off.  None when the shape is not covered."""
+        heads, d = int(heads), int(d)
+        if X.dim() != 2 or heads < 1 or d < 1 or X.shape[1] != heads * d or act not in (0, 1):
+            return None
+        n, fin = X.shape
+        fout = d if mean else fin
+        if fout > GAT_TAIL_MAX_F or fin > GAT_TAIL_MAX_IN or not self._tail_mat_ok(X, n, fin) or not self._tail_mat_ok(out, n, fout):
+            return None
+        if not self._bn_vec_ok(fout, torch.float32, bias) or not self._bn_vec_ok(n, torch.int64, row_ids) or \
+                not self._bn_vec_ok(1, torch.int64, step):
+            return None
+        Y = out if out is not None else torch.empty((n, fout), dtype=torch.float32, device=self.device)
+        _lib.check(self.lib.pgcn_gat_tail_forward_f32(X.data_ptr(), self._ld(X), n, heads, d, 1 if mean else 0, _ptr(bias), int(act),
+                                                      _ptr(row_ids), int(seed) & ((1 << 64) - 1), _ptr(step), int(layer), int(thr),
+                                                      Y.data_ptr(), self._ld(Y), self._stream()), "pgcn_gat_tail_forward_f32")
+        return Y
+
+    def gat_tail_backward(self, G: torch.Tensor, Y: Optional[torch.Tensor], heads: int, d: int, mean: bool, act: int,
+                          row_ids: Optional[torch.Tensor] = None, seed: int = 0, step: Optional[torch.Tensor] = None, layer: int = 0,
+                          thr: int = 0, want_dx: bool = True, want_dbias: bool = True, out: Optional[torch.Tensor] = None):
+        """(dX, dbias) of the same tail from G and the saved Y (needed with ELU only); the keep bits are formed again from the key
+        (pgcn_gat_tail_backward_f32; one pass + the second level of the sums).  dX is n x heads * d, dbias fp32 [fout], THIS rank's
+        column sums added in double.  ``want_dx`` False: dX is None (sums only); ``want_dbias`` False: dbias is None (one launch).
+        None when the shape is not covered."""
+        heads, d = int(heads), int(d)
+        if G.dim() != 2 or heads < 1 or d < 1 or act not in (0, 1) or (act and Y is None):
+            return None
+        n, fout = G.shape
+        fin = heads * d
+        if fout != (d if mean else fin) or fout > GAT_TAIL_MAX_F or fin > GAT_TAIL_MAX_IN or not self._tail_mat_ok(G, n, fout) or \
+                not self._tail_mat_ok(Y if act else None, n, fout) or not self._tail_mat_ok(out, n, fin):
+            return None
+        if not self._bn_vec_ok(n, torch.int64, row_ids) or not self._bn_vec_ok(1, torch.int64, step):
+            return None
+        dX = dbias = ws = None
+        ws_bytes = 0
+        if want_dx:
+            dX = out if out is not None else torch.empty((n, fin), dtype=torch.float32, device=self.device)
+        if want_dbias:
+            dbias = torch.empty(fout, dtype=torch.float32, device=self.device)
+            ws_bytes = int(self.lib.pgcn_gat_tail_ws_bytes(n, fout))
+            ws = torch.empty(ws_bytes // 8, dtype=torch.float64, device=self.device)
+        _lib.check(self.lib.pgcn_gat_tail_backward_f32(G.data_ptr(), self._ld(G), Y.data_ptr() if act else None, self._ld(Y) if act else 0,
+                                                       n, heads, d, 1 if mean else 0, int(act), _ptr(row_ids), int(seed) & ((1 << 64) - 1),
+                                                       _ptr(step), int(layer), int(thr), _ptr(dX), self._ld(dX) if want_dx else 0,
+                                                       _ptr(dbias), _ptr(ws), ws_bytes, self._stream()), "pgcn_gat_tail_backward_f32")
+        return dX, dbias
 
     # -- layer normalisation of a vertex over its features + residual link, fused with ReLU and dropout (csrc/pgcn_layernorm.hip)
     def ln_relu_forward(self, X: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: float, R: Optional[torch.Tensor] = None,
