@@ -208,19 +208,10 @@ def gat_tail_backward_composed(G, Y, heads, d, mean=False, act=0, row_ids=None, 
 
 
 def _tail_kernels(X, width, bias=None, row_ids=None):
-    """The provider whose tail kernels take these operands, or None (CPU tensors, the checker-backed provider of the tests, widths
-    above the kernels', another dtype or layout).  Decided BEFORE the first launch."""
-    k = _kernel_provider if _kernel_provider is not None else getattr(_engine_current, "k", None)
-    if k is None or not hasattr(k, "gat_tail_forward") or not hasattr(k, "gat_tail_backward"):
-        return None
-    if not (X.is_cuda and X.dim() == 2 and X.dtype is torch.float32 and 0 < X.shape[1] <= _kernels.GAT_TAIL_MAX_IN
-            and 0 < width <= _kernels.GAT_TAIL_MAX_F and (X.stride(1) == 1 or X.shape[1] == 1 or X.shape[0] == 0)
-            and (X.shape[0] <= 1 or X.stride(0) >= X.shape[1])):
-        return None
-    if bias is not None and not (bias.is_cuda and bias.device == X.device and bias.dtype is torch.float32 and bias.is_contiguous()
-                                 and bias.numel() == width):
-        return None
-    return k if _pgcn._row_ids_ok(row_ids, X.shape[0]) and (row_ids is None or row_ids.device == X.device) else None
+    """The provider whose tail kernels take X (heads * d columns) for an output of ``width`` columns, or None: PGCN._rowband_kernels."""
+    return _pgcn._rowband_kernels(_kernel_provider if _kernel_provider is not None else getattr(_engine_current, "k", None),
+                                  ("gat_tail_forward", "gat_tail_backward"), (X,), (bias,), row_ids, width=width,
+                                  max_in=_kernels.GAT_TAIL_MAX_IN)
 
 
 class _GatTail(torch.autograd.Function):

@@ -861,18 +861,40 @@ def batchnorm_relu_backward_composed(G, Y, X, mean, invstd, gamma, n_global, sca
     return a * ((gm - c1) - xh * c2), dgamma, dbeta
 
 
-def _bn_kernels(X, vectors=(), row_ids=None):
-    """The provider whose batch-norm kernels take X and the per-column vectors, or None (CPU tensors, the checker-backed provider of
-    the tests, more than 1024 columns, another dtype or layout).  Decided BEFORE the first launch: a step never changes route
-    between its collectives."""
-    k = _kernel_provider if _kernel_provider is not None else getattr(_engine_current, "k", None)
-    if k is None or not hasattr(k, "bn_colstats") or not (X.is_cuda and X.dim() == 2 and X.dtype is torch.float32 and 0 < X.shape[1] <= _kernels.BN_MAX_F
-                                                          and (X.stride(1) == 1 or X.shape[1] == 1 or X.shape[0] == 0)):
+def _rowband_kernels(k, methods, mats, vectors=(), row_ids=None, step=None, width=None, max_in=None, check_ld=True):
+    """``k`` if it is a provider whose row-band kernels (csrc/pgcn_rowband.h) take these operands, else None (no provider, CPU tensors,
+    the checker-backed provider of the tests, too many columns, another dtype or layout).  Decided BEFORE the first launch: a step
+    never changes route between its collectives.  ``methods``: what the provider must have; ``mats``: the matrices (None: absent),
+    all of mats[0]'s shape, at most ``max_in`` columns (default: the kernels' limit); ``vectors``: the per-column vectors (None:
+    absent) of ``width`` elements (default: the matrices' width, always within the kernels' limit); ``row_ids`` / ``step``: the
+    dropout's operands.  ``check_ld`` off: a leading dimension below the width is left to the provider's method (the batch-norm
+    gate, which then raises instead of taking the composition)."""
+    X = mats[0]
+    if k is None:
         return None
-    if not all(v.is_cuda and v.device == X.device and v.dtype is torch.float32 and v.is_contiguous() and v.numel() == X.shape[1]
-               for v in vectors):
+    for m in methods:
+        if not hasattr(k, m):
+            return None
+    for t in mats:
+        if t is not None and not (t.is_cuda and t.dim() == 2 and t.dtype is torch.float32 and t.shape == X.shape and t.device == X.device
+                                  and (t.stride(1) == 1 or t.shape[1] == 1 or t.shape[0] == 0)
+                                  and (not check_ld or t.shape[0] <= 1 or t.stride(0) >= t.shape[1])):
+            return None
+    width = X.shape[1] if width is None else width
+    if not (0 < X.shape[1] <= (max_in or _kernels.ROWBAND_MAX_F) and 0 < width <= _kernels.ROWBAND_MAX_F):
+        return None
+    for v in vectors:
+        if v is not None and not (v.is_cuda and v.device == X.device and v.dtype is torch.float32 and v.is_contiguous() and v.numel() == width):
+            return None
+    if step is not None and not (step.is_cuda and step.device == X.device and step.dtype is torch.int64 and step.numel() == 1):
         return None
     return k if _row_ids_ok(row_ids, X.shape[0]) and (row_ids is None or row_ids.device == X.device) else None
+
+
+def _bn_kernels(X, vectors=(), row_ids=None):
+    """The provider whose batch-norm kernels take X and the per-column vectors, or None."""
+    return _rowband_kernels(_kernel_provider if _kernel_provider is not None else getattr(_engine_current, "k", None), ("bn_colstats",),
+                            (X,), vectors, row_ids, check_ld=False)
 
 
 def _bn_must(out, what, gate="_bn_kernels"):
@@ -972,22 +994,9 @@ def layernorm_relu_backward_composed(G, X, mean, rstd, gamma, bits, scale=1.0):
 
 
 def _ln_kernels(X, vectors=(), R=None, row_ids=None, step=None):
-    """The provider whose layer-norm kernels take X, the per-column vectors and the residual, or None (CPU tensors, the checker-backed
-    provider of the tests, more than 1024 columns, another dtype or layout).  Decided BEFORE the first launch, as ``_bn_kernels``."""
-    k = _kernel_provider if _kernel_provider is not None else getattr(_engine_current, "k", None)
-    if k is None or not hasattr(k, "ln_relu_forward") or not hasattr(k, "ln_relu_backward"):
-        return None
-    for t in (X, R):
-        if t is not None and not (t.is_cuda and t.dim() == 2 and t.dtype is torch.float32 and t.shape == X.shape and t.device == X.device
-                                  and 0 < t.shape[1] <= _kernels.LN_MAX_F and (t.stride(1) == 1 or t.shape[1] == 1 or t.shape[0] == 0)
-                                  and (t.shape[0] <= 1 or t.stride(0) >= t.shape[1])):
-            return None
-    if not all(v.is_cuda and v.device == X.device and v.dtype is torch.float32 and v.is_contiguous() and v.numel() == X.shape[1]
-               for v in vectors):
-        return None
-    if step is not None and not (step.is_cuda and step.device == X.device and step.dtype is torch.int64 and step.numel() == 1):
-        return None
-    return k if _row_ids_ok(row_ids, X.shape[0]) and (row_ids is None or row_ids.device == X.device) else None
+    """The provider whose layer-norm kernels take X, the per-column vectors and the residual, or None."""
+    return _rowband_kernels(_kernel_provider if _kernel_provider is not None else getattr(_engine_current, "k", None),
+                            ("ln_relu_forward", "ln_relu_backward"), (X, R), vectors, row_ids, step)
 
 
 class _LayerNormReluDropout(torch.autograd.Function):
@@ -1066,20 +1075,9 @@ def combine_backward_composed(G, Y=None, relu=True, scale=1.0, want_dbias=True):
 
 
 def _combine_kernels(Z1, Z2=None, bias=None, row_ids=None):
-    """The provider whose combine kernels take these operands, or None (CPU tensors, the checker-backed provider of the tests, more than
-    1024 columns, another dtype or layout).  Decided BEFORE the first launch."""
-    k = _kernel_provider if _kernel_provider is not None else getattr(_engine_current, "k", None)
-    if k is None or not hasattr(k, "combine_forward") or not hasattr(k, "combine_backward"):
-        return None
-    for t in (Z1, Z2):
-        if t is not None and not (t.is_cuda and t.dim() == 2 and t.dtype is torch.float32 and t.shape == Z1.shape and t.device == Z1.device
-                                  and 0 < t.shape[1] <= _kernels.COMBINE_MAX_F and (t.stride(1) == 1 or t.shape[1] == 1 or t.shape[0] == 0)
-                                  and (t.shape[0] <= 1 or t.stride(0) >= t.shape[1])):
-            return None
-    if bias is not None and not (bias.is_cuda and bias.device == Z1.device and bias.dtype is torch.float32 and bias.is_contiguous()
-                                 and bias.numel() == Z1.shape[1]):
-        return None
-    return k if _row_ids_ok(row_ids, Z1.shape[0]) and (row_ids is None or row_ids.device == Z1.device) else None
+    """The provider whose combine kernels take these operands, or None."""
+    return _rowband_kernels(_kernel_provider if _kernel_provider is not None else getattr(_engine_current, "k", None),
+                            ("combine_forward", "combine_backward"), (Z1, Z2), (bias,), row_ids)
 
 
 class _CombineBiasReluDropout(torch.autograd.Function):

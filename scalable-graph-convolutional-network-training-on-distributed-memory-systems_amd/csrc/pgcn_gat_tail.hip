@@ -11,76 +11,23 @@
 // derivative.  It does NOT give the mask (Y == 0 is a dropped element or a == 0), and X is not kept for the backward, so the keep
 // bits are formed again from the key: one fmix32 per element, no mask tensor written or read.
 //
-// Layout as in pgcn_combine.hip: 256 threads; a thread owns FOUR consecutive OUTPUT columns, TPR = the power of two >=
-// ceil(fout / 4) threads span a row, 256 / TPR row groups walk a band of consecutive rows, four rows per thread in flight; in mean
-// mode a thread reads its four columns of every head (heads strided loads per output quad) and adds them in index order.  The
-// bias and the column's share of the dropout hash are loaded / formed once per thread, before the row loop.  fout <= 1024.  One
-// float4 per thread, row and head when fout % 4 == 0 (so d % 4 == 0 in mean mode) and every base and leading dimension keeps the
-// rows 16-byte aligned, four guarded scalars otherwise: the same thread does the same arithmetic in the same order, so both paths
-// leave the same bits (this file is compiled with contraction off).
-//
-// dbias: as in pgcn_combine.hip -- a block of the backward owns kSumRows consecutive rows, adds Gm in double registers, folds the
-// row groups through LDS by a fixed tree and writes ONE partial record [fout] of doubles; the second launch adds the records in a
-// fixed order.  No floating-point atomics; a NaN or inf stays in its own column.  Raw pointers + a stream, no allocation, no
-// synchronisation: graph-capturable.
+// The layout of pgcn_rowband.h over the OUTPUT columns (fout <= 1024), four rows per thread in flight; in mean mode a thread reads
+// its four columns of every head (heads strided loads per output quad, so the float4 path needs d % 4 == 0) and adds them in index
+// order.  The dropout pieces and the deterministic column sums (dbias: partial records [fout]) are those of pgcn_rowband.h too.
+// This file is compiled with contraction off.  Raw pointers + a stream, no allocation, no synchronisation: graph-capturable.
 #include <hip/hip_runtime.h>
 #include <float.h>
 #include <math.h>
 #include <stdint.h>
 
 #include "pgcn_internal.h"
-
-#define PG_DROPOUT_FN __host__ __device__ __forceinline__
-#include "../gemm/pgcn_dropout.h"
+#include "pgcn_rowband.h"
 
 namespace {
 
-constexpr int kThreads = 256;
-constexpr int kSumRows = 512;      // rows of a block of the backward (kernels.GAT_TAIL_SUM_ROWS restates it)
-constexpr int kApplyRows = 128;    // rows of a block of the forward
-constexpr int kFinalCols = 32;     // columns of a block of the second level
-constexpr int kFinalGroups = kThreads / kFinalCols;
-constexpr int kMaxF = 1024;        // widest output
-constexpr int kMaxIn = 8192;       // widest input (heads * d)
-
-struct Quad {
-    float v[4];
-};
-
-// (no __restrict__ on the matrices: Y may be X itself; a thread reads its own elements before it writes them)
-template <bool VEC>
-__device__ __forceinline__ Quad load_quad(const float *row, int c0, int f) {
-    Quad q;
-    if constexpr (VEC) {
-        const float4 t = *reinterpret_cast<const float4 *>(row + c0);
-        q.v[0] = t.x, q.v[1] = t.y, q.v[2] = t.z, q.v[3] = t.w;
-    } else {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) q.v[j] = c0 + j < f ? row[c0 + j] : 0.f;
-    }
-    return q;
-}
-
-template <bool VEC>
-__device__ __forceinline__ void store_quad(float *row, int c0, int f, const Quad &q) {
-    if constexpr (VEC) {
-        *reinterpret_cast<float4 *>(row + c0) = make_float4(q.v[0], q.v[1], q.v[2], q.v[3]);
-    } else {
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-            if (c0 + j < f) row[c0 + j] = q.v[j];
-    }
-}
+constexpr int kMaxIn = 8192;       // widest input (heads * d); kMaxF bounds the output
 
 __device__ __forceinline__ float elu(float t) { return t > 0.f ? t : expm1f(t); }      // (NaN stays NaN, -0.0 stays -0.0)
-
-struct DropArgs {
-    const int64_t *row_ids;
-    const int64_t *step;       // NULL: no dropout
-    uint64_t seed;
-    uint32_t layer, thr;
-    float scale, inv_scale;
-};
 
 // `f` is the OUTPUT width (d in mean mode, heads * d otherwise); in mean mode head k of a row starts at column k * f of X.
 template <bool VEC>
@@ -88,25 +35,15 @@ __global__ __launch_bounds__(kThreads) void forward_kernel(const float *X, int64
                                                            int nsum, float inv_heads, int log2_tpr, int act, DropArgs d, float *Y,
                                                            int64_t ldy) {
 #pragma clang fp contract(off)
-    const int tid = threadIdx.x, u = tid & ((1 << log2_tpr) - 1), rg = tid >> log2_tpr, ngroups = kThreads >> log2_tpr;
-    const int c0 = 4 * u;
+    const auto [tpr, u, rg, ngroups, c0, r0, rend] = band_of(log2_tpr, kApplyRows, nrows);
     if (c0 >= f) return;
-    const int64_t r0 = (int64_t)blockIdx.x * kApplyRows;
-    const int64_t rend = r0 + kApplyRows < nrows ? r0 + kApplyRows : nrows;
     const bool has_bias = bias != nullptr;
     float b[4] = {0.f, 0.f, 0.f, 0.f};
     if (has_bias) {
 #pragma unroll
         for (int j = 0; j < 4; ++j) b[j] = c0 + j < f ? bias[c0 + j] : 0.f;
     }
-    const bool drop = d.step != nullptr;
-    uint64_t key = 0;
-    uint32_t dcol[4] = {0, 0, 0, 0};
-    if (drop) {
-        key = dropout_key(d.seed, (uint64_t)d.step[0], d.layer);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) dcol[j] = dropout_col(key, (uint32_t)(c0 + j));      // the column's share: once per column
-    }
+    const DropCols dc = drop_cols(d.step, d.seed, d.layer, c0);
     for (int64_t r = r0 + rg; r < rend; r += 4 * (int64_t)ngroups) {
         Quad p[4];
 #pragma unroll
@@ -141,11 +78,10 @@ __global__ __launch_bounds__(kThreads) void forward_kernel(const float *X, int64
                 if (has_bias) t = t + b[j];
                 y.v[j] = act ? elu(t) : t;
             }
-            if (drop) {
-                const uint64_t grow = d.row_ids ? (uint64_t)d.row_ids[rr] : (uint64_t)rr;
-                const uint32_t term = dropout_row(key, grow), hi = (uint32_t)(grow >> 32);
+            if (dc.on) {
+                const DropRow dr = drop_row(d.row_ids, dc, rr);
 #pragma unroll
-                for (int j = 0; j < 4; ++j) y.v[j] = dropout_u(dcol[j], term, hi) >= d.thr ? y.v[j] * d.scale : 0.f;
+                for (int j = 0; j < 4; ++j) y.v[j] = drop_keep(dc, dr, j, d.thr) ? y.v[j] * d.scale : 0.f;
             }
             store_quad<VEC>(Y + rr * ldy, c0, f, y);
         }
@@ -160,21 +96,12 @@ __global__ __launch_bounds__(kThreads) void backward_kernel(const float *G, int6
                                                             DropArgs d, float *dX, int64_t lddx, double *__restrict__ ws) {
 #pragma clang fp contract(off)
     __shared__ double sm[4 * kThreads];
-    const int tid = threadIdx.x, u = tid & ((1 << log2_tpr) - 1), rg = tid >> log2_tpr, ngroups = kThreads >> log2_tpr;
-    const int c0 = 4 * u;
+    const auto [tpr, u, rg, ngroups, c0, r0, rend] = band_of(log2_tpr, kSumRows, nrows);
     const bool active = c0 < f;
-    const int64_t r0 = (int64_t)blockIdx.x * kSumRows;
-    const int64_t rend = r0 + kSumRows < nrows ? r0 + kSumRows : nrows;
     double acc[4] = {0, 0, 0, 0};
     if (active) {
-        const bool drop = d.step != nullptr;
-        uint64_t key = 0;
-        uint32_t dcol[4] = {0, 0, 0, 0};
-        if (drop) {
-            key = dropout_key(d.seed, (uint64_t)d.step[0], d.layer);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) dcol[j] = dropout_col(key, (uint32_t)(c0 + j));
-        }
+        const DropCols dc = drop_cols(d.step, d.seed, d.layer, c0);
+        const bool drop = dc.on;
         for (int64_t r = r0 + rg; r < rend; r += 4 * (int64_t)ngroups) {
             Quad g[4], y[4];
 #pragma unroll
@@ -190,11 +117,7 @@ __global__ __launch_bounds__(kThreads) void backward_kernel(const float *G, int6
             for (int k = 0; k < 4; ++k) {
                 const int64_t rr = r + (int64_t)k * ngroups;
                 if (rr >= rend) break;
-                uint32_t term = 0, hi = 0;
-                if (drop) {
-                    const uint64_t grow = d.row_ids ? (uint64_t)d.row_ids[rr] : (uint64_t)rr;
-                    term = dropout_row(key, grow), hi = (uint32_t)(grow >> 32);
-                }
+                const DropRow dr = drop ? drop_row(d.row_ids, dc, rr) : DropRow{0, 0};
                 Quad o, x;
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
@@ -205,7 +128,7 @@ __global__ __launch_bounds__(kThreads) void backward_kernel(const float *G, int6
                         if (drop) e = e * d.inv_scale;
                         gm = gm * (e + 1.0f);
                     }
-                    if (drop && dropout_u(dcol[j], term, hi) < d.thr) gm = 0.f;
+                    if (drop && !drop_keep(dc, dr, j, d.thr)) gm = 0.f;
                     o.v[j] = gm;
                     acc[j] += (double)gm;                // (a lane beyond the last column loaded zeros: it adds zeros and stores nothing)
                     x.v[j] = nsum > 1 ? gm * inv_heads : gm;
@@ -217,73 +140,18 @@ __global__ __launch_bounds__(kThreads) void backward_kernel(const float *G, int6
         }
     }
     if (ws == nullptr) return;                           // (uniform over the block: no barrier is skipped by a part of it)
-    // fold the 256 / TPR row groups through LDS by a fixed tree, k-major: neighbouring threads touch neighbouring doubles
-#pragma unroll
-    for (int k = 0; k < 4; ++k) sm[k * kThreads + tid] = acc[k];
-    for (int s = ngroups >> 1; s >= 1; s >>= 1) {
-        __syncthreads();
-        if (rg < s) {
-#pragma unroll
-            for (int k = 0; k < 4; ++k) sm[k * kThreads + tid] += sm[k * kThreads + tid + (s << log2_tpr)];
-        }
-    }
-    __syncthreads();
-    if (rg == 0 && active) {
-        double *rec = ws + (int64_t)blockIdx.x * f;
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-            if (c0 + j < f) rec[c0 + j] = sm[j * kThreads + tid];
-    }
+    fold_row_groups(acc, sm, log2_tpr);
+    if (rg == 0 && active) write_partial(acc, ws, blockIdx.x, c0, f);
 }
 
-// Second level: block b owns columns 32 b .. 32 b + 31; group g of its threads adds records g, g + 8, ... in that order, then the
-// 8 groups are folded by a fixed tree.  No record (nrows == 0): zeros.
+// Second level of the f sums.  No record (nrows == 0): zeros.
 __global__ __launch_bounds__(kThreads) void finalize_kernel(const double *__restrict__ ws, int64_t nbands, int f, float *__restrict__ dbias) {
-    __shared__ double sm[kThreads];
-    const int tid = threadIdx.x, lane = tid & (kFinalCols - 1), grp = tid / kFinalCols;
-    const int o = blockIdx.x * kFinalCols + lane;
-    double acc = 0.0;
-    if (o < f)
-        for (int64_t b = grp; b < nbands; b += kFinalGroups) acc += ws[b * (int64_t)f + o];
-    sm[tid] = acc;
-    for (int s = kFinalGroups >> 1; s >= 1; s >>= 1) {
-        __syncthreads();
-        if (grp < s) sm[tid] += sm[tid + s * kFinalCols];
-    }
-    if (grp == 0 && o < f) dbias[o] = (float)sm[tid];
-}
-
-int log2_threads_per_row(int f) {
-    const int quads = (f + 3) / 4;
-    int l = 0;
-    while ((1 << l) < quads) ++l;
-    return l;
-}
-
-bool aligned16(const void *p) { return ((uintptr_t)p % 16) == 0; }
-bool rows16(int64_t ld) { return ld % 4 == 0; }
-int64_t bands(int64_t nrows) { return (nrows + kSumRows - 1) / kSumRows; }
-
-DropArgs drop_args(const int64_t *row_ids, uint64_t seed, const int64_t *step, uint32_t layer, uint32_t thr) {
-#pragma clang fp contract(off)
-    DropArgs a;
-    a.row_ids = row_ids;
-    a.step = thr > 0 ? step : nullptr;     // (thr == 0 keeps everything at scale 1: the path without dropout, bit for bit)
-    a.seed = seed;
-    a.layer = layer;
-    a.thr = thr;
-    a.scale = dropout_scale(thr);
-    a.inv_scale = 1.0f / a.scale;
-    return a;
+    final_sum<1>(ws, nbands, f, [=](int o, double v) { dbias[o] = (float)v; });
 }
 
 }  // namespace
 
-extern "C" int64_t pgcn_gat_tail_ws_bytes(int64_t nrows, int32_t fout) {
-    if (nrows < 0 || fout < 1 || fout > kMaxF) return -1;
-    const int64_t nb = bands(nrows);
-    return (nb > 0 ? nb : 1) * (int64_t)fout * (int64_t)sizeof(double);
-}
+extern "C" int64_t pgcn_gat_tail_ws_bytes(int64_t nrows, int32_t fout) { return ws_bytes(nrows, fout, 1); }
 
 extern "C" int pgcn_gat_tail_forward_f32(const float *X, int64_t ldx, int64_t nrows, int32_t heads, int32_t d, int32_t mean,
                                          const float *bias, int32_t act, const int64_t *row_ids, uint64_t seed, const int64_t *step,
@@ -303,15 +171,9 @@ extern "C" int pgcn_gat_tail_forward_f32(const float *X, int64_t ldx, int64_t nr
     const DropArgs da = drop_args(row_ids, seed, step, layer, thr);
     const int f = (int)fout, nsum = mean ? (int)heads : 1;
     const float inv_heads = 1.0f / (float)heads;
-    const int l2 = log2_threads_per_row(f);
-    const int64_t nb = (nrows + kApplyRows - 1) / kApplyRows;
     const bool vec = f % 4 == 0 && rows16(ldx) && rows16(ldy) && aligned16(X) && aligned16(Y);
-    if (vec)
-        hipLaunchKernelGGL(forward_kernel<true>, dim3((unsigned)nb), dim3(kThreads), 0, (hipStream_t)stream, X, ldx, bias, nrows, f, nsum,
-                           inv_heads, l2, (int)act, da, Y, ldy);
-    else
-        hipLaunchKernelGGL(forward_kernel<false>, dim3((unsigned)nb), dim3(kThreads), 0, (hipStream_t)stream, X, ldx, bias, nrows, f, nsum,
-                           inv_heads, l2, (int)act, da, Y, ldy);
+    launch(vec ? forward_kernel<true> : forward_kernel<false>, apply_blocks(nrows), (hipStream_t)stream, X, ldx, bias, nrows, f, nsum,
+           inv_heads, log2_threads_per_row(f), act, da, Y, ldy);
     PGCN_HIP_CHECK(hipGetLastError());
     return PGCN_OK;
 }
@@ -347,17 +209,12 @@ extern "C" int pgcn_gat_tail_backward_f32(const float *G, int64_t ldg, const flo
         const bool vec = f % 4 == 0 && rows16(ldg) && aligned16(G) && (!act || (rows16(ldy) && aligned16(Y))) &&
                          (!dX || (rows16(lddx) && aligned16(dX)));
         double *rec = dbias ? (double *)ws : nullptr;
-        if (vec)
-            hipLaunchKernelGGL(backward_kernel<true>, dim3((unsigned)nb), dim3(kThreads), 0, s, G, ldg, Y, ldy, nrows, f, nsum, inv_heads, l2,
-                               (int)act, da, dX, lddx, rec);
-        else
-            hipLaunchKernelGGL(backward_kernel<false>, dim3((unsigned)nb), dim3(kThreads), 0, s, G, ldg, Y, ldy, nrows, f, nsum, inv_heads, l2,
-                               (int)act, da, dX, lddx, rec);
+        launch(vec ? backward_kernel<true> : backward_kernel<false>, nb, s, G, ldg, Y, ldy, nrows, f, nsum, inv_heads, l2, act, da, dX, lddx,
+               rec);
         PGCN_HIP_CHECK(hipGetLastError());
     }
     if (dbias) {
-        hipLaunchKernelGGL(finalize_kernel, dim3((unsigned)((f + kFinalCols - 1) / kFinalCols)), dim3(kThreads), 0, s, (const double *)ws, nb,
-                           f, dbias);
+        launch(finalize_kernel, final_blocks(f), s, ws, nb, f, dbias);
         PGCN_HIP_CHECK(hipGetLastError());
     }
     return PGCN_OK;

@@ -205,15 +205,11 @@ def masked_bce_stats_views(record: torch.Tensor) -> MaskedBCEStats:
     return MaskedBCEStats(record[0:4].view(torch.float64), record[4:8], record[8:12], record[12:16], record[16:20])
 
 
-BN_MAX_F = 1024          # widest block the batch-norm kernels take (csrc/pgcn_norm.hip: 256 threads x 4 columns)
-BN_STAT_ROWS = 512       # rows of a band of its column-sum kernels (kStatRows; pgcn_bn_colstats_ws_bytes counts one record per band)
-COMBINE_MAX_F = 1024     # widest block the combine kernels take (csrc/pgcn_combine.hip: the same layout)
-COMBINE_SUM_ROWS = 512   # rows of a block of its backward (kSumRows; pgcn_combine_ws_bytes counts one record per block)
-GAT_TAIL_MAX_F = 1024    # widest output of the GAT tail kernels (csrc/pgcn_gat_tail.hip: the same layout)
-GAT_TAIL_MAX_IN = 8192   # widest input (heads * d) they read
-GAT_TAIL_SUM_ROWS = 512  # rows of a block of their backward (kSumRows; pgcn_gat_tail_ws_bytes counts one record per block)
-LN_MAX_F = 1024          # widest block the layer-norm kernels take (csrc/pgcn_layernorm.hip: the same layout)
-LN_STAT_ROWS = 512       # rows of a block of its backward (kBandRows; pgcn_ln_ws_bytes counts one record per block)
+ROWBAND_MAX_F = 1024     # widest block (output) the row-band layer kernels take (csrc/pgcn_rowband.h, kMaxF: 256 threads x 4 columns)
+ROWBAND_SUM_ROWS = 512   # rows of a band of their column-sum kernels (kSumRows; every pgcn_*_ws_bytes counts one record per band)
+BN_MAX_F = COMBINE_MAX_F = GAT_TAIL_MAX_F = LN_MAX_F = ROWBAND_MAX_F                      # (batch norm, combine, GAT tail, layer norm:
+BN_STAT_ROWS = COMBINE_SUM_ROWS = GAT_TAIL_SUM_ROWS = LN_STAT_ROWS = ROWBAND_SUM_ROWS     # the names their gates and tests use)
+GAT_TAIL_MAX_IN = 8192   # widest input (heads * d) the GAT tail kernels read
 
 
 class HipKernels:
@@ -1120,12 +1116,21 @@ class HipKernels:
         return True
 
     # -- batch normalisation over all vertices, fused with ReLU and dropout (csrc/pgcn_norm.hip) --------------------
-    def _bn_mat_ok(self, *ts: torch.Tensor) -> bool:
-        X = ts[0]
+    def _mat_ok(self, t: Optional[torch.Tensor], n: int, width: int) -> bool:
         # (the stride of a dimension of size 1, and every stride of an empty matrix, is never used: torch leaves them arbitrary)
-        return all(t.is_cuda and t.device == self.device and t.dim() == 2 and t.dtype is torch.float32 and t.shape == X.shape and
-                   (t.stride(1) == 1 or t.shape[1] == 1 or t.shape[0] == 0) and (t.shape[0] <= 1 or t.stride(0) >= t.shape[1])
-                   for t in ts) and 0 < X.shape[1] <= BN_MAX_F
+        return t is None or (t.is_cuda and t.device == self.device and t.dim() == 2 and t.dtype is torch.float32 and
+                             tuple(t.shape) == (n, width) and (t.stride(1) == 1 or width == 1 or n == 0) and
+                             (n <= 1 or t.stride(0) >= width))
+
+    def _bn_mat_ok(self, X: torch.Tensor, *more: Optional[torch.Tensor]) -> bool:
+        """X and every further matrix (None: absent) have X's shape and a layout the row-band kernels take."""
+        if X.dim() != 2 or not 0 < X.shape[1] <= ROWBAND_MAX_F:
+            return False
+        n, f = X.shape
+        for t in (X,) + more:
+            if not self._mat_ok(t, n, f):
+                return False
+        return True
 
     def _bn_vec_ok(self, f: int, dtype, *ts: Optional[torch.Tensor]) -> bool:
         return all(t is None or (t.is_cuda and t.device == self.device and t.dtype is dtype and t.is_contiguous() and t.numel() >= f)
@@ -1135,9 +1140,12 @@ class HipKernels:
     def _ld(t: torch.Tensor) -> int:
         return max(t.stride(0), t.shape[1]) if t.shape[0] > 1 else t.shape[1]
 
-    def _bn_ws(self, n: int, f: int):
-        ws_bytes = int(self.lib.pgcn_bn_colstats_ws_bytes(n, f))
-        return torch.empty(ws_bytes // 8, dtype=torch.float64, device=self.device), ws_bytes
+    def _sums_ws(self, ws_bytes_fn, n: int, f: int, outs: int = 0):
+        """(ws, ws_bytes, ...): the work-space of a column-sum kernel, ``ws_bytes_fn(n, f)`` bytes of float64, and ``outs`` fp32 [f]
+        vectors for the sums it leaves."""
+        ws_bytes = int(ws_bytes_fn(n, f))
+        return (torch.empty(ws_bytes // 8, dtype=torch.float64, device=self.device), ws_bytes,
+                *[torch.empty(f, dtype=torch.float32, device=self.device) for _ in range(outs)])
 
     def bn_colstats(self, X: torch.Tensor, sums: Optional[torch.Tensor] = None):
         """float64 [2 f + 1] on the device: the column sums of X, of X^2, and the row count (pgcn_bn_colstats_f32) -- what ONE
@@ -1150,7 +1158,7 @@ class HipKernels:
             sums = torch.empty(2 * f + 1, dtype=torch.float64, device=self.device)
         elif not (self._bn_vec_ok(2 * f + 1, torch.float64, sums)):
             return None
-        ws, ws_bytes = self._bn_ws(n, f)
+        ws, ws_bytes = self._sums_ws(self.lib.pgcn_bn_colstats_ws_bytes, n, f)
         _lib.check(self.lib.pgcn_bn_colstats_f32(X.data_ptr(), self._ld(X), n, f, sums.data_ptr(), ws.data_ptr(), ws_bytes,
                                                  self._stream()), "pgcn_bn_colstats_f32")
         return sums
@@ -1176,7 +1184,7 @@ class HipKernels:
         """Y = keep ? max(0, gamma (X - mean) invstd + beta) * scale : 0 in one pass (pgcn_bn_relu_apply_f32); ``step`` None or
         ``thr`` 0: no dropout.  ``step``: one int64 on the device, read by the kernel; ``row_ids``: int64 [n] global ids (None: the
         row index).  None when the shape is not covered."""
-        if not self._bn_mat_ok(X) or (out is not None and not self._bn_mat_ok(X, out)):
+        if not self._bn_mat_ok(X, out):
             return None
         n, f = X.shape
         if not self._bn_vec_ok(f, torch.float32, mean, invstd, gamma, beta) or not self._bn_vec_ok(n, torch.int64, row_ids) or \
@@ -1199,9 +1207,7 @@ class HipKernels:
         if not self._bn_vec_ok(f, torch.float32, mean, invstd):
             return None
         sums = torch.empty(2 * f, dtype=torch.float64, device=self.device)
-        dgamma = torch.empty(f, dtype=torch.float32, device=self.device)
-        dbeta = torch.empty(f, dtype=torch.float32, device=self.device)
-        ws, ws_bytes = self._bn_ws(n, f)
+        ws, ws_bytes, dgamma, dbeta = self._sums_ws(self.lib.pgcn_bn_colstats_ws_bytes, n, f, 2)
         _lib.check(self.lib.pgcn_bn_backward_stats_f32(G.data_ptr(), self._ld(G), Y.data_ptr(), self._ld(Y), X.data_ptr(), self._ld(X), n, f,
                                                        mean.data_ptr(), invstd.data_ptr(), float(scale), sums.data_ptr(),
                                                        dgamma.data_ptr(), dbeta.data_ptr(), ws.data_ptr(), ws_bytes, self._stream()),
@@ -1211,7 +1217,7 @@ class HipKernels:
     def bn_relu_backward(self, G: torch.Tensor, Y: torch.Tensor, X: torch.Tensor, mean: torch.Tensor, invstd: torch.Tensor,
                          gamma: torch.Tensor, sums: torch.Tensor, n_global: int, scale: float, out: Optional[torch.Tensor] = None):
         """dX = gamma invstd (g' - S1 / N - xh S2 / N) in one pass from the GLOBAL sums (pgcn_bn_relu_backward_f32), or None."""
-        if not self._bn_mat_ok(X, G, Y) or (out is not None and not self._bn_mat_ok(X, out)):
+        if not self._bn_mat_ok(X, G, Y, out):
             return None
         n, f = X.shape
         if not self._bn_vec_ok(f, torch.float32, mean, invstd, gamma) or not self._bn_vec_ok(2 * f, torch.float64, sums):
@@ -1231,8 +1237,7 @@ class HipKernels:
         ``bias`` None: that term is absent.  ``step`` None or ``thr`` 0: no dropout; ``step``: one int64 on the device, read by the
         kernel; ``row_ids``: int64 [n] global ids (None: the row index).  ``out`` may be Z1 itself.  None when the shape is not
         covered."""
-        mats = (Z1,) + ((Z2,) if Z2 is not None else ()) + ((out,) if out is not None else ())
-        if not self._bn_mat_ok(*mats):
+        if not self._bn_mat_ok(Z1, Z2, out):
             return None
         n, f = Z1.shape
         if not self._bn_vec_ok(f, torch.float32, bias) or not self._bn_vec_ok(n, torch.int64, row_ids) or \
@@ -1250,8 +1255,7 @@ class HipKernels:
         """(Gm, dbias): Gm = Y > 0 ? G * scale : 0 with ``relu`` (G itself without), dbias = fp32 [f], THIS rank's column sums of
         Gm added in double (pgcn_combine_backward_f32; one pass + the second level of the sums).  ``want_gm`` False: Gm is None
         (sums only); ``want_dbias`` False: dbias is None (one launch).  None when the shape is not covered."""
-        mats = (G,) + ((Y,) if relu else ()) + ((out,) if out is not None else ())
-        if (relu and Y is None) or not self._bn_mat_ok(*mats):
+        if (relu and Y is None) or not self._bn_mat_ok(G, Y if relu else None, out):
             return None
         n, f = G.shape
         Gm = dbias = ws = None
@@ -1259,20 +1263,13 @@ class HipKernels:
         if want_gm:
             Gm = out if out is not None else torch.empty((n, f), dtype=torch.float32, device=self.device)
         if want_dbias:
-            dbias = torch.empty(f, dtype=torch.float32, device=self.device)
-            ws_bytes = int(self.lib.pgcn_combine_ws_bytes(n, f))
-            ws = torch.empty(ws_bytes // 8, dtype=torch.float64, device=self.device)
+            ws, ws_bytes, dbias = self._sums_ws(self.lib.pgcn_combine_ws_bytes, n, f, 1)
         _lib.check(self.lib.pgcn_combine_backward_f32(G.data_ptr(), self._ld(G), Y.data_ptr() if relu else None, self._ld(Y) if relu else 0,
                                                       n, f, 1 if relu else 0, float(scale), _ptr(Gm), self._ld(Gm) if want_gm else 0,
                                                       _ptr(dbias), _ptr(ws), ws_bytes, self._stream()), "pgcn_combine_backward_f32")
         return Gm, dbias
 
     # -- the tail of a GAT layer: head mean, bias, ELU and dropout (csrc/pgcn_gat_tail.hip) -------------------------------
-    def _tail_mat_ok(self, t: Optional[torch.Tensor], n: int, width: int) -> bool:
-        return t is None or (t.is_cuda and t.device == self.device and t.dim() == 2 and t.dtype is torch.float32 and
-                             tuple(t.shape) == (n, width) and (t.stride(1) == 1 or width == 1 or n == 0) and
-                             (n <= 1 or t.stride(0) >= width))
-
     def gat_tail_forward(self, X: torch.Tensor, heads: int, d: int, mean: bool, bias: Optional[torch.Tensor], act: int,
                          row_ids: Optional[torch.Tensor] = None, seed: int = 0, step: Optional[torch.Tensor] = None, layer: int = 0,
                          thr: int = 0, out: Optional[torch.Tensor] = None):
@@ -1285,7 +1282,7 @@ class HipKernels:
             return None
         n, fin = X.shape
         fout = d if mean else fin
-        if fout > GAT_TAIL_MAX_F or fin > GAT_TAIL_MAX_IN or not self._tail_mat_ok(X, n, fin) or not self._tail_mat_ok(out, n, fout):
+        if fout > GAT_TAIL_MAX_F or fin > GAT_TAIL_MAX_IN or not self._mat_ok(X, n, fin) or not self._mat_ok(out, n, fout):
             return None
         if not self._bn_vec_ok(fout, torch.float32, bias) or not self._bn_vec_ok(n, torch.int64, row_ids) or \
                 not self._bn_vec_ok(1, torch.int64, step):
@@ -1308,8 +1305,8 @@ class HipKernels:
             return None
         n, fout = G.shape
         fin = heads * d
-        if fout != (d if mean else fin) or fout > GAT_TAIL_MAX_F or fin > GAT_TAIL_MAX_IN or not self._tail_mat_ok(G, n, fout) or \
-                not self._tail_mat_ok(Y if act else None, n, fout) or not self._tail_mat_ok(out, n, fin):
+        if fout != (d if mean else fin) or fout > GAT_TAIL_MAX_F or fin > GAT_TAIL_MAX_IN or not self._mat_ok(G, n, fout) or \
+                not self._mat_ok(Y if act else None, n, fout) or not self._mat_ok(out, n, fin):
             return None
         if not self._bn_vec_ok(n, torch.int64, row_ids) or not self._bn_vec_ok(1, torch.int64, step):
             return None
@@ -1318,9 +1315,7 @@ class HipKernels:
         if want_dx:
             dX = out if out is not None else torch.empty((n, fin), dtype=torch.float32, device=self.device)
         if want_dbias:
-            dbias = torch.empty(fout, dtype=torch.float32, device=self.device)
-            ws_bytes = int(self.lib.pgcn_gat_tail_ws_bytes(n, fout))
-            ws = torch.empty(ws_bytes // 8, dtype=torch.float64, device=self.device)
+            ws, ws_bytes, dbias = self._sums_ws(self.lib.pgcn_gat_tail_ws_bytes, n, fout, 1)
         _lib.check(self.lib.pgcn_gat_tail_backward_f32(G.data_ptr(), self._ld(G), Y.data_ptr() if act else None, self._ld(Y) if act else 0,
                                                        n, heads, d, 1 if mean else 0, int(act), _ptr(row_ids), int(seed) & ((1 << 64) - 1),
                                                        _ptr(step), int(layer), int(thr), _ptr(dX), self._ld(dX) if want_dx else 0,
@@ -1336,8 +1331,7 @@ class HipKernels:
         kept and pre-activation > 0.  ``R`` None: nothing is added; ``out`` may be R itself.  ``step`` None or ``thr`` 0: no dropout;
         ``step``: one int64 on the device, read by the kernel; ``row_ids``: int64 [n] global ids (None: the row index).  ``save``
         False (inference): the three are None and not written.  None when the shape is not covered."""
-        mats = (X,) + ((R,) if R is not None else ()) + ((out,) if out is not None else ())
-        if not self._bn_mat_ok(*mats) or X.shape[1] > LN_MAX_F:
+        if not self._bn_mat_ok(X, R, out):
             return None
         n, f = X.shape
         if not self._bn_vec_ok(f, torch.float32, gamma, beta) or not self._bn_vec_ok(n, torch.int64, row_ids) or \
@@ -1360,7 +1354,7 @@ class HipKernels:
         """(dX, dgamma, dbeta) of the same layer from G, X and the forward's bits (pgcn_ln_relu_backward_f32; one pass + the second
         level of the column sums): dgamma / dbeta fp32 [f], THIS rank's sums added in double; ``want_sums`` False: both None, one
         launch.  None when the shape is not covered."""
-        if not self._bn_mat_ok(X, G) or (out is not None and not self._bn_mat_ok(X, out)) or X.shape[1] > LN_MAX_F:
+        if not self._bn_mat_ok(X, G, out):
             return None
         n, f = X.shape
         if not self._bn_vec_ok(f, torch.float32, gamma) or not self._bn_vec_ok(n, torch.float32, mean, rstd) or mean is None or rstd is None:
@@ -1372,10 +1366,7 @@ class HipKernels:
         dgamma = dbeta = ws = None
         ws_bytes = 0
         if want_sums:
-            dgamma = torch.empty(f, dtype=torch.float32, device=self.device)
-            dbeta = torch.empty(f, dtype=torch.float32, device=self.device)
-            ws_bytes = int(self.lib.pgcn_ln_ws_bytes(n, f))
-            ws = torch.empty(ws_bytes // 8, dtype=torch.float64, device=self.device)
+            ws, ws_bytes, dgamma, dbeta = self._sums_ws(self.lib.pgcn_ln_ws_bytes, n, f, 2)
         _lib.check(self.lib.pgcn_ln_relu_backward_f32(G.data_ptr(), self._ld(G), X.data_ptr(), self._ld(X), n, f, mean.data_ptr(),
                                                       rstd.data_ptr(), gamma.data_ptr(), mask.data_ptr(), float(scale), dX.data_ptr(),
                                                       self._ld(dX), _ptr(dgamma), _ptr(dbeta), _ptr(ws), ws_bytes, self._stream()),
