@@ -22,7 +22,6 @@ What changed underneath:
 """
 from __future__ import annotations
 
-import contextlib
 import getopt
 import math
 import os
@@ -42,7 +41,7 @@ from . import gat as _gat
 from . import ingest as _ingest
 from . import kernels as _kernels
 from . import nodedata as _nodedata
-from . import optim as _optim
+from . import nodeloss as _nodeloss
 from . import partition as _partition
 
 # module-level state, same names as PGAT.py:23-35
@@ -377,63 +376,50 @@ def initiliaze_parameters(model):
 
 def local_loss(logits, labels, n_global):
     """PGAT.py:214-215 split over the ranks: (sum over OWNED rows of nll) / n."""
-    k = _kernel_provider if _kernel_provider is not None else getattr(_engine_current, "k", None)
+    k = _loss_provider()
     if (k is not None and hasattr(k, "nll_rows") and logits.is_cuda and logits.dtype is torch.float32 and logits.shape[1] <= 1024
             and logits.stride(1) == 1 and labels.dtype is torch.int64 and labels.is_contiguous()):
-        return _pgcn._RowNLLSum.apply(logits, labels, k) / n_global          # one-pass HIP kernels
+        return _nodeloss.RowNLLSum.apply(logits, labels, k) / n_global          # one-pass HIP kernels
     picked = logits.gather(1, labels.unsqueeze(1)).squeeze(1)
     return (torch.logsumexp(logits, 1) - picked).sum() / n_global
 
 
-@contextlib.contextmanager
-def pgcn_state():
-    """PGCN's loss, evaluation and statistics functions read PGCN's module state (device, rank, world size, provider): inside this
-    context they read PGAT's.  What was there before comes back on exit."""
-    names = ("device", "myrank", "world_size", "_kernel_provider")
-    saved = [getattr(_pgcn, a) for a in names]
-    k = _kernel_provider if _kernel_provider is not None else getattr(_engine_current, "k", None)
-    _pgcn.device, _pgcn.myrank, _pgcn.world_size, _pgcn._kernel_provider = device, myrank, world_size, k
-    try:
-        yield
-    finally:
-        for a, v in zip(names, saved):
-            setattr(_pgcn, a, v)
+# ---- node classification: nodeloss.py on THIS module's state (provider, world size), read when a binding is called.  The ranks'
+# losses add up, so do their gradients: sum_gradients(model) ----------------------------------------------------------------------
+
+def _loss_provider():
+    return _kernel_provider if _kernel_provider is not None else getattr(_engine_current, "k", None)
 
 
-def masked_loss(logits, labels, split, n_train_global):
-    """PGCN.masked_loss on this module's provider (call ``backward`` inside ``pgcn_state()`` as well: it picks its kernel then)."""
-    with pgcn_state():
-        return _pgcn.masked_loss(logits, labels, split, n_train_global)
+def _masked_kernels(logits, labels, split):
+    return _nodeloss.masked_kernels(_loss_provider(), "single", logits, labels, split)
+
+
+def _masked_bce_kernels(logits, labels_words, split):
+    return _nodeloss.masked_kernels(_loss_provider(), "multilabel", logits, labels_words, split)
+
+
+def masked_loss(logits, labels, split, n_train_global):       # (through PGCN's binding, the provider handed in: one place sees every loss)
+    return _pgcn.masked_loss(logits, labels, split, n_train_global, k=_masked_kernels(logits, labels, split))
 
 
 def masked_bce_loss(logits, labels_words, split, n_train_global):
-    with pgcn_state():
-        return _pgcn.masked_bce_loss(logits, labels_words, split, n_train_global)
+    return _pgcn.masked_bce_loss(logits, labels_words, split, n_train_global, k=_masked_bce_kernels(logits, labels_words, split))
+
+
+def _global_stats(st, C=None):
+    return _nodeloss.global_stats(st, C, world_size, _all_reduce)
 
 
 def evaluate(model, H, labels, split):
-    """PGCN.evaluate for a model of PGAT layers.  Collective."""
-    with pgcn_state():
-        return _pgcn.evaluate(model, H, labels, split)
+    return _nodeloss.evaluate(model, H, labels, split, "single", _masked_kernels, _global_stats)
 
 
 def evaluate_multilabel(model, H, labels_words, split):
-    with pgcn_state():
-        return _pgcn.evaluate_multilabel(model, H, labels_words, split)
+    return _nodeloss.evaluate(model, H, labels_words, split, "multilabel", _masked_bce_kernels, _global_stats)
 
 
-def _global_stats(st):
-    with pgcn_state():
-        return _pgcn._global_stats(st)
-
-
-def _global_stats_multilabel(st, C):
-    with pgcn_state():
-        return _pgcn._global_stats_multilabel(st, C)
-
-
-TASKS = _pgcn.TASKS
-OPTIMIZERS = _pgcn.OPTIMIZERS
+TASKS, OPTIMIZERS = _pgcn.TASKS, _pgcn.OPTIMIZERS
 
 
 def build_classifier(A, fin, classes, nlayers, hidden, K, out_heads=1, dropout=0.0, bias=False, state=None):
@@ -458,9 +444,8 @@ def _train_on_data(A, n, nlayers, features, labels, split, task=None, hidden=Non
     after the update.  ``optimizer="fused"``: optim.FlatAdam, the gradients reduced in place in its arena.  The initial parameters
     are drawn under ``dropout_seed`` on every rank alike (the caller's generator is left as it was), so a run is a function of its
     arguments and not of the number of ranks."""
-    multilabel = task == "multilabel"
-    load = _nodedata.load_multilabel if multilabel else _nodedata.load
-    data = load(features, labels, split, A.part.owned, n, device=device)
+    multilabel, task = task == "multilabel", _nodeloss.TASKS[task or "single"]
+    data = task.load(features, labels, split, A.part.owned, n, device=device)
     K = heads
     hidden = int(8 * K if hidden is None else hidden)
     out_heads = int(1 if out_heads is None else out_heads)
@@ -480,69 +465,40 @@ def _train_on_data(A, n, nlayers, features, labels, split, task=None, hidden=Non
         _pgcn.tune_dense_gemms(A.part.n_local, widths[i], device, m.out_features + 2 * m.heads)
     model = model.to(device)
     initiliaze_parameters(model)
-    fused = None
-    if optimizer == "fused":
-        fused = _optim.FlatAdam(model.parameters(), lr=lr, weight_decay=weight_decay, decoupled=bool(decoupled_decay),
-                                kernels=_kernel_provider if _kernel_provider is not None else A.k)
-    elif decoupled_decay:
-        opt = torch.optim.AdamW(model.parameters(), lr=lr, weight_decay=weight_decay)
-    elif weight_decay:
-        opt = torch.optim.Adam(model.parameters(), lr=lr, weight_decay=weight_decay)
-    else:
-        opt = torch.optim.Adam(model.parameters(), lr=lr)
+    fused, opt = _nodeloss.make_optimizer(model.parameters(), optimizer, lr, weight_decay, bool(decoupled_decay),
+                                          _kernel_provider if _kernel_provider is not None else A.k)
     H, y, s = data.features, data.labels, data.split           # (H needs no gradient)
+    loss_of, evaluate_of = (masked_bce_loss, evaluate_multilabel) if multilabel else (masked_loss, evaluate)
 
     history, best = [], None
     if device.type == "cuda":
         torch.cuda.synchronize(device)
     start = time.time()
-    with pgcn_state():
-        for epoch in range(epochs):
-            model.train()
-            loss, st = (_pgcn.masked_bce_loss if multilabel else _pgcn.masked_loss)(model(H), y, s, n_train)
-            if fused is not None:
-                loss.backward()
-                if world_size > 1:
-                    _reduce_sum(fused.flat_g)                      # (the ranks' SUM: the loss is split over the owned rows)
-                fused.grad_scale = 1.0
-                fused.step()
-            else:
-                opt.zero_grad()
-                loss.backward()
-                sum_gradients(model)
-                opt.step()
-            if state is not None:
-                state.advance()
-            if not (epoch % eval_every == 0 or epoch == epochs - 1):
-                continue
-            if multilabel:
-                ev = _pgcn.evaluate_multilabel(model, H, y, s) if state is not None else _pgcn._global_stats_multilabel(st, data.classes)
-                l, f1 = ev["loss"], ev["micro_f1"]
-                history.append({"epoch": epoch, "loss": l["train"], "train": f1["train"], "val": f1["val"], "test": f1["test"],
-                                "losses": l, "micro_f1": f1, "tp": ev["tp"], "fp": ev["fp"], "fn": ev["fn"], "rows": ev["rows"]})
-                fmt = "Epoch {:05d} | Loss {:.4f} | Train F1 {:.4f} | Val F1 {:.4f} | Test F1 {:.4f}"
-            else:
-                ev = _pgcn.evaluate(model, H, y, s) if state is not None else _pgcn._global_stats(st)
-                l, acc = ev["loss"], ev["acc"]
-                history.append({"epoch": epoch, "loss": l["train"], "train": acc["train"], "val": acc["val"], "test": acc["test"],
-                                "losses": l, "correct": ev["correct"], "rows": ev["rows"]})
-                fmt = "Epoch {:05d} | Loss {:.4f} | Train {:.4f} | Val {:.4f} | Test {:.4f}"
-            h = history[-1]
-            if best is None or h["val"] > best["val"]:             # (the first epoch of the best validation score)
-                best = h
-            if myrank == 0:
-                print(fmt.format(epoch, h["loss"], h["train"], h["val"], h["test"]), flush=True)
+    for epoch in range(epochs):
+        model.train()
+        loss, st = loss_of(model(H), y, s, n_train)
+        if fused is not None:
+            loss.backward()
+            if world_size > 1:
+                _reduce_sum(fused.flat_g)                      # (the ranks' SUM: the loss is split over the owned rows)
+            fused.grad_scale = 1.0
+            fused.step()
+        else:
+            opt.zero_grad()
+            loss.backward()
+            sum_gradients(model)
+            opt.step()
+        if state is not None:
+            state.advance()
+        if epoch % eval_every == 0 or epoch == epochs - 1:
+            ev = evaluate_of(model, H, y, s) if state is not None else _global_stats(st, data.classes)
+            best = _nodeloss.report(task, epoch, ev, history, best, myrank == 0)
     if device.type == "cuda":
         torch.cuda.synchronize(device)
     elapsed = torch.tensor([time.time() - start], device=device)
     if world_size > 1:
         _all_reduce(elapsed, dist.ReduceOp.MAX)
-    if best is None:
-        best = {"epoch": -1, "val": float("nan"), "test": float("nan")}
-    if myrank == 0:
-        print("Elapsed time {:.4f}  ms/epoch: {:.3f}".format(elapsed.item(), 1e3 * elapsed.item() / max(epochs, 1)), flush=True)
-        print(("Best Val F1 {:.4f} at epoch {:05d} | Test F1 {:.4f}" if multilabel else "Best Val {:.4f} at epoch {:05d} | Test {:.4f}")
-              .format(best["val"], best["epoch"], best["test"]), flush=True)
+    best = _nodeloss.close(task, elapsed.item(), epochs, best, myrank == 0)
     model.history, model.best, model.widths = history, best, widths
     return model
 

@@ -38,8 +38,8 @@ from . import dropout as _dropout
 from . import engine as _engine
 from . import ingest as _ingest
 from . import kernels as _kernels
-from . import nodedata as _nodedata
-from . import optim as _optim
+from . import nodedata as _nodedata       # noqa: F401  (tests reach nodedata through this name)
+from . import nodeloss as _nodeloss
 from . import partition as _partition
 
 # module-level state, same names as PGCN.py:23-35
@@ -59,6 +59,7 @@ stats = {}
 
 # new state
 _kernel_provider = None   # tests may inject a checker-backed provider; product uses HipKernels
+_OWN = object()           # default of a loss's provider argument: the one this module's state names
 _partition_cache = {}
 _engine_current = None
 _exchanger = None
@@ -1453,20 +1454,7 @@ def initiliaze_parameters(model):
         o += p.numel()
 
 
-class _RowNLLSum(torch.autograd.Function):
-    """sum_i nll(log_softmax(x_i), y_i) through the one-pass HIP kernels (pgcn_nll_rows_f32 / _backward_f32)."""
-
-    @staticmethod
-    def forward(ctx, logits, labels, kernels):
-        loss_rows, lse = kernels.nll_rows(logits, labels)
-        ctx.k = kernels
-        ctx.save_for_backward(logits, labels, lse)
-        return loss_rows.sum()
-
-    @staticmethod
-    def backward(ctx, g):
-        logits, labels, lse = ctx.saved_tensors
-        return ctx.k.nll_rows_backward(logits, labels, lse, g, 1.0), None, None
+_RowNLLSum = _nodeloss.RowNLLSum
 
 
 def local_loss(logits, labels, n_global):
@@ -1475,7 +1463,7 @@ def local_loss(logits, labels, n_global):
     i.e. each missing row contributes log(f) (quirk Q4, kept for comparable output)."""
     f = logits.shape[1]
     missing = n_global - logits.shape[0]
-    k = _kernel_provider if _kernel_provider is not None else getattr(_engine_current, "k", None)
+    k = _loss_provider()
     if (k is not None and hasattr(k, "nll_rows") and logits.is_cuda and logits.dtype is torch.float32 and f <= 1024
             and logits.stride(1) == 1 and labels.dtype is torch.int64 and labels.is_contiguous()):
         nll_sum = _RowNLLSum.apply(logits, labels, k)
@@ -1487,216 +1475,59 @@ def local_loss(logits, labels, n_global):
     return (nll_sum + missing * math.log(f)) / n_global
 
 
+# ---- node classification: nodeloss.py on THIS module's state (provider, world size), read when a binding is called.  The ranks'
+# losses add up, so do their gradients: average_gradients(model, average=False) ---------------------------------------------------
+
+def _loss_provider():
+    return _kernel_provider if _kernel_provider is not None else getattr(_engine_current, "k", None)
+
+
 def _masked_kernels(logits, labels, split):
-    """The provider whose masked_nll takes these operands, or None (CPU tensors, a provider without the kernel such as the
-    checker-backed one of the tests, another dtype or layout)."""
-    k = _kernel_provider if _kernel_provider is not None else getattr(_engine_current, "k", None)
-    if (k is not None and hasattr(k, "masked_nll") and logits.is_cuda and logits.dim() == 2 and logits.dtype is torch.float32
-            and logits.stride(1) == 1 and labels.dtype is torch.int64 and labels.is_contiguous()
-            and split.dtype is torch.uint8 and split.is_contiguous()):
-        return k
-    return None
+    return _nodeloss.masked_kernels(_loss_provider(), "single", logits, labels, split)
 
 
-def masked_stats_composed(logits, labels, split):
-    """(lse_rows, MaskedStats) from framework operations: the same numbers as pgcn_masked_nll_f32 (row losses in the logits'
-    precision, sums in float64, arg-max = the first of equal maxima, NaN for a label outside [0, C) on a row of a set)."""
-    C = logits.shape[1]
-    lse = torch.logsumexp(logits, 1)
-    valid = (labels >= 0) & (labels < C)
-    picked = logits.gather(1, labels.clamp(0, C - 1).unsqueeze(1)).squeeze(1)
-    nll = torch.where(valid, lse - picked, torch.full((), float("nan"), dtype=logits.dtype, device=logits.device)).double()
-    hit = valid & (logits.argmax(1) == labels)
-    zero = torch.zeros((), dtype=torch.float64, device=logits.device)
-    sets = [split == k for k in range(4)]
-    loss_sum = torch.stack([zero] + [torch.where(m, nll, zero).sum() for m in sets[1:]])
-    correct = torch.stack([torch.zeros((), dtype=torch.int64, device=logits.device)] + [(m & hit).sum() for m in sets[1:]])
-    rows = torch.stack([(m if k else (split == 0) | (split > 3)).sum() for k, m in enumerate(sets)])
-    return lse, _kernels.MaskedStats(loss_sum, correct, rows)
+def _masked_bce_kernels(logits, labels_words, split):
+    return _nodeloss.masked_kernels(_loss_provider(), "multilabel", logits, labels_words, split)
+
+
+masked_stats_composed = _nodeloss.masked_stats_composed
+masked_bce_stats_composed = _nodeloss.masked_bce_stats_composed
+unpack_label_bits = _nodeloss.unpack_label_bits
 
 
 def masked_stats(logits, labels, split):
-    """(lse_rows, MaskedStats) of one pass over the logits: pgcn_masked_nll_f32 where a provider has it, else the composition."""
-    k = _masked_kernels(logits, labels, split)
-    out = k.masked_nll(logits, labels, split) if k is not None else None       # (None: a shape the kernel refuses)
-    return out if out is not None else masked_stats_composed(logits, labels, split)
-
-
-class _MaskedNLL(torch.autograd.Function):
-    """loss_sum[train] * scale through pgcn_masked_nll_f32 / _backward_f32; the record of all three sets rides along."""
-
-    @staticmethod
-    def forward(ctx, logits, labels, split, scale):
-        lse, st = masked_stats(logits, labels, split)
-        ctx.scale = float(scale)
-        ctx.save_for_backward(logits, labels, split, lse)
-        ctx.mark_non_differentiable(st.loss_sum, st.correct, st.rows)
-        return (st.loss_sum[1] * ctx.scale).to(logits.dtype), st.loss_sum, st.correct, st.rows
-
-    @staticmethod
-    def backward(ctx, g, *_):
-        logits, labels, split, lse = ctx.saved_tensors
-        k = _masked_kernels(logits, labels, split)
-        dX = k.masked_nll_backward(logits, labels, split, lse, g, ctx.scale) if k is not None else None
-        if dX is None:
-            onehot = torch.arange(logits.shape[1], device=logits.device).unsqueeze(0) == labels.unsqueeze(1)
-            dX = torch.where((split == 1).unsqueeze(1),
-                             (g.to(logits.dtype) * ctx.scale) * (torch.exp(logits - lse.unsqueeze(1)) - onehot.to(logits.dtype)),
-                             torch.zeros((), dtype=logits.dtype, device=logits.device))
-        return dX, None, None, None
-
-
-def masked_loss(logits, labels, split, n_train_global):
-    """(loss, stats): the cross entropy of the TRAIN rows this rank owns over the global number of train rows -- the ranks'
-    losses add up to the mean over the train set, their gradients to its gradient (``average_gradients(model, average=False)``)
-    -- and the per-set record of the same pass (kernels.MaskedStats: loss sums, correct counts, row counts by split code).
-    ``split``: uint8 per owned row, 0 no set / 1 train / 2 val / 3 test.  No ``missing . log f`` term: that quirk belongs to
-    the synthetic loop (``local_loss``)."""
-    loss, loss_sum, correct, rows = _MaskedNLL.apply(logits, labels, split, 1.0 / float(n_train_global))
-    return loss, _kernels.MaskedStats(loss_sum, correct, rows)
-
-
-def _global_stats(st):
-    """The nine numbers of a record summed over the ranks in one float64 all-reduce (counts are exact below 2^53):
-    {"loss": {set: mean loss}, "acc": {set: accuracy}, "correct": {set: rows predicted right}, "rows": {set: rows}} as Python
-    numbers, sets "train" / "val" / "test"."""
-    nine = torch.cat([st.loss_sum[1:], st.correct[1:].double(), st.rows[1:].double()])
-    if world_size > 1:
-        _all_reduce(nine)
-    v = nine.tolist()
-    out = {"loss": {}, "acc": {}, "correct": {}, "rows": {}}
-    for j, name in enumerate(_nodedata.SPLIT_NAMES[1:]):
-        r = v[6 + j]
-        out["rows"][name], out["correct"][name] = int(r), int(v[3 + j])
-        out["loss"][name] = v[j] / r if r else float("nan")
-        out["acc"][name] = v[3 + j] / r if r else float("nan")
-    return out
-
-
-def evaluate(model, H, labels, split):
-    """One eval-mode forward without autograd, one pass of the masked kernel, one all-reduce: {"loss": {set: mean loss},
-    "acc": {set: accuracy}, "correct": {set: count}, "rows": {set: rows}} over ALL ranks' rows, sets "train" / "val" / "test".
-    Collective."""
-    was_training = model.training
-    model.eval()
-    try:
-        with torch.no_grad():
-            _, st = masked_stats(model(H), labels, split)
-    finally:
-        model.train(was_training)
-    return _global_stats(st)
-
-
-# ---- multi-label tasks: masked binary cross entropy with logits, micro-F1 ---------------------------------------------------------
-
-def _masked_bce_kernels(logits, labels_words, split):
-    """The provider whose masked_bce takes these operands, or None (CPU tensors, a provider without the kernel, another dtype
-    or layout, more than 1024 columns)."""
-    k = _kernel_provider if _kernel_provider is not None else getattr(_engine_current, "k", None)
-    if (k is not None and hasattr(k, "masked_bce") and logits.is_cuda and logits.dim() == 2 and logits.dtype is torch.float32
-            and logits.stride(1) == 1 and labels_words.dtype is torch.int32 and labels_words.is_contiguous()
-            and split.dtype is torch.uint8 and split.is_contiguous()):
-        return k
-    return None
-
-
-def unpack_label_bits(labels_words, C):
-    """bool [n, C] from the packed label words (int32 [n, ceil(C / 32)], nodedata.pack_label_words); bits at or above C are
-    dropped."""
-    shifts = torch.arange(32, dtype=torch.int32, device=labels_words.device)
-    bits = (labels_words.unsqueeze(2) >> shifts) & 1          # (arithmetic shift: the bit that arrives at position 0 is the same)
-    return bits.reshape(labels_words.shape[0], 32 * labels_words.shape[1])[:, :C].bool()
-
-
-def masked_bce_stats_composed(logits, labels_words, split):
-    """kernels.MaskedBCEStats from framework operations: the same numbers as pgcn_masked_bce_f32 (element losses
-    y ? softplus(-x) : softplus(x) with softplus(t) = max(t, 0) + log1p(exp(-|t|)), row sums in the logits' precision, sums
-    over rows in float64; prediction x > 0; selects, so a NaN stays in its own set and rows in no set count for nothing)."""
-    y = unpack_label_bits(labels_words, logits.shape[1])
-    t = torch.where(y, -logits, logits)
-    row = (t.clamp_min(0) + torch.log1p(torch.exp(-logits.abs()))).sum(1).double()
-    pred = logits > 0
-    tp, fp, fn = (pred & y).sum(1), (pred & ~y).sum(1), (~pred & y).sum(1)
-    zero = torch.zeros((), dtype=torch.float64, device=logits.device)
-    izero = torch.zeros((), dtype=torch.int64, device=logits.device)
-    sets = [split == k for k in (1, 2, 3)]
-    loss_sum = torch.stack([zero] + [torch.where(m, row, zero).sum() for m in sets])
-    counts = [torch.stack([izero] + [torch.where(m, c, izero).sum() for m in sets]) for c in (tp, fp, fn)]
-    rows = torch.stack([((split == 0) | (split > 3)).sum()] + [m.sum() for m in sets])
-    return _kernels.MaskedBCEStats(loss_sum, counts[0], counts[1], counts[2], rows)
+    return _nodeloss.masked_stats(logits, labels, split, _masked_kernels(logits, labels, split))
 
 
 def masked_bce_stats(logits, labels_words, split):
-    """kernels.MaskedBCEStats of one pass over the logits: pgcn_masked_bce_f32 where a provider has it, else the composition."""
-    k = _masked_bce_kernels(logits, labels_words, split)
-    out = k.masked_bce(logits, labels_words, split) if k is not None else None       # (None: a shape the kernel refuses)
-    return out if out is not None else masked_bce_stats_composed(logits, labels_words, split)
+    return _nodeloss.masked_bce_stats(logits, labels_words, split, _masked_bce_kernels(logits, labels_words, split))
 
 
-class _MaskedBCE(torch.autograd.Function):
-    """loss_sum[train] * scale through pgcn_masked_bce_f32 / _backward_f32; the record of all three sets rides along."""
-
-    @staticmethod
-    def forward(ctx, logits, labels_words, split, scale):
-        st = masked_bce_stats(logits, labels_words, split)
-        ctx.scale = float(scale)
-        ctx.save_for_backward(logits, labels_words, split)
-        ctx.mark_non_differentiable(*st)
-        return ((st.loss_sum[1] * ctx.scale).to(logits.dtype),) + tuple(st)
-
-    @staticmethod
-    def backward(ctx, g, *_):
-        logits, labels_words, split = ctx.saved_tensors
-        k = _masked_bce_kernels(logits, labels_words, split)
-        dX = k.masked_bce_backward(logits, labels_words, split, g, ctx.scale) if k is not None else None
-        if dX is None:
-            y = unpack_label_bits(labels_words, logits.shape[1]).to(logits.dtype)
-            dX = torch.where((split == 1).unsqueeze(1), (g.to(logits.dtype) * ctx.scale) * (torch.sigmoid(logits) - y),
-                             torch.zeros((), dtype=logits.dtype, device=logits.device))
-        return dX, None, None, None
+def masked_loss(logits, labels, split, n_train_global, k=_OWN):       # (k: the caller's provider, PGAT's; None: the composition)
+    return _nodeloss.masked_loss(logits, labels, split, n_train_global, _masked_kernels(logits, labels, split) if k is _OWN else k)
 
 
-def masked_bce_loss(logits, labels_words, split, n_train_global):
-    """(loss, stats) of a multi-label task: the binary cross entropy with logits of the TRAIN rows this rank owns over
-    ``n_train_global * C`` elements -- the ranks' losses add up to ``BCEWithLogitsLoss(reduction="mean")`` over the global train
-    rows, their gradients to its gradient (``average_gradients(model, average=False)``) -- and the per-set record of the same
-    pass (kernels.MaskedBCEStats).  ``labels_words``: int32 [n_local, ceil(C / 32)] (nodedata.pack_label_words)."""
-    out = _MaskedBCE.apply(logits, labels_words, split, 1.0 / (float(n_train_global) * logits.shape[1]))
-    return out[0], _kernels.MaskedBCEStats(*out[1:])
+def masked_bce_loss(logits, words, split, n_train_global, k=_OWN):
+    return _nodeloss.masked_bce_loss(logits, words, split, n_train_global, _masked_bce_kernels(logits, words, split) if k is _OWN else k)
 
 
-def _global_stats_multilabel(st, C):
-    """The fifteen numbers of a multi-label record summed over the ranks in one float64 all-reduce (counts are exact below
-    2^53): {"loss": {set: mean loss per element}, "micro_f1": {set: 2 tp / (2 tp + fp + fn), NaN when that is 0 / 0},
-    "tp" / "fp" / "fn" / "rows": {set: count}} as Python numbers, sets "train" / "val" / "test"."""
-    v = torch.cat([st.loss_sum[1:], st.tp[1:].double(), st.fp[1:].double(), st.fn[1:].double(), st.rows[1:].double()])
-    if world_size > 1:
-        _all_reduce(v)
-    v = v.tolist()
-    out = {"loss": {}, "micro_f1": {}, "tp": {}, "fp": {}, "fn": {}, "rows": {}}
-    for j, name in enumerate(_nodedata.SPLIT_NAMES[1:]):
-        tp, fp, fn, r = (int(v[3 * q + j]) for q in (1, 2, 3, 4))
-        out["tp"][name], out["fp"][name], out["fn"][name], out["rows"][name] = tp, fp, fn, r
-        out["loss"][name] = v[j] / (r * C) if r else float("nan")
-        out["micro_f1"][name] = 2 * tp / (2 * tp + fp + fn) if 2 * tp + fp + fn else float("nan")
-    return out
+def _global_stats(st, C=None):
+    return _nodeloss.global_stats(st, C, world_size, _all_reduce)
+
+
+_global_stats_multilabel = _global_stats       # (a multi-label record needs its C)
+
+
+def evaluate(model, H, labels, split):
+    return _nodeloss.evaluate(model, H, labels, split, "single", _masked_kernels, _global_stats)
 
 
 def evaluate_multilabel(model, H, labels_words, split):
-    """``evaluate`` for a multi-label task (``evaluate`` itself keeps single-label int64 vectors): one eval-mode forward without
-    autograd, one pass of the masked BCE kernel, one all-reduce; the dictionary of ``_global_stats_multilabel``.  Collective."""
-    was_training = model.training
-    model.eval()
-    try:
-        with torch.no_grad():
-            logits = model(H)
-            st = masked_bce_stats(logits, labels_words, split)
-    finally:
-        model.train(was_training)
-    return _global_stats_multilabel(st, logits.shape[1])
+    return _nodeloss.evaluate(model, H, labels_words, split, "multilabel", _masked_bce_kernels, _global_stats)
 
 
-OPTIMIZERS = ("torch", "fused")       # --optimizer / run(optimizer=...): torch.optim.Adam[W] (the default) or optim.FlatAdam
+TASKS = tuple(_nodeloss.TASKS)         # --task / run(task=...): "single", one class per vertex (the default), or "multilabel"
+OPTIMIZERS = _nodeloss.OPTIMIZERS      # --optimizer / run(optimizer=...): "torch" (the default) or "fused"
 
 
 def _train_on_data(A, n, nlayers, nfeatures, features, labels, split, hidden, epochs, lr, eval_every, dropout, dropout_seed,
@@ -1716,8 +1547,8 @@ def _train_on_data(A, n, nlayers, nfeatures, features, labels, split, hidden, ep
     every layer gets a root weight / a bias (class PGCN; a normalised layer owns no bias) -- parameters like the rest.
     ``norm="node"``: every layer but the last normalises each vertex's product over its own features (no collective, no buffers).
     ``residual``: every layer but the last whose two widths are equal adds its input to its output (class PGCN)."""
-    load = _nodedata.load_multilabel if multilabel else _nodedata.load
-    data = load(features, labels, split, A.part.owned, n, device=device)
+    task = _nodeloss.TASKS["multilabel" if multilabel else "single"]
+    data = task.load(features, labels, split, A.part.owned, n, device=device)
     hidden = int(nfeatures if hidden is None else hidden)
     epochs = int(4 if epochs is None else epochs)
     lr = float(1e-3 if lr is None else lr)
@@ -1736,16 +1567,9 @@ def _train_on_data(A, n, nlayers, nfeatures, features, labels, split, hidden, ep
                                  **extra, **({"residual": True} if residual and i < nlayers - 1 and widths[i] == widths[i + 1] else {}))
                             for i in range(nlayers)]).to(device)
     initiliaze_parameters(model)
-    fused = None
-    if optimizer == "fused":
-        fused = _optim.FlatAdam(model.parameters(), lr=lr, weight_decay=weight_decay, decoupled=decoupled_decay)
-    elif decoupled_decay:
-        opt = torch.optim.AdamW(model.parameters(), lr=lr, weight_decay=weight_decay)
-    elif weight_decay:
-        opt = torch.optim.Adam(model.parameters(), lr=lr, weight_decay=weight_decay)
-    else:
-        opt = torch.optim.Adam(model.parameters(), lr=lr)
+    fused, opt = _nodeloss.make_optimizer(model.parameters(), optimizer, lr, weight_decay, decoupled_decay)
     H, y, s = data.features, data.labels, data.split           # (H needs no gradient)
+    loss_of, evaluate_of = (masked_bce_loss, evaluate_multilabel) if multilabel else (masked_loss, evaluate)
 
     history, best = [], None
     if device.type == "cuda":
@@ -1753,7 +1577,7 @@ def _train_on_data(A, n, nlayers, nfeatures, features, labels, split, hidden, ep
     start = time.time()
     for epoch in range(epochs):
         model.train()
-        loss, st = (masked_bce_loss if multilabel else masked_loss)(model(H), y, s, n_train)
+        loss, st = loss_of(model(H), y, s, n_train)
         if fused is not None:
             loss.backward()
             fused.reduce_gradients(average=False)
@@ -1765,43 +1589,18 @@ def _train_on_data(A, n, nlayers, nfeatures, features, labels, split, hidden, ep
             opt.step()
         if state is not None:
             state.advance()
-        if multilabel and (epoch % eval_every == 0 or epoch == epochs - 1):
-            ev = evaluate_multilabel(model, H, y, s) if state is not None else _global_stats_multilabel(st, data.classes)
-            l, f1 = ev["loss"], ev["micro_f1"]
-            history.append({"epoch": epoch, "loss": l["train"], "train": f1["train"], "val": f1["val"], "test": f1["test"],
-                            "losses": l, "micro_f1": f1, "tp": ev["tp"], "fp": ev["fp"], "fn": ev["fn"], "rows": ev["rows"]})
-            if best is None or f1["val"] > best["val"]:            # (the first epoch of the best validation micro-F1)
-                best = history[-1]
-            if myrank == 0:
-                print("Epoch {:05d} | Loss {:.4f} | Train F1 {:.4f} | Val F1 {:.4f} | Test F1 {:.4f}".format(
-                    epoch, l["train"], f1["train"], f1["val"], f1["test"]), flush=True)
-        elif epoch % eval_every == 0 or epoch == epochs - 1:
-            ev = evaluate(model, H, y, s) if state is not None else _global_stats(st)
-            l, acc = ev["loss"], ev["acc"]
-            history.append({"epoch": epoch, "loss": l["train"], "train": acc["train"], "val": acc["val"], "test": acc["test"],
-                            "losses": l, "correct": ev["correct"], "rows": ev["rows"]})
-            if best is None or acc["val"] > best["val"]:           # (the first epoch of the best validation accuracy)
-                best = history[-1]
-            if myrank == 0:
-                print("Epoch {:05d} | Loss {:.4f} | Train {:.4f} | Val {:.4f} | Test {:.4f}".format(
-                    epoch, l["train"], acc["train"], acc["val"], acc["test"]), flush=True)
+        if epoch % eval_every == 0 or epoch == epochs - 1:
+            ev = evaluate_of(model, H, y, s) if state is not None else _global_stats(st, data.classes)
+            best = _nodeloss.report(task, epoch, ev, history, best, myrank == 0)
     if device.type == "cuda":
         torch.cuda.synchronize(device)
     elapsed = torch.tensor([time.time() - start], device=device)
     if world_size > 1:
         _all_reduce(elapsed, dist.ReduceOp.MAX)
     _sync_stats(A)
-    if best is None:
-        best = {"epoch": -1, "val": float("nan"), "test": float("nan")}
-    if myrank == 0:
-        print("Elapsed time {:.4f}  ms/epoch: {:.3f}".format(elapsed.item(), 1e3 * elapsed.item() / max(epochs, 1)), flush=True)
-        print(("Best Val F1 {:.4f} at epoch {:05d} | Test F1 {:.4f}" if multilabel else "Best Val {:.4f} at epoch {:05d} | Test {:.4f}")
-              .format(best["val"], best["epoch"], best["test"]), flush=True)
+    best = _nodeloss.close(task, elapsed.item(), epochs, best, myrank == 0)
     model.history, model.best, model.widths = history, best, widths
     return model
-
-
-TASKS = ("single", "multilabel")       # --task / run(task=...): one class per vertex (the default) or a 0 / 1 label matrix
 
 
 def run(rank, size, nlayers, nfeatures, path_A, path_partvec, backend, normalize=None, dropout=0.0, dropout_seed=0,
@@ -1860,7 +1659,7 @@ def run(rank, size, nlayers, nfeatures, path_A, path_partvec, backend, normalize
 
     partvec = _partition.read_partvec(path_partvec)       # first line: n part ids (PGCN.py:172-173); .gz accepted
     if all(given):         # reads the files alone: every rank raises alike, before any collective
-        (_nodedata.open_checked_multilabel if multilabel else _nodedata.open_checked)(features, labels, split, len(partvec))
+        _nodeloss.TASKS[task or "single"].open_checked(features, labels, split, len(partvec))
     _partition_cache.clear()
     if _ingest.is_shard_prefix(path_A, rank):
         # binary CSR shards written ahead of time (ingest.write_shards / tools/make_shards.py): this rank reads

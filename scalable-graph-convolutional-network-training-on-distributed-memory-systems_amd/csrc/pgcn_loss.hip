@@ -12,18 +12,18 @@
 // 1 train, 2 val, 3 test).  ONE pass over the logits leaves lse_i for every row and, per set, the sum of the row losses, the
 // number of rows whose arg-max (lowest index among equal maxima) is the label, and the number of rows: the training loss and the
 // three accuracies of a step without logits[mask] (a host synchronisation), without an argmax / eq / sum chain per set.  A block
-// owns 64 consecutive rows and writes one partial record; a second, one-block launch adds the records in block order -- no
-// floating-point atomics, two calls give the same bits.  4 C + 9 bytes per row forward; the backward writes g (softmax - onehot)
+// owns 64 consecutive rows and writes one partial record; a second, one-block launch adds the records (pgcn_setrecord.h: the
+// record, the fixed order of its sums and what that promises).  4 C + 9 bytes per row forward; the backward writes g (softmax - onehot)
 // on train rows and zeros elsewhere, and reads the logits of train rows only.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
 
 #include "pgcn_internal.h"
+#include "pgcn_setrecord.h"
 
 namespace {
 
-constexpr int kThreads = 256;
 constexpr int kMaxPerLane = 16;
 
 __device__ __forceinline__ float wsum(float v) {
@@ -155,37 +155,14 @@ __global__ __launch_bounds__(kThreads) void nll_rows_backward_v4_kernel(const fl
 }
 
 // ---- masked loss + accuracy ------------------------------------------------------------------------------------------------------
-constexpr int kMaskedRows = 64;          // rows per block of the forward: one partial record per 64 rows
-constexpr int kStatWords = 12;           // pgcn_masked_nll_stats: double loss_sum[4], int64 correct[4], int64 rows[4]
+using NllRecord = SetRecord<1>;          // pgcn_masked_nll_stats: double loss_sum[4], int64 correct[4], int64 rows[4]
+static_assert(sizeof(pgcn_masked_nll_stats) == NllRecord::kWords * sizeof(unsigned long long), "record layout");
 constexpr int kNoColumn = 0x7fffffff;
 
-// what one lane has seen of the rows it leads (slot 0 = rows in no set: counted, nothing else)
-struct SetAcc {
-    double loss[3];
-    int correct[3];
-    int rows[4];
-    __device__ __forceinline__ void clear() {
-        loss[0] = loss[1] = loss[2] = 0.0;
-        correct[0] = correct[1] = correct[2] = 0;
-        rows[0] = rows[1] = rows[2] = rows[3] = 0;
-    }
-    // selects, not products: a NaN row loss reaches its own set only
-    __device__ __forceinline__ void add(int k, float nll, bool hit) {
-#pragma unroll
-        for (int s = 0; s < 3; ++s) {
-            loss[s] += (k == s + 1) ? (double)nll : 0.0;
-            correct[s] += (k == s + 1 && hit) ? 1 : 0;
-        }
-#pragma unroll
-        for (int s = 0; s < 4; ++s) rows[s] += (k == s) ? 1 : 0;
-    }
-};
-
 // the row's part of the statistics, by the lane that leads the row.  Labels of rows in no set are not read.
-__device__ __forceinline__ void masked_row(SetAcc &acc, const float *__restrict__ X, int64_t ldx, const int64_t *__restrict__ labels,
+__device__ __forceinline__ void masked_row(NllRecord &acc, const float *__restrict__ X, int64_t ldx, const int64_t *__restrict__ labels,
                                            const uint8_t *__restrict__ split, int64_t i, int32_t f, float l, int best) {
-    const int s = split[i];
-    const int k = s <= 3 ? s : 0;
+    const int k = split_code(split, i);
     float nll = 0.f;
     bool hit = false;
     if (k != 0) {
@@ -195,52 +172,8 @@ __device__ __forceinline__ void masked_row(SetAcc &acc, const float *__restrict_
         nll = valid ? l - X[i * ldx + y] : __builtin_nanf("");
         hit = valid && (int64_t)best == y;
     }
-    acc.add(k, nll, hit);
-}
-
-// butterfly over the wave, then the block's four waves in order: one record per block, fixed order
-__device__ __forceinline__ void masked_block_store(SetAcc &acc, unsigned long long *__restrict__ part) {
-    __shared__ double s_loss[kThreads / 64][3];
-    __shared__ int s_cnt[kThreads / 64][7];
-    for (int o = 32; o > 0; o >>= 1) {
-#pragma unroll
-        for (int s = 0; s < 3; ++s) {
-            acc.loss[s] += __shfl_xor(acc.loss[s], o, 64);
-            acc.correct[s] += __shfl_xor(acc.correct[s], o, 64);
-        }
-#pragma unroll
-        for (int s = 0; s < 4; ++s) acc.rows[s] += __shfl_xor(acc.rows[s], o, 64);
-    }
-    const int w = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) {
-        for (int s = 0; s < 3; ++s) {
-            s_loss[w][s] = acc.loss[s];
-            s_cnt[w][s] = acc.correct[s];
-        }
-        for (int s = 0; s < 4; ++s) s_cnt[w][3 + s] = acc.rows[s];
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double *pl = reinterpret_cast<double *>(part + (size_t)blockIdx.x * kStatWords);
-        long long *pc = reinterpret_cast<long long *>(part + (size_t)blockIdx.x * kStatWords) + 4;
-        pl[0] = 0.0;
-        pc[0] = 0;
-        for (int s = 0; s < 3; ++s) {
-            double a = s_loss[0][s];
-            long long c = s_cnt[0][s];
-            for (int v = 1; v < kThreads / 64; ++v) {
-                a += s_loss[v][s];
-                c += s_cnt[v][s];
-            }
-            pl[1 + s] = a;
-            pc[1 + s] = c;
-        }
-        for (int s = 0; s < 4; ++s) {
-            long long c = s_cnt[0][3 + s];
-            for (int v = 1; v < kThreads / 64; ++v) c += s_cnt[v][3 + s];
-            pc[4 + s] = c;
-        }
-    }
+    const int c[1] = {hit ? 1 : 0};
+    acc.add(k, nll, c);
 }
 
 // general widths: a wave owns a row (lane j takes columns j, j + 64, ...; Q of them), 4 rows per step, 16 steps per block
@@ -250,11 +183,11 @@ __global__ __launch_bounds__(kThreads) void masked_nll_kernel(const float *__res
                                                               const uint8_t *__restrict__ split, int64_t nrows, int32_t f,
                                                               float *__restrict__ lse, unsigned long long *__restrict__ part) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    SetAcc acc;
+    NllRecord acc;
     acc.clear();
 #pragma unroll 4
-    for (int it = 0; it < kMaskedRows / 4; ++it) {
-        const int64_t i = (int64_t)blockIdx.x * kMaskedRows + it * 4 + wave;
+    for (int it = 0; it < kSetRows / 4; ++it) {
+        const int64_t i = (int64_t)blockIdx.x * kSetRows + it * 4 + wave;
         if (i >= nrows) break;                            // (wave-uniform)
         const float *x = X + i * ldx;
         float v[Q];
@@ -283,7 +216,7 @@ __global__ __launch_bounds__(kThreads) void masked_nll_kernel(const float *__res
             masked_row(acc, X, ldx, labels, split, i, f, l, best);
         }
     }
-    masked_block_store(acc, part);
+    acc.block_store(part);
 }
 
 // f % 4 == 0, f <= 256, 16-byte aligned rows: 16 lanes own a row (CH float4 chunks each), 16 rows per step, 4 steps per block
@@ -294,11 +227,11 @@ __global__ __launch_bounds__(kThreads) void masked_nll_v4_kernel(const float *__
                                                                  float *__restrict__ lse, unsigned long long *__restrict__ part) {
     const int lane = threadIdx.x & 63, sub = lane & 15;
     const int nch = f >> 2;
-    SetAcc acc;
+    NllRecord acc;
     acc.clear();
 #pragma unroll
-    for (int it = 0; it < kMaskedRows / 16; ++it) {
-        const int64_t i = (int64_t)blockIdx.x * kMaskedRows + it * 16 + (threadIdx.x >> 6) * 4 + (lane >> 4);
+    for (int it = 0; it < kSetRows / 16; ++it) {
+        const int64_t i = (int64_t)blockIdx.x * kSetRows + it * 16 + (threadIdx.x >> 6) * 4 + (lane >> 4);
         const bool act = i < nrows;
         const float4 *x4 = reinterpret_cast<const float4 *>(X + (act ? i : 0) * ldx);
         float4 v[CH];
@@ -335,55 +268,7 @@ __global__ __launch_bounds__(kThreads) void masked_nll_v4_kernel(const float *__
             masked_row(acc, X, ldx, labels, split, i, f, l, best);
         }
     }
-    masked_block_store(acc, part);
-}
-
-// one block: thread t adds records t, t + 256, ... in that order, then the same butterfly / wave order as above
-__global__ __launch_bounds__(kThreads) void masked_nll_finalize_kernel(const unsigned long long *__restrict__ part, int64_t nblocks,
-                                                                       unsigned long long *__restrict__ stats) {
-    __shared__ double s_loss[kThreads / 64][3];
-    __shared__ long long s_cnt[kThreads / 64][7];
-    double loss[3] = {0.0, 0.0, 0.0};
-    long long cnt[7] = {0, 0, 0, 0, 0, 0, 0};
-    for (int64_t b = threadIdx.x; b < nblocks; b += kThreads) {
-        const double *pl = reinterpret_cast<const double *>(part + b * kStatWords);
-        const long long *pc = reinterpret_cast<const long long *>(part + b * kStatWords) + 4;
-#pragma unroll
-        for (int s = 0; s < 3; ++s) {
-            loss[s] += pl[1 + s];
-            cnt[s] += pc[1 + s];
-        }
-#pragma unroll
-        for (int s = 0; s < 4; ++s) cnt[3 + s] += pc[4 + s];
-    }
-    for (int o = 32; o > 0; o >>= 1) {
-#pragma unroll
-        for (int s = 0; s < 3; ++s) loss[s] += __shfl_xor(loss[s], o, 64);
-#pragma unroll
-        for (int s = 0; s < 7; ++s) cnt[s] += __shfl_xor(cnt[s], o, 64);
-    }
-    const int w = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) {
-        for (int s = 0; s < 3; ++s) s_loss[w][s] = loss[s];
-        for (int s = 0; s < 7; ++s) s_cnt[w][s] = cnt[s];
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double *ol = reinterpret_cast<double *>(stats);
-        long long *oc = reinterpret_cast<long long *>(stats) + 4;
-        ol[0] = 0.0;
-        oc[0] = 0;
-        for (int s = 0; s < 3; ++s) {
-            double a = s_loss[0][s];
-            for (int v = 1; v < kThreads / 64; ++v) a += s_loss[v][s];
-            ol[1 + s] = a;
-        }
-        for (int s = 0; s < 7; ++s) {
-            long long c = s_cnt[0][s];
-            for (int v = 1; v < kThreads / 64; ++v) c += s_cnt[v][s];
-            oc[1 + s] = c;                                // correct[1..3], then rows[0..3]
-        }
-    }
+    acc.block_store(part);
 }
 
 __global__ __launch_bounds__(kThreads) void masked_nll_backward_kernel(const float *__restrict__ X, int64_t ldx,
@@ -483,24 +368,19 @@ extern "C" int pgcn_nll_rows_backward_f32(const float *X, int64_t ldx, const int
     return PGCN_OK;
 }
 
-extern "C" int64_t pgcn_masked_nll_ws_bytes(int64_t nrows) {
-    const int64_t blocks = nrows > 0 ? (nrows + kMaskedRows - 1) / kMaskedRows : 1;
-    return blocks * kStatWords * (int64_t)sizeof(unsigned long long);
-}
+extern "C" int64_t pgcn_masked_nll_ws_bytes(int64_t nrows) { return set_ws_bytes<1>(nrows); }
 
 extern "C" int pgcn_masked_nll_f32(const float *X, int64_t ldx, const int64_t *labels, const uint8_t *split, int64_t nrows,
                                    int32_t C, float *lse_rows, pgcn_masked_nll_stats *stats, void *ws, int64_t ws_bytes,
                                    pgcn_stream_t stream) {
     if (nrows < 0 || C <= 0 || ldx < C) return pgcn_set_error(PGCN_EINVAL, "pgcn_masked_nll_f32: bad sizes");
     if (C > 64 * kMaxPerLane) return pgcn_set_error(PGCN_EUNSUPPORTED, "pgcn_masked_nll_f32: more than 1024 columns");
-    if (!stats || (uintptr_t)stats % 8 != 0) return pgcn_set_error(PGCN_EINVAL, "pgcn_masked_nll_f32: stats must be 8-byte aligned");
-    const int64_t blocks = (nrows + kMaskedRows - 1) / kMaskedRows;
-    if (blocks > 0x7fffffffLL) return pgcn_set_error(PGCN_EINVAL, "pgcn_masked_nll_f32: too many rows");
+    int64_t blocks;
+    if (int rc = set_check_record("pgcn_masked_nll_f32", stats, nrows, &blocks)) return rc;
     unsigned long long *part = static_cast<unsigned long long *>(ws);
     if (nrows > 0) {
         if (!X || !labels || !split || !lse_rows) return pgcn_set_error(PGCN_EINVAL, "pgcn_masked_nll_f32: null pointer");
-        if (!ws || (uintptr_t)ws % 8 != 0 || ws_bytes < pgcn_masked_nll_ws_bytes(nrows))
-            return pgcn_set_error(PGCN_EINVAL, "pgcn_masked_nll_f32: work-space too small or not 8-byte aligned");
+        if (int rc = set_check_ws<1>("pgcn_masked_nll_f32", ws, ws_bytes, nrows)) return rc;
         const dim3 grid((unsigned)blocks), block(kThreads);
         hipStream_t st = (hipStream_t)stream;
 #define PGCN_MASKED_LAUNCH(kernel) hipLaunchKernelGGL(kernel, grid, block, 0, st, X, ldx, labels, split, nrows, C, lse_rows, part)
@@ -517,11 +397,7 @@ extern "C" int pgcn_masked_nll_f32(const float *X, int64_t ldx, const int64_t *l
 #undef PGCN_MASKED_LAUNCH
         PGCN_HIP_CHECK(hipGetLastError());
     }
-    // (no rows: the record is still written -- all zeros)
-    hipLaunchKernelGGL(masked_nll_finalize_kernel, dim3(1), dim3(kThreads), 0, (hipStream_t)stream, part, blocks,
-                       reinterpret_cast<unsigned long long *>(stats));
-    PGCN_HIP_CHECK(hipGetLastError());
-    return PGCN_OK;
+    return set_finalize<1>(ws, blocks, stats, stream);
 }
 
 extern "C" int pgcn_masked_nll_backward_f32(const float *X, int64_t ldx, const int64_t *labels, const uint8_t *split,

@@ -188,8 +188,13 @@ class MaskedStats(NamedTuple):
     rows: torch.Tensor          # int64 [4]
 
 
+def set_record_views(record: torch.Tensor, planes: int) -> list:
+    """A per-set record's fields (csrc/pgcn_setrecord.h), all aliasing it: words 0-3 as float64 (loss_sum), the planes, rows."""
+    return [record[0:4].view(torch.float64)] + [record[4 * q:4 * q + 4] for q in range(1, planes + 2)]
+
+
 def masked_stats_views(record: torch.Tensor) -> MaskedStats:
-    return MaskedStats(record[0:4].view(torch.float64), record[4:8], record[8:12])
+    return MaskedStats(*set_record_views(record, 1))
 
 
 class MaskedBCEStats(NamedTuple):
@@ -202,7 +207,11 @@ class MaskedBCEStats(NamedTuple):
 
 
 def masked_bce_stats_views(record: torch.Tensor) -> MaskedBCEStats:
-    return MaskedBCEStats(record[0:4].view(torch.float64), record[4:8], record[8:12], record[12:16], record[16:20])
+    return MaskedBCEStats(*set_record_views(record, 3))
+
+
+def _gscale(g: torch.Tensor) -> torch.Tensor:       # a loss's incoming gradient as the one float32 its backward kernel reads
+    return g.reshape(1).to(torch.float32).contiguous()
 
 
 ROWBAND_MAX_F = 1024     # widest block (output) the row-band layer kernels take (csrc/pgcn_rowband.h, kMaxF: 256 threads x 4 columns)
@@ -1013,16 +1022,21 @@ class HipKernels:
         if X.shape[0] != n:
             raise _lib.PgcnError("nll_rows_backward: %d rows of logits for %d labels" % (X.shape[0], n))
         dX = torch.empty((n, f), dtype=torch.float32, device=self.device)
-        g = gscale.reshape(1).to(torch.float32).contiguous()
+        g = _gscale(gscale)
         _lib.check(self.lib.pgcn_nll_rows_backward_f32(X.data_ptr(), X.stride(0), labels.data_ptr(), lse.data_ptr(),
                                                        g.data_ptr(), scale, n, f, dX.data_ptr(), dX.stride(0),
                                                        self._stream()), "pgcn_nll_rows_backward_f32")
         return dX
 
     @staticmethod
-    def _masked_ok(X: torch.Tensor, labels: torch.Tensor, split: torch.Tensor) -> bool:
+    def _masked_ok(X: torch.Tensor, labels: torch.Tensor, split: torch.Tensor, dtype=torch.int64, dim: Optional[int] = None) -> bool:
         return (X.dim() == 2 and 0 < X.shape[1] <= 1024 and X.stride(1) == 1 and X.dtype is torch.float32 and
-                labels.dtype is torch.int64 and labels.is_contiguous() and split.dtype is torch.uint8 and split.is_contiguous())
+                labels.dtype is dtype and (dim is None or labels.dim() == dim) and labels.is_contiguous() and
+                split.dtype is torch.uint8 and split.is_contiguous())
+
+    def _set_record(self, planes: int, ws_bytes: int):
+        record = torch.empty(4 * (2 + planes), dtype=torch.int64, device=self.device)
+        return record, torch.empty(ws_bytes // 8, dtype=torch.int64, device=self.device)
 
     def masked_nll(self, X: torch.Tensor, labels: torch.Tensor, split: torch.Tensor):
         """(lse_rows, MaskedStats) of pgcn_masked_nll_f32: the per-set loss sums, correct counts and row counts of one pass
@@ -1034,9 +1048,8 @@ class HipKernels:
             raise _lib.PgcnError("masked_nll: %d rows of logits for %d labels, %d split codes" % (n, labels.numel(), split.numel()))
         self._check_dense(X, n, "X")
         lse = torch.empty(n, dtype=torch.float32, device=self.device)
-        record = torch.empty(12, dtype=torch.int64, device=self.device)
         ws_bytes = int(self.lib.pgcn_masked_nll_ws_bytes(n))
-        ws = torch.empty(ws_bytes // 8, dtype=torch.int64, device=self.device)
+        record, ws = self._set_record(1, ws_bytes)
         _lib.check(self.lib.pgcn_masked_nll_f32(X.data_ptr(), X.stride(0), labels.data_ptr(), split.data_ptr(), n, C, lse.data_ptr(),
                                                 record.data_ptr(), ws.data_ptr(), ws_bytes, self._stream()), "pgcn_masked_nll_f32")
         return lse, masked_stats_views(record)
@@ -1050,16 +1063,14 @@ class HipKernels:
         if labels.numel() != n or split.numel() != n or lse.numel() != n:
             raise _lib.PgcnError("masked_nll_backward: %d rows of logits for %d labels" % (n, labels.numel()))
         dX = torch.empty((n, C), dtype=torch.float32, device=self.device)
-        g = gscale.reshape(1).to(torch.float32).contiguous()
+        g = _gscale(gscale)
         _lib.check(self.lib.pgcn_masked_nll_backward_f32(X.data_ptr(), X.stride(0), labels.data_ptr(), split.data_ptr(),
                                                          lse.data_ptr(), g.data_ptr(), scale, n, C, dX.data_ptr(), dX.stride(0),
                                                          self._stream()), "pgcn_masked_nll_backward_f32")
         return dX
 
     def _masked_bce_ok(self, X: torch.Tensor, words: torch.Tensor, split: torch.Tensor) -> bool:
-        return (X.dim() == 2 and 0 < X.shape[1] <= 1024 and X.stride(1) == 1 and X.dtype is torch.float32 and
-                words.dtype is torch.int32 and words.dim() == 2 and words.is_contiguous() and split.dtype is torch.uint8 and
-                split.is_contiguous() and getattr(self.lib, "pgcn_masked_bce_f32", None) is not None)
+        return self._masked_ok(X, words, split, torch.int32, 2) and getattr(self.lib, "pgcn_masked_bce_f32", None) is not None
 
     def masked_bce(self, X: torch.Tensor, labels_words: torch.Tensor, split: torch.Tensor):
         """MaskedBCEStats of pgcn_masked_bce_f32: the per-set sums of the element-wise binary cross entropy with logits, the
@@ -1074,9 +1085,8 @@ class HipKernels:
             raise _lib.PgcnError("masked_bce: %d x %d logits for label words %s, %d split codes"
                                  % (n, C, tuple(labels_words.shape), split.numel()))
         self._check_dense(X, n, "X")
-        record = torch.empty(20, dtype=torch.int64, device=self.device)
         ws_bytes = int(self.lib.pgcn_masked_bce_ws_bytes(n))
-        ws = torch.empty(ws_bytes // 8, dtype=torch.int64, device=self.device)
+        record, ws = self._set_record(3, ws_bytes)
         _lib.check(self.lib.pgcn_masked_bce_f32(X.data_ptr(), X.stride(0), labels_words.data_ptr(), split.data_ptr(), n, C,
                                                 record.data_ptr(), ws.data_ptr(), ws_bytes, self._stream()), "pgcn_masked_bce_f32")
         return masked_bce_stats_views(record)
@@ -1091,7 +1101,7 @@ class HipKernels:
             raise _lib.PgcnError("masked_bce_backward: %d x %d logits for label words %s, %d split codes"
                                  % (n, C, tuple(labels_words.shape), split.numel()))
         dX = torch.empty((n, C), dtype=torch.float32, device=self.device)
-        g = gscale.reshape(1).to(torch.float32).contiguous()
+        g = _gscale(gscale)
         _lib.check(self.lib.pgcn_masked_bce_backward_f32(X.data_ptr(), X.stride(0), labels_words.data_ptr(), split.data_ptr(),
                                                          g.data_ptr(), scale, n, C, dX.data_ptr(), dX.stride(0),
                                                          self._stream()), "pgcn_masked_bce_backward_f32")

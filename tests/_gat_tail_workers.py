@@ -258,22 +258,21 @@ def grad_worker(rank, P, port, paths, gpu, q, jobs=(), n=None, steps=2):
             for k, prm in model.named_parameters():
                 prm.copy_(torch.from_numpy(job["params"][k]))
         rec = {"tag": tag(o), "own": own, "loss": [], "logits": [], "grads": [], "hip": type(eng.k).__name__}
-        with M.pgcn_state():
-            for s in range(steps):
-                model.train()
-                model.zero_grad()
-                logits = model(data.features)
-                loss, _ = (M._pgcn.masked_bce_loss if multilabel else M._pgcn.masked_loss)(logits, data.labels, data.split, data.counts[1])
-                loss.backward()
-                M.sum_gradients(model)
-                rec["loss"].append(float(loss.detach().double().cpu()))
-                rec["logits"].append(logits.detach().cpu().numpy())
-                rec["grads"].append({k: prm.grad.detach().cpu().numpy().copy() for k, prm in model.named_parameters()})
-                if state is not None:
-                    state.advance()
-            model.eval()
-            with torch.no_grad():
-                rec["eval_logits"] = model(data.features).cpu().numpy()
+        for s in range(steps):
+            model.train()
+            model.zero_grad()
+            logits = model(data.features)
+            loss, _ = (M.masked_bce_loss if multilabel else M.masked_loss)(logits, data.labels, data.split, data.counts[1])
+            loss.backward()
+            M.sum_gradients(model)
+            rec["loss"].append(float(loss.detach().double().cpu()))
+            rec["logits"].append(logits.detach().cpu().numpy())
+            rec["grads"].append({k: prm.grad.detach().cpu().numpy().copy() for k, prm in model.named_parameters()})
+            if state is not None:
+                state.advance()
+        model.eval()
+        with torch.no_grad():
+            rec["eval_logits"] = model(data.features).cpu().numpy()
         results.append(rec)
     if gpu:
         torch.cuda.synchronize()

@@ -286,3 +286,26 @@ def test_run_refuses_task_without_files_or_unknown(dataset):
     with pytest.raises(ValueError, match="task takes"):
         M.run(0, 1, 2, 16, gpath("karate.mtx"), gpath("karate.mtx.1.rp"), "gloo", features=paths["features"], labels=paths["labels"],
               split=paths["split"], task="multiclass")
+
+
+# ---- the per-set record (csrc/pgcn_setrecord.h) -------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("planes,views,fields", [(1, "masked_stats_views", ("loss_sum", "correct", "rows")),
+                                                 (3, "masked_bce_stats_views", ("loss_sum", "tp", "fp", "fn", "rows"))])
+def test_record_views_are_the_fields_in_the_documented_order(planes, views, fields):
+    """double loss_sum[4], then `planes` planes of int64[4], then int64 rows[4]: every view aliases its four words of the record."""
+    k = pkg("kernels")
+    record = torch.arange(100, 100 + 4 * (2 + planes), dtype=torch.int64)       # hand-filled: word w holds 100 + w
+    st = getattr(k, views)(record)
+    assert st._fields == fields and len(k.set_record_views(record, planes)) == planes + 2
+    assert st.loss_sum.dtype is torch.float64 and st.loss_sum.shape == (4,) and st.loss_sum.data_ptr() == record.data_ptr()
+    assert st.loss_sum.view(torch.int64).tolist() == [100, 101, 102, 103]
+    for q in range(1, planes + 2):
+        assert st[q].dtype is torch.int64 and st[q].tolist() == [100 + 4 * q + j for j in range(4)]
+        assert st[q].data_ptr() == record.data_ptr() + 32 * q
+    st.loss_sum[2] = 1.5                                                        # the float64 view aliases words 0-3 ...
+    assert record[2].item() == int(np.float64(1.5).view(np.int64))
+    record[1] = int(np.float64(-2.25).view(np.int64))
+    assert st.loss_sum[1].item() == -2.25
+    st.rows[3] = 7                                                              # ... and the last view the last four
+    assert record[-1].item() == 7

@@ -12,6 +12,9 @@ pytestmark = pytest.mark.gpu
 
 NROWS = [0, 1, 63, 64, 65, 4161]           # 4161 = 65 blocks of 64 rows + 1: the second-level sum sees more than a wave of partials
 COLUMNS = [1, 3, 32, 33, 100, 121, 1024]
+# 16449 = 257 blocks of 64 rows + 1: more partial records than the 256 threads that add them, so a thread takes a second record
+# (the wave-per-row kernel at C = 3, the 16-lanes-per-row kernel at C = 100)
+CASES = [(n, C) for n in NROWS for C in COLUMNS] + [(16449, 3), (16449, 100)]
 # relative to max(1, |float64 sum|): the bound of the loss_sum comparison of tests/test_nodeclass_gpu.py, kept as it is.  Expected error:
 # a row sum of at most 1024 fp32 terms in a fixed tree order (a few 1e-7), rows added in double.  The test prints the kernel's error and
 # that of torch's fp32 binary_cross_entropy_with_logits(reduction="sum") on the same inputs before it asserts.
@@ -94,8 +97,7 @@ def _check_backward(K, dev, xt, words, st_, x, y, s):
     return dx
 
 
-@pytest.mark.parametrize("C", COLUMNS)
-@pytest.mark.parametrize("n", NROWS)
+@pytest.mark.parametrize("n,C", CASES)
 def test_kernels_against_float64(K, dev, n, C):
     x, y, s = _host_case(n, C)
     xt, words, st_ = _device_case(dev, x, y, s)
