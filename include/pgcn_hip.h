@@ -696,6 +696,27 @@ int pgcn_ln_relu_backward_f32(const float *G, int64_t ldg, const float *X, int64
                               const float *rstd, const float *gamma, const int32_t *mask, float scale, float *dX, int64_t lddx,
                               float *dgamma, float *dbeta, void *ws, int64_t ws_bytes, pgcn_stream_t stream);
 
+/* ---- from logits to predictions (checkpoint.py: write_predictions; --predict) -----------------------------------------------------
+ * One pass over an nrows x C block of logits of OWNED rows leaves what a user stores.  Row-local: a row's outputs depend on that row
+ * alone -- not on its position, the block that met it, nrows or the rank.  No atomics, no work-space: the same input gives the same bits.
+ * task == 0, one class per row:  m_i = max_j X[i,j] (fmaxf: a NaN is dropped);  cls[i] = the lowest j with X[i,j] == m_i -- the first
+ *   of equal maxima, the arg-max that pgcn_masked_nll_f32 counts as a hit when it is the label, on every row, a row that holds NaN
+ *   included (a row of NaN only has no such j: cls[i] = -1, which no label equals);  e_ij = expf(X[i,j] - m_i);  s_i = sum_j e_ij in
+ *   fp32 -- a thread adds its four columns in a fixed order, then a fixed tree of depth <= log2(TPR) + 1 over the TPR threads of the
+ *   row;  conf[i] = 1 / s_i, the softmax probability of class cls[i];  prob[i,j] = e_ij / s_i.  A row that holds a NaN, or whose
+ *   maximum is infinite, has NaN in conf and prob (like torch.softmax); its cls is as stated.  bits is not touched.
+ * task == 1, multi-label:  bit (c % 32) of bits[i * ceil(C / 32) + c / 32] is X[i,c] > 0 -- the prediction of pgcn_masked_bce_f32 (a
+ *   NaN and both zeros are not > 0); bits at and above C are 0; the words are contiguous, the layout of the packed label words that
+ *   pgcn_masked_bce_f32 reads.  prob[i,c] = 1 / (1 + expf(-X[i,c])).  cls and conf are not touched.
+ * Every output pointer may be NULL: that output is not formed (none left: nothing is launched).  Row-major with leading dimensions
+ * in elements (ldx for X, ldp for prob; cls, conf and bits are contiguous), 64-bit row offsets; every C from 1 to 1024; a thread owns
+ * four consecutive columns -- one float4 when C % 4 == 0 and X and prob keep their rows 16-byte aligned, four guarded scalars
+ * otherwise, the same bits either way.  One launch; nrows == 0: none.  PGCN_EINVAL, nothing launched, no HIP call made: nrows < 0,
+ * C < 1, C > 1024, ldx < C, prob with ldp < C, another task, X NULL with nrows > 0, cls not 8-byte or another pointer not 4-byte
+ * aligned.  Raw pointers + a stream, no allocation, no synchronisation (graph-capturable).                                          */
+int pgcn_predict_f32(const float *X, int64_t ldx, int64_t nrows, int32_t C, int32_t task, int64_t *cls, float *conf, uint32_t *bits,
+                     float *prob, int64_t ldp, pgcn_stream_t stream);
+
 /* ---- boundary-row pack / unpack -------------------------------------------
  * out[r,:] = H[idx[r],:]                      replaces H[indices]   GPU/PGCN.py:104
  * H[idx[r],:] (+)= in[r,:]                    replaces X[indices] = buf   :115

@@ -35,6 +35,7 @@ import torch.multiprocessing as mp
 import torch.nn as nn
 
 from . import PGCN as _pgcn
+from . import checkpoint as _checkpoint
 from . import dropout as _dropout
 from . import engine as _engine
 from . import gat as _gat
@@ -419,6 +420,30 @@ def evaluate_multilabel(model, H, labels_words, split):
     return _nodeloss.evaluate(model, H, labels_words, split, "multilabel", _masked_bce_kernels, _global_stats)
 
 
+def predict(model, H, task, want_conf=True, want_prob=False):
+    """kernels.Prediction of the owned rows ``H``: one eval-mode forward without autograd, one pass of pgcn_predict_f32 on this
+    module's provider (the composition where it takes none).  ``task``: "single" | "multilabel"."""
+    return _nodeloss.predict(model, H, task, lambda logits: _nodeloss.predict_kernels(_loss_provider(), logits), want_conf, want_prob)
+
+
+_predict = predict        # (inside _train_on_data ``predict`` is the argument: the files' prefix)
+
+
+def _barrier():
+    """Every rank has arrived (and its host waits for it): one tiny all-reduce."""
+    if world_size > 1:
+        _all_reduce(torch.zeros(1, device=device)).item()
+
+
+def _architecture(fin, classes, nlayers, task=None, hidden=None, out_heads=None, dropout=0.0, dropout_seed=0, bias=None, **_):
+    """checkpoint.architecture of the model ``_train_on_data`` builds from these arguments (and this module's ``heads``)."""
+    widths = [int(fin)] + [int(8 * heads if hidden is None else hidden)] * (nlayers - 1) + [int(classes)]
+    # (the initial parameters are drawn under dropout_seed, with or without dropout: the record keeps it in the dropout case only,
+    # where it also seeds the masks -- a resumed run draws no initial parameters)
+    return _checkpoint.architecture(widths, task, dropout, dropout_seed, bias=bias, heads=heads,
+                                    out_heads=1 if out_heads is None else out_heads)
+
+
 TASKS, OPTIMIZERS = _pgcn.TASKS, _pgcn.OPTIMIZERS
 
 
@@ -437,13 +462,16 @@ def build_classifier(A, fin, classes, nlayers, hidden, K, out_heads=1, dropout=0
 
 
 def _train_on_data(A, n, nlayers, features, labels, split, task=None, hidden=None, out_heads=None, epochs=None, lr=None,
-                   eval_every=None, dropout=0.0, dropout_seed=0, bias=None, weight_decay=None, decoupled_decay=None, optimizer=None):
+                   eval_every=None, dropout=0.0, dropout_seed=0, bias=None, weight_decay=None, decoupled_decay=None, optimizer=None,
+                   save=None, load=None, predict=None, proba=None):
     """The loop of ``run`` on real inputs, the scheme of PGCN._train_on_data: constant features, Adam, the masked loss over the train
     rows (``task="multilabel"``: the masked binary cross entropy and micro-F1).  Reports every ``eval_every`` epochs: without
     dropout from the record of the training step's own pass (the logits BEFORE that step's update), with dropout from ``evaluate``
     after the update.  ``optimizer="fused"``: optim.FlatAdam, the gradients reduced in place in its arena.  The initial parameters
     are drawn under ``dropout_seed`` on every rank alike (the caller's generator is left as it was), so a run is a function of its
-    arguments and not of the number of ranks."""
+    arguments and not of the number of ranks.  ``save`` / ``load`` / ``predict`` / ``proba``: checkpoint.py (``Hooks``), as in
+    PGCN._train_on_data -- ``epochs`` MORE epochs follow a loaded checkpoint, numbered from its count on."""
+    kind = task or "single"
     multilabel, task = task == "multilabel", _nodeloss.TASKS[task or "single"]
     data = task.load(features, labels, split, A.part.owned, n, device=device)
     K = heads
@@ -470,12 +498,19 @@ def _train_on_data(A, n, nlayers, features, labels, split, task=None, hidden=Non
     H, y, s = data.features, data.labels, data.split           # (H needs no gradient)
     loss_of, evaluate_of = (masked_bce_loss, evaluate_multilabel) if multilabel else (masked_loss, evaluate)
 
-    history, best = [], None
+    first, history, best, hooks = 0, [], None, None
+    if save is not None or load is not None or predict is not None or proba:
+        arch = _architecture(data.fin, data.classes, nlayers, kind, hidden, out_heads, dropout, dropout_seed, bias)
+        hooks = _checkpoint.Hooks("PGAT", arch, model, fused, opt, state, save, load, predict, proba, myrank, _barrier)
+        first, history, best = hooks.resume()
+    last = first + epochs - 1
     if device.type == "cuda":
         torch.cuda.synchronize(device)
     start = time.time()
-    for epoch in range(epochs):
+    for epoch in range(first, first + epochs):
         model.train()
+        if hooks is not None and state is None and (epoch % eval_every == 0 or epoch == last):
+            hooks.stage()
         loss, st = loss_of(model(H), y, s, n_train)
         if fused is not None:
             loss.backward()
@@ -490,14 +525,20 @@ def _train_on_data(A, n, nlayers, features, labels, split, task=None, hidden=Non
             opt.step()
         if state is not None:
             state.advance()
-        if epoch % eval_every == 0 or epoch == epochs - 1:
+        if epoch % eval_every == 0 or epoch == last:
             ev = evaluate_of(model, H, y, s) if state is not None else _global_stats(st, data.classes)
             best = _nodeloss.report(task, epoch, ev, history, best, myrank == 0)
+            if hooks is not None:
+                hooks.reported(best, history[-1])
     if device.type == "cuda":
         torch.cuda.synchronize(device)
     elapsed = torch.tensor([time.time() - start], device=device)
     if world_size > 1:
         _all_reduce(elapsed, dist.ReduceOp.MAX)
+    if hooks is not None:
+        hooks.finish(first + epochs, history, best,
+                     lambda want_prob: (_predict(model, H, kind, True, want_prob), A.part.owned, n, data.classes))
+        model.best_state = hooks.best_state
     best = _nodeloss.close(task, elapsed.item(), epochs, best, myrank == 0)
     model.history, model.best, model.widths = history, best, widths
     return model
@@ -506,8 +547,8 @@ def _train_on_data(A, n, nlayers, features, labels, split, task=None, hidden=Non
 def run(rank, size, nlayers, nfeatures, path_A, path_partvec, backend, epochs=None, features=None, labels=None, split=None, **data):
     """PGAT.py:165-233.  ``features`` / ``labels`` / ``split`` (.npy files in global vertex order, nodedata.py; all three or none):
     train the classifier of ``build_classifier`` on them instead of the synthetic loop (``_train_on_data`` takes the other keyword
-    arguments: task, hidden, out_heads, lr, eval_every, dropout, dropout_seed, bias, weight_decay, decoupled_decay, optimizer); the
-    returned model carries ``history``, ``best`` and ``widths``."""
+    arguments: task, hidden, out_heads, lr, eval_every, dropout, dropout_seed, bias, weight_decay, decoupled_decay, optimizer, and
+    save, load, predict, proba -- checkpoint.py, as in PGCN.run); the returned model carries ``history``, ``best`` and ``widths``."""
     global myrank, world_size, send_map, recv_map, device, X, recv_buffers, send_buffers
     files = [v for v in (features, labels, split) if v is not None]
     if len(files) not in (0, 3) or (data and not files):
@@ -516,6 +557,8 @@ def run(rank, size, nlayers, nfeatures, path_A, path_partvec, backend, epochs=No
         raise ValueError("task takes %s, got %r" % (" | ".join(TASKS), data.get("task")))
     if data.get("optimizer") not in (None,) + OPTIMIZERS:
         raise ValueError("optimizer takes %s, got %r" % (" | ".join(OPTIMIZERS), data.get("optimizer")))
+    if data.get("proba") and data.get("predict") is None:
+        raise ValueError("proba needs predict")
     if files and mode == "reference":
         raise ValueError("the reference layer has no bias, activation, head mean or dropout: train on data in standard mode")
     myrank = rank
@@ -533,6 +576,11 @@ def run(rank, size, nlayers, nfeatures, path_A, path_partvec, backend, epochs=No
     with open(path_partvec) as f:
         partvec = list(map(int, f.readline().split()))
     n = A.shape[0]
+    if files and data.get("load") is not None:       # reads the files alone: every rank raises alike, before any collective
+        opened = _nodeloss.TASKS[data.get("task") or "single"].open_checked(features, labels, split, n)
+        data["load"] = _checkpoint.load(data["load"], "PGAT", _architecture(opened[3], opened[4], nlayers, **data),
+                                        data.get("optimizer") or "torch")
+        del opened
 
     send_map, recv_map = compute_communication_maps(A, partvec, rank, size)
     A = get_partitiont_of_adjacency_matrix(A, partvec, rank)
@@ -614,7 +662,8 @@ def main(argv):
     try:
         opts, args = getopt.getopt(argv, "a:p:b:s:l:f:", ["mode=", "heads=", "features=", "labels=", "split=", "task=", "hidden=",
                                                           "out-heads=", "epochs=", "lr=", "eval-every=", "dropout=", "dropout-seed=",
-                                                          "bias", "weight-decay=", "adamw", "optimizer="])
+                                                          "bias", "weight-decay=", "adamw", "optimizer=", "save=", "load=", "predict=",
+                                                          "proba"])
     except getopt.GetoptError:
         print("a:p:b:", flush=True)
         sys.exit(2)
@@ -658,6 +707,10 @@ def main(argv):
             if arg not in OPTIMIZERS:
                 refuse("--optimizer takes %s, got %r" % ("|".join(OPTIMIZERS), arg))
             data["optimizer"] = arg
+        elif opt in ('--save', '--load', '--predict'):      # checkpoint.py: write / resume from a checkpoint; the prediction files' prefix
+            data[opt[2:]] = arg
+        elif opt == '--proba':         # with --predict: <prefix>.prob.npy too
+            data["proba"] = True
         elif opt == '--lr':
             try:
                 data["lr"] = float(arg)
@@ -684,11 +737,15 @@ def main(argv):
     files = [k for k in ("features", "labels", "split") if k in data]
     if data and len(files) != 3:
         refuse("--features, --labels and --split go together (and --task, --hidden, --out-heads, --epochs, --lr, --eval-every, --dropout, "
-               "--dropout-seed, --bias, --weight-decay, --adamw, --optimizer need them); got %s"
+               "--dropout-seed, --bias, --weight-decay, --adamw, --save, --load, --predict, --proba, --optimizer need them); got %s"
                % ", ".join("--" + {"decoupled_decay": "adamw"}.get(k, k.replace("_", "-")) for k in sorted(data)))
     for k in files:
         if not os.path.exists(data[k]):
             refuse("--%s: no such file %r" % (k, data[k]))
+    if data.get("proba") and "predict" not in data:
+        refuse("--proba needs --predict")
+    if "load" in data and not os.path.exists(data["load"]):
+        refuse("--load: no such file %r" % (data["load"],))
     if data and mode == "reference":
         refuse("--mode reference has no bias, activation, head mean or dropout: --features needs --mode standard")
     if data and heads >= 1 and data.get("hidden", 8 * heads) % heads:

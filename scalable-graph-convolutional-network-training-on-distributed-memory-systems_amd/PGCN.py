@@ -34,6 +34,7 @@ import torch.multiprocessing as mp
 import torch.nn as nn
 import torch.nn.functional as F
 
+from . import checkpoint as _checkpoint
 from . import dropout as _dropout
 from . import engine as _engine
 from . import ingest as _ingest
@@ -1526,13 +1527,35 @@ def evaluate_multilabel(model, H, labels_words, split):
     return _nodeloss.evaluate(model, H, labels_words, split, "multilabel", _masked_bce_kernels, _global_stats)
 
 
+def predict(model, H, task, want_conf=True, want_prob=False):
+    """kernels.Prediction of the owned rows ``H``: one eval-mode forward without autograd, one pass of pgcn_predict_f32 on this
+    module's provider (the composition where it takes none).  ``task``: "single" | "multilabel"."""
+    return _nodeloss.predict(model, H, task, lambda logits: _nodeloss.predict_kernels(_loss_provider(), logits), want_conf, want_prob)
+
+
+_predict = predict        # (inside run and _train_on_data ``predict`` is the argument: the files' prefix)
+
+
+def _barrier():
+    """Every rank has arrived (and its host waits for it): one tiny all-reduce through the transport that carries the others."""
+    if world_size > 1:
+        _all_reduce(torch.zeros(1, device=device)).item()
+
+
+def _architecture(fin, classes, nlayers, nfeatures, hidden, multilabel, dropout, dropout_seed, norm, root_weight, bias, residual):
+    """checkpoint.architecture of the model ``_train_on_data`` builds from these arguments."""
+    widths = [int(fin)] + [int(nfeatures if hidden is None else hidden)] * (nlayers - 1) + [int(classes)]
+    return _checkpoint.architecture(widths, "multilabel" if multilabel else "single", dropout, dropout_seed, norm, root_weight, bias,
+                                    residual)
+
+
 TASKS = tuple(_nodeloss.TASKS)         # --task / run(task=...): "single", one class per vertex (the default), or "multilabel"
 OPTIMIZERS = _nodeloss.OPTIMIZERS      # --optimizer / run(optimizer=...): "torch" (the default) or "fused"
 
 
 def _train_on_data(A, n, nlayers, nfeatures, features, labels, split, hidden, epochs, lr, eval_every, dropout, dropout_seed,
                    multilabel=False, weight_decay=0.0, decoupled_decay=False, optimizer="torch", norm=None, root_weight=None, bias=None,
-                   residual=None):
+                   residual=None, save=None, load=None, predict=None, proba=None):
     """The loop of ``run`` on real inputs: widths fin -> hidden -> ... -> C, no ReLU on the last layer, constant features (the
     first layer's backward aggregation is skipped), Adam, the masked loss over the train rows.  Reports every ``eval_every``
     epochs: without dropout from the record of the training step's own pass (the logits BEFORE that step's update), with
@@ -1546,7 +1569,11 @@ def _train_on_data(A, n, nlayers, nfeatures, features, labels, split, hidden, ep
     own (the graph's statistics), with dropout ``evaluate`` runs in eval mode (the running statistics).  ``root_weight`` / ``bias``:
     every layer gets a root weight / a bias (class PGCN; a normalised layer owns no bias) -- parameters like the rest.
     ``norm="node"``: every layer but the last normalises each vertex's product over its own features (no collective, no buffers).
-    ``residual``: every layer but the last whose two widths are equal adds its input to its output (class PGCN)."""
+    ``residual``: every layer but the last whose two widths are equal adds its input to its output (class PGCN).
+    ``save`` / ``load`` / ``predict`` / ``proba``: checkpoint.py (``Hooks``) -- ``load`` (a path, or the dict ``checkpoint.load``
+    read) is applied after the optimiser is built and ``epochs`` MORE epochs follow, numbered from the checkpoint's count on (0:
+    nothing is trained); ``save``: the checkpoint after the loop; ``predict``: the prefix of the prediction files, written from the
+    best epoch's weights (``proba``: the probabilities too).  With none of the four nothing is copied and nothing more printed."""
     task = _nodeloss.TASKS["multilabel" if multilabel else "single"]
     data = task.load(features, labels, split, A.part.owned, n, device=device)
     hidden = int(nfeatures if hidden is None else hidden)
@@ -1571,12 +1598,20 @@ def _train_on_data(A, n, nlayers, nfeatures, features, labels, split, hidden, ep
     H, y, s = data.features, data.labels, data.split           # (H needs no gradient)
     loss_of, evaluate_of = (masked_bce_loss, evaluate_multilabel) if multilabel else (masked_loss, evaluate)
 
-    history, best = [], None
+    first, history, best, hooks = 0, [], None, None
+    if save is not None or load is not None or predict is not None or proba:
+        arch = _architecture(data.fin, data.classes, nlayers, nfeatures, hidden, multilabel, dropout, dropout_seed, norm, root_weight,
+                             bias, residual)
+        hooks = _checkpoint.Hooks("PGCN", arch, model, fused, opt, state, save, load, predict, proba, myrank, _barrier)
+        first, history, best = hooks.resume()
+    last = first + epochs - 1
     if device.type == "cuda":
         torch.cuda.synchronize(device)
     start = time.time()
-    for epoch in range(epochs):
+    for epoch in range(first, first + epochs):
         model.train()
+        if hooks is not None and state is None and (epoch % eval_every == 0 or epoch == last):
+            hooks.stage()
         loss, st = loss_of(model(H), y, s, n_train)
         if fused is not None:
             loss.backward()
@@ -1589,15 +1624,22 @@ def _train_on_data(A, n, nlayers, nfeatures, features, labels, split, hidden, ep
             opt.step()
         if state is not None:
             state.advance()
-        if epoch % eval_every == 0 or epoch == epochs - 1:
+        if epoch % eval_every == 0 or epoch == last:
             ev = evaluate_of(model, H, y, s) if state is not None else _global_stats(st, data.classes)
             best = _nodeloss.report(task, epoch, ev, history, best, myrank == 0)
+            if hooks is not None:
+                hooks.reported(best, history[-1])
     if device.type == "cuda":
         torch.cuda.synchronize(device)
     elapsed = torch.tensor([time.time() - start], device=device)
     if world_size > 1:
         _all_reduce(elapsed, dist.ReduceOp.MAX)
     _sync_stats(A)
+    if hooks is not None:
+        kind = "multilabel" if multilabel else "single"
+        hooks.finish(first + epochs, history, best,
+                     lambda want_prob: (_predict(model, H, kind, True, want_prob), A.part.owned, n, data.classes))
+        model.best_state = hooks.best_state
     best = _nodeloss.close(task, elapsed.item(), epochs, best, myrank == 0)
     model.history, model.best, model.widths = history, best, widths
     return model
@@ -1605,7 +1647,8 @@ def _train_on_data(A, n, nlayers, nfeatures, features, labels, split, hidden, ep
 
 def run(rank, size, nlayers, nfeatures, path_A, path_partvec, backend, normalize=None, dropout=0.0, dropout_seed=0,
         features=None, labels=None, split=None, hidden=None, epochs=None, lr=None, eval_every=None, task=None,
-        weight_decay=None, decoupled_decay=None, optimizer=None, norm=None, root_weight=None, bias=None, residual=None):
+        weight_decay=None, decoupled_decay=None, optimizer=None, norm=None, root_weight=None, bias=None, residual=None,
+        save=None, load=None, predict=None, proba=None):
     """PGCN.py:162-238.  ``normalize="sym"``: train on D_r^-1/2 (A + I) D_c^-1/2 of the pattern of ``path_A``, built on the fly
     (partition.build_partition) instead of by the offline pass preprocess/GrB-GNN-IDG.py.  ``dropout`` > 0: the output of every
     layer but the last is dropped with that probability (class PGCN), masks from (``dropout_seed``, step, layer, global row,
@@ -1622,7 +1665,12 @@ def run(rank, size, nlayers, nfeatures, path_A, path_partvec, backend, normalize
     files).  ``root_weight`` / ``bias`` (True; need the three files): every layer is the GraphSAGE-style
     act((A H) W_n^T + H W_r^T + b) of class PGCN instead of act((A H) W^T).  ``norm="node"``: layer normalisation of every vertex
     over its own features instead (row-local: no collective).  ``residual`` (True; needs the three files): every layer but the last
-    whose two widths are equal returns H + layer(H)."""
+    whose two widths are equal returns H + layer(H).
+    ``save`` / ``load`` (checkpoint files, checkpoint.py), ``predict`` (the prefix of the prediction files) and ``proba`` (True: the
+    probabilities too; needs ``predict``) need the three files: ``load`` resumes -- ``epochs`` more epochs, 0 allowed --, ``save``
+    writes the checkpoint after the loop, ``predict`` writes <prefix>.pred.npy (the format of ``labels``), .conf.npy and, with
+    ``proba``, .prob.npy for ALL n vertices from the weights of the best epoch.  A checkpoint of another launcher, architecture or
+    optimiser kind raises ValueError on every rank, before any collective."""
     global myrank, world_size, send_map, recv_map, device, X, recv_buffers, send_buffers, stats
     myrank = rank
     world_size = size
@@ -1648,6 +1696,10 @@ def run(rank, size, nlayers, nfeatures, path_A, path_partvec, backend, normalize
         raise ValueError("root_weight and bias need features, labels and split")
     if residual is not None and not all(given):
         raise ValueError("residual needs features, labels and split")
+    if (save is not None or load is not None or predict is not None or proba is not None) and not all(given):
+        raise ValueError("save, load, predict and proba need features, labels and split")
+    if proba and predict is None:
+        raise ValueError("proba needs predict")
     if torch.cuda.is_available():
         device = torch.device(f'cuda:{myrank % torch.cuda.device_count()}')
         torch.cuda.set_device(device)
@@ -1659,7 +1711,12 @@ def run(rank, size, nlayers, nfeatures, path_A, path_partvec, backend, normalize
 
     partvec = _partition.read_partvec(path_partvec)       # first line: n part ids (PGCN.py:172-173); .gz accepted
     if all(given):         # reads the files alone: every rank raises alike, before any collective
-        _nodeloss.TASKS[task or "single"].open_checked(features, labels, split, len(partvec))
+        opened = _nodeloss.TASKS[task or "single"].open_checked(features, labels, split, len(partvec))
+        if load is not None:
+            arch = _architecture(opened[3], opened[4], nlayers, nfeatures, hidden, multilabel, dropout, dropout_seed, norm, root_weight,
+                                 bias, residual)
+            load = _checkpoint.load(load, "PGCN", arch, optimizer or "torch")
+        del opened
     _partition_cache.clear()
     if _ingest.is_shard_prefix(path_A, rank):
         # binary CSR shards written ahead of time (ingest.write_shards / tools/make_shards.py): this rank reads
@@ -1703,7 +1760,8 @@ def run(rank, size, nlayers, nfeatures, path_A, path_partvec, backend, normalize
                               dropout_seed, multilabel, float(weight_decay or 0.0), bool(decoupled_decay), optimizer or "torch",
                               **({"norm": norm} if norm not in (None, "none") else {}),
                               **({"root_weight": True} if root_weight else {}), **({"bias": True} if bias else {}),
-                              **({"residual": True} if residual else {}))
+                              **({"residual": True} if residual else {}),
+                              **{k: v for k, v in (("save", save), ("load", load), ("predict", predict), ("proba", proba)) if v is not None})
 
     owned = A.part.owned.to(device)
     # PGCN.py:186-188 synthetic features H[i,:] = i, owned rows only
@@ -1778,7 +1836,8 @@ def run(rank, size, nlayers, nfeatures, path_A, path_partvec, backend, normalize
 
 def init_process(rank, size, fn, nlayers, nfeatures, path_A, path_partvec, backend, normalize=None, dropout=0.0, dropout_seed=0,
                  features=None, labels=None, split=None, hidden=None, epochs=None, lr=None, eval_every=None, task=None,
-                 weight_decay=None, decoupled_decay=None, optimizer=None, norm=None, root_weight=None, bias=None, residual=None):
+                 weight_decay=None, decoupled_decay=None, optimizer=None, norm=None, root_weight=None, bias=None, residual=None,
+                 save=None, load=None, predict=None, proba=None):
     """PGCN.py:241-253."""
     global _exchanger
     dist.init_process_group(backend, rank=rank, world_size=size)
@@ -1797,7 +1856,7 @@ def init_process(rank, size, fn, nlayers, nfeatures, path_A, path_partvec, backe
     for name, v in (("features", features), ("labels", labels), ("split", split), ("hidden", hidden), ("epochs", epochs), ("lr", lr),
                     ("eval_every", eval_every), ("task", task), ("weight_decay", weight_decay), ("decoupled_decay", decoupled_decay),
                     ("optimizer", optimizer), ("norm", norm), ("root_weight", root_weight), ("bias", bias),
-                    ("residual", residual)):
+                    ("residual", residual), ("save", save), ("load", load), ("predict", predict), ("proba", proba)):
         if v is not None:
             kw[name] = v
     fn(rank, size, nlayers, nfeatures, path_A, path_partvec, backend, **kw)     # (no option given: today's call)
@@ -1822,7 +1881,8 @@ def main(argv):
     try:
         opts, args = getopt.getopt(argv, "a:p:b:s:l:f:", ["normalize=", "dropout=", "dropout-seed=", "features=", "labels=", "split=",
                                                           "hidden=", "epochs=", "lr=", "eval-every=", "task=", "weight-decay=", "adamw",
-                                                          "optimizer=", "norm=", "root-weight", "bias", "residual"])
+                                                          "optimizer=", "norm=", "root-weight", "bias", "residual", "save=", "load=",
+                                                          "predict=", "proba"])
     except getopt.GetoptError:
         print("a:p:b:", flush=True)
         sys.exit(2)
@@ -1888,6 +1948,10 @@ def main(argv):
             data["bias"] = True
         elif opt == '--residual':      # every layer but the last whose widths are equal returns H + layer(H) (class PGCN)
             data["residual"] = True
+        elif opt in ('--save', '--load', '--predict'):      # checkpoint.py: write / resume from a checkpoint; the prediction files' prefix
+            data[opt[2:]] = arg
+        elif opt == '--proba':         # with --predict: <prefix>.prob.npy too
+            data["proba"] = True
         elif opt == '--lr':
             try:
                 data["lr"] = float(arg)
@@ -1911,13 +1975,19 @@ def main(argv):
     os.environ.setdefault("WORLD_SIZE", str(size))
     files = [k for k in ("features", "labels", "split") if k in data]
     if data and len(files) != 3:
-        print("--features, --labels and --split go together (and --hidden, --epochs, --lr, --eval-every, --task, --weight-decay, --adamw, --optimizer, --norm, --residual, --root-weight, --bias need them); got %s"
+        print("--features, --labels and --split go together (and --hidden, --epochs, --lr, --eval-every, --task, --weight-decay, --adamw, --optimizer, --save, --load, --predict, --proba, --norm, --residual, --root-weight, --bias need them); got %s"
               % ", ".join("--" + {"decoupled_decay": "adamw"}.get(k, k.replace("_", "-")) for k in sorted(data)), flush=True)
         sys.exit(2)
     for k in files:
         if not os.path.exists(data[k]):
             print("--%s: no such file %r" % (k, data[k]), flush=True)
             sys.exit(2)
+    if data.get("proba") and "predict" not in data:
+        print("--proba needs --predict", flush=True)
+        sys.exit(2)
+    if "load" in data and not os.path.exists(data["load"]):
+        print("--load: no such file %r" % (data["load"],), flush=True)
+        sys.exit(2)
 
     mp.set_start_method("spawn", force=True)
     args = (rank, size, run, nlayers, nfeatures, path_A, path_partvec, backend, normalize)
@@ -1929,14 +1999,18 @@ def main(argv):
         layer_opts = tuple(data.get(k) for k in ("root_weight", "bias"))
         has_residual = data.get("residual") is not None
         has_layer_opts = any(v is not None for v in layer_opts) or has_residual
-        if any(v is not None for v in extra) or data.get("norm") is not None or has_layer_opts:      # (none given: the argument tuple of before)
-            args += extra
-        if data.get("norm") is not None or has_layer_opts:
-            args += (data.get("norm"),)
-        if has_layer_opts:
-            args += layer_opts
-        if has_residual:                   # (the tuple grows only when --residual is given)
-            args += (True,)
+        keep = tuple(data.get(k) for k in ("save", "load", "predict", "proba"))
+        if any(v is not None for v in keep):      # (the four ride behind every earlier option: the tuple is complete up to them)
+            args += extra + (data.get("norm"),) + layer_opts + (data.get("residual"),) + keep
+        else:
+            if any(v is not None for v in extra) or data.get("norm") is not None or has_layer_opts:      # (none given: the argument tuple of before)
+                args += extra
+            if data.get("norm") is not None or has_layer_opts:
+                args += (data.get("norm"),)
+            if has_layer_opts:
+                args += layer_opts
+            if has_residual:                   # (the tuple grows only when --residual is given)
+                args += (True,)
     p = mp.Process(target=init_process, args=args)
     p.start()
     p.join()

@@ -128,6 +128,7 @@ SIGNATURES = {
                                                 _u32, _vp, _i64, _vp, _vp, _vp, _vp]),
     "pgcn_ln_relu_backward_f32": (ctypes.c_int, [_vp, _i64, _vp, _i64, _i64, _i32, _vp, _vp, _vp, _vp, ctypes.c_float, _vp, _i64, _vp, _vp,
                                                  _vp, _i64, _vp]),
+    "pgcn_predict_f32": (ctypes.c_int, [_vp, _i64, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _i64, _vp]),
     "pgcn_gather_rows_f32": (ctypes.c_int, [_vp, _i64, _vp, _i64, _vp, _i64, _i32, _vp]),
     "pgcn_scatter_rows_f32": (ctypes.c_int, [_vp, _i64, _vp, _i64, _vp, _i64, _i32, _i32, _vp]),
     "pgcn_comm_unique_id": (ctypes.c_int, [_vp]),

@@ -1,5 +1,5 @@
 // pgcn_rowband.h -- the layout, the dropout pieces and the deterministic column sums that the row-band layer kernels share
-// (pgcn_norm.hip, pgcn_combine.hip, pgcn_layernorm.hip, pgcn_gat_tail.hip).  Header-only, everything in an anonymous namespace: each
+// (pgcn_norm.hip, pgcn_combine.hip, pgcn_layernorm.hip, pgcn_gat_tail.hip; pgcn_predict.hip takes the layout alone).  Header-only, everything in an anonymous namespace: each
 // translation unit keeps its own copy under its own compile flags.  Nothing in here depends on -ffp-contract: the floating-point
 // work is additions of doubles, nothing a contraction could fuse; the element arithmetic stays in the including file.
 //

@@ -210,6 +210,14 @@ def masked_bce_stats_views(record: torch.Tensor) -> MaskedBCEStats:
     return MaskedBCEStats(*set_record_views(record, 3))
 
 
+class Prediction(NamedTuple):
+    """What pgcn_predict_f32 leaves of a block of logits (None: not formed, or not of this task)."""
+    cls: Optional[torch.Tensor]       # int64 [n]: the first of a row's equal maxima (-1: a row of NaN only)         -- task "single"
+    conf: Optional[torch.Tensor]      # float32 [n]: the softmax probability of that class                           -- task "single"
+    bits: Optional[torch.Tensor]      # int32 [n, ceil(C / 32)]: x > 0, the layout of nodedata.pack_label_words      -- task "multilabel"
+    prob: Optional[torch.Tensor]      # float32 [n, C]: the softmax of a row / the sigmoid of an element
+
+
 def _gscale(g: torch.Tensor) -> torch.Tensor:       # a loss's incoming gradient as the one float32 its backward kernel reads
     return g.reshape(1).to(torch.float32).contiguous()
 
@@ -1106,6 +1114,28 @@ class HipKernels:
                                                          g.data_ptr(), scale, n, C, dX.data_ptr(), dX.stride(0),
                                                          self._stream()), "pgcn_masked_bce_backward_f32")
         return dX
+
+    def predict(self, logits: torch.Tensor, task: str, want_conf: bool = True, want_prob: bool = False):
+        """Prediction of pgcn_predict_f32, one pass over the logits: task "single": cls (the arg-max that masked_nll counts), conf
+        where ``want_conf``, the softmax where ``want_prob``; "multilabel": bits (x > 0, what masked_bce counts; int32 words, torch
+        has no arithmetic on uint32), the sigmoid where ``want_prob``.  None when the operand is not covered (more than 1024
+        columns, another dtype, device or layout)."""
+        if task not in ("single", "multilabel"):
+            raise _lib.PgcnError("predict: task takes single | multilabel, got %r" % (task,))
+        if not (logits.is_cuda and logits.device == self.device and logits.dim() == 2 and logits.dtype is torch.float32 and
+                0 < logits.shape[1] <= ROWBAND_MAX_F and (logits.stride(1) == 1 or logits.shape[1] == 1 or logits.shape[0] == 0) and
+                (logits.shape[0] <= 1 or logits.stride(0) >= logits.shape[1])):
+            return None
+        n, C = logits.shape
+        ldx = logits.stride(0) if n > 1 else C
+        single = task == "single"
+        cls = torch.empty(n, dtype=torch.int64, device=self.device) if single else None
+        conf = torch.empty(n, dtype=torch.float32, device=self.device) if single and want_conf else None
+        bits = torch.empty((n, (C + 31) // 32), dtype=torch.int32, device=self.device) if not single else None
+        prob = torch.empty((n, C), dtype=torch.float32, device=self.device) if want_prob else None
+        _lib.check(self.lib.pgcn_predict_f32(logits.data_ptr(), ldx, n, C, 0 if single else 1, _ptr(cls), _ptr(conf), _ptr(bits),
+                                             _ptr(prob), C, self._stream()), "pgcn_predict_f32")
+        return Prediction(cls, conf, bits, prob)
 
     def adam_step(self, p: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: torch.Tensor, step: torch.Tensor, lr: float, betas,
                   eps: float, weight_decay: float, decoupled: bool, grad_scale: float, zero_grad: bool):

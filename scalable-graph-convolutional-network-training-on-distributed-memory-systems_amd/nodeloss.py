@@ -188,6 +188,58 @@ def evaluate(model, H, labels, split, task, gate, reduce):
     return reduce(st, logits.shape[1])
 
 
+# ---- from logits to predictions (--predict): csrc/pgcn_predict.hip, or the same rules from framework operations -------------------
+
+def predict_composed(logits, task, want_conf=True, want_prob=False):
+    """kernels.Prediction from framework operations, the rules of pgcn_predict_f32.  "single": ``cls`` = the first of the equal
+    maxima of a row, a NaN dropped from the maximum and equal to nothing (-1 on a row of NaN only) -- what pgcn_masked_nll_f32 and
+    ``masked_stats_composed`` count as a hit; ``conf`` = 1 / sum_j exp(x_j - max); ``prob`` = exp(x_j - max) / that sum.
+    "multilabel": ``bits`` = the packed words of x > 0 (int32 [n, ceil(C / 32)], the layout of nodedata.pack_label_words);
+    ``prob`` = 1 / (1 + exp(-x))."""
+    n, C = logits.shape
+    if task == "multilabel":
+        from . import dropout as _dropout
+        prob = 1.0 / (1.0 + torch.exp(-logits)) if want_prob else None
+        return _kernels.Prediction(None, None, _dropout.pack_words(logits > 0), prob)
+    neg = torch.full((), float("-inf"), dtype=logits.dtype, device=logits.device)
+    m = torch.where(torch.isnan(logits), neg, logits).max(1, keepdim=True).values if C else logits.new_zeros((n, 1))
+    cols = torch.arange(C, dtype=torch.int64, device=logits.device).unsqueeze(0)
+    first = torch.where(logits == m, cols, torch.full((), C, dtype=torch.int64, device=logits.device)).min(1).values
+    cls = torch.where(first == C, torch.full_like(first, -1), first)
+    conf = prob = None
+    if want_conf or want_prob:
+        e = torch.exp(logits - m)
+        s = e.sum(1, keepdim=True)
+        conf = (1.0 / s).squeeze(1) if want_conf else None
+        prob = e / s if want_prob else None
+    return _kernels.Prediction(cls, conf, None, prob)
+
+
+def predict_kernels(k, logits):
+    """``k`` if its ``predict`` takes these logits, else None (no provider or kernel, CPU tensors, another layout): the gate of
+    ``masked_kernels``."""
+    if (k is not None and hasattr(k, "predict") and logits.is_cuda and logits.dim() == 2 and logits.dtype is torch.float32
+            and logits.stride(1) == 1):
+        return k
+    return None
+
+
+def predict(model, H, task, k=None, want_conf=True, want_prob=False):
+    """One eval-mode forward without autograd, then one pass from the logits of the owned rows to kernels.Prediction:
+    pgcn_predict_f32 of the provider ``k`` (a provider, or a callable that names one for the logits), else the composition.
+    Collective where the model's forward is."""
+    was_training = model.training
+    model.eval()
+    try:
+        with torch.no_grad():
+            logits = model(H)
+            k = k(logits) if callable(k) else k
+            out = k.predict(logits, task, want_conf, want_prob) if k is not None else None     # (None: a shape the kernel refuses)
+            return out if out is not None else predict_composed(logits, task, want_conf, want_prob)
+    finally:
+        model.train(was_training)
+
+
 # What differs between the tasks of a training loop (--task): the provider's forward method and its labels' dtype; nodedata's
 # loader and file check; the record of one pass (the operands, then the provider); the key of global_stats that a report calls
 # Train / Val / Test; the line of an epoch and the last line.  (The loss is the launcher's own binding: it names the provider.)
