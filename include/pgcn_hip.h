@@ -544,6 +544,34 @@ int pgcn_adam_step_f32(float *p, float *g, float *m, float *v, int64_t n, double
                        double weight_decay, int32_t decoupled, float grad_scale, int32_t zero_grad, const int64_t *step,
                        pgcn_stream_t stream);
 
+/* ---- the step under control: gradient clipping and a learning-rate schedule read on the device (optim.py has the definitions) ----
+ * pgcn_grad_sumsq_f32: partial[0 .. parts) = partial sums of (double)g[i] * (double)g[i] over g[0 .. n), doubles; parts must be
+ *   pgcn_grad_sumsq_parts(n) (a function of n alone: ceil(n / 1024), at most 256, 0 for n <= 0).  Every product is exact; a lane adds
+ *   its float4 chunks in trip order, a fixed LDS tree follows: the result is a function of n and the bits of g, the same for a base
+ *   that is 16-byte aligned (float4 loads) and one that is not (scalar loads).  No atomics, no allocation (graph-capturable).
+ *   n == 0: PGCN_OK, nothing launched.  PGCN_EINVAL: n < 0, another `parts`, a null or misaligned pointer.
+ * pgcn_adam_step_ctl_f32: pgcn_adam_step_f32 with its learning rate and gradient factor formed by the kernel:
+ *   t = *step;  lr = lr_at(t; kind, base, warmup, horizon, lr_min, step_every, gamma):
+ *     kind 0 constant: s = base;   kind 1 cosine: u = clamp((t - warmup) / (horizon - warmup), 0, 1),
+ *     s = lr_min + (base - lr_min) * 0.5 * (1 + cos(pi u));   kind 2 step: s = base * gamma^floor(max(t - warmup, 0) / step_every);
+ *     lr = s (t + 1) / warmup for t < warmup, else s          -- all in double; AdamW's shrink is 1 - lr * weight_decay
+ *   max_norm > 0: sumsq = partial[0] + ... + partial[parts - 1] in index order (every block adds them itself),
+ *     norm = sqrt(sumsq) |grad_scale|,  c = max_norm / (norm + 1e-6),  coef = c < 1 ? c : (isnan(c) ? c : 1) in double
+ *     (torch.nn.utils.clip_grad_norm_, error_if_nonfinite off), and the factor of every gradient element is the fp32 product
+ *     grad_scale * (float)coef: with coef == 1 the step's bits are those of the unclipped step.  max_norm == 0: no clip, `partial`
+ *     is not read and may be null.
+ *   ctl (DEVICE, 4 doubles) receives {sumsq, norm, coef, lr} ({0, 0, 1, lr} without clip) from block 0.
+ *   kind 0, warmup 0, max_norm 0: the bits of pgcn_adam_step_f32 with lr = base.
+ * PGCN_EINVAL, nothing launched: what pgcn_adam_step_f32 refuses; an unknown kind; a schedule value that is not finite or negative;
+ *   horizon <= warmup or lr_min > base for cosine; step_every < 1; gamma outside (0, 1] for step; max_norm < 0 or NaN; a null or
+ *   misaligned ctl or step, or partial while clipping; parts != pgcn_grad_sumsq_parts(n) while clipping.                        */
+int32_t pgcn_grad_sumsq_parts(int64_t n);
+int pgcn_grad_sumsq_f32(const float *g, int64_t n, double *partial, int32_t parts, pgcn_stream_t stream);
+int pgcn_adam_step_ctl_f32(float *p, float *g, float *m, float *v, int64_t n, int32_t kind, double base, double warmup, double horizon,
+                           double lr_min, double step_every, double gamma, double max_norm, const double *partial, int32_t parts,
+                           double *ctl, double beta1, double beta2, double eps, double weight_decay, int32_t decoupled,
+                           float grad_scale, int32_t zero_grad, const int64_t *step, pgcn_stream_t stream);
+
 /* ---- batch normalisation over all vertices, fused with ReLU and dropout (PGCN.py: _BatchNormReluDropout) ----------
  * The layer y = drop(relu(BN(x))) of an nrows x f block of OWNED rows whose statistics are those of ALL ranks' rows:
  *   forward   pgcn_bn_colstats_f32  ->  [one float64 all-reduce of 2 f + 1 numbers]  ->  pgcn_bn_prepare_f32  ->  pgcn_bn_relu_apply_f32

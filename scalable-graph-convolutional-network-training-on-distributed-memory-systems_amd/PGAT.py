@@ -463,8 +463,9 @@ def build_classifier(A, fin, classes, nlayers, hidden, K, out_heads=1, dropout=0
 
 def _train_on_data(A, n, nlayers, features, labels, split, task=None, hidden=None, out_heads=None, epochs=None, lr=None,
                    eval_every=None, dropout=0.0, dropout_seed=0, bias=None, weight_decay=None, decoupled_decay=None, optimizer=None,
-                   save=None, load=None, predict=None, proba=None):
-    """The loop of ``run`` on real inputs, the scheme of PGCN._train_on_data: constant features, Adam, the masked loss over the train
+                   save=None, load=None, predict=None, proba=None, control=None):
+    """The loop of ``run`` on real inputs, the scheme of PGCN._train_on_data (``control``: ``nodeloss.Control``, as there):
+    constant features, Adam, the masked loss over the train
     rows (``task="multilabel"``: the masked binary cross entropy and micro-F1).  Reports every ``eval_every`` epochs: without
     dropout from the record of the training step's own pass (the logits BEFORE that step's update), with dropout from ``evaluate``
     after the update.  ``optimizer="fused"``: optim.FlatAdam, the gradients reduced in place in its arena.  The initial parameters
@@ -504,6 +505,7 @@ def _train_on_data(A, n, nlayers, features, labels, split, task=None, hidden=Non
         hooks = _checkpoint.Hooks("PGAT", arch, model, fused, opt, state, save, load, predict, proba, myrank, _barrier)
         first, history, best = hooks.resume()
     last = first + epochs - 1
+    ctrl = _nodeloss.Control(control, lr).start(first, epochs, fused, opt, model.parameters()) if control else None
     if device.type == "cuda":
         torch.cuda.synchronize(device)
     start = time.time()
@@ -522,14 +524,21 @@ def _train_on_data(A, n, nlayers, features, labels, split, task=None, hidden=Non
             opt.zero_grad()
             loss.backward()
             sum_gradients(model)
+            if ctrl is not None:
+                ctrl.before_step(epoch)
             opt.step()
         if state is not None:
             state.advance()
         if epoch % eval_every == 0 or epoch == last:
             ev = evaluate_of(model, H, y, s) if state is not None else _global_stats(st, data.classes)
+            if ctrl is not None:
+                ev.update(ctrl.entry())
             best = _nodeloss.report(task, epoch, ev, history, best, myrank == 0)
             if hooks is not None:
                 hooks.reported(best, history[-1])
+            if ctrl is not None and ctrl.stop(history, myrank == 0):
+                epochs = epoch + 1 - first           # (the epochs actually run: ms/epoch, the checkpoint's count)
+                break
     if device.type == "cuda":
         torch.cuda.synchronize(device)
     elapsed = torch.tensor([time.time() - start], device=device)
@@ -548,7 +557,9 @@ def run(rank, size, nlayers, nfeatures, path_A, path_partvec, backend, epochs=No
     """PGAT.py:165-233.  ``features`` / ``labels`` / ``split`` (.npy files in global vertex order, nodedata.py; all three or none):
     train the classifier of ``build_classifier`` on them instead of the synthetic loop (``_train_on_data`` takes the other keyword
     arguments: task, hidden, out_heads, lr, eval_every, dropout, dropout_seed, bias, weight_decay, decoupled_decay, optimizer, and
-    save, load, predict, proba -- checkpoint.py, as in PGCN.run); the returned model carries ``history``, ``best`` and ``widths``."""
+    save, load, predict, proba -- checkpoint.py, as in PGCN.run -- and the options of nodeloss.CONTROL: clip_norm, lr_schedule,
+    lr_warmup, lr_min, lr_step, lr_gamma, lr_horizon, patience, as in PGCN.run); the returned model carries ``history``, ``best`` and
+    ``widths``."""
     global myrank, world_size, send_map, recv_map, device, X, recv_buffers, send_buffers
     files = [v for v in (features, labels, split) if v is not None]
     if len(files) not in (0, 3) or (data and not files):
@@ -561,6 +572,13 @@ def run(rank, size, nlayers, nfeatures, path_A, path_partvec, backend, epochs=No
         raise ValueError("proba needs predict")
     if files and mode == "reference":
         raise ValueError("the reference layer has no bias, activation, head mean or dropout: train on data in standard mode")
+    control = {k: data.pop(k) for k in list(data) if k in _nodeloss.CONTROL}
+    control = {k: v for k, v in control.items() if v is not None}
+    if control:            # each value, what goes together, the horizon against the warm-up: before any collective
+        ctrl = _nodeloss.Control(control, float(1e-3 if data.get("lr") is None else data["lr"]))
+        if data.get("load") is None:
+            ctrl.start(0, int(4 if epochs is None else epochs))
+        data["control"] = control
     myrank = rank
     world_size = size
     if torch.cuda.is_available():
@@ -663,12 +681,17 @@ def main(argv):
         opts, args = getopt.getopt(argv, "a:p:b:s:l:f:", ["mode=", "heads=", "features=", "labels=", "split=", "task=", "hidden=",
                                                           "out-heads=", "epochs=", "lr=", "eval-every=", "dropout=", "dropout-seed=",
                                                           "bias", "weight-decay=", "adamw", "optimizer=", "save=", "load=", "predict=",
-                                                          "proba"])
+                                                          "proba"] + [f[2:] + "=" for f in _nodeloss.CONTROL_FLAGS.split(", ")])
     except getopt.GetoptError:
         print("a:p:b:", flush=True)
         sys.exit(2)
     for opt, arg in opts:
-        if opt in ('--features', '--labels', '--split'):       # .npy files in global vertex order (nodedata.py)
+        if opt[2:].replace("-", "_") in _nodeloss.CONTROL:       # clipping, the schedule, early stopping (nodeloss.Control)
+            try:
+                data[opt[2:].replace("-", "_")] = _nodeloss.control_value(opt[2:].replace("-", "_"), arg, flag=True)
+            except ValueError as e:
+                refuse(str(e))
+        elif opt in ('--features', '--labels', '--split'):       # .npy files in global vertex order (nodedata.py)
             data[opt[2:]] = arg
         elif opt in ('--hidden', '--out-heads', '--epochs', '--eval-every'):
             try:
@@ -737,8 +760,8 @@ def main(argv):
     files = [k for k in ("features", "labels", "split") if k in data]
     if data and len(files) != 3:
         refuse("--features, --labels and --split go together (and --task, --hidden, --out-heads, --epochs, --lr, --eval-every, --dropout, "
-               "--dropout-seed, --bias, --weight-decay, --adamw, --save, --load, --predict, --proba, --optimizer need them); got %s"
-               % ", ".join("--" + {"decoupled_decay": "adamw"}.get(k, k.replace("_", "-")) for k in sorted(data)))
+               "--dropout-seed, --bias, --weight-decay, --adamw, --save, --load, --predict, --proba, --optimizer, %s need them); got %%s"
+               % _nodeloss.CONTROL_FLAGS % ", ".join("--" + {"decoupled_decay": "adamw"}.get(k, k.replace("_", "-")) for k in sorted(data)))
     for k in files:
         if not os.path.exists(data[k]):
             refuse("--%s: no such file %r" % (k, data[k]))
@@ -748,6 +771,14 @@ def main(argv):
         refuse("--load: no such file %r" % (data["load"],))
     if data and mode == "reference":
         refuse("--mode reference has no bias, activation, head mean or dropout: --features needs --mode standard")
+    control = {k: data[k] for k in _nodeloss.CONTROL if k in data}
+    if control:
+        try:               # what goes together; the horizon against the warm-up where the first epoch is known (no --load)
+            ctrl = _nodeloss.Control(control, data.get("lr", 1e-3), flag=True)
+            if "load" not in data:
+                ctrl.start(0, data.get("epochs", 4))
+        except ValueError as e:
+            refuse(str(e))
     if data and heads >= 1 and data.get("hidden", 8 * heads) % heads:
         refuse("--hidden takes a multiple of --heads (%d), got %r" % (heads, str(data["hidden"])))
     env_rank = os.environ.get("SLURM_PROCID", os.environ.get("RANK"))

@@ -1555,7 +1555,7 @@ OPTIMIZERS = _nodeloss.OPTIMIZERS      # --optimizer / run(optimizer=...): "torc
 
 def _train_on_data(A, n, nlayers, nfeatures, features, labels, split, hidden, epochs, lr, eval_every, dropout, dropout_seed,
                    multilabel=False, weight_decay=0.0, decoupled_decay=False, optimizer="torch", norm=None, root_weight=None, bias=None,
-                   residual=None, save=None, load=None, predict=None, proba=None):
+                   residual=None, save=None, load=None, predict=None, proba=None, control=None):
     """The loop of ``run`` on real inputs: widths fin -> hidden -> ... -> C, no ReLU on the last layer, constant features (the
     first layer's backward aggregation is skipped), Adam, the masked loss over the train rows.  Reports every ``eval_every``
     epochs: without dropout from the record of the training step's own pass (the logits BEFORE that step's update), with
@@ -1573,13 +1573,16 @@ def _train_on_data(A, n, nlayers, nfeatures, features, labels, split, hidden, ep
     ``save`` / ``load`` / ``predict`` / ``proba``: checkpoint.py (``Hooks``) -- ``load`` (a path, or the dict ``checkpoint.load``
     read) is applied after the optimiser is built and ``epochs`` MORE epochs follow, numbered from the checkpoint's count on (0:
     nothing is trained); ``save``: the checkpoint after the loop; ``predict``: the prefix of the prediction files, written from the
-    best epoch's weights (``proba``: the probabilities too).  With none of the four nothing is copied and nothing more printed."""
+    best epoch's weights (``proba``: the probabilities too).  With none of the four nothing is copied and nothing more printed.
+    ``control``: the options of nodeloss.CONTROL that were given (gradient clipping, the learning-rate schedule, early stopping:
+    ``nodeloss.Control``); None: the loop of before, call for call."""
     task = _nodeloss.TASKS["multilabel" if multilabel else "single"]
     data = task.load(features, labels, split, A.part.owned, n, device=device)
     hidden = int(nfeatures if hidden is None else hidden)
     epochs = int(4 if epochs is None else epochs)
     lr = float(1e-3 if lr is None else lr)
     eval_every = max(1, int(1 if eval_every is None else eval_every))
+    ctrl = _nodeloss.Control(control, lr) if control else None
     n_train = data.counts[1]
     if n_train < 1:
         raise ValueError("split %r: no train rows" % (split,))
@@ -1605,6 +1608,8 @@ def _train_on_data(A, n, nlayers, nfeatures, features, labels, split, hidden, ep
         hooks = _checkpoint.Hooks("PGCN", arch, model, fused, opt, state, save, load, predict, proba, myrank, _barrier)
         first, history, best = hooks.resume()
     last = first + epochs - 1
+    if ctrl is not None:
+        ctrl.start(first, epochs, fused, opt, model.parameters())
     if device.type == "cuda":
         torch.cuda.synchronize(device)
     start = time.time()
@@ -1621,14 +1626,21 @@ def _train_on_data(A, n, nlayers, nfeatures, features, labels, split, hidden, ep
             opt.zero_grad()
             loss.backward()
             average_gradients(model, average=False)
+            if ctrl is not None:
+                ctrl.before_step(epoch)
             opt.step()
         if state is not None:
             state.advance()
         if epoch % eval_every == 0 or epoch == last:
             ev = evaluate_of(model, H, y, s) if state is not None else _global_stats(st, data.classes)
+            if ctrl is not None:
+                ev.update(ctrl.entry())
             best = _nodeloss.report(task, epoch, ev, history, best, myrank == 0)
             if hooks is not None:
                 hooks.reported(best, history[-1])
+            if ctrl is not None and ctrl.stop(history, myrank == 0):
+                epochs = epoch + 1 - first           # (the epochs actually run: ms/epoch, the checkpoint's count)
+                break
     if device.type == "cuda":
         torch.cuda.synchronize(device)
     elapsed = torch.tensor([time.time() - start], device=device)
@@ -1648,7 +1660,7 @@ def _train_on_data(A, n, nlayers, nfeatures, features, labels, split, hidden, ep
 def run(rank, size, nlayers, nfeatures, path_A, path_partvec, backend, normalize=None, dropout=0.0, dropout_seed=0,
         features=None, labels=None, split=None, hidden=None, epochs=None, lr=None, eval_every=None, task=None,
         weight_decay=None, decoupled_decay=None, optimizer=None, norm=None, root_weight=None, bias=None, residual=None,
-        save=None, load=None, predict=None, proba=None):
+        save=None, load=None, predict=None, proba=None, **control):
     """PGCN.py:162-238.  ``normalize="sym"``: train on D_r^-1/2 (A + I) D_c^-1/2 of the pattern of ``path_A``, built on the fly
     (partition.build_partition) instead of by the offline pass preprocess/GrB-GNN-IDG.py.  ``dropout`` > 0: the output of every
     layer but the last is dropped with that probability (class PGCN), masks from (``dropout_seed``, step, layer, global row,
@@ -1670,8 +1682,17 @@ def run(rank, size, nlayers, nfeatures, path_A, path_partvec, backend, normalize
     probabilities too; needs ``predict``) need the three files: ``load`` resumes -- ``epochs`` more epochs, 0 allowed --, ``save``
     writes the checkpoint after the loop, ``predict`` writes <prefix>.pred.npy (the format of ``labels``), .conf.npy and, with
     ``proba``, .prob.npy for ALL n vertices from the weights of the best epoch.  A checkpoint of another launcher, architecture or
-    optimiser kind raises ValueError on every rank, before any collective."""
+    optimiser kind raises ValueError on every rank, before any collective.
+    ``clip_norm`` (the global L2 norm the gradient is clipped to), ``lr_schedule`` ("constant" | "cosine" | "step"), ``lr_warmup``
+    (updates of linear warm-up), ``lr_min`` and ``lr_horizon`` (cosine: the floor, and the update at which it is reached -- by
+    default the first epoch + ``epochs``), ``lr_step`` and ``lr_gamma`` (step: every how many updates, and the factor, 0.1), and
+    ``patience`` (stop after that many reported epochs without a better validation score) need the three files:
+    ``nodeloss.Control``, optim.py has the definitions.  The history's entries then carry ``lr`` (and ``gnorm``, ``clip``)."""
     global myrank, world_size, send_map, recv_map, device, X, recv_buffers, send_buffers, stats
+    for name in control:
+        if name not in _nodeloss.CONTROL:
+            raise TypeError("run() got an unexpected keyword argument %r" % (name,))
+    control = {name: v for name, v in control.items() if v is not None}
     myrank = rank
     world_size = size
     given = [v is not None for v in (features, labels, split)]
@@ -1700,6 +1721,12 @@ def run(rank, size, nlayers, nfeatures, path_A, path_partvec, backend, normalize
         raise ValueError("save, load, predict and proba need features, labels and split")
     if proba and predict is None:
         raise ValueError("proba needs predict")
+    if control and not all(given):
+        raise ValueError("%s need features, labels and split" % ", ".join(control))
+    if control:            # each value, what goes together, the horizon against the warm-up: before any collective
+        ctrl = _nodeloss.Control(control, float(1e-3 if lr is None else lr))
+        if load is None:
+            ctrl.start(0, int(4 if epochs is None else epochs))
     if torch.cuda.is_available():
         device = torch.device(f'cuda:{myrank % torch.cuda.device_count()}')
         torch.cuda.set_device(device)
@@ -1717,6 +1744,8 @@ def run(rank, size, nlayers, nfeatures, path_A, path_partvec, backend, normalize
                                  bias, residual)
             load = _checkpoint.load(load, "PGCN", arch, optimizer or "torch")
         del opened
+        if control and load is not None:        # (the horizon against the warm-up, from the epoch the checkpoint stands at)
+            ctrl.start(int(load["epochs"]), int(4 if epochs is None else epochs))
     _partition_cache.clear()
     if _ingest.is_shard_prefix(path_A, rank):
         # binary CSR shards written ahead of time (ingest.write_shards / tools/make_shards.py): this rank reads
@@ -1761,7 +1790,8 @@ def run(rank, size, nlayers, nfeatures, path_A, path_partvec, backend, normalize
                               **({"norm": norm} if norm not in (None, "none") else {}),
                               **({"root_weight": True} if root_weight else {}), **({"bias": True} if bias else {}),
                               **({"residual": True} if residual else {}),
-                              **{k: v for k, v in (("save", save), ("load", load), ("predict", predict), ("proba", proba)) if v is not None})
+                              **{k: v for k, v in (("save", save), ("load", load), ("predict", predict), ("proba", proba)) if v is not None},
+                              **({"control": control} if control else {}))
 
     owned = A.part.owned.to(device)
     # PGCN.py:186-188 synthetic features H[i,:] = i, owned rows only
@@ -1837,8 +1867,8 @@ def run(rank, size, nlayers, nfeatures, path_A, path_partvec, backend, normalize
 def init_process(rank, size, fn, nlayers, nfeatures, path_A, path_partvec, backend, normalize=None, dropout=0.0, dropout_seed=0,
                  features=None, labels=None, split=None, hidden=None, epochs=None, lr=None, eval_every=None, task=None,
                  weight_decay=None, decoupled_decay=None, optimizer=None, norm=None, root_weight=None, bias=None, residual=None,
-                 save=None, load=None, predict=None, proba=None):
-    """PGCN.py:241-253."""
+                 save=None, load=None, predict=None, proba=None, control=None):
+    """PGCN.py:241-253.  ``control``: the given options of nodeloss.CONTROL as one dict (None: today's call)."""
     global _exchanger
     dist.init_process_group(backend, rank=rank, world_size=size)
 
@@ -1859,6 +1889,7 @@ def init_process(rank, size, fn, nlayers, nfeatures, path_A, path_partvec, backe
                     ("residual", residual), ("save", save), ("load", load), ("predict", predict), ("proba", proba)):
         if v is not None:
             kw[name] = v
+    kw.update(control or {})
     fn(rank, size, nlayers, nfeatures, path_A, path_partvec, backend, **kw)     # (no option given: today's call)
 
     if _exchanger is not None:
@@ -1882,12 +1913,18 @@ def main(argv):
         opts, args = getopt.getopt(argv, "a:p:b:s:l:f:", ["normalize=", "dropout=", "dropout-seed=", "features=", "labels=", "split=",
                                                           "hidden=", "epochs=", "lr=", "eval-every=", "task=", "weight-decay=", "adamw",
                                                           "optimizer=", "norm=", "root-weight", "bias", "residual", "save=", "load=",
-                                                          "predict=", "proba"])
+                                                          "predict=", "proba"] + [f[2:] + "=" for f in _nodeloss.CONTROL_FLAGS.split(", ")])
     except getopt.GetoptError:
         print("a:p:b:", flush=True)
         sys.exit(2)
     for opt, arg in opts:
-        if opt == '--normalize':       # train on D^-1/2 (A + I) D^-1/2 of the input's pattern (partition.build_partition)
+        if opt[2:].replace("-", "_") in _nodeloss.CONTROL:       # clipping, the schedule, early stopping (nodeloss.Control)
+            try:
+                data[opt[2:].replace("-", "_")] = _nodeloss.control_value(opt[2:].replace("-", "_"), arg, flag=True)
+            except ValueError as e:
+                print(e, flush=True)
+                sys.exit(2)
+        elif opt == '--normalize':      # train on D^-1/2 (A + I) D^-1/2 of the input's pattern (partition.build_partition)
             if arg not in _partition.NORMALIZE:
                 print("--normalize takes %s, got %r" % ("|".join(_partition.NORMALIZE), arg), flush=True)
                 sys.exit(2)
@@ -1975,8 +2012,8 @@ def main(argv):
     os.environ.setdefault("WORLD_SIZE", str(size))
     files = [k for k in ("features", "labels", "split") if k in data]
     if data and len(files) != 3:
-        print("--features, --labels and --split go together (and --hidden, --epochs, --lr, --eval-every, --task, --weight-decay, --adamw, --optimizer, --save, --load, --predict, --proba, --norm, --residual, --root-weight, --bias need them); got %s"
-              % ", ".join("--" + {"decoupled_decay": "adamw"}.get(k, k.replace("_", "-")) for k in sorted(data)), flush=True)
+        print("--features, --labels and --split go together (and --hidden, --epochs, --lr, --eval-every, --task, --weight-decay, --adamw, --optimizer, --save, --load, --predict, --proba, %s, --norm, --residual, --root-weight, --bias need them); got %%s"
+              % _nodeloss.CONTROL_FLAGS % ", ".join("--" + {"decoupled_decay": "adamw"}.get(k, k.replace("_", "-")) for k in sorted(data)), flush=True)
         sys.exit(2)
     for k in files:
         if not os.path.exists(data[k]):
@@ -1988,6 +2025,15 @@ def main(argv):
     if "load" in data and not os.path.exists(data["load"]):
         print("--load: no such file %r" % (data["load"],), flush=True)
         sys.exit(2)
+    control = {k: data[k] for k in _nodeloss.CONTROL if k in data}
+    if control:
+        try:               # what goes together; the horizon against the warm-up where the first epoch is known (no --load)
+            ctrl = _nodeloss.Control(control, data.get("lr", 1e-3), flag=True)
+            if "load" not in data:
+                ctrl.start(0, data.get("epochs", 4))
+        except ValueError as e:
+            print(e, flush=True)
+            sys.exit(2)
 
     mp.set_start_method("spawn", force=True)
     args = (rank, size, run, nlayers, nfeatures, path_A, path_partvec, backend, normalize)
@@ -2000,8 +2046,9 @@ def main(argv):
         has_residual = data.get("residual") is not None
         has_layer_opts = any(v is not None for v in layer_opts) or has_residual
         keep = tuple(data.get(k) for k in ("save", "load", "predict", "proba"))
-        if any(v is not None for v in keep):      # (the four ride behind every earlier option: the tuple is complete up to them)
-            args += extra + (data.get("norm"),) + layer_opts + (data.get("residual"),) + keep
+        if any(v is not None for v in keep) or control:      # (the four ride behind every earlier option: the tuple is complete up to
+            args += extra + (data.get("norm"),) + layer_opts + (data.get("residual"),) + keep       # them; the control options, one dict,
+            args += (control,) if control else ()                                                   # behind the four)
         else:
             if any(v is not None for v in extra) or data.get("norm") is not None or has_layer_opts:      # (none given: the argument tuple of before)
                 args += extra

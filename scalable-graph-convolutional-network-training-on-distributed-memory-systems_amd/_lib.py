@@ -105,6 +105,10 @@ SIGNATURES = {
     "pgcn_masked_bce_backward_f32": (ctypes.c_int, [_vp, _i64, _vp, _vp, _vp, ctypes.c_float, _i64, _i32, _vp, _i64, _vp]),
     "pgcn_adam_step_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, ctypes.c_double, ctypes.c_double, ctypes.c_double,
                                           ctypes.c_double, ctypes.c_double, _i32, ctypes.c_float, _i32, _vp, _vp]),
+    "pgcn_grad_sumsq_parts": (_i32, [_i64]),
+    "pgcn_grad_sumsq_f32": (ctypes.c_int, [_vp, _i64, _vp, _i32, _vp]),
+    "pgcn_adam_step_ctl_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _i32] + [ctypes.c_double] * 7 + [_vp, _i32, _vp] +
+                               [ctypes.c_double] * 4 + [_i32, ctypes.c_float, _i32, _vp, _vp]),
     "pgcn_bn_colstats_ws_bytes": (_i64, [_i64, _i32]),
     "pgcn_bn_colstats_f32": (ctypes.c_int, [_vp, _i64, _i64, _i32, _vp, _vp, _i64, _vp]),
     "pgcn_bn_prepare_f32": (ctypes.c_int, [_vp, _i32, ctypes.c_double, ctypes.c_double, _i32, _vp, _vp, _vp, _vp, _vp]),

@@ -1155,6 +1155,51 @@ class HipKernels:
                                                self._stream()), "pgcn_adam_step_f32")
         return True
 
+    def grad_sumsq_parts(self, n: int) -> int:
+        """The number of partial sums ``grad_sumsq`` writes for n floats (pgcn_grad_sumsq_parts: a function of n alone, <= 256)."""
+        return int(self.lib.pgcn_grad_sumsq_parts(int(n)))
+
+    def grad_sumsq(self, g: torch.Tensor, partial: Optional[torch.Tensor] = None):
+        """``partial`` (float64 [grad_sumsq_parts(n)] on g's device; None: allocated here) filled with the partial sums of squares
+        of the flat fp32 array g in ONE launch (pgcn_grad_sumsq_f32): what ``adam_step_ctl`` adds up for the clip.  Returns
+        ``partial``, or None for what the kernel does not cover (as ``adam_step``)."""
+        if not (g.is_cuda and g.device == self.device and g.dtype is torch.float32 and g.is_contiguous()):
+            return None
+        parts = self.grad_sumsq_parts(g.numel())
+        if partial is None:
+            partial = torch.empty(parts, dtype=torch.float64, device=g.device)
+        elif not (partial.device == g.device and partial.dtype is torch.float64 and partial.is_contiguous() and partial.numel() == parts):
+            return None
+        _lib.check(self.lib.pgcn_grad_sumsq_f32(g.data_ptr(), g.numel(), partial.data_ptr(), parts, self._stream()), "pgcn_grad_sumsq_f32")
+        return partial
+
+    def adam_step_ctl(self, p: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: torch.Tensor, step: torch.Tensor, sched, max_norm,
+                      partial: Optional[torch.Tensor], ctl: torch.Tensor, betas, eps: float, weight_decay: float, decoupled: bool,
+                      grad_scale: float, zero_grad: bool):
+        """``adam_step`` with the learning rate ``optim.lr_at(*step, sched)`` and the clip coefficient of ``max_norm`` (None or 0: no
+        clip) formed by the kernel (pgcn_adam_step_ctl_f32) from ``partial`` (``grad_sumsq`` of g); ``ctl``: float64 [4] on the
+        device, receives {sumsq, norm, coef, lr}.  Returns True, or None for what the kernel does not cover (as ``adam_step``)."""
+        ts = (p, g, m, v)
+        if not all(t.is_cuda and t.device == p.device and t.dtype is torch.float32 and t.is_contiguous() and t.numel() == p.numel()
+                   for t in ts):
+            return None
+        if not (step.device == p.device == self.device and step.dtype is torch.int64 and step.numel() == 1):
+            return None
+        clip = bool(max_norm)
+        if not (ctl.device == p.device and ctl.dtype is torch.float64 and ctl.is_contiguous() and ctl.numel() == 4):
+            return None
+        if clip and not (partial is not None and partial.device == p.device and partial.dtype is torch.float64 and partial.is_contiguous()):
+            return None
+        from .optim import SCHEDULE_KINDS      # (the entry point's `kind` is the index)
+        kind, base, warmup, horizon, lr_min, step_every, gamma = sched
+        _lib.check(self.lib.pgcn_adam_step_ctl_f32(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel(),
+                                                   SCHEDULE_KINDS.index(kind), float(base), float(warmup), float(horizon), float(lr_min),
+                                                   float(step_every), float(gamma), float(max_norm or 0.0), _ptr(partial) if clip else None,
+                                                   partial.numel() if clip else 0, ctl.data_ptr(), float(betas[0]), float(betas[1]),
+                                                   float(eps), float(weight_decay), 1 if decoupled else 0, float(grad_scale),
+                                                   1 if zero_grad else 0, step.data_ptr(), self._stream()), "pgcn_adam_step_ctl_f32")
+        return True
+
     # -- batch normalisation over all vertices, fused with ReLU and dropout (csrc/pgcn_norm.hip) --------------------
     def _mat_ok(self, t: Optional[torch.Tensor], n: int, width: int) -> bool:
         # (the stride of a dimension of size 1, and every stride of an empty matrix, is never used: torch leaves them arbitrary)

@@ -2,6 +2,7 @@
 module's state: a function takes the kernel provider ``k`` whose masked kernels take the operands (``masked_kernels`` is the gate;
 None: the composition from framework operations) and, if it is collective, the world size and an ``all_reduce`` callable.  The
 launchers bind these functions to their own state, read when a binding is called.  ``TASKS``: what differs between the tasks."""
+import math
 from collections import namedtuple
 
 import torch
@@ -276,6 +277,117 @@ TASKS = {       # --task / run(task=...): one class per vertex (the default) or 
                        "Best Val F1 {:.4f} at epoch {:05d} | Test F1 {:.4f}"),
 }
 OPTIMIZERS = ("torch", "fused")       # --optimizer / run(optimizer=...): torch.optim.Adam[W] (the default) or optim.FlatAdam
+
+
+_WHOLE = lambda lo: (int, lambda x: x >= lo, "an integer >= %d" % lo)
+CONTROL = {     # run(...)'s keyword (its option: "--" + the name with dashes): (type, what it accepts, in words)
+    "clip_norm": (float, lambda x: math.isfinite(x) and x > 0.0, "a finite number > 0"),
+    "lr_schedule": (str, lambda x: x in _optim.SCHEDULE_KINDS, " | ".join(_optim.SCHEDULE_KINDS)),
+    "lr_warmup": _WHOLE(0),
+    "lr_min": (float, lambda x: math.isfinite(x) and x >= 0.0, "a finite number >= 0"),
+    "lr_step": _WHOLE(1),
+    "lr_gamma": (float, lambda x: 0.0 < x <= 1.0, "a number in (0, 1]"),
+    "lr_horizon": _WHOLE(1),
+    "patience": _WHOLE(1),
+}
+CONTROL_FLAGS = ", ".join("--" + name.replace("_", "-") for name in CONTROL)
+
+
+def option_name(name, flag, value=None):
+    """``name`` of ``CONTROL`` (with ``value``: set to it) as run's keyword, or with ``flag`` as on the command line."""
+    if flag:
+        return "--" + name.replace("_", "-") + ("" if value is None else " %s" % value)
+    return name + ("" if value is None else "=%s" % value)
+
+
+def control_value(name, value, flag=False):
+    """``value`` of the option ``name`` of ``CONTROL`` in its type; ValueError with the option's own message (``flag``: named as on
+    the command line) for what it does not take."""
+    kind, accepts, takes = CONTROL[name]
+    try:
+        if kind is int and not isinstance(value, str) and int(value) != value:
+            raise ValueError
+        x = kind(value)
+        if not accepts(x):
+            raise ValueError
+    except (TypeError, ValueError, OverflowError):
+        raise ValueError("%s takes %s, got %r" % (option_name(name, flag), takes, value))
+    return x
+
+
+class Control:
+    """What the two training loops do for --clip-norm, --lr-schedule / --lr-warmup / --lr-min / --lr-step / --lr-gamma /
+    --lr-horizon and --patience, stated once (optim.py has the definitions of the clip and of ``lr_at``).  A loop builds one only
+    when an option is given -- ``Control(options, lr)`` checks each value and what goes together (``flag``: its messages name the
+    options as the command line does) -- and calls, in this order:
+    ``start(first, epochs, fused, opt, params)`` after the optimiser is built and a checkpoint resumed (the horizon defaults to
+    ``first + epochs``; optim.FlatAdam takes the clip and the schedule from here on); ``before_step(epoch)`` between the gradients'
+    reduction and ``opt.step()`` of torch's optimiser (``clip_grad_norm_``, then the epoch's rate into every parameter group; the
+    fused step needs no call); ``entry()`` on a reporting epoch -- what joins the reported entry: ``lr``, and ``gnorm`` / ``clip``
+    when clipping, the only wait for the device --; ``stop(history)`` after ``report``.
+
+    ``patience=K``: stop after K consecutive reported epochs whose validation score did not beat the best, by ``report``'s strict
+    ``>``; counted from ``history`` (a resumed run carries it), whose numbers are all-reduced, so every rank stops alike."""
+
+    def __init__(self, options, lr, flag=False):
+        o = {name: control_value(name, v, flag) for name, v in options.items() if v is not None}
+        self.flag = flag
+        self.max_norm, self.patience = o.get("clip_norm"), o.get("patience")
+        self.kind = o.get("lr_schedule", "constant")
+        for name, kind in (("lr_min", "cosine"), ("lr_horizon", "cosine"), ("lr_step", "step"), ("lr_gamma", "step")):
+            if name in o and self.kind != kind:
+                raise ValueError("%s needs %s" % (option_name(name, flag), option_name("lr_schedule", flag, kind)))
+        if self.kind == "step" and "lr_step" not in o:
+            raise ValueError("%s needs %s" % (option_name("lr_schedule", flag, "step"), option_name("lr_step", flag)))
+        if o.get("lr_min", 0.0) > lr:
+            raise ValueError("%s takes a number <= %s (%r), got %r" % (option_name("lr_min", flag), option_name("lr", flag), lr, o["lr_min"]))
+        self.lr, self.warmup, self.lr_min, self.horizon = float(lr), o.get("lr_warmup", 0), o.get("lr_min", 0.0), o.get("lr_horizon")
+        self.step_every, self.gamma = o.get("lr_step", 1), o.get("lr_gamma", 0.1)
+        self.scheduled = "lr_schedule" in o or "lr_warmup" in o
+        self.schedule = self.fused = self.opt = self.params = self._norm = None
+
+    def start(self, first, epochs, fused=None, opt=None, params=()):
+        horizon = self.horizon if self.horizon is not None else first + epochs
+        if self.kind == "cosine" and horizon <= self.warmup:
+            raise ValueError("%s (%d; by default the first epoch + %s) must be above %s (%d)"
+                             % (option_name("lr_horizon", self.flag), horizon, option_name("epochs", self.flag),
+                                option_name("lr_warmup", self.flag), self.warmup))
+        self.schedule = _optim.check_schedule((self.kind, self.lr, self.warmup, horizon, self.lr_min, self.step_every, self.gamma))
+        self.fused, self.opt, self.params = fused, opt, list(params)
+        if fused is not None and (self.max_norm is not None or self.scheduled):
+            fused.set_control(self.max_norm, self.schedule if self.scheduled else None)
+        return self
+
+    def before_step(self, epoch):
+        if self.max_norm is not None:
+            self._norm = torch.nn.utils.clip_grad_norm_(self.params, self.max_norm)
+        if self.scheduled:
+            for group in self.opt.param_groups:
+                group["lr"] = _optim.lr_at(epoch, self.schedule)
+
+    def entry(self):
+        if self.fused is not None:
+            rec = self.fused.control() or {}
+        else:
+            rec = {"lr": self.opt.param_groups[0]["lr"]} if self.scheduled or self.max_norm is not None else {}
+            if self._norm is not None:
+                rec["gnorm"] = float(self._norm)
+                c = self.max_norm / (rec["gnorm"] + 1e-6)
+                rec["clip"] = c if c < 1.0 or math.isnan(c) else 1.0
+        return {key: rec[key] for key in ("lr",) + (("gnorm", "clip") if self.max_norm is not None else ()) if key in rec}
+
+    def stop(self, history, show=False):
+        """True when the last ``patience`` entries of ``history`` all follow its best entry; prints the line where ``show``."""
+        if self.patience is None or not history:
+            return False
+        at = 0
+        for i, h in enumerate(history):
+            if h["val"] > history[at]["val"]:
+                at = i
+        stale = len(history) - 1 - at
+        if stale >= self.patience and show:
+            print("Stopped early at epoch {:05d}: no better Val in {} reports".format(history[-1]["epoch"], stale), flush=True)
+        return stale >= self.patience
 
 
 def make_optimizer(params, optimizer, lr, weight_decay, decoupled, kernels=None):

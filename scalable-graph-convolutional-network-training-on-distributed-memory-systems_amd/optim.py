@@ -7,11 +7,30 @@ ranks' sum is one in-place all-reduce of that buffer (no ``cat``, no copy back),
 in a one-element int64 tensor ON THE DEVICE, as in ``dropout.DropoutState``: the kernel reads it, ``step()`` adds 1 with a
 device-side add, so a captured graph of a training step applies the right bias correction at every replay.
 
-Limit under capture: the hyper-parameters (lr, betas, eps, weight decay, the gradient scale) are launch arguments, so a captured
-graph bakes them in -- there is no learning-rate schedule here.
+Under capture: betas, eps, the weight decay and the gradient scale are launch arguments, so a captured graph bakes them in.  The
+learning rate and the clip coefficient need not be: with ``schedule`` / ``max_norm`` the step is ``pgcn_adam_step_ctl_f32``, which
+forms both ON THE DEVICE -- the rate from the step count it reads anyway, the coefficient from the partial sums of squares that one
+more launch (``pgcn_grad_sumsq_f32``) leaves behind -- so a replayed graph takes the rate and the clip of ITS replay.  The clip costs
+one extra launch, the schedule none, and the host never waits: ``control()`` alone reads the record back.
 
-``adam_step_composed`` is the same arithmetic in framework operations: what ``step()`` runs for CPU tensors and for a provider
-without the kernel (the checker-backed provider of the CPU tests), in the pattern of ``PGCN.masked_bce_stats_composed``."""
+Definitions (the kernel, the composition and the tests follow them).  ``t``: the updates already made, ``step_count``.
+
+  lr_at(t, sched), in double, sched = (kind, base, warmup W >= 0, horizon T, lr_min, step_every S, gamma):
+    constant                               s = base
+    cosine  (T > W, 0 <= lr_min <= base)   u = clamp((t - W) / (T - W), 0, 1);  s = lr_min + (base - lr_min) * 0.5 * (1 + cos(pi u))
+    step    (S >= 1, 0 < gamma <= 1)       s = base * gamma ** floor(max(t - W, 0) / S)
+    lr = s * (t + 1) / W for t < W, else s.        AdamW's decoupled shrink uses the same lr: keep = 1 - lr * weight_decay.
+
+  clip (global L2 norm, max_norm > 0, in double):
+    sumsq = sum g_i^2 over the flat gradient arena (its padding is zero and stays zero);  norm = sqrt(sumsq) * |grad_scale|
+    c = max_norm / (norm + 1e-6);  coef = c < 1 ? c : (isnan(c) ? c : 1)  -- torch.nn.utils.clip_grad_norm_(error_if_nonfinite=False):
+    a NaN norm makes every parameter NaN, an infinite one gives coef = 0;  coef_f = (float)coef
+    the factor of every gradient element is grad_scale * coef_f, ONE fp32 product: with coef == 1 the step's bits are those of the
+    unclipped step.
+
+``adam_step_composed`` / ``adam_step_ctl_composed`` are the same arithmetic in framework operations: what ``step()`` runs for CPU
+tensors and for a provider without the kernels (the checker-backed provider of the CPU tests), in the pattern of
+``PGCN.masked_bce_stats_composed``."""
 from __future__ import annotations
 
 import math
@@ -29,12 +48,70 @@ def _check_hyper(lr, betas, eps, weight_decay):
         raise ValueError("betas must be below 1, got %r" % (tuple(betas),))
 
 
+SCHEDULE_KINDS = ("constant", "cosine", "step")
+
+
+def constant_schedule(lr):
+    return ("constant", float(lr), 0, 0, 0.0, 1, 1.0)
+
+
+def check_schedule(sched):
+    """``sched`` = (kind, base, warmup, horizon, lr_min, step_every, gamma) with its numbers as Python floats and ints; ValueError
+    for what the definition does not cover."""
+    try:
+        kind, base, W, T, lr_min, S, gamma = sched
+        base, lr_min, gamma = float(base), float(lr_min), float(gamma)
+        if int(W) != W or int(T) != T or int(S) != S:
+            raise ValueError
+        W, T, S = int(W), int(T), int(S)
+    except (TypeError, ValueError, OverflowError):
+        raise ValueError("a schedule is (kind, base, warmup, horizon, lr_min, step_every, gamma) with whole numbers for warmup, "
+                         "horizon and step_every, got %r" % (sched,))
+    if kind not in SCHEDULE_KINDS:
+        raise ValueError("a schedule's kind takes %s, got %r" % (" | ".join(SCHEDULE_KINDS), kind))
+    for name, x in (("base", base), ("warmup", W), ("horizon", T), ("lr_min", lr_min), ("step_every", S), ("gamma", gamma)):
+        if not (math.isfinite(x) and x >= 0):
+            raise ValueError("a schedule's %s must be finite and >= 0, got %r" % (name, x))
+    if S < 1:
+        raise ValueError("a schedule's step_every must be >= 1, got %r" % (S,))
+    if kind == "cosine" and not (T > W and lr_min <= base):
+        raise ValueError("a cosine schedule needs horizon > warmup and lr_min <= base, got horizon %r warmup %r lr_min %r base %r"
+                         % (T, W, lr_min, base))
+    if kind == "step" and not 0.0 < gamma <= 1.0:
+        raise ValueError("a step schedule needs 0 < gamma <= 1, got %r" % (gamma,))
+    return kind, base, W, T, lr_min, S, gamma
+
+
+def lr_at(t, sched):
+    """The learning rate of update ``t`` (0-based: the updates already made) under ``sched``, in Python doubles: the module's
+    definition."""
+    kind, base, W, T, lr_min, S, gamma = check_schedule(sched)
+    t = int(t)
+    s = base
+    if kind == "cosine":
+        u = min(max((t - W) / (T - W), 0.0), 1.0)
+        s = lr_min + (base - lr_min) * 0.5 * (1.0 + math.cos(math.pi * u))
+    elif kind == "step":
+        s = base * gamma ** (max(t - W, 0) // S)
+    return s * (t + 1) / W if t < W else s
+
+
+def check_max_norm(max_norm):
+    """None (no clip) or the float of a ``max_norm`` > 0; ValueError otherwise."""
+    if max_norm is None:
+        return None
+    if not float(max_norm) > 0.0:
+        raise ValueError("max_norm must be > 0 (None: no clip), got %r" % (max_norm,))
+    return float(max_norm)
+
+
 def adam_step_composed(p, g, m, v, step, lr, betas, eps, weight_decay, decoupled, grad_scale, zero_grad):
     """One Adam / AdamW update of p, m, v from g, in place, in the order of operations of torch.optim.Adam / AdamW (and of
     pgcn_adam_step_f32):  gi = g * grad_scale;  coupled: gi += weight_decay * p;  decoupled: p *= 1 - lr * weight_decay;
     m += (gi - m) * (1 - beta1);  v = beta2 * v + (1 - beta2) * gi * gi;  p -= (lr / bc1) * (m / (sqrt(v) / sqrt(bc2) + eps))
     with bc = 1 - beta^t, t = step + 1, formed in float64;  ``zero_grad``: g = 0 afterwards.  ``step``: a one-element int64
-    tensor, read with tensor operations (no host wait), never written."""
+    tensor, read with tensor operations (no host wait), never written.  ``lr``: a Python float, or a 0-dim float64 tensor on
+    ``step``'s device; ``grad_scale``: a Python float, or a 0-dim tensor of p's dtype and device (``adam_step_ctl_composed``)."""
     beta1, beta2 = float(betas[0]), float(betas[1])
     t = (step.reshape(()) + 1).to(torch.float64)
     bc1 = 1.0 - torch.pow(torch.full((), beta1, dtype=torch.float64, device=t.device), t)
@@ -43,7 +120,9 @@ def adam_step_composed(p, g, m, v, step, lr, betas, eps, weight_decay, decoupled
     sqrt_bc2 = bc2.sqrt().to(device=p.device, dtype=p.dtype)
     with torch.no_grad():
         gi = g * grad_scale
-        if decoupled:
+        if decoupled and isinstance(lr, torch.Tensor):
+            p.mul_((1.0 - lr * weight_decay).to(device=p.device, dtype=p.dtype))
+        elif decoupled:
             p.mul_(1.0 - lr * weight_decay)
         elif weight_decay != 0.0:
             gi.add_(p, alpha=weight_decay)
@@ -53,6 +132,37 @@ def adam_step_composed(p, g, m, v, step, lr, betas, eps, weight_decay, decoupled
         p.sub_((m / denom).mul_(step_size))
         if zero_grad:
             g.zero_()
+
+
+def lr_at_composed(step, sched):
+    """``lr_at(step, sched)`` as a 0-dim float64 tensor on ``step``'s device, from tensor operations (no host wait)."""
+    kind, base, W, T, lr_min, S, gamma = check_schedule(sched)
+    t = step.reshape(()).to(torch.float64)
+    s = torch.full((), base, dtype=torch.float64, device=t.device)
+    if kind == "cosine":
+        u = ((t - W) / (T - W)).clamp(0.0, 1.0)
+        s = lr_min + (base - lr_min) * 0.5 * (1.0 + torch.cos(math.pi * u))
+    elif kind == "step":
+        s = base * torch.pow(torch.full((), gamma, dtype=torch.float64, device=t.device), torch.floor((t - W).clamp_min(0.0) / S))
+    return torch.where(t < W, s * (t + 1.0) / W, s) if W > 0 else s
+
+
+def adam_step_ctl_composed(p, g, m, v, step, sched, max_norm, ctl, betas, eps, weight_decay, decoupled, grad_scale, zero_grad):
+    """``adam_step_composed`` with lr = ``lr_at(step, sched)`` and, for ``max_norm`` (None or 0: no clip), the clip coefficient of the
+    module's definition, both formed from tensors (no host wait); ``ctl`` (float64 [4]) receives {sumsq, norm, coef, lr} ({0, 0, 1,
+    lr} without clip).  The arithmetic of pgcn_grad_sumsq_f32 + pgcn_adam_step_ctl_f32; the order of the sum of squares is the
+    framework's."""
+    lr = lr_at_composed(step, sched)
+    zero = torch.zeros((), dtype=torch.float64, device=g.device)
+    sumsq, norm, coef, factor = zero, zero, zero + 1.0, grad_scale
+    if max_norm:
+        sumsq = g.double().square().sum()
+        norm = sumsq.sqrt() * abs(float(grad_scale))
+        c = float(max_norm) / (norm + 1e-6)
+        coef = torch.where(c < 1.0, c, torch.where(torch.isnan(c), c, zero + 1.0))
+        factor = torch.full((), float(grad_scale), dtype=p.dtype, device=p.device) * coef.to(device=p.device, dtype=p.dtype)
+    ctl.copy_(torch.stack([sumsq, norm, coef, lr.to(g.device)]))
+    adam_step_composed(p, g, m, v, step, lr, betas, eps, weight_decay, decoupled, factor, zero_grad)
 
 
 def _default_kernels(device):
@@ -80,9 +190,15 @@ class FlatAdam:
 
     ``kernels``: the provider whose ``adam_step`` runs the update (kernels.HipKernels); None: the training loop's provider, or a
     HipKernels of the parameters' HIP device.  A provider without ``adam_step``, or one that answers None (CPU tensors), takes
-    ``adam_step_composed``."""
+    ``adam_step_composed``.
 
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, decoupled=False, kernels=None):
+    ``max_norm`` (a float > 0) / ``schedule`` (a ``lr_at`` tuple; its base replaces ``lr``): the step under control of the module's
+    docstring -- ``grad_sumsq`` (only when clipping) and ``adam_step_ctl`` of the provider, else ``adam_step_ctl_composed``; the
+    record {sumsq, norm, coef, lr} of the last step stays on the device in ``ctl``, and ``control()`` reads it.  With both None
+    ``step()`` makes exactly the call described above and neither buffer exists."""
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, decoupled=False, kernels=None, max_norm=None,
+                 schedule=None):
         self.params = list(params)
         if not self.params:
             raise ValueError("FlatAdam got no parameters")
@@ -110,6 +226,23 @@ class FlatAdam:
             for p, seg in zip(self.params, self._segments(self.flat_g)):
                 p.grad = seg
         self.kernels = kernels if kernels is not None else _default_kernels(device)
+        self.set_control(max_norm, schedule)
+
+    def set_control(self, max_norm=None, schedule=None):
+        """Puts the following steps under control (the class's docstring), or with both None back to the plain step; allocates the
+        record and the partial sums here, so that ``step()`` allocates nothing."""
+        self.max_norm = check_max_norm(max_norm)
+        self.schedule = None if schedule is None else check_schedule(schedule)
+        self.ctl = self.partial = None
+        if self.max_norm is None and self.schedule is None:
+            return
+        if self.schedule is None:
+            self.schedule = constant_schedule(self.lr)
+        self.lr = self.schedule[1]
+        device, k = self.flat_p.device, self.kernels
+        self.ctl = torch.zeros(4, dtype=torch.float64, device=device)
+        if self.max_norm is not None and device.type == "cuda" and hasattr(k, "grad_sumsq_parts"):
+            self.partial = torch.zeros(k.grad_sumsq_parts(self.numel), dtype=torch.float64, device=device)
 
     def _segments(self, flat):
         return [flat[o:o + p.numel()].view(p.shape) for p, o in zip(self.params, self.offsets)]
@@ -126,14 +259,32 @@ class FlatAdam:
 
     def step(self):
         """One update of every parameter: one launch over the arena that also clears the gradients, then the device-side add to the
-        step count."""
-        args = (self.flat_p, self.flat_g, self.exp_avg, self.exp_avg_sq, self.step_count, self.lr, self.betas, self.eps,
-                self.weight_decay, self.decoupled, self.grad_scale, True)
+        step count.  Under control: the launch of the sums of squares first when clipping, and the step that reads them."""
         k = self.kernels
-        if k is None or not hasattr(k, "adam_step") or k.adam_step(*args) is None:
-            adam_step_composed(*args)
+        if self.ctl is None:
+            args = (self.flat_p, self.flat_g, self.exp_avg, self.exp_avg_sq, self.step_count, self.lr, self.betas, self.eps,
+                    self.weight_decay, self.decoupled, self.grad_scale, True)
+            if k is None or not hasattr(k, "adam_step") or k.adam_step(*args) is None:
+                adam_step_composed(*args)
+        else:
+            head = (self.flat_p, self.flat_g, self.exp_avg, self.exp_avg_sq, self.step_count, self.schedule, self.max_norm)
+            tail = (self.ctl, self.betas, self.eps, self.weight_decay, self.decoupled, self.grad_scale, True)
+            done = None
+            if k is not None and hasattr(k, "adam_step_ctl") and (self.max_norm is None or self.partial is not None):
+                if self.max_norm is None or k.grad_sumsq(self.flat_g, self.partial) is not None:
+                    done = k.adam_step_ctl(*head, self.partial, *tail)
+            if done is None:
+                adam_step_ctl_composed(*head, *tail)
         self.step_count.add_(1)
         self.grad_scale = 1.0
+
+    def control(self):
+        """The record of the last step under control as host floats, {"sumsq", "gnorm", "clip", "lr"} (``clip``: the coefficient, 1
+        when the norm was within ``max_norm``); None without ``max_norm`` / ``schedule``.  The one place that waits for the device."""
+        if self.ctl is None:
+            return None
+        sumsq, norm, coef, lr = self.ctl.tolist()
+        return {"sumsq": sumsq, "gnorm": norm, "clip": coef, "lr": lr}
 
     def zero_grad(self):
         """Clears ``flat_g`` (only needed when a step was skipped: ``step()`` clears what it reads)."""
