@@ -294,6 +294,37 @@ int pgcn_spmm_fixup_f32(const int32_t *fix, int64_t nfix, const int32_t *slot_id
                         const int32_t *row_map, const float *partial_ws, float *C, int64_t ldc,
                         int32_t f, uint32_t flags, pgcn_stream_t stream);
 
+/* ---- element-wise MAX over the neighbourhood (GraphSAGE-pool / PNA style aggregation; no counterpart in the reference) ----
+ * OUT[i, c] = max over the stored columns j of row i of B[j, c] (stored values are ignored), ARG[i, c] = the SMALLEST GLOBAL id of a
+ * column that attains it (fp32 ==, so -0.0 ties with +0.0; OUT takes that column's bits); a row without entries: OUT = 0.0f, ARG = -1.
+ * pairs: 2 x int32 per stored entry {col, global id of col}, 8-byte aligned, in the order of rowptr; the pairs of every TASK of
+ * the plan in ASCENDING GLOBAL ID (a row that is one task ordered as a whole, a sliced row per col % nslices group) -- inside a task
+ * the kernel lets an equal value never replace.  tasks / seg / nslices / fix /
+ * nslots: a plan of pgcn_spmm_plan_host as pgcn_spmm_csr_plan_f32 takes it -- unsliced (nslices = 1, seg ignored; tasks NULL: one task
+ * per row, ntasks = rows, nfix = 0) or XCD-sliced (the entries of every row grouped by col % nslices, seg the HOST array of nslices + 1
+ * segment bounds): placement only, the results do not depend on it.  A candidate (v, g) replaces the state (cur, a)
+ * when a < 0 || v > cur || (v == cur && g < a): a total order, so the result does not depend on the numbering of the columns, on the cut
+ * of a row into tasks, or -- with PGCN_SPMM_ACCUMULATE, which starts from the row's current (OUT, ARG) instead of (0.0f, -1) -- on how
+ * the candidates are split over several calls.  ws: nslots x f floats (values) followed by nslots x f int32 (args) for the pieces of
+ * cut rows, merged in slot order by a second kernel.  flags: PGCN_SPMM_ACCUMULATE, _XCD_SWIZZLE, _OFFSETS32, _FPASS64.  Any f >= 1 and leading
+ * dimensions >= f; a float4 / int4 body when f % 4 == 0 with 16-byte aligned operands, a scalar body otherwise, the same bits.  Inputs
+ * are finite by contract.  No atomics, deterministic.
+ *
+ * pgcn_aggmax_backward_csr_plan_f32: D[r, c] = sum over the stored entries i of row r of the TRANSPOSED structure of
+ * (ARG[i, c] == rowgid[r] ? G[i, c] : 0) -- gather form, entries in storage order, the pieces of a cut row added in slot order
+ * (pgcn_spmm_fixup_f32): deterministic, no atomics.  col: int32 per entry, rowgid[rows]: the global id of every row, slot_row[nslots]:
+ * the row of every slot (required when nslots > 0).  D is written, never accumulated into.  PGCN_SPMM_OFFSETS32: every byte offset into
+ * G AND ARG fits 32 bits.  partial_ws: nslots x f floats.                                                                          */
+int pgcn_aggmax_csr_plan_f32(const int64_t *rowptr, const int32_t *pairs, const int32_t *tasks, int64_t ntasks,
+                             const int64_t *seg, int32_t nslices, const int32_t *fix, int64_t nfix, const float *B, int64_t ldb, float *OUT, int64_t ldo,
+                             int32_t *ARG, int64_t lda, int32_t f, void *ws, int64_t ws_bytes, int64_t nslots,
+                             uint32_t flags, pgcn_stream_t stream);
+int pgcn_aggmax_backward_csr_plan_f32(const int64_t *rowptr, const int32_t *col, const int32_t *rowgid,
+                                      const int32_t *slot_row, const int32_t *tasks, int64_t ntasks, const int64_t *seg,
+                                      int32_t nslices, const int32_t *fix, int64_t nfix, const float *G, int64_t ldg, const int32_t *ARG, int64_t lda, float *D,
+                                      int64_t ldd, int32_t f, float *partial_ws, int64_t partial_ws_elems, int64_t nslots,
+                                      uint32_t flags, pgcn_stream_t stream);
+
 /* The same product with the weights RECOMPUTED per entry instead of read from planes -- the transposed product of
  * the GAT backward pass, dZ = A_alpha^T . dOut on the transposed structure (rows = columns of A): entry (row j,
  * col i) weighs alpha_ij = (exp(e - m_i) - em_i) / D_i, e = [LeakyReLU](s1_i + s2_j), from rowstat[i] = (s1, m, 1/D, em)

@@ -194,6 +194,31 @@ class PSpMM(torch.autograd.Function):
         return None, dH
 
 
+AGGRS = ("sum", "max")          # --aggr / run(aggr=...) / PGCN(aggr=...): the weighted sum A . H (the default) or the element-wise max
+
+
+class PAggMax(torch.autograd.Function):
+    """The element-wise max over a vertex's stored neighbourhood in place of ``PSpMM``'s weighted sum (csrc/pgcn_aggmax.hip; the stored
+    values are ignored, under ``normalize="sym"`` a vertex is its own neighbour): forward ``A.forward_max`` with the halo exchange,
+    backward ``A.backward_max`` -- every gradient element goes to the one neighbour that won, the smallest global id among equals.
+    Saved: ARG alone (int32, global ids).  The constant feature matrix of the first layer needs no gradient: nothing is aggregated."""
+
+    @staticmethod
+    def forward(ctx, A, H):
+        ctx.A = A
+        OUT, ARG = A.forward_max(H)
+        ctx.save_for_backward(ARG)
+        return OUT
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        dH = ctx.A.backward_max(grad_output, ctx.saved_tensors[0]) if ctx.needs_input_grad[1] else None
+        join = getattr(ctx.A, "join_wgrad", None)        # (as PSpMM.backward: the weight gradient parked on the engine's side stream)
+        if join is not None:
+            join()
+        return None, dH
+
+
 # ---- the dense products by rocBLAS solution index (gemm/pgcn_gemm.cpp) ---------------------------------------------------
 # Plumbing beside the graded path: x . W^T and g . W of a layer are stock rocBLAS GEMMs either way; PyTorch's default pick
 # is 15-20 % slower at the benchmark shapes than the kernel PyTorch's TunableOp finds, but switching TunableOp on
@@ -1285,11 +1310,18 @@ class PGCN(nn.Module):
     ``residual=True`` (opt-in; needs ``relu=True`` and ``in_features == out_features``): the output is H + layer(H).  With
     ``norm="node"`` the addition happens inside the node's kernel (its operand R, one extra read); with every other layer kind
     (plain, dropout, batch norm, root weight / bias) it is a framework addition AFTER the existing node -- one more pass over the
-    output, no new kernel.  Off by default: ``forward`` then takes the branches of before."""
+    output, no new kernel.  Off by default: ``forward`` then takes the branches of before.
+
+    ``aggr="max"`` (opt-in): the aggregation is ``PAggMax`` -- the element-wise max over the stored neighbourhood, stored values
+    ignored -- instead of ``PSpMM``; every other option composes unchanged and the layer owns the same parameters.  None or "sum":
+    the branches of before."""
 
     def __init__(self, A, in_features, out_features, dropout=0.0, layer=0, state=None, relu=True, norm=None, root_weight=False, bias=False,
-                 residual=False):
+                 residual=False, aggr=None):
         super(PGCN, self).__init__()
+        if aggr not in AGGRS + (None,):
+            raise ValueError("aggr takes %s, got %r" % (" | ".join(AGGRS), aggr))
+        self._aggregate = PAggMax.apply if aggr == "max" else PSpMM.apply
         self.linear = nn.Linear(in_features, out_features, bias=False)
         self.A = A
         self.send_map = send_map
@@ -1367,10 +1399,10 @@ class PGCN(nn.Module):
 
     def _layer(self, H, R=None):
         if self.root_weight or self.has_bias:
-            return self._forward_combined(H, PSpMM.apply(self.A, H), R)
+            return self._forward_combined(H, self._aggregate(self.A, H), R)
         if self.norm == "node":
-            return self._node_norm(_LinearNoBias.apply(PSpMM.apply(self.A, H), self.linear.weight), H, R)
-        H = PSpMM.apply(self.A, H)
+            return self._node_norm(_LinearNoBias.apply(self._aggregate(self.A, H), self.linear.weight), H, R)
+        H = self._aggregate(self.A, H)
         if not self.relu:
             return _LinearNoBias.apply(H, self.linear.weight)
         if self.norm is not None:
@@ -1542,11 +1574,11 @@ def _barrier():
         _all_reduce(torch.zeros(1, device=device)).item()
 
 
-def _architecture(fin, classes, nlayers, nfeatures, hidden, multilabel, dropout, dropout_seed, norm, root_weight, bias, residual):
+def _architecture(fin, classes, nlayers, nfeatures, hidden, multilabel, dropout, dropout_seed, norm, root_weight, bias, residual, aggr=None):
     """checkpoint.architecture of the model ``_train_on_data`` builds from these arguments."""
     widths = [int(fin)] + [int(nfeatures if hidden is None else hidden)] * (nlayers - 1) + [int(classes)]
     return _checkpoint.architecture(widths, "multilabel" if multilabel else "single", dropout, dropout_seed, norm, root_weight, bias,
-                                    residual)
+                                    residual, **({"aggr": aggr} if aggr == "max" else {}))
 
 
 TASKS = tuple(_nodeloss.TASKS)         # --task / run(task=...): "single", one class per vertex (the default), or "multilabel"
@@ -1555,7 +1587,7 @@ OPTIMIZERS = _nodeloss.OPTIMIZERS      # --optimizer / run(optimizer=...): "torc
 
 def _train_on_data(A, n, nlayers, nfeatures, features, labels, split, hidden, epochs, lr, eval_every, dropout, dropout_seed,
                    multilabel=False, weight_decay=0.0, decoupled_decay=False, optimizer="torch", norm=None, root_weight=None, bias=None,
-                   residual=None, save=None, load=None, predict=None, proba=None, control=None):
+                   residual=None, save=None, load=None, predict=None, proba=None, control=None, aggr=None):
     """The loop of ``run`` on real inputs: widths fin -> hidden -> ... -> C, no ReLU on the last layer, constant features (the
     first layer's backward aggregation is skipped), Adam, the masked loss over the train rows.  Reports every ``eval_every``
     epochs: without dropout from the record of the training step's own pass (the logits BEFORE that step's update), with
@@ -1575,7 +1607,8 @@ def _train_on_data(A, n, nlayers, nfeatures, features, labels, split, hidden, ep
     nothing is trained); ``save``: the checkpoint after the loop; ``predict``: the prefix of the prediction files, written from the
     best epoch's weights (``proba``: the probabilities too).  With none of the four nothing is copied and nothing more printed.
     ``control``: the options of nodeloss.CONTROL that were given (gradient clipping, the learning-rate schedule, early stopping:
-    ``nodeloss.Control``); None: the loop of before, call for call."""
+    ``nodeloss.Control``); None: the loop of before, call for call.  ``aggr="max"``: every layer aggregates by the element-wise max
+    (class PGCN, ``PAggMax``); None or "sum": the weighted sum of before."""
     task = _nodeloss.TASKS["multilabel" if multilabel else "single"]
     data = task.load(features, labels, split, A.part.owned, n, device=device)
     hidden = int(nfeatures if hidden is None else hidden)
@@ -1592,6 +1625,8 @@ def _train_on_data(A, n, nlayers, nfeatures, features, labels, split, hidden, ep
     _dropout.threshold(dropout)
     state = _dropout.DropoutState(dropout_seed, device) if dropout > 0.0 else None
     extra = dict(({"root_weight": True} if root_weight else {}), **({"bias": True} if bias else {}))       # (neither: the call of before)
+    if aggr == "max":
+        extra["aggr"] = "max"
     model = nn.Sequential(*[PGCN(A, widths[i], widths[i + 1], dropout=dropout if i < nlayers - 1 else 0.0, layer=i, state=state,
                                  relu=i < nlayers - 1, **({"norm": norm} if norm not in (None, "none") and i < nlayers - 1 else {}),
                                  **extra, **({"residual": True} if residual and i < nlayers - 1 and widths[i] == widths[i + 1] else {}))
@@ -1604,7 +1639,7 @@ def _train_on_data(A, n, nlayers, nfeatures, features, labels, split, hidden, ep
     first, history, best, hooks = 0, [], None, None
     if save is not None or load is not None or predict is not None or proba:
         arch = _architecture(data.fin, data.classes, nlayers, nfeatures, hidden, multilabel, dropout, dropout_seed, norm, root_weight,
-                             bias, residual)
+                             bias, residual, aggr)
         hooks = _checkpoint.Hooks("PGCN", arch, model, fused, opt, state, save, load, predict, proba, myrank, _barrier)
         first, history, best = hooks.resume()
     last = first + epochs - 1
@@ -1660,7 +1695,7 @@ def _train_on_data(A, n, nlayers, nfeatures, features, labels, split, hidden, ep
 def run(rank, size, nlayers, nfeatures, path_A, path_partvec, backend, normalize=None, dropout=0.0, dropout_seed=0,
         features=None, labels=None, split=None, hidden=None, epochs=None, lr=None, eval_every=None, task=None,
         weight_decay=None, decoupled_decay=None, optimizer=None, norm=None, root_weight=None, bias=None, residual=None,
-        save=None, load=None, predict=None, proba=None, **control):
+        save=None, load=None, predict=None, proba=None, aggr=None, **control):
     """PGCN.py:162-238.  ``normalize="sym"``: train on D_r^-1/2 (A + I) D_c^-1/2 of the pattern of ``path_A``, built on the fly
     (partition.build_partition) instead of by the offline pass preprocess/GrB-GNN-IDG.py.  ``dropout`` > 0: the output of every
     layer but the last is dropped with that probability (class PGCN), masks from (``dropout_seed``, step, layer, global row,
@@ -1687,7 +1722,10 @@ def run(rank, size, nlayers, nfeatures, path_A, path_partvec, backend, normalize
     (updates of linear warm-up), ``lr_min`` and ``lr_horizon`` (cosine: the floor, and the update at which it is reached -- by
     default the first epoch + ``epochs``), ``lr_step`` and ``lr_gamma`` (step: every how many updates, and the factor, 0.1), and
     ``patience`` (stop after that many reported epochs without a better validation score) need the three files:
-    ``nodeloss.Control``, optim.py has the definitions.  The history's entries then carry ``lr`` (and ``gnorm``, ``clip``)."""
+    ``nodeloss.Control``, optim.py has the definitions.  The history's entries then carry ``lr`` (and ``gnorm``, ``clip``).
+    ``aggr`` ("sum", the default, or "max"; needs the three files): every layer aggregates by the element-wise max over a vertex's
+    stored neighbourhood instead of the weighted sum (``PAggMax``; the stored values are ignored, with ``normalize="sym"`` a vertex is
+    its own neighbour).  A checkpoint records it: loading one written with the other aggregation raises ValueError naming ``aggr``."""
     global myrank, world_size, send_map, recv_map, device, X, recv_buffers, send_buffers, stats
     for name in control:
         if name not in _nodeloss.CONTROL:
@@ -1717,6 +1755,10 @@ def run(rank, size, nlayers, nfeatures, path_A, path_partvec, backend, normalize
         raise ValueError("root_weight and bias need features, labels and split")
     if residual is not None and not all(given):
         raise ValueError("residual needs features, labels and split")
+    if aggr not in AGGRS + (None,):
+        raise ValueError("aggr takes %s, got %r" % (" | ".join(AGGRS), aggr))
+    if aggr is not None and not all(given):
+        raise ValueError("aggr=%r needs features, labels and split" % (aggr,))
     if (save is not None or load is not None or predict is not None or proba is not None) and not all(given):
         raise ValueError("save, load, predict and proba need features, labels and split")
     if proba and predict is None:
@@ -1741,7 +1783,7 @@ def run(rank, size, nlayers, nfeatures, path_A, path_partvec, backend, normalize
         opened = _nodeloss.TASKS[task or "single"].open_checked(features, labels, split, len(partvec))
         if load is not None:
             arch = _architecture(opened[3], opened[4], nlayers, nfeatures, hidden, multilabel, dropout, dropout_seed, norm, root_weight,
-                                 bias, residual)
+                                 bias, residual, aggr)
             load = _checkpoint.load(load, "PGCN", arch, optimizer or "torch")
         del opened
         if control and load is not None:        # (the horizon against the warm-up, from the epoch the checkpoint stands at)
@@ -1791,7 +1833,7 @@ def run(rank, size, nlayers, nfeatures, path_A, path_partvec, backend, normalize
                               **({"root_weight": True} if root_weight else {}), **({"bias": True} if bias else {}),
                               **({"residual": True} if residual else {}),
                               **{k: v for k, v in (("save", save), ("load", load), ("predict", predict), ("proba", proba)) if v is not None},
-                              **({"control": control} if control else {}))
+                              **({"control": control} if control else {}), **({"aggr": "max"} if aggr == "max" else {}))
 
     owned = A.part.owned.to(device)
     # PGCN.py:186-188 synthetic features H[i,:] = i, owned rows only
@@ -1867,8 +1909,8 @@ def run(rank, size, nlayers, nfeatures, path_A, path_partvec, backend, normalize
 def init_process(rank, size, fn, nlayers, nfeatures, path_A, path_partvec, backend, normalize=None, dropout=0.0, dropout_seed=0,
                  features=None, labels=None, split=None, hidden=None, epochs=None, lr=None, eval_every=None, task=None,
                  weight_decay=None, decoupled_decay=None, optimizer=None, norm=None, root_weight=None, bias=None, residual=None,
-                 save=None, load=None, predict=None, proba=None, control=None):
-    """PGCN.py:241-253.  ``control``: the given options of nodeloss.CONTROL as one dict (None: today's call)."""
+                 save=None, load=None, predict=None, proba=None, control=None, aggr=None):
+    """PGCN.py:241-253.  ``control``: the given options of nodeloss.CONTROL as one dict (None: today's call).  ``aggr``: run's."""
     global _exchanger
     dist.init_process_group(backend, rank=rank, world_size=size)
 
@@ -1886,7 +1928,7 @@ def init_process(rank, size, fn, nlayers, nfeatures, path_A, path_partvec, backe
     for name, v in (("features", features), ("labels", labels), ("split", split), ("hidden", hidden), ("epochs", epochs), ("lr", lr),
                     ("eval_every", eval_every), ("task", task), ("weight_decay", weight_decay), ("decoupled_decay", decoupled_decay),
                     ("optimizer", optimizer), ("norm", norm), ("root_weight", root_weight), ("bias", bias),
-                    ("residual", residual), ("save", save), ("load", load), ("predict", predict), ("proba", proba)):
+                    ("residual", residual), ("save", save), ("load", load), ("predict", predict), ("proba", proba), ("aggr", aggr)):
         if v is not None:
             kw[name] = v
     kw.update(control or {})
@@ -1913,7 +1955,7 @@ def main(argv):
         opts, args = getopt.getopt(argv, "a:p:b:s:l:f:", ["normalize=", "dropout=", "dropout-seed=", "features=", "labels=", "split=",
                                                           "hidden=", "epochs=", "lr=", "eval-every=", "task=", "weight-decay=", "adamw",
                                                           "optimizer=", "norm=", "root-weight", "bias", "residual", "save=", "load=",
-                                                          "predict=", "proba"] + [f[2:] + "=" for f in _nodeloss.CONTROL_FLAGS.split(", ")])
+                                                          "predict=", "proba", "aggr="] + [f[2:] + "=" for f in _nodeloss.CONTROL_FLAGS.split(", ")])
     except getopt.GetoptError:
         print("a:p:b:", flush=True)
         sys.exit(2)
@@ -1979,6 +2021,12 @@ def main(argv):
                 sys.exit(2)
             if arg != "none" or "norm" in data:
                 data["norm"] = arg
+        elif opt == '--aggr':          # sum (the default) | max (the element-wise max over the neighbourhood: PAggMax) -- every layer
+            if arg not in AGGRS:
+                print("--aggr takes %s, got %r" % ("|".join(AGGRS), arg), flush=True)
+                sys.exit(2)
+            if arg != "sum" or "aggr" in data:
+                data["aggr"] = arg
         elif opt == '--root-weight':   # every layer adds H . W_r^T: a vertex's own features get their own weights (class PGCN)
             data["root_weight"] = True
         elif opt == '--bias':          # every layer adds a bias (a normalised layer keeps bn_bias alone)
@@ -2012,7 +2060,7 @@ def main(argv):
     os.environ.setdefault("WORLD_SIZE", str(size))
     files = [k for k in ("features", "labels", "split") if k in data]
     if data and len(files) != 3:
-        print("--features, --labels and --split go together (and --hidden, --epochs, --lr, --eval-every, --task, --weight-decay, --adamw, --optimizer, --save, --load, --predict, --proba, %s, --norm, --residual, --root-weight, --bias need them); got %%s"
+        print("--features, --labels and --split go together (and --hidden, --epochs, --lr, --eval-every, --task, --weight-decay, --adamw, --optimizer, --save, --load, --predict, --proba, --aggr, %s, --norm, --residual, --root-weight, --bias need them); got %%s"
               % _nodeloss.CONTROL_FLAGS % ", ".join("--" + {"decoupled_decay": "adamw"}.get(k, k.replace("_", "-")) for k in sorted(data)), flush=True)
         sys.exit(2)
     for k in files:
@@ -2058,7 +2106,7 @@ def main(argv):
                 args += layer_opts
             if has_residual:                   # (the tuple grows only when --residual is given)
                 args += (True,)
-    p = mp.Process(target=init_process, args=args)
+    p = mp.Process(target=init_process, args=args, **({"kwargs": {"aggr": data["aggr"]}} if "aggr" in data else {}))
     p.start()
     p.join()
     if p.exitcode != 0:

@@ -74,6 +74,10 @@ SIGNATURES = {
                                                       _i64, _vp, _i64, _i64, _vp]),
     "pgcn_dense_bf16x3_image_bytes": (_i64, [_i64, _i32]),
     "pgcn_spmm_fixup_f32": (ctypes.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _i64, _i32, _u32, _vp]),
+    "pgcn_aggmax_csr_plan_f32": (ctypes.c_int, [_vp, _vp, _vp, _i64, _vp, _i32, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _i32, _vp, _i64,
+                                                _i64, _u32, _vp]),
+    "pgcn_aggmax_backward_csr_plan_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _i32, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64,
+                                                         _i32, _vp, _i64, _i64, _u32, _vp]),
     "pgcn_spmm_plan_host": (ctypes.c_int, [_vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _vp, _i64, _vp, _i64, _vp,
                                            ctypes.POINTER(_i64), ctypes.POINTER(_i64),
                                            ctypes.POINTER(_i64)]),

@@ -37,18 +37,22 @@ import torch
 from . import nodedata as _nodedata
 
 FORMAT_VERSION = 1
-ARCH_FIELDS = ("task", "layers", "widths", "norm", "root_weight", "bias", "residual", "heads", "out_heads", "dropout", "dropout_seed")
+ARCH_FIELDS = ("task", "layers", "widths", "norm", "root_weight", "bias", "residual", "heads", "out_heads", "dropout", "dropout_seed", "aggr")
 
 
 def architecture(widths, task, dropout=0.0, dropout_seed=0, norm=None, root_weight=None, bias=None, residual=None, heads=None,
-                 out_heads=None):
+                 out_heads=None, aggr=None):
     """The plain-value record of what a model was built from; two models of equal records have state dicts of equal keys and shapes,
-    and draw the same dropout masks."""
-    return {"widths": [int(w) for w in widths], "layers": len(widths) - 1, "task": str(task or "single"),
+    and draw the same dropout masks.  ``aggr``: the key exists only for "max" -- a record of the weighted sum is the record of before,
+    and compares equal to every checkpoint written without the key."""
+    arch = {"widths": [int(w) for w in widths], "layers": len(widths) - 1, "task": str(task or "single"),
             "norm": "none" if norm in (None, "none") else str(norm), "root_weight": bool(root_weight), "bias": bool(bias),
             "residual": bool(residual), "heads": None if heads is None else int(heads),
             "out_heads": None if out_heads is None else int(out_heads), "dropout": float(dropout),
             "dropout_seed": int(dropout_seed) if float(dropout) > 0.0 else 0}
+    if aggr == "max":
+        arch["aggr"] = "max"
+    return arch
 
 
 def _cpu(sd):

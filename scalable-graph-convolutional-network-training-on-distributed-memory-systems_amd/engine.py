@@ -438,6 +438,93 @@ class BoundaryExchange:
             probe.reduces.append((nbytes, span, (w0, w1)))
 
 
+# --------------------------------------------------------------------------
+# max aggregation: the composed route (framework operations; the definitions of csrc/pgcn_aggmax.hip)
+
+
+@dataclasses.dataclass
+class ComposedMaxCSR:
+    """The whole pattern of a block as (row, col, global id of col) per stored entry, ordered by (row, global id): what
+    ``aggmax_composed`` / ``aggmax_backward_composed`` walk.  A transposed structure carries no ids (its rows get theirs per call)."""
+    nrows: int
+    ncols: int
+    nnz: int
+    row: torch.Tensor                       # int64 [nnz]
+    col: torch.Tensor                       # int64 [nnz]
+    gid: Optional[torch.Tensor] = None      # int64 [nnz]
+
+
+def composed_max_csr(csr, col_gid: Optional[torch.Tensor], device) -> ComposedMaxCSR:
+    from .partition import full_csr
+    rowptr, col, _ = full_csr(csr)
+    rowptr, col = rowptr.cpu(), col.cpu().to(torch.int64)
+    nrows = int(rowptr.numel()) - 1
+    row = torch.repeat_interleave(torch.arange(nrows, dtype=torch.int64), rowptr[1:] - rowptr[:-1])
+    gid = None
+    if col_gid is not None:
+        gid = torch.as_tensor(col_gid).cpu().to(torch.int64)[col]
+        order = torch.argsort(row * (int(gid.max()) + 1 if gid.numel() else 1) + gid)
+        row, col, gid = row[order], col[order], gid[order].to(device)
+    return ComposedMaxCSR(nrows, csr.ncols, int(col.numel()), row.to(device), col.to(device), gid)
+
+
+def _max_better(v, g, cur, a):
+    """The update rule of the max aggregation: candidate (v, g) replaces the state (cur, a)."""
+    return (g >= 0) & ((a < 0) | (v > cur) | ((v == cur) & (g < a)))
+
+
+def aggmax_composed(A: ComposedMaxCSR, B: torch.Tensor, OUT: torch.Tensor, ARG: torch.Tensor, accumulate: bool = False):
+    """(OUT, ARG) of ``HipKernels.aggmax`` from framework operations, bit for bit: per row and feature the largest B[col] over the
+    stored entries, the smallest global id among the entries that attain it (fp32 ==), OUT that entry's bits; a row without entries
+    (0.0, -1).  ``accumulate``: the rows' current (OUT, ARG) compete under the same rule.  nnz x f temporaries: the route of CPU
+    tensors and of providers without the kernels."""
+    n, f = A.nrows, B.shape[1]
+    val = torch.zeros((n, f), dtype=B.dtype, device=B.device)
+    arg = torch.full((n, f), -1, dtype=torch.int64, device=B.device)
+    if A.nnz:
+        X = B.detach()[A.col]                                                          # nnz x f, entries by (row, global id)
+        ridx = A.row.unsqueeze(1).expand(-1, f)
+        top = torch.full((n, f), float("-inf"), dtype=B.dtype, device=B.device).scatter_reduce(0, ridx, X, "amax", include_self=True)
+        e = torch.arange(A.nnz, dtype=torch.int64, device=B.device).unsqueeze(1).expand(-1, f)
+        e = torch.where(X == top[A.row], e, torch.full_like(e, A.nnz))
+        win = torch.full((n, f), A.nnz, dtype=torch.int64, device=B.device).scatter_reduce(0, ridx, e, "amin", include_self=True)
+        has = win < A.nnz                                                              # (False: a row without entries)
+        win = win.clamp(max=A.nnz - 1)
+        val = torch.where(has, torch.gather(X, 0, win), val)                           # the winner's own bits (-0.0 stays -0.0)
+        arg = torch.where(has, A.gid[win], arg)
+    arg = arg.to(torch.int32)
+    if accumulate:
+        cur, a = OUT[:n], ARG[:n]
+        take = _max_better(val, arg, cur, a)
+        val, arg = torch.where(take, val, cur), torch.where(take, arg, a)
+    OUT[:n] = val
+    ARG[:n] = arg
+    return OUT, ARG
+
+
+def aggmax_backward_composed(AT: ComposedMaxCSR, row_gid: torch.Tensor, G: torch.Tensor, ARG: torch.Tensor, D: torch.Tensor):
+    """D of ``HipKernels.aggmax_backward`` from framework operations: D[r] = sum over the stored entries i of row r of the transposed
+    structure of (ARG[i] == row_gid[r] ? G[i] : 0).  The same definition; only the order of the fp32 additions is the framework's."""
+    D[:AT.nrows] = 0
+    if AT.nnz:
+        hit = ARG[AT.col] == row_gid.to(ARG.dtype)[AT.row].unsqueeze(1)
+        D[:AT.nrows].index_add_(0, AT.row, torch.where(hit, G.detach()[AT.col], torch.zeros((), dtype=G.dtype, device=G.device)))
+    return D
+
+
+@dataclasses.dataclass
+class MaxStructures:
+    """What ``AggregationEngine.forward_max`` / ``backward_max`` run on, built at the first max call: the whole pattern of every
+    block (kernels.DeviceMaxCSR, or ComposedMaxCSR on the composed route) and the global ids as int32."""
+    composed: bool
+    loc: object
+    halo: list
+    loc_T: object
+    halo_T: list
+    owned: torch.Tensor
+    halo_global: torch.Tensor
+
+
 class AggregationEngine(BoundaryExchange):
     """Owns rank p's device-resident pieces and runs the aggregation forward/backward."""
 
@@ -457,6 +544,7 @@ class AggregationEngine(BoundaryExchange):
         self.A_halo_T = [kernels.prepare(a) for a in part.A_halo_T]
         self._wgrad_stream = None       # side stream of the weight gradients (tuning.wgrad_lane), made on first use
         self._wgrad_parked = []         # [(event after a weight gradient on that stream, tensors it reads)] not yet joined
+        self._max: Optional[MaxStructures] = None      # the max aggregation's structures, built at the first forward_max / backward_max
 
     # ------------------------------------------------------------------
     def wgrad_lane(self, launch, reads, join_now=False):
@@ -557,6 +645,83 @@ class AggregationEngine(BoundaryExchange):
         """Parallel-GCN's backward (main.c:343-404): exchange rows of G with the FORWARD
         maps and apply A (valid when A = A^T)."""
         return self.forward(G)
+
+    # ------------------------------------------------------------------
+    # max aggregation (csrc/pgcn_aggmax.hip; DESIGN.md section 4): OUT[i, c] = max over the stored columns j of row i of H[j, c], ARG the
+    # smallest GLOBAL id that attains it -- the same bits under any part vector, numbering and split into local / halo structures
+    def _max_structures(self) -> MaxStructures:
+        """Built once, at the first max call: an engine that only sums never holds them.  The route is chosen here, before the first
+        launch: the provider's kernels on a HIP device, else the composed framework route (same definition, same OUT / ARG bits)."""
+        if self._max is None:
+            part, k = self.part, self.k
+            if part.n >= 2 ** 31:
+                raise ValueError("max aggregation keeps global ids as int32: n = %d >= 2^31 is not supported" % part.n)
+            composed = not (self.on_gpu and all(hasattr(k, m) for m in ("prepare_max", "aggmax", "aggmax_backward")))
+            if composed:
+                fwd = lambda a, gid: composed_max_csr(a, gid, self.device)
+            else:
+                fwd = lambda a, gid: k.prepare_max(a, gid)
+            if part.A_loc_T is None:
+                loc_T, halo_T = None, []
+            else:
+                loc_T, halo_T = fwd(part.A_loc_T, None), [fwd(a, None) for a in part.A_halo_T]
+            self._max = MaxStructures(composed, fwd(part.A_loc, part.owned), [fwd(a, part.halo_global) for a in part.A_halo],
+                                      loc_T, halo_T, part.owned.to(self.device, torch.int32).contiguous(),
+                                      part.halo_global.to(self.device, torch.int32).contiguous())
+        return self._max
+
+    def forward_max(self, H: torch.Tensor):
+        """(OUT, ARG): the element-wise max of H over every owned vertex's stored neighbourhood (stored values ignored) and the
+        global id that attains it (int32; -1 and 0.0 for a vertex without neighbours).  The exchange is ``forward``'s."""
+        if H.shape[0] != self.n_local:
+            raise ValueError("H must hold exactly the %d owned rows" % self.n_local)
+        m = self._max_structures()
+        run = aggmax_composed if m.composed else self.k.aggmax
+        H = H.contiguous()
+        f = H.shape[1]
+        OUT = torch.empty((self.n_local, f), dtype=torch.float32, device=self.device)
+        ARG = torch.empty((self.n_local, f), dtype=torch.int32, device=self.device)
+        if self.size == 1:
+            return run(m.loc, H, OUT, ARG)
+        send = self._slab("send", self.n_send, f)
+        halo = self._slab("halo", self.n_halo, f)
+        self.k.gather_rows(H, self.send_idx, send)
+        waits = self._exchange_all(send, self.round_send_off, halo, self.round_recv_off, f, tag="forward")
+        run(m.loc, H, OUT, ARG)                  # overlaps the exchange
+        for r in range(self.rounds):
+            waits[r]()
+            run(m.halo[r], halo, OUT, ARG, accumulate=True)      # round r's candidates join the local result; overlaps round r+1
+        return OUT, ARG
+
+    def backward_max(self, G: torch.Tensor, ARG: torch.Tensor) -> torch.Tensor:
+        """dH[j, c] = sum of G[i, c] over the vertices i whose ARG[i, c] is j: every gradient element goes to the one neighbour that
+        won.  Partial sums for rows owned by peers travel home like ``backward``'s and are ADDED."""
+        m = self._max_structures()
+        if m.loc_T is None:
+            raise RuntimeError("partition was built without the transposed pieces")
+        run = aggmax_backward_composed if m.composed else self.k.aggmax_backward
+        G = G.contiguous()
+        f = G.shape[1]
+        dH = torch.empty((self.n_local, f), dtype=torch.float32, device=self.device)
+        if self.size == 1:
+            return run(m.loc_T, m.owned, G, ARG, dH)
+        partial = self._slab("halo", self.n_halo, f)
+        back = self._slab("send", self.n_send, f)
+        ready = []
+        for r in range(self.rounds):
+            b0, b1 = self.round_recv_off[r][0], self.round_recv_off[r][-1]
+            run(m.halo_T[r], m.halo_global[b0:b1], G, ARG, partial[b0:b1])
+            if self.overlap:
+                ev = torch.cuda.Event()
+                ev.record(torch.cuda.current_stream(self.device))
+                ready.append(ev)
+        waits = self._exchange_all(partial, self.round_recv_off, back, self.round_send_off, f,
+                                   ready if self.overlap else None, tag="backward")
+        run(m.loc_T, m.owned, G, ARG, dH)
+        for r in range(self.rounds):
+            waits[r]()
+            self.k.spmm(self.unpack[r], back, dH, accumulate=True)      # returned rows are sums: backward's unpack
+        return dH
 
     # ------------------------------------------------------------------
     def alg_bytes_forward(self, f: int) -> int:

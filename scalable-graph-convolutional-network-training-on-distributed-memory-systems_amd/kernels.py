@@ -139,6 +139,37 @@ class DeviceCore:
     nnz: int
 
 
+@dataclass
+class DeviceMaxCSR:
+    """The WHOLE pattern of a block as plain CSR for the max aggregation (pgcn_aggmax.hip; ``HipKernels.prepare_max``), with its
+    plan: unsliced, or XCD-sliced like the sum path's structures (the entries of a row grouped by col % nslices).  Forward structures
+    hold ``pairs`` (col, global id of col); transposed ones ``col`` alone."""
+    nrows: int
+    ncols: int
+    nnz: int
+    rowptr: torch.Tensor                    # int64 [nrows + 1]
+    pairs: Optional[torch.Tensor] = None    # int32 [nnz, 2] {col, global id of col}
+    col: Optional[torch.Tensor] = None      # int32 [nnz]
+    tasks: Optional[torch.Tensor] = None    # int32 [ntasks, 4] (None: one task per row)
+    fix: Optional[torch.Tensor] = None      # int32 [nfix, 4]
+    ntasks: int = 0
+    nfix: int = 0
+    nslots: int = 0
+    nslices: int = 1
+    seg: Optional[object] = None            # ctypes int64[nslices + 1] (host): task segment bounds of a sliced plan
+    slot_row: Optional[torch.Tensor] = None  # int32 [nslots] row of every slot (transposed structures)
+    ws: Optional[torch.Tensor] = None       # work-space of the cut rows (grown on demand)
+    retired_ws: list = field(default_factory=list)
+    launch_cache: dict = field(default_factory=dict)
+
+    def alg_bytes(self, f: int, backward: bool = False) -> int:
+        """Compulsory HBM bytes of one launch: the index stream (8 B per entry forward, 4 B backward), the row pointers, every
+        operand row once (G and ARG backward) and the rows written (OUT and ARG forward)."""
+        if backward:
+            return 4 * self.nnz + 8 * (self.nrows + 1) + 2 * 4 * f * self.ncols + 4 * f * self.nrows
+        return 8 * self.nnz + 8 * (self.nrows + 1) + 4 * f * self.ncols + 2 * 4 * f * self.nrows
+
+
 def build_plan(rowptr_host: np.ndarray, chunk: int, slice_cnt: Optional[np.ndarray] = None,
                small_row: int = DEFAULT_SMALL_ROW, force: bool = False,
                row_flags: Optional[np.ndarray] = None, ngroups: int = 1,
@@ -558,6 +589,192 @@ class HipKernels:
             produce(B, C)
             fixup(C)
         return hybrid
+
+    # -- max aggregation (pgcn_aggmax.hip) -----------------------------------
+    def prepare_max(self, csr: HostCSR, col_gid: Optional[torch.Tensor] = None, chunk: Optional[int] = None,
+                    nslices: Optional[int] = None) -> DeviceMaxCSR:
+        """The whole pattern of ``csr`` (partition.full_csr: the strips and blocks cannot take a max) as plain CSR over its OUTPUT
+        rows, stored values dropped.  ``col_gid`` (int [ncols], global id of every column): a forward structure for ``aggmax``;
+        None: a transposed structure for ``aggmax_backward``.  ``chunk``: entries per task of a long row (tuning.aggmax_chunk).
+        ``nslices``: 1 = the unsliced plan, 8 = the XCD-sliced one (every XCD's L2 then holds one slice of the operand rows); None:
+        partition.pick_nslices -- sliced from tuning.slice_min_cols columns on, like the sum path's structures."""
+        from .partition import full_csr, pick_nslices
+        dev = self.device
+        rowptr, col, _ = full_csr(csr)
+        nrows, nnz = int(rowptr.numel()) - 1, int(col.numel())
+        S = pick_nslices(csr.ncols) if nslices is None else int(nslices)
+        if not 1 <= S <= _lib.MAX_SLICES:
+            raise _lib.PgcnError("prepare_max: nslices must lie in 1 .. %d, got %d" % (_lib.MAX_SLICES, S))
+        gid = None
+        if col_gid is not None:
+            gid = torch.as_tensor(col_gid).to(col.device, torch.int64)
+            if gid.numel() < csr.ncols:
+                raise _lib.PgcnError("prepare_max: col_gid has %d entries, the block has %d columns" % (gid.numel(), csr.ncols))
+            if gid.numel() and (int(gid.min()) < 0 or int(gid.max()) >= 2 ** 31):
+                raise _lib.PgcnError("prepare_max: global ids must lie in [0, 2^31): ARG is int32")
+        slice_cnt = None
+        if nrows and nnz and (S > 1 or gid is not None):
+            # every row's entries grouped by col % S; inside a group in ascending global id (forward: what lets the kernel keep the
+            # first of equal values inside a task) or in ascending column (transposed)
+            c64 = col.to(torch.int64)
+            lens = rowptr[1:] - rowptr[:-1]
+            key = torch.repeat_interleave(torch.arange(nrows, device=col.device), lens) * S + c64 % S
+            if S > 1:
+                slice_cnt = torch.bincount(key, minlength=nrows * S).view(nrows, S).to(torch.int32).cpu().numpy()
+            if gid is not None:
+                # (a row of at most small_row entries is ONE unsliced task of the plan: ascending over the whole row, not per group)
+                key = torch.where(torch.repeat_interleave(lens > self.small_row, lens), key, key - c64 % S)
+                order = torch.argsort(gid[c64])
+                order = order[torch.argsort(key[order], stable=True)]
+            else:
+                order = torch.argsort(key, stable=True)
+            col = col[order]
+            del c64, key, order
+        rowptr, col = rowptr.cpu(), col.cpu().to(torch.int32)
+        top = _T.aggmax_chunk if chunk is None else int(chunk)
+        if top < 1:
+            raise _lib.PgcnError("prepare_max: chunk must be >= 1, got %d" % top)
+        chunk = top
+        if self.adaptive_chunk:
+            e = max(nnz, 1) // 8192
+            chunk = min(top, max(64, 1 << max(e.bit_length() - 1, 0)))
+        tasks, fix, nslots, seg = None, None, 0, None
+        if nrows:
+            tasks, fix, nslots, seg = build_plan(rowptr.numpy(), chunk, slice_cnt, self.small_row)
+        d = DeviceMaxCSR(nrows=nrows, ncols=csr.ncols, nnz=nnz, rowptr=rowptr.to(dev, torch.int64).contiguous())
+        if gid is not None:
+            g32 = gid.cpu()[col.to(torch.int64)].to(torch.int32)
+            # what the kernel relies on, checked against the plan itself: no task holds a descent of global ids
+            if nnz > 1:
+                breaks = np.concatenate([[0], np.cumsum(np.diff(g32.numpy().astype(np.int64)) <= 0)])       # descents before entry k
+                if tasks is not None:
+                    kbeg = (tasks[:, 1].astype(np.int64) << 32) | (tasks[:, 0].astype(np.int64) & 0xffffffff)
+                    tlen = tasks[:, 2].astype(np.int64)
+                else:
+                    kbeg, tlen = rowptr.numpy()[:-1], np.diff(rowptr.numpy())
+                live = tlen > 1
+                if (breaks[(kbeg + tlen - 1)[live]] != breaks[kbeg[live]]).any():
+                    raise _lib.PgcnError("prepare_max: a task of the plan holds entries out of global-id order")
+            d.pairs = torch.stack([col, g32], 1).contiguous().to(dev)
+        else:
+            d.col = col.contiguous().to(dev)
+        if tasks is not None:
+            d.tasks = torch.from_numpy(tasks).to(dev)
+            d.fix = torch.from_numpy(np.ascontiguousarray(fix)).to(dev) if fix.shape[0] else None
+            d.ntasks, d.nfix, d.nslots = tasks.shape[0], fix.shape[0], nslots
+            if slice_cnt is not None:
+                d.nslices, d.seg = S, seg
+            if col_gid is None and nslots > 0:
+                cnt = fix[:, 2].astype(np.int64)       # the slots of a row are consecutive from fix[:, 1] on
+                pos = np.repeat(fix[:, 1].astype(np.int64), cnt) + np.arange(int(cnt.sum())) - np.repeat(np.cumsum(cnt) - cnt, cnt)
+                srow = np.zeros(nslots, dtype=np.int32)
+                srow[pos] = np.repeat(fix[:, 0], cnt)
+                d.slot_row = torch.from_numpy(srow).to(dev)
+        else:
+            d.ntasks = nrows
+        return d
+
+    def _max_operand(self, t: torch.Tensor, rows: int, dtype, what: str):
+        if not (t.is_cuda and t.dtype is dtype and t.dim() == 2 and (t.shape[1] == 1 or t.stride(1) == 1) and t.stride(0) >= t.shape[1]):
+            raise _lib.PgcnError("%s must be a row-major %s CUDA matrix" % (what, str(dtype).replace("torch.", "")))
+        if t.shape[0] < rows:
+            raise _lib.PgcnError("%s has %d rows, need %d" % (what, t.shape[0], rows))
+
+    def _max_fpass(self, A: DeviceMaxCSR, f: int) -> int:
+        """The 64-feature passes of the gather kernels under ``spmm``'s rule (tuning.fpass: "auto" = whole graphs at f > 64)."""
+        if self.fpass == "auto":
+            return _lib.SPMM_FPASS64 if (f > 64 and A.ncols * f * 4 >= (96 << 20) and A.nnz >= 8_000_000) else 0
+        return 0            # ("64": base_flags carries it)
+
+    def _max_ws(self, A: DeviceMaxCSR, nbytes: int):
+        if nbytes and (A.ws is None or A.ws.numel() < nbytes):
+            if A.ws is not None:
+                A.retired_ws.append(A.ws)           # (a binding made earlier still launches into it)
+            A.ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+            A.launch_cache.clear()
+        return _ptr(A.ws), (0 if A.ws is None else A.ws.numel())
+
+    def aggmax(self, A: DeviceMaxCSR, B: torch.Tensor, OUT: torch.Tensor, ARG: torch.Tensor, accumulate: bool = False):
+        """(OUT, ARG) of the element-wise max over the stored columns of every row of ``A`` (include/pgcn_hip.h,
+        pgcn_aggmax_csr_plan_f32) on the current stream; ``accumulate``: the rows' current (OUT, ARG) are candidates too.  Bound once
+        per shape like ``spmm``.  Rows beyond ``A.nrows`` are not touched."""
+        if A.pairs is None:
+            raise _lib.PgcnError("aggmax needs a structure made by prepare_max(csr, col_gid)")
+        key = (B.stride(0), OUT.stride(0), ARG.stride(0), B.shape[1], bool(accumulate))
+        fn = A.launch_cache.get(key)
+        if fn is None:
+            f = B.shape[1]
+            self._max_operand(B, A.ncols, torch.float32, "B")
+            self._max_operand(OUT, A.nrows, torch.float32, "OUT")
+            self._max_operand(ARG, A.nrows, torch.int32, "ARG")
+            if OUT.shape[1] != f or ARG.shape[1] != f:
+                raise _lib.PgcnError("B, OUT and ARG widths differ")
+            ldb, ldo, lda = max(B.stride(0), f), max(OUT.stride(0), f), max(ARG.stride(0), f)
+            nrows = A.nrows
+            if nrows == 0 or (A.nnz == 0 and accumulate):
+                fn = lambda B, OUT, ARG: None
+            elif A.nnz == 0:            # nothing to launch: every row is empty (memsets, plumbing)
+                def fn(B, OUT, ARG):
+                    OUT[:nrows].zero_()
+                    ARG[:nrows].fill_(-1)
+            else:
+                flags = self.base_flags | (_lib.SPMM_ACCUMULATE if accumulate else 0) | self._max_fpass(A, f)
+                if (A.ncols + 1) * ldb * 4 < 2 ** 32:
+                    flags |= _lib.SPMM_OFFSETS32
+                ws, ws_n = self._max_ws(A, A.nslots * f * 8)
+                lib, check, stream = self.lib, _lib.check, self._stream
+                rowptr, pairs, tasks, ntasks, fix, nfix, nslots = (A.rowptr.data_ptr(), A.pairs.data_ptr(), _ptr(A.tasks), A.ntasks,
+                                                                   _ptr(A.fix), A.nfix, A.nslots)
+                seg, nslices = A.seg, A.nslices
+
+                def fn(B, OUT, ARG):
+                    check(lib.pgcn_aggmax_csr_plan_f32(rowptr, pairs, tasks, ntasks, seg, nslices, fix, nfix, B.data_ptr(), ldb, OUT.data_ptr(), ldo,
+                                                       ARG.data_ptr(), lda, f, ws, ws_n, nslots, flags, stream()),
+                          "pgcn_aggmax_csr_plan_f32")
+            A.launch_cache[key] = fn
+        fn(B, OUT, ARG)
+        return OUT, ARG
+
+    def aggmax_backward(self, AT: DeviceMaxCSR, row_gid: torch.Tensor, G: torch.Tensor, ARG: torch.Tensor, D: torch.Tensor):
+        """D[r] = sum over the stored entries i of row r of the transposed structure of (ARG[i] == row_gid[r] ? G[i] : 0), element-wise
+        (pgcn_aggmax_backward_csr_plan_f32): deterministic, D is written.  ``row_gid``: int32 [AT.nrows] on the device."""
+        if AT.col is None:
+            raise _lib.PgcnError("aggmax_backward needs a structure made by prepare_max(csr) without col_gid")
+        if not (row_gid.is_cuda and row_gid.dtype is torch.int32 and row_gid.dim() == 1 and row_gid.is_contiguous()
+                and row_gid.numel() >= AT.nrows):
+            raise _lib.PgcnError("row_gid must be a contiguous int32 CUDA vector of at least %d entries" % AT.nrows)
+        key = (G.stride(0), ARG.stride(0), D.stride(0), G.shape[1])
+        fn = AT.launch_cache.get(key)
+        if fn is None:
+            f = G.shape[1]
+            self._max_operand(G, AT.ncols, torch.float32, "G")
+            self._max_operand(ARG, AT.ncols, torch.int32, "ARG")
+            self._max_operand(D, AT.nrows, torch.float32, "D")
+            if ARG.shape[1] != f or D.shape[1] != f:
+                raise _lib.PgcnError("G, ARG and D widths differ")
+            ldg, lda, ldd = max(G.stride(0), f), max(ARG.stride(0), f), max(D.stride(0), f)
+            nrows = AT.nrows
+            if nrows == 0:
+                fn = lambda gid, G, ARG, D: None
+            elif AT.nnz == 0:
+                fn = lambda gid, G, ARG, D: D[:nrows].zero_()
+            else:
+                flags = self.base_flags | self._max_fpass(AT, f)
+                if (AT.ncols + 1) * max(ldg, lda) * 4 < 2 ** 32:
+                    flags |= _lib.SPMM_OFFSETS32
+                ws, ws_n = self._max_ws(AT, AT.nslots * f * 4)
+                lib, check, stream = self.lib, _lib.check, self._stream
+                rowptr, col, srow, tasks, ntasks, fix, nfix, nslots = (AT.rowptr.data_ptr(), AT.col.data_ptr(), _ptr(AT.slot_row),
+                                                                       _ptr(AT.tasks), AT.ntasks, _ptr(AT.fix), AT.nfix, AT.nslots)
+                seg, nslices = AT.seg, AT.nslices
+
+                def fn(gid, G, ARG, D):
+                    check(lib.pgcn_aggmax_backward_csr_plan_f32(rowptr, col, gid.data_ptr(), srow, tasks, ntasks, seg, nslices, fix, nfix, G.data_ptr(),
+                                                                ldg, ARG.data_ptr(), lda, D.data_ptr(), ldd, f, ws, ws_n // 4, nslots,
+                                                                flags, stream()), "pgcn_aggmax_backward_csr_plan_f32")
+            AT.launch_cache[key] = fn
+        fn(row_gid, G, ARG, D)
+        return D
 
     # -- GAT path (pgcn_gat.hip) ---------------------------------------------
     def prepare_gat(self, csr: HostCSR, rows_wave: torch.Tensor, rows_block: torch.Tensor, chunk: Optional[int] = None,

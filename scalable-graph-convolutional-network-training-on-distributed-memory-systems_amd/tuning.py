@@ -29,6 +29,8 @@ class Tuning:
     group_min_row: int = 4096        # column groups (explicit `ngroups` only) cut rows at least this long
     fpass: str = "auto"              # 64-feature passes of the gather part: auto (whole graphs, f > 64) | 64 | 0
     xcd_swizzle: bool = True         # unsliced plans: one contiguous row range per XCD
+    aggmax_chunk: int = 1024         # max aggregation (pgcn_aggmax.hip): entries per task of a long row of its plain, unsliced plans (forward and
+                                     # transposed), shrunk on small blocks like spmm_chunk; not swept yet: the sum path's value
     # ---- XCD-sliced storage ---------------------------------------------------------------------------------
     slices: int = 8                  # = XCDs of an MI355X
     slice_min_cols: int = 16384      # narrower operands fit one L2: stored unsliced
