@@ -682,6 +682,32 @@ int pgcn_combine_backward_f32(const float *G, int64_t ldg, const float *Y, int64
                               float scale, float *Gm, int64_t ldgm, float *dbias, void *ws, int64_t ws_bytes,
                               pgcn_stream_t stream);
 
+/* ---- personalised-PageRank propagation of the logits (APPNP; PGCN.py: PPropagate; no counterpart in the reference) ----
+ * Z^0 = H, Z^{k+1} = (1 - alpha) A Z^k + alpha H (k = 0 .. K-1), output Z^K.  The aggregation is the engine's; these kernels are the
+ * element-wise half of a step and of the adjoint's.  a = alpha (fp32), b = 1.0f - a, both formed on the host, once; every operation
+ * below is rounded to fp32 on its own (no fma), fl() marks one rounding.
+ *
+ * pgcn_ppr_step_f32:  Y[i,j] = fl(fl(b S[i,j]) + fl(a H[i,j])), S the aggregation of the previous iterate.  Y may be S (or H) itself,
+ *   with equal leading dimensions.
+ * pgcn_ppr_step_backward_f32: one step of G^{k-1} = (1 - alpha) A^T G^k, dH = alpha sum_{k=1..K} G^k + G^0; T = A^T G is the caller's.
+ *   acc = D ? fl(D + fl(a G)) : fl(a G) (D NULL: the first step, nothing is added);
+ *   last == 0: Dout = acc and Gout = fl(b T);   last != 0: Dout = fl(acc + fl(b T)), the input gradient -- Gout is not written and may
+ *   be NULL.  Gout may be T (or G) and Dout may be D (or G, T) themselves, with equal leading dimensions; Gout and Dout differ.
+ *
+ * Both: the layout of the row-band kernels (256 threads, four consecutive columns per thread, 128 rows per block, 64-bit row
+ * addresses); f from 1 to 1024 (PGCN_EUNSUPPORTED above); float4 when f % 4 == 0 and every base and leading dimension keeps rows
+ * 16-byte aligned, four guarded scalars otherwise, the same bits either way.  Contiguous operands (every leading dimension == f)
+ * of a width that is no multiple of 4 run through the same kernels as rows of 128 columns and one short last row -- element-wise
+ * work, the same bits, float4 traffic: two launches.  A NaN or inf stays in its own element.  Otherwise one launch; nrows == 0:
+ * none.  PGCN_EINVAL, nothing launched: a null required pointer (nrows > 0: an empty operand has none), nrows < 0, f < 1, a leading
+ * dimension below f, in place with differing leading dimensions, alpha not finite or outside [0, 1).  Raw pointers + a stream, no
+ * allocation, no synchronisation (graph-capturable).                                                                       */
+int pgcn_ppr_step_f32(const float *S, int64_t lds, const float *H, int64_t ldh, int64_t nrows, int32_t f, float alpha, float *Y,
+                      int64_t ldy, pgcn_stream_t stream);
+int pgcn_ppr_step_backward_f32(const float *G, int64_t ldg, const float *T, int64_t ldt, const float *D, int64_t ldd, int64_t nrows,
+                               int32_t f, float alpha, int32_t last, float *Gout, int64_t ldgo, float *Dout, int64_t lddo,
+                               pgcn_stream_t stream);
+
 /* ---- the tail of a GAT layer: head mean, bias, ELU and dropout (PGAT.py: _GatTail) ------------------------------------
  * A GAT layer ends with drop(act(reduce_heads(X) + b)); X is the nrows x heads * d output of the aggregation on OWNED rows, the
  * heads side by side.  The output width is fout = mean ? d : heads * d.

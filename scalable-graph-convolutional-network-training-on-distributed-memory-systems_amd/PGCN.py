@@ -219,6 +219,52 @@ class PAggMax(torch.autograd.Function):
         return None, dH
 
 
+class PPropagate(torch.autograd.Function):
+    """Personalised-PageRank propagation of the logits (APPNP: predict, then propagate; csrc/pgcn_propagate.hip): Z^0 = H,
+    Z^{k+1} = (1 - alpha) A Z^k + alpha H, output Z^K -- forward ``A.propagate`` (K aggregations at the width of H, each with the
+    halo exchange, each followed by one element-wise pass), backward its exact adjoint ``A.propagate_backward``.  The map is linear in
+    H: nothing is saved.  An input that needs no gradient is not propagated backward."""
+
+    @staticmethod
+    def forward(ctx, A, H, K, alpha):
+        ctx.A, ctx.K, ctx.alpha = A, K, alpha
+        return A.propagate(H, K, alpha)
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        dH = ctx.A.propagate_backward(grad_output, ctx.K, ctx.alpha) if ctx.needs_input_grad[1] else None
+        join = getattr(ctx.A, "join_wgrad", None)        # (as PSpMM.backward: a weight gradient parked on the engine's side stream)
+        if join is not None:
+            join()
+        return None, dH, None, None
+
+
+class Propagate(nn.Module):
+    """``PPropagate`` as the last module of a model: K steps of personalised PageRank with teleport probability ``alpha`` over the
+    engine's stored matrix (meant for a normalised one: on a raw pattern the result grows like ||A||^K).  No parameters, no buffers,
+    the same in ``train()`` and ``eval()``."""
+
+    def __init__(self, A, K, alpha=0.1):
+        super(Propagate, self).__init__()
+        if isinstance(K, bool) or not isinstance(K, int) or K < 1:
+            raise ValueError("propagate takes an integer K >= 1, got %r" % (K,))
+        alpha = float(alpha)
+        if not 0.0 <= alpha < 1.0:
+            raise ValueError("ppr_alpha takes a finite value with 0 <= alpha < 1, got %r" % (alpha,))
+        self.A, self.K, self.alpha = A, K, alpha
+
+    def extra_repr(self):
+        return "K=%d, alpha=%g" % (self.K, self.alpha)
+
+    def forward(self, H):
+        return PPropagate.apply(self.A, H, self.K, self.alpha)
+
+
+def _no_aggregation(A, H):
+    """``PGCN(aggregate=False)``: the layer's input is its own 'aggregation' (a dense layer, the MLP in front of ``Propagate``)."""
+    return H
+
+
 # ---- the dense products by rocBLAS solution index (gemm/pgcn_gemm.cpp) ---------------------------------------------------
 # Plumbing beside the graded path: x . W^T and g . W of a layer are stock rocBLAS GEMMs either way; PyTorch's default pick
 # is 15-20 % slower at the benchmark shapes than the kernel PyTorch's TunableOp finds, but switching TunableOp on
@@ -1314,14 +1360,22 @@ class PGCN(nn.Module):
 
     ``aggr="max"`` (opt-in): the aggregation is ``PAggMax`` -- the element-wise max over the stored neighbourhood, stored values
     ignored -- instead of ``PSpMM``; every other option composes unchanged and the layer owns the same parameters.  None or "sum":
-    the branches of before."""
+    the branches of before.
+
+    ``aggregate=False`` (opt-in): the layer does not aggregate -- act(H W^T ...), a dense layer over the vertices' own rows (the MLP
+    in front of ``Propagate``); no exchange, no engine call.  Every other option composes through the same nodes, and the layer owns
+    the same parameters under the same state-dict keys.  Refused with ``aggr="max"`` (nothing to take a max over) and with
+    ``root_weight=True`` (the root product IS this layer).  True: the branches of before."""
 
     def __init__(self, A, in_features, out_features, dropout=0.0, layer=0, state=None, relu=True, norm=None, root_weight=False, bias=False,
-                 residual=False, aggr=None):
+                 residual=False, aggr=None, aggregate=True):
         super(PGCN, self).__init__()
         if aggr not in AGGRS + (None,):
             raise ValueError("aggr takes %s, got %r" % (" | ".join(AGGRS), aggr))
-        self._aggregate = PAggMax.apply if aggr == "max" else PSpMM.apply
+        self.aggregate = bool(aggregate)
+        if not self.aggregate and (aggr == "max" or root_weight):
+            raise ValueError("aggregate=False does not go with %s" % ('aggr="max"' if aggr == "max" else "root_weight=True"))
+        self._aggregate = _no_aggregation if not self.aggregate else PAggMax.apply if aggr == "max" else PSpMM.apply
         self.linear = nn.Linear(in_features, out_features, bias=False)
         self.A = A
         self.send_map = send_map
@@ -1574,11 +1628,30 @@ def _barrier():
         _all_reduce(torch.zeros(1, device=device)).item()
 
 
-def _architecture(fin, classes, nlayers, nfeatures, hidden, multilabel, dropout, dropout_seed, norm, root_weight, bias, residual, aggr=None):
+def _architecture(fin, classes, nlayers, nfeatures, hidden, multilabel, dropout, dropout_seed, norm, root_weight, bias, residual, aggr=None,
+                  propagate=None, ppr_alpha=None, dense_layers=None):
     """checkpoint.architecture of the model ``_train_on_data`` builds from these arguments."""
     widths = [int(fin)] + [int(nfeatures if hidden is None else hidden)] * (nlayers - 1) + [int(classes)]
     return _checkpoint.architecture(widths, "multilabel" if multilabel else "single", dropout, dropout_seed, norm, root_weight, bias,
-                                    residual, **({"aggr": aggr} if aggr == "max" else {}))
+                                    residual, **({"aggr": aggr} if aggr == "max" else {}),
+                                    **({"propagate": (propagate, PPR_ALPHA if ppr_alpha is None else ppr_alpha)} if propagate is not None else {}),
+                                    **({"dense_layers": True} if dense_layers else {}))
+
+
+PPR_ALPHA = 0.1                        # --ppr-alpha / run(ppr_alpha=...): the teleport probability of --propagate when none is given
+
+
+def _check_propagate(propagate, ppr_alpha, dense_layers, aggr=None, root_weight=None):
+    """ValueError for values of run's ``propagate`` / ``ppr_alpha`` / ``dense_layers`` that no model can be built from."""
+    if propagate is not None and (isinstance(propagate, bool) or not isinstance(propagate, int) or propagate < 1):
+        raise ValueError("propagate takes an integer >= 1, got %r" % (propagate,))
+    if ppr_alpha is not None:
+        if propagate is None:
+            raise ValueError("ppr_alpha needs propagate")
+        if isinstance(ppr_alpha, bool) or not isinstance(ppr_alpha, (int, float)) or not 0.0 <= float(ppr_alpha) < 1.0:
+            raise ValueError("ppr_alpha takes a finite number with 0 <= alpha < 1, got %r" % (ppr_alpha,))
+    if dense_layers and (aggr == "max" or root_weight):
+        raise ValueError("dense_layers does not go with %s" % ('aggr="max"' if aggr == "max" else "root_weight"))
 
 
 TASKS = tuple(_nodeloss.TASKS)         # --task / run(task=...): "single", one class per vertex (the default), or "multilabel"
@@ -1587,7 +1660,8 @@ OPTIMIZERS = _nodeloss.OPTIMIZERS      # --optimizer / run(optimizer=...): "torc
 
 def _train_on_data(A, n, nlayers, nfeatures, features, labels, split, hidden, epochs, lr, eval_every, dropout, dropout_seed,
                    multilabel=False, weight_decay=0.0, decoupled_decay=False, optimizer="torch", norm=None, root_weight=None, bias=None,
-                   residual=None, save=None, load=None, predict=None, proba=None, control=None, aggr=None):
+                   residual=None, save=None, load=None, predict=None, proba=None, control=None, aggr=None, propagate=None, ppr_alpha=None,
+                   dense_layers=None):
     """The loop of ``run`` on real inputs: widths fin -> hidden -> ... -> C, no ReLU on the last layer, constant features (the
     first layer's backward aggregation is skipped), Adam, the masked loss over the train rows.  Reports every ``eval_every``
     epochs: without dropout from the record of the training step's own pass (the logits BEFORE that step's update), with
@@ -1608,7 +1682,11 @@ def _train_on_data(A, n, nlayers, nfeatures, features, labels, split, hidden, ep
     best epoch's weights (``proba``: the probabilities too).  With none of the four nothing is copied and nothing more printed.
     ``control``: the options of nodeloss.CONTROL that were given (gradient clipping, the learning-rate schedule, early stopping:
     ``nodeloss.Control``); None: the loop of before, call for call.  ``aggr="max"``: every layer aggregates by the element-wise max
-    (class PGCN, ``PAggMax``); None or "sum": the weighted sum of before."""
+    (class PGCN, ``PAggMax``); None or "sum": the weighted sum of before.  ``propagate=K`` (``ppr_alpha``, default 0.1): the module
+    ``Propagate`` follows the last layer -- K steps of personalised PageRank over the logits (APPNP); loss, ``evaluate`` and the
+    predictions go through it.  ``dense_layers``: no layer aggregates (``PGCN(aggregate=False)``: the MLP in front of it).  None: the
+    model of before."""
+    _check_propagate(propagate, ppr_alpha, dense_layers, aggr, root_weight)
     task = _nodeloss.TASKS["multilabel" if multilabel else "single"]
     data = task.load(features, labels, split, A.part.owned, n, device=device)
     hidden = int(nfeatures if hidden is None else hidden)
@@ -1627,10 +1705,13 @@ def _train_on_data(A, n, nlayers, nfeatures, features, labels, split, hidden, ep
     extra = dict(({"root_weight": True} if root_weight else {}), **({"bias": True} if bias else {}))       # (neither: the call of before)
     if aggr == "max":
         extra["aggr"] = "max"
+    if dense_layers:
+        extra["aggregate"] = False
+    tail = [Propagate(A, propagate, PPR_ALPHA if ppr_alpha is None else float(ppr_alpha))] if propagate is not None else []
     model = nn.Sequential(*[PGCN(A, widths[i], widths[i + 1], dropout=dropout if i < nlayers - 1 else 0.0, layer=i, state=state,
                                  relu=i < nlayers - 1, **({"norm": norm} if norm not in (None, "none") and i < nlayers - 1 else {}),
                                  **extra, **({"residual": True} if residual and i < nlayers - 1 and widths[i] == widths[i + 1] else {}))
-                            for i in range(nlayers)]).to(device)
+                            for i in range(nlayers)] + tail).to(device)
     initiliaze_parameters(model)
     fused, opt = _nodeloss.make_optimizer(model.parameters(), optimizer, lr, weight_decay, decoupled_decay)
     H, y, s = data.features, data.labels, data.split           # (H needs no gradient)
@@ -1639,7 +1720,7 @@ def _train_on_data(A, n, nlayers, nfeatures, features, labels, split, hidden, ep
     first, history, best, hooks = 0, [], None, None
     if save is not None or load is not None or predict is not None or proba:
         arch = _architecture(data.fin, data.classes, nlayers, nfeatures, hidden, multilabel, dropout, dropout_seed, norm, root_weight,
-                             bias, residual, aggr)
+                             bias, residual, aggr, propagate, ppr_alpha, dense_layers)
         hooks = _checkpoint.Hooks("PGCN", arch, model, fused, opt, state, save, load, predict, proba, myrank, _barrier)
         first, history, best = hooks.resume()
     last = first + epochs - 1
@@ -1695,7 +1776,7 @@ def _train_on_data(A, n, nlayers, nfeatures, features, labels, split, hidden, ep
 def run(rank, size, nlayers, nfeatures, path_A, path_partvec, backend, normalize=None, dropout=0.0, dropout_seed=0,
         features=None, labels=None, split=None, hidden=None, epochs=None, lr=None, eval_every=None, task=None,
         weight_decay=None, decoupled_decay=None, optimizer=None, norm=None, root_weight=None, bias=None, residual=None,
-        save=None, load=None, predict=None, proba=None, aggr=None, **control):
+        save=None, load=None, predict=None, proba=None, aggr=None, propagate=None, ppr_alpha=None, dense_layers=None, **control):
     """PGCN.py:162-238.  ``normalize="sym"``: train on D_r^-1/2 (A + I) D_c^-1/2 of the pattern of ``path_A``, built on the fly
     (partition.build_partition) instead of by the offline pass preprocess/GrB-GNN-IDG.py.  ``dropout`` > 0: the output of every
     layer but the last is dropped with that probability (class PGCN), masks from (``dropout_seed``, step, layer, global row,
@@ -1725,7 +1806,13 @@ def run(rank, size, nlayers, nfeatures, path_A, path_partvec, backend, normalize
     ``nodeloss.Control``, optim.py has the definitions.  The history's entries then carry ``lr`` (and ``gnorm``, ``clip``).
     ``aggr`` ("sum", the default, or "max"; needs the three files): every layer aggregates by the element-wise max over a vertex's
     stored neighbourhood instead of the weighted sum (``PAggMax``; the stored values are ignored, with ``normalize="sym"`` a vertex is
-    its own neighbour).  A checkpoint records it: loading one written with the other aggregation raises ValueError naming ``aggr``."""
+    its own neighbour).  A checkpoint records it: loading one written with the other aggregation raises ValueError naming ``aggr``.
+    ``propagate`` (an integer K >= 1; needs the three files): the logits of the last layer are propagated by K steps of personalised
+    PageRank, Z <- (1 - alpha) A Z + alpha H (APPNP; ``Propagate``), with ``ppr_alpha`` (0 <= alpha < 1, default 0.1; needs
+    ``propagate``) the teleport probability.  It uses the stored matrix: meant for ``normalize="sym"`` or a normalised file, on a raw
+    pattern the logits grow like ||A||^K.  ``dense_layers`` (True; needs the three files): no layer aggregates -- with ``propagate``
+    that is APPNP's predict-then-propagate.  A checkpoint records both: loading one under another K, alpha or layer kind raises
+    ValueError naming ``propagate`` / ``dense_layers``."""
     global myrank, world_size, send_map, recv_map, device, X, recv_buffers, send_buffers, stats
     for name in control:
         if name not in _nodeloss.CONTROL:
@@ -1759,6 +1846,9 @@ def run(rank, size, nlayers, nfeatures, path_A, path_partvec, backend, normalize
         raise ValueError("aggr takes %s, got %r" % (" | ".join(AGGRS), aggr))
     if aggr is not None and not all(given):
         raise ValueError("aggr=%r needs features, labels and split" % (aggr,))
+    _check_propagate(propagate, ppr_alpha, dense_layers, aggr, root_weight)
+    if (propagate is not None or ppr_alpha is not None or dense_layers is not None) and not all(given):
+        raise ValueError("propagate, ppr_alpha and dense_layers need features, labels and split")
     if (save is not None or load is not None or predict is not None or proba is not None) and not all(given):
         raise ValueError("save, load, predict and proba need features, labels and split")
     if proba and predict is None:
@@ -1783,7 +1873,7 @@ def run(rank, size, nlayers, nfeatures, path_A, path_partvec, backend, normalize
         opened = _nodeloss.TASKS[task or "single"].open_checked(features, labels, split, len(partvec))
         if load is not None:
             arch = _architecture(opened[3], opened[4], nlayers, nfeatures, hidden, multilabel, dropout, dropout_seed, norm, root_weight,
-                                 bias, residual, aggr)
+                                 bias, residual, aggr, propagate, ppr_alpha, dense_layers)
             load = _checkpoint.load(load, "PGCN", arch, optimizer or "torch")
         del opened
         if control and load is not None:        # (the horizon against the warm-up, from the epoch the checkpoint stands at)
@@ -1833,7 +1923,9 @@ def run(rank, size, nlayers, nfeatures, path_A, path_partvec, backend, normalize
                               **({"root_weight": True} if root_weight else {}), **({"bias": True} if bias else {}),
                               **({"residual": True} if residual else {}),
                               **{k: v for k, v in (("save", save), ("load", load), ("predict", predict), ("proba", proba)) if v is not None},
-                              **({"control": control} if control else {}), **({"aggr": "max"} if aggr == "max" else {}))
+                              **({"control": control} if control else {}), **({"aggr": "max"} if aggr == "max" else {}),
+                              **{k: v for k, v in (("propagate", propagate), ("ppr_alpha", ppr_alpha)) if v is not None},
+                              **({"dense_layers": True} if dense_layers else {}))
 
     owned = A.part.owned.to(device)
     # PGCN.py:186-188 synthetic features H[i,:] = i, owned rows only
@@ -1909,8 +2001,9 @@ def run(rank, size, nlayers, nfeatures, path_A, path_partvec, backend, normalize
 def init_process(rank, size, fn, nlayers, nfeatures, path_A, path_partvec, backend, normalize=None, dropout=0.0, dropout_seed=0,
                  features=None, labels=None, split=None, hidden=None, epochs=None, lr=None, eval_every=None, task=None,
                  weight_decay=None, decoupled_decay=None, optimizer=None, norm=None, root_weight=None, bias=None, residual=None,
-                 save=None, load=None, predict=None, proba=None, control=None, aggr=None):
-    """PGCN.py:241-253.  ``control``: the given options of nodeloss.CONTROL as one dict (None: today's call).  ``aggr``: run's."""
+                 save=None, load=None, predict=None, proba=None, control=None, aggr=None, propagate=None, ppr_alpha=None, dense_layers=None):
+    """PGCN.py:241-253.  ``control``: the given options of nodeloss.CONTROL as one dict (None: today's call).  ``aggr``, ``propagate``,
+    ``ppr_alpha``, ``dense_layers``: run's."""
     global _exchanger
     dist.init_process_group(backend, rank=rank, world_size=size)
 
@@ -1928,7 +2021,8 @@ def init_process(rank, size, fn, nlayers, nfeatures, path_A, path_partvec, backe
     for name, v in (("features", features), ("labels", labels), ("split", split), ("hidden", hidden), ("epochs", epochs), ("lr", lr),
                     ("eval_every", eval_every), ("task", task), ("weight_decay", weight_decay), ("decoupled_decay", decoupled_decay),
                     ("optimizer", optimizer), ("norm", norm), ("root_weight", root_weight), ("bias", bias),
-                    ("residual", residual), ("save", save), ("load", load), ("predict", predict), ("proba", proba), ("aggr", aggr)):
+                    ("residual", residual), ("save", save), ("load", load), ("predict", predict), ("proba", proba), ("aggr", aggr),
+                    ("propagate", propagate), ("ppr_alpha", ppr_alpha), ("dense_layers", dense_layers)):
         if v is not None:
             kw[name] = v
     kw.update(control or {})
@@ -1955,7 +2049,7 @@ def main(argv):
         opts, args = getopt.getopt(argv, "a:p:b:s:l:f:", ["normalize=", "dropout=", "dropout-seed=", "features=", "labels=", "split=",
                                                           "hidden=", "epochs=", "lr=", "eval-every=", "task=", "weight-decay=", "adamw",
                                                           "optimizer=", "norm=", "root-weight", "bias", "residual", "save=", "load=",
-                                                          "predict=", "proba", "aggr="] + [f[2:] + "=" for f in _nodeloss.CONTROL_FLAGS.split(", ")])
+                                                          "predict=", "proba", "aggr=", "propagate=", "ppr-alpha=", "dense-layers"] + [f[2:] + "=" for f in _nodeloss.CONTROL_FLAGS.split(", ")])
     except getopt.GetoptError:
         print("a:p:b:", flush=True)
         sys.exit(2)
@@ -2027,6 +2121,24 @@ def main(argv):
                 sys.exit(2)
             if arg != "sum" or "aggr" in data:
                 data["aggr"] = arg
+        elif opt == '--propagate':     # K steps of personalised PageRank over the logits of the last layer (APPNP: class Propagate)
+            try:
+                data["propagate"] = int(arg)
+                if data["propagate"] < 1:
+                    raise ValueError
+            except ValueError:
+                print("--propagate takes an integer >= 1, got %r" % arg, flush=True)
+                sys.exit(2)
+        elif opt == '--ppr-alpha':     # the teleport probability of --propagate (0.1)
+            try:
+                data["ppr_alpha"] = float(arg)
+                if not 0.0 <= data["ppr_alpha"] < 1.0:
+                    raise ValueError
+            except ValueError:
+                print("--ppr-alpha takes a number >= 0 and < 1, got %r" % arg, flush=True)
+                sys.exit(2)
+        elif opt == '--dense-layers':  # no layer aggregates (PGCN(aggregate=False)): with --propagate, predict then propagate
+            data["dense_layers"] = True
         elif opt == '--root-weight':   # every layer adds H . W_r^T: a vertex's own features get their own weights (class PGCN)
             data["root_weight"] = True
         elif opt == '--bias':          # every layer adds a bias (a normalised layer keeps bn_bias alone)
@@ -2060,7 +2172,7 @@ def main(argv):
     os.environ.setdefault("WORLD_SIZE", str(size))
     files = [k for k in ("features", "labels", "split") if k in data]
     if data and len(files) != 3:
-        print("--features, --labels and --split go together (and --hidden, --epochs, --lr, --eval-every, --task, --weight-decay, --adamw, --optimizer, --save, --load, --predict, --proba, --aggr, %s, --norm, --residual, --root-weight, --bias need them); got %%s"
+        print("--features, --labels and --split go together (and --hidden, --epochs, --lr, --eval-every, --task, --weight-decay, --adamw, --optimizer, --save, --load, --predict, --proba, --aggr, --propagate, --ppr-alpha, --dense-layers, %s, --norm, --residual, --root-weight, --bias need them); got %%s"
               % _nodeloss.CONTROL_FLAGS % ", ".join("--" + {"decoupled_decay": "adamw"}.get(k, k.replace("_", "-")) for k in sorted(data)), flush=True)
         sys.exit(2)
     for k in files:
@@ -2069,6 +2181,12 @@ def main(argv):
             sys.exit(2)
     if data.get("proba") and "predict" not in data:
         print("--proba needs --predict", flush=True)
+        sys.exit(2)
+    if "ppr_alpha" in data and "propagate" not in data:
+        print("--ppr-alpha needs --propagate", flush=True)
+        sys.exit(2)
+    if "dense_layers" in data and (data.get("aggr") == "max" or "root_weight" in data):
+        print("--dense-layers does not go with %s" % ("--aggr max" if data.get("aggr") == "max" else "--root-weight"), flush=True)
         sys.exit(2)
     if "load" in data and not os.path.exists(data["load"]):
         print("--load: no such file %r" % (data["load"],), flush=True)
@@ -2106,7 +2224,8 @@ def main(argv):
                 args += layer_opts
             if has_residual:                   # (the tuple grows only when --residual is given)
                 args += (True,)
-    p = mp.Process(target=init_process, args=args, **({"kwargs": {"aggr": data["aggr"]}} if "aggr" in data else {}))
+    named = {k: data[k] for k in ("aggr", "propagate", "ppr_alpha", "dense_layers") if k in data}      # (by name, only when given)
+    p = mp.Process(target=init_process, args=args, **({"kwargs": named} if named else {}))
     p.start()
     p.join()
     if p.exitcode != 0:

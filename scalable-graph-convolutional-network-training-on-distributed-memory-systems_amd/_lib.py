@@ -126,6 +126,9 @@ SIGNATURES = {
     "pgcn_combine_forward_f32": (ctypes.c_int, [_vp, _i64, _vp, _i64, _vp, _i64, _i32, _i32, _vp, ctypes.c_uint64, _vp, _u32, _u32, _vp,
                                                 _i64, _vp]),
     "pgcn_combine_backward_f32": (ctypes.c_int, [_vp, _i64, _vp, _i64, _i64, _i32, _i32, ctypes.c_float, _vp, _i64, _vp, _vp, _i64, _vp]),
+    "pgcn_ppr_step_f32": (ctypes.c_int, [_vp, _i64, _vp, _i64, _i64, _i32, ctypes.c_float, _vp, _i64, _vp]),
+    "pgcn_ppr_step_backward_f32": (ctypes.c_int, [_vp, _i64, _vp, _i64, _vp, _i64, _i64, _i32, ctypes.c_float, _i32, _vp, _i64, _vp, _i64,
+                                                  _vp]),
     "pgcn_gat_tail_ws_bytes": (_i64, [_i64, _i32]),
     "pgcn_gat_tail_forward_f32": (ctypes.c_int, [_vp, _i64, _i64, _i32, _i32, _i32, _vp, _i32, _vp, ctypes.c_uint64, _vp, _u32, _u32, _vp,
                                                  _i64, _vp]),

@@ -525,6 +525,44 @@ class MaxStructures:
     halo_global: torch.Tensor
 
 
+# --------------------------------------------------------------------------
+# personalised-PageRank propagation: the composed route (framework operations; the definitions of csrc/pgcn_propagate.hip)
+
+
+def ppr_coefficients(alpha):
+    """(a, b) = (float32(alpha), 1.0f - a) as Python floats holding exactly those fp32 values: what the kernels form on the host."""
+    a = torch.tensor(float(alpha), dtype=torch.float32)
+    return float(a), float(1.0 - a)
+
+
+def ppr_step_composed(S: torch.Tensor, H: torch.Tensor, alpha: float, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Y of ``HipKernels.ppr_step`` from framework operations, bit for bit: (b S) + (a H), each product and the sum rounded to fp32
+    on its own.  ``out`` may be S itself."""
+    a, b = ppr_coefficients(alpha)
+    return torch.add(S * b, H.detach() * a, out=out)
+
+
+def ppr_step_backward_composed(G: torch.Tensor, T: torch.Tensor, D: Optional[torch.Tensor], alpha: float, last: bool,
+                               gout: Optional[torch.Tensor] = None, dout: Optional[torch.Tensor] = None):
+    """(Gout, Dout) of ``HipKernels.ppr_step_backward`` from framework operations, bit for bit."""
+    a, b = ppr_coefficients(alpha)
+    acc = G.detach() * a
+    if D is not None:
+        acc = D + acc
+    bt = T * b
+    if last:
+        return None, torch.add(acc, bt, out=dout)
+    if dout is None:
+        dout = acc
+    elif dout is not acc:
+        dout.copy_(acc)
+    if gout is None:
+        gout = bt
+    else:
+        gout.copy_(bt)
+    return gout, dout
+
+
 class AggregationEngine(BoundaryExchange):
     """Owns rank p's device-resident pieces and runs the aggregation forward/backward."""
 
@@ -598,8 +636,11 @@ class AggregationEngine(BoundaryExchange):
         if H.shape[0] != self.n_local:
             raise ValueError("H must hold exactly the %d owned rows" % self.n_local)
         H = H.contiguous()
+        return self._forward_into(H, torch.empty((self.n_local, H.shape[1]), dtype=torch.float32, device=self.device))
+
+    def _forward_into(self, H: torch.Tensor, C: torch.Tensor) -> torch.Tensor:
+        """``forward`` of a contiguous H into the caller's C (n_local x f, not H itself)."""
         f = H.shape[1]
-        C = torch.empty((self.n_local, f), dtype=torch.float32, device=self.device)
         if self.size == 1:
             return self.k.spmm(self.A_loc, H, C)
         send = self._slab("send", self.n_send, f)
@@ -617,8 +658,11 @@ class AggregationEngine(BoundaryExchange):
         if self.A_loc_T is None:
             raise RuntimeError("partition was built without the transposed pieces")
         G = G.contiguous()
+        return self._backward_into(G, torch.empty((self.n_local, G.shape[1]), dtype=torch.float32, device=self.device))
+
+    def _backward_into(self, G: torch.Tensor, dH: torch.Tensor) -> torch.Tensor:
+        """``backward`` of a contiguous G into the caller's dH (n_local x f, not G itself)."""
         f = G.shape[1]
-        dH = torch.empty((self.n_local, f), dtype=torch.float32, device=self.device)
         if self.size == 1:
             return self.k.spmm(self.A_loc_T, G, dH)
         partial = self._slab("halo", self.n_halo, f)
@@ -645,6 +689,64 @@ class AggregationEngine(BoundaryExchange):
         """Parallel-GCN's backward (main.c:343-404): exchange rows of G with the FORWARD
         maps and apply A (valid when A = A^T)."""
         return self.forward(G)
+
+    # ------------------------------------------------------------------
+    # personalised-PageRank propagation (APPNP; csrc/pgcn_propagate.hip; DESIGN.md section 4): Z^0 = H, Z^{k+1} = (1 - alpha) A Z^k +
+    # alpha H, output Z^K.  Linear in H: nothing is saved for the adjoint.  K aggregations with ``forward``'s exchange and overlap
+    # (the send / halo slabs are the same), each followed by one element-wise pass; two n_local x f buffers take turns, so besides
+    # the result one (forward) or two (backward) scratch matrices are live, whatever K is.
+    def _ppr_route(self, K, alpha):
+        """(step, step_backward) of the route, chosen before the first launch: the provider's kernels on a HIP device, else the
+        composed framework route with the same arithmetic (CPU tensors, providers without the kernels).  Nothing is built or kept."""
+        if isinstance(K, bool) or not isinstance(K, int) or K < 1:
+            raise ValueError("propagate takes an integer K >= 1, got %r" % (K,))
+        alpha = float(alpha)
+        if not 0.0 <= alpha < 1.0 or ppr_coefficients(alpha)[0] >= 1.0:        # (a NaN fails the comparison; so does +-inf)
+            raise ValueError("propagate takes a finite alpha with 0 <= alpha < 1, got %r" % (alpha,))
+        if self.on_gpu and all(hasattr(self.k, m) for m in ("ppr_step", "ppr_step_backward")):
+            return alpha, self._ppr_kernel(self.k.ppr_step), self._ppr_kernel(self.k.ppr_step_backward)
+        return alpha, ppr_step_composed, ppr_step_backward_composed
+
+    @staticmethod
+    def _ppr_kernel(fn):
+        def run(*args, **kw):
+            out = fn(*args, **kw)
+            if out is None:           # (no quiet second route once the kernels were chosen)
+                raise ValueError("%s does not cover this operand (fp32, unit-stride columns, at most %d of them)"
+                                 % (fn.__name__, 1024))
+            return out
+        return run
+
+    def propagate(self, H: torch.Tensor, K: int, alpha: float) -> torch.Tensor:
+        """Z^K of Z^0 = H, Z^{k+1} = fl(fl(b A Z^k) + fl(a H)) with a = float32(alpha), b = 1 - a  (H: n_local x f, owned rows)."""
+        alpha, step, _ = self._ppr_route(K, alpha)
+        if H.shape[0] != self.n_local:
+            raise ValueError("H must hold exactly the %d owned rows" % self.n_local)
+        H = H.detach().contiguous()
+        bufs = [torch.empty((self.n_local, H.shape[1]), dtype=torch.float32, device=self.device) for _ in range(min(K, 2))]
+        Z = H
+        for k in range(K):
+            S = self._forward_into(Z, bufs[k % 2])
+            Z = step(S, H, alpha, out=S)
+        return Z
+
+    def propagate_backward(self, G: torch.Tensor, K: int, alpha: float) -> torch.Tensor:
+        """The exact adjoint of ``propagate``: dH = alpha sum_{k=1..K} G^k + G^0 with G^K = G, G^{k-1} = (1 - alpha) A^T G^k, one
+        ``backward`` and one element-wise pass per step."""
+        alpha, _, step_backward = self._ppr_route(K, alpha)
+        if self.A_loc_T is None:
+            raise RuntimeError("partition was built without the transposed pieces")
+        if G.shape[0] != self.n_local:
+            raise ValueError("G must hold exactly the %d owned rows" % self.n_local)
+        G = G.detach().contiguous()
+        bufs = [torch.empty((self.n_local, G.shape[1]), dtype=torch.float32, device=self.device) for _ in range(min(K, 2))]
+        D = None
+        for k in range(K):
+            last = k == K - 1
+            T = self._backward_into(G, bufs[k % 2])
+            # (the last step of K = 1 has no D yet: its sum is written over T)
+            G, D = step_backward(G, T, D, alpha, last, gout=None if last else T, dout=D if D is not None else (T if last else None))
+        return D
 
     # ------------------------------------------------------------------
     # max aggregation (csrc/pgcn_aggmax.hip; DESIGN.md section 4): OUT[i, c] = max over the stored columns j of row i of H[j, c], ARG the

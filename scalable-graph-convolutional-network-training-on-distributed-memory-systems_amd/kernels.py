@@ -1571,6 +1571,34 @@ class HipKernels:
                                                       _ptr(dbias), _ptr(ws), ws_bytes, self._stream()), "pgcn_combine_backward_f32")
         return Gm, dbias
 
+    # -- personalised-PageRank propagation: the element-wise half of a step and of its adjoint (csrc/pgcn_propagate.hip) ---------
+    def ppr_step(self, S: torch.Tensor, H: torch.Tensor, alpha: float, out: Optional[torch.Tensor] = None):
+        """Y = fl(fl(b S) + fl(a H)) with a = float32(alpha), b = 1 - a, in one pass (pgcn_ppr_step_f32); S is the aggregation of the
+        previous iterate.  ``out`` may be S itself.  None when the shape is not covered."""
+        if not self._bn_mat_ok(S, H, out):
+            return None
+        n, f = S.shape
+        Y = out if out is not None else torch.empty((n, f), dtype=torch.float32, device=self.device)
+        _lib.check(self.lib.pgcn_ppr_step_f32(S.data_ptr(), self._ld(S), H.data_ptr(), self._ld(H), n, f, float(alpha), Y.data_ptr(),
+                                              self._ld(Y), self._stream()), "pgcn_ppr_step_f32")
+        return Y
+
+    def ppr_step_backward(self, G: torch.Tensor, T: torch.Tensor, D: Optional[torch.Tensor], alpha: float, last: bool,
+                          gout: Optional[torch.Tensor] = None, dout: Optional[torch.Tensor] = None):
+        """(Gout, Dout) of one step of the adjoint recursion from G = G^k and T = A^T G (pgcn_ppr_step_backward_f32): acc = D + a G
+        (``D`` None: a G alone); not ``last``: Dout = acc, Gout = b T; ``last``: Dout = acc + b T, the input gradient, and Gout is
+        None.  ``gout`` may be T and ``dout`` may be D themselves.  None when the shape is not covered."""
+        if not self._bn_mat_ok(G, T, D, dout, None if last else gout):
+            return None
+        n, f = G.shape
+        Gout = None if last else (gout if gout is not None else torch.empty((n, f), dtype=torch.float32, device=self.device))
+        Dout = dout if dout is not None else torch.empty((n, f), dtype=torch.float32, device=self.device)
+        _lib.check(self.lib.pgcn_ppr_step_backward_f32(G.data_ptr(), self._ld(G), T.data_ptr(), self._ld(T), _ptr(D),
+                                                       self._ld(D) if D is not None else 0, n, f, float(alpha), 1 if last else 0,
+                                                       _ptr(Gout), self._ld(Gout) if Gout is not None else 0, Dout.data_ptr(),
+                                                       self._ld(Dout), self._stream()), "pgcn_ppr_step_backward_f32")
+        return Gout, Dout
+
     # -- the tail of a GAT layer: head mean, bias, ELU and dropout (csrc/pgcn_gat_tail.hip) -------------------------------
     def gat_tail_forward(self, X: torch.Tensor, heads: int, d: int, mean: bool, bias: Optional[torch.Tensor], act: int,
                          row_ids: Optional[torch.Tensor] = None, seed: int = 0, step: Optional[torch.Tensor] = None, layer: int = 0,
