@@ -325,6 +325,39 @@ int pgcn_aggmax_backward_csr_plan_f32(const int64_t *rowptr, const int32_t *col,
                                       int64_t ldd, int32_t f, float *partial_ws, int64_t partial_ws_elems, int64_t nslots,
                                       uint32_t flags, pgcn_stream_t stream);
 
+/* ---- DropEdge (Rong et al., ICLR 2020; no counterpart in the reference): the aggregation over a pattern whose entries are dropped
+ * anew at every training step and renormalised.  csrc/pgcn_dropedge.h states the keep function:
+ *   keep(gi, gj) = gi == gj || u(seed, step[0], min(gi, gj), max(gi, gj)) >= thr      (GLOBAL ids below 2^31; thr: dropout's threshold)
+ * -- symmetric, so the transposed structure sees the same mask; self loops stay; independent of owner rank and local numbering.
+ * step: ONE int64 in DEVICE memory, read by the kernels (a new step needs no new binding).
+ *
+ * pgcn_dropedge_sum_csr_plan_f32: C[i, .] (+)= sum over the KEPT stored entries (i, j) of row i of B[j, .].  pairs / tasks / seg /
+ * nslices / fix / nslots: a structure and plan as pgcn_aggmax_csr_plan_f32 takes them (the order of the pairs inside a task is free
+ * here); row_gid[rows]: the global id of every row; slot_row[nslots]: the row of every slot (required when nslots > 0).  keep is
+ * evaluated once per entry; a dropped entry's row of B is NOT loaded and contributes nothing whatever it holds (no multiply by
+ * zero).  Kept entries are added in storage order, the pieces of a cut row in slot order (pgcn_spmm_fixup_f32): deterministic, no
+ * float atomics.  flags: PGCN_SPMM_ACCUMULATE, _XCD_SWIZZLE, _OFFSETS32, _FPASS64.  Any f >= 1 and leading dimensions >= f; a float4
+ * body when f % 4 == 0 with 16-byte aligned operands, a scalar body otherwise, the same bits.  partial_ws: nslots x f floats.
+ *
+ * pgcn_dropedge_count_csr_plan_i32: count[i] (+)= the number of kept stored entries of row i, exact; no rows of any operand are
+ * read.  Without PGCN_SPMM_ACCUMULATE the nrows counts are zeroed first (rows without a task end at 0).
+ *
+ * pgcn_dropedge_scales_f32: scale[i] = count[i] > 0 ? fl32(1 / sqrt((double)count[i])) : 1 -- double sqrt and division, rounded once
+ * to fp32: the bits of partition.degree_scales.
+ *
+ * pgcn_row_scale_f32: Y[i, c] = fl(s[i] * X[i, c]), one rounded product; Y may be X (then ldy == ldx).  Any f >= 1.                 */
+int pgcn_dropedge_sum_csr_plan_f32(const int64_t *rowptr, const int32_t *pairs, const int32_t *row_gid, const int32_t *slot_row,
+                                   const int32_t *tasks, int64_t ntasks, const int64_t *seg, int32_t nslices, const int32_t *fix,
+                                   int64_t nfix, const float *B, int64_t ldb, float *C, int64_t ldc, int32_t f, float *partial_ws,
+                                   int64_t partial_ws_elems, int64_t nslots, uint64_t seed, const int64_t *step, uint32_t thr,
+                                   uint32_t flags, pgcn_stream_t stream);
+int pgcn_dropedge_count_csr_plan_i32(const int64_t *rowptr, const int32_t *pairs, const int32_t *row_gid, const int32_t *slot_row,
+                                     const int32_t *tasks, int64_t ntasks, int64_t nslots, int64_t nrows, int32_t *count, uint64_t seed,
+                                     const int64_t *step, uint32_t thr, uint32_t flags, pgcn_stream_t stream);
+int pgcn_dropedge_scales_f32(const int32_t *count, int64_t n, float *scale, pgcn_stream_t stream);
+int pgcn_row_scale_f32(const float *X, int64_t ldx, const float *s, int64_t nrows, int32_t f, float *Y, int64_t ldy,
+                       pgcn_stream_t stream);
+
 /* The same product with the weights RECOMPUTED per entry instead of read from planes -- the transposed product of
  * the GAT backward pass, dZ = A_alpha^T . dOut on the transposed structure (rows = columns of A): entry (row j,
  * col i) weighs alpha_ij = (exp(e - m_i) - em_i) / D_i, e = [LeakyReLU](s1_i + s2_j), from rowstat[i] = (s1, m, 1/D, em)

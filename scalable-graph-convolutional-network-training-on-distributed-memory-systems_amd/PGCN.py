@@ -219,6 +219,27 @@ class PAggMax(torch.autograd.Function):
         return None, dH
 
 
+class PSpMMDrop(torch.autograd.Function):
+    """``PSpMM`` under DropEdge (Rong et al., ICLR 2020; csrc/pgcn_dropedge.hip): the aggregation over the stored pattern of A + I
+    minus the entries dropped in this training step, renormalised -- forward ``A.forward_drop``, backward ``A.backward_drop`` under the
+    same mask (``drop``: the model's dropout.EdgeDrop; the mask is a function of its state's seed and step and of the two GLOBAL ids
+    of an entry, so every part vector drops the same edges, and all layers of a step share one mask).  Nothing is saved.  The
+    constant feature matrix of the first layer needs no gradient: nothing is aggregated backward."""
+
+    @staticmethod
+    def forward(ctx, A, H, drop):
+        ctx.A, ctx.drop = A, drop
+        return A.forward_drop(H, drop)
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        dH = ctx.A.backward_drop(grad_output, ctx.drop) if ctx.needs_input_grad[1] else None
+        join = getattr(ctx.A, "join_wgrad", None)        # (as PSpMM.backward: the weight gradient parked on the engine's side stream)
+        if join is not None:
+            join()
+        return None, dH, None
+
+
 class PPropagate(torch.autograd.Function):
     """Personalised-PageRank propagation of the logits (APPNP: predict, then propagate; csrc/pgcn_propagate.hip): Z^0 = H,
     Z^{k+1} = (1 - alpha) A Z^k + alpha H, output Z^K -- forward ``A.propagate`` (K aggregations at the width of H, each with the
@@ -242,7 +263,8 @@ class PPropagate(torch.autograd.Function):
 class Propagate(nn.Module):
     """``PPropagate`` as the last module of a model: K steps of personalised PageRank with teleport probability ``alpha`` over the
     engine's stored matrix (meant for a normalised one: on a raw pattern the result grows like ||A||^K).  No parameters, no buffers,
-    the same in ``train()`` and ``eval()``."""
+    the same in ``train()`` and ``eval()``.  In a model with DropEdge (``PGCN(drop_edge=...)``) it keeps using the UNDROPPED matrix:
+    the mask acts on the layers' aggregations only."""
 
     def __init__(self, A, K, alpha=0.1):
         super(Propagate, self).__init__()
@@ -1365,10 +1387,15 @@ class PGCN(nn.Module):
     ``aggregate=False`` (opt-in): the layer does not aggregate -- act(H W^T ...), a dense layer over the vertices' own rows (the MLP
     in front of ``Propagate``); no exchange, no engine call.  Every other option composes through the same nodes, and the layer owns
     the same parameters under the same state-dict keys.  Refused with ``aggr="max"`` (nothing to take a max over) and with
-    ``root_weight=True`` (the root product IS this layer).  True: the branches of before."""
+    ``root_weight=True`` (the root product IS this layer).  True: the branches of before.
+
+    ``drop_edge=ctx`` (opt-in; a dropout.EdgeDrop, shared by the layers of a model): DropEdge -- in training mode the aggregation is
+    ``PSpMMDrop``, over the entries of the pattern that survive this step, renormalised; ``A`` must be built with
+    ``normalize="sym"``.  ``eval()``, or a probability of 0, takes ``PSpMM`` bit for bit.  Refused with ``aggr="max"`` and
+    ``aggregate=False``.  None: the branches of before."""
 
     def __init__(self, A, in_features, out_features, dropout=0.0, layer=0, state=None, relu=True, norm=None, root_weight=False, bias=False,
-                 residual=False, aggr=None, aggregate=True):
+                 residual=False, aggr=None, aggregate=True, drop_edge=None):
         super(PGCN, self).__init__()
         if aggr not in AGGRS + (None,):
             raise ValueError("aggr takes %s, got %r" % (" | ".join(AGGRS), aggr))
@@ -1376,6 +1403,12 @@ class PGCN(nn.Module):
         if not self.aggregate and (aggr == "max" or root_weight):
             raise ValueError("aggregate=False does not go with %s" % ('aggr="max"' if aggr == "max" else "root_weight=True"))
         self._aggregate = _no_aggregation if not self.aggregate else PAggMax.apply if aggr == "max" else PSpMM.apply
+        if drop_edge is not None:
+            if aggr == "max" or not self.aggregate:
+                raise ValueError("drop_edge does not go with %s" % ('aggr="max"' if aggr == "max" else "aggregate=False"))
+            if drop_edge.on:
+                self.drop_edge = drop_edge
+                self._aggregate = self._aggregate_drop
         self.linear = nn.Linear(in_features, out_features, bias=False)
         self.A = A
         self.send_map = send_map
@@ -1412,6 +1445,10 @@ class PGCN(nn.Module):
             self.root = nn.Linear(in_features, out_features, bias=False)
         if self.has_bias:
             self.bias = nn.Parameter(torch.zeros(out_features))
+
+    def _aggregate_drop(self, A, H):
+        """The aggregation of a layer with DropEdge on: dropped and renormalised in training mode, ``PSpMM`` in eval mode."""
+        return PSpMMDrop.apply(A, H, self.drop_edge) if self.training else PSpMM.apply(A, H)
 
     def _global_row_ids(self, H):
         if self._row_ids is None or self._row_ids.device != H.device:      # global ids in local row order, once
@@ -1629,13 +1666,33 @@ def _barrier():
 
 
 def _architecture(fin, classes, nlayers, nfeatures, hidden, multilabel, dropout, dropout_seed, norm, root_weight, bias, residual, aggr=None,
-                  propagate=None, ppr_alpha=None, dense_layers=None):
-    """checkpoint.architecture of the model ``_train_on_data`` builds from these arguments."""
+                  propagate=None, ppr_alpha=None, dense_layers=None, drop_edge=None):
+    """checkpoint.architecture of the model ``_train_on_data`` builds from these arguments (``drop_edge``: recorded only when it is
+    positive, so that earlier checkpoints compare as before)."""
     widths = [int(fin)] + [int(nfeatures if hidden is None else hidden)] * (nlayers - 1) + [int(classes)]
     return _checkpoint.architecture(widths, "multilabel" if multilabel else "single", dropout, dropout_seed, norm, root_weight, bias,
                                     residual, **({"aggr": aggr} if aggr == "max" else {}),
                                     **({"propagate": (propagate, PPR_ALPHA if ppr_alpha is None else ppr_alpha)} if propagate is not None else {}),
-                                    **({"dense_layers": True} if dense_layers else {}))
+                                    **({"dense_layers": True} if dense_layers else {}),
+                                    **({"drop_edge": float(drop_edge)} if drop_edge else {}))
+
+
+def _check_drop_edge(drop_edge, normalize=None, aggr=None, dense_layers=None, check_normalize=True):
+    """ValueError for a ``drop_edge`` that no model can be built from: not a probability in [0, 1), or positive without
+    ``normalize="sym"`` (a weighted or pre-normalised matrix cannot be renormalised), with ``aggr="max"`` or with ``dense_layers``."""
+    if drop_edge is None:
+        return
+    if isinstance(drop_edge, bool) or not isinstance(drop_edge, (int, float)):
+        raise ValueError("drop_edge takes a probability in [0, 1), got %r" % (drop_edge,))
+    _dropout.threshold(drop_edge)
+    if float(drop_edge) > 0.0:
+        if check_normalize and normalize != "sym":
+            raise ValueError("drop_edge needs normalize='sym': DropEdge renormalises the pattern of A + I, a weighted or pre-normalised "
+                             "matrix cannot be renormalised")
+        if aggr == "max":
+            raise ValueError('drop_edge does not go with aggr="max"')
+        if dense_layers:
+            raise ValueError("drop_edge does not go with dense_layers: nothing is aggregated")
 
 
 PPR_ALPHA = 0.1                        # --ppr-alpha / run(ppr_alpha=...): the teleport probability of --propagate when none is given
@@ -1661,7 +1718,7 @@ OPTIMIZERS = _nodeloss.OPTIMIZERS      # --optimizer / run(optimizer=...): "torc
 def _train_on_data(A, n, nlayers, nfeatures, features, labels, split, hidden, epochs, lr, eval_every, dropout, dropout_seed,
                    multilabel=False, weight_decay=0.0, decoupled_decay=False, optimizer="torch", norm=None, root_weight=None, bias=None,
                    residual=None, save=None, load=None, predict=None, proba=None, control=None, aggr=None, propagate=None, ppr_alpha=None,
-                   dense_layers=None):
+                   dense_layers=None, drop_edge=None):
     """The loop of ``run`` on real inputs: widths fin -> hidden -> ... -> C, no ReLU on the last layer, constant features (the
     first layer's backward aggregation is skipped), Adam, the masked loss over the train rows.  Reports every ``eval_every``
     epochs: without dropout from the record of the training step's own pass (the logits BEFORE that step's update), with
@@ -1685,8 +1742,13 @@ def _train_on_data(A, n, nlayers, nfeatures, features, labels, split, hidden, ep
     (class PGCN, ``PAggMax``); None or "sum": the weighted sum of before.  ``propagate=K`` (``ppr_alpha``, default 0.1): the module
     ``Propagate`` follows the last layer -- K steps of personalised PageRank over the logits (APPNP); loss, ``evaluate`` and the
     predictions go through it.  ``dense_layers``: no layer aggregates (``PGCN(aggregate=False)``: the MLP in front of it).  None: the
-    model of before."""
+    model of before.  ``drop_edge=P`` > 0: DropEdge -- every layer's aggregation runs, in training mode, over the entries of the
+    pattern that survive the step, renormalised (class PGCN, ``PSpMMDrop``; ``A`` built with ``normalize="sym"``); the mask's seed and
+    step are the dropout state's, which then exists even with ``dropout`` = 0, and the reporting rule is dropout's: ``evaluate`` in
+    eval mode after the update.  ``Propagate`` keeps the undropped matrix."""
     _check_propagate(propagate, ppr_alpha, dense_layers, aggr, root_weight)
+    _check_drop_edge(drop_edge, getattr(A.part, "normalize", None), aggr, dense_layers)
+    drop_edge = float(drop_edge or 0.0)
     task = _nodeloss.TASKS["multilabel" if multilabel else "single"]
     data = task.load(features, labels, split, A.part.owned, n, device=device)
     hidden = int(nfeatures if hidden is None else hidden)
@@ -1701,12 +1763,14 @@ def _train_on_data(A, n, nlayers, nfeatures, features, labels, split, hidden, ep
     for a, b in zip(widths, widths[1:]):
         tune_dense_gemms(A.part.n_local, a, device, b)
     _dropout.threshold(dropout)
-    state = _dropout.DropoutState(dropout_seed, device) if dropout > 0.0 else None
+    state = _dropout.DropoutState(dropout_seed, device) if dropout > 0.0 or drop_edge > 0.0 else None
     extra = dict(({"root_weight": True} if root_weight else {}), **({"bias": True} if bias else {}))       # (neither: the call of before)
     if aggr == "max":
         extra["aggr"] = "max"
     if dense_layers:
         extra["aggregate"] = False
+    if drop_edge > 0.0:
+        extra["drop_edge"] = _dropout.EdgeDrop(drop_edge, state)       # one context: the layers of a step share the mask and its scales
     tail = [Propagate(A, propagate, PPR_ALPHA if ppr_alpha is None else float(ppr_alpha))] if propagate is not None else []
     model = nn.Sequential(*[PGCN(A, widths[i], widths[i + 1], dropout=dropout if i < nlayers - 1 else 0.0, layer=i, state=state,
                                  relu=i < nlayers - 1, **({"norm": norm} if norm not in (None, "none") and i < nlayers - 1 else {}),
@@ -1720,7 +1784,7 @@ def _train_on_data(A, n, nlayers, nfeatures, features, labels, split, hidden, ep
     first, history, best, hooks = 0, [], None, None
     if save is not None or load is not None or predict is not None or proba:
         arch = _architecture(data.fin, data.classes, nlayers, nfeatures, hidden, multilabel, dropout, dropout_seed, norm, root_weight,
-                             bias, residual, aggr, propagate, ppr_alpha, dense_layers)
+                             bias, residual, aggr, propagate, ppr_alpha, dense_layers, drop_edge)
         hooks = _checkpoint.Hooks("PGCN", arch, model, fused, opt, state, save, load, predict, proba, myrank, _barrier)
         first, history, best = hooks.resume()
     last = first + epochs - 1
@@ -1776,7 +1840,8 @@ def _train_on_data(A, n, nlayers, nfeatures, features, labels, split, hidden, ep
 def run(rank, size, nlayers, nfeatures, path_A, path_partvec, backend, normalize=None, dropout=0.0, dropout_seed=0,
         features=None, labels=None, split=None, hidden=None, epochs=None, lr=None, eval_every=None, task=None,
         weight_decay=None, decoupled_decay=None, optimizer=None, norm=None, root_weight=None, bias=None, residual=None,
-        save=None, load=None, predict=None, proba=None, aggr=None, propagate=None, ppr_alpha=None, dense_layers=None, **control):
+        save=None, load=None, predict=None, proba=None, aggr=None, propagate=None, ppr_alpha=None, dense_layers=None, drop_edge=None,
+        **control):
     """PGCN.py:162-238.  ``normalize="sym"``: train on D_r^-1/2 (A + I) D_c^-1/2 of the pattern of ``path_A``, built on the fly
     (partition.build_partition) instead of by the offline pass preprocess/GrB-GNN-IDG.py.  ``dropout`` > 0: the output of every
     layer but the last is dropped with that probability (class PGCN), masks from (``dropout_seed``, step, layer, global row,
@@ -1812,7 +1877,12 @@ def run(rank, size, nlayers, nfeatures, path_A, path_partvec, backend, normalize
     ``propagate``) the teleport probability.  It uses the stored matrix: meant for ``normalize="sym"`` or a normalised file, on a raw
     pattern the logits grow like ||A||^K.  ``dense_layers`` (True; needs the three files): no layer aggregates -- with ``propagate``
     that is APPNP's predict-then-propagate.  A checkpoint records both: loading one under another K, alpha or layer kind raises
-    ValueError naming ``propagate`` / ``dense_layers``."""
+    ValueError naming ``propagate`` / ``dense_layers``.
+    ``drop_edge`` (a probability in [0, 1); needs the three files and ``normalize="sym"``): DropEdge -- at every training step
+    every stored entry of the pattern of A + I off the diagonal is dropped with that probability, in both directions at once, and
+    what is left is renormalised by its own degrees (``PSpMMDrop``, csrc/pgcn_dropedge.hip); one mask for all layers of a step, keyed
+    by (``dropout_seed``, step, the two global ids) and so the same under any part vector; evaluation runs on the full matrix.  Not
+    with ``aggr="max"`` or ``dense_layers``.  A checkpoint records a positive value and resumes exactly (the dropout step)."""
     global myrank, world_size, send_map, recv_map, device, X, recv_buffers, send_buffers, stats
     for name in control:
         if name not in _nodeloss.CONTROL:
@@ -1849,6 +1919,9 @@ def run(rank, size, nlayers, nfeatures, path_A, path_partvec, backend, normalize
     _check_propagate(propagate, ppr_alpha, dense_layers, aggr, root_weight)
     if (propagate is not None or ppr_alpha is not None or dense_layers is not None) and not all(given):
         raise ValueError("propagate, ppr_alpha and dense_layers need features, labels and split")
+    _check_drop_edge(drop_edge, normalize, aggr, dense_layers)
+    if drop_edge is not None and not all(given):
+        raise ValueError("drop_edge needs features, labels and split")
     if (save is not None or load is not None or predict is not None or proba is not None) and not all(given):
         raise ValueError("save, load, predict and proba need features, labels and split")
     if proba and predict is None:
@@ -1873,7 +1946,7 @@ def run(rank, size, nlayers, nfeatures, path_A, path_partvec, backend, normalize
         opened = _nodeloss.TASKS[task or "single"].open_checked(features, labels, split, len(partvec))
         if load is not None:
             arch = _architecture(opened[3], opened[4], nlayers, nfeatures, hidden, multilabel, dropout, dropout_seed, norm, root_weight,
-                                 bias, residual, aggr, propagate, ppr_alpha, dense_layers)
+                                 bias, residual, aggr, propagate, ppr_alpha, dense_layers, drop_edge)
             load = _checkpoint.load(load, "PGCN", arch, optimizer or "torch")
         del opened
         if control and load is not None:        # (the horizon against the warm-up, from the epoch the checkpoint stands at)
@@ -1925,7 +1998,8 @@ def run(rank, size, nlayers, nfeatures, path_A, path_partvec, backend, normalize
                               **{k: v for k, v in (("save", save), ("load", load), ("predict", predict), ("proba", proba)) if v is not None},
                               **({"control": control} if control else {}), **({"aggr": "max"} if aggr == "max" else {}),
                               **{k: v for k, v in (("propagate", propagate), ("ppr_alpha", ppr_alpha)) if v is not None},
-                              **({"dense_layers": True} if dense_layers else {}))
+                              **({"dense_layers": True} if dense_layers else {}),
+                              **({"drop_edge": float(drop_edge)} if drop_edge else {}))
 
     owned = A.part.owned.to(device)
     # PGCN.py:186-188 synthetic features H[i,:] = i, owned rows only
@@ -2001,9 +2075,10 @@ def run(rank, size, nlayers, nfeatures, path_A, path_partvec, backend, normalize
 def init_process(rank, size, fn, nlayers, nfeatures, path_A, path_partvec, backend, normalize=None, dropout=0.0, dropout_seed=0,
                  features=None, labels=None, split=None, hidden=None, epochs=None, lr=None, eval_every=None, task=None,
                  weight_decay=None, decoupled_decay=None, optimizer=None, norm=None, root_weight=None, bias=None, residual=None,
-                 save=None, load=None, predict=None, proba=None, control=None, aggr=None, propagate=None, ppr_alpha=None, dense_layers=None):
+                 save=None, load=None, predict=None, proba=None, control=None, aggr=None, propagate=None, ppr_alpha=None, dense_layers=None,
+                 drop_edge=None):
     """PGCN.py:241-253.  ``control``: the given options of nodeloss.CONTROL as one dict (None: today's call).  ``aggr``, ``propagate``,
-    ``ppr_alpha``, ``dense_layers``: run's."""
+    ``ppr_alpha``, ``dense_layers``, ``drop_edge``: run's."""
     global _exchanger
     dist.init_process_group(backend, rank=rank, world_size=size)
 
@@ -2018,6 +2093,8 @@ def init_process(rank, size, fn, nlayers, nfeatures, path_A, path_partvec, backe
         kw["normalize"] = normalize
     if dropout > 0.0:
         kw["dropout"], kw["dropout_seed"] = dropout, dropout_seed
+    if drop_edge is not None:
+        kw["drop_edge"], kw["dropout_seed"] = drop_edge, dropout_seed       # (the edge mask's seed, with or without feature dropout)
     for name, v in (("features", features), ("labels", labels), ("split", split), ("hidden", hidden), ("epochs", epochs), ("lr", lr),
                     ("eval_every", eval_every), ("task", task), ("weight_decay", weight_decay), ("decoupled_decay", decoupled_decay),
                     ("optimizer", optimizer), ("norm", norm), ("root_weight", root_weight), ("bias", bias),
@@ -2049,7 +2126,7 @@ def main(argv):
         opts, args = getopt.getopt(argv, "a:p:b:s:l:f:", ["normalize=", "dropout=", "dropout-seed=", "features=", "labels=", "split=",
                                                           "hidden=", "epochs=", "lr=", "eval-every=", "task=", "weight-decay=", "adamw",
                                                           "optimizer=", "norm=", "root-weight", "bias", "residual", "save=", "load=",
-                                                          "predict=", "proba", "aggr=", "propagate=", "ppr-alpha=", "dense-layers"] + [f[2:] + "=" for f in _nodeloss.CONTROL_FLAGS.split(", ")])
+                                                          "predict=", "proba", "aggr=", "propagate=", "ppr-alpha=", "dense-layers", "drop-edge="] + [f[2:] + "=" for f in _nodeloss.CONTROL_FLAGS.split(", ")])
     except getopt.GetoptError:
         print("a:p:b:", flush=True)
         sys.exit(2)
@@ -2139,6 +2216,14 @@ def main(argv):
                 sys.exit(2)
         elif opt == '--dense-layers':  # no layer aggregates (PGCN(aggregate=False)): with --propagate, predict then propagate
             data["dense_layers"] = True
+        elif opt == '--drop-edge':     # DropEdge: drop every off-diagonal entry of the pattern with this probability at every training
+            #                                step and renormalise what is left (PSpMMDrop); needs --normalize sym
+            try:
+                data["drop_edge"] = float(arg)
+                _dropout.threshold(data["drop_edge"])
+            except ValueError:
+                print("--drop-edge takes a probability in [0, 1), got %r" % arg, flush=True)
+                sys.exit(2)
         elif opt == '--root-weight':   # every layer adds H . W_r^T: a vertex's own features get their own weights (class PGCN)
             data["root_weight"] = True
         elif opt == '--bias':          # every layer adds a bias (a normalised layer keeps bn_bias alone)
@@ -2172,7 +2257,7 @@ def main(argv):
     os.environ.setdefault("WORLD_SIZE", str(size))
     files = [k for k in ("features", "labels", "split") if k in data]
     if data and len(files) != 3:
-        print("--features, --labels and --split go together (and --hidden, --epochs, --lr, --eval-every, --task, --weight-decay, --adamw, --optimizer, --save, --load, --predict, --proba, --aggr, --propagate, --ppr-alpha, --dense-layers, %s, --norm, --residual, --root-weight, --bias need them); got %%s"
+        print("--features, --labels and --split go together (and --hidden, --epochs, --lr, --eval-every, --task, --weight-decay, --adamw, --optimizer, --save, --load, --predict, --proba, --aggr, --propagate, --ppr-alpha, --dense-layers, --drop-edge, %s, --norm, --residual, --root-weight, --bias need them); got %%s"
               % _nodeloss.CONTROL_FLAGS % ", ".join("--" + {"decoupled_decay": "adamw"}.get(k, k.replace("_", "-")) for k in sorted(data)), flush=True)
         sys.exit(2)
     for k in files:
@@ -2188,6 +2273,14 @@ def main(argv):
     if "dense_layers" in data and (data.get("aggr") == "max" or "root_weight" in data):
         print("--dense-layers does not go with %s" % ("--aggr max" if data.get("aggr") == "max" else "--root-weight"), flush=True)
         sys.exit(2)
+    if data.get("drop_edge", 0.0) > 0.0:
+        if normalize != "sym":
+            print("--drop-edge needs --normalize sym: DropEdge renormalises the pattern of A + I, a weighted or pre-normalised matrix "
+                  "cannot be renormalised", flush=True)
+            sys.exit(2)
+        if data.get("aggr") == "max" or "dense_layers" in data:
+            print("--drop-edge does not go with %s" % ("--aggr max" if data.get("aggr") == "max" else "--dense-layers"), flush=True)
+            sys.exit(2)
     if "load" in data and not os.path.exists(data["load"]):
         print("--load: no such file %r" % (data["load"],), flush=True)
         sys.exit(2)
@@ -2224,7 +2317,7 @@ def main(argv):
                 args += layer_opts
             if has_residual:                   # (the tuple grows only when --residual is given)
                 args += (True,)
-    named = {k: data[k] for k in ("aggr", "propagate", "ppr_alpha", "dense_layers") if k in data}      # (by name, only when given)
+    named = {k: data[k] for k in ("aggr", "propagate", "ppr_alpha", "dense_layers", "drop_edge") if k in data}      # (by name, only when given)
     p = mp.Process(target=init_process, args=args, **({"kwargs": named} if named else {}))
     p.start()
     p.join()

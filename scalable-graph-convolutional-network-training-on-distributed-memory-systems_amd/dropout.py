@@ -77,15 +77,72 @@ def pack_words(keep):
 
 class DropoutState:
     """What the layers of one model share: the seed and the training step as a one-element int64 tensor ON THE DEVICE -- the
-    kernels read it from memory, so a captured graph of a training step draws new masks at every replay."""
+    kernels read it from memory, so a captured graph of a training step draws new masks at every replay.  ``tick``: a host-side
+    count of the changes of the step (``advance``, a checkpoint's resume), which tells ``EdgeDrop`` that what it derived from the
+    step is stale without a device read."""
 
     def __init__(self, seed=0, device="cpu"):
         self.seed = int(seed) & _M64
         self.step = torch.zeros(1, dtype=torch.int64, device=device)
+        self.tick = 0
 
     def advance(self):
         """Next training step (a device-side add: capturable)."""
         self.step.add_(1)
+        self.tick += 1
 
     def host_step(self) -> int:
         return int(self.step.item())
+
+
+# ---- DropEdge: the host statement of csrc/pgcn_dropedge.h (include/pgcn_hip.h has the contract) ------------------------------
+EDGE_LAYER = 1 << 20          # the `layer` of the edge mask's key: reserved, above any layer index
+
+
+def _ids(x):
+    return np.ascontiguousarray(x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else x).astype(np.int64)
+
+
+def edge_u(seed, step, gi, gj):
+    """u (uint32 numpy, the shape of gi) of the stored entries (gi, gj), GLOBAL ids below 2^31: the hash of feature dropout of
+    (key(seed, step, EDGE_LAYER), row = min(gi, gj), column = max(gi, gj)) -- symmetric in (gi, gj)."""
+    gi, gj = _ids(gi), _ids(gj)
+    if gi.size and (min(int(gi.min()), int(gj.min())) < 0 or max(int(gi.max()), int(gj.max())) >= 2 ** 31):
+        raise ValueError("DropEdge takes global ids in [0, 2^31)")
+    k = key(seed, step, EDGE_LAYER)
+    klo, khi = np.uint32(k & 0xFFFFFFFF), np.uint32(k >> 32)
+    lo, hi = np.minimum(gi, gj).astype(np.uint32), np.maximum(gi, gj).astype(np.uint32)
+    with np.errstate(over="ignore"):
+        return _fmix32(_fmix32(hi ^ klo) ^ lo ^ khi)
+
+
+def edge_keep(seed, step, gi, gj, thr):
+    """bool numpy: the stored entry (gi, gj) survives the step -- ``gi == gj or u >= thr``: self loops always stay, an undirected
+    edge goes or stays in both directions, one mask serves all layers of the step."""
+    return (_ids(gi) == _ids(gj)) | (edge_u(seed, step, gi, gj) >= np.uint32(thr))
+
+
+class EdgeDrop:
+    """DropEdge of one model (Rong et al., ICLR 2020): the drop probability, its threshold and the ``DropoutState`` whose seed and
+    step key the mask -- the one feature dropout uses.  ``PGCN(..., drop_edge=ctx)`` hands it to ``AggregationEngine.forward_drop`` /
+    ``backward_drop``; the engine parks the step's kept-entry counts and scales in ``cache`` (``AggregationEngine.drop_refresh``) and
+    ``fresh`` says whether they still belong to the state's step."""
+
+    def __init__(self, p, state: DropoutState):
+        self.p = float(p)
+        self.thr, _ = threshold(p)
+        if state is None:
+            raise ValueError("EdgeDrop needs a DropoutState (the seed and the step of the mask)")
+        self.state = state
+        self.cache = None           # (engine's, for state.tick == self.tick)
+        self.tick = -1
+
+    @property
+    def on(self) -> bool:
+        return self.thr > 0
+
+    def fresh(self, owner) -> bool:
+        return self.cache is not None and self.tick == self.state.tick and self.cache.owner is owner
+
+    def park(self, cache):
+        self.cache, self.tick = cache, self.state.tick

@@ -526,6 +526,79 @@ class MaxStructures:
 
 
 # --------------------------------------------------------------------------
+# DropEdge: the composed route (framework operations + the numpy keep function; the definitions of csrc/pgcn_dropedge.hip)
+
+
+def _host_step(step) -> int:
+    return int(step.item()) if isinstance(step, torch.Tensor) else int(step)
+
+
+def dropedge_keep_composed(A: ComposedMaxCSR, row_gid: torch.Tensor, seed: int, step, thr: int) -> torch.Tensor:
+    """bool [nnz] on A's device: which stored entries of ``A`` DropEdge keeps in ``step`` (dropout.edge_keep over the global ids of
+    every entry's row and column).  Kept on the structure for the last (row ids, seed, step, thr): the layers of a step share it."""
+    from . import dropout as _dropout
+    key = (row_gid.data_ptr(), int(row_gid.numel()), int(seed), _host_step(step), int(thr))
+    last = getattr(A, "_drop_keep", None)
+    if last is None or last[0] != key:
+        gi = row_gid.detach().cpu().to(torch.int64)[A.row.cpu()]
+        keep = torch.from_numpy(_dropout.edge_keep(seed, key[3], gi, A.gid.cpu(), thr)) if A.nnz else torch.zeros(0, dtype=torch.bool)
+        A._drop_keep = last = (key, keep.to(A.row.device))
+    return last[1]
+
+
+def dropedge_sum_composed(A: ComposedMaxCSR, row_gid: torch.Tensor, B: torch.Tensor, C: torch.Tensor, seed: int, step, thr: int,
+                          accumulate: bool = False) -> torch.Tensor:
+    """C of ``HipKernels.dropedge_sum`` from framework operations: C[i] (+)= sum of B[j] over the kept stored entries (i, j).  The
+    same definition; only the order of the fp32 additions is the framework's.  A dropped entry's row of B is never read."""
+    if not accumulate:
+        C[:A.nrows] = 0
+    if A.nnz:
+        keep = dropedge_keep_composed(A, row_gid, seed, step, thr)
+        C[:A.nrows].index_add_(0, A.row[keep], B.detach()[A.col[keep]])
+    return C
+
+
+def dropedge_count_composed(A: ComposedMaxCSR, row_gid: torch.Tensor, count: torch.Tensor, seed: int, step, thr: int,
+                            accumulate: bool = False) -> torch.Tensor:
+    """count of ``HipKernels.dropedge_count`` from framework operations: count[i] (+)= kept stored entries of row i (int32, exact)."""
+    n = torch.zeros(A.nrows, dtype=torch.int64, device=count.device)
+    if A.nnz:
+        n = torch.bincount(A.row[dropedge_keep_composed(A, row_gid, seed, step, thr)], minlength=A.nrows)
+    count[:A.nrows] = (count[:A.nrows] + n.to(torch.int32)) if accumulate else n.to(torch.int32)
+    return count
+
+
+def row_scale_composed(X: torch.Tensor, s: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``HipKernels.row_scale`` from framework operations, bit for bit: one rounded fp32 product per element."""
+    return torch.mul(X.detach(), s[:X.shape[0]].unsqueeze(1), out=out)
+
+
+@dataclasses.dataclass
+class DropEdgeStructures:
+    """What ``AggregationEngine.forward_drop`` / ``backward_drop`` run on, built at the first use: the whole pattern of every block
+    as (col, global id) pairs -- forward AND transposed ones, the keep function takes both ids (kernels.DeviceMaxCSR, or
+    ComposedMaxCSR on the composed route) -- and the global ids as int32.  8 B per stored entry for the forward pairs and 8 B for the
+    transposed ones, beside the sum path's structures (one rank, symmetric A: one set serves both)."""
+    composed: bool
+    loc: object
+    halo: list
+    loc_T: object
+    halo_T: list
+    owned: torch.Tensor
+    halo_global: torch.Tensor
+
+
+@dataclasses.dataclass
+class DropScales:
+    """The kept-entry counts of one training step and their scales, by owned vertex (``AggregationEngine.drop_refresh``)."""
+    owner: object
+    r: torch.Tensor         # int32 [n_local]: kept stored entries of every owned ROW
+    c: torch.Tensor         # int32 [n_local]: kept stored entries of every owned COLUMN (over the rows of all ranks)
+    s_r: torch.Tensor       # fp32: partition.degree_scales(r)
+    s_c: torch.Tensor       # fp32: partition.degree_scales(c)
+
+
+# --------------------------------------------------------------------------
 # personalised-PageRank propagation: the composed route (framework operations; the definitions of csrc/pgcn_propagate.hip)
 
 
@@ -583,6 +656,7 @@ class AggregationEngine(BoundaryExchange):
         self._wgrad_stream = None       # side stream of the weight gradients (tuning.wgrad_lane), made on first use
         self._wgrad_parked = []         # [(event after a weight gradient on that stream, tensors it reads)] not yet joined
         self._max: Optional[MaxStructures] = None      # the max aggregation's structures, built at the first forward_max / backward_max
+        self._drop: Optional[DropEdgeStructures] = None    # DropEdge's structures, built at the first forward_drop / drop_refresh
 
     # ------------------------------------------------------------------
     def wgrad_lane(self, launch, reads, join_now=False):
@@ -824,6 +898,146 @@ class AggregationEngine(BoundaryExchange):
             waits[r]()
             self.k.spmm(self.unpack[r], back, dH, accumulate=True)      # returned rows are sums: backward's unpack
         return dH
+
+    # ------------------------------------------------------------------
+    # DropEdge (csrc/pgcn_dropedge.hip): the aggregation over the stored pattern minus the entries dropped in this
+    # training step, renormalised -- normalize="sym"'s arithmetic on the kept pattern M:
+    #   forward   Y  = s_r * (M  (s_c * H))      backward   dH = s_c * (M^T (s_r * G))      s = degree_scales of M's row / column counts
+    # keep is a function of (seed, step, the two GLOBAL ids): any part vector drops the same entries.
+    DROP_KERNELS = ("prepare_max", "dropedge_sum", "dropedge_count", "dropedge_scales", "row_scale")
+
+    def _drop_structures(self) -> DropEdgeStructures:
+        """Built once, at the first use: an engine that never drops holds none of it.  The route is chosen here, before the first
+        launch: the provider's kernels on a HIP device, else the composed framework route (same definition, same counts and scales)."""
+        if self._drop is None:
+            part, k = self.part, self.k
+            if getattr(part, "normalize", None) != "sym":
+                raise ValueError("DropEdge renormalises the pattern of A + I: the partition must be built with normalize='sym' "
+                                 "(a weighted or pre-normalised matrix cannot be renormalised), got normalize=%r"
+                                 % (getattr(part, "normalize", None),))
+            if part.n >= 2 ** 31:
+                raise ValueError("DropEdge keeps global ids as int32: n = %d >= 2^31 is not supported" % part.n)
+            if part.A_loc_T is None:
+                raise RuntimeError("partition was built without the transposed pieces")
+            composed = not (self.on_gpu and all(hasattr(k, m) for m in self.DROP_KERNELS))
+            if composed:
+                fwd = lambda a, gid: composed_max_csr(a, gid, self.device)
+            else:
+                fwd = lambda a, gid: k.prepare_max(a, gid)
+            loc = fwd(part.A_loc, part.owned)
+            loc_T = loc if part.A_loc_T is part.A_loc else fwd(part.A_loc_T, part.owned)
+            m = DropEdgeStructures(composed, loc, [fwd(a, part.halo_global) for a in part.A_halo], loc_T,
+                                   [fwd(a, part.owned) for a in part.A_halo_T], part.owned.to(self.device, torch.int32).contiguous(),
+                                   part.halo_global.to(self.device, torch.int32).contiguous())
+            if part.n >= 2 ** 24:       # the partial counts of halo columns travel as fp32: every degree must stay below 2^24
+                def longest(a):
+                    rp = a.rowptr if not composed else torch.bincount(a.row, minlength=a.nrows + 1).cumsum(0)
+                    return int((rp[1:] - rp[:-1]).max()) if a.nrows and rp.numel() > 1 else 0
+                rows = sum(longest(a) for a in [m.loc] + m.halo)
+                cols = max([longest(a) for a in [m.loc_T] + m.halo_T])
+                if max(rows, cols) >= 2 ** 24:
+                    raise ValueError("DropEdge: a vertex of degree >= 2^24 is not supported (the counts travel as fp32)")
+            self._drop = m
+        return self._drop
+
+    def drop_refresh(self, ctx) -> DropScales:
+        """The kept-entry counts and scales of the CURRENT step of ``ctx`` (dropout.EdgeDrop), formed once per step and reused by
+        every layer's forward and backward.  r: a count pass over the forward structures (every entry of an owned row lives on its
+        owner: no exchange).  c: a count pass over the transposed structures; the partial counts of halo columns travel home through
+        ``backward``'s exchange at width 1, as fp32 (exact below 2^24).  One rank with A_loc_T = A_loc: one count serves both."""
+        if ctx.fresh(self):
+            return ctx.cache
+        m = self._drop_structures()
+        seed, step, thr = ctx.state.seed, ctx.state.step, ctx.thr
+        count = dropedge_count_composed if m.composed else self.k.dropedge_count
+        r = torch.empty(self.n_local, dtype=torch.int32, device=self.device)
+        count(m.loc, m.owned, r, seed, step, thr)
+        for q in range(self.rounds if self.size > 1 else 0):
+            count(m.halo[q], m.owned, r, seed, step, thr, accumulate=True)
+        if m.loc_T is m.loc and self.size == 1:
+            c = r
+        else:
+            c = torch.empty(self.n_local, dtype=torch.int32, device=self.device)
+            count(m.loc_T, m.owned, c, seed, step, thr)
+            if self.size > 1:
+                partial = torch.zeros(max(self.n_halo, 1), dtype=torch.int32, device=self.device)
+                for q in range(self.rounds):
+                    b0, b1 = self.round_recv_off[q][0], self.round_recv_off[q][-1]
+                    count(m.halo_T[q], m.halo_global[b0:b1], partial[b0:b1], seed, step, thr)
+                wire = self._slab("halo", self.n_halo, 1)
+                back = self._slab("send", self.n_send, 1)
+                wire[:partial.numel(), 0] = partial
+                waits = self._exchange_all(wire, self.round_recv_off, back, self.round_send_off, 1, None, tag="backward")
+                cf = c.to(torch.float32).unsqueeze(1).contiguous()
+                for q in range(self.rounds):
+                    waits[q]()
+                    self.k.spmm(self.unpack[q], back, cf, accumulate=True)
+                c = cf[:, 0].to(torch.int32)
+        if m.composed:
+            from .partition import degree_scales
+            s_r, s_c = degree_scales(r), (degree_scales(c) if c is not r else None)
+        else:
+            s_r, s_c = self.k.dropedge_scales(r), (self.k.dropedge_scales(c) if c is not r else None)
+        ctx.park(DropScales(self, r, c, s_r, s_r if s_c is None else s_c))
+        return ctx.cache
+
+    def forward_drop(self, H: torch.Tensor, ctx) -> torch.Tensor:
+        """Y = s_r * (M (s_c * H)) over the entries M that ``ctx`` (dropout.EdgeDrop) keeps in its state's current step; the
+        exchange, overlap and slabs are ``forward``'s (the rows sent are the scaled ones: a halo column's scale is its owner's)."""
+        if H.shape[0] != self.n_local:
+            raise ValueError("H must hold exactly the %d owned rows" % self.n_local)
+        d = self.drop_refresh(ctx)
+        m = self._drop
+        seed, step, thr = ctx.state.seed, ctx.state.step, ctx.thr
+        run = dropedge_sum_composed if m.composed else self.k.dropedge_sum
+        scale = row_scale_composed if m.composed else self.k.row_scale
+        f = H.shape[1]
+        Hs = scale(H.contiguous(), d.s_c)
+        S = torch.empty((self.n_local, f), dtype=torch.float32, device=self.device)
+        if self.size == 1:
+            run(m.loc, m.owned, Hs, S, seed, step, thr)
+            return scale(S, d.s_r, out=S)
+        send = self._slab("send", self.n_send, f)
+        halo = self._slab("halo", self.n_halo, f)
+        self.k.gather_rows(Hs, self.send_idx, send)
+        waits = self._exchange_all(send, self.round_send_off, halo, self.round_recv_off, f, tag="forward")
+        run(m.loc, m.owned, Hs, S, seed, step, thr)              # overlaps the exchange
+        for q in range(self.rounds):
+            waits[q]()
+            run(m.halo[q], m.owned, halo, S, seed, step, thr, accumulate=True)
+        return scale(S, d.s_r, out=S)
+
+    def backward_drop(self, G: torch.Tensor, ctx) -> torch.Tensor:
+        """dH = s_c * (M^T (s_r * G)): the adjoint of ``forward_drop`` under the same mask (the step must not have advanced in
+        between).  Partial sums for rows owned by peers travel home like ``backward``'s and are ADDED."""
+        d = self.drop_refresh(ctx)
+        m = self._drop
+        seed, step, thr = ctx.state.seed, ctx.state.step, ctx.thr
+        run = dropedge_sum_composed if m.composed else self.k.dropedge_sum
+        scale = row_scale_composed if m.composed else self.k.row_scale
+        f = G.shape[1]
+        Gs = scale(G.contiguous(), d.s_r)
+        T = torch.empty((self.n_local, f), dtype=torch.float32, device=self.device)
+        if self.size == 1:
+            run(m.loc_T, m.owned, Gs, T, seed, step, thr)
+            return scale(T, d.s_c, out=T)
+        partial = self._slab("halo", self.n_halo, f)
+        back = self._slab("send", self.n_send, f)
+        ready = []
+        for q in range(self.rounds):
+            b0, b1 = self.round_recv_off[q][0], self.round_recv_off[q][-1]
+            run(m.halo_T[q], m.halo_global[b0:b1], Gs, partial[b0:b1], seed, step, thr)
+            if self.overlap:
+                ev = torch.cuda.Event()
+                ev.record(torch.cuda.current_stream(self.device))
+                ready.append(ev)
+        waits = self._exchange_all(partial, self.round_recv_off, back, self.round_send_off, f,
+                                   ready if self.overlap else None, tag="backward")
+        run(m.loc_T, m.owned, Gs, T, seed, step, thr)
+        for q in range(self.rounds):
+            waits[q]()
+            self.k.spmm(self.unpack[q], back, T, accumulate=True)      # returned rows are sums: backward's unpack
+        return scale(T, d.s_c, out=T)
 
     # ------------------------------------------------------------------
     def alg_bytes_forward(self, f: int) -> int:

@@ -776,6 +776,126 @@ class HipKernels:
         fn(row_gid, G, ARG, D)
         return D
 
+    # -- DropEdge (pgcn_dropedge.hip) -----------------------------------------
+    def _drop_structure(self, A: DeviceMaxCSR, row_gid: torch.Tensor, what: str):
+        """What the drop kernels need of a ``prepare_max(csr, col_gid)`` structure: the pairs, and the row of every slot of a cut row
+        (``prepare_max`` keeps it for transposed structures only; made here once, on the device, from the fix list)."""
+        if A.pairs is None:
+            raise _lib.PgcnError("%s needs a structure made by prepare_max(csr, col_gid)" % what)
+        if not (row_gid.is_cuda and row_gid.dtype is torch.int32 and row_gid.dim() == 1 and row_gid.is_contiguous()
+                and row_gid.numel() >= A.nrows):
+            raise _lib.PgcnError("row_gid must be a contiguous int32 CUDA vector of at least %d entries" % A.nrows)
+        if A.nslots > 0 and A.slot_row is None:
+            cnt = A.fix[:, 2].to(torch.int64)                 # the slots of a row are consecutive from fix[:, 1] on
+            first = torch.cumsum(cnt, 0) - cnt
+            pos = torch.repeat_interleave(A.fix[:, 1].to(torch.int64) - first, cnt) + torch.arange(int(cnt.sum()), device=cnt.device)
+            srow = torch.zeros(A.nslots, dtype=torch.int32, device=self.device)
+            srow[pos] = torch.repeat_interleave(A.fix[:, 0], cnt)
+            A.slot_row = srow
+
+    @staticmethod
+    def _drop_step(step: torch.Tensor):
+        if not (step.is_cuda and step.dtype is torch.int64 and step.numel() == 1):
+            raise _lib.PgcnError("step must be a one-element int64 CUDA tensor (dropout.DropoutState.step)")
+
+    def dropedge_sum(self, A: DeviceMaxCSR, row_gid: torch.Tensor, B: torch.Tensor, C: torch.Tensor, seed: int, step: torch.Tensor,
+                     thr: int, accumulate: bool = False) -> torch.Tensor:
+        """C[i] (+)= sum of B[j] over the stored entries (i, j) of ``A`` that DropEdge keeps in the step held by ``step`` (include/pgcn_hip.h,
+        pgcn_dropedge_sum_csr_plan_f32; csrc/pgcn_dropedge.h has the keep function) on the current stream.  ``A``: a structure of
+        ``prepare_max(csr, col_gid)`` -- forward or transposed, both carry (col, global id) pairs; ``row_gid``: int32 [A.nrows] on the
+        device, the global id of every row; ``step``: the one-element int64 device tensor the kernel reads the step from (writing a
+        new step into it needs no new binding).  Bound once per shape like ``spmm``.  Rows beyond ``A.nrows`` are not touched."""
+        key = ("sum", B.stride(0), C.stride(0), B.shape[1], bool(accumulate), int(seed), int(thr))
+        fn = A.launch_cache.get(key)
+        if fn is None:
+            f = B.shape[1]
+            self._drop_structure(A, row_gid, "dropedge_sum")
+            self._max_operand(B, A.ncols, torch.float32, "B")
+            self._max_operand(C, A.nrows, torch.float32, "C")
+            if C.shape[1] != f:
+                raise _lib.PgcnError("B and C widths differ")
+            if not 0 <= int(thr) < 2 ** 32:
+                raise _lib.PgcnError("thr must lie in [0, 2^32)")
+            ldb, ldc = max(B.stride(0), f), max(C.stride(0), f)
+            nrows = A.nrows
+            if nrows == 0 or (A.nnz == 0 and accumulate):
+                fn = lambda gid, B, C, step: None
+            elif A.nnz == 0:
+                fn = lambda gid, B, C, step: C[:nrows].zero_()
+            else:
+                flags = self.base_flags | (_lib.SPMM_ACCUMULATE if accumulate else 0) | self._max_fpass(A, f)
+                if (A.ncols + 1) * ldb * 4 < 2 ** 32:
+                    flags |= _lib.SPMM_OFFSETS32
+                ws, ws_n = self._max_ws(A, A.nslots * f * 4)
+                lib, check, stream = self.lib, _lib.check, self._stream
+                rowptr, pairs, srow, tasks, ntasks, fix, nfix, nslots = (A.rowptr.data_ptr(), A.pairs.data_ptr(), _ptr(A.slot_row),
+                                                                         _ptr(A.tasks), A.ntasks, _ptr(A.fix), A.nfix, A.nslots)
+                seg, nslices, seed64, thr32 = A.seg, A.nslices, int(seed) & (2 ** 64 - 1), int(thr)
+
+                def fn(gid, B, C, step):
+                    check(lib.pgcn_dropedge_sum_csr_plan_f32(rowptr, pairs, gid.data_ptr(), srow, tasks, ntasks, seg, nslices, fix, nfix,
+                                                             B.data_ptr(), ldb, C.data_ptr(), ldc, f, ws, ws_n // 4, nslots, seed64,
+                                                             step.data_ptr(), thr32, flags, stream()), "pgcn_dropedge_sum_csr_plan_f32")
+            A.launch_cache[key] = fn
+        self._drop_step(step)
+        fn(row_gid, B, C, step)
+        return C
+
+    def dropedge_count(self, A: DeviceMaxCSR, row_gid: torch.Tensor, count: torch.Tensor, seed: int, step: torch.Tensor, thr: int,
+                       accumulate: bool = False) -> torch.Tensor:
+        """count[i] (+)= the number of stored entries of row i of ``A`` that DropEdge keeps (pgcn_dropedge_count_csr_plan_i32): exact
+        int32, no operand rows read.  ``count``: contiguous int32 [>= A.nrows] on the device."""
+        key = ("count", bool(accumulate), int(seed), int(thr))
+        fn = A.launch_cache.get(key)
+        if fn is None:
+            self._drop_structure(A, row_gid, "dropedge_count")
+            if not 0 <= int(thr) < 2 ** 32:
+                raise _lib.PgcnError("thr must lie in [0, 2^32)")
+            lib, check, stream = self.lib, _lib.check, self._stream
+            rowptr, pairs, srow, tasks, ntasks, nslots, nrows = (A.rowptr.data_ptr(), A.pairs.data_ptr(), _ptr(A.slot_row), _ptr(A.tasks),
+                                                                 A.ntasks if A.nnz else 0, A.nslots, A.nrows)
+            flags, seed64, thr32 = (_lib.SPMM_ACCUMULATE if accumulate else 0), int(seed) & (2 ** 64 - 1), int(thr)
+
+            def fn(gid, count, step):
+                check(lib.pgcn_dropedge_count_csr_plan_i32(rowptr, pairs, gid.data_ptr(), srow, tasks, ntasks, nslots, nrows, count.data_ptr(),
+                                                           seed64, step.data_ptr(), thr32, flags, stream()), "pgcn_dropedge_count_csr_plan_i32")
+            A.launch_cache[key] = fn
+        if not (count.is_cuda and count.dtype is torch.int32 and count.dim() == 1 and count.is_contiguous() and count.numel() >= A.nrows):
+            raise _lib.PgcnError("count must be a contiguous int32 CUDA vector of at least %d entries" % A.nrows)
+        self._drop_step(step)
+        fn(row_gid, count, step)
+        return count
+
+    def dropedge_scales(self, count: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """fl32(count^-1/2) of an int32 count vector on the device, 1 where the count is 0 (pgcn_dropedge_scales_f32): the bits of
+        partition.degree_scales."""
+        if not (count.is_cuda and count.dtype is torch.int32 and count.dim() == 1 and count.is_contiguous()):
+            raise _lib.PgcnError("count must be a contiguous int32 CUDA vector")
+        if out is None:
+            out = torch.empty(count.numel(), dtype=torch.float32, device=count.device)
+        elif not (out.is_cuda and out.dtype is torch.float32 and out.dim() == 1 and out.is_contiguous() and out.numel() >= count.numel()):
+            raise _lib.PgcnError("out must be a contiguous fp32 CUDA vector of at least %d entries" % count.numel())
+        _lib.check(self.lib.pgcn_dropedge_scales_f32(count.data_ptr(), count.numel(), out.data_ptr(), self._stream()), "pgcn_dropedge_scales_f32")
+        return out
+
+    def row_scale(self, X: torch.Tensor, s: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """out[i] = fl(s[i] * X[i]) (pgcn_row_scale_f32; one rounded product per element); ``out`` may be X itself, None: a new
+        matrix.  ``s``: contiguous fp32 [>= rows of X] on the device."""
+        n = X.shape[0]
+        self._max_operand(X, n, torch.float32, "X")
+        if out is None:
+            out = torch.empty((n, X.shape[1]), dtype=torch.float32, device=X.device)
+        else:
+            self._max_operand(out, n, torch.float32, "out")
+            if out.shape[1] != X.shape[1]:
+                raise _lib.PgcnError("X and out widths differ")
+        if not (s.is_cuda and s.dtype is torch.float32 and s.dim() == 1 and s.is_contiguous() and s.numel() >= n):
+            raise _lib.PgcnError("s must be a contiguous fp32 CUDA vector of at least %d entries" % n)
+        f = X.shape[1]
+        _lib.check(self.lib.pgcn_row_scale_f32(X.data_ptr(), max(X.stride(0), f), s.data_ptr(), n, f, out.data_ptr(), max(out.stride(0), f),
+                                               self._stream()), "pgcn_row_scale_f32")
+        return out
+
     # -- GAT path (pgcn_gat.hip) ---------------------------------------------
     def prepare_gat(self, csr: HostCSR, rows_wave: torch.Tensor, rows_block: torch.Tensor, chunk: Optional[int] = None,
                     small_row: Optional[int] = None) -> DeviceCSR:

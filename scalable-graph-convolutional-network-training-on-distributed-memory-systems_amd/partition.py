@@ -847,6 +847,8 @@ class Partition:
     order_info: Optional[dict] = None   # how the global vertex order was chosen (vertex_order)
     local_bands: Optional[torch.Tensor] = None   # int64 starts of the vertex order's bands in LOCAL row numbering (None: one band); the grid of
                                                  # the bf16 blocks of A_loc -- and of the attention blocks, gat.py -- restarts there
+    normalize: Optional[str] = None     # build_partition*(normalize=): "sym" = the structures hold the PATTERN of A + I and the degree scales
+                                        # (what DropEdge renormalises: engine.AggregationEngine.forward_drop)
 
     @property
     def rounds(self) -> int:
@@ -976,6 +978,7 @@ def build_partition(row: torch.Tensor, col: torch.Tensor, val: torch.Tensor, n: 
     p = _finish_partition(row[mine], col[mine], val[mine], n, part, rank, size, gorder, grank, suniq,
                           int(row.numel()), with_transpose, rounds, order_info.get("_bands"), scales, values)
     p.order_info = order_info
+    p.normalize = normalize
     return p
 
 
@@ -1044,8 +1047,10 @@ def build_partition_local(row: torch.Tensor, col: torch.Tensor, val: torch.Tenso
         pcol = part_[col64]
         away = pcol != rank
         suniq = torch.unique(pcol[away] * n + grank[row64[away]])            # (requesting rank, degree rank of MY row)
-        return _finish_partition(row64, col64, val, n, part_, rank, size, gorder, grank, suniq,
-                                 int(emulate.get("nnz_global", row64.numel())), with_transpose, rounds, scales=scales, values=values)
+        p = _finish_partition(row64, col64, val, n, part_, rank, size, gorder, grank, suniq,
+                              int(emulate.get("nnz_global", row64.numel())), with_transpose, rounds, scales=scales, values=values)
+        p.normalize = normalize
+        return p
     gloo = size > 1 and dist.get_backend(group) == "gloo"
 
     def to_wire(t):            # gloo moves host tensors; nccl (= RCCL) device tensors
@@ -1087,8 +1092,10 @@ def build_partition_local(row: torch.Tensor, col: torch.Tensor, val: torch.Tenso
         suniq = torch.unique(src * n + recv_ids.to(dev))                              # (requesting rank, degree rank)
     if scales is None and DENSE3_VALUES == "factored" and gdeg is not None:
         scales = (degree_scales(gdeg // 2),) * 2
-    return _finish_partition(row, col, val, n, part, rank, size, gorder, grank, suniq, int(nnz_global),
-                             with_transpose, rounds, scales=scales, values=values)
+    p = _finish_partition(row, col, val, n, part, rank, size, gorder, grank, suniq, int(nnz_global),
+                          with_transpose, rounds, scales=scales, values=values)
+    p.normalize = normalize
+    return p
 
 
 def _check_partvec(partvec, n: int, size: int, dev) -> torch.Tensor:
