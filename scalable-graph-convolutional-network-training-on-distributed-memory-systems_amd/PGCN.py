@@ -471,7 +471,7 @@ def mask_words(width):
 def unpack_sign_mask(mask, width):
     """bool [n, width] from the int32 sign-mask words (plain tensor ops: tests and the rare fall-back of the backward)."""
     bits = (mask.to(torch.int64).unsqueeze(-1) >> torch.arange(32, device=mask.device)) & 1
-    return bits.reshape(mask.shape[0], -1)[:, :width].bool()
+    return bits.reshape(mask.shape[0], mask.shape[1] * 32)[:, :width].bool()      # (no -1: a rank without rows has a 0 x words mask)
 
 
 def linear_relu_call(L, x, weight, relu, stream, want_mask=False):

@@ -424,7 +424,8 @@ class HipKernels:
         return torch.cuda.current_stream(self.device).cuda_stream
 
     def _check_dense(self, t: torch.Tensor, rows: int, what: str):
-        if not (t.is_cuda and t.dtype == torch.float32 and t.dim() == 2 and t.stride(1) == 1):
+        # (every stride of a matrix without rows is arbitrary and never used: numpy hands torch (0, 0) for a rank's 0 x f features)
+        if not (t.is_cuda and t.dtype == torch.float32 and t.dim() == 2 and (t.stride(1) == 1 or t.shape[0] == 0)):
             raise _lib.PgcnError("%s must be a row-major fp32 CUDA matrix" % what)
         if t.shape[0] < rows:
             raise _lib.PgcnError("%s has %d rows, need %d" % (what, t.shape[0], rows))
@@ -675,7 +676,10 @@ class HipKernels:
         return d
 
     def _max_operand(self, t: torch.Tensor, rows: int, dtype, what: str):
-        if not (t.is_cuda and t.dtype is dtype and t.dim() == 2 and (t.shape[1] == 1 or t.stride(1) == 1) and t.stride(0) >= t.shape[1]):
+        # (as ``_check_dense``: no stride of a matrix without rows is used, nor the row stride of a single row -- the bindings take
+        # max(stride(0), f) as the leading dimension)
+        if not (t.is_cuda and t.dtype is dtype and t.dim() == 2 and (t.shape[1] == 1 or t.stride(1) == 1 or t.shape[0] == 0) and
+                (t.shape[0] <= 1 or t.stride(0) >= t.shape[1])):
             raise _lib.PgcnError("%s must be a row-major %s CUDA matrix" % (what, str(dtype).replace("torch.", "")))
         if t.shape[0] < rows:
             raise _lib.PgcnError("%s has %d rows, need %d" % (what, t.shape[0], rows))

@@ -165,6 +165,39 @@ def test_backward_routes_every_gradient_to_the_winner(dev, case, f, how):
             assert torch.equal(D2.view(torch.int32), D.contiguous().view(torch.int32))
 
 
+def test_operands_without_rows_and_of_one_row_whatever_their_strides(K, dev):
+    """The max and DropEdge wrappers on a rank that owns nothing (0 x f operands with numpy's strides (0, 0), structures without rows
+    or without columns) and on a single row whose row stride is below f: no stride of a matrix without rows is used, nor the row
+    stride of one row."""
+    f = 4
+
+    def none(dtype):
+        return torch.empty_strided((0, f), (0, 0), dtype=dtype, device=dev)
+    gid0, gid32 = torch.zeros(0, dtype=torch.int64), torch.zeros(0, dtype=torch.int32, device=dev)
+    step = torch.zeros(1, dtype=torch.int64, device=dev)
+    A = K.prepare_max(_host_csr(sp.csr_matrix((0, 0))), gid0)
+    AT = K.prepare_max(_host_csr(sp.csr_matrix((0, 0))), None)
+    K.aggmax(A, none(torch.float32), none(torch.float32), none(torch.int32))
+    K.aggmax_backward(AT, gid32, none(torch.float32), none(torch.int32), none(torch.float32))
+    K.dropedge_sum(A, gid32, none(torch.float32), none(torch.float32), 11, step, 1 << 31)
+    # rows and no column (the halo block of a rank that receives nothing): every row is empty
+    halo = K.prepare_max(_host_csr(sp.csr_matrix((3, 0))), gid0)
+    OUT, ARG = torch.full((3, f), 7.0, device=dev), torch.full((3, f), 7, dtype=torch.int32, device=dev)
+    K.aggmax(halo, none(torch.float32), OUT, ARG)
+    assert torch.equal(OUT, torch.zeros_like(OUT)) and torch.equal(ARG, torch.full_like(ARG, -1))
+    C = torch.full((3, f), 7.0, device=dev)
+    K.dropedge_sum(halo, torch.arange(3, dtype=torch.int32, device=dev), none(torch.float32), C, 11, step, 1 << 31)
+    assert torch.equal(C, torch.zeros_like(C))
+    # one row, one stored entry, the operand's row stride 1
+    one = K.prepare_max(_host_csr(sp.csr_matrix(np.ones((1, 1)))), torch.tensor([GID0]))
+    B = torch.empty_strided((1, f), (1, 1), dtype=torch.float32, device=dev)
+    B.copy_(torch.tensor([[-1.0, 2.0, -3.0, 4.0]]))
+    OUT, ARG = torch.empty((1, f), device=dev), torch.empty((1, f), dtype=torch.int32, device=dev)
+    K.aggmax(one, B, OUT, ARG)
+    torch.cuda.synchronize()
+    assert torch.equal(OUT, B.contiguous()) and torch.equal(ARG, torch.full_like(ARG, GID0))
+
+
 def test_rows_beyond_two_to_the_32_elements(K, dev):
     """Row offsets beyond 2^31 bytes and 2^32 elements reached through the leading dimension (tests/_bigstride.py): the strided
     results equal the compact ones bit for bit and nothing is written outside the operand windows."""

@@ -417,6 +417,26 @@ def test_spmm_edge_cases(K, dev):
     np.testing.assert_array_equal(got, np.vstack([B2[2], np.zeros(4, np.float32)]))
 
 
+def test_spmm_takes_an_operand_without_rows_whatever_its_strides(K, dev):
+    """A rank that owns nothing: its 0 x f features come from numpy with the strides (0, 0), its local block has no rows, and the
+    halo block of a rank that receives nothing has rows and no columns.  No stride of a matrix without rows is ever used."""
+    f = 4
+    host = torch.from_numpy(np.zeros((5, f), np.float32)[np.zeros(0, np.int64)])
+    assert host.stride() == (0, 0)                                  # (what nodedata.load hands the model on such a rank)
+    B = torch.empty_strided((0, f), (0, 0), dtype=torch.float32, device=dev)
+    none = K.prepare(_host_csr(sp.csr_matrix((0, 0), dtype=np.float32)))
+    C = torch.empty_strided((0, f), (0, 0), dtype=torch.float32, device=dev)
+    assert K.spmm(none, B, C) is C and K.spmm(none, B, C, accumulate=True) is C
+    halo = K.prepare(_host_csr(sp.csr_matrix((3, 0), dtype=np.float32)))
+    C = torch.full((3, f), float("nan"), device=dev)
+    K.spmm(halo, B, C)
+    assert torch.equal(C, torch.zeros_like(C))
+    C.fill_(7.0)
+    K.spmm(halo, B, C, accumulate=True)
+    torch.cuda.synchronize()
+    assert torch.equal(C, torch.full_like(C, 7.0))
+
+
 def test_spmm_row_map(K, dev):
     partition = pkg("partition")
     A = sp.csr_matrix(mmread(gpath("gemat11p.A.mtx"))).astype(np.float32)
