@@ -325,6 +325,38 @@ int pgcn_aggmax_backward_csr_plan_f32(const int64_t *rowptr, const int32_t *col,
                                       int64_t ldd, int32_t f, float *partial_ws, int64_t partial_ws_elems, int64_t nslots,
                                       uint32_t flags, pgcn_stream_t stream);
 
+/* ---- SOFTMAX aggregation over the neighbourhood (DeeperGCN, Li et al. 2020; no counterpart in the reference) ----
+ * One softmax PER FEATURE column c over the stored columns j of row i (stored values are ignored), x_j = B[j, c], beta finite and >= 0:
+ *   LSE[i, c] = log sum_j exp(beta x_j)        OUT[i, c] = sum_j exp(beta x_j - LSE[i, c]) x_j        a row without entries: 0.0f, -inf
+ * beta = 0 is the mean of the neighbourhood, beta -> inf its max.  pairs / tasks / seg / nslices / fix / nslots: a structure and plan as
+ * pgcn_aggmax_csr_plan_f32 takes them (the global-id half of a pair is not read, the order of the entries inside a task is free).  A
+ * finished (OUT, LSE) is a mergeable state, "mass e^LSE with mean OUT":
+ *   L = max(L1, L2), e1 = exp(L1 - L), e2 = exp(L2 - L):  LSE' = L + log(e1 + e2),  OUT' = (OUT1 e1 + OUT2 e2) / (e1 + e2)
+ * (-inf: absent; two absent groups merge to absent).  The rule merges the pieces of a cut row in slot order (ws: nslots x f floats of
+ * OUT followed by nslots x f floats of LSE) and, with PGCN_SPMM_ACCUMULATE, takes the row's current (OUT, LSE) as one more group; without
+ * it the outputs are written, whatever they held.  The results are NOT bit-identical under different plans or splits (the order of the
+ * additions differs, as for the sum).  flags: PGCN_SPMM_ACCUMULATE, _XCD_SWIZZLE, _OFFSETS32, _FPASS64.  Any f >= 1 and leading
+ * dimensions >= f; a float4 body when f % 4 == 0 with 16-byte aligned operands, a guarded scalar body otherwise.  Inputs are finite by
+ * contract.  PGCN_EINVAL without touching a device on null pointers, f < 1, ld < f, a negative or non-finite beta; a structure without
+ * rows returns at once.  No atomics, deterministic.
+ *
+ * pgcn_aggsoftmax_backward_csr_plan_f32: over the TRANSPOSED structure (col: int32 per entry, slot_row[nslots]: the row of every slot,
+ * required when nslots > 0), X the rows of this structure (x = X[r, c]), G / OUT / LSE indexed by the stored entries i:
+ *   D[r, c] = sum over the stored entries i of row r of G[i, c] exp(beta X[r, c] - LSE[i, c]) (1 + beta (X[r, c] - OUT[i, c]))
+ * -- gather form, entries in storage order, the pieces of a cut row added in slot order (pgcn_spmm_fixup_f32): deterministic, no atomics;
+ * the float4 and the scalar body give the same bits.  D is written, never accumulated into.  PGCN_SPMM_OFFSETS32: every byte offset into
+ * G, OUT AND LSE fits 32 bits.  partial_ws: nslots x f floats.                                                                      */
+int pgcn_aggsoftmax_csr_plan_f32(const int64_t *rowptr, const int32_t *pairs, const int32_t *tasks, int64_t ntasks,
+                                 const int64_t *seg, int32_t nslices, const int32_t *fix, int64_t nfix, const float *B, int64_t ldb,
+                                 float *OUT, int64_t ldo, float *LSE, int64_t ldl, float beta, int32_t f, void *ws, int64_t ws_bytes,
+                                 int64_t nslots, uint32_t flags, pgcn_stream_t stream);
+int pgcn_aggsoftmax_backward_csr_plan_f32(const int64_t *rowptr, const int32_t *col, const int32_t *slot_row, const int32_t *tasks,
+                                          int64_t ntasks, const int64_t *seg, int32_t nslices, const int32_t *fix, int64_t nfix,
+                                          const float *X, int64_t ldx, const float *G, int64_t ldg, const float *OUT, int64_t ldo,
+                                          const float *LSE, int64_t ldl, float *D, int64_t ldd, float beta, int32_t f,
+                                          float *partial_ws, int64_t partial_ws_elems, int64_t nslots, uint32_t flags,
+                                          pgcn_stream_t stream);
+
 /* ---- DropEdge (Rong et al., ICLR 2020; no counterpart in the reference): the aggregation over a pattern whose entries are dropped
  * anew at every training step and renormalised.  csrc/pgcn_dropedge.h states the keep function:
  *   keep(gi, gj) = gi == gj || u(seed, step[0], min(gi, gj), max(gi, gj)) >= thr      (GLOBAL ids below 2^31; thr: dropout's threshold)

@@ -219,6 +219,42 @@ class PAggMax(torch.autograd.Function):
         return None, dH
 
 
+def _softmax_beta(value, what="softmax_beta"):
+    """A finite number >= 0 as float (0 and 0.0 are values; a bool is not a number here)."""
+    import numbers
+    if isinstance(value, bool) or not isinstance(value, numbers.Real) or not math.isfinite(value) or value < 0:
+        raise ValueError("%s takes a finite number >= 0, got %r" % (what, value))
+    return float(value)
+
+
+class PAggSoftmax(torch.autograd.Function):
+    """The softmax aggregation of DeeperGCN (Li et al., 2020) in place of ``PSpMM``'s weighted sum (csrc/pgcn_aggsoftmax.hip; the stored
+    values are ignored, under ``normalize="sym"`` a vertex is its own neighbour): per feature the softmax(beta x)-weighted mean of the
+    neighbourhood -- beta = 0 its mean, beta -> inf its max.  Forward ``A.forward_softmax`` with the halo exchange, backward
+    ``A.backward_softmax``: every neighbour receives gradient.  Saved: H, the received halo rows, OUT (the output the next node keeps
+    anyway) and LSE.  The constant feature matrix of the first layer needs no gradient: nothing is saved, nothing is aggregated."""
+
+    @staticmethod
+    def forward(ctx, A, H, beta):
+        ctx.A, ctx.beta = A, beta
+        OUT, LSE, halo = A.forward_softmax(H, beta)
+        if ctx.needs_input_grad[1]:
+            ctx.has_halo = halo is not None
+            ctx.save_for_backward(H, OUT, LSE, *([halo] if halo is not None else []))
+        return OUT
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        dH = None
+        if ctx.needs_input_grad[1]:
+            H, OUT, LSE = ctx.saved_tensors[:3]
+            dH = ctx.A.backward_softmax(grad_output, H, ctx.saved_tensors[3] if ctx.has_halo else None, OUT, LSE, ctx.beta)
+        join = getattr(ctx.A, "join_wgrad", None)        # (as PSpMM.backward: the weight gradient parked on the engine's side stream)
+        if join is not None:
+            join()
+        return None, dH, None
+
+
 class PSpMMDrop(torch.autograd.Function):
     """``PSpMM`` under DropEdge (Rong et al., ICLR 2020; csrc/pgcn_dropedge.hip): the aggregation over the stored pattern of A + I
     minus the entries dropped in this training step, renormalised -- forward ``A.forward_drop``, backward ``A.backward_drop`` under the
@@ -1392,14 +1428,24 @@ class PGCN(nn.Module):
     ``drop_edge=ctx`` (opt-in; a dropout.EdgeDrop, shared by the layers of a model): DropEdge -- in training mode the aggregation is
     ``PSpMMDrop``, over the entries of the pattern that survive this step, renormalised; ``A`` must be built with
     ``normalize="sym"``.  ``eval()``, or a probability of 0, takes ``PSpMM`` bit for bit.  Refused with ``aggr="max"`` and
-    ``aggregate=False``.  None: the branches of before."""
+    ``aggregate=False``.  None: the branches of before.
+
+    ``softmax_beta=B`` (opt-in; a finite number >= 0, 0 included, no bool): the aggregation is ``PAggSoftmax`` -- per feature the
+    softmax(B x)-weighted mean of the stored neighbourhood, stored values ignored -- instead of ``PSpMM``; every other option
+    composes through the same nodes and the layer owns the same parameters under the same keys.  Refused with ``aggr="max"``,
+    ``aggregate=False`` and an active ``drop_edge``.  None: the branches of before."""
 
     def __init__(self, A, in_features, out_features, dropout=0.0, layer=0, state=None, relu=True, norm=None, root_weight=False, bias=False,
-                 residual=False, aggr=None, aggregate=True, drop_edge=None):
+                 residual=False, aggr=None, aggregate=True, drop_edge=None, softmax_beta=None):
         super(PGCN, self).__init__()
         if aggr not in AGGRS + (None,):
             raise ValueError("aggr takes %s, got %r" % (" | ".join(AGGRS), aggr))
         self.aggregate = bool(aggregate)
+        if softmax_beta is not None:
+            softmax_beta = _softmax_beta(softmax_beta)
+            if aggr == "max" or not self.aggregate or (drop_edge is not None and drop_edge.on):
+                raise ValueError("softmax_beta does not go with %s" % ('aggr="max"' if aggr == "max" else "aggregate=False"
+                                                                       if not self.aggregate else "drop_edge"))
         if not self.aggregate and (aggr == "max" or root_weight):
             raise ValueError("aggregate=False does not go with %s" % ('aggr="max"' if aggr == "max" else "root_weight=True"))
         self._aggregate = _no_aggregation if not self.aggregate else PAggMax.apply if aggr == "max" else PSpMM.apply
@@ -1409,6 +1455,9 @@ class PGCN(nn.Module):
             if drop_edge.on:
                 self.drop_edge = drop_edge
                 self._aggregate = self._aggregate_drop
+        if softmax_beta is not None:
+            self.softmax_beta = softmax_beta
+            self._aggregate = self._aggregate_softmax
         self.linear = nn.Linear(in_features, out_features, bias=False)
         self.A = A
         self.send_map = send_map
@@ -1449,6 +1498,9 @@ class PGCN(nn.Module):
     def _aggregate_drop(self, A, H):
         """The aggregation of a layer with DropEdge on: dropped and renormalised in training mode, ``PSpMM`` in eval mode."""
         return PSpMMDrop.apply(A, H, self.drop_edge) if self.training else PSpMM.apply(A, H)
+
+    def _aggregate_softmax(self, A, H):
+        return PAggSoftmax.apply(A, H, self.softmax_beta)
 
     def _global_row_ids(self, H):
         if self._row_ids is None or self._row_ids.device != H.device:      # global ids in local row order, once
@@ -1666,7 +1718,7 @@ def _barrier():
 
 
 def _architecture(fin, classes, nlayers, nfeatures, hidden, multilabel, dropout, dropout_seed, norm, root_weight, bias, residual, aggr=None,
-                  propagate=None, ppr_alpha=None, dense_layers=None, drop_edge=None):
+                  propagate=None, ppr_alpha=None, dense_layers=None, drop_edge=None, softmax_beta=None):
     """checkpoint.architecture of the model ``_train_on_data`` builds from these arguments (``drop_edge``: recorded only when it is
     positive, so that earlier checkpoints compare as before)."""
     widths = [int(fin)] + [int(nfeatures if hidden is None else hidden)] * (nlayers - 1) + [int(classes)]
@@ -1674,7 +1726,22 @@ def _architecture(fin, classes, nlayers, nfeatures, hidden, multilabel, dropout,
                                     residual, **({"aggr": aggr} if aggr == "max" else {}),
                                     **({"propagate": (propagate, PPR_ALPHA if ppr_alpha is None else ppr_alpha)} if propagate is not None else {}),
                                     **({"dense_layers": True} if dense_layers else {}),
-                                    **({"drop_edge": float(drop_edge)} if drop_edge else {}))
+                                    **({"drop_edge": float(drop_edge)} if drop_edge else {}),
+                                    **({"softmax_beta": float(softmax_beta)} if softmax_beta is not None else {}))
+
+
+def _check_softmax_beta(softmax_beta, aggr=None, dense_layers=None, drop_edge=None):
+    """ValueError for a ``softmax_beta`` that no model can be built from: not a finite number >= 0, or given with ``aggr="max"``,
+    ``dense_layers`` or a positive ``drop_edge``."""
+    if softmax_beta is None:
+        return
+    _softmax_beta(softmax_beta)
+    if aggr == "max":
+        raise ValueError('softmax_beta does not go with aggr="max"')
+    if dense_layers:
+        raise ValueError("softmax_beta does not go with dense_layers: nothing is aggregated")
+    if drop_edge:
+        raise ValueError("softmax_beta does not go with drop_edge")
 
 
 def _check_drop_edge(drop_edge, normalize=None, aggr=None, dense_layers=None, check_normalize=True):
@@ -1718,7 +1785,7 @@ OPTIMIZERS = _nodeloss.OPTIMIZERS      # --optimizer / run(optimizer=...): "torc
 def _train_on_data(A, n, nlayers, nfeatures, features, labels, split, hidden, epochs, lr, eval_every, dropout, dropout_seed,
                    multilabel=False, weight_decay=0.0, decoupled_decay=False, optimizer="torch", norm=None, root_weight=None, bias=None,
                    residual=None, save=None, load=None, predict=None, proba=None, control=None, aggr=None, propagate=None, ppr_alpha=None,
-                   dense_layers=None, drop_edge=None):
+                   dense_layers=None, drop_edge=None, softmax_beta=None):
     """The loop of ``run`` on real inputs: widths fin -> hidden -> ... -> C, no ReLU on the last layer, constant features (the
     first layer's backward aggregation is skipped), Adam, the masked loss over the train rows.  Reports every ``eval_every``
     epochs: without dropout from the record of the training step's own pass (the logits BEFORE that step's update), with
@@ -1745,9 +1812,11 @@ def _train_on_data(A, n, nlayers, nfeatures, features, labels, split, hidden, ep
     model of before.  ``drop_edge=P`` > 0: DropEdge -- every layer's aggregation runs, in training mode, over the entries of the
     pattern that survive the step, renormalised (class PGCN, ``PSpMMDrop``; ``A`` built with ``normalize="sym"``); the mask's seed and
     step are the dropout state's, which then exists even with ``dropout`` = 0, and the reporting rule is dropout's: ``evaluate`` in
-    eval mode after the update.  ``Propagate`` keeps the undropped matrix."""
+    eval mode after the update.  ``Propagate`` keeps the undropped matrix.  ``softmax_beta=B``: every layer aggregates by the softmax
+    aggregation (class PGCN, ``PAggSoftmax``); ``Propagate`` keeps ``PSpMM``.  None: the model of before."""
     _check_propagate(propagate, ppr_alpha, dense_layers, aggr, root_weight)
     _check_drop_edge(drop_edge, getattr(A.part, "normalize", None), aggr, dense_layers)
+    _check_softmax_beta(softmax_beta, aggr, dense_layers, drop_edge)
     drop_edge = float(drop_edge or 0.0)
     task = _nodeloss.TASKS["multilabel" if multilabel else "single"]
     data = task.load(features, labels, split, A.part.owned, n, device=device)
@@ -1771,6 +1840,8 @@ def _train_on_data(A, n, nlayers, nfeatures, features, labels, split, hidden, ep
         extra["aggregate"] = False
     if drop_edge > 0.0:
         extra["drop_edge"] = _dropout.EdgeDrop(drop_edge, state)       # one context: the layers of a step share the mask and its scales
+    if softmax_beta is not None:
+        extra["softmax_beta"] = softmax_beta
     tail = [Propagate(A, propagate, PPR_ALPHA if ppr_alpha is None else float(ppr_alpha))] if propagate is not None else []
     model = nn.Sequential(*[PGCN(A, widths[i], widths[i + 1], dropout=dropout if i < nlayers - 1 else 0.0, layer=i, state=state,
                                  relu=i < nlayers - 1, **({"norm": norm} if norm not in (None, "none") and i < nlayers - 1 else {}),
@@ -1784,7 +1855,7 @@ def _train_on_data(A, n, nlayers, nfeatures, features, labels, split, hidden, ep
     first, history, best, hooks = 0, [], None, None
     if save is not None or load is not None or predict is not None or proba:
         arch = _architecture(data.fin, data.classes, nlayers, nfeatures, hidden, multilabel, dropout, dropout_seed, norm, root_weight,
-                             bias, residual, aggr, propagate, ppr_alpha, dense_layers, drop_edge)
+                             bias, residual, aggr, propagate, ppr_alpha, dense_layers, drop_edge, softmax_beta)
         hooks = _checkpoint.Hooks("PGCN", arch, model, fused, opt, state, save, load, predict, proba, myrank, _barrier)
         first, history, best = hooks.resume()
     last = first + epochs - 1
@@ -1841,7 +1912,7 @@ def run(rank, size, nlayers, nfeatures, path_A, path_partvec, backend, normalize
         features=None, labels=None, split=None, hidden=None, epochs=None, lr=None, eval_every=None, task=None,
         weight_decay=None, decoupled_decay=None, optimizer=None, norm=None, root_weight=None, bias=None, residual=None,
         save=None, load=None, predict=None, proba=None, aggr=None, propagate=None, ppr_alpha=None, dense_layers=None, drop_edge=None,
-        **control):
+        softmax_beta=None, **control):
     """PGCN.py:162-238.  ``normalize="sym"``: train on D_r^-1/2 (A + I) D_c^-1/2 of the pattern of ``path_A``, built on the fly
     (partition.build_partition) instead of by the offline pass preprocess/GrB-GNN-IDG.py.  ``dropout`` > 0: the output of every
     layer but the last is dropped with that probability (class PGCN), masks from (``dropout_seed``, step, layer, global row,
@@ -1882,7 +1953,12 @@ def run(rank, size, nlayers, nfeatures, path_A, path_partvec, backend, normalize
     every stored entry of the pattern of A + I off the diagonal is dropped with that probability, in both directions at once, and
     what is left is renormalised by its own degrees (``PSpMMDrop``, csrc/pgcn_dropedge.hip); one mask for all layers of a step, keyed
     by (``dropout_seed``, step, the two global ids) and so the same under any part vector; evaluation runs on the full matrix.  Not
-    with ``aggr="max"`` or ``dense_layers``.  A checkpoint records a positive value and resumes exactly (the dropout step)."""
+    with ``aggr="max"`` or ``dense_layers``.  A checkpoint records a positive value and resumes exactly (the dropout step).
+    ``softmax_beta`` (a finite number >= 0; needs the three files): every layer aggregates by the softmax aggregation of DeeperGCN
+    (``PAggSoftmax``, csrc/pgcn_aggsoftmax.hip): per feature the softmax(beta x)-weighted mean of a vertex's stored neighbourhood --
+    0 its mean, large values its max; the stored values are ignored, with ``normalize="sym"`` a vertex is its own neighbour.  Not
+    with ``aggr="max"``, ``dense_layers`` or a positive ``drop_edge``.  A checkpoint records it: loading one under another value, or
+    without it, raises ValueError naming ``softmax_beta``."""
     global myrank, world_size, send_map, recv_map, device, X, recv_buffers, send_buffers, stats
     for name in control:
         if name not in _nodeloss.CONTROL:
@@ -1922,6 +1998,9 @@ def run(rank, size, nlayers, nfeatures, path_A, path_partvec, backend, normalize
     _check_drop_edge(drop_edge, normalize, aggr, dense_layers)
     if drop_edge is not None and not all(given):
         raise ValueError("drop_edge needs features, labels and split")
+    _check_softmax_beta(softmax_beta, aggr, dense_layers, drop_edge)
+    if softmax_beta is not None and not all(given):
+        raise ValueError("softmax_beta needs features, labels and split")
     if (save is not None or load is not None or predict is not None or proba is not None) and not all(given):
         raise ValueError("save, load, predict and proba need features, labels and split")
     if proba and predict is None:
@@ -1946,7 +2025,7 @@ def run(rank, size, nlayers, nfeatures, path_A, path_partvec, backend, normalize
         opened = _nodeloss.TASKS[task or "single"].open_checked(features, labels, split, len(partvec))
         if load is not None:
             arch = _architecture(opened[3], opened[4], nlayers, nfeatures, hidden, multilabel, dropout, dropout_seed, norm, root_weight,
-                                 bias, residual, aggr, propagate, ppr_alpha, dense_layers, drop_edge)
+                                 bias, residual, aggr, propagate, ppr_alpha, dense_layers, drop_edge, softmax_beta)
             load = _checkpoint.load(load, "PGCN", arch, optimizer or "torch")
         del opened
         if control and load is not None:        # (the horizon against the warm-up, from the epoch the checkpoint stands at)
@@ -1999,7 +2078,8 @@ def run(rank, size, nlayers, nfeatures, path_A, path_partvec, backend, normalize
                               **({"control": control} if control else {}), **({"aggr": "max"} if aggr == "max" else {}),
                               **{k: v for k, v in (("propagate", propagate), ("ppr_alpha", ppr_alpha)) if v is not None},
                               **({"dense_layers": True} if dense_layers else {}),
-                              **({"drop_edge": float(drop_edge)} if drop_edge else {}))
+                              **({"drop_edge": float(drop_edge)} if drop_edge else {}),
+                              **({"softmax_beta": float(softmax_beta)} if softmax_beta is not None else {}))
 
     owned = A.part.owned.to(device)
     # PGCN.py:186-188 synthetic features H[i,:] = i, owned rows only
@@ -2076,9 +2156,9 @@ def init_process(rank, size, fn, nlayers, nfeatures, path_A, path_partvec, backe
                  features=None, labels=None, split=None, hidden=None, epochs=None, lr=None, eval_every=None, task=None,
                  weight_decay=None, decoupled_decay=None, optimizer=None, norm=None, root_weight=None, bias=None, residual=None,
                  save=None, load=None, predict=None, proba=None, control=None, aggr=None, propagate=None, ppr_alpha=None, dense_layers=None,
-                 drop_edge=None):
+                 drop_edge=None, softmax_beta=None):
     """PGCN.py:241-253.  ``control``: the given options of nodeloss.CONTROL as one dict (None: today's call).  ``aggr``, ``propagate``,
-    ``ppr_alpha``, ``dense_layers``, ``drop_edge``: run's."""
+    ``ppr_alpha``, ``dense_layers``, ``drop_edge``, ``softmax_beta``: run's."""
     global _exchanger
     dist.init_process_group(backend, rank=rank, world_size=size)
 
@@ -2099,7 +2179,8 @@ def init_process(rank, size, fn, nlayers, nfeatures, path_A, path_partvec, backe
                     ("eval_every", eval_every), ("task", task), ("weight_decay", weight_decay), ("decoupled_decay", decoupled_decay),
                     ("optimizer", optimizer), ("norm", norm), ("root_weight", root_weight), ("bias", bias),
                     ("residual", residual), ("save", save), ("load", load), ("predict", predict), ("proba", proba), ("aggr", aggr),
-                    ("propagate", propagate), ("ppr_alpha", ppr_alpha), ("dense_layers", dense_layers)):
+                    ("propagate", propagate), ("ppr_alpha", ppr_alpha), ("dense_layers", dense_layers),
+                    ("softmax_beta", softmax_beta)):
         if v is not None:
             kw[name] = v
     kw.update(control or {})
@@ -2126,7 +2207,7 @@ def main(argv):
         opts, args = getopt.getopt(argv, "a:p:b:s:l:f:", ["normalize=", "dropout=", "dropout-seed=", "features=", "labels=", "split=",
                                                           "hidden=", "epochs=", "lr=", "eval-every=", "task=", "weight-decay=", "adamw",
                                                           "optimizer=", "norm=", "root-weight", "bias", "residual", "save=", "load=",
-                                                          "predict=", "proba", "aggr=", "propagate=", "ppr-alpha=", "dense-layers", "drop-edge="] + [f[2:] + "=" for f in _nodeloss.CONTROL_FLAGS.split(", ")])
+                                                          "predict=", "proba", "aggr=", "propagate=", "ppr-alpha=", "dense-layers", "drop-edge=", "softmax-aggr="] + [f[2:] + "=" for f in _nodeloss.CONTROL_FLAGS.split(", ")])
     except getopt.GetoptError:
         print("a:p:b:", flush=True)
         sys.exit(2)
@@ -2224,6 +2305,14 @@ def main(argv):
             except ValueError:
                 print("--drop-edge takes a probability in [0, 1), got %r" % arg, flush=True)
                 sys.exit(2)
+        elif opt == '--softmax-aggr':  # the softmax aggregation of DeeperGCN with this beta (0: the mean, large: the max): PAggSoftmax
+            try:
+                data["softmax_beta"] = float(arg)
+                if not (data["softmax_beta"] >= 0.0 and math.isfinite(data["softmax_beta"])):
+                    raise ValueError
+            except ValueError:
+                print("--softmax-aggr takes a finite number >= 0, got %r" % arg, flush=True)
+                sys.exit(2)
         elif opt == '--root-weight':   # every layer adds H . W_r^T: a vertex's own features get their own weights (class PGCN)
             data["root_weight"] = True
         elif opt == '--bias':          # every layer adds a bias (a normalised layer keeps bn_bias alone)
@@ -2257,7 +2346,7 @@ def main(argv):
     os.environ.setdefault("WORLD_SIZE", str(size))
     files = [k for k in ("features", "labels", "split") if k in data]
     if data and len(files) != 3:
-        print("--features, --labels and --split go together (and --hidden, --epochs, --lr, --eval-every, --task, --weight-decay, --adamw, --optimizer, --save, --load, --predict, --proba, --aggr, --propagate, --ppr-alpha, --dense-layers, --drop-edge, %s, --norm, --residual, --root-weight, --bias need them); got %%s"
+        print("--features, --labels and --split go together (and --hidden, --epochs, --lr, --eval-every, --task, --weight-decay, --adamw, --optimizer, --save, --load, --predict, --proba, --aggr, --propagate, --ppr-alpha, --dense-layers, --drop-edge, --softmax-aggr, %s, --norm, --residual, --root-weight, --bias need them); got %%s"
               % _nodeloss.CONTROL_FLAGS % ", ".join("--" + {"decoupled_decay": "adamw"}.get(k, k.replace("_", "-")) for k in sorted(data)), flush=True)
         sys.exit(2)
     for k in files:
@@ -2280,6 +2369,12 @@ def main(argv):
             sys.exit(2)
         if data.get("aggr") == "max" or "dense_layers" in data:
             print("--drop-edge does not go with %s" % ("--aggr max" if data.get("aggr") == "max" else "--dense-layers"), flush=True)
+            sys.exit(2)
+    if "softmax_beta" in data:
+        clash = ("--aggr max" if data.get("aggr") == "max" else "--dense-layers" if "dense_layers" in data
+                 else "--drop-edge" if data.get("drop_edge", 0.0) > 0.0 else None)
+        if clash:
+            print("--softmax-aggr does not go with %s" % clash, flush=True)
             sys.exit(2)
     if "load" in data and not os.path.exists(data["load"]):
         print("--load: no such file %r" % (data["load"],), flush=True)
@@ -2317,7 +2412,7 @@ def main(argv):
                 args += layer_opts
             if has_residual:                   # (the tuple grows only when --residual is given)
                 args += (True,)
-    named = {k: data[k] for k in ("aggr", "propagate", "ppr_alpha", "dense_layers", "drop_edge") if k in data}      # (by name, only when given)
+    named = {k: data[k] for k in ("aggr", "propagate", "ppr_alpha", "dense_layers", "drop_edge", "softmax_beta") if k in data}      # (by name, only when given)
     p = mp.Process(target=init_process, args=args, **({"kwargs": named} if named else {}))
     p.start()
     p.join()

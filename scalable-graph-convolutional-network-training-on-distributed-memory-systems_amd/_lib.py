@@ -78,6 +78,10 @@ SIGNATURES = {
                                                 _i64, _u32, _vp]),
     "pgcn_aggmax_backward_csr_plan_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _i32, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64,
                                                          _i32, _vp, _i64, _i64, _u32, _vp]),
+    "pgcn_aggsoftmax_csr_plan_f32": (ctypes.c_int, [_vp, _vp, _vp, _i64, _vp, _i32, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, ctypes.c_float,
+                                                    _i32, _vp, _i64, _i64, _u32, _vp]),
+    "pgcn_aggsoftmax_backward_csr_plan_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _vp, _i32, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64,
+                                                             _vp, _i64, _vp, _i64, ctypes.c_float, _i32, _vp, _i64, _i64, _u32, _vp]),
     "pgcn_dropedge_sum_csr_plan_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _i32, _vp, _i64, _vp, _i64, _vp, _i64, _i32, _vp,
                                                       _i64, _i64, ctypes.c_uint64, _vp, _u32, _u32, _vp]),
     "pgcn_dropedge_count_csr_plan_i32": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, ctypes.c_uint64, _vp, _u32, _u32,

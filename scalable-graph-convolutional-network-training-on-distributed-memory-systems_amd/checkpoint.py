@@ -38,17 +38,18 @@ from . import nodedata as _nodedata
 
 FORMAT_VERSION = 1
 ARCH_FIELDS = ("task", "layers", "widths", "norm", "root_weight", "bias", "residual", "heads", "out_heads", "dropout", "dropout_seed", "aggr",
-               "drop_edge", "propagate", "dense_layers")
+               "drop_edge", "softmax_beta", "propagate", "dense_layers")
 
 
 def architecture(widths, task, dropout=0.0, dropout_seed=0, norm=None, root_weight=None, bias=None, residual=None, heads=None,
-                 out_heads=None, aggr=None, propagate=None, dense_layers=None, drop_edge=None):
+                 out_heads=None, aggr=None, propagate=None, dense_layers=None, drop_edge=None, softmax_beta=None):
     """The plain-value record of what a model was built from; two models of equal records have state dicts of equal keys and shapes,
     and draw the same dropout masks.  ``aggr``: the key exists only for "max" -- a record of the weighted sum is the record of before,
     and compares equal to every checkpoint written without the key.  Likewise ``propagate`` ((K, alpha): the key holds [K, alpha]
     only when the model ends with the personalised-PageRank propagation) and ``dense_layers`` (True only when the layers do not
     aggregate): without them the record is the record of before.  ``drop_edge``: the key holds the DropEdge probability only when it is
-    positive; the mask's seed is ``dropout_seed``, recorded when either probability is positive."""
+    positive; the mask's seed is ``dropout_seed``, recorded when either probability is positive.  ``softmax_beta``: the key holds the
+    softmax aggregation's beta (a float, 0.0 included) only when one is given."""
     arch = {"widths": [int(w) for w in widths], "layers": len(widths) - 1, "task": str(task or "single"),
             "norm": "none" if norm in (None, "none") else str(norm), "root_weight": bool(root_weight), "bias": bool(bias),
             "residual": bool(residual), "heads": None if heads is None else int(heads),
@@ -62,6 +63,8 @@ def architecture(widths, task, dropout=0.0, dropout_seed=0, norm=None, root_weig
         arch["dense_layers"] = True
     if float(drop_edge or 0.0) > 0.0:
         arch["drop_edge"] = float(drop_edge)
+    if softmax_beta is not None:
+        arch["softmax_beta"] = float(softmax_beta)
     return arch
 
 

@@ -512,6 +512,61 @@ def aggmax_backward_composed(AT: ComposedMaxCSR, row_gid: torch.Tensor, G: torch
     return D
 
 
+# --------------------------------------------------------------------------
+# softmax aggregation: the composed route (framework operations; the definitions of csrc/pgcn_aggsoftmax.hip)
+
+
+def softmax_merge(o1, l1, o2, l2):
+    """The merge rule of the softmax aggregation: two finished groups (OUT, LSE) -- "mass e^LSE with mean OUT" -- as one.  -inf:
+    absent; two absent groups merge to absent (0.0, -inf), no NaN."""
+    L = torch.maximum(l1, l2)
+    none = L == float("-inf")
+    Ls = torch.where(none, torch.zeros_like(L), L)
+    e1, e2 = torch.exp(l1 - Ls), torch.exp(l2 - Ls)
+    t = e1 + e2
+    out = torch.where(none, torch.zeros_like(o1), (o1 * e1 + o2 * e2) / torch.where(none, torch.ones_like(t), t))
+    return out, torch.where(none, L, Ls + torch.log(torch.where(none, torch.ones_like(t), t)))
+
+
+def aggsoftmax_composed(A: ComposedMaxCSR, B: torch.Tensor, OUT: torch.Tensor, LSE: torch.Tensor, beta, accumulate: bool = False):
+    """(OUT, LSE) of ``HipKernels.aggsoftmax`` from framework operations: per row and feature the softmax(beta x)-weighted mean of
+    B[col] over the stored entries and the log of the sum of exp(beta x); a row without entries (0.0, -inf).  ``accumulate``: the rows'
+    current (OUT, LSE) join by ``softmax_merge``.  nnz x f temporaries: the route of CPU tensors and of providers without the kernels."""
+    n, f, beta = A.nrows, B.shape[1], float(beta)
+    out = torch.zeros((n, f), dtype=B.dtype, device=B.device)
+    lse = torch.full((n, f), float("-inf"), dtype=B.dtype, device=B.device)
+    if A.nnz:
+        X = B.detach()[A.col]                                                          # nnz x f
+        ridx = A.row.unsqueeze(1).expand(-1, f)
+        top = torch.full((n, f), float("-inf"), dtype=B.dtype, device=B.device).scatter_reduce(0, ridx, beta * X, "amax", include_self=True)
+        E = torch.exp(beta * X - top[A.row])                                           # the running maximum: no overflow
+        s = torch.zeros((n, f), dtype=B.dtype, device=B.device).index_add_(0, A.row, E)
+        w = torch.zeros((n, f), dtype=B.dtype, device=B.device).index_add_(0, A.row, E * X)
+        has = s > 0
+        one = torch.ones_like(s)
+        out = torch.where(has, w / torch.where(has, s, one), out)
+        lse = torch.where(has, top + torch.log(torch.where(has, s, one)), lse)
+    if accumulate:
+        out, lse = softmax_merge(OUT[:n], LSE[:n], out, lse)
+    OUT[:n] = out
+    LSE[:n] = lse
+    return OUT, LSE
+
+
+def aggsoftmax_backward_composed(AT: ComposedMaxCSR, X: torch.Tensor, G: torch.Tensor, OUT: torch.Tensor, LSE: torch.Tensor,
+                                 D: torch.Tensor, beta):
+    """D of ``HipKernels.aggsoftmax_backward`` from framework operations: D[r] = sum over the stored entries i of row r of the
+    transposed structure of G[i] exp(beta X[r] - LSE[i]) (1 + beta (X[r] - OUT[i])).  The same definition; only the order of the fp32
+    additions is the framework's."""
+    beta = float(beta)
+    D[:AT.nrows] = 0
+    if AT.nnz:
+        x = X.detach()[AT.row]
+        term = G.detach()[AT.col] * torch.exp(beta * x - LSE[AT.col]) * (1 + beta * (x - OUT[AT.col]))
+        D[:AT.nrows].index_add_(0, AT.row, term)
+    return D
+
+
 @dataclasses.dataclass
 class MaxStructures:
     """What ``AggregationEngine.forward_max`` / ``backward_max`` run on, built at the first max call: the whole pattern of every
@@ -825,14 +880,15 @@ class AggregationEngine(BoundaryExchange):
     # ------------------------------------------------------------------
     # max aggregation (csrc/pgcn_aggmax.hip): OUT[i, c] = max over the stored columns j of row i of H[j, c], ARG the
     # smallest GLOBAL id that attains it -- the same bits under any part vector, numbering and split into local / halo structures
-    def _max_structures(self) -> MaxStructures:
-        """Built once, at the first max call: an engine that only sums never holds them.  The route is chosen here, before the first
-        launch: the provider's kernels on a HIP device, else the composed framework route (same definition, same OUT / ARG bits)."""
+    def _max_structures(self, kernels=("aggmax", "aggmax_backward")) -> MaxStructures:
+        """Built once, at the first max (or softmax) call: an engine that only sums never holds them.  The route is chosen here, before
+        the first launch: the provider's kernels on a HIP device (``kernels``: the two the caller launches), else the composed framework
+        route (same definition, same OUT / ARG bits)."""
         if self._max is None:
             part, k = self.part, self.k
             if part.n >= 2 ** 31:
                 raise ValueError("max aggregation keeps global ids as int32: n = %d >= 2^31 is not supported" % part.n)
-            composed = not (self.on_gpu and all(hasattr(k, m) for m in ("prepare_max", "aggmax", "aggmax_backward")))
+            composed = not (self.on_gpu and all(hasattr(k, m) for m in ("prepare_max",) + tuple(kernels)))
             if composed:
                 fwd = lambda a, gid: composed_max_csr(a, gid, self.device)
             else:
@@ -894,6 +950,68 @@ class AggregationEngine(BoundaryExchange):
         waits = self._exchange_all(partial, self.round_recv_off, back, self.round_send_off, f,
                                    ready if self.overlap else None, tag="backward")
         run(m.loc_T, m.owned, G, ARG, dH)
+        for r in range(self.rounds):
+            waits[r]()
+            self.k.spmm(self.unpack[r], back, dH, accumulate=True)      # returned rows are sums: backward's unpack
+        return dH
+
+    # ------------------------------------------------------------------
+    # softmax aggregation (csrc/pgcn_aggsoftmax.hip): OUT[i, c] = sum_j softmax_j(beta H[j, c]) H[j, c] over the stored
+    # columns j of row i, LSE the log of the softmax's denominator.  On ``_max_structures()``: nothing new is prepared.
+    SOFTMAX_KERNELS = ("aggsoftmax", "aggsoftmax_backward")
+
+    def forward_softmax(self, H: torch.Tensor, beta):
+        """(OUT, LSE, halo): the softmax aggregation of H over every owned vertex's stored neighbourhood (stored values ignored; 0.0
+        and -inf for a vertex without neighbours), and the received boundary rows as a tensor of its own (None at size 1): the
+        backward needs x_j of halo columns on the rank that owns i.  The exchange and its overlap are ``forward_max``'s."""
+        if H.shape[0] != self.n_local:
+            raise ValueError("H must hold exactly the %d owned rows" % self.n_local)
+        m = self._max_structures(self.SOFTMAX_KERNELS)
+        run = aggsoftmax_composed if m.composed else self.k.aggsoftmax
+        H = H.contiguous()
+        f = H.shape[1]
+        OUT = torch.empty((self.n_local, f), dtype=torch.float32, device=self.device)
+        LSE = torch.empty((self.n_local, f), dtype=torch.float32, device=self.device)
+        if self.size == 1:
+            run(m.loc, H, OUT, LSE, beta)
+            return OUT, LSE, None
+        send = self._slab("send", self.n_send, f)
+        # kept for the backward: not the reused slab (at least one row, like a slab: a rank that receives nothing still hands the
+        # exchange an address)
+        halo = torch.empty((max(self.n_halo, 1), f), dtype=torch.float32, device=self.device)
+        self.k.gather_rows(H, self.send_idx, send)
+        waits = self._exchange_all(send, self.round_send_off, halo, self.round_recv_off, f, tag="forward")
+        run(m.loc, H, OUT, LSE, beta)            # overlaps the exchange
+        for r in range(self.rounds):
+            waits[r]()
+            run(m.halo[r], halo, OUT, LSE, beta, accumulate=True)      # round r's group joins the local result; overlaps round r+1
+        return OUT, LSE, halo
+
+    def backward_softmax(self, G: torch.Tensor, H: torch.Tensor, halo, OUT: torch.Tensor, LSE: torch.Tensor, beta) -> torch.Tensor:
+        """dH[j, c] = sum over the vertices i that hold j of G[i, c] p_ij,c (1 + beta (H[j, c] - OUT[i, c])): every neighbour receives
+        gradient.  Partial sums for rows owned by peers travel home like ``backward``'s and are ADDED."""
+        m = self._max_structures(self.SOFTMAX_KERNELS)
+        if m.loc_T is None:
+            raise RuntimeError("partition was built without the transposed pieces")
+        run = aggsoftmax_backward_composed if m.composed else self.k.aggsoftmax_backward
+        G, H = G.contiguous(), H.contiguous()
+        f = G.shape[1]
+        dH = torch.empty((self.n_local, f), dtype=torch.float32, device=self.device)
+        if self.size == 1:
+            return run(m.loc_T, H, G, OUT, LSE, dH, beta)
+        partial = self._slab("halo", self.n_halo, f)
+        back = self._slab("send", self.n_send, f)
+        ready = []
+        for r in range(self.rounds):
+            b0, b1 = self.round_recv_off[r][0], self.round_recv_off[r][-1]
+            run(m.halo_T[r], halo[b0:b1], G, OUT, LSE, partial[b0:b1], beta)
+            if self.overlap:
+                ev = torch.cuda.Event()
+                ev.record(torch.cuda.current_stream(self.device))
+                ready.append(ev)
+        waits = self._exchange_all(partial, self.round_recv_off, back, self.round_send_off, f,
+                                   ready if self.overlap else None, tag="backward")
+        run(m.loc_T, H, G, OUT, LSE, dH, beta)
         for r in range(self.rounds):
             waits[r]()
             self.k.spmm(self.unpack[r], back, dH, accumulate=True)      # returned rows are sums: backward's unpack

@@ -780,6 +780,100 @@ class HipKernels:
         fn(row_gid, G, ARG, D)
         return D
 
+    # -- softmax aggregation (pgcn_aggsoftmax.hip) ----------------------------
+    @staticmethod
+    def _softmax_beta(beta) -> float:
+        b = float(beta)
+        if not (0.0 <= b < float("inf")):
+            raise _lib.PgcnError("beta must be a finite number >= 0, got %r" % (beta,))
+        return b
+
+    def aggsoftmax(self, A: DeviceMaxCSR, B: torch.Tensor, OUT: torch.Tensor, LSE: torch.Tensor, beta, accumulate: bool = False):
+        """(OUT, LSE) of the softmax aggregation over the stored columns of every row of ``A`` (include/pgcn_hip.h,
+        pgcn_aggsoftmax_csr_plan_f32; a ``prepare_max(csr, col_gid)`` structure, nothing else is prepared) on the current stream;
+        ``accumulate``: the rows' current (OUT, LSE) join as one more group under the merge rule.  Bound once per operand set like
+        ``aggmax``.  Rows beyond ``A.nrows`` are not touched."""
+        if A.pairs is None:
+            raise _lib.PgcnError("aggsoftmax needs a structure made by prepare_max(csr, col_gid)")
+        beta = self._softmax_beta(beta)
+        key = ("softmax", B.stride(0), OUT.stride(0), LSE.stride(0), B.shape[1], beta, bool(accumulate))
+        fn = A.launch_cache.get(key)
+        if fn is None:
+            f = B.shape[1]
+            self._max_operand(B, A.ncols, torch.float32, "B")
+            self._max_operand(OUT, A.nrows, torch.float32, "OUT")
+            self._max_operand(LSE, A.nrows, torch.float32, "LSE")
+            if OUT.shape[1] != f or LSE.shape[1] != f:
+                raise _lib.PgcnError("B, OUT and LSE widths differ")
+            ldb, ldo, ldl = max(B.stride(0), f), max(OUT.stride(0), f), max(LSE.stride(0), f)
+            nrows = A.nrows
+            if nrows == 0 or (A.nnz == 0 and accumulate):
+                fn = lambda B, OUT, LSE: None
+            elif A.nnz == 0:            # nothing to launch: every row is empty (memsets, plumbing)
+                def fn(B, OUT, LSE):
+                    OUT[:nrows].zero_()
+                    LSE[:nrows].fill_(float("-inf"))
+            else:
+                flags = self.base_flags | (_lib.SPMM_ACCUMULATE if accumulate else 0) | self._max_fpass(A, f)
+                if (A.ncols + 1) * ldb * 4 < 2 ** 32:
+                    flags |= _lib.SPMM_OFFSETS32
+                ws, ws_n = self._max_ws(A, A.nslots * f * 8)
+                lib, check, stream = self.lib, _lib.check, self._stream
+                rowptr, pairs, tasks, ntasks, fix, nfix, nslots = (A.rowptr.data_ptr(), A.pairs.data_ptr(), _ptr(A.tasks), A.ntasks,
+                                                                   _ptr(A.fix), A.nfix, A.nslots)
+                seg, nslices = A.seg, A.nslices
+
+                def fn(B, OUT, LSE):
+                    check(lib.pgcn_aggsoftmax_csr_plan_f32(rowptr, pairs, tasks, ntasks, seg, nslices, fix, nfix, B.data_ptr(), ldb,
+                                                           OUT.data_ptr(), ldo, LSE.data_ptr(), ldl, beta, f, ws, ws_n, nslots, flags,
+                                                           stream()), "pgcn_aggsoftmax_csr_plan_f32")
+            A.launch_cache[key] = fn
+        fn(B, OUT, LSE)
+        return OUT, LSE
+
+    def aggsoftmax_backward(self, AT: DeviceMaxCSR, X: torch.Tensor, G: torch.Tensor, OUT: torch.Tensor, LSE: torch.Tensor,
+                            D: torch.Tensor, beta):
+        """D[r] = sum over the stored entries i of row r of the transposed structure of G[i] exp(beta X[r] - LSE[i]) (1 + beta (X[r] -
+        OUT[i])), element-wise (pgcn_aggsoftmax_backward_csr_plan_f32): deterministic, D is written.  ``X``: the rows of ``AT``."""
+        if AT.col is None:
+            raise _lib.PgcnError("aggsoftmax_backward needs a structure made by prepare_max(csr) without col_gid")
+        beta = self._softmax_beta(beta)
+        key = ("softmax", X.stride(0), G.stride(0), OUT.stride(0), LSE.stride(0), D.stride(0), G.shape[1], beta)
+        fn = AT.launch_cache.get(key)
+        if fn is None:
+            f = G.shape[1]
+            self._max_operand(X, AT.nrows, torch.float32, "X")
+            self._max_operand(G, AT.ncols, torch.float32, "G")
+            self._max_operand(OUT, AT.ncols, torch.float32, "OUT")
+            self._max_operand(LSE, AT.ncols, torch.float32, "LSE")
+            self._max_operand(D, AT.nrows, torch.float32, "D")
+            if not (X.shape[1] == OUT.shape[1] == LSE.shape[1] == D.shape[1] == f):
+                raise _lib.PgcnError("X, G, OUT, LSE and D widths differ")
+            ldx, ldg, ldo, ldl, ldd = (max(t.stride(0), f) for t in (X, G, OUT, LSE, D))
+            nrows = AT.nrows
+            if nrows == 0:
+                fn = lambda X, G, OUT, LSE, D: None
+            elif AT.nnz == 0:
+                fn = lambda X, G, OUT, LSE, D: D[:nrows].zero_()
+            else:
+                flags = self.base_flags | self._max_fpass(AT, f)
+                if (AT.ncols + 1) * max(ldg, ldo, ldl) * 4 < 2 ** 32:
+                    flags |= _lib.SPMM_OFFSETS32
+                ws, ws_n = self._max_ws(AT, AT.nslots * f * 4)
+                lib, check, stream = self.lib, _lib.check, self._stream
+                rowptr, col, srow, tasks, ntasks, fix, nfix, nslots = (AT.rowptr.data_ptr(), AT.col.data_ptr(), _ptr(AT.slot_row),
+                                                                       _ptr(AT.tasks), AT.ntasks, _ptr(AT.fix), AT.nfix, AT.nslots)
+                seg, nslices = AT.seg, AT.nslices
+
+                def fn(X, G, OUT, LSE, D):
+                    check(lib.pgcn_aggsoftmax_backward_csr_plan_f32(rowptr, col, srow, tasks, ntasks, seg, nslices, fix, nfix, X.data_ptr(),
+                                                                    ldx, G.data_ptr(), ldg, OUT.data_ptr(), ldo, LSE.data_ptr(), ldl,
+                                                                    D.data_ptr(), ldd, beta, f, ws, ws_n // 4, nslots, flags, stream()),
+                          "pgcn_aggsoftmax_backward_csr_plan_f32")
+            AT.launch_cache[key] = fn
+        fn(X, G, OUT, LSE, D)
+        return D
+
     # -- DropEdge (pgcn_dropedge.hip) -----------------------------------------
     def _drop_structure(self, A: DeviceMaxCSR, row_gid: torch.Tensor, what: str):
         """What the drop kernels need of a ``prepare_max(csr, col_gid)`` structure: the pairs, and the row of every slot of a cut row
