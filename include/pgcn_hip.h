@@ -294,6 +294,46 @@ int pgcn_spmm_fixup_f32(const int32_t *fix, int64_t nfix, const int32_t *slot_id
                         const int32_t *row_map, const float *partial_ws, float *C, int64_t ldc,
                         int32_t f, uint32_t flags, pgcn_stream_t stream);
 
+/* ---- reuse of the aggregation of an unchanged operand (no counterpart in the reference) ----
+ * pgcn_rows_sync_f32: one pass over H[nrows x f] and a kept copy ref[nrows x f] (leading dimensions ldh, ldr >= f; ref must not be H).
+ * The elements are compared as 32-BIT PATTERNS: -0.0 differs from +0.0, a NaN equals itself only with the same payload.  Where they
+ * differ -- everywhere if force != 0 -- ref = H.  changed[0] (device, int32, never NULL) = 1 if anything differed or force was set,
+ * else 0; the word is set by the call itself, in stream order (a one-thread kernel ahead of the compare), not by a memset.  Any f >= 1,
+ * any leading dimension, 64-bit row offsets; 16-byte loads where both bases are 16-byte aligned and the operands are contiguous or f,
+ * ldh and ldr are multiples of 4, single words otherwise.  nrows = 0 sets the word and may pass NULL for H and ref.  No allocation, no
+ * synchronisation, plain vector stores: graph-capturable.  Reads 2 * nrows * f * 4 bytes; writes nothing while the operand stays.  */
+int pgcn_rows_sync_f32(const float *H, int64_t ldh, float *ref, int64_t ldr, int64_t nrows, int32_t f, int32_t force,
+                       int32_t *changed, pgcn_stream_t stream);
+
+/* The kernels of the sum path's launch group with a predicate: the argument list of the entry point without _if, plus
+ * `const int32_t *run_if` before the stream.  run_if == NULL: exactly that entry point (which forwards here).  Otherwise run_if points
+ * to ONE device word that an earlier launch on the stream has written (pgcn_rows_sync_f32's changed): every workgroup of every launch
+ * reads it first, through a wave-uniform scalar load, before any other memory access, and returns when it is 0 -- then neither C, the
+ * partial-sum work-space nor the panel image is touched.  With the word != 0 the kernels run as without it: the same grids, tiles,
+ * orders and bits.  The checks of the plain entry points apply (their messages carry the plain names).  A caller predicates EVERY
+ * launch of a group on the same word, the fix-up included, and keeps C and the operand's copy between calls.
+ * The value-free entry points (pgcn_spmm_csr_scaled_f32, ..._plan_scaled_f32, pgcn_spmm_strip_vf_f32,
+ * pgcn_spmm_dense_pat_bf16x3_f32) have no predicated form.                                                                      */
+int pgcn_spmm_csr_if_f32(const int64_t *rowptr, const int32_t *col, const float *val, int64_t nrows, const float *B, int64_t ldb,
+                         float *C, int64_t ldc, int32_t f, uint32_t flags, const int32_t *run_if, pgcn_stream_t stream);
+int pgcn_spmm_csr_plan_if_f32(const int64_t *rowptr, const int32_t *col, const float *val, const int32_t *tasks, int64_t ntasks,
+                              const int64_t *seg, int32_t nslices, const int32_t *fix, int64_t nfix, const int32_t *row_map,
+                              const float *B, int64_t ldb, float *C, int64_t ldc, int32_t f, float *partial_ws,
+                              int64_t partial_ws_elems, int64_t nslots, uint32_t flags, const int32_t *run_if, pgcn_stream_t stream);
+int pgcn_spmm_core_if_f32(const int32_t *work, int64_t nwork, const int32_t *tile_panel, const int64_t *tile_base,
+                          const int32_t *seg_off, const int32_t *ccol, const float *cval, const float *B, int64_t ldb, int64_t ncols,
+                          int32_t f, float *partial_ws, int64_t partial_ws_elems, int64_t nslots_total, const int32_t *run_if,
+                          pgcn_stream_t stream);
+int pgcn_spmm_strip_if_f32(const int32_t *work, int64_t nwork, const int32_t *recs, const int32_t *pairs, const float *B, int64_t ldb,
+                           int64_t ncols, int32_t f, float *partial_ws, int64_t partial_ws_elems, int64_t nslots_total,
+                           const int32_t *run_if, pgcn_stream_t stream);
+int pgcn_spmm_dense_bf16x3_if_f32(const int32_t *work, int64_t nwork, const int32_t *blk_img, const float *vals3,
+                                  const int32_t *panel_list, int64_t npanels, const float *B, int64_t ldb, int64_t ncols, int32_t f,
+                                  void *image_ws, int64_t image_ws_bytes, float *partial_ws, int64_t partial_ws_elems,
+                                  int64_t nslots_total, const int32_t *run_if, pgcn_stream_t stream);
+int pgcn_spmm_fixup_if_f32(const int32_t *fix, int64_t nfix, const int32_t *slot_ids, const int32_t *row_map, const float *partial_ws,
+                           float *C, int64_t ldc, int32_t f, uint32_t flags, const int32_t *run_if, pgcn_stream_t stream);
+
 /* ---- element-wise MAX over the neighbourhood (GraphSAGE-pool / PNA style aggregation; no counterpart in the reference) ----
  * OUT[i, c] = max over the stored columns j of row i of B[j, c] (stored values are ignored), ARG[i, c] = the SMALLEST GLOBAL id of a
  * column that attains it (fp32 ==, so -0.0 ties with +0.0; OUT takes that column's bits); a row without entries: OUT = 0.0f, ARG = -1.

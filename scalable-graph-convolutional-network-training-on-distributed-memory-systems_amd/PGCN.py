@@ -181,7 +181,11 @@ class PSpMM(torch.autograd.Function):
     @staticmethod
     def forward(ctx, A, H):
         ctx.A = A
-        return A.forward(H)          # message counters live in A.stats; run() publishes them
+        # A graph leaf (no grad_fn, whatever its requires_grad; the input still carries its autograd identity here) is an operand that
+        # nothing in the graph produces anew every step -- typically the input features, the same matrix every epoch: the engine may
+        # keep its aggregation while its bits stay (AggregationEngine.forward_reusing; the same bits as forward)
+        reusing = getattr(A, "forward_reusing", None) if H.grad_fn is None else None
+        return reusing(H) if reusing is not None else A.forward(H)   # message counters live in A.stats; run() publishes them
 
     @staticmethod
     def backward(ctx, grad_output):

@@ -48,6 +48,17 @@ SIGNATURES = {
     "pgcn_spmm_csr_f32": (ctypes.c_int, [_vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _i32, _u32, _vp]),
     "pgcn_spmm_csr_plan_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _vp, _i32, _vp, _i64, _vp, _vp,
                                               _i64, _vp, _i64, _i32, _vp, _i64, _i64, _u32, _vp]),
+    # the *_if entry points: the plain argument list with `const int32_t *run_if` before the stream (NULL: the plain call)
+    "pgcn_spmm_csr_if_f32": (ctypes.c_int, [_vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _i32, _u32, _vp, _vp]),
+    "pgcn_spmm_csr_plan_if_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _vp, _i32, _vp, _i64, _vp, _vp,
+                                                 _i64, _vp, _i64, _i32, _vp, _i64, _i64, _u32, _vp, _vp]),
+    "pgcn_spmm_core_if_f32": (ctypes.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _vp,
+                                             _i64, _i64, _vp, _vp]),
+    "pgcn_spmm_strip_if_f32": (ctypes.c_int, [_vp, _i64, _vp, _vp, _vp, _i64, _i64, _i32, _vp, _i64, _i64, _vp, _vp]),
+    "pgcn_spmm_dense_bf16x3_if_f32": (ctypes.c_int, [_vp, _i64, _vp, _vp, _vp, _i64, _vp, _i64, _i64, _i32, _vp, _i64, _vp, _i64, _i64,
+                                                     _vp, _vp]),
+    "pgcn_spmm_fixup_if_f32": (ctypes.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _i64, _i32, _u32, _vp, _vp]),
+    "pgcn_rows_sync_f32": (ctypes.c_int, [_vp, _i64, _vp, _i64, _i64, _i32, _i32, _vp, _vp]),
     "pgcn_spmm_csr_scaled_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _i32, _u32, _vp]),
     "pgcn_spmm_csr_plan_scaled_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i32, _vp, _i64, _vp, _vp,
                                                      _i64, _vp, _i64, _i32, _vp, _i64, _i64, _u32, _vp]),

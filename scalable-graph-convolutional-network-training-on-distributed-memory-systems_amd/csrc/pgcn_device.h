@@ -24,4 +24,11 @@ __device__ __forceinline__ void vstore(float *p, const float (&x)[VEC]) {
     if constexpr (VEC == 2) { *reinterpret_cast<V *>(p) = make_float2(x[0], x[1]); }
     if constexpr (VEC == 4) { *reinterpret_cast<V *>(p) = make_float4(x[0], x[1], x[2], x[3]); }
 }
+
+// The predicate of the *_if entry points (include/pgcn_hip.h): run_if == NULL -- always run; otherwise one device word that an
+// earlier launch on the stream left (pgcn_rows_sync_f32), 0 = the whole launch group is skipped.  The pointer is a kernel argument,
+// so the word comes through one wave-uniform scalar load; a kernel calls this before any other memory access and returns on true.
+__device__ __forceinline__ bool pgcn_group_off(const int32_t *__restrict__ run_if) {
+    return run_if != nullptr && __builtin_amdgcn_readfirstlane(*run_if) == 0;
+}
 #endif

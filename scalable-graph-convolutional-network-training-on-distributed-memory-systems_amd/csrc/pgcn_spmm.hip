@@ -55,7 +55,8 @@ __global__ __launch_bounds__(kThreads, 6) void spmm_tasks_kernel(
     const float *__restrict__ val, const int4 *__restrict__ tasks, int64_t ntasks,
     const int32_t *__restrict__ row_map, const float *__restrict__ B, int64_t ldb,
     float *__restrict__ C, int64_t ldc, int32_t f, float *__restrict__ partial,
-    int64_t nblocks, uint32_t flags, int32_t nslices, SliceSeg seg, Scales sc) {
+    int64_t nblocks, uint32_t flags, int32_t nslices, SliceSeg seg, Scales sc, const int32_t *__restrict__ run_if) {
+    if (pgcn_group_off(run_if)) return;
     constexpr int G = 64 / LPR;
     const int lane = threadIdx.x & 63;
     const int wave = threadIdx.x >> 6;
@@ -107,7 +108,8 @@ template <int LPR, int VEC>
 __global__ __launch_bounds__(kThreads) void spmm_fixup_kernel(
     const int4 *__restrict__ fix, int64_t nfix, const int32_t *__restrict__ row_map,
     const float *__restrict__ partial, float *__restrict__ C, int64_t ldc, int32_t f,
-    uint32_t flags) {
+    uint32_t flags, const int32_t *__restrict__ run_if) {
+    if (pgcn_group_off(run_if)) return;
     constexpr int G = 64 / LPR;
     const int lane = threadIdx.x & 63;
     const int wave = threadIdx.x >> 6;
@@ -160,10 +162,10 @@ template <int LPR, int VEC, bool HAS_VAL, bool OFF32, bool SCALED>
 int launch_tasks(const int64_t *rowptr, const int32_t *col, const float *val, const int4 *tasks,
                  int64_t ntasks, const int32_t *row_map, const float *B, int64_t ldb, float *C,
                  int64_t ldc, int32_t f, float *partial, int64_t grid, int ntiles, uint32_t flags,
-                 int nslices, const SliceSeg &seg, const Scales &sc, hipStream_t s) {
+                 int nslices, const SliceSeg &seg, const Scales &sc, const int32_t *run_if, hipStream_t s) {
     hipLaunchKernelGGL((spmm_tasks_kernel<LPR, VEC, HAS_VAL, OFF32, SCALED>), dim3((unsigned)grid, ntiles),
                        dim3(kThreads), 0, s, rowptr, col, val, tasks, ntasks, row_map, B, ldb, C, ldc,
-                       f, partial, grid, flags, nslices, seg, sc);
+                       f, partial, grid, flags, nslices, seg, sc, run_if);
     PGCN_HIP_CHECK(hipGetLastError());
     return PGCN_OK;
 }
@@ -173,7 +175,7 @@ int launch(const int64_t *rowptr, const int32_t *col, const float *val, const in
            int64_t ntasks, const int64_t *seg_host, int nslices, const int32_t *fix, int64_t nfix,
            const int32_t *row_map,
            const float *B, int64_t ldb, float *C, int64_t ldc, int32_t f, float *partial,
-           uint32_t flags, const Scales &sc, hipStream_t s) {
+           uint32_t flags, const Scales &sc, const int32_t *run_if, hipStream_t s) {
     constexpr int G = 64 / LPR;
     const int ntiles = (f + LPR * VEC - 1) / (LPR * VEC);
     if (ntasks > 0) {
@@ -197,7 +199,7 @@ int launch(const int64_t *rowptr, const int32_t *col, const float *val, const in
         int rc;
 #define PGCN_LT(HV, O32, SC)                                                                        \
     rc = launch_tasks<LPR, VEC, HV, O32, SC>(rowptr, col, val, t4, ntasks, row_map, B, ldb, C, ldc, f, \
-                                             partial, grid, ntiles, flags, nslices, seg, sc, s)
+                                             partial, grid, ntiles, flags, nslices, seg, sc, run_if, s)
         if (val)         { if (off32) PGCN_LT(true, true, false); else PGCN_LT(true, false, false); }
         else if (sc.col) { if (off32) PGCN_LT(false, true, true); else PGCN_LT(false, false, true); }
         else             { if (off32) PGCN_LT(false, true, false); else PGCN_LT(false, false, false); }
@@ -209,7 +211,7 @@ int launch(const int64_t *rowptr, const int32_t *col, const float *val, const in
         const int64_t grid = (nfix + per_block - 1) / per_block;
         hipLaunchKernelGGL((spmm_fixup_kernel<LPR, VEC>), dim3((unsigned)grid, ntiles), dim3(kThreads),
                            0, s, reinterpret_cast<const int4 *>(fix), nfix, row_map, partial, C, ldc,
-                           f, flags);
+                           f, flags, run_if);
         PGCN_HIP_CHECK(hipGetLastError());
     }
     return PGCN_OK;
@@ -219,7 +221,8 @@ int dispatch(const int64_t *rowptr, const int32_t *col, const float *val, const 
              int64_t ntasks, const int64_t *seg, int nslices, const int32_t *fix, int64_t nfix,
              const int32_t *row_map,
              const float *B, int64_t ldb, float *C, int64_t ldc, int32_t f, float *partial,
-             uint32_t flags, hipStream_t s, const Scales &sc = Scales{nullptr, nullptr, nullptr}) {
+             uint32_t flags, hipStream_t s, const int32_t *run_if = nullptr,
+             const Scales &sc = Scales{nullptr, nullptr, nullptr}) {
     Shape sh = pick_shape(f, B, ldb, C, ldc, partial);
     // feature passes: fewer lanes per task -> the grid's y dimension walks the features 64 at a time (pass-major
     // dispatch order), so the rows of B one pass touches are 256 B each and a pass's working set is half the panel
@@ -228,7 +231,7 @@ int dispatch(const int64_t *rowptr, const int32_t *col, const float *val, const 
 #define PGCN_CASE(L, V)                                                                       \
     if (sh.lpr == L && sh.vec == V)                                                           \
         return launch<L, V>(rowptr, col, val, tasks, ntasks, seg, nslices, fix, nfix, row_map, \
-                            B, ldb, C, ldc, f, partial, flags, sc, s);
+                            B, ldb, C, ldc, f, partial, flags, sc, run_if, s);
     PGCN_CASE(1, 4) PGCN_CASE(2, 4) PGCN_CASE(4, 4) PGCN_CASE(8, 4) PGCN_CASE(16, 4)
     PGCN_CASE(32, 4) PGCN_CASE(64, 4)
     PGCN_CASE(1, 1) PGCN_CASE(2, 1) PGCN_CASE(4, 1) PGCN_CASE(8, 1) PGCN_CASE(16, 1)
@@ -239,9 +242,12 @@ int dispatch(const int64_t *rowptr, const int32_t *col, const float *val, const 
 
 }  // namespace
 
-extern "C" int pgcn_spmm_csr_f32(const int64_t *rowptr, const int32_t *col, const float *val,
-                                 int64_t nrows, const float *B, int64_t ldb, float *C,
-                                 int64_t ldc, int32_t f, uint32_t flags, pgcn_stream_t stream) {
+// The *_if entry points: run_if == NULL is the plain call; otherwise every workgroup of every launch returns at once when the
+// device word is 0 (pgcn_device.h: pgcn_group_off).  Checks, grids and kernels are the same either way.
+extern "C" int pgcn_spmm_csr_if_f32(const int64_t *rowptr, const int32_t *col, const float *val,
+                                    int64_t nrows, const float *B, int64_t ldb, float *C,
+                                    int64_t ldc, int32_t f, uint32_t flags, const int32_t *run_if,
+                                    pgcn_stream_t stream) {
     if (nrows < 0 || f <= 0 || ldb < f || ldc < f)
         return pgcn_set_error(PGCN_EINVAL, "pgcn_spmm_csr_f32: bad sizes");
     if (nrows == 0) return PGCN_OK;
@@ -249,16 +255,22 @@ extern "C" int pgcn_spmm_csr_f32(const int64_t *rowptr, const int32_t *col, cons
         return pgcn_set_error(PGCN_EINVAL, "pgcn_spmm_csr_f32: null pointer");
     if (nrows > 0x7fffffffLL) return pgcn_set_error(PGCN_EINVAL, "pgcn_spmm_csr_f32: nrows >= 2^31");
     return dispatch(rowptr, col, val, nullptr, nrows, nullptr, 1, nullptr, 0, nullptr, B, ldb, C,
-                    ldc, f, nullptr, flags, (hipStream_t)stream);
+                    ldc, f, nullptr, flags, (hipStream_t)stream, run_if);
 }
 
-extern "C" int pgcn_spmm_csr_plan_f32(const int64_t *rowptr, const int32_t *col, const float *val,
-                                      const int32_t *tasks, int64_t ntasks, const int64_t *seg,
-                                      int32_t nslices, const int32_t *fix, int64_t nfix,
-                                      const int32_t *row_map, const float *B, int64_t ldb,
-                                      float *C, int64_t ldc, int32_t f, float *partial_ws,
-                                      int64_t partial_ws_elems, int64_t nslots, uint32_t flags,
-                                      pgcn_stream_t stream) {
+extern "C" int pgcn_spmm_csr_f32(const int64_t *rowptr, const int32_t *col, const float *val,
+                                 int64_t nrows, const float *B, int64_t ldb, float *C,
+                                 int64_t ldc, int32_t f, uint32_t flags, pgcn_stream_t stream) {
+    return pgcn_spmm_csr_if_f32(rowptr, col, val, nrows, B, ldb, C, ldc, f, flags, nullptr, stream);
+}
+
+extern "C" int pgcn_spmm_csr_plan_if_f32(const int64_t *rowptr, const int32_t *col, const float *val,
+                                         const int32_t *tasks, int64_t ntasks, const int64_t *seg,
+                                         int32_t nslices, const int32_t *fix, int64_t nfix,
+                                         const int32_t *row_map, const float *B, int64_t ldb,
+                                         float *C, int64_t ldc, int32_t f, float *partial_ws,
+                                         int64_t partial_ws_elems, int64_t nslots, uint32_t flags,
+                                         const int32_t *run_if, pgcn_stream_t stream) {
     if (ntasks < 0 || nfix < 0 || f <= 0 || ldb < f || ldc < f || nslices < 1 ||
         nslices > PGCN_MAX_SLICES || (nslices > 1 && !seg))
         return pgcn_set_error(PGCN_EINVAL, "pgcn_spmm_csr_plan_f32: bad sizes");
@@ -271,7 +283,18 @@ extern "C" int pgcn_spmm_csr_plan_f32(const int64_t *rowptr, const int32_t *col,
     if (nslots < 0 || (nslots > 0 && partial_ws_elems < nslots * (int64_t)f))
         return pgcn_set_error(PGCN_ENOMEM, "pgcn_spmm_csr_plan_f32: partial work-space too small");
     return dispatch(rowptr, col, val, tasks, ntasks, seg, nslices, fix, nfix, row_map, B, ldb, C,
-                    ldc, f, partial_ws, flags, (hipStream_t)stream);
+                    ldc, f, partial_ws, flags, (hipStream_t)stream, run_if);
+}
+
+extern "C" int pgcn_spmm_csr_plan_f32(const int64_t *rowptr, const int32_t *col, const float *val,
+                                      const int32_t *tasks, int64_t ntasks, const int64_t *seg,
+                                      int32_t nslices, const int32_t *fix, int64_t nfix,
+                                      const int32_t *row_map, const float *B, int64_t ldb,
+                                      float *C, int64_t ldc, int32_t f, float *partial_ws,
+                                      int64_t partial_ws_elems, int64_t nslots, uint32_t flags,
+                                      pgcn_stream_t stream) {
+    return pgcn_spmm_csr_plan_if_f32(rowptr, col, val, tasks, ntasks, seg, nslices, fix, nfix, row_map, B, ldb, C, ldc, f,
+                                     partial_ws, partial_ws_elems, nslots, flags, nullptr, stream);
 }
 
 // Value-free structures (partition.csr_from_coo, value-free): C (+)= diag(r) P diag(c) . B.  The weight of an entry is
@@ -287,7 +310,7 @@ extern "C" int pgcn_spmm_csr_scaled_f32(const int64_t *rowptr, const int32_t *co
         return pgcn_set_error(PGCN_EINVAL, "pgcn_spmm_csr_scaled_f32: null pointer");
     if (nrows > 0x7fffffffLL) return pgcn_set_error(PGCN_EINVAL, "pgcn_spmm_csr_scaled_f32: nrows >= 2^31");
     return dispatch(rowptr, col, nullptr, nullptr, nrows, nullptr, 1, nullptr, 0, nullptr, B, ldb, C,
-                    ldc, f, nullptr, flags, (hipStream_t)stream, Scales{col_scale, row_scale, nullptr});
+                    ldc, f, nullptr, flags, (hipStream_t)stream, nullptr, Scales{col_scale, row_scale, nullptr});
 }
 
 extern "C" int pgcn_spmm_csr_plan_scaled_f32(const int64_t *rowptr, const int32_t *col, const float *row_scale,
@@ -311,5 +334,5 @@ extern "C" int pgcn_spmm_csr_plan_scaled_f32(const int64_t *rowptr, const int32_
     if (nslots < 0 || (nslots > 0 && partial_ws_elems < nslots * (int64_t)f))
         return pgcn_set_error(PGCN_ENOMEM, "pgcn_spmm_csr_plan_scaled_f32: partial work-space too small");
     return dispatch(rowptr, col, nullptr, tasks, ntasks, seg, nslices, fix, nfix, row_map, B, ldb, C,
-                    ldc, f, partial_ws, flags, (hipStream_t)stream, Scales{col_scale, row_scale, slot_row});
+                    ldc, f, partial_ws, flags, (hipStream_t)stream, nullptr, Scales{col_scale, row_scale, slot_row});
 }

@@ -38,8 +38,9 @@ __global__ __launch_bounds__(kCoreThreads, 4) void spmm_core_kernel(
     const int4 *__restrict__ work, const int32_t *__restrict__ tile_panel,
     const int64_t *__restrict__ tile_base, const int32_t *__restrict__ seg_off,
     const int32_t *__restrict__ ccol, const float *__restrict__ cval, const float *__restrict__ B,
-    int64_t ldb, int64_t ncols, int32_t f, float *__restrict__ partial) {
+    int64_t ldb, int64_t ncols, int32_t f, float *__restrict__ partial, const int32_t *__restrict__ run_if) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
+    if (pgcn_group_off(run_if)) return;
     pgcn_bodies::core_piece_body<VEC>(work[blockIdx.x], tile_panel, tile_base, seg_off, ccol, cval, B, ldb, ncols, f,
                                       partial, smem, blockIdx.y * 32 * VEC);
 }
@@ -50,7 +51,8 @@ template <int LPR, int VEC>
 __global__ __launch_bounds__(256) void spmm_fixup_list_kernel(
     const int4 *__restrict__ fix, int64_t nfix, const int32_t *__restrict__ slot_ids,
     const int32_t *__restrict__ row_map, const float *__restrict__ partial, float *__restrict__ C,
-    int64_t ldc, int32_t f, uint32_t flags) {
+    int64_t ldc, int32_t f, uint32_t flags, const int32_t *__restrict__ run_if) {
+    if (pgcn_group_off(run_if)) return;
     constexpr int G = 64 / LPR;
     const int lane = threadIdx.x & 63;
     const int wave = threadIdx.x >> 6;
@@ -99,25 +101,26 @@ bool aligned16(const void *a, const void *b, int64_t lda, int64_t ldb_, int32_t 
 
 template <int LPR, int VEC>
 int launch_fixup(const int32_t *fix, int64_t nfix, const int32_t *slot_ids, const int32_t *row_map,
-                 const float *partial, float *C, int64_t ldc, int32_t f, uint32_t flags, hipStream_t s) {
+                 const float *partial, float *C, int64_t ldc, int32_t f, uint32_t flags, const int32_t *run_if, hipStream_t s) {
     constexpr int G = 64 / LPR;
     const int ntiles = (f + LPR * VEC - 1) / (LPR * VEC);
     const int64_t per_block = 4 * G;
     const int64_t grid = (nfix + per_block - 1) / per_block;
     hipLaunchKernelGGL((spmm_fixup_list_kernel<LPR, VEC>), dim3((unsigned)grid, ntiles), dim3(256), 0, s,
-                       reinterpret_cast<const int4 *>(fix), nfix, slot_ids, row_map, partial, C, ldc, f, flags);
+                       reinterpret_cast<const int4 *>(fix), nfix, slot_ids, row_map, partial, C, ldc, f, flags, run_if);
     PGCN_HIP_CHECK(hipGetLastError());
     return PGCN_OK;
 }
 
 }  // namespace
 
-extern "C" int pgcn_spmm_core_f32(const int32_t *work, int64_t nwork, const int32_t *tile_panel,
-                                  const int64_t *tile_base, const int32_t *seg_off,
-                                  const int32_t *ccol, const float *cval, const float *B,
-                                  int64_t ldb, int64_t ncols, int32_t f, float *partial_ws,
-                                  int64_t partial_ws_elems, int64_t nslots_total,
-                                  pgcn_stream_t stream) {
+// The *_if entry points: run_if == NULL is the plain call; otherwise every workgroup returns at once when the device word is 0.
+extern "C" int pgcn_spmm_core_if_f32(const int32_t *work, int64_t nwork, const int32_t *tile_panel,
+                                     const int64_t *tile_base, const int32_t *seg_off,
+                                     const int32_t *ccol, const float *cval, const float *B,
+                                     int64_t ldb, int64_t ncols, int32_t f, float *partial_ws,
+                                     int64_t partial_ws_elems, int64_t nslots_total, const int32_t *run_if,
+                                     pgcn_stream_t stream) {
     if (nwork < 0 || f <= 0 || ldb < f || ncols < 0)
         return pgcn_set_error(PGCN_EINVAL, "pgcn_spmm_core_f32: bad sizes");
     if (nwork == 0) return PGCN_OK;
@@ -140,21 +143,32 @@ extern "C" int pgcn_spmm_core_f32(const int32_t *work, int64_t nwork, const int3
         const int ntiles = (f + 127) / 128;
         hipLaunchKernelGGL((spmm_core_kernel<4>), dim3((unsigned)nwork, ntiles), dim3(kCoreThreads), smem, s,
                            reinterpret_cast<const int4 *>(work), tile_panel, tile_base, seg_off, ccol, cval,
-                           B, ldb, ncols, f, partial_ws);
+                           B, ldb, ncols, f, partial_ws, run_if);
     } else {
         const size_t smem = (size_t)(TC + 1) * 32 * 4 + (kCoreThreads / 64) * 512;
         const int ntiles = (f + 31) / 32;
         hipLaunchKernelGGL((spmm_core_kernel<1>), dim3((unsigned)nwork, ntiles), dim3(kCoreThreads), smem, s,
                            reinterpret_cast<const int4 *>(work), tile_panel, tile_base, seg_off, ccol, cval,
-                           B, ldb, ncols, f, partial_ws);
+                           B, ldb, ncols, f, partial_ws, run_if);
     }
     PGCN_HIP_CHECK(hipGetLastError());
     return PGCN_OK;
 }
 
-extern "C" int pgcn_spmm_fixup_f32(const int32_t *fix, int64_t nfix, const int32_t *slot_ids,
-                                   const int32_t *row_map, const float *partial_ws, float *C,
-                                   int64_t ldc, int32_t f, uint32_t flags, pgcn_stream_t stream) {
+extern "C" int pgcn_spmm_core_f32(const int32_t *work, int64_t nwork, const int32_t *tile_panel,
+                                  const int64_t *tile_base, const int32_t *seg_off,
+                                  const int32_t *ccol, const float *cval, const float *B,
+                                  int64_t ldb, int64_t ncols, int32_t f, float *partial_ws,
+                                  int64_t partial_ws_elems, int64_t nslots_total,
+                                  pgcn_stream_t stream) {
+    return pgcn_spmm_core_if_f32(work, nwork, tile_panel, tile_base, seg_off, ccol, cval, B, ldb, ncols, f, partial_ws,
+                                 partial_ws_elems, nslots_total, nullptr, stream);
+}
+
+extern "C" int pgcn_spmm_fixup_if_f32(const int32_t *fix, int64_t nfix, const int32_t *slot_ids,
+                                      const int32_t *row_map, const float *partial_ws, float *C,
+                                      int64_t ldc, int32_t f, uint32_t flags, const int32_t *run_if,
+                                      pgcn_stream_t stream) {
     if (nfix < 0 || f <= 0 || ldc < f) return pgcn_set_error(PGCN_EINVAL, "pgcn_spmm_fixup_f32: bad sizes");
     if (nfix == 0) return PGCN_OK;
     if (!fix || !partial_ws || !C) return pgcn_set_error(PGCN_EINVAL, "pgcn_spmm_fixup_f32: null pointer");
@@ -165,9 +179,15 @@ extern "C" int pgcn_spmm_fixup_f32(const int32_t *fix, int64_t nfix, const int32
     int lpr = 1;
     while (lpr < nv && lpr < 64) lpr *= 2;
 #define PGCN_FX(L, V) \
-    if (lpr == L && vec == V) return launch_fixup<L, V>(fix, nfix, slot_ids, row_map, partial_ws, C, ldc, f, flags, s);
+    if (lpr == L && vec == V) return launch_fixup<L, V>(fix, nfix, slot_ids, row_map, partial_ws, C, ldc, f, flags, run_if, s);
     PGCN_FX(1, 4) PGCN_FX(2, 4) PGCN_FX(4, 4) PGCN_FX(8, 4) PGCN_FX(16, 4) PGCN_FX(32, 4) PGCN_FX(64, 4)
     PGCN_FX(1, 1) PGCN_FX(2, 1) PGCN_FX(4, 1) PGCN_FX(8, 1) PGCN_FX(16, 1) PGCN_FX(32, 1) PGCN_FX(64, 1)
 #undef PGCN_FX
     return pgcn_set_error(PGCN_EINVAL, "pgcn_spmm_fixup_f32: no kernel shape");
+}
+
+extern "C" int pgcn_spmm_fixup_f32(const int32_t *fix, int64_t nfix, const int32_t *slot_ids,
+                                   const int32_t *row_map, const float *partial_ws, float *C,
+                                   int64_t ldc, int32_t f, uint32_t flags, pgcn_stream_t stream) {
+    return pgcn_spmm_fixup_if_f32(fix, nfix, slot_ids, row_map, partial_ws, C, ldc, f, flags, nullptr, stream);
 }

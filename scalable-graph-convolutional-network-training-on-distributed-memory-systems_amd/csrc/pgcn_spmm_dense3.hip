@@ -51,6 +51,7 @@
 #include <type_traits>
 
 #include "pgcn_bf16x3.h"
+#include "pgcn_device.h"
 #include "pgcn_internal.h"
 #include "pgcn_once.h"
 
@@ -295,8 +296,9 @@ template <int NBLK>
 __global__ __launch_bounds__(kThreads, 2) void spmm_dense3_kernel(
     const int4 *__restrict__ work, const int32_t *__restrict__ blk_img, const int32_t *__restrict__ panel_list,
     const float *__restrict__ vals3, const char *__restrict__ image, const float *__restrict__ B, int64_t ldb, int64_t ncols,
-    int32_t f, float *__restrict__ partial) {
+    int32_t f, float *__restrict__ partial, const int32_t *__restrict__ run_if) {
     extern __shared__ __attribute__((aligned(16))) char smem3[];
+    if (pgcn_group_off(run_if)) return;
     int4 wk = work[blockIdx.x];
     wk.y = __builtin_amdgcn_readfirstlane(wk.y); wk.z = __builtin_amdgcn_readfirstlane(wk.z);
     const int fb = blockIdx.y, nfb = gridDim.y;
@@ -553,11 +555,23 @@ extern "C" int64_t pgcn_dense_bf16x3_image_bytes(int64_t npanels, int32_t f) {
     return npanels * (int64_t)((f + kT - 1) / kT) * kImgBytes;
 }
 
-extern "C" int pgcn_spmm_dense_bf16x3_f32(const int32_t *work, int64_t nwork, const int32_t *blk_img, const float *vals3,
-                                          const int32_t *panel_list, int64_t npanels, const float *B, int64_t ldb,
-                                          int64_t ncols, int32_t f, void *image_ws, int64_t image_ws_bytes,
-                                          float *partial_ws, int64_t partial_ws_elems, int64_t nslots_total,
-                                          pgcn_stream_t stream) {
+namespace {
+// The panel split of a predicated product (the plain kernel is shared with pgcn_gat_blocks.hip and stays as it is).
+__global__ __launch_bounds__(kSplitThreads) void spmm_split_panels_if_kernel(const int32_t *__restrict__ panel_list, const float *__restrict__ B,
+                                                                             int64_t ldb, int64_t ncols, int32_t f, u32x4 *__restrict__ image,
+                                                                             const int32_t *__restrict__ run_if) {
+    if (pgcn_group_off(run_if)) return;
+    split_panels_body<false>(panel_list, B, ldb, ncols, f, nullptr, image);
+}
+}  // namespace
+
+// pgcn_spmm_dense_bf16x3_f32 is this with run_if == NULL; otherwise every workgroup of the split and of the block kernel returns at
+// once when the device word is 0: neither the image nor a slot is written.
+extern "C" int pgcn_spmm_dense_bf16x3_if_f32(const int32_t *work, int64_t nwork, const int32_t *blk_img, const float *vals3,
+                                             const int32_t *panel_list, int64_t npanels, const float *B, int64_t ldb,
+                                             int64_t ncols, int32_t f, void *image_ws, int64_t image_ws_bytes,
+                                             float *partial_ws, int64_t partial_ws_elems, int64_t nslots_total,
+                                             const int32_t *run_if, pgcn_stream_t stream) {
     if (nwork < 0 || npanels < 0 || f <= 0 || ldb < f || ncols < 0)
         return pgcn_set_error(PGCN_EINVAL, "pgcn_spmm_dense_bf16x3_f32: bad sizes");
     if (nwork == 0) return PGCN_OK;
@@ -582,20 +596,33 @@ extern "C" int pgcn_spmm_dense_bf16x3_f32(const int32_t *work, int64_t nwork, co
         return rc;
     hipStream_t s = (hipStream_t)stream;
     const unsigned nfb = (unsigned)((f + kT - 1) / kT);
-    hipLaunchKernelGGL(spmm_split_panels_kernel, dim3((unsigned)npanels, nfb), dim3(kSplitThreads), 0, s, panel_list, B, ldb, ncols, f,
-                       reinterpret_cast<u32x4 *>(image_ws));
+    if (run_if)
+        hipLaunchKernelGGL(spmm_split_panels_if_kernel, dim3((unsigned)npanels, nfb), dim3(kSplitThreads), 0, s, panel_list, B, ldb, ncols, f,
+                           reinterpret_cast<u32x4 *>(image_ws), run_if);
+    else
+        hipLaunchKernelGGL(spmm_split_panels_kernel, dim3((unsigned)npanels, nfb), dim3(kSplitThreads), 0, s, panel_list, B, ldb, ncols, f,
+                           reinterpret_cast<u32x4 *>(image_ws));
     PGCN_HIP_CHECK(hipGetLastError());
     const int4 *w4 = reinterpret_cast<const int4 *>(work);
     const char *img = reinterpret_cast<const char *>(image_ws);
     const dim3 grid((unsigned)nwork, nfb), block(kThreads);
     switch (((f < kT ? f : kT) + 31) / 32) {
-        case 1: hipLaunchKernelGGL(spmm_dense3_kernel<1>, grid, block, kSmem3, s, w4, blk_img, panel_list, vals3, img, B, ldb, ncols, f, partial_ws); break;
-        case 2: hipLaunchKernelGGL(spmm_dense3_kernel<2>, grid, block, kSmem3, s, w4, blk_img, panel_list, vals3, img, B, ldb, ncols, f, partial_ws); break;
-        case 3: hipLaunchKernelGGL(spmm_dense3_kernel<3>, grid, block, kSmem3, s, w4, blk_img, panel_list, vals3, img, B, ldb, ncols, f, partial_ws); break;
-        default: hipLaunchKernelGGL(spmm_dense3_kernel<4>, grid, block, kSmem3, s, w4, blk_img, panel_list, vals3, img, B, ldb, ncols, f, partial_ws); break;
+        case 1: hipLaunchKernelGGL(spmm_dense3_kernel<1>, grid, block, kSmem3, s, w4, blk_img, panel_list, vals3, img, B, ldb, ncols, f, partial_ws, run_if); break;
+        case 2: hipLaunchKernelGGL(spmm_dense3_kernel<2>, grid, block, kSmem3, s, w4, blk_img, panel_list, vals3, img, B, ldb, ncols, f, partial_ws, run_if); break;
+        case 3: hipLaunchKernelGGL(spmm_dense3_kernel<3>, grid, block, kSmem3, s, w4, blk_img, panel_list, vals3, img, B, ldb, ncols, f, partial_ws, run_if); break;
+        default: hipLaunchKernelGGL(spmm_dense3_kernel<4>, grid, block, kSmem3, s, w4, blk_img, panel_list, vals3, img, B, ldb, ncols, f, partial_ws, run_if); break;
     }
     PGCN_HIP_CHECK(hipGetLastError());
     return PGCN_OK;
+}
+
+extern "C" int pgcn_spmm_dense_bf16x3_f32(const int32_t *work, int64_t nwork, const int32_t *blk_img, const float *vals3,
+                                          const int32_t *panel_list, int64_t npanels, const float *B, int64_t ldb,
+                                          int64_t ncols, int32_t f, void *image_ws, int64_t image_ws_bytes,
+                                          float *partial_ws, int64_t partial_ws_elems, int64_t nslots_total,
+                                          pgcn_stream_t stream) {
+    return pgcn_spmm_dense_bf16x3_if_f32(work, nwork, blk_img, vals3, panel_list, npanels, B, ldb, ncols, f, image_ws, image_ws_bytes,
+                                         partial_ws, partial_ws_elems, nslots_total, nullptr, stream);
 }
 
 // Value-free blocks (pattern / factored): the block structure and work-space of pgcn_spmm_dense_bf16x3_f32, bits instead of vals3.

@@ -35,6 +35,7 @@
 #include <stdint.h>
 #include <stdlib.h>
 
+#include "pgcn_device.h"
 #include "pgcn_internal.h"
 #include "pgcn_once.h"
 
@@ -220,8 +221,10 @@ __device__ __forceinline__ void compute_record(const int ISSUE, f32x2 (&acc)[RW]
 template <int PROBE>
 __global__ __launch_bounds__(kThreads, 1) void spmm_strip_kernel(
     const int4 *__restrict__ work, const int4 *__restrict__ recs, const int32_t *__restrict__ pairs,
-    const float *__restrict__ B, int64_t ldb, int64_t ncols, int32_t f, float *__restrict__ partial) {
+    const float *__restrict__ B, int64_t ldb, int64_t ncols, int32_t f, float *__restrict__ partial,
+    const int32_t *__restrict__ run_if) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
+    if (pgcn_group_off(run_if)) return;    // (pgcn_spmm_strip_if_f32: ahead of every access and of the scheduled blocks below)
     int4 wk = work[blockIdx.x];
     wk.x = __builtin_amdgcn_readfirstlane(wk.x); wk.y = __builtin_amdgcn_readfirstlane(wk.y);   // wave-uniform: scalar control flow
     wk.z = __builtin_amdgcn_readfirstlane(wk.z); wk.w = __builtin_amdgcn_readfirstlane(wk.w);
@@ -579,7 +582,9 @@ __global__ __launch_bounds__(kThreads, 1) void spmm_strip_vf_generic_kernel(
 // lane (blockIdx.y walks the features 32 at a time).  Correctness path, not a fast path.
 __global__ __launch_bounds__(kThreads, 1) void spmm_strip_generic_kernel(
     const int4 *__restrict__ work, const int4 *__restrict__ recs, const int32_t *__restrict__ pairs,
-    const float *__restrict__ B, int64_t ldb, int64_t ncols, int32_t f, float *__restrict__ partial) {
+    const float *__restrict__ B, int64_t ldb, int64_t ncols, int32_t f, float *__restrict__ partial,
+    const int32_t *__restrict__ run_if) {
+    if (pgcn_group_off(run_if)) return;
     const int4 wk = work[blockIdx.x];
     const int sub = threadIdx.x & 31;
     const int g32 = threadIdx.x >> 5;      // 32 groups of 32 lanes, 16 rows each: row = i * 32 + g32
@@ -612,9 +617,11 @@ __global__ __launch_bounds__(kThreads, 1) void spmm_strip_generic_kernel(
 
 }  // namespace
 
-extern "C" int pgcn_spmm_strip_f32(const int32_t *work, int64_t nwork, const int32_t *recs, const int32_t *pairs,
-                                    const float *B, int64_t ldb, int64_t ncols, int32_t f, float *partial_ws,
-                                    int64_t partial_ws_elems, int64_t nslots_total, pgcn_stream_t stream) {
+// pgcn_spmm_strip_f32 is this with run_if == NULL; otherwise every workgroup returns at once when the device word is 0.
+extern "C" int pgcn_spmm_strip_if_f32(const int32_t *work, int64_t nwork, const int32_t *recs, const int32_t *pairs,
+                                       const float *B, int64_t ldb, int64_t ncols, int32_t f, float *partial_ws,
+                                       int64_t partial_ws_elems, int64_t nslots_total, const int32_t *run_if,
+                                       pgcn_stream_t stream) {
     if (nwork < 0 || f <= 0 || ldb < f || ncols < TC) return pgcn_set_error(PGCN_EINVAL, "pgcn_spmm_strip_f32: bad sizes (a panel is 128 rows of B)");
     if (ldb > kMaxLdb)
         return pgcn_set_error(PGCN_EINVAL, "pgcn_spmm_strip_f32: leading dimension ldb too large for the 32-bit lane offsets of the panel copies (at most 34636829 floats)");
@@ -647,18 +654,24 @@ extern "C" int pgcn_spmm_strip_f32(const int32_t *work, int64_t nwork, const int
         // measurement build only (tools/ab_build.sh exp -DPGCN_EXPERIMENTS): PGCN_STRIP_PROBE = 1 no compute phase,
         // 2 no panel staging, 4 phase timers instead of results
         static const int probe = getenv("PGCN_STRIP_PROBE") ? atoi(getenv("PGCN_STRIP_PROBE")) : 0;
-        if (probe == 1) hipLaunchKernelGGL(spmm_strip_kernel<1>, grid, dim3(kThreads), kSmem, s, w4, r4, pairs, B, ldb, ncols, f, partial_ws);
-        else if (probe == 2) hipLaunchKernelGGL(spmm_strip_kernel<2>, grid, dim3(kThreads), kSmem, s, w4, r4, pairs, B, ldb, ncols, f, partial_ws);
-        else if (probe == 4) hipLaunchKernelGGL(spmm_strip_kernel<4>, grid, dim3(kThreads), kSmem, s, w4, r4, pairs, B, ldb, ncols, f, partial_ws);
+        if (probe == 1) hipLaunchKernelGGL(spmm_strip_kernel<1>, grid, dim3(kThreads), kSmem, s, w4, r4, pairs, B, ldb, ncols, f, partial_ws, run_if);
+        else if (probe == 2) hipLaunchKernelGGL(spmm_strip_kernel<2>, grid, dim3(kThreads), kSmem, s, w4, r4, pairs, B, ldb, ncols, f, partial_ws, run_if);
+        else if (probe == 4) hipLaunchKernelGGL(spmm_strip_kernel<4>, grid, dim3(kThreads), kSmem, s, w4, r4, pairs, B, ldb, ncols, f, partial_ws, run_if);
         else
 #endif
-        hipLaunchKernelGGL(spmm_strip_kernel<0>, grid, dim3(kThreads), kSmem, s, w4, r4, pairs, B, ldb, ncols, f, partial_ws);
+        hipLaunchKernelGGL(spmm_strip_kernel<0>, grid, dim3(kThreads), kSmem, s, w4, r4, pairs, B, ldb, ncols, f, partial_ws, run_if);
     } else {
         hipLaunchKernelGGL(spmm_strip_generic_kernel, dim3((unsigned)nwork, (unsigned)((f + 31) / 32)), dim3(kThreads), 0, s,
-                           w4, r4, pairs, B, ldb, ncols, f, partial_ws);
+                           w4, r4, pairs, B, ldb, ncols, f, partial_ws, run_if);
     }
     PGCN_HIP_CHECK(hipGetLastError());
     return PGCN_OK;
+}
+
+extern "C" int pgcn_spmm_strip_f32(const int32_t *work, int64_t nwork, const int32_t *recs, const int32_t *pairs,
+                                    const float *B, int64_t ldb, int64_t ncols, int32_t f, float *partial_ws,
+                                    int64_t partial_ws_elems, int64_t nslots_total, pgcn_stream_t stream) {
+    return pgcn_spmm_strip_if_f32(work, nwork, recs, pairs, B, ldb, ncols, f, partial_ws, partial_ws_elems, nslots_total, nullptr, stream);
 }
 
 extern "C" int pgcn_spmm_strip_vf_f32(const int32_t *work, int64_t nwork, const int32_t *recs, const int32_t *offs,

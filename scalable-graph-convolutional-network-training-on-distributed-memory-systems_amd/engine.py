@@ -26,6 +26,7 @@ from __future__ import annotations
 import ctypes
 import os
 import dataclasses
+import weakref
 from typing import Dict, List, Optional
 
 import torch
@@ -33,6 +34,7 @@ import torch.distributed as dist
 
 from . import _lib
 from .partition import Partition
+from .tuning import T as _T
 
 
 # --------------------------------------------------------------------------
@@ -691,6 +693,19 @@ def ppr_step_backward_composed(G: torch.Tensor, T: torch.Tensor, D: Optional[tor
     return gout, dout
 
 
+@dataclasses.dataclass
+class ReuseRecord:
+    """What ``AggregationEngine.forward_reusing`` knows about the one operand it follows.  The identity is the host's filter (an operand
+    that is written through autograd-aware operations moves its version and never pays for the compare); whether the kept result is
+    still right is decided on the device, from the operand's bits (``changed``)."""
+    key: tuple                                  # (data pointer, shape, strides) of the candidate
+    version: int                                # its _version when last seen
+    who: "weakref.ref"                          # the tensor object itself
+    ref: Optional[torch.Tensor] = None          # the kept copy of the operand (armed records)
+    C: Optional[torch.Tensor] = None            # the kept aggregation A . ref
+    changed: Optional[torch.Tensor] = None      # int32 [1]: what the last rows_sync found; the run_if word of the launch group
+
+
 class AggregationEngine(BoundaryExchange):
     """Owns rank p's device-resident pieces and runs the aggregation forward/backward."""
 
@@ -712,6 +727,10 @@ class AggregationEngine(BoundaryExchange):
         self._wgrad_parked = []         # [(event after a weight gradient on that stream, tensors it reads)] not yet joined
         self._max: Optional[MaxStructures] = None      # the max aggregation's structures, built at the first forward_max / backward_max
         self._drop: Optional[DropEdgeStructures] = None    # DropEdge's structures, built at the first forward_drop / drop_refresh
+        self.reuse_operand = bool(_T.reuse_operand)     # forward_reusing may keep the aggregation of an unchanged operand ...
+        self.reuse_max_bytes = int(_T.reuse_max_bytes)  # ... whose copy and result fit in this
+        self._reuse: Optional[ReuseRecord] = None       # the operand forward_reusing follows: a candidate, or armed (ref and C kept)
+        self._reuse_aside: Optional[ReuseRecord] = None # a candidate seen while an armed record of another live operand is kept
 
     # ------------------------------------------------------------------
     def wgrad_lane(self, launch, reads, join_now=False):
@@ -766,6 +785,64 @@ class AggregationEngine(BoundaryExchange):
             raise ValueError("H must hold exactly the %d owned rows" % self.n_local)
         H = H.contiguous()
         return self._forward_into(H, torch.empty((self.n_local, H.shape[1]), dtype=torch.float32, device=self.device))
+
+    def _reuse_eligible(self, H: torch.Tensor) -> bool:
+        """May ``forward_reusing`` follow H?  One rank (with halo rows the decision would need every rank's word), a contiguous fp32
+        matrix of the owned rows on the device, copy + result within ``reuse_max_bytes``, and a provider with a predicated launch
+        group for this structure (``spmm_if_supported``: not the value-free kernels)."""
+        k = self.k
+        return (self.reuse_operand and self.size == 1 and H.dim() == 2 and H.shape[0] == self.n_local and H.numel() > 0
+                and H.dtype is torch.float32 and H.device.type == self.device.type and H.is_contiguous()
+                and 2 * H.numel() * 4 <= self.reuse_max_bytes
+                and hasattr(k, "spmm_if") and hasattr(k, "rows_sync") and k.spmm_if_supported(self.A_loc))
+
+    def forward_reusing(self, H: torch.Tensor) -> torch.Tensor:
+        """``forward`` for an operand that may well be the one of the last call (a graph leaf: the input features are the same matrix
+        every epoch).  The result is the same bits; the caller must not write into it, and must be done with an earlier result of the
+        same operand before it changes that operand and calls again (from the second sighting on every result aliases one kept C).
+
+        First sighting of an operand: ``forward``; the candidate is remembered.  Second sighting (the same tensor, address, layout and
+        version): a kept copy ``ref`` and a kept ``C`` are allocated, ``rows_sync(force)`` fills ref and sets the word, the predicated
+        launch group runs.  Every later sighting: ``rows_sync`` compares H with ref bit for bit on the device -- 2 n f 4 bytes read,
+        nothing written while H stays -- and the launch group returns at once unless something differed; a write that no version
+        counter sees (``H.data``, a bare pointer, a static buffer refilled between replays of a captured graph) is therefore followed.
+        A moved version or another operand: ``forward`` with a fresh C, and that operand starts over as the candidate.  One
+        exception keeps the product's own training loop reusing: an ARMED record whose operand is alive and unwritten survives the
+        sighting of other operands -- an evaluation without autograd between two epochs hands every hidden activation in as a leaf,
+        a new tensor each time -- and the newcomer is followed aside; it takes the record's place at its own second sighting.
+        No host synchronisation anywhere."""
+        if not self._reuse_eligible(H):
+            self._reuse = self._reuse_aside = None
+            return self.forward(H)
+        key = (H.data_ptr(), tuple(H.shape), tuple(H.stride()))
+
+        def is_this(r):
+            return r is not None and r.key == key and r.version == H._version and r.who() is H
+
+        rec = self._reuse
+        if not is_this(rec):
+            kept = rec.who() if rec is not None and rec.C is not None else None
+            holds = kept is not None and kept is not H and kept._version == rec.version    # armed, for another live, unwritten operand
+            if holds and is_this(self._reuse_aside):
+                rec = self._reuse = self._reuse_aside       # the newcomer's second sighting: it takes the record's place
+                self._reuse_aside = None
+            else:
+                new = ReuseRecord(key, H._version, weakref.ref(H))
+                if holds:
+                    self._reuse_aside = new                 # (the armed record stays)
+                else:
+                    self._reuse, self._reuse_aside = new, None
+                return self.forward(H)
+        arm = rec.C is None
+        if arm and self.device.type == "cuda" and torch.cuda.is_current_stream_capturing():
+            return self.forward(H)              # (a captured graph would replay the forced copy and the full group for ever: arm outside)
+        if arm:
+            rec.ref = torch.empty_like(H)
+            rec.C = torch.empty((self.n_local, H.shape[1]), dtype=torch.float32, device=self.device)
+            rec.changed = torch.empty(1, dtype=torch.int32, device=self.device)
+        self.k.rows_sync(H, rec.ref, rec.changed, force=arm)
+        self.k.spmm_if(self.A_loc, H, rec.C, rec.changed)
+        return rec.C.view(rec.C.shape)          # a new tensor object every time, never the kept one itself
 
     def _forward_into(self, H: torch.Tensor, C: torch.Tensor) -> torch.Tensor:
         """``forward`` of a contiguous H into the caller's C (n_local x f, not H itself)."""

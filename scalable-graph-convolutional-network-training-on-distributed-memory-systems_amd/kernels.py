@@ -449,8 +449,53 @@ class HipKernels:
         fn(B, C)
         return C
 
-    def _bind_spmm(self, A: DeviceCSR, B: torch.Tensor, C: torch.Tensor, accumulate: bool):
+    def spmm_if_supported(self, A: DeviceCSR) -> bool:
+        """Has every kernel of A's launch group a predicated form?  Not the value-free ones (pattern / factored structures)."""
+        return (A.values == "stored" and A.col_scale is None and (A.strip is None or A.strip.offs is None)
+                and (A.dense3 is None or A.dense3.bits is None))
+
+    def spmm_if(self, A: DeviceCSR, B: torch.Tensor, C: torch.Tensor, run_if: torch.Tensor, accumulate: bool = False) -> torch.Tensor:
+        """``spmm`` with every launch of the group predicated on the device word ``run_if`` (int32, one element; ``rows_sync`` leaves
+        it): 0 = every workgroup returns at once and C keeps what it holds.  The same lanes, fork and join, grids and kernels.  A method
+        of its own, not a route through ``spmm``: whoever wraps ``spmm`` to time real launch groups (bench.py's KernelTimer) must not
+        see a skipped one."""
+        if not (B.is_cuda and C.is_cuda and B.dtype is torch.float32 and C.dtype is torch.float32):
+            raise _lib.PgcnError("B and C must be fp32 CUDA matrices")
+        if B.shape[0] < A.ncols or (A.row_map is None and C.shape[0] < A.nrows):
+            raise _lib.PgcnError("B or C has too few rows")
+        if not (run_if.is_cuda and run_if.dtype is torch.int32 and run_if.numel() == 1):
+            raise _lib.PgcnError("run_if must be one int32 word on the device")
+        key = (B.stride(0), C.stride(0), B.shape[1], accumulate, C.shape[1], B.stride(1), C.stride(1), run_if.data_ptr())
+        fn = A.launch_cache.get(key)
+        if fn is None:
+            fn = self._bind_spmm(A, B, C, accumulate, run_if)
+            A.launch_cache[key] = fn
+        fn(B, C)
+        return C
+
+    def rows_sync(self, H: torch.Tensor, ref: torch.Tensor, changed: torch.Tensor, force: bool = False) -> torch.Tensor:
+        """pgcn_rows_sync_f32: ``changed[0]`` = 1 if H differs from ``ref`` anywhere as bit patterns (or ``force``), else 0; ref = H where
+        they differ (everywhere under ``force``).  One pass, on the current stream."""
+        for t, what in ((H, "H"), (ref, "ref")):
+            if not (t.is_cuda and t.dtype is torch.float32 and t.dim() == 2 and (t.stride(1) == 1 or t.shape[0] == 0 or t.shape[1] == 1)):
+                raise _lib.PgcnError("%s must be a row-major fp32 CUDA matrix" % what)
+        if H.shape != ref.shape:
+            raise _lib.PgcnError("H and ref differ in shape")
+        if not (changed.is_cuda and changed.dtype is torch.int32 and changed.numel() >= 1):
+            raise _lib.PgcnError("changed must be an int32 word on the device")
+        n, f = H.shape
+        _lib.check(self.lib.pgcn_rows_sync_f32(H.data_ptr() if n else None, max(H.stride(0), f) if n else f,
+                                               ref.data_ptr() if n else None, max(ref.stride(0), f) if n else f, n, f, int(bool(force)),
+                                               changed.data_ptr(), self._stream()), "pgcn_rows_sync_f32")
+        return changed
+
+    def _bind_spmm(self, A: DeviceCSR, B: torch.Tensor, C: torch.Tensor, accumulate: bool, run_if: Optional[torch.Tensor] = None):
+        """``run_if`` (spmm_if): the device word every launch of the group is predicated on -- the *_if entry points, the same
+        arguments otherwise; None: the plain ones."""
         f = B.shape[1]
+        pred = None if run_if is None else run_if.data_ptr()
+        if pred is not None and not self.spmm_if_supported(A):
+            raise _lib.PgcnError("the value-free kernels have no predicated form (HipKernels.spmm_if_supported)")
         self._check_dense(B, A.ncols, "B")
         self._check_dense(C, 0, "C")
         if C.shape[1] != f:
@@ -481,6 +526,11 @@ class HipKernels:
                     check(lib.pgcn_spmm_csr_scaled_f32(rowptr, col, rsc, csc, nrows, B.data_ptr(), ldb, C.data_ptr(), ldc, f,
                                                        flags, stream()), "pgcn_spmm_csr_scaled_f32")
                 return simple_scaled
+            if pred is not None:
+                def simple_if(B, C):
+                    check(lib.pgcn_spmm_csr_if_f32(rowptr, col, val, nrows, B.data_ptr(), ldb, C.data_ptr(), ldc, f,
+                                                   flags, pred, stream()), "pgcn_spmm_csr_if_f32")
+                return simple_if
             def simple(B, C):
                 check(lib.pgcn_spmm_csr_f32(rowptr, col, val, nrows, B.data_ptr(), ldb, C.data_ptr(), ldc, f,
                                             flags, stream()), "pgcn_spmm_csr_f32")
@@ -502,6 +552,12 @@ class HipKernels:
                                                             B.data_ptr(), ldb, C.data_ptr(), ldc, f, ws, ws_n, nslots, flags,
                                                             stream()), "pgcn_spmm_csr_plan_scaled_f32")
                 return planned_scaled
+            if pred is not None:
+                def planned_if(B, C):
+                    check(lib.pgcn_spmm_csr_plan_if_f32(rowptr, col, val, tasks, ntasks, seg, nslices, fix, nfix, rmap,
+                                                        B.data_ptr(), ldb, C.data_ptr(), ldc, f, ws, ws_n, nslots, flags,
+                                                        pred, stream()), "pgcn_spmm_csr_plan_if_f32")
+                return planned_if
             def planned(B, C):
                 check(lib.pgcn_spmm_csr_plan_f32(rowptr, col, val, tasks, ntasks, seg, nslices, fix, nfix, rmap,
                                                  B.data_ptr(), ldb, C.data_ptr(), ldc, f, ws, ws_n, nslots, flags,
@@ -566,6 +622,19 @@ class HipKernels:
                 check(lib.pgcn_spmm_dense_bf16x3_f32(w3, n3, bi3, v3, pl3, np3, b, ldb, ncols, f, img3, imgb3, ws, ws_n, nst, s),
                       "pgcn_spmm_dense_bf16x3_f32")
 
+        def launch_if(name, b, c, s):
+            if name == "gather":
+                check(lib.pgcn_spmm_csr_plan_if_f32(rowptr, col, val, tasks, ntasks, seg, nslices, None, 0, rmap, b, ldb,
+                                                    c, ldc, f, ws, ws_n, nslots, gflags, pred, s), "pgcn_spmm_csr_plan_if_f32")
+            elif name == "strip":
+                check(lib.pgcn_spmm_strip_if_f32(sw, sn, srec, spairs, b, ldb, ncols, f, ws, ws_n, nst, pred, s), "pgcn_spmm_strip_if_f32")
+            else:
+                check(lib.pgcn_spmm_dense_bf16x3_if_f32(w3, n3, bi3, v3, pl3, np3, b, ldb, ncols, f, img3, imgb3, ws, ws_n, nst, pred, s),
+                      "pgcn_spmm_dense_bf16x3_if_f32")
+
+        if pred is not None:
+            launch = launch_if
+
         def produce(B, C):
             b, c, s = B.data_ptr(), C.data_ptr(), stream()
             if nside:
@@ -577,13 +646,20 @@ class HipKernels:
                         launch(name, b, c, o)
             for name in lanes[-1]:
                 launch(name, b, c, s)
-            if co is not None:
+            if co is not None and pred is not None:
+                check(lib.pgcn_spmm_core_if_f32(cw, cn, ctp, ctb, cso, ccol, cval, b, ldb, ncols, f, ws, ws_n, nst, pred, s),
+                      "pgcn_spmm_core_if_f32")
+            elif co is not None:
                 check(lib.pgcn_spmm_core_f32(cw, cn, ctp, ctb, cso, ccol, cval, b, ldb, ncols, f, ws, ws_n, nst, s),
                       "pgcn_spmm_core_f32")
             for i in range(nside):
                 cur.wait_stream(sides[i])
 
         def fixup(C):
+            if pred is not None:
+                check(lib.pgcn_spmm_fixup_if_f32(fixp, nfa, slots, rmap, ws, C.data_ptr(), ldc, f, fflags, pred, stream()),
+                      "pgcn_spmm_fixup_if_f32")
+                return
             check(lib.pgcn_spmm_fixup_f32(fixp, nfa, slots, rmap, ws, C.data_ptr(), ldc, f, fflags, stream()), "pgcn_spmm_fixup_f32")
 
         def hybrid(B, C):

@@ -78,6 +78,12 @@ class Tuning:
                                      # part and the bf16 blocks (r04, Reddit shape: one stream 1.610 ms, this 1.545; strips + dense3 beside the
                                      # gather 1.572, three streams 1.57-1.58; lanes confined to disjoint CU ranges 2.9-5.8 ms: profiles/r04_lanes.txt)
     lanes_min_nnz: int = 20000000    # smaller matrices keep one stream
+    # ---- reuse of an unchanged operand's aggregation ------------------------------------------------------------
+    reuse_operand: int = 1           # single-rank engines keep A . H of a graph-leaf operand (the input features: the same matrix every epoch) and,
+                                     # from its third sighting on, skip the launch group while a device-side bitwise compare of H against a kept
+                                     # copy finds no change (engine.AggregationEngine.forward_reusing, csrc/pgcn_reuse.hip); 0 = the launches
+                                     # of before, exactly -- the A/B switch of the measurement (HISTORY.md section 32)
+    reuse_max_bytes: int = 1 << 30   # ... for operands whose kept copy and kept result (2 n f 4 bytes) fit in this: a memory bound, not a tuned value
     # ---- vertex order ---------------------------------------------------------------------------------------
     degree_sort: bool = True
     order: str = "auto"              # degree | community | auto (label propagation, kept when it finds structure)
