@@ -478,6 +478,47 @@ int pgcn_spmm_heads_forward2_f32(const int64_t *rowptr, const int32_t *col, cons
                                  float *C2, int64_t ldc2, float *partial_ws, int64_t partial_ws_elems, int64_t nslots,
                                  uint32_t flags, pgcn_stream_t stream);
 
+/* ---- ATTENTION DROPOUT (Velickovic et al., ICLR 2018, section 3.3; no counterpart in the reference): the two gather passes above with
+ * the normalised coefficients dropped anew at every training step, per entry AND head (pgcn_gat_attndrop.hip).  csrc/pgcn_attndrop.h
+ * states the keep function:
+ *   keep(gi, gj, k) = u(seed, step[0], layer, gi, gj, k) >= thr,   scale = dropout_scale(thr)     (gemm/pgcn_dropout.h)
+ * gi: the GLOBAL id of the attending vertex (the row of the softmax), gj: of its neighbour, both below 2^31; k: the head, 0-based;
+ * layer in [0, 2^20).  Not symmetric in (gi, gj); self entries are dropped like any other; independent of owner rank and local
+ * numbering.  step: ONE int64 in DEVICE memory, read by the kernels (a captured step draws a new mask at every replay).  thr: dropout's
+ * threshold of the drop probability (0: nothing is dropped, scale 1).
+ *
+ * pgcn_gat_attndrop_forward2_f32: pgcn_spmm_heads_forward2_f32 in mode 0 with alpha' = keep ? alpha * scale : 0 and c' likewise:
+ *   C[i, 0 .. F)           (+)= sum_j alpha'_ij B_j          alpha: the softmax of the WHOLE row (rowstat); a row that loses every
+ *                                                             entry of a head gives exact zeros there
+ *   C2[i, 0 .. F)          (+)= V_i = sum_j c'_ij B_j,       c_ij = alpha_ij LeakyReLU'(s1_i + s2_j)
+ *   C2[i, F .. F + heads)  (+)= C_i = sum_j c_ij             UNMASKED: a dropped entry still acts on the scores through the normalisation
+ * row_gid[nrows]: global ids of the structure's rows (gi), col_gid[ncols]: of its columns (gj).  Work-space as the model call's.
+ *
+ * pgcn_gat_attndrop_grad_f32: pgcn_spmm_heads_grad_f32 in mode 0 without the de output, on the TRANSPOSED structure (row j, col i):
+ *   C[j, 0 .. F)           (+)= sum_i alpha'_ij B_i                                     (B = dOut)
+ *   C[j, F .. F + heads)   (+)= ds2_j = sum_i (c'_ij <B_i, Z_j> - c_ij t_i)             t_i = <dOut_i, out_i> of the MASKED out
+ * HERE row_gid[nrows] holds the ids of the transposed structure's rows, which are the NEIGHBOURS gj, and col_gid[ncols] those of its
+ * columns, which are the ATTENDING vertices gi: the mask of entry (i, j) is the one the forward call drew.  ds1_i = <dOut_i, V_i> -
+ * t_i C_i as before (pgcn_gat_row_dots_f32), from the masked V and the unmasked C.
+ *
+ * Both: one wave per task of the plan, fixed summation order, slots + pgcn_spmm_fixup_f32 for cut rows, no atomics; the gathers are
+ * unpredicated and a dropped weight is an exact 0.  PGCN_EUNSUPPORTED unless heads is 1 .. 8, d is 32, 64, 128 or 256 and
+ * heads * d <= 256 (and 16-byte aligned operands, leading dimensions % 4 == 0).  flags: PGCN_SPMM_ACCUMULATE.                        */
+int pgcn_gat_attndrop_forward2_f32(const int64_t *rowptr, const int32_t *col, const float *rowstat, const float *s2,
+                                   int64_t lds2, float slope, int32_t heads, int32_t d, int64_t nrows,
+                                   const int32_t *tasks, int64_t ntasks, const int64_t *seg, int32_t nslices,
+                                   const int32_t *fix, int64_t nfix, const float *B, int64_t ldb, float *C, int64_t ldc,
+                                   float *C2, int64_t ldc2, float *partial_ws, int64_t partial_ws_elems, int64_t nslots,
+                                   uint32_t flags, const int32_t *row_gid, const int32_t *col_gid, uint64_t seed,
+                                   const int64_t *step, int32_t layer, uint32_t thr, pgcn_stream_t stream);
+int pgcn_gat_attndrop_grad_f32(const int64_t *rowptr, const int32_t *col, const float *rowstat, const float *s2,
+                               int64_t lds2, float slope, int32_t heads, int32_t d, int64_t nrows, const int32_t *tasks,
+                               int64_t ntasks, const int64_t *seg, int32_t nslices, const int32_t *fix, int64_t nfix,
+                               const float *B, int64_t ldb, const float *Z, int64_t ldz, const float *t, float *C,
+                               int64_t ldc, float *partial_ws, int64_t partial_ws_elems, int64_t nslots, uint32_t flags,
+                               const int32_t *row_gid, const int32_t *col_gid, uint64_t seed, const int64_t *step,
+                               int32_t layer, uint32_t thr, pgcn_stream_t stream);
+
 /* The dense 512 x 128 BLOCKS of the attention pattern on the bf16 matrix cores (r06, pgcn_gat_blocks.hip): the entries inside the
  * listed blocks of the products above, with the weights computed in registers from the same statistics and split into three bf16
  * planes (fp32 accuracy, as pgcn_spmm_dense_bf16x3_f32).  work / blk_img / panel_list / npanels / image_ws: the block structure and

@@ -263,10 +263,13 @@ class PGAT(nn.Module):
     of the heads, out_features / K columns (the output layer of the GAT paper) -- ``out_features`` stays the projected width;
     ``dropout`` drops the layer's output in training mode, masks from ``state`` (a dropout.DropoutState the model's layers share),
     ``layer`` and the GLOBAL row ids, so P ranks under any part vector draw the masks of one rank.  One kernel each way
-    (``_GatTail``).  Not here: dropout on the attention coefficients, norms, residual links."""
+    (``_GatTail``).  ``attn_dropout`` drops the NORMALISED attention coefficients in training mode, per entry and head and after the
+    softmax over the whole row (the GAT paper's p = 0.6): alpha' = keep ? alpha / (1 - p) : 0, keep a pure function of (seed, step,
+    layer, head, the two GLOBAL vertex ids) -- csrc/pgcn_attndrop.h, ``gat.GatEngine``; it needs ``state`` like ``dropout``, and an
+    evaluation pass makes exactly the calls of a layer without it.  Not here: norms, residual links."""
 
     def __init__(self, A, in_features, out_features, heads=None, bias=False, activation=None, concat=True, dropout=0.0, layer=0,
-                 state=None):
+                 state=None, attn_dropout=0.0):
         super(PGAT, self).__init__()
         K = globals()["heads"] if heads is None else heads
         if out_features % K:
@@ -295,6 +298,15 @@ class PGAT(nn.Module):
             raise ValueError("the reference layer has no bias, activation, head mean or dropout")
         if self.has_bias:
             self.bias = nn.Parameter(torch.zeros(out_features if self.concat else out_features // K))
+        self.attn_dropout = float(attn_dropout)
+        _dropout.threshold(attn_dropout)
+        self._attn_drop = None
+        if self.attn_dropout > 0.0:
+            if state is None:
+                raise ValueError("attn_dropout=%r needs state=dropout.DropoutState(...) shared by the model's layers" % (attn_dropout,))
+            if A is not None and getattr(A, "mode", "standard") == "reference":
+                raise ValueError("the reference layer has no attention dropout (attn_dropout needs mode='standard')")
+            self._attn_drop = _dropout.AttnDrop(attn_dropout, state, self.layer)
         self.reset_parameters()
 
     def reset_parameters(self):
@@ -318,6 +330,8 @@ class PGAT(nn.Module):
         st = self._state
         if st is None or st.busy or (st.heads, st.d) != (K, d):
             st = self._state = self.A.new_layer_state(K, d)
+        if self._attn_drop is not None:                                 # (a layer without the option never touches the field)
+            st.drop = self._attn_drop if self.training else None
         out = _gat.GatAggregatePacked.apply(self.A, st, ZS)             # :144-149 on the stored entries
         if not self._has_tail:
             return out
@@ -435,35 +449,41 @@ def _barrier():
         _all_reduce(torch.zeros(1, device=device)).item()
 
 
-def _architecture(fin, classes, nlayers, task=None, hidden=None, out_heads=None, dropout=0.0, dropout_seed=0, bias=None, **_):
+def _architecture(fin, classes, nlayers, task=None, hidden=None, out_heads=None, dropout=0.0, dropout_seed=0, bias=None,
+                  attn_dropout=0.0, **_):
     """checkpoint.architecture of the model ``_train_on_data`` builds from these arguments (and this module's ``heads``)."""
     widths = [int(fin)] + [int(8 * heads if hidden is None else hidden)] * (nlayers - 1) + [int(classes)]
     # (the initial parameters are drawn under dropout_seed, with or without dropout: the record keeps it in the dropout case only,
     # where it also seeds the masks -- a resumed run draws no initial parameters)
+    extra = {"attn_dropout": float(attn_dropout)} if attn_dropout and float(attn_dropout) > 0.0 else {}
     return _checkpoint.architecture(widths, task, dropout, dropout_seed, bias=bias, heads=heads,
-                                    out_heads=1 if out_heads is None else out_heads)
+                                    out_heads=1 if out_heads is None else out_heads, **extra)
 
 
 TASKS, OPTIMIZERS = _pgcn.TASKS, _pgcn.OPTIMIZERS
 
 
-def build_classifier(A, fin, classes, nlayers, hidden, K, out_heads=1, dropout=0.0, bias=False, state=None):
+def build_classifier(A, fin, classes, nlayers, hidden, K, out_heads=1, dropout=0.0, bias=False, state=None, attn_dropout=0.0):
     """The model of the GAT paper on the engine ``A``: layers 0 .. L-2 are K concatenated heads of hidden / K columns, ELU, dropout
-    on their output; the last layer averages ``out_heads`` heads of ``classes`` columns.  ``widths``: the layers' input widths and
-    the class count."""
+    on their output; the last layer averages ``out_heads`` heads of ``classes`` columns.  ``attn_dropout``: dropout on the attention
+    coefficients of EVERY layer, the last one included, as in the paper.  ``widths``: the layers' input widths and the class count."""
     if hidden % K:
         raise ValueError("hidden (%d) must be divisible by the number of heads (%d)" % (hidden, K))
     widths = [fin] + [hidden] * (nlayers - 1) + [classes]
     extra = {"bias": True} if bias else {}
+    last = {}
+    if attn_dropout and float(attn_dropout) > 0.0:       # (absent: the constructor calls of before)
+        extra["attn_dropout"] = float(attn_dropout)
+        last = {"layer": nlayers - 1, "state": state}
     layers = [PGAT(A, widths[i], hidden, heads=K, activation="elu", dropout=dropout, layer=i, state=state, **extra)
               for i in range(nlayers - 1)]
-    layers.append(PGAT(A, widths[nlayers - 1], out_heads * classes, heads=out_heads, concat=False, **extra))
+    layers.append(PGAT(A, widths[nlayers - 1], out_heads * classes, heads=out_heads, concat=False, **extra, **last))
     return nn.Sequential(*layers), widths
 
 
 def _train_on_data(A, n, nlayers, features, labels, split, task=None, hidden=None, out_heads=None, epochs=None, lr=None,
                    eval_every=None, dropout=0.0, dropout_seed=0, bias=None, weight_decay=None, decoupled_decay=None, optimizer=None,
-                   save=None, load=None, predict=None, proba=None, control=None):
+                   save=None, load=None, predict=None, proba=None, control=None, attn_dropout=0.0):
     """The loop of ``run`` on real inputs, the scheme of PGCN._train_on_data (``control``: ``nodeloss.Control``, as there):
     constant features, Adam, the masked loss over the train
     rows (``task="multilabel"``: the masked binary cross entropy and micro-F1).  Reports every ``eval_every`` epochs: without
@@ -486,10 +506,14 @@ def _train_on_data(A, n, nlayers, features, labels, split, task=None, hidden=Non
     if n_train < 1:
         raise ValueError("split %r: no train rows" % (split,))
     _dropout.threshold(dropout)
-    state = _dropout.DropoutState(dropout_seed, device) if dropout > 0.0 else None
+    attn_dropout = float(attn_dropout or 0.0)
+    _dropout.threshold(attn_dropout)
+    # (with --dropout 0 the state exists for the attention mask alone: its seed and its step)
+    state = _dropout.DropoutState(dropout_seed, device) if dropout > 0.0 or attn_dropout > 0.0 else None
     with torch.random.fork_rng(devices=[]):        # every rank draws the SAME initial parameters, from the seed of the command line:
         torch.manual_seed(int(dropout_seed))       # -s 1 and -s P then train one model (the ranks' mean of equal draws is that draw)
-        model, widths = build_classifier(A, data.fin, data.classes, nlayers, hidden, K, out_heads, dropout, bool(bias), state)
+        model, widths = build_classifier(A, data.fin, data.classes, nlayers, hidden, K, out_heads, dropout, bool(bias), state,
+                                         **({"attn_dropout": attn_dropout} if attn_dropout > 0.0 else {}))
     for i, m in enumerate(model):
         _pgcn.tune_dense_gemms(A.part.n_local, widths[i], device, m.out_features + 2 * m.heads)
     model = model.to(device)
@@ -501,7 +525,7 @@ def _train_on_data(A, n, nlayers, features, labels, split, task=None, hidden=Non
 
     first, history, best, hooks = 0, [], None, None
     if save is not None or load is not None or predict is not None or proba:
-        arch = _architecture(data.fin, data.classes, nlayers, kind, hidden, out_heads, dropout, dropout_seed, bias)
+        arch = _architecture(data.fin, data.classes, nlayers, kind, hidden, out_heads, dropout, dropout_seed, bias, attn_dropout)
         hooks = _checkpoint.Hooks("PGAT", arch, model, fused, opt, state, save, load, predict, proba, myrank, _barrier)
         first, history, best = hooks.resume()
     last = first + epochs - 1
@@ -556,7 +580,7 @@ def _train_on_data(A, n, nlayers, features, labels, split, task=None, hidden=Non
 def run(rank, size, nlayers, nfeatures, path_A, path_partvec, backend, epochs=None, features=None, labels=None, split=None, **data):
     """PGAT.py:165-233.  ``features`` / ``labels`` / ``split`` (.npy files in global vertex order, nodedata.py; all three or none):
     train the classifier of ``build_classifier`` on them instead of the synthetic loop (``_train_on_data`` takes the other keyword
-    arguments: task, hidden, out_heads, lr, eval_every, dropout, dropout_seed, bias, weight_decay, decoupled_decay, optimizer, and
+    arguments: task, hidden, out_heads, lr, eval_every, dropout, dropout_seed, attn_dropout, bias, weight_decay, decoupled_decay, optimizer, and
     save, load, predict, proba -- checkpoint.py, as in PGCN.run -- and the options of nodeloss.CONTROL: clip_norm, lr_schedule,
     lr_warmup, lr_min, lr_step, lr_gamma, lr_horizon, patience, as in PGCN.run); the returned model carries ``history``, ``best`` and
     ``widths``."""
@@ -571,7 +595,13 @@ def run(rank, size, nlayers, nfeatures, path_A, path_partvec, backend, epochs=No
     if data.get("proba") and data.get("predict") is None:
         raise ValueError("proba needs predict")
     if files and mode == "reference":
-        raise ValueError("the reference layer has no bias, activation, head mean or dropout: train on data in standard mode")
+        raise ValueError("the reference layer has no bias, activation, head mean, dropout or attention dropout (attn_dropout): train "
+                         "on data in standard mode")
+    if data.get("attn_dropout") is not None:
+        try:
+            _dropout.threshold(data["attn_dropout"])
+        except (TypeError, ValueError):
+            raise ValueError("attn_dropout takes a probability in [0, 1), got %r" % (data["attn_dropout"],))
     control = {k: data.pop(k) for k in list(data) if k in _nodeloss.CONTROL}
     control = {k: v for k, v in control.items() if v is not None}
     if control:            # each value, what goes together, the horizon against the warm-up: before any collective
@@ -679,7 +709,7 @@ def main(argv):
 
     try:
         opts, args = getopt.getopt(argv, "a:p:b:s:l:f:", ["mode=", "heads=", "features=", "labels=", "split=", "task=", "hidden=",
-                                                          "out-heads=", "epochs=", "lr=", "eval-every=", "dropout=", "dropout-seed=",
+                                                          "out-heads=", "epochs=", "lr=", "eval-every=", "dropout=", "dropout-seed=", "attn-dropout=",
                                                           "bias", "weight-decay=", "adamw", "optimizer=", "save=", "load=", "predict=",
                                                           "proba"] + [f[2:] + "=" for f in _nodeloss.CONTROL_FLAGS.split(", ")])
     except getopt.GetoptError:
@@ -710,6 +740,12 @@ def main(argv):
                 _dropout.threshold(data["dropout"])
             except ValueError:
                 refuse("--dropout takes a probability in [0, 1), got %r" % arg)
+        elif opt == '--attn-dropout':  # drop the normalised attention coefficients of every layer with this probability (class PGAT)
+            try:
+                data["attn_dropout"] = float(arg)
+                _dropout.threshold(data["attn_dropout"])
+            except ValueError:
+                refuse("--attn-dropout takes a probability in [0, 1), got %r" % arg)
         elif opt == '--dropout-seed':
             try:
                 data["dropout_seed"] = int(arg)
@@ -760,7 +796,7 @@ def main(argv):
     files = [k for k in ("features", "labels", "split") if k in data]
     if data and len(files) != 3:
         refuse("--features, --labels and --split go together (and --task, --hidden, --out-heads, --epochs, --lr, --eval-every, --dropout, "
-               "--dropout-seed, --bias, --weight-decay, --adamw, --save, --load, --predict, --proba, --optimizer, %s need them); got %%s"
+               "--dropout-seed, --attn-dropout, --bias, --weight-decay, --adamw, --save, --load, --predict, --proba, --optimizer, %s need them); got %%s"
                % _nodeloss.CONTROL_FLAGS % ", ".join("--" + {"decoupled_decay": "adamw"}.get(k, k.replace("_", "-")) for k in sorted(data)))
     for k in files:
         if not os.path.exists(data[k]):
@@ -770,7 +806,8 @@ def main(argv):
     if "load" in data and not os.path.exists(data["load"]):
         refuse("--load: no such file %r" % (data["load"],))
     if data and mode == "reference":
-        refuse("--mode reference has no bias, activation, head mean or dropout: --features needs --mode standard")
+        refuse("--mode reference has no bias, activation, head mean, dropout or attention dropout: --features (and --attn-dropout) "
+               "need --mode standard")
     control = {k: data[k] for k in _nodeloss.CONTROL if k in data}
     if control:
         try:               # what goes together; the horizon against the warm-up where the first epoch is known (no --load)

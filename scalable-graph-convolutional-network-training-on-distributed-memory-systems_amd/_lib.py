@@ -76,6 +76,12 @@ SIGNATURES = {
     "pgcn_spmm_heads_forward2_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, ctypes.c_float, _i32, _i32, _i32, _i64, _vp, _i64,
                                                     _vp, _i32, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _i64, _u32,
                                                     _vp]),
+    "pgcn_gat_attndrop_forward2_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, ctypes.c_float, _i32, _i32, _i64, _vp, _i64,
+                                                      _vp, _i32, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _i64, _u32,
+                                                      _vp, _vp, ctypes.c_uint64, _vp, _i32, _u32, _vp]),
+    "pgcn_gat_attndrop_grad_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, ctypes.c_float, _i32, _i32, _i64, _vp, _i64,
+                                                  _vp, _i32, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _i64,
+                                                  _u32, _vp, _vp, ctypes.c_uint64, _vp, _i32, _u32, _vp]),
     "pgcn_gat_blocks_forward_f32": (ctypes.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i64, ctypes.c_float, _i32, _i32, _i64, _i64,
                                                    _vp, _i64, _vp, _i64, _vp, _i64, _i64, _vp]),
     "pgcn_gat_blocks_backward_f32": (ctypes.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _i64, ctypes.c_float, _i32,

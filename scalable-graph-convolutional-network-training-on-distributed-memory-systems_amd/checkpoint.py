@@ -37,24 +37,27 @@ import torch
 from . import nodedata as _nodedata
 
 FORMAT_VERSION = 1
-ARCH_FIELDS = ("task", "layers", "widths", "norm", "root_weight", "bias", "residual", "heads", "out_heads", "dropout", "dropout_seed", "aggr",
+ARCH_FIELDS = ("task", "layers", "widths", "norm", "root_weight", "bias", "residual", "heads", "out_heads", "dropout", "attn_dropout", "dropout_seed", "aggr",
                "drop_edge", "softmax_beta", "propagate", "dense_layers")
 
 
 def architecture(widths, task, dropout=0.0, dropout_seed=0, norm=None, root_weight=None, bias=None, residual=None, heads=None,
-                 out_heads=None, aggr=None, propagate=None, dense_layers=None, drop_edge=None, softmax_beta=None):
+                 out_heads=None, aggr=None, propagate=None, dense_layers=None, drop_edge=None, softmax_beta=None, attn_dropout=None):
     """The plain-value record of what a model was built from; two models of equal records have state dicts of equal keys and shapes,
     and draw the same dropout masks.  ``aggr``: the key exists only for "max" -- a record of the weighted sum is the record of before,
     and compares equal to every checkpoint written without the key.  Likewise ``propagate`` ((K, alpha): the key holds [K, alpha]
     only when the model ends with the personalised-PageRank propagation) and ``dense_layers`` (True only when the layers do not
     aggregate): without them the record is the record of before.  ``drop_edge``: the key holds the DropEdge probability only when it is
     positive; the mask's seed is ``dropout_seed``, recorded when either probability is positive.  ``softmax_beta``: the key holds the
-    softmax aggregation's beta (a float, 0.0 included) only when one is given."""
+    softmax aggregation's beta (a float, 0.0 included) only when one is given.  ``attn_dropout``: the key holds the GAT layers' attention
+    dropout probability only when it is positive (its mask, too, is keyed by ``dropout_seed``); it is compared before the seed, so a
+    checkpoint loaded under another value is refused in its name."""
     arch = {"widths": [int(w) for w in widths], "layers": len(widths) - 1, "task": str(task or "single"),
             "norm": "none" if norm in (None, "none") else str(norm), "root_weight": bool(root_weight), "bias": bool(bias),
             "residual": bool(residual), "heads": None if heads is None else int(heads),
             "out_heads": None if out_heads is None else int(out_heads), "dropout": float(dropout),
-            "dropout_seed": int(dropout_seed) if float(dropout) > 0.0 or float(drop_edge or 0.0) > 0.0 else 0}
+            "dropout_seed": int(dropout_seed) if float(dropout) > 0.0 or float(drop_edge or 0.0) > 0.0
+            or float(attn_dropout or 0.0) > 0.0 else 0}
     if aggr == "max":
         arch["aggr"] = "max"
     if propagate is not None:
@@ -65,6 +68,8 @@ def architecture(widths, task, dropout=0.0, dropout_seed=0, norm=None, root_weig
         arch["drop_edge"] = float(drop_edge)
     if softmax_beta is not None:
         arch["softmax_beta"] = float(softmax_beta)
+    if float(attn_dropout or 0.0) > 0.0:
+        arch["attn_dropout"] = float(attn_dropout)
     return arch
 
 

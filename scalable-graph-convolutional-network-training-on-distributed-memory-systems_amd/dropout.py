@@ -122,6 +122,50 @@ def edge_keep(seed, step, gi, gj, thr):
     return (_ids(gi) == _ids(gj)) | (edge_u(seed, step, gi, gj) >= np.uint32(thr))
 
 
+# ---- attention dropout: the host statement of csrc/pgcn_attndrop.h (include/pgcn_hip.h has the contract) ----------------------
+ATTN_LAYER = 1 << 21          # added to the layer index in the mask's key: reserved, above any layer index and above EDGE_LAYER
+
+
+def attn_u(seed, step, layer, gi, gj, heads):
+    """u (uint32 numpy [len(gi), heads]) of the attention coefficients of the stored entries (gi attends to gj), GLOBAL ids below
+    2^31: fmix32(fmix32(fmix32(gj ^ lo32(key)) ^ gi ^ hi32(key)) ^ (k + 1)) under key(seed, step, ATTN_LAYER + layer) -- the hash of
+    feature dropout with the head in the place of the row id's high half.  Not symmetric in (gi, gj)."""
+    gi, gj = _ids(gi).reshape(-1), _ids(gj).reshape(-1)
+    if gi.size and (min(int(gi.min()), int(gj.min())) < 0 or max(int(gi.max()), int(gj.max())) >= 2 ** 31):
+        raise ValueError("attention dropout takes global ids in [0, 2^31)")
+    if not 0 <= int(layer) < EDGE_LAYER:
+        raise ValueError("attention dropout takes a layer index in [0, 2^20)")
+    k = key(seed, step, ATTN_LAYER + int(layer))
+    klo, khi = np.uint32(k & 0xFFFFFFFF), np.uint32(k >> 32)
+    with np.errstate(over="ignore"):
+        b = _fmix32(_fmix32(gj.astype(np.uint32) ^ klo) ^ gi.astype(np.uint32) ^ khi)
+        return _fmix32(b[:, None] ^ (np.arange(int(heads), dtype=np.uint32) + np.uint32(1))[None, :])
+
+
+def attn_keep(seed, step, layer, gi, gj, heads, thr):
+    """bool numpy [len(gi), heads]: the coefficient of entry (gi, gj) and head k survives the step -- ``u >= thr``; self entries are
+    dropped like any other."""
+    return attn_u(seed, step, layer, gi, gj, heads) >= np.uint32(thr)
+
+
+class AttnDrop:
+    """Attention dropout of one GAT layer: the drop probability's threshold and scale, the ``DropoutState`` whose seed and step key
+    the mask, and the layer index.  ``PGAT(..., attn_dropout=p)`` hands it to ``GatEngine.forward`` through the layer state."""
+
+    def __init__(self, p, state: DropoutState, layer: int = 0):
+        self.p = float(p)
+        self.thr, self.scale = threshold(p)
+        if state is None:
+            raise ValueError("AttnDrop needs a DropoutState (the seed and the step of the mask)")
+        if not 0 <= int(layer) < EDGE_LAYER:
+            raise ValueError("attention dropout takes a layer index in [0, 2^20)")
+        self.state, self.layer = state, int(layer)
+
+    @property
+    def on(self) -> bool:
+        return self.thr > 0
+
+
 class EdgeDrop:
     """DropEdge of one model (Rong et al., ICLR 2020): the drop probability, its threshold and the ``DropoutState`` whose seed and
     step key the mask -- the one feature dropout uses.  ``PGCN(..., drop_edge=ctx)`` hands it to ``AggregationEngine.forward_drop`` /

@@ -25,6 +25,15 @@ Two semantics (``mode``): "standard" = LeakyReLU + softmax over the neighbours, 
 row take part in the softmax with logit 0: out_i = sum_edges alpha_ij Z_j + beta_i sum_all Z_j, the
 global column sum being one small all-reduce.  In both modes P ranks compute exactly what one
 process computes on the whole graph (owned rows).
+
+Attention dropout (standard mode; ``GatLayerState.drop`` = a ``dropout.AttnDrop`` whose threshold is positive): the aggregation uses
+alpha'_ijk = keep(i, j, k) ? alpha_ijk * scale : 0 with the softmax's statistics of the WHOLE row, the mask a pure function of
+(seed, step, layer, head, the two GLOBAL vertex ids) -- csrc/pgcn_attndrop.h.  The two gather passes then run over the WHOLE
+structures with pgcn_gat_attndrop_forward2_f32 / _grad_f32 (the dense blocks take no part), or -- CPU tensors, providers without the
+two methods, shapes the kernels refuse -- as tensor operations over the entry list (``_drop_forward`` / ``_drop_backward``):
+    out_i = sum_j alpha'_ij Z_j,  V_i = sum_j c'_ij Z_j,  C_i = sum_j c_ij (UNMASKED),  t_i = <dOut_i, out_i>,
+    dZ_j = sum_i alpha'_ij dOut_i,  ds2_j = sum_i (c'_ij dp_ij - c_ij t_i),  ds1_i = <dOut_i, V_i> - t_i C_i.
+Without a context, or at threshold 0, every call is the one made before.
 """
 from __future__ import annotations
 
@@ -165,6 +174,9 @@ class GatLayerState:
     s1: Optional[torch.Tensor] = None
     out: Optional[torch.Tensor] = None
     busy: bool = False                   # a forward whose backward has not run yet owns these buffers
+    drop: Optional[object] = None        # dropout.AttnDrop of the NEXT forward (the layer sets it in training mode), or None
+    dropped: Optional[object] = None     # ... of the last forward, for its backward
+    entries: Optional[tuple] = None      # the composed masked forward's (rows, cols, alpha', c', c), kept for its backward
 
 
 class GatEngine(BoundaryExchange):
@@ -220,6 +232,8 @@ class GatEngine(BoundaryExchange):
         self.perm = g.perm.to(self.device)
         self._inv_perm = None              # forward entry -> its position in the transposed structure (built on demand)
         self._scratch = {}
+        self._gid_cache = {}
+        self._entry_cache = None
         self.sliced_grad = _T.gat_sliced   # XCD-sliced edge gradient where the shape allows
         # the edge gradient over the balanced tasks of the SpMM plan (pgcn_gat_edge_grad_tasks_f32)
         self.task_grad = _T.gat_task_grad and hasattr(kernels, "gat_edge_grad_tasks")
@@ -273,8 +287,28 @@ class GatEngine(BoundaryExchange):
         return buf
 
     # -- one pass = the gather kernel over the entries outside the blocks + the blocks ------------------------------
-    def _forward2(self, name: str, st: GatLayerState, s2, B, out, K: int, d: int, accumulate: bool = False) -> bool:
+    def _gids(self, name: str):
+        """(row ids, column ids) of structure ``name``: the int32 GLOBAL ids of its two index spaces (attention dropout's mask)."""
+        g = self._gid_cache.get(name)
+        if g is None:
+            own = self.part.owned.to(device=self.device, dtype=torch.int32).contiguous()
+            hal = self.part.halo_global.to(device=self.device, dtype=torch.int32).contiguous()
+            both = torch.cat([own, hal]).contiguous()
+            g = {"fwd": (own, both), "bwd": (both, own), "fwd_local": (own, own), "fwd_halo": (own, hal), "bwd_halo": (hal, own),
+                 "bwd_local": (own, own)}
+            self._gid_cache.update(g)
+            g = g[name]
+        return g
+
+    def _drop_kernels(self, K: int, d: int) -> bool:
+        return hasattr(self.k, "gat_attndrop_forward2") and hasattr(self.k, "gat_attndrop_grad") and self.covers(K, d)
+
+    def _forward2(self, name: str, st: GatLayerState, s2, B, out, K: int, d: int, accumulate: bool = False, drop=None) -> bool:
         A = getattr(self, name)
+        if drop is not None:               # attention dropout: the WHOLE structure in the masked gather kernel, no blocks
+            rg, cg = self._gids(name)
+            return self.k.gat_attndrop_forward2(A, st.rowstat, s2, self.slope, B, out, st.V, K, d, rg, cg, drop.state.seed,
+                                                drop.state.step, drop.layer, drop.thr, accumulate=accumulate)
         part = self.parts.get(name) if d == 64 else None
         if not self.k.spmm_heads_forward2(part[0] if part else A, st.rowstat, s2, self.slope, self.mode_id, B, out, st.V, K, d,
                                           accumulate=accumulate):
@@ -283,8 +317,12 @@ class GatEngine(BoundaryExchange):
             raise RuntimeError("the block part of the GAT forward was refused after the gather part was taken")
         return True
 
-    def _grad(self, name: str, st: GatLayerState, s2, dOut, Z, t, dZc, K: int, d: int) -> bool:
+    def _grad(self, name: str, st: GatLayerState, s2, dOut, Z, t, dZc, K: int, d: int, drop=None) -> bool:
         AT = getattr(self, name)
+        if drop is not None:
+            rg, cg = self._gids(name)      # (rows of the transposed structure: the neighbours gj; its columns: the attending gi)
+            return self.k.gat_attndrop_grad(AT, st.rowstat, s2, self.slope, dOut, Z, t, dZc, K, d, rg, cg, drop.state.seed,
+                                            drop.state.step, drop.layer, drop.thr)
         part = self.parts.get(name) if d == 64 else None
         if not self.k.spmm_heads_grad(part[0] if part else AT, st.rowstat, s2, self.slope, self.mode_id, dOut, Z, t, dZc, None, K, d):
             return False
@@ -302,6 +340,10 @@ class GatEngine(BoundaryExchange):
         n_p, n_h = self.n_local, self.n_halo
         if Z.shape != (n_p, F) or s1.shape != (n_p, K) or s2.shape != (n_p, K):
             raise ValueError("expected Z %s, s1/s2 %s" % ((n_p, F), (n_p, K)))
+        drop = st.drop if st.drop is not None and st.drop.on else None
+        if drop is not None and self.mode_id != 0:
+            raise ValueError("attention dropout needs mode='standard': the reference layer has none")
+        st.dropped, st.entries = drop, None
         if panel is not None and n_h == 0 and panel.shape[0] == n_p and panel.shape[1] >= F + K and panel.shape[1] % 4 == 0 \
                 and panel.stride(1) == 1 and panel.stride(0) == panel.shape[1] and panel.dtype is torch.float32 \
                 and panel.data_ptr() % 16 == 0:
@@ -323,7 +365,7 @@ class GatEngine(BoundaryExchange):
         out = torch.empty((n_p, F), dtype=torch.float32, device=self.device)
         st.fused = False
         split = (self.size > 1 and self.overlap and n_h > 0 and self.fwd_halo is not None and self.fused_fwd and self.covers(K, d)
-                 and self.mode_id == 0)
+                 and self.mode_id == 0 and (drop is None or self._drop_kernels(K, d)))
         if split:
             # N > 1 (r06): the statistics of the edge softmax need s2 only -- its halo rows (16 bytes each) are exchanged FIRST, the 1 KB
             # rows of [Z | s2] follow on the comm stream under the statistics pass and the product over the LOCAL columns; the product
@@ -341,11 +383,11 @@ class GatEngine(BoundaryExchange):
             pw2 = F + (K + 3) // 4 * 4
             if st.V is None or st.V.shape != (n_p, pw2):
                 st.V = torch.empty((n_p, pw2), dtype=torch.float32, device=self.device)
-            ok = self._forward2("fwd_local", st, st.s2c[:n_p], Zc[:n_p], out, K, d)
+            ok = self._forward2("fwd_local", st, st.s2c[:n_p], Zc[:n_p], out, K, d, drop=drop)
             for w in wz:
                 w()
             if ok:
-                ok = self._forward2("fwd_halo", st, st.s2c[n_p:], Zc[n_p:], out, K, d, accumulate=True)
+                ok = self._forward2("fwd_halo", st, st.s2c[n_p:], Zc[n_p:], out, K, d, accumulate=True, drop=drop)
             if not ok:
                 raise RuntimeError("the split GAT forward was refused by a kernel whose shape `covers` accepted")
             st.fused = True
@@ -357,6 +399,17 @@ class GatEngine(BoundaryExchange):
             for w in self._exchange_all(send, self.round_send_off, Zc[n_p:], self.round_recv_off, Fp):
                 w()
         st.s2c.copy_(Zc[:, F:F + K])        # compact: the per-entry s2 gathers stay in L2 instead of striding the panel
+        if drop is not None:
+            # attention dropout: statistics of the WHOLE rows, then ONE masked gather pass over the whole structure -- or the composition
+            self.k.gat_edge_softmax(self.fwd, st.s1, st.s2c, K, self.slope, self.mode_id, self.n_global, None, st.beta, st.rowstat)
+            pw2 = F + (K + 3) // 4 * 4
+            if st.V is None or st.V.shape != (n_p, pw2):
+                st.V = torch.empty((n_p, pw2), dtype=torch.float32, device=self.device)
+            if not (self._drop_kernels(K, d) and self._forward2("fwd", st, st.s2c, Zc, out, K, d, drop=drop)):
+                self._drop_forward(st, drop, Zc, out)
+            st.fused = True
+            st.out = out
+            return out
         if self.fused_fwd and self.covers(K, d):
             # statistics only, then ONE gather pass: out, and V | C for the backward's ds1 (no alpha planes, no de)
             self.k.gat_edge_softmax(self.fwd, st.s1, st.s2c, K, self.slope, self.mode_id, self.n_global,
@@ -387,6 +440,9 @@ class GatEngine(BoundaryExchange):
         n_p, n_h = self.n_local, self.n_halo
         Fp = st.Zc.shape[1]
         dOut = dOut.contiguous()
+        drop = st.dropped
+        if drop is not None and st.entries is not None:
+            return self._drop_backward(st, dOut, pack)
         dots = None
         if hasattr(self.k, "gat_row_dots") and dOut.stride(1) == 1 and st.out.stride(1) == 1:
             # t and (fused forward) ds1 in ONE pass over dOut, out and V (r05) instead of four element-wise / reduction launches
@@ -399,12 +455,12 @@ class GatEngine(BoundaryExchange):
         if st.fused and self.bwd_halo is not None and self.overlap and n_h > 0:
             # N > 1 (r06): the same pass in two parts -- the HALO rows of [dZ | ds2] first, their way home on the comm stream under the
             # local rows' part
-            if self._grad("bwd_halo", st, st.s2c[n_p:], dOut, st.Zc[n_p:], t, dZc[n_p:], K, d):
+            if self._grad("bwd_halo", st, st.s2c[n_p:], dOut, st.Zc[n_p:], t, dZc[n_p:], K, d, drop=drop):
                 if Fp > F + K:
                     dZc[n_p:, F + K:].zero_()
                 back = self._slab("gat_send", self.n_send, Fp)
                 waits = self._exchange_all(dZc[n_p:], self.round_recv_off, back, self.round_send_off, Fp, tag="backward")
-                if not self._grad("bwd_local", st, st.s2c[:n_p], dOut, st.Zc[:n_p], t, dZc[:n_p], K, d):
+                if not self._grad("bwd_local", st, st.s2c[:n_p], dOut, st.Zc[:n_p], t, dZc[:n_p], K, d, drop=drop):
                     raise RuntimeError("the local part of the fused GAT backward was refused after its halo part was taken")
                 ds1 = dots[1] if dots is not None and dots[1] is not None else \
                     (dOut.view(n_p, K, d) * st.V[:, :F].view(n_p, K, d)).sum(-1) - t * st.V[:, F:F + K]
@@ -412,10 +468,12 @@ class GatEngine(BoundaryExchange):
         if st.fused:
             # one gather pass: dZc = A_alpha^T . dOut and ds2 = the row sums of the edge gradient, which is not stored:
             # ds1 = its column sums = <dOut_i, V_i> - t_i C_i from the forward pass's second accumulator
-            if self._grad("bwd", st, st.s2c, dOut, st.Zc, t, dZc, K, d):
+            if self._grad("bwd", st, st.s2c, dOut, st.Zc, t, dZc, K, d, drop=drop):
                 ds1 = dots[1] if dots is not None and dots[1] is not None else \
                     (dOut.view(n_p, K, d) * st.V[:, :F].view(n_p, K, d)).sum(-1) - t * st.V[:, F:F + K]
                 return self._finish_backward(st, dOut, dZc, ds1, pack)
+            if drop is not None:           # the masked kernel refused operands its forward twin took: the composition, same mask
+                return self._drop_backward(st, dOut, pack)
             # the fused kernel refused operands its forward twin took (an alignment / stride of dOut or the work-space that
             # `covers` does not model): the unfused passes need the alpha planes the fused forward never wrote -- build them now
             self.k.gat_edge_softmax(self.fwd, st.s1, st.s2c, K, self.slope, self.mode_id, self.n_global,
@@ -463,6 +521,60 @@ class GatEngine(BoundaryExchange):
                 for k in range(K):
                     self.k.spmm(bwd_heads[k], dOut[:, k * d:(k + 1) * d], dZc[:, k * d:(k + 1) * d])
         self.k.csr_row_sums(self.bwd, self.perm, de, K, dZc[:, F:F + K])
+        return self._finish_backward(st, dOut, dZc, ds1, pack)
+
+    # -- attention dropout as tensor operations over the entry list (CPU tensors, other providers, shapes the kernels refuse) --------
+    def _drop_entries(self, st: GatLayerState, drop):
+        """(rows, cols, alpha', c', c) of the forward structure's entries, [nnz] and [nnz, K]: the weights from the row statistics as
+        the kernels form them, the keep bits from ``dropout.attn_keep`` under the state's step (one device read)."""
+        from . import dropout as _dropout
+        if self._entry_cache is None:
+            rp = self.graph.fwd.rowptr.to(torch.int64)
+            rows = torch.repeat_interleave(torch.arange(self.n_local, dtype=torch.int64), (rp[1:] - rp[:-1]).cpu())
+            cols = self.graph.fwd.col.to(torch.int64).cpu()
+            own, hal = self.part.owned.to(torch.int64).cpu(), self.part.halo_global.to(torch.int64).cpu()
+            self._entry_cache = (rows.to(self.device), cols.to(self.device), own[rows].numpy(), torch.cat([own, hal])[cols].numpy())
+        rows, cols, gi, gj = self._entry_cache
+        K = st.heads
+        q = st.rowstat[rows]                                   # [nnz, K, 4] (s1, m, 1/D, 0)
+        raw = q[:, :, 0] + st.s2c[cols]
+        pos = raw > 0
+        alpha = (torch.exp(torch.where(pos, raw, raw * self.slope) - q[:, :, 1]) - q[:, :, 3]) * q[:, :, 2]
+        c = alpha * torch.where(pos, torch.ones((), dtype=raw.dtype, device=raw.device), torch.full((), self.slope, dtype=raw.dtype,
+                                                                                                    device=raw.device))
+        keep = torch.from_numpy(_dropout.attn_keep(drop.state.seed, drop.state.host_step(), drop.layer, gi, gj, K, drop.thr)
+                                .reshape(-1, K)).to(self.device)
+        zero = torch.zeros((), dtype=raw.dtype, device=raw.device)
+        return rows, cols, torch.where(keep, alpha * drop.scale, zero), torch.where(keep, c * drop.scale, zero), c
+
+    def _drop_forward(self, st: GatLayerState, drop, Zc: torch.Tensor, out: torch.Tensor):
+        K, d = st.heads, st.d
+        F, n_p = K * d, self.n_local
+        st.entries = rows, cols, am, cm, c = self._drop_entries(st, drop)
+        Zj = Zc[:, :F].reshape(-1, K, d)[cols]
+        out.zero_()
+        out.view(n_p, K, d).index_add_(0, rows, am.unsqueeze(-1) * Zj)
+        st.V.zero_()
+        V = torch.zeros((n_p, K, d), dtype=torch.float32, device=self.device).index_add_(0, rows, cm.unsqueeze(-1) * Zj)
+        st.V[:, :F].copy_(V.view(n_p, F))
+        st.V[:, F:F + K].index_add_(0, rows, c)
+
+    def _drop_backward(self, st: GatLayerState, dOut: torch.Tensor, pack: Optional[torch.Tensor] = None):
+        K, d = st.heads, st.d
+        F, n_p, n_h = K * d, self.n_local, self.n_halo
+        Fp = st.Zc.shape[1]
+        rows, cols, am, cm, c = st.entries if st.entries is not None else self._drop_entries(st, st.dropped)
+        G = dOut.view(n_p, K, d)
+        t = (G * st.out.view(n_p, K, d)).sum(-1)                                   # of the MASKED out
+        ds1 = (G * st.V[:, :F].view(n_p, K, d)).sum(-1) - t * st.V[:, F:F + K]     # masked V, unmasked C
+        Gi = G[rows]
+        dp = (Gi * st.Zc[:, :F].reshape(-1, K, d)[cols]).sum(-1)
+        de = cm * dp - c * t[rows]
+        dZc = self._slab("gat_dzc", n_p + n_h, Fp)[:n_p + n_h]
+        dZc.zero_()
+        dZ = torch.zeros((n_p + n_h, K, d), dtype=torch.float32, device=self.device).index_add_(0, cols, am.unsqueeze(-1) * Gi)
+        dZc[:, :F].copy_(dZ.view(n_p + n_h, F))
+        dZc[:, F:F + K].index_add_(0, cols, de)
         return self._finish_backward(st, dOut, dZc, ds1, pack)
 
     def _finish_backward(self, st: GatLayerState, dOut: torch.Tensor, dZc: torch.Tensor, ds1: torch.Tensor,

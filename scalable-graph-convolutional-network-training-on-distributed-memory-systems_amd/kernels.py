@@ -1251,6 +1251,104 @@ class HipKernels:
         _lib.check(rc, "pgcn_spmm_heads_grad_f32")
         return True
 
+    # -- attention dropout (pgcn_gat_attndrop.hip): the masked twins of the two calls above ------------------------------
+    def _check_attn_mask(self, A: DeviceCSR, row_gid: torch.Tensor, col_gid: torch.Tensor, step: torch.Tensor, layer: int, thr: int):
+        for t, n, what in ((row_gid, A.nrows, "row_gid"), (col_gid, A.ncols, "col_gid")):
+            if not (t.is_cuda and t.dtype is torch.int32 and t.dim() == 1 and t.is_contiguous() and t.numel() >= n):
+                raise _lib.PgcnError("%s must be a contiguous int32 CUDA vector of at least %d global ids" % (what, n))
+        if not (step.is_cuda and step.dtype is torch.int64 and step.numel() == 1):
+            raise _lib.PgcnError("step must be a one-element int64 CUDA tensor (dropout.DropoutState.step)")
+        if not (0 <= int(layer) < (1 << 20) and 0 <= int(thr) <= 0xFFFFFFFF):
+            raise _lib.PgcnError("layer must be in [0, 2^20) and thr a 32-bit threshold")
+
+    def gat_attndrop_forward2(self, A: DeviceCSR, rowstat: torch.Tensor, s2: torch.Tensor, slope: float, B: torch.Tensor,
+                              C: torch.Tensor, C2: torch.Tensor, heads: int, d: int, row_gid: torch.Tensor, col_gid: torch.Tensor,
+                              seed: int, step: torch.Tensor, layer: int, thr: int, accumulate: bool = False) -> bool:
+        """``spmm_heads_forward2`` in standard mode under attention dropout (pgcn_gat_attndrop_forward2_f32): C[:, :F] (+)= sum_j
+        alpha'_ij B_j and C2[:, :F] (+)= V = sum_j c'_ij B_j with alpha' = keep ? alpha * scale : 0 (c' likewise), C2[:, F:F+heads] (+)=
+        sum_j c_ij UNMASKED.  keep: csrc/pgcn_attndrop.h under (seed, step, layer, row_gid[row] = gi, col_gid[col] = gj, head); ``step``
+        a one-element int64 device tensor.  False = shape not covered (heads 1-8, d 32 / 64 / 128 / 256, heads * d <= 256)."""
+        F = heads * d
+        hl = d // 4
+        if d % 4 or hl < 8 or hl & (hl - 1) or F > 256 or not 1 <= heads <= 8:
+            return False
+        pw2 = F + (heads + 3) // 4 * 4
+        self._check_rows(s2, A.ncols, heads, "s2")
+        if not (rowstat.is_cuda and rowstat.dtype is torch.float32 and rowstat.is_contiguous()
+                and rowstat.numel() == A.nrows * heads * 4):
+            raise _lib.PgcnError("rowstat must be a contiguous fp32 [nrows, heads, 4] CUDA tensor")
+        self._check_dense(B, A.ncols, "B")
+        self._check_dense(C, A.nrows, "C")
+        self._check_dense(C2, A.nrows, "C2")
+        if B.shape[1] < F or C.shape[1] < F or C2.shape[1] < pw2 or A.row_map is not None:
+            raise _lib.PgcnError("B / C narrower than heads * d, C2 narrower than heads * d + heads (rounded up to 4), "
+                                 "or a compact-row structure")
+        self._check_attn_mask(A, row_gid, col_gid, step, layer, thr)
+        if A.col.numel() == 0:
+            if not accumulate:
+                C[:A.nrows, :F].zero_()
+                C2[:A.nrows, :pw2].zero_()
+            return True
+        need = A.nslots * (F + pw2)
+        if need and (A.ws is None or A.ws.numel() < need):
+            A.ws = torch.empty(need, dtype=torch.float32, device=self.device)
+            A.launch_cache.clear()
+        flags = _lib.SPMM_ACCUMULATE if accumulate else 0
+        rc = self.lib.pgcn_gat_attndrop_forward2_f32(
+            A.rowptr.data_ptr(), A.col.data_ptr(), rowstat.data_ptr(), s2.data_ptr(), s2.stride(0), slope, heads, d,
+            A.nrows, _ptr(A.tasks), A.ntasks, A.seg, A.nslices, _ptr(A.fix), A.nfix, B.data_ptr(), B.stride(0),
+            C.data_ptr(), C.stride(0), C2.data_ptr(), C2.stride(0), _ptr(A.ws), 0 if A.ws is None else A.ws.numel(),
+            A.nslots, flags, row_gid.data_ptr(), col_gid.data_ptr(), int(seed) & 0xFFFFFFFFFFFFFFFF, step.data_ptr(), int(layer),
+            int(thr), self._stream())
+        if rc == _lib.PGCN_EUNSUPPORTED:
+            return False
+        _lib.check(rc, "pgcn_gat_attndrop_forward2_f32")
+        return True
+
+    def gat_attndrop_grad(self, AT: DeviceCSR, rowstat: torch.Tensor, s2: torch.Tensor, slope: float, B: torch.Tensor,
+                          Z: torch.Tensor, t: torch.Tensor, C: torch.Tensor, heads: int, d: int, row_gid: torch.Tensor,
+                          col_gid: torch.Tensor, seed: int, step: torch.Tensor, layer: int, thr: int, accumulate: bool = False) -> bool:
+        """``spmm_heads_grad`` (no ``de``) in standard mode under attention dropout (pgcn_gat_attndrop_grad_f32), on the TRANSPOSED
+        structure: C[:, :F] (+)= sum_i alpha'_ij B_i, C[:, F:F+heads] (+)= ds2_j = sum_i (c'_ij <B_i, Z_j> - c_ij t_i).  ``row_gid``: the
+        global ids of AT's rows (the neighbours gj), ``col_gid``: of its columns (the attending vertices gi).  False = shape not
+        covered."""
+        F = heads * d
+        hl = d // 4
+        if d % 4 or hl < 8 or hl & (hl - 1) or F > 256 or not 1 <= heads <= 8:
+            return False
+        pw = F + (heads + 3) // 4 * 4
+        self._check_rows(s2, AT.nrows, heads, "s2")
+        self._check_rows(t, AT.ncols, heads, "t")
+        if not (rowstat.is_cuda and rowstat.dtype is torch.float32 and rowstat.is_contiguous()
+                and rowstat.numel() == AT.ncols * heads * 4):
+            raise _lib.PgcnError("rowstat must be a contiguous fp32 [ncols, heads, 4] CUDA tensor")
+        self._check_dense(B, AT.ncols, "B")
+        self._check_dense(Z, AT.nrows, "Z")
+        self._check_dense(C, AT.nrows, "C")
+        if B.shape[1] < F or Z.shape[1] < F or C.shape[1] < pw or AT.row_map is not None or t.stride(0) != heads:
+            raise _lib.PgcnError("B / Z narrower than heads * d, C narrower than heads * d + heads (rounded up to 4), "
+                                 "t not contiguous, or a compact-row structure")
+        self._check_attn_mask(AT, row_gid, col_gid, step, layer, thr)
+        if AT.col.numel() == 0:
+            if not accumulate:
+                C[:AT.nrows, :pw].zero_()
+            return True
+        need = AT.nslots * pw
+        if need and (AT.ws is None or AT.ws.numel() < need):
+            AT.ws = torch.empty(need, dtype=torch.float32, device=self.device)
+            AT.launch_cache.clear()
+        flags = _lib.SPMM_ACCUMULATE if accumulate else 0
+        rc = self.lib.pgcn_gat_attndrop_grad_f32(
+            AT.rowptr.data_ptr(), AT.col.data_ptr(), rowstat.data_ptr(), s2.data_ptr(), s2.stride(0), slope, heads, d,
+            AT.nrows, _ptr(AT.tasks), AT.ntasks, AT.seg, AT.nslices, _ptr(AT.fix), AT.nfix, B.data_ptr(), B.stride(0),
+            Z.data_ptr(), Z.stride(0), t.data_ptr(), C.data_ptr(), C.stride(0), _ptr(AT.ws),
+            0 if AT.ws is None else AT.ws.numel(), AT.nslots, flags, row_gid.data_ptr(), col_gid.data_ptr(),
+            int(seed) & 0xFFFFFFFFFFFFFFFF, step.data_ptr(), int(layer), int(thr), self._stream())
+        if rc == _lib.PGCN_EUNSUPPORTED:
+            return False
+        _lib.check(rc, "pgcn_gat_attndrop_grad_f32")
+        return True
+
     # -- the dense blocks of an attention pattern (pgcn_gat_blocks.hip, r06) ------------------------------------------
     @staticmethod
     def gat_block_bits(h3) -> torch.Tensor:
