@@ -519,6 +519,61 @@ int pgcn_gat_attndrop_grad_f32(const int64_t *rowptr, const int32_t *col, const 
                                const int32_t *row_gid, const int32_t *col_gid, uint64_t seed, const int64_t *step,
                                int32_t layer, uint32_t thr, pgcn_stream_t stream);
 
+/* ---- GATv2: dynamic attention (Brody, Alon, Yahav, ICLR 2022; no counterpart in the reference, whose PGAT.py:144-149 is the static score)
+ * Per layer with `heads` heads of width d, F = heads * d, on the stored entries (i, j) of a pattern structure ("i attends to j"):
+ *   e_ijk     = sum_c a[c][k] * LeakyReLU(Zt[i][k d + c] + Zs[j][k d + c])      a: [d][heads], contiguous; LeakyReLU(x) = x > 0 ? x : slope x
+ *   alpha_i.k = softmax of e_i.k over the stored entries of row i (the row's maximum subtracted)
+ *   out_i     = sum_j alpha_ij Zs_j                                             pgcn_spmm_heads_f32 on the alpha planes, unchanged
+ *   de_ijk    = alpha_ijk (<dOut[i][k d ..], Zs[j][k d ..]> - t[i][k]),         t_ik = <dOut_ik, out_ik>; formed as alpha_ijk (q_ijk - T_ik),
+ *               q_ijk = <dOut_ik, Zs_jk - out_ik>, T_ik = sum_j alpha_ijk q_ijk from THE SAME q (two passes): the rows of de sum to
+ *               zero to rounding, so an error shared by a row (the rounding of t or out) cannot come back through dZt and da
+ *   dZt[i][k d + c] = sum_j de_ijk a[c][k] LReLU'(x_ijkc),   x_ijkc = Zt[i][k d + c] + Zs[j][k d + c],   LReLU'(x) = x > 0 ? 1 : slope
+ *   dZs[j][k d + c] = sum_i (de_ijk a[c][k] LReLU'(x_ijkc) + alpha_ijk dOut[i][k d + c])
+ *   da[c][k]        = sum_ij de_ijk LReLU(x_ijkc)
+ * The score does not split into a term of i and a term of j, so scores, alpha and de are PLANES: head-major [heads][plane stride] in the
+ * storage order of `col`, the layout pgcn_spmm_heads_f32 consumes.  tasks / ntasks / seg / nslices / fix / nfix / nslots: the plan of
+ * pgcn_spmm_plan_host on the same structure (tasks == NULL: one task per row).  One wave per task, the task's own row and a lane's four
+ * elements of `a` in registers, the other end's rows gathered in batches of 8; rows cut by the plan go through slot rows of F floats and
+ * pgcn_spmm_fixup_f32.  Every sum runs in a fixed order, no atomics: two calls give the same bits.  Nothing is written beyond column F of
+ * a row.  PGCN_EUNSUPPORTED unless heads is 1 .. 8, d is 32, 64, 128 or 256, heads * d <= 256, the row operands are 16-byte aligned and
+ * their leading dimensions multiples of 4 (callers then compose the layer from tensor operations).
+ *
+ * pgcn_gatv2_scores_f32:    E[k][p] = e of entry p and head k.  Zt: rows of the structure, Zs: its columns.  Every entry is written by
+ *                           the one task that owns it.
+ * pgcn_gatv2_softmax_f32:   E -> alpha in place, over the row lists of pgcn_gat_edge_softmax_f32 (a wave per listed row, a 256-thread
+ *                           workgroup per row of rows_block); an empty row writes nothing.  Any heads >= 1.
+ * pgcn_gatv2_grad_rows_f32: over the FORWARD structure (row i owns the work), two passes: writes the de planes, dZt (+)= (flags:
+ *                           PGCN_SPMM_ACCUMULATE) and da (overwritten; THIS structure's sum).  out: the forward's output rows
+ *                           (nrows x ldout, read).  t_ws: nrows x heads floats of scratch, the T above (written by pass 1, read by
+ *                           pass 2).  da_ws: pgcn_gatv2_da_ws_elems(...) floats of scratch -- one row of F partial sums per
+ *                           workgroup, added in index order by two small launches.
+ * pgcn_gatv2_grad_cols_f32: over the TRANSPOSED structure (row j owns the work, its columns are the attending i): alpha_t / de_t are the
+ *                           planes in ITS storage order (pgcn_csr_permute_f32 with the graph's permutation); Zs: rows of the transposed
+ *                           structure, Zt / dOut: its columns.  dZs (+)= (PGCN_SPMM_ACCUMULATE).
+ * pgcn_gatv2_da_ws_elems:   floats of da_ws for that plan (-1: bad arguments).  Host only.                                            */
+int pgcn_gatv2_scores_f32(const int64_t *rowptr, const int32_t *col, int64_t nrows, const int32_t *tasks, int64_t ntasks,
+                          const int64_t *seg, int32_t nslices, const float *Zt, int64_t ldt, const float *Zs, int64_t lds,
+                          const float *a, int32_t heads, int32_t d, float slope, float *E, int64_t plane_stride,
+                          pgcn_stream_t stream);
+int pgcn_gatv2_softmax_f32(const int64_t *rowptr, int64_t nrows, const int32_t *rows_wave, int64_t nrows_wave,
+                           const int32_t *rows_block, int64_t nrows_block, int32_t heads, float *E, int64_t plane_stride,
+                           pgcn_stream_t stream);
+int64_t pgcn_gatv2_da_ws_elems(int64_t nrows, const int32_t *tasks, int64_t ntasks, const int64_t *seg, int32_t nslices,
+                               int32_t heads, int32_t d);
+int pgcn_gatv2_grad_rows_f32(const int64_t *rowptr, const int32_t *col, int64_t nrows, const int32_t *tasks, int64_t ntasks,
+                             const int64_t *seg, int32_t nslices, const int32_t *fix, int64_t nfix, const float *Zt, int64_t ldt,
+                             const float *Zs, int64_t lds, const float *a, const float *alpha, int64_t alpha_stride,
+                             const float *dOut, int64_t ldo, const float *out, int64_t ldout, float *t_ws, int32_t heads,
+                             int32_t d, float slope, float *de, int64_t de_stride, float *dZt, int64_t ldz, float *da,
+                             float *partial_ws, int64_t partial_ws_elems, int64_t nslots, float *da_ws, int64_t da_ws_elems,
+                             uint32_t flags, pgcn_stream_t stream);
+int pgcn_gatv2_grad_cols_f32(const int64_t *rowptr, const int32_t *col, int64_t nrows, const int32_t *tasks, int64_t ntasks,
+                             const int64_t *seg, int32_t nslices, const int32_t *fix, int64_t nfix, const float *Zs, int64_t lds,
+                             const float *Zt, int64_t ldt, const float *dOut, int64_t ldo, const float *a, const float *alpha_t,
+                             int64_t alpha_stride, const float *de_t, int64_t de_stride, int32_t heads, int32_t d, float slope,
+                             float *dZs, int64_t ldz, float *partial_ws, int64_t partial_ws_elems, int64_t nslots, uint32_t flags,
+                             pgcn_stream_t stream);
+
 /* The dense 512 x 128 BLOCKS of the attention pattern on the bf16 matrix cores (r06, pgcn_gat_blocks.hip): the entries inside the
  * listed blocks of the products above, with the weights computed in registers from the same statistics and split into three bf16
  * planes (fp32 accuracy, as pgcn_spmm_dense_bf16x3_f32).  work / blk_img / panel_list / npanels / image_ws: the block structure and

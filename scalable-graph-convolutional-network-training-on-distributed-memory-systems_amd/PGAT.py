@@ -162,6 +162,7 @@ class Comm(torch.autograd.Function):
 
 # ---- the tail of a layer: head mean, bias, ELU and dropout (csrc/pgcn_gat_tail.hip) -------------------------------------------------
 ACTIVATIONS = (None, "elu")
+ATTENTIONS = ("v1", "v2")
 
 
 def _f32_inv(x):
@@ -266,10 +267,15 @@ class PGAT(nn.Module):
     (``_GatTail``).  ``attn_dropout`` drops the NORMALISED attention coefficients in training mode, per entry and head and after the
     softmax over the whole row (the GAT paper's p = 0.6): alpha' = keep ? alpha / (1 - p) : 0, keep a pure function of (seed, step,
     layer, head, the two GLOBAL vertex ids) -- csrc/pgcn_attndrop.h, ``gat.GatEngine``; it needs ``state`` like ``dropout``, and an
-    evaluation pass makes exactly the calls of a layer without it.  Not here: norms, residual links."""
+    evaluation pass makes exactly the calls of a layer without it.  Not here: norms, residual links.
+
+    ``attention="v2"``: the DYNAMIC score of GATv2 (Brody, Alon, Yahav, ICLR 2022), e_ijk = sum_c a[c,k] LeakyReLU(Zt[i,k,c] +
+    Zs[j,k,c]) with Zs = H Ws^T (``linear``: the messages and the neighbour's side of the score) and Zt = H Wt^T (``linear_t``: the
+    attending vertex's side; ``share_weights=True``: Wt is Ws, one projection); ``attention`` then has shape (d, K).  The tail is the
+    same.  Not with the reference mode, not with ``attn_dropout``.  ``attention="v1"`` (the default) is the layer of before."""
 
     def __init__(self, A, in_features, out_features, heads=None, bias=False, activation=None, concat=True, dropout=0.0, layer=0,
-                 state=None, attn_dropout=0.0):
+                 state=None, attn_dropout=0.0, attention="v1", share_weights=False):
         super(PGAT, self).__init__()
         K = globals()["heads"] if heads is None else heads
         if out_features % K:
@@ -282,8 +288,22 @@ class PGAT(nn.Module):
         self.A = A
         self.send_map = send_map
         self.recv_map = recv_map
+        if attention not in ATTENTIONS:
+            raise ValueError("attention takes %s, got %r" % (" | ".join(ATTENTIONS), attention))
+        self.version, self.share_weights = attention, bool(share_weights)
+        if self.share_weights and attention != "v2":
+            raise ValueError("share_weights needs attention='v2': the v1 layer has one projection")
+        if attention == "v2" and A is not None and getattr(A, "mode", "standard") == "reference":
+            raise ValueError("the reference layer has the static score only (attention='v2' needs mode='standard')")
+        if attention == "v2" and float(attn_dropout) > 0.0:
+            raise ValueError("attention='v2' with attn_dropout is not implemented: use attention='v1', or attn_dropout=0")
         self.linear = nn.Linear(in_features, out_features, bias=False)
-        self.attention = nn.Parameter(torch.empty(size=(2 * out_features // K, K)))   # (2F, 1) for one head, :127
+        if attention == "v2":
+            if not self.share_weights:
+                self.linear_t = nn.Linear(in_features, out_features, bias=False)
+            self.attention = nn.Parameter(torch.empty(size=(out_features // K, K)))
+        else:
+            self.attention = nn.Parameter(torch.empty(size=(2 * out_features // K, K)))   # (2F, 1) for one head, :127
         self._state = None
         if activation not in ACTIVATIONS:
             raise ValueError("activation takes None | 'elu', got %r" % (activation,))
@@ -312,10 +332,34 @@ class PGAT(nn.Module):
     def reset_parameters(self):
         gain = nn.init.calculate_gain('relu')
         nn.init.xavier_normal_(self.linear.weight, gain=gain)
+        if self.version == "v2" and not self.share_weights:
+            nn.init.xavier_normal_(self.linear_t.weight, gain=gain)
         nn.init.xavier_normal_(self.attention, gain=gain)
+
+    @property
+    def projected_width(self):
+        """Columns of the layer's ONE dense product: [Z | z2 | z1] (v1), [Zs | Zt] (v2), Zs (v2, shared weights)."""
+        if self.version == "v2":
+            return self.out_features * (1 if self.share_weights else 2)
+        return self.out_features + 2 * self.heads
+
+    def _forward_v2(self, H):
+        K, d = self.heads, self.out_features // self.heads
+        F = self.out_features
+        if self.share_weights:
+            Zs = Zt = _pgcn._LinearNoBias.apply(H, self.linear.weight)
+        else:                                # both projections as ONE product over the stacked weight: n x 2F = [Zs | Zt]
+            ZZ = _pgcn._LinearNoBias.apply(H, torch.cat([self.linear.weight, self.linear_t.weight], 0))
+            Zs, Zt = ZZ[:, :F], ZZ[:, F:]
+        st = self._state
+        if st is None or st.busy or (st.heads, st.d) != (K, d):
+            st = self._state = self.A.new_layer_state(K, d)
+        return _gat.GatV2Aggregate.apply(self.A, st, Zt, Zs, self.attention)
 
     def forward(self, H):
         K, d = self.heads, self.out_features // self.heads
+        if self.version == "v2":
+            return self._tail(self._forward_v2(H), K, d)
         # Z = self.linear(H) (:140), z1 = Z a1 (:141), z2 = Z a2 (:142) as ONE product: z_k = Z_k a_k = H (W_k^T a_k), so the 2K
         # projection columns ride along as 2K more rows of the weight (K x in each, a tiny product of their own; autograd carries
         # their gradients back to W and the attention vectors).  The per-head einsums they replace ran as skinny batched GEMMs:
@@ -333,6 +377,9 @@ class PGAT(nn.Module):
         if self._attn_drop is not None:                                 # (a layer without the option never touches the field)
             st.drop = self._attn_drop if self.training else None
         out = _gat.GatAggregatePacked.apply(self.A, st, ZS)             # :144-149 on the stored entries
+        return self._tail(out, K, d)
+
+    def _tail(self, out, K, d):
         if not self._has_tail:
             return out
         # (its own output: GatEngine.backward reads the state's `out` buffer, so the tail never runs in place here)
@@ -450,12 +497,14 @@ def _barrier():
 
 
 def _architecture(fin, classes, nlayers, task=None, hidden=None, out_heads=None, dropout=0.0, dropout_seed=0, bias=None,
-                  attn_dropout=0.0, **_):
+                  attn_dropout=0.0, attention=None, share_weights=None, **_):
     """checkpoint.architecture of the model ``_train_on_data`` builds from these arguments (and this module's ``heads``)."""
     widths = [int(fin)] + [int(8 * heads if hidden is None else hidden)] * (nlayers - 1) + [int(classes)]
     # (the initial parameters are drawn under dropout_seed, with or without dropout: the record keeps it in the dropout case only,
     # where it also seeds the masks -- a resumed run draws no initial parameters)
     extra = {"attn_dropout": float(attn_dropout)} if attn_dropout and float(attn_dropout) > 0.0 else {}
+    if attention not in (None, "v1"):                    # (v1: the record of before)
+        extra.update(attention=str(attention), share_weights=bool(share_weights))
     return _checkpoint.architecture(widths, task, dropout, dropout_seed, bias=bias, heads=heads,
                                     out_heads=1 if out_heads is None else out_heads, **extra)
 
@@ -463,10 +512,12 @@ def _architecture(fin, classes, nlayers, task=None, hidden=None, out_heads=None,
 TASKS, OPTIMIZERS = _pgcn.TASKS, _pgcn.OPTIMIZERS
 
 
-def build_classifier(A, fin, classes, nlayers, hidden, K, out_heads=1, dropout=0.0, bias=False, state=None, attn_dropout=0.0):
+def build_classifier(A, fin, classes, nlayers, hidden, K, out_heads=1, dropout=0.0, bias=False, state=None, attn_dropout=0.0,
+                     attention="v1", share_weights=False):
     """The model of the GAT paper on the engine ``A``: layers 0 .. L-2 are K concatenated heads of hidden / K columns, ELU, dropout
     on their output; the last layer averages ``out_heads`` heads of ``classes`` columns.  ``attn_dropout``: dropout on the attention
-    coefficients of EVERY layer, the last one included, as in the paper.  ``widths``: the layers' input widths and the class count."""
+    coefficients of EVERY layer, the last one included, as in the paper.  ``attention="v2"`` (and ``share_weights``): every layer takes
+    the dynamic score of GATv2 (class PGAT).  ``widths``: the layers' input widths and the class count."""
     if hidden % K:
         raise ValueError("hidden (%d) must be divisible by the number of heads (%d)" % (hidden, K))
     widths = [fin] + [hidden] * (nlayers - 1) + [classes]
@@ -475,6 +526,8 @@ def build_classifier(A, fin, classes, nlayers, hidden, K, out_heads=1, dropout=0
     if attn_dropout and float(attn_dropout) > 0.0:       # (absent: the constructor calls of before)
         extra["attn_dropout"] = float(attn_dropout)
         last = {"layer": nlayers - 1, "state": state}
+    if attention != "v1" or share_weights:               # (absent: the constructor calls of before)
+        extra.update(attention=attention, share_weights=bool(share_weights))
     layers = [PGAT(A, widths[i], hidden, heads=K, activation="elu", dropout=dropout, layer=i, state=state, **extra)
               for i in range(nlayers - 1)]
     layers.append(PGAT(A, widths[nlayers - 1], out_heads * classes, heads=out_heads, concat=False, **extra, **last))
@@ -483,7 +536,7 @@ def build_classifier(A, fin, classes, nlayers, hidden, K, out_heads=1, dropout=0
 
 def _train_on_data(A, n, nlayers, features, labels, split, task=None, hidden=None, out_heads=None, epochs=None, lr=None,
                    eval_every=None, dropout=0.0, dropout_seed=0, bias=None, weight_decay=None, decoupled_decay=None, optimizer=None,
-                   save=None, load=None, predict=None, proba=None, control=None, attn_dropout=0.0):
+                   save=None, load=None, predict=None, proba=None, control=None, attn_dropout=0.0, attention=None, share_weights=None):
     """The loop of ``run`` on real inputs, the scheme of PGCN._train_on_data (``control``: ``nodeloss.Control``, as there):
     constant features, Adam, the masked loss over the train
     rows (``task="multilabel"``: the masked binary cross entropy and micro-F1).  Reports every ``eval_every`` epochs: without
@@ -513,9 +566,11 @@ def _train_on_data(A, n, nlayers, features, labels, split, task=None, hidden=Non
     with torch.random.fork_rng(devices=[]):        # every rank draws the SAME initial parameters, from the seed of the command line:
         torch.manual_seed(int(dropout_seed))       # -s 1 and -s P then train one model (the ranks' mean of equal draws is that draw)
         model, widths = build_classifier(A, data.fin, data.classes, nlayers, hidden, K, out_heads, dropout, bool(bias), state,
-                                         **({"attn_dropout": attn_dropout} if attn_dropout > 0.0 else {}))
+                                         **({"attn_dropout": attn_dropout} if attn_dropout > 0.0 else {}),
+                                         **({"attention": attention, "share_weights": bool(share_weights)}
+                                            if attention not in (None, "v1") or share_weights else {}))
     for i, m in enumerate(model):
-        _pgcn.tune_dense_gemms(A.part.n_local, widths[i], device, m.out_features + 2 * m.heads)
+        _pgcn.tune_dense_gemms(A.part.n_local, widths[i], device, m.projected_width)
     model = model.to(device)
     initiliaze_parameters(model)
     fused, opt = _nodeloss.make_optimizer(model.parameters(), optimizer, lr, weight_decay, bool(decoupled_decay),
@@ -525,7 +580,8 @@ def _train_on_data(A, n, nlayers, features, labels, split, task=None, hidden=Non
 
     first, history, best, hooks = 0, [], None, None
     if save is not None or load is not None or predict is not None or proba:
-        arch = _architecture(data.fin, data.classes, nlayers, kind, hidden, out_heads, dropout, dropout_seed, bias, attn_dropout)
+        arch = _architecture(data.fin, data.classes, nlayers, kind, hidden, out_heads, dropout, dropout_seed, bias, attn_dropout,
+                             attention, share_weights)
         hooks = _checkpoint.Hooks("PGAT", arch, model, fused, opt, state, save, load, predict, proba, myrank, _barrier)
         first, history, best = hooks.resume()
     last = first + epochs - 1
@@ -580,14 +636,16 @@ def _train_on_data(A, n, nlayers, features, labels, split, task=None, hidden=Non
 def run(rank, size, nlayers, nfeatures, path_A, path_partvec, backend, epochs=None, features=None, labels=None, split=None, **data):
     """PGAT.py:165-233.  ``features`` / ``labels`` / ``split`` (.npy files in global vertex order, nodedata.py; all three or none):
     train the classifier of ``build_classifier`` on them instead of the synthetic loop (``_train_on_data`` takes the other keyword
-    arguments: task, hidden, out_heads, lr, eval_every, dropout, dropout_seed, attn_dropout, bias, weight_decay, decoupled_decay, optimizer, and
+    arguments: task, hidden, out_heads, lr, eval_every, dropout, dropout_seed, attn_dropout, attention, share_weights, bias, weight_decay, decoupled_decay, optimizer, and
     save, load, predict, proba -- checkpoint.py, as in PGCN.run -- and the options of nodeloss.CONTROL: clip_norm, lr_schedule,
     lr_warmup, lr_min, lr_step, lr_gamma, lr_horizon, patience, as in PGCN.run); the returned model carries ``history``, ``best`` and
     ``widths``."""
     global myrank, world_size, send_map, recv_map, device, X, recv_buffers, send_buffers
     files = [v for v in (features, labels, split) if v is not None]
+    synthetic = {k: data.pop(k) for k in ("attention", "share_weights") if k in data and not files}     # (allowed without files)
     if len(files) not in (0, 3) or (data and not files):
         raise ValueError("features, labels and split go together, and the other options need them")
+    data.update(synthetic)
     if data.get("task") not in (None,) + TASKS:
         raise ValueError("task takes %s, got %r" % (" | ".join(TASKS), data.get("task")))
     if data.get("optimizer") not in (None,) + OPTIMIZERS:
@@ -602,6 +660,14 @@ def run(rank, size, nlayers, nfeatures, path_A, path_partvec, backend, epochs=No
             _dropout.threshold(data["attn_dropout"])
         except (TypeError, ValueError):
             raise ValueError("attn_dropout takes a probability in [0, 1), got %r" % (data["attn_dropout"],))
+    if data.get("attention") not in (None,) + ATTENTIONS:
+        raise ValueError("attention takes %s, got %r" % (" | ".join(ATTENTIONS), data.get("attention")))
+    if data.get("share_weights") and data.get("attention") != "v2":
+        raise ValueError("share_weights needs attention='v2': the v1 layer has one projection")
+    if data.get("attention") == "v2" and mode == "reference":
+        raise ValueError("the reference layer has the static score only: attention='v2' needs standard mode")
+    if data.get("attention") == "v2" and float(data.get("attn_dropout") or 0.0) > 0.0:
+        raise ValueError("attention='v2' with attn_dropout is not implemented: use attention='v1', or attn_dropout=0")
     control = {k: data.pop(k) for k in list(data) if k in _nodeloss.CONTROL}
     control = {k: v for k, v in control.items() if v is not None}
     if control:            # each value, what goes together, the horizon against the warm-up: before any collective
@@ -643,7 +709,8 @@ def run(rank, size, nlayers, nfeatures, path_A, path_partvec, backend, epochs=No
     labels = owned % nfeatures                                                                         # :202
 
     _pgcn.tune_dense_gemms(A.part.n_local, nfeatures, device)     # library GEMM choice for H.W^T made in set-up
-    model = nn.Sequential(*[PGAT(A, nfeatures, nfeatures) for _ in range(nlayers)])
+    v2 = {"attention": "v2", "share_weights": bool(data.get("share_weights"))} if data.get("attention") == "v2" else {}
+    model = nn.Sequential(*[PGAT(A, nfeatures, nfeatures, **v2) for _ in range(nlayers)])
     model = model.to(device)
     initiliaze_parameters(model)
     optimizer = torch.optim.Adam(model.parameters(), lr=1e-3)
@@ -702,6 +769,7 @@ def main(argv):
     global path_A, path_partvec, mode, heads
     backend, size, nlayers, nfeatures = "nccl", 1, 1, 4
     data = {}          # the node-classification options that were given (run's keyword arguments)
+    score = {}         # --attention / --share-weights: allowed with and without --features
 
     def refuse(text):
         print(text, flush=True)
@@ -711,7 +779,7 @@ def main(argv):
         opts, args = getopt.getopt(argv, "a:p:b:s:l:f:", ["mode=", "heads=", "features=", "labels=", "split=", "task=", "hidden=",
                                                           "out-heads=", "epochs=", "lr=", "eval-every=", "dropout=", "dropout-seed=", "attn-dropout=",
                                                           "bias", "weight-decay=", "adamw", "optimizer=", "save=", "load=", "predict=",
-                                                          "proba"] + [f[2:] + "=" for f in _nodeloss.CONTROL_FLAGS.split(", ")])
+                                                          "proba", "attention=", "share-weights"] + [f[2:] + "=" for f in _nodeloss.CONTROL_FLAGS.split(", ")])
     except getopt.GetoptError:
         print("a:p:b:", flush=True)
         sys.exit(2)
@@ -746,6 +814,12 @@ def main(argv):
                 _dropout.threshold(data["attn_dropout"])
             except ValueError:
                 refuse("--attn-dropout takes a probability in [0, 1), got %r" % arg)
+        elif opt == '--attention':     # v1: the static score of GAT (the default) | v2: the dynamic score of GATv2 (class PGAT)
+            if arg not in ATTENTIONS:
+                refuse("--attention takes %s, got %r" % ("|".join(ATTENTIONS), arg))
+            score["attention"] = arg
+        elif opt == '--share-weights':  # with --attention v2: one projection for both sides of the score
+            score["share_weights"] = True
         elif opt == '--dropout-seed':
             try:
                 data["dropout_seed"] = int(arg)
@@ -793,6 +867,14 @@ def main(argv):
             mode = arg
         elif opt == '--heads':
             heads = int(arg)
+    if score.get("share_weights") and score.get("attention") != "v2":
+        refuse("--share-weights needs --attention v2: the v1 layer has one projection")
+    if score.get("attention") == "v2" and mode == "reference":
+        refuse("--mode reference has the static score only: --attention v2 needs --mode standard")
+    if score.get("attention") == "v2" and data.get("attn_dropout", 0.0) > 0.0:
+        refuse("--attention v2 with --attn-dropout is not implemented: use --attention v1, or leave --attn-dropout out")
+    if score.get("attention") == "v1":
+        score.pop("attention")                          # (the default: the call of before)
     files = [k for k in ("features", "labels", "split") if k in data]
     if data and len(files) != 3:
         refuse("--features, --labels and --split go together (and --task, --hidden, --out-heads, --epochs, --lr, --eval-every, --dropout, "
@@ -818,6 +900,7 @@ def main(argv):
             refuse(str(e))
     if data and heads >= 1 and data.get("hidden", 8 * heads) % heads:
         refuse("--hidden takes a multiple of --heads (%d), got %r" % (heads, str(data["hidden"])))
+    data.update(score)
     env_rank = os.environ.get("SLURM_PROCID", os.environ.get("RANK"))
     mp.set_start_method("spawn", force=True)
     if env_rank is not None:

@@ -82,6 +82,15 @@ SIGNATURES = {
     "pgcn_gat_attndrop_grad_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, ctypes.c_float, _i32, _i32, _i64, _vp, _i64,
                                                   _vp, _i32, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _i64,
                                                   _u32, _vp, _vp, ctypes.c_uint64, _vp, _i32, _u32, _vp]),
+    "pgcn_gatv2_scores_f32": (ctypes.c_int, [_vp, _vp, _i64, _vp, _i64, _vp, _i32, _vp, _i64, _vp, _i64, _vp, _i32, _i32, ctypes.c_float,
+                                             _vp, _i64, _vp]),
+    "pgcn_gatv2_softmax_f32": (ctypes.c_int, [_vp, _i64, _vp, _i64, _vp, _i64, _i32, _vp, _i64, _vp]),
+    "pgcn_gatv2_da_ws_elems": (_i64, [_i64, _vp, _i64, _vp, _i32, _i32, _i32]),
+    "pgcn_gatv2_grad_rows_f32": (ctypes.c_int, [_vp, _vp, _i64, _vp, _i64, _vp, _i32, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp,
+                                                _i64, _vp, _i64, _vp, _i32, _i32, ctypes.c_float, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _i64, _vp, _i64,
+                                                _u32, _vp]),
+    "pgcn_gatv2_grad_cols_f32": (ctypes.c_int, [_vp, _vp, _i64, _vp, _i64, _vp, _i32, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp,
+                                                _i64, _vp, _i64, _i32, _i32, ctypes.c_float, _vp, _i64, _vp, _i64, _i64, _u32, _vp]),
     "pgcn_gat_blocks_forward_f32": (ctypes.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i64, ctypes.c_float, _i32, _i32, _i64, _i64,
                                                    _vp, _i64, _vp, _i64, _vp, _i64, _i64, _vp]),
     "pgcn_gat_blocks_backward_f32": (ctypes.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _i64, ctypes.c_float, _i32,

@@ -37,12 +37,13 @@ import torch
 from . import nodedata as _nodedata
 
 FORMAT_VERSION = 1
-ARCH_FIELDS = ("task", "layers", "widths", "norm", "root_weight", "bias", "residual", "heads", "out_heads", "dropout", "attn_dropout", "dropout_seed", "aggr",
+ARCH_FIELDS = ("task", "layers", "widths", "norm", "root_weight", "bias", "residual", "heads", "out_heads", "dropout", "attn_dropout", "attention", "share_weights", "dropout_seed", "aggr",
                "drop_edge", "softmax_beta", "propagate", "dense_layers")
 
 
 def architecture(widths, task, dropout=0.0, dropout_seed=0, norm=None, root_weight=None, bias=None, residual=None, heads=None,
-                 out_heads=None, aggr=None, propagate=None, dense_layers=None, drop_edge=None, softmax_beta=None, attn_dropout=None):
+                 out_heads=None, aggr=None, propagate=None, dense_layers=None, drop_edge=None, softmax_beta=None, attn_dropout=None, attention=None,
+                 share_weights=None):
     """The plain-value record of what a model was built from; two models of equal records have state dicts of equal keys and shapes,
     and draw the same dropout masks.  ``aggr``: the key exists only for "max" -- a record of the weighted sum is the record of before,
     and compares equal to every checkpoint written without the key.  Likewise ``propagate`` ((K, alpha): the key holds [K, alpha]
@@ -51,7 +52,9 @@ def architecture(widths, task, dropout=0.0, dropout_seed=0, norm=None, root_weig
     positive; the mask's seed is ``dropout_seed``, recorded when either probability is positive.  ``softmax_beta``: the key holds the
     softmax aggregation's beta (a float, 0.0 included) only when one is given.  ``attn_dropout``: the key holds the GAT layers' attention
     dropout probability only when it is positive (its mask, too, is keyed by ``dropout_seed``); it is compared before the seed, so a
-    checkpoint loaded under another value is refused in its name."""
+    checkpoint loaded under another value is refused in its name.  ``attention`` / ``share_weights``: the keys exist only for the GATv2
+    layers ("v2", and whether the two projections are one); a record without them is a v1 model, so a v1 checkpoint under a v2 command
+    line, or the reverse, is refused in the name of ``attention``."""
     arch = {"widths": [int(w) for w in widths], "layers": len(widths) - 1, "task": str(task or "single"),
             "norm": "none" if norm in (None, "none") else str(norm), "root_weight": bool(root_weight), "bias": bool(bias),
             "residual": bool(residual), "heads": None if heads is None else int(heads),
@@ -70,6 +73,8 @@ def architecture(widths, task, dropout=0.0, dropout_seed=0, norm=None, root_weig
         arch["softmax_beta"] = float(softmax_beta)
     if float(attn_dropout or 0.0) > 0.0:
         arch["attn_dropout"] = float(attn_dropout)
+    if attention not in (None, "v1"):
+        arch["attention"], arch["share_weights"] = str(attention), bool(share_weights)
     return arch
 
 

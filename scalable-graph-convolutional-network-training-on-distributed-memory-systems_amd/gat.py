@@ -34,6 +34,19 @@ two methods, shapes the kernels refuse -- as tensor operations over the entry li
     out_i = sum_j alpha'_ij Z_j,  V_i = sum_j c'_ij Z_j,  C_i = sum_j c_ij (UNMASKED),  t_i = <dOut_i, out_i>,
     dZ_j = sum_i alpha'_ij dOut_i,  ds2_j = sum_i (c'_ij dp_ij - c_ij t_i),  ds1_i = <dOut_i, V_i> - t_i C_i.
 Without a context, or at threshold 0, every call is the one made before.
+
+GATv2 (``GatEngine.forward_v2`` / ``backward_v2``, ``GatV2Aggregate``; standard mode): the DYNAMIC score e_ijk = sum_c a[c,k]
+LeakyReLU(Zt[i,k,c] + Zs[j,k,c]) of Brody, Alon, Yahav (ICLR 2022) in place of LeakyReLU(s1_i + s2_j).  It does not split into a term
+of i and a term of j, so nothing of the recomputing kernels applies: scores, alpha and de are head-major planes [K][nnz] in the storage
+order of ``fwd`` (csrc/pgcn_gatv2.hip).
+    forward   rows of Zs -> all-to-all-v -> panel Zc = [local ; halo], width F padded to 4 (no s2 column); Zt never leaves its rank
+              scores over the tasks of fwd (pgcn_gatv2_scores_f32), softmax in place (pgcn_gatv2_softmax_f32),
+              out = A_alpha . Zc (pgcn_spmm_heads_f32, unchanged).  Kept for the backward: the alpha planes (4K bytes per entry)
+    backward  over fwd, two passes: q = <dOut_i, Zs_j - out_i> and T_i = sum_j alpha q, then de = alpha (q - T), dZt, da (pgcn_gatv2_grad_rows_f32); alpha and de into the
+              transposed order (pgcn_csr_permute_f32); over bwd: dZs (pgcn_gatv2_grad_cols_f32); halo rows of dZs travel home and are
+              ADDED (the reverse all-to-all-v of the v1 path).  da is this rank's partial sum, like any weight gradient.
+The unsplit structures only: the pass waits for the halo rows.  CPU tensors, providers without the four methods and shapes the kernels
+refuse take the same arithmetic as tensor operations over the entry list (``_v2_forward`` / ``_v2_backward``).
 """
 from __future__ import annotations
 
@@ -177,6 +190,9 @@ class GatLayerState:
     drop: Optional[object] = None        # dropout.AttnDrop of the NEXT forward (the layer sets it in training mode), or None
     dropped: Optional[object] = None     # ... of the last forward, for its backward
     entries: Optional[tuple] = None      # the composed masked forward's (rows, cols, alpha', c', c), kept for its backward
+    Zt: Optional[torch.Tensor] = None    # GATv2: the target-side projection of the last forward_v2 (owned rows, never exchanged)
+    att: Optional[torch.Tensor] = None   # ... its attention parameter a [d, heads]
+    alpha_e: Optional[torch.Tensor] = None   # ... and, on the composed route, alpha per entry [nnz, heads] in double (None: the planes hold it)
 
 
 class GatEngine(BoundaryExchange):
@@ -234,6 +250,7 @@ class GatEngine(BoundaryExchange):
         self._scratch = {}
         self._gid_cache = {}
         self._entry_cache = None
+        self._v2_entries = None
         self.sliced_grad = _T.gat_sliced   # XCD-sliced edge gradient where the shape allows
         # the edge gradient over the balanced tasks of the SpMM plan (pgcn_gat_edge_grad_tasks_f32)
         self.task_grad = _T.gat_task_grad and hasattr(kernels, "gat_edge_grad_tasks")
@@ -577,6 +594,141 @@ class GatEngine(BoundaryExchange):
         dZc[:, F:F + K].index_add_(0, cols, de)
         return self._finish_backward(st, dOut, dZc, ds1, pack)
 
+    # -- GATv2: the dynamic score (csrc/pgcn_gatv2.hip) ---------------------------------------------------------------------------------
+    def _v2_kernels(self, K: int, d: int) -> bool:
+        return all(hasattr(self.k, m) for m in ("gatv2_scores", "gatv2_softmax", "gatv2_grad_rows", "gatv2_grad_cols", "csr_permute",
+                                                "spmm_heads")) and self.covers(K, d)
+
+    def _v2_entry_list(self):
+        if self._v2_entries is None:
+            rp = self.graph.fwd.rowptr.to(torch.int64).cpu()
+            rows = torch.repeat_interleave(torch.arange(self.n_local, dtype=torch.int64), rp[1:] - rp[:-1])
+            self._v2_entries = (rows.to(self.device), self.graph.fwd.col.to(torch.int64).to(self.device))
+        return self._v2_entries
+
+    def forward_v2(self, st: GatLayerState, Zt: torch.Tensor, Zs: torch.Tensor, a: torch.Tensor) -> torch.Tensor:
+        """out_i = sum_j alpha_ij Zs_j with alpha the softmax over row i of e_ijk = sum_c a[c,k] LeakyReLU(Zt[i,k,c] + Zs[j,k,c]).
+        Zt, Zs: [n_local, heads * d] of the owned rows (column slices of one projection are fine); a: [d, heads]."""
+        K, d = st.heads, st.d
+        F = K * d
+        n_p, n_h = self.n_local, self.n_halo
+        if self.mode_id != 0:
+            raise ValueError("GATv2 needs mode='standard': the reference layer has the static score only")
+        if st.drop is not None and st.drop.on:
+            raise ValueError("GATv2 with attention dropout is not implemented: use attention='v1' with attn_dropout, or attn_dropout=0")
+        if Zt.shape != (n_p, F) or Zs.shape != (n_p, F) or tuple(a.shape) != (d, K):
+            raise ValueError("expected Zt / Zs %s and a %s" % ((n_p, F), (d, K)))
+        Zt, a = Zt.detach(), a.detach().contiguous()
+        Fp = (F + 3) // 4 * 4
+        # ONE rank only: the projection itself is the gather panel (never written through).  A rank of several without halo rows still
+        # has its part in the all-to-all-v below -- its peers wait for it -- so it takes the copy-in branch like every other rank
+        if self.size == 1 and n_h == 0 and Zs.stride(1) == 1 and Zs.stride(0) % 4 == 0 and Zs.data_ptr() % 16 == 0 \
+                and Zs.dtype is torch.float32 and n_p > 0:
+            st.Zc = Zc = Zs.detach()
+            st.Zc_borrowed = True
+        else:
+            if st.Zc is None or st.Zc_borrowed or st.Zc.shape != (n_p + n_h, Fp):
+                st.Zc = torch.zeros((n_p + n_h, Fp), dtype=torch.float32, device=self.device)
+                st.Zc_borrowed = False
+            Zc = st.Zc
+            Zc[:n_p, :F].copy_(Zs)
+            if self.size > 1:                    # the rows of Zs only: Zt is row i's own
+                send = self._slab("gat_send", self.n_send, Fp)
+                self.k.gather_rows(Zc[:n_p], self.send_idx, send)
+                for w in self._exchange_all(send, self.round_send_off, Zc[n_p:], self.round_recv_off, Fp):
+                    w()
+        if Zt.stride(1) != 1:
+            Zt = Zt.contiguous()
+        out = torch.empty((n_p, F), dtype=torch.float32, device=self.device)
+        st.Zt, st.att, st.alpha_e, st.dropped, st.entries, st.fused = Zt, a, None, None, None, False
+        done = False
+        if self._v2_kernels(K, d):
+            if st.alpha is None or st.alpha.shape != (K, max(self.nnz, 1)):
+                st.alpha = torch.zeros((K, max(self.nnz, 1)), dtype=torch.float32, device=self.device)
+                st.fwd_heads = None
+            if self.k.gatv2_scores(self.fwd, Zt, Zc, a, self.slope, st.alpha, K, d):
+                self.k.gatv2_softmax(self.fwd, st.alpha, K)
+                if self.nnz == 0:
+                    out.zero_()
+                elif not self.k.spmm_heads(self.fwd, st.alpha, Zc, out, K, d):
+                    raise RuntimeError("the multi-head product refused a shape the GATv2 score kernel took")
+                done = True
+        if not done:
+            self._v2_forward(st, Zt, Zc, a, out)
+        st.out = out
+        return out
+
+    def backward_v2(self, st: GatLayerState, dOut: torch.Tensor):
+        """(dZt, dZs, da) of the last ``forward_v2`` for the owned rows; da [d, heads] is THIS rank's partial sum."""
+        K, d = st.heads, st.d
+        F = K * d
+        n_p, n_h = self.n_local, self.n_halo
+        Fp = (F + 3) // 4 * 4
+        dOut = dOut.contiguous()
+        dZc = self._slab("gat_dzs", n_p + n_h, Fp)[:n_p + n_h]
+        dZt = None
+        if st.alpha_e is None:
+            de = self._plane_scratch("v2_de", K)
+            dZt = torch.empty((n_p, F), dtype=torch.float32, device=self.device)
+            da = torch.empty((d, K), dtype=torch.float32, device=self.device)
+            if self.k.gatv2_grad_rows(self.fwd, st.Zt, st.Zc, st.att, st.alpha, dOut, st.out, self.slope, de, dZt, da, K, d):
+                alpha_t, de_t = self._plane_scratch("v2_alpha_t", K), self._plane_scratch("v2_de_t", K)
+                self.k.csr_permute(st.alpha, self.perm, alpha_t)
+                self.k.csr_permute(de, self.perm, de_t)
+                if not self.k.gatv2_grad_cols(self.bwd, st.Zc, st.Zt, dOut, st.att, alpha_t, de_t, self.slope, dZc, K, d):
+                    dZt = None
+            else:
+                dZt = None
+        if dZt is None:                          # the composed route, or a kernel refused operands its forward twin took
+            dZt, da = self._v2_backward(st, dOut, dZc)
+        if Fp > F:
+            dZc[:, F:].zero_()
+        if self.size > 1:                        # partial rows of dZs back to their owners, ADDED
+            back = self._slab("gat_send", self.n_send, Fp)
+            waits = self._exchange_all(dZc[n_p:], self.round_recv_off, back, self.round_send_off, Fp, tag="backward")
+            for r in range(self.rounds):
+                waits[r]()
+                self.k.spmm(self.unpack[r], back, dZc[:n_p], accumulate=True)
+        return dZt, dZc[:n_p, :F].clone(), da
+
+    # -- ... as tensor operations over the entry list (CPU tensors, other providers, shapes the kernels refuse) ------------------------
+    def _v2_forward(self, st: GatLayerState, Zt: torch.Tensor, Zc: torch.Tensor, a: torch.Tensor, out: torch.Tensor):
+        """The definition over the entry list, formed in DOUBLE and rounded once per output: this route is the fall-back and not the
+        hot path, and its sums over a row's entries (and, for da, over all entries) then add nothing to the layer's float32 error."""
+        K, d = st.heads, st.d
+        F, n_p = K * d, self.n_local
+        rows, cols = self._v2_entry_list()
+        f64 = torch.float64
+        Zj = Zc[:, :F].reshape(-1, K, d)[cols].to(f64)
+        x = Zt.reshape(n_p, K, d)[rows].to(f64) + Zj
+        e = (torch.where(x > 0, x, x * self.slope) * a.to(f64).t().unsqueeze(0)).sum(-1)
+        m = torch.full((n_p, K), -float("inf"), dtype=f64, device=e.device).scatter_reduce(0, rows.unsqueeze(1).expand(-1, K), e, "amax",
+                                                                                           include_self=True)
+        ex = torch.exp(e - m[rows])
+        D = torch.zeros((n_p, K), dtype=f64, device=e.device).index_add_(0, rows, ex)
+        st.alpha_e = ex / D[rows]                                              # (kept in double for the backward)
+        out.copy_(torch.zeros((n_p, K, d), dtype=f64, device=e.device).index_add_(0, rows, st.alpha_e.unsqueeze(-1) * Zj).view(n_p, F))
+
+    def _v2_backward(self, st: GatLayerState, dOut: torch.Tensor, dZc: torch.Tensor):
+        K, d = st.heads, st.d
+        F, n_p, n_h = K * d, self.n_local, self.n_halo
+        rows, cols = self._v2_entry_list()
+        f64 = torch.float64
+        alpha = st.alpha_e if st.alpha_e is not None else st.alpha[:, :self.nnz].t().to(f64)
+        G = dOut.view(n_p, K, d).to(f64)
+        Gi, Zj = G[rows], st.Zc[:, :F].reshape(-1, K, d)[cols].to(f64)
+        q = (Gi * (Zj - st.out.view(n_p, K, d)[rows].to(f64))).sum(-1)        # = <dOut_i, Zs_j> - t_i, and de as the kernels form it:
+        de = alpha * (q - torch.zeros((n_p, K), dtype=f64, device=q.device).index_add_(0, rows, alpha * q)[rows])
+        x = st.Zt.reshape(n_p, K, d)[rows].to(f64) + Zj
+        pos = x > 0
+        w = de.unsqueeze(-1) * st.att.to(f64).t().unsqueeze(0)
+        w = torch.where(pos, w, w * self.slope)
+        dZt = torch.zeros((n_p, K, d), dtype=f64, device=self.device).index_add_(0, rows, w).view(n_p, F).to(torch.float32)
+        dZs = torch.zeros((n_p + n_h, K, d), dtype=f64, device=self.device).index_add_(0, cols, w + alpha.unsqueeze(-1) * Gi)
+        dZc[:, :F].copy_(dZs.view(n_p + n_h, F))
+        da = (de.unsqueeze(-1) * torch.where(pos, x, x * self.slope)).sum(0).t().contiguous().to(torch.float32)
+        return dZt, da
+
     def _finish_backward(self, st: GatLayerState, dOut: torch.Tensor, dZc: torch.Tensor, ds1: torch.Tensor,
                          pack: Optional[torch.Tensor] = None, waits=None):
         """Halo rows of [dZ | ds2] back to their owners (added), then the owned rows.  ``waits`` = (slab, waiters) of an exchange
@@ -627,6 +779,25 @@ class GatAggregate(torch.autograd.Function):
         dZ, ds1, ds2 = ctx.engine.backward(ctx.state, grad_output)
         ctx.state.busy = False
         return None, None, dZ, ds1, ds2
+
+
+class GatV2Aggregate(torch.autograd.Function):
+    """out = GATv2 aggregation of (Zt, Zs, a) on ``engine`` with ``state``'s buffers (``GatEngine.forward_v2``)."""
+
+    @staticmethod
+    def forward(ctx, engine: GatEngine, state: GatLayerState, Zt, Zs, a):
+        if state.busy:
+            raise RuntimeError("GAT layer state is still owned by a forward whose backward has not run; "
+                               "use a fresh state (GatEngine.new_layer_state) for a second forward")
+        ctx.engine, ctx.state = engine, state
+        state.busy = any(ctx.needs_input_grad)
+        return engine.forward_v2(state, Zt, Zs, a)
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        dZt, dZs, da = ctx.engine.backward_v2(ctx.state, grad_output)
+        ctx.state.busy = False
+        return None, None, dZt, dZs, da
 
 
 class GatAggregatePacked(torch.autograd.Function):

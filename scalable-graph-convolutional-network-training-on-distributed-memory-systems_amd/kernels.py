@@ -1349,6 +1349,143 @@ class HipKernels:
         _lib.check(rc, "pgcn_gat_attndrop_grad_f32")
         return True
 
+    # -- GATv2: dynamic attention (pgcn_gatv2.hip) -------------------------------------------------------------------
+    @staticmethod
+    def _v2_shape(heads: int, d: int) -> bool:
+        hl = d // 4
+        return not (d % 4 or hl < 8 or hl & (hl - 1) or heads * d > 256 or not 1 <= heads <= 8)
+
+    def _v2_planes(self, A: DeviceCSR, heads: int, *planes: torch.Tensor):
+        nnz = A.col.numel()
+        for p in planes:
+            if not (p.is_cuda and p.dtype is torch.float32 and p.dim() == 2 and p.shape[0] == heads and p.stride(1) == 1
+                    and p.shape[1] >= nnz and (heads == 1 or p.stride(0) >= nnz)):
+                raise _lib.PgcnError("score / alpha / de planes must be [heads, >= nnz] fp32 CUDA planes")
+
+    def _v2_attention(self, a: torch.Tensor, heads: int, d: int):
+        if not (a.is_cuda and a.dtype is torch.float32 and tuple(a.shape) == (d, heads) and a.is_contiguous()):
+            raise _lib.PgcnError("a must be a contiguous fp32 [d, heads] CUDA tensor")
+
+    def gatv2_scores(self, A: DeviceCSR, Zt: torch.Tensor, Zs: torch.Tensor, a: torch.Tensor, slope: float, E: torch.Tensor,
+                     heads: int, d: int) -> bool:
+        """E[k, p] = sum_c a[c, k] LeakyReLU(Zt[i, k d + c] + Zs[j, k d + c]) for every stored entry p = (i, j) of ``A``, storage order
+        (pgcn_gatv2_scores_f32).  Zt: the rows of A, Zs: its columns.  False = shape not covered (heads 1-8, d 32 / 64 / 128 / 256,
+        heads * d <= 256, 16-byte rows)."""
+        F = heads * d
+        if not self._v2_shape(heads, d):
+            return False
+        self._check_dense(Zt, A.nrows, "Zt")
+        self._check_dense(Zs, A.ncols, "Zs")
+        self._v2_attention(a, heads, d)
+        self._v2_planes(A, heads, E)
+        if Zt.shape[1] < F or Zs.shape[1] < F or A.row_map is not None:
+            raise _lib.PgcnError("Zt / Zs narrower than heads * d, or a compact-row structure")
+        if A.col.numel() == 0:
+            return True
+        rc = self.lib.pgcn_gatv2_scores_f32(
+            A.rowptr.data_ptr(), A.col.data_ptr(), A.nrows, _ptr(A.tasks), A.ntasks, A.seg, A.nslices, Zt.data_ptr(), Zt.stride(0),
+            Zs.data_ptr(), Zs.stride(0), a.data_ptr(), heads, d, slope, E.data_ptr(), E.stride(0), self._stream())
+        if rc == _lib.PGCN_EUNSUPPORTED:
+            return False
+        _lib.check(rc, "pgcn_gatv2_scores_f32")
+        return True
+
+    def gatv2_softmax(self, A: DeviceCSR, E: torch.Tensor, heads: int) -> None:
+        """The score planes of ``gatv2_scores`` become the alpha planes, in place: the softmax over every row's stored entries, the
+        row's maximum subtracted (pgcn_gatv2_softmax_f32)."""
+        self._v2_planes(A, heads, E)
+        if A.col.numel() == 0:
+            return
+        _lib.check(self.lib.pgcn_gatv2_softmax_f32(A.rowptr.data_ptr(), A.nrows, *self._lists(A), heads, E.data_ptr(), E.stride(0),
+                                                   self._stream()), "pgcn_gatv2_softmax_f32")
+
+    def gatv2_grad_rows(self, A: DeviceCSR, Zt: torch.Tensor, Zs: torch.Tensor, a: torch.Tensor, alpha: torch.Tensor, dOut: torch.Tensor,
+                        out: torch.Tensor, slope: float, de: torch.Tensor, dZt: torch.Tensor, da: torch.Tensor, heads: int, d: int,
+                        accumulate: bool = False) -> bool:
+        """Over the FORWARD structure (pgcn_gatv2_grad_rows_f32): the ``de`` planes, de = alpha (q - sum_j alpha q), q = <dOut_i, Zs_j - out_i> (``out``: the forward's output rows); dZt[:, :F] (+)=
+        sum_j de a LReLU'(Zt_i + Zs_j); da [d, heads] = sum_ij de LReLU(Zt_i + Zs_j) of THIS structure (overwritten).  False = shape
+        not covered."""
+        F = heads * d
+        if not self._v2_shape(heads, d):
+            return False
+        self._check_dense(Zt, A.nrows, "Zt")
+        self._check_dense(Zs, A.ncols, "Zs")
+        self._check_dense(dOut, A.nrows, "dOut")
+        self._check_dense(dZt, A.nrows, "dZt")
+        self._check_dense(out, A.nrows, "out")
+        self._v2_attention(a, heads, d)
+        self._v2_attention(da, heads, d)
+        self._v2_planes(A, heads, alpha, de)
+        if min(Zt.shape[1], Zs.shape[1], dOut.shape[1], dZt.shape[1], out.shape[1]) < F or A.row_map is not None:
+            raise _lib.PgcnError("Zt / Zs / dOut / out / dZt narrower than heads * d, or a compact-row structure")
+        if A.col.numel() == 0:
+            da.zero_()
+            if not accumulate:
+                dZt[:A.nrows, :F].zero_()
+            return True
+        need = A.nslots * F
+        if need and (A.ws is None or A.ws.numel() < need):
+            A.ws = torch.empty(need, dtype=torch.float32, device=self.device)
+            A.launch_cache.clear()
+        nda = int(self.lib.pgcn_gatv2_da_ws_elems(A.nrows, _ptr(A.tasks), A.ntasks, A.seg, A.nslices, heads, d))
+        if nda < 0:
+            raise _lib.PgcnError("pgcn_gatv2_da_ws_elems refused the plan")
+        # the two scratch buffers of the call (the da partial rows; T_i = sum_j alpha_ij q_ij of pass 1) belong to the PROVIDER: one of
+        # each for every engine and layer that uses it, written and read within this call -- good for one stream, which is how the
+        # engines call (the comm stream never runs these kernels); two streams on one provider would need a pair each
+        ws = getattr(self, "_v2_da_ws", None)
+        if ws is None or ws.numel() < nda:
+            ws = self._v2_da_ws = torch.empty(max(nda, 1), dtype=torch.float32, device=self.device)
+        tws = getattr(self, "_v2_t_ws", None)
+        if tws is None or tws.numel() < max(A.nrows, 1) * heads:
+            tws = self._v2_t_ws = torch.empty(max(A.nrows, 1) * heads, dtype=torch.float32, device=self.device)
+        flags = _lib.SPMM_ACCUMULATE if accumulate else 0
+        rc = self.lib.pgcn_gatv2_grad_rows_f32(
+            A.rowptr.data_ptr(), A.col.data_ptr(), A.nrows, _ptr(A.tasks), A.ntasks, A.seg, A.nslices, _ptr(A.fix), A.nfix,
+            Zt.data_ptr(), Zt.stride(0), Zs.data_ptr(), Zs.stride(0), a.data_ptr(), alpha.data_ptr(), alpha.stride(0), dOut.data_ptr(),
+            dOut.stride(0), out.data_ptr(), out.stride(0), tws.data_ptr(), heads, d, slope, de.data_ptr(), de.stride(0), dZt.data_ptr(), dZt.stride(0), da.data_ptr(),
+            _ptr(A.ws), 0 if A.ws is None else A.ws.numel(), A.nslots, ws.data_ptr(), ws.numel(), flags, self._stream())
+        if rc == _lib.PGCN_EUNSUPPORTED:
+            return False
+        _lib.check(rc, "pgcn_gatv2_grad_rows_f32")
+        return True
+
+    def gatv2_grad_cols(self, AT: DeviceCSR, Zs: torch.Tensor, Zt: torch.Tensor, dOut: torch.Tensor, a: torch.Tensor,
+                        alpha_t: torch.Tensor, de_t: torch.Tensor, slope: float, dZs: torch.Tensor, heads: int, d: int,
+                        accumulate: bool = False) -> bool:
+        """Over the TRANSPOSED structure (pgcn_gatv2_grad_cols_f32; row j, its columns the attending i; ``alpha_t`` / ``de_t``: the
+        planes in ITS storage order): dZs[:, :F] (+)= sum_i (de a LReLU'(Zt_i + Zs_j) + alpha dOut_i).  Zs: the rows of AT, Zt / dOut:
+        its columns.  False = shape not covered."""
+        F = heads * d
+        if not self._v2_shape(heads, d):
+            return False
+        self._check_dense(Zs, AT.nrows, "Zs")
+        self._check_dense(Zt, AT.ncols, "Zt")
+        self._check_dense(dOut, AT.ncols, "dOut")
+        self._check_dense(dZs, AT.nrows, "dZs")
+        self._v2_attention(a, heads, d)
+        self._v2_planes(AT, heads, alpha_t, de_t)
+        if min(Zt.shape[1], Zs.shape[1], dOut.shape[1], dZs.shape[1]) < F or AT.row_map is not None:
+            raise _lib.PgcnError("Zs / Zt / dOut / dZs narrower than heads * d, or a compact-row structure")
+        if AT.col.numel() == 0:
+            if not accumulate:
+                dZs[:AT.nrows, :F].zero_()
+            return True
+        need = AT.nslots * F
+        if need and (AT.ws is None or AT.ws.numel() < need):
+            AT.ws = torch.empty(need, dtype=torch.float32, device=self.device)
+            AT.launch_cache.clear()
+        flags = _lib.SPMM_ACCUMULATE if accumulate else 0
+        rc = self.lib.pgcn_gatv2_grad_cols_f32(
+            AT.rowptr.data_ptr(), AT.col.data_ptr(), AT.nrows, _ptr(AT.tasks), AT.ntasks, AT.seg, AT.nslices, _ptr(AT.fix), AT.nfix,
+            Zs.data_ptr(), Zs.stride(0), Zt.data_ptr(), Zt.stride(0), dOut.data_ptr(), dOut.stride(0), a.data_ptr(), alpha_t.data_ptr(),
+            alpha_t.stride(0), de_t.data_ptr(), de_t.stride(0), heads, d, slope, dZs.data_ptr(), dZs.stride(0), _ptr(AT.ws),
+            0 if AT.ws is None else AT.ws.numel(), AT.nslots, flags, self._stream())
+        if rc == _lib.PGCN_EUNSUPPORTED:
+            return False
+        _lib.check(rc, "pgcn_gatv2_grad_cols_f32")
+        return True
+
     # -- the dense blocks of an attention pattern (pgcn_gat_blocks.hip, r06) ------------------------------------------
     @staticmethod
     def gat_block_bits(h3) -> torch.Tensor:
