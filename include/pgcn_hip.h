@@ -574,6 +574,55 @@ int pgcn_gatv2_grad_cols_f32(const int64_t *rowptr, const int32_t *col, int64_t 
                              float *dZs, int64_t ldz, float *partial_ws, int64_t partial_ws_elems, int64_t nslots, uint32_t flags,
                              pgcn_stream_t stream);
 
+/* ---- Scaled dot-product attention (the layer of the graph transformers: Shi et al., "Masked label prediction", IJCAI 2021, without edge
+ * features; no counterpart in the reference).  Per layer with `heads` heads of width d, F = heads * d, s = 1 / sqrt(d), on the stored
+ * entries (i, j) of a pattern structure ("i attends to j"):
+ *   e_ijk     = s <Zq[i][k d ..], Zk[j][k d ..]>
+ *   alpha_i.k = softmax of e_i.k over the stored entries of row i (the row's maximum subtracted)    pgcn_gatv2_softmax_f32, unchanged
+ *   out_i     = sum_j alpha_ij Zv_j                                                                 pgcn_spmm_heads_f32, unchanged
+ *   q_ijk     = <dOut[i][k d ..], Zv[j][k d ..] - out[i][k d ..]>,  T_ik = sum_j alpha_ijk q_ijk,  de_ijk = alpha_ijk (q_ijk - T_ik):
+ *               q and T from THE SAME products (two passes), so the rows of de sum to zero to rounding and an error shared by a row cannot
+ *               come back through dZq, whose key rows may share a large common component
+ *   dZq[i][k d + c] = s sum_j de_ijk Zk[j][k d + c]
+ *   dZk[j][k d + c] = s sum_i de_ijk Zq[i][k d + c]
+ *   dZv[j][k d + c] =   sum_i alpha_ijk dOut[i][k d + c]
+ * Scores, alpha and de are PLANES: head-major [heads][plane stride] in the storage order of `col` of the FORWARD structure.  tasks /
+ * ntasks / seg / nslices / fix / nfix / nslots: the plan of pgcn_spmm_plan_host on the structure walked (tasks == NULL: one task per row).
+ * One wave per task, the task's own row in registers, the other end's rows gathered in batches of 8; rows cut by the plan go through slot
+ * rows of F floats and pgcn_spmm_fixup_f32.  Every sum runs in a fixed order, no atomics: two calls give the same bits.  Every row operand
+ * takes a leading dimension (Zk / Zv, and dZk / dZv, may be column slices of one panel); nothing is written beyond column F of a row.
+ * PGCN_EUNSUPPORTED unless heads is 1 .. 8, d is 32, 64, 128 or 256, heads * d <= 256, the row operands are 16-byte aligned and their
+ * leading dimensions multiples of 4 (callers then compose the layer from tensor operations).  An empty row gives out = 0 and dZq = 0, a
+ * column without entries dZk = dZv = 0.
+ *
+ * pgcn_gatdot_scores_f32:    E[k][p] = e of entry p and head k.  Zq: rows of the structure, Zk: its columns.  Every entry is written by
+ *                            the one task that owns it.  The dot is multiplied and added in double and s <Zq_i, Zk_j> rounded once: its
+ *                            absolute error enters an exponential, and a float32 dot of large opposing terms loses eps sum |Zq_c Zk_c|.
+ * pgcn_gatdot_grad_rows_f32: over the FORWARD structure (row i owns the work), two passes: pass 1 gathers Zv_j and writes q into the de
+ *                            planes and T into t_ws (nrows x heads floats of scratch; slots and the fix-up for cut rows); pass 2 forms de
+ *                            in place, gathers Zk_j, and dZq (+)= (flags: PGCN_SPMM_ACCUMULATE).  out: the forward's output rows (read).
+ *                            de is always overwritten.  partial_ws: nslots x F floats.
+ * pgcn_gatdot_grad_cols_f32: over the TRANSPOSED structure (row j owns the work, its columns are the attending i).  alpha / de: the planes
+ *                            in the FORWARD storage order; perm[p] = the forward position of this structure's entry p (the permutation of
+ *                            pgcn_csr_permute_f32): every plane word is read through it, no permuted copy exists.  Zq / dOut: the columns
+ *                            of the transposed structure, gathered in one walk.  dZk (+)=, dZv (+)= (PGCN_SPMM_ACCUMULATE).  partial_ws:
+ *                            2 x nslots x F floats (the slot rows of dZk, then those of dZv).                                            */
+int pgcn_gatdot_scores_f32(const int64_t *rowptr, const int32_t *col, int64_t nrows, const int32_t *tasks, int64_t ntasks,
+                           const int64_t *seg, int32_t nslices, const float *Zq, int64_t ldq, const float *Zk, int64_t ldk,
+                           int32_t heads, int32_t d, float *E, int64_t plane_stride, pgcn_stream_t stream);
+int pgcn_gatdot_grad_rows_f32(const int64_t *rowptr, const int32_t *col, int64_t nrows, const int32_t *tasks, int64_t ntasks,
+                              const int64_t *seg, int32_t nslices, const int32_t *fix, int64_t nfix, const float *Zk, int64_t ldk,
+                              const float *Zv, int64_t ldv, const float *alpha, int64_t alpha_stride, const float *dOut, int64_t ldo,
+                              const float *out, int64_t ldout, float *t_ws, int32_t heads, int32_t d, float *de, int64_t de_stride,
+                              float *dZq, int64_t ldz, float *partial_ws, int64_t partial_ws_elems, int64_t nslots, uint32_t flags,
+                              pgcn_stream_t stream);
+int pgcn_gatdot_grad_cols_f32(const int64_t *rowptr, const int32_t *col, int64_t nrows, const int32_t *tasks, int64_t ntasks,
+                              const int64_t *seg, int32_t nslices, const int32_t *fix, int64_t nfix, const int64_t *perm,
+                              const float *Zq, int64_t ldq, const float *dOut, int64_t ldo, const float *alpha, int64_t alpha_stride,
+                              const float *de, int64_t de_stride, int32_t heads, int32_t d, float *dZk, int64_t ldzk, float *dZv,
+                              int64_t ldzv, float *partial_ws, int64_t partial_ws_elems, int64_t nslots, uint32_t flags,
+                              pgcn_stream_t stream);
+
 /* The dense 512 x 128 BLOCKS of the attention pattern on the bf16 matrix cores (r06, pgcn_gat_blocks.hip): the entries inside the
  * listed blocks of the products above, with the weights computed in registers from the same statistics and split into three bf16
  * planes (fp32 accuracy, as pgcn_spmm_dense_bf16x3_f32).  work / blk_img / panel_list / npanels / image_ws: the block structure and

@@ -162,7 +162,7 @@ class Comm(torch.autograd.Function):
 
 # ---- the tail of a layer: head mean, bias, ELU and dropout (csrc/pgcn_gat_tail.hip) -------------------------------------------------
 ACTIVATIONS = (None, "elu")
-ATTENTIONS = ("v1", "v2")
+ATTENTIONS = ("v1", "v2", "dot")
 
 
 def _f32_inv(x):
@@ -272,7 +272,13 @@ class PGAT(nn.Module):
     ``attention="v2"``: the DYNAMIC score of GATv2 (Brody, Alon, Yahav, ICLR 2022), e_ijk = sum_c a[c,k] LeakyReLU(Zt[i,k,c] +
     Zs[j,k,c]) with Zs = H Ws^T (``linear``: the messages and the neighbour's side of the score) and Zt = H Wt^T (``linear_t``: the
     attending vertex's side; ``share_weights=True``: Wt is Ws, one projection); ``attention`` then has shape (d, K).  The tail is the
-    same.  Not with the reference mode, not with ``attn_dropout``.  ``attention="v1"`` (the default) is the layer of before."""
+    same.  Not with the reference mode, not with ``attn_dropout``.  ``attention="v1"`` (the default) is the layer of before.
+
+    ``attention="dot"``: the scaled dot-product score of the graph transformers (Shi et al., IJCAI 2021; no edge features),
+    e_ijk = <Zq[i,k,:], Zk[j,k,:]> / sqrt(d) with separate values: out_i = sum_j alpha_ij Zv_j, Zv = H Wv^T (``linear``: the messages,
+    under the key they have in every other layer), Zk = H Wk^T (``linear_k``), Zq = H Wq^T (``linear_q``); no projection biases and
+    no ``attention`` parameter (it is None).  The tail is the same.  Not with ``share_weights``, the reference mode or
+    ``attn_dropout``."""
 
     def __init__(self, A, in_features, out_features, heads=None, bias=False, activation=None, concat=True, dropout=0.0, layer=0,
                  state=None, attn_dropout=0.0, attention="v1", share_weights=False):
@@ -291,8 +297,14 @@ class PGAT(nn.Module):
         if attention not in ATTENTIONS:
             raise ValueError("attention takes %s, got %r" % (" | ".join(ATTENTIONS), attention))
         self.version, self.share_weights = attention, bool(share_weights)
+        if self.share_weights and attention == "dot":
+            raise ValueError("share_weights needs attention='v2': the dot layer keeps its query, key and value projections apart")
         if self.share_weights and attention != "v2":
             raise ValueError("share_weights needs attention='v2': the v1 layer has one projection")
+        if attention == "dot" and A is not None and getattr(A, "mode", "standard") == "reference":
+            raise ValueError("the reference layer has the static score only (attention='dot' needs mode='standard')")
+        if attention == "dot" and float(attn_dropout) > 0.0:
+            raise ValueError("attention='dot' with attn_dropout is not implemented: use attention='v1', or attn_dropout=0")
         if attention == "v2" and A is not None and getattr(A, "mode", "standard") == "reference":
             raise ValueError("the reference layer has the static score only (attention='v2' needs mode='standard')")
         if attention == "v2" and float(attn_dropout) > 0.0:
@@ -302,6 +314,10 @@ class PGAT(nn.Module):
             if not self.share_weights:
                 self.linear_t = nn.Linear(in_features, out_features, bias=False)
             self.attention = nn.Parameter(torch.empty(size=(out_features // K, K)))
+        elif attention == "dot":
+            self.linear_k = nn.Linear(in_features, out_features, bias=False)
+            self.linear_q = nn.Linear(in_features, out_features, bias=False)
+            self.register_parameter("attention", None)
         else:
             self.attention = nn.Parameter(torch.empty(size=(2 * out_features // K, K)))   # (2F, 1) for one head, :127
         self._state = None
@@ -334,11 +350,17 @@ class PGAT(nn.Module):
         nn.init.xavier_normal_(self.linear.weight, gain=gain)
         if self.version == "v2" and not self.share_weights:
             nn.init.xavier_normal_(self.linear_t.weight, gain=gain)
+        if self.version == "dot":
+            nn.init.xavier_normal_(self.linear_k.weight, gain=gain)
+            nn.init.xavier_normal_(self.linear_q.weight, gain=gain)
+            return
         nn.init.xavier_normal_(self.attention, gain=gain)
 
     @property
     def projected_width(self):
-        """Columns of the layer's ONE dense product: [Z | z2 | z1] (v1), [Zs | Zt] (v2), Zs (v2, shared weights)."""
+        """Columns of the layer's ONE dense product: [Z | z2 | z1] (v1), [Zs | Zt] (v2), Zs (v2, shared weights), [Zk | Zv | Zq] (dot)."""
+        if self.version == "dot":
+            return 3 * self.out_features
         if self.version == "v2":
             return self.out_features * (1 if self.share_weights else 2)
         return self.out_features + 2 * self.heads
@@ -356,10 +378,23 @@ class PGAT(nn.Module):
             st = self._state = self.A.new_layer_state(K, d)
         return _gat.GatV2Aggregate.apply(self.A, st, Zt, Zs, self.attention)
 
+    def _forward_dot(self, H):
+        K, d = self.heads, self.out_features // self.heads
+        F = self.out_features
+        # the three projections as ONE product over the stacked weight: n x 3F = [Zk | Zv | Zq] -- keys and values side by side, so the
+        # rows that cross ranks (and, on one rank, the gather panel itself) are one contiguous slice
+        ZZ = _pgcn._LinearNoBias.apply(H, torch.cat([self.linear_k.weight, self.linear.weight, self.linear_q.weight], 0))
+        st = self._state
+        if st is None or st.busy or (st.heads, st.d) != (K, d):
+            st = self._state = self.A.new_layer_state(K, d)
+        return _gat.GatDotAggregate.apply(self.A, st, ZZ[:, 2 * F:], ZZ[:, :F], ZZ[:, F:2 * F])
+
     def forward(self, H):
         K, d = self.heads, self.out_features // self.heads
         if self.version == "v2":
             return self._tail(self._forward_v2(H), K, d)
+        if self.version == "dot":
+            return self._tail(self._forward_dot(H), K, d)
         # Z = self.linear(H) (:140), z1 = Z a1 (:141), z2 = Z a2 (:142) as ONE product: z_k = Z_k a_k = H (W_k^T a_k), so the 2K
         # projection columns ride along as 2K more rows of the weight (K x in each, a tiny product of their own; autograd carries
         # their gradients back to W and the attention vectors).  The per-head einsums they replace ran as skinny batched GEMMs:
@@ -517,7 +552,7 @@ def build_classifier(A, fin, classes, nlayers, hidden, K, out_heads=1, dropout=0
     """The model of the GAT paper on the engine ``A``: layers 0 .. L-2 are K concatenated heads of hidden / K columns, ELU, dropout
     on their output; the last layer averages ``out_heads`` heads of ``classes`` columns.  ``attn_dropout``: dropout on the attention
     coefficients of EVERY layer, the last one included, as in the paper.  ``attention="v2"`` (and ``share_weights``): every layer takes
-    the dynamic score of GATv2 (class PGAT).  ``widths``: the layers' input widths and the class count."""
+    the dynamic score of GATv2, ``attention="dot"``: the scaled dot-product score with separate queries, keys and values (class PGAT).  ``widths``: the layers' input widths and the class count."""
     if hidden % K:
         raise ValueError("hidden (%d) must be divisible by the number of heads (%d)" % (hidden, K))
     widths = [fin] + [hidden] * (nlayers - 1) + [classes]
@@ -662,8 +697,14 @@ def run(rank, size, nlayers, nfeatures, path_A, path_partvec, backend, epochs=No
             raise ValueError("attn_dropout takes a probability in [0, 1), got %r" % (data["attn_dropout"],))
     if data.get("attention") not in (None,) + ATTENTIONS:
         raise ValueError("attention takes %s, got %r" % (" | ".join(ATTENTIONS), data.get("attention")))
+    if data.get("share_weights") and data.get("attention") == "dot":
+        raise ValueError("share_weights needs attention='v2': the dot layer keeps its query, key and value projections apart")
     if data.get("share_weights") and data.get("attention") != "v2":
         raise ValueError("share_weights needs attention='v2': the v1 layer has one projection")
+    if data.get("attention") == "dot" and mode == "reference":
+        raise ValueError("the reference layer has the static score only: attention='dot' needs standard mode")
+    if data.get("attention") == "dot" and float(data.get("attn_dropout") or 0.0) > 0.0:
+        raise ValueError("attention='dot' with attn_dropout is not implemented: use attention='v1', or attn_dropout=0")
     if data.get("attention") == "v2" and mode == "reference":
         raise ValueError("the reference layer has the static score only: attention='v2' needs standard mode")
     if data.get("attention") == "v2" and float(data.get("attn_dropout") or 0.0) > 0.0:
@@ -710,6 +751,8 @@ def run(rank, size, nlayers, nfeatures, path_A, path_partvec, backend, epochs=No
 
     _pgcn.tune_dense_gemms(A.part.n_local, nfeatures, device)     # library GEMM choice for H.W^T made in set-up
     v2 = {"attention": "v2", "share_weights": bool(data.get("share_weights"))} if data.get("attention") == "v2" else {}
+    if data.get("attention") == "dot":
+        v2 = {"attention": "dot"}
     model = nn.Sequential(*[PGAT(A, nfeatures, nfeatures, **v2) for _ in range(nlayers)])
     model = model.to(device)
     initiliaze_parameters(model)
@@ -814,9 +857,9 @@ def main(argv):
                 _dropout.threshold(data["attn_dropout"])
             except ValueError:
                 refuse("--attn-dropout takes a probability in [0, 1), got %r" % arg)
-        elif opt == '--attention':     # v1: the static score of GAT (the default) | v2: the dynamic score of GATv2 (class PGAT)
-            if arg not in ATTENTIONS:
-                refuse("--attention takes %s, got %r" % ("|".join(ATTENTIONS), arg))
+        elif opt == '--attention':     # v1: the static score of GAT (the default) | v2: the dynamic score of GATv2 | dot: the scaled
+            if arg not in ATTENTIONS:  # dot-product score with separate queries, keys and values (class PGAT)
+                refuse("--attention takes %s, got %r (or %s, the scaled dot-product score)" % ("|".join(ATTENTIONS[:2]), arg, ATTENTIONS[2]))
             score["attention"] = arg
         elif opt == '--share-weights':  # with --attention v2: one projection for both sides of the score
             score["share_weights"] = True
@@ -867,8 +910,14 @@ def main(argv):
             mode = arg
         elif opt == '--heads':
             heads = int(arg)
+    if score.get("share_weights") and score.get("attention") == "dot":
+        refuse("--share-weights needs --attention v2: the dot layer keeps its query, key and value projections apart")
     if score.get("share_weights") and score.get("attention") != "v2":
         refuse("--share-weights needs --attention v2: the v1 layer has one projection")
+    if score.get("attention") == "dot" and mode == "reference":
+        refuse("--mode reference has the static score only: --attention dot needs --mode standard")
+    if score.get("attention") == "dot" and data.get("attn_dropout", 0.0) > 0.0:
+        refuse("--attention dot with --attn-dropout is not implemented: use --attention v1, or leave --attn-dropout out")
     if score.get("attention") == "v2" and mode == "reference":
         refuse("--mode reference has the static score only: --attention v2 needs --mode standard")
     if score.get("attention") == "v2" and data.get("attn_dropout", 0.0) > 0.0:

@@ -91,6 +91,11 @@ SIGNATURES = {
                                                 _u32, _vp]),
     "pgcn_gatv2_grad_cols_f32": (ctypes.c_int, [_vp, _vp, _i64, _vp, _i64, _vp, _i32, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp,
                                                 _i64, _vp, _i64, _i32, _i32, ctypes.c_float, _vp, _i64, _vp, _i64, _i64, _u32, _vp]),
+    "pgcn_gatdot_scores_f32": (ctypes.c_int, [_vp, _vp, _i64, _vp, _i64, _vp, _i32, _vp, _i64, _vp, _i64, _i32, _i32, _vp, _i64, _vp]),
+    "pgcn_gatdot_grad_rows_f32": (ctypes.c_int, [_vp, _vp, _i64, _vp, _i64, _vp, _i32, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64,
+                                                 _vp, _i64, _vp, _i32, _i32, _vp, _i64, _vp, _i64, _vp, _i64, _i64, _u32, _vp]),
+    "pgcn_gatdot_grad_cols_f32": (ctypes.c_int, [_vp, _vp, _i64, _vp, _i64, _vp, _i32, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp,
+                                                 _i64, _i32, _i32, _vp, _i64, _vp, _i64, _vp, _i64, _i64, _u32, _vp]),
     "pgcn_gat_blocks_forward_f32": (ctypes.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i64, ctypes.c_float, _i32, _i32, _i64, _i64,
                                                    _vp, _i64, _vp, _i64, _vp, _i64, _i64, _vp]),
     "pgcn_gat_blocks_backward_f32": (ctypes.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _i64, ctypes.c_float, _i32,

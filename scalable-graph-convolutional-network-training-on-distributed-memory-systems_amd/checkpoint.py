@@ -54,7 +54,8 @@ def architecture(widths, task, dropout=0.0, dropout_seed=0, norm=None, root_weig
     dropout probability only when it is positive (its mask, too, is keyed by ``dropout_seed``); it is compared before the seed, so a
     checkpoint loaded under another value is refused in its name.  ``attention`` / ``share_weights``: the keys exist only for the GATv2
     layers ("v2", and whether the two projections are one); a record without them is a v1 model, so a v1 checkpoint under a v2 command
-    line, or the reverse, is refused in the name of ``attention``."""
+    line, or the reverse, is refused in the name of ``attention``.  The dot-product layers record ``attention: "dot"`` the same way
+    (``share_weights`` stays False there), so every pair of v1, v2 and dot is told apart by that field."""
     arch = {"widths": [int(w) for w in widths], "layers": len(widths) - 1, "task": str(task or "single"),
             "norm": "none" if norm in (None, "none") else str(norm), "root_weight": bool(root_weight), "bias": bool(bias),
             "residual": bool(residual), "heads": None if heads is None else int(heads),

@@ -47,6 +47,18 @@ order of ``fwd`` (csrc/pgcn_gatv2.hip).
               ADDED (the reverse all-to-all-v of the v1 path).  da is this rank's partial sum, like any weight gradient.
 The unsplit structures only: the pass waits for the halo rows.  CPU tensors, providers without the four methods and shapes the kernels
 refuse take the same arithmetic as tensor operations over the entry list (``_v2_forward`` / ``_v2_backward``).
+
+Scaled dot-product attention (``GatEngine.forward_dot`` / ``backward_dot``, ``GatDotAggregate``; standard mode): the score of the graph
+transformers, e_ijk = <Zq[i,k,:], Zk[j,k,:]> / sqrt(d), with separate values: out_i = sum_j alpha_ij Zv_j (csrc/pgcn_gatdot.hip;
+DESIGN.md section 4).  The planes, the softmax and the multi-head product are those of GATv2.
+    forward   rows of [Zk | Zv] -> ONE all-to-all-v at width 2 Fp -> panel [local ; halo] x 2 Fp (Fp = F padded to 4; keys in columns
+              [0, F), values in [Fp, Fp + F)); Zq never leaves its rank.  Scores (pgcn_gatdot_scores_f32), softmax in place
+              (pgcn_gatv2_softmax_f32), out = A_alpha . Zv (pgcn_spmm_heads_f32).  Kept for the backward: the alpha planes
+    backward  over fwd, two passes: q = <dOut_i, Zv_j - out_i> and T_i, then de = alpha (q - T) and dZq (pgcn_gatdot_grad_rows_f32);
+              over bwd: dZk and dZv in ONE walk that reads the forward-order planes through the entry permutation
+              (pgcn_gatdot_grad_cols_f32; nothing is permuted) into one gradient panel of the forward panel's layout, whose halo rows
+              travel home and are ADDED (the reverse all-to-all-v, at width 2 Fp).
+CPU tensors, providers without the three methods and shapes the kernels refuse take ``_dot_forward`` / ``_dot_backward``.
 """
 from __future__ import annotations
 
@@ -193,6 +205,7 @@ class GatLayerState:
     Zt: Optional[torch.Tensor] = None    # GATv2: the target-side projection of the last forward_v2 (owned rows, never exchanged)
     att: Optional[torch.Tensor] = None   # ... its attention parameter a [d, heads]
     alpha_e: Optional[torch.Tensor] = None   # ... and, on the composed route, alpha per entry [nnz, heads] in double (None: the planes hold it)
+    Zq: Optional[torch.Tensor] = None    # dot-product attention: the query projection of the last forward_dot (owned rows, never exchanged)
 
 
 class GatEngine(BoundaryExchange):
@@ -729,6 +742,135 @@ class GatEngine(BoundaryExchange):
         da = (de.unsqueeze(-1) * torch.where(pos, x, x * self.slope)).sum(0).t().contiguous().to(torch.float32)
         return dZt, da
 
+    # -- scaled dot-product attention: separate queries, keys and values (csrc/pgcn_gatdot.hip) -----------------------------------------
+    def _dot_kernels(self, K: int, d: int) -> bool:
+        return all(hasattr(self.k, m) for m in ("gatdot_scores", "gatv2_softmax", "gatdot_grad_rows", "gatdot_grad_cols",
+                                                "spmm_heads")) and self.covers(K, d)
+
+    def forward_dot(self, st: GatLayerState, Zq: torch.Tensor, Zk: torch.Tensor, Zv: torch.Tensor) -> torch.Tensor:
+        """out_i = sum_j alpha_ij Zv_j with alpha the softmax over row i of e_ijk = <Zq[i,k,:], Zk[j,k,:]> / sqrt(d).  Zq, Zk, Zv:
+        [n_local, heads * d] of the owned rows (column slices of one projection are fine)."""
+        K, d = st.heads, st.d
+        F = K * d
+        n_p, n_h = self.n_local, self.n_halo
+        if self.mode_id != 0:
+            raise ValueError("dot-product attention needs mode='standard': the reference layer has the static score only")
+        if st.drop is not None and st.drop.on:
+            raise ValueError("dot-product attention with attention dropout is not implemented: use attention='v1' with attn_dropout, "
+                             "or attn_dropout=0")
+        if Zq.shape != (n_p, F) or Zk.shape != (n_p, F) or Zv.shape != (n_p, F):
+            raise ValueError("expected Zq / Zk / Zv %s" % ((n_p, F),))
+        Zq, Zk, Zv = Zq.detach(), Zk.detach(), Zv.detach()
+        Fp = (F + 3) // 4 * 4
+        # ONE rank only, and [Zk | Zv] adjacent column slices of one aligned projection: they ARE the gather panel (never written
+        # through).  A rank of several without halo rows still has its part in the all-to-all-v below -- its peers wait for it
+        if self.size == 1 and n_h == 0 and n_p > 0 and Fp == F and Zk.dtype is torch.float32 and Zv.dtype is torch.float32 \
+                and Zk.stride(1) == 1 and Zv.stride(1) == 1 and Zk.stride(0) == Zv.stride(0) >= 2 * F and Zk.stride(0) % 4 == 0 \
+                and Zk.data_ptr() % 16 == 0 and Zv.data_ptr() == Zk.data_ptr() + 4 * F \
+                and Zk.untyped_storage().data_ptr() == Zv.untyped_storage().data_ptr():
+            st.Zc = Zc = Zk.as_strided((n_p, 2 * F), (Zk.stride(0), 1))
+            st.Zc_borrowed = True
+        else:
+            if st.Zc is None or st.Zc_borrowed or st.Zc.shape != (n_p + n_h, 2 * Fp):
+                st.Zc = torch.zeros((n_p + n_h, 2 * Fp), dtype=torch.float32, device=self.device)
+                st.Zc_borrowed = False
+            Zc = st.Zc
+            Zc[:n_p, :F].copy_(Zk)
+            Zc[:n_p, Fp:Fp + F].copy_(Zv)
+            if self.size > 1:                    # keys and values of the boundary rows in one exchange; Zq is row i's own
+                send = self._slab("gat_send", self.n_send, 2 * Fp)
+                self.k.gather_rows(Zc[:n_p], self.send_idx, send)
+                for w in self._exchange_all(send, self.round_send_off, Zc[n_p:], self.round_recv_off, 2 * Fp):
+                    w()
+        if Zq.stride(1) != 1:
+            Zq = Zq.contiguous()
+        out = torch.empty((n_p, F), dtype=torch.float32, device=self.device)
+        st.Zq, st.alpha_e, st.dropped, st.entries, st.fused = Zq, None, None, None, False
+        done = False
+        if self._dot_kernels(K, d):
+            if st.alpha is None or st.alpha.shape != (K, max(self.nnz, 1)):
+                st.alpha = torch.zeros((K, max(self.nnz, 1)), dtype=torch.float32, device=self.device)
+                st.fwd_heads = None
+            if self.k.gatdot_scores(self.fwd, Zq, Zc[:, :F], st.alpha, K, d):
+                self.k.gatv2_softmax(self.fwd, st.alpha, K)
+                if self.nnz == 0:
+                    out.zero_()
+                elif not self.k.spmm_heads(self.fwd, st.alpha, Zc[:, Fp:Fp + F], out, K, d):
+                    raise RuntimeError("the multi-head product refused a shape the dot-product score kernel took")
+                done = True
+        if not done:
+            self._dot_forward(st, Zq, Zc, out)
+        st.out = out
+        return out
+
+    def backward_dot(self, st: GatLayerState, dOut: torch.Tensor):
+        """(dZq, dZk, dZv) of the last ``forward_dot`` for the owned rows."""
+        K, d = st.heads, st.d
+        F = K * d
+        n_p, n_h = self.n_local, self.n_halo
+        Fp = (F + 3) // 4 * 4
+        dOut = dOut.contiguous()
+        dZc = self._slab("gat_dkv", n_p + n_h, 2 * Fp)[:n_p + n_h]       # the gradient panel: [dZk | dZv] in the forward panel's layout
+        Zc = st.Zc
+        dZq = None
+        if st.alpha_e is None:
+            de = self._plane_scratch("dot_de", K)
+            dZq = torch.empty((n_p, F), dtype=torch.float32, device=self.device)
+            if not (self.k.gatdot_grad_rows(self.fwd, Zc[:, :F], Zc[:, Fp:Fp + F], st.alpha, dOut, st.out, de, dZq, K, d)
+                    and self.k.gatdot_grad_cols(self.bwd, self.perm, st.Zq, dOut, st.alpha, de, dZc[:, :F], dZc[:, Fp:Fp + F], K, d)):
+                dZq = None
+        if dZq is None:                          # the composed route, or a kernel refused operands its forward twin took
+            dZq = self._dot_backward(st, dOut, dZc)
+        if Fp > F:
+            dZc[:, F:Fp].zero_()
+            dZc[:, Fp + F:].zero_()
+        if self.size > 1:                        # partial rows of [dZk | dZv] back to their owners, ADDED
+            back = self._slab("gat_send", self.n_send, 2 * Fp)
+            waits = self._exchange_all(dZc[n_p:], self.round_recv_off, back, self.round_send_off, 2 * Fp, tag="backward")
+            for r in range(self.rounds):
+                waits[r]()
+                self.k.spmm(self.unpack[r], back, dZc[:n_p], accumulate=True)
+        return dZq, dZc[:n_p, :F].clone(), dZc[:n_p, Fp:Fp + F].clone()
+
+    # -- ... as tensor operations over the entry list (CPU tensors, other providers, shapes the kernels refuse) ------------------------
+    def _dot_forward(self, st: GatLayerState, Zq: torch.Tensor, Zc: torch.Tensor, out: torch.Tensor):
+        """The definition over the entry list, formed in DOUBLE and rounded once per output, like ``_v2_forward``."""
+        K, d = st.heads, st.d
+        F, n_p = K * d, self.n_local
+        Fp = (F + 3) // 4 * 4
+        rows, cols = self._v2_entry_list()
+        f64 = torch.float64
+        Kj = Zc[:, :F].reshape(-1, K, d)[cols].to(f64)
+        e = (Zq.reshape(n_p, K, d)[rows].to(f64) * Kj).sum(-1) / float(d) ** 0.5
+        m = torch.full((n_p, K), -float("inf"), dtype=f64, device=e.device).scatter_reduce(0, rows.unsqueeze(1).expand(-1, K), e, "amax",
+                                                                                           include_self=True)
+        ex = torch.exp(e - m[rows])
+        D = torch.zeros((n_p, K), dtype=f64, device=e.device).index_add_(0, rows, ex)
+        st.alpha_e = ex / D[rows]                                              # (kept in double for the backward)
+        Vj = Zc[:, Fp:Fp + F].reshape(-1, K, d)[cols].to(f64)
+        out.copy_(torch.zeros((n_p, K, d), dtype=f64, device=e.device).index_add_(0, rows, st.alpha_e.unsqueeze(-1) * Vj).view(n_p, F))
+
+    def _dot_backward(self, st: GatLayerState, dOut: torch.Tensor, dZc: torch.Tensor) -> torch.Tensor:
+        K, d = st.heads, st.d
+        F, n_p, n_h = K * d, self.n_local, self.n_halo
+        Fp = (F + 3) // 4 * 4
+        rows, cols = self._v2_entry_list()
+        f64 = torch.float64
+        s = 1.0 / float(d) ** 0.5
+        alpha = st.alpha_e if st.alpha_e is not None else st.alpha[:, :self.nnz].t().to(f64)
+        G = dOut.view(n_p, K, d).to(f64)
+        Gi = G[rows]
+        Kj, Vj = (st.Zc[:, c0:c0 + F].reshape(-1, K, d)[cols].to(f64) for c0 in (0, Fp))
+        q = (Gi * (Vj - st.out.view(n_p, K, d)[rows].to(f64))).sum(-1)          # de as the kernels form it: q and T from the same products
+        de = alpha * (q - torch.zeros((n_p, K), dtype=f64, device=q.device).index_add_(0, rows, alpha * q)[rows])
+        w = de.unsqueeze(-1)
+        dZq = (s * torch.zeros((n_p, K, d), dtype=f64, device=self.device).index_add_(0, rows, w * Kj)).view(n_p, F).to(torch.float32)
+        dZk = s * torch.zeros((n_p + n_h, K, d), dtype=f64, device=self.device).index_add_(0, cols, w * st.Zq.reshape(n_p, K, d)[rows].to(f64))
+        dZv = torch.zeros((n_p + n_h, K, d), dtype=f64, device=self.device).index_add_(0, cols, alpha.unsqueeze(-1) * Gi)
+        dZc[:, :F].copy_(dZk.view(n_p + n_h, F))
+        dZc[:, Fp:Fp + F].copy_(dZv.view(n_p + n_h, F))
+        return dZq
+
     def _finish_backward(self, st: GatLayerState, dOut: torch.Tensor, dZc: torch.Tensor, ds1: torch.Tensor,
                          pack: Optional[torch.Tensor] = None, waits=None):
         """Halo rows of [dZ | ds2] back to their owners (added), then the owned rows.  ``waits`` = (slab, waiters) of an exchange
@@ -798,6 +940,25 @@ class GatV2Aggregate(torch.autograd.Function):
         dZt, dZs, da = ctx.engine.backward_v2(ctx.state, grad_output)
         ctx.state.busy = False
         return None, None, dZt, dZs, da
+
+
+class GatDotAggregate(torch.autograd.Function):
+    """out = dot-product attention of (Zq, Zk, Zv) on ``engine`` with ``state``'s buffers (``GatEngine.forward_dot``)."""
+
+    @staticmethod
+    def forward(ctx, engine: GatEngine, state: GatLayerState, Zq, Zk, Zv):
+        if state.busy:
+            raise RuntimeError("GAT layer state is still owned by a forward whose backward has not run; "
+                               "use a fresh state (GatEngine.new_layer_state) for a second forward")
+        ctx.engine, ctx.state = engine, state
+        state.busy = any(ctx.needs_input_grad)
+        return engine.forward_dot(state, Zq, Zk, Zv)
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        dZq, dZk, dZv = ctx.engine.backward_dot(ctx.state, grad_output)
+        ctx.state.busy = False
+        return None, None, dZq, dZk, dZv
 
 
 class GatAggregatePacked(torch.autograd.Function):

@@ -1486,6 +1486,97 @@ class HipKernels:
         _lib.check(rc, "pgcn_gatv2_grad_cols_f32")
         return True
 
+    # -- scaled dot-product attention (pgcn_gatdot.hip) ----------------------------------------------------------------
+    def _dot_rows(self, F: int, A: DeviceCSR, **mats) -> None:
+        """Every named matrix is a row-major fp32 CUDA matrix of enough rows (its value: (tensor, rows)) and at least F columns."""
+        for what, (t, rows) in mats.items():
+            self._check_dense(t, rows, what)
+            if t.shape[1] < F:
+                raise _lib.PgcnError("%s is narrower than heads * d" % what)
+        if A.row_map is not None:
+            raise _lib.PgcnError("a compact-row structure")
+
+    def gatdot_scores(self, A: DeviceCSR, Zq: torch.Tensor, Zk: torch.Tensor, E: torch.Tensor, heads: int, d: int) -> bool:
+        """E[k, p] = <Zq[i, k d ..], Zk[j, k d ..]> / sqrt(d) for every stored entry p = (i, j) of ``A``, storage order
+        (pgcn_gatdot_scores_f32).  Zq: the rows of A, Zk: its columns.  False = shape not covered (heads 1-8, d 32 / 64 / 128 / 256,
+        heads * d <= 256, 16-byte rows, leading dimensions % 4 == 0)."""
+        if not self._v2_shape(heads, d):
+            return False
+        self._dot_rows(heads * d, A, Zq=(Zq, A.nrows), Zk=(Zk, A.ncols))
+        self._v2_planes(A, heads, E)
+        if A.col.numel() == 0:
+            return True
+        rc = self.lib.pgcn_gatdot_scores_f32(
+            A.rowptr.data_ptr(), A.col.data_ptr(), A.nrows, _ptr(A.tasks), A.ntasks, A.seg, A.nslices, Zq.data_ptr(), Zq.stride(0),
+            Zk.data_ptr(), Zk.stride(0), heads, d, E.data_ptr(), E.stride(0), self._stream())
+        if rc == _lib.PGCN_EUNSUPPORTED:
+            return False
+        _lib.check(rc, "pgcn_gatdot_scores_f32")
+        return True
+
+    def _slot_ws(self, A: DeviceCSR, need: int) -> None:
+        if need and (A.ws is None or A.ws.numel() < need):
+            A.ws = torch.empty(need, dtype=torch.float32, device=self.device)
+            A.launch_cache.clear()
+
+    def gatdot_grad_rows(self, A: DeviceCSR, Zk: torch.Tensor, Zv: torch.Tensor, alpha: torch.Tensor, dOut: torch.Tensor,
+                         out: torch.Tensor, de: torch.Tensor, dZq: torch.Tensor, heads: int, d: int, accumulate: bool = False) -> bool:
+        """Over the FORWARD structure (pgcn_gatdot_grad_rows_f32): the ``de`` planes, de = alpha (q - sum_j alpha q), q = <dOut_i,
+        Zv_j - out_i> (``out``: the forward's output rows), always overwritten; dZq[:, :F] (+)= sum_j de Zk_j / sqrt(d).  False = shape
+        not covered."""
+        F = heads * d
+        if not self._v2_shape(heads, d):
+            return False
+        self._dot_rows(F, A, Zk=(Zk, A.ncols), Zv=(Zv, A.ncols), dOut=(dOut, A.nrows), out=(out, A.nrows), dZq=(dZq, A.nrows))
+        self._v2_planes(A, heads, alpha, de)
+        if A.col.numel() == 0:
+            if not accumulate:
+                dZq[:A.nrows, :F].zero_()
+            return True
+        self._slot_ws(A, A.nslots * F)
+        # T_i = sum_j alpha_ij q_ij of pass 1 belongs to the PROVIDER, like the scratch of gatv2_grad_rows: written and read within this call
+        tws = getattr(self, "_v2_t_ws", None)
+        if tws is None or tws.numel() < max(A.nrows, 1) * heads:
+            tws = self._v2_t_ws = torch.empty(max(A.nrows, 1) * heads, dtype=torch.float32, device=self.device)
+        rc = self.lib.pgcn_gatdot_grad_rows_f32(
+            A.rowptr.data_ptr(), A.col.data_ptr(), A.nrows, _ptr(A.tasks), A.ntasks, A.seg, A.nslices, _ptr(A.fix), A.nfix,
+            Zk.data_ptr(), Zk.stride(0), Zv.data_ptr(), Zv.stride(0), alpha.data_ptr(), alpha.stride(0), dOut.data_ptr(), dOut.stride(0),
+            out.data_ptr(), out.stride(0), tws.data_ptr(), heads, d, de.data_ptr(), de.stride(0), dZq.data_ptr(), dZq.stride(0),
+            _ptr(A.ws), 0 if A.ws is None else A.ws.numel(), A.nslots, _lib.SPMM_ACCUMULATE if accumulate else 0, self._stream())
+        if rc == _lib.PGCN_EUNSUPPORTED:
+            return False
+        _lib.check(rc, "pgcn_gatdot_grad_rows_f32")
+        return True
+
+    def gatdot_grad_cols(self, AT: DeviceCSR, perm: torch.Tensor, Zq: torch.Tensor, dOut: torch.Tensor, alpha: torch.Tensor,
+                         de: torch.Tensor, dZk: torch.Tensor, dZv: torch.Tensor, heads: int, d: int, accumulate: bool = False) -> bool:
+        """Over the TRANSPOSED structure (pgcn_gatdot_grad_cols_f32; row j, its columns the attending i): dZk[:, :F] (+)= sum_i de Zq_i /
+        sqrt(d), dZv[:, :F] (+)= sum_i alpha dOut_i.  ``alpha`` / ``de``: the planes in the FORWARD storage order, read through ``perm``
+        (int64, perm[p] = the forward position of AT's entry p).  Zq / dOut: the columns of AT.  False = shape not covered."""
+        F = heads * d
+        if not self._v2_shape(heads, d):
+            return False
+        self._dot_rows(F, AT, Zq=(Zq, AT.ncols), dOut=(dOut, AT.ncols), dZk=(dZk, AT.nrows), dZv=(dZv, AT.nrows))
+        self._v2_planes(AT, heads, alpha, de)
+        nnz = AT.col.numel()
+        if not (perm.is_cuda and perm.dtype is torch.int64 and perm.dim() == 1 and perm.numel() == nnz and perm.is_contiguous()):
+            raise _lib.PgcnError("perm must be a contiguous int64 CUDA vector of one word per entry")
+        if nnz == 0:
+            if not accumulate:
+                dZk[:AT.nrows, :F].zero_()
+                dZv[:AT.nrows, :F].zero_()
+            return True
+        self._slot_ws(AT, 2 * AT.nslots * F)
+        rc = self.lib.pgcn_gatdot_grad_cols_f32(
+            AT.rowptr.data_ptr(), AT.col.data_ptr(), AT.nrows, _ptr(AT.tasks), AT.ntasks, AT.seg, AT.nslices, _ptr(AT.fix), AT.nfix,
+            perm.data_ptr(), Zq.data_ptr(), Zq.stride(0), dOut.data_ptr(), dOut.stride(0), alpha.data_ptr(), alpha.stride(0),
+            de.data_ptr(), de.stride(0), heads, d, dZk.data_ptr(), dZk.stride(0), dZv.data_ptr(), dZv.stride(0), _ptr(AT.ws),
+            0 if AT.ws is None else AT.ws.numel(), AT.nslots, _lib.SPMM_ACCUMULATE if accumulate else 0, self._stream())
+        if rc == _lib.PGCN_EUNSUPPORTED:
+            return False
+        _lib.check(rc, "pgcn_gatdot_grad_cols_f32")
+        return True
+
     # -- the dense blocks of an attention pattern (pgcn_gat_blocks.hip, r06) ------------------------------------------
     @staticmethod
     def gat_block_bits(h3) -> torch.Tensor:
