@@ -255,6 +255,31 @@ class _GatTail(torch.autograd.Function):
         return (dX if want_dx else None, dbias) + (None,) * 9
 
 
+# The conflicts among the score options (attention, share_weights, the reference mode, attn_dropout), stated once; the constructor of
+# PGAT ("layer"), run() and the command line ("flags") each render one in their own spelling (%s: the attention, or why no sharing)
+_NO_SHARING = {"v1": "the v1 layer has one projection", "dot": "the dot layer keeps its query, key and value projections apart"}
+_CONFLICTS = {
+    "layer": ("share_weights needs attention='v2': %s", "the reference layer has the static score only (attention='%s' needs mode='standard')",
+              "attention='%s' with attn_dropout is not implemented: use attention='v1', or attn_dropout=0"),
+    "run": ("share_weights needs attention='v2': %s", "the reference layer has the static score only: attention='%s' needs standard mode",
+            "attention='%s' with attn_dropout is not implemented: use attention='v1', or attn_dropout=0"),
+    "flags": ("--share-weights needs --attention v2: %s", "--mode reference has the static score only: --attention %s needs --mode standard",
+              "--attention %s with --attn-dropout is not implemented: use --attention v1, or leave --attn-dropout out")}
+
+
+def _score_conflict(where, attention, share_weights, reference, attn_dropout):
+    """The first conflict among the score options in ``where``'s spelling, or None.  ``attention``: one of ATTENTIONS, or None = v1."""
+    attention = attention or "v1"
+    sharing, mode_, dropping = _CONFLICTS[where]
+    if share_weights and attention != "v2":
+        return sharing % _NO_SHARING[attention]
+    if attention != "v1" and reference:
+        return mode_ % attention
+    if attention != "v1" and float(attn_dropout or 0.0) > 0.0:
+        return dropping % attention
+    return None
+
+
 class PGAT(nn.Module):
     """PGAT.py:120-151.  ``out_features`` is the total width; with K heads each head has
     out_features / K columns and its own attention vector (column k of ``attention``).
@@ -297,18 +322,10 @@ class PGAT(nn.Module):
         if attention not in ATTENTIONS:
             raise ValueError("attention takes %s, got %r" % (" | ".join(ATTENTIONS), attention))
         self.version, self.share_weights = attention, bool(share_weights)
-        if self.share_weights and attention == "dot":
-            raise ValueError("share_weights needs attention='v2': the dot layer keeps its query, key and value projections apart")
-        if self.share_weights and attention != "v2":
-            raise ValueError("share_weights needs attention='v2': the v1 layer has one projection")
-        if attention == "dot" and A is not None and getattr(A, "mode", "standard") == "reference":
-            raise ValueError("the reference layer has the static score only (attention='dot' needs mode='standard')")
-        if attention == "dot" and float(attn_dropout) > 0.0:
-            raise ValueError("attention='dot' with attn_dropout is not implemented: use attention='v1', or attn_dropout=0")
-        if attention == "v2" and A is not None and getattr(A, "mode", "standard") == "reference":
-            raise ValueError("the reference layer has the static score only (attention='v2' needs mode='standard')")
-        if attention == "v2" and float(attn_dropout) > 0.0:
-            raise ValueError("attention='v2' with attn_dropout is not implemented: use attention='v1', or attn_dropout=0")
+        conflict = _score_conflict("layer", attention, self.share_weights, A is not None and getattr(A, "mode", "standard") == "reference",
+                                   attn_dropout)
+        if conflict:
+            raise ValueError(conflict)
         self.linear = nn.Linear(in_features, out_features, bias=False)
         if attention == "v2":
             if not self.share_weights:
@@ -365,6 +382,14 @@ class PGAT(nn.Module):
             return self.out_features * (1 if self.share_weights else 2)
         return self.out_features + 2 * self.heads
 
+    def _layer_state(self, K, d):
+        # the buffers that live from forward to backward belong to ONE forward: a second forward of this layer
+        # before the first one's backward (evaluation pass in between, shared weights, two graphs) gets its own
+        st = self._state
+        if st is None or st.busy or (st.heads, st.d) != (K, d):
+            st = self._state = self.A.new_layer_state(K, d)
+        return st
+
     def _forward_v2(self, H):
         K, d = self.heads, self.out_features // self.heads
         F = self.out_features
@@ -373,10 +398,7 @@ class PGAT(nn.Module):
         else:                                # both projections as ONE product over the stacked weight: n x 2F = [Zs | Zt]
             ZZ = _pgcn._LinearNoBias.apply(H, torch.cat([self.linear.weight, self.linear_t.weight], 0))
             Zs, Zt = ZZ[:, :F], ZZ[:, F:]
-        st = self._state
-        if st is None or st.busy or (st.heads, st.d) != (K, d):
-            st = self._state = self.A.new_layer_state(K, d)
-        return _gat.GatV2Aggregate.apply(self.A, st, Zt, Zs, self.attention)
+        return _gat.GatV2Aggregate.apply(self.A, self._layer_state(K, d), Zt, Zs, self.attention)
 
     def _forward_dot(self, H):
         K, d = self.heads, self.out_features // self.heads
@@ -384,10 +406,7 @@ class PGAT(nn.Module):
         # the three projections as ONE product over the stacked weight: n x 3F = [Zk | Zv | Zq] -- keys and values side by side, so the
         # rows that cross ranks (and, on one rank, the gather panel itself) are one contiguous slice
         ZZ = _pgcn._LinearNoBias.apply(H, torch.cat([self.linear_k.weight, self.linear.weight, self.linear_q.weight], 0))
-        st = self._state
-        if st is None or st.busy or (st.heads, st.d) != (K, d):
-            st = self._state = self.A.new_layer_state(K, d)
-        return _gat.GatDotAggregate.apply(self.A, st, ZZ[:, 2 * F:], ZZ[:, :F], ZZ[:, F:2 * F])
+        return _gat.GatDotAggregate.apply(self.A, self._layer_state(K, d), ZZ[:, 2 * F:], ZZ[:, :F], ZZ[:, F:2 * F])
 
     def forward(self, H):
         K, d = self.heads, self.out_features // self.heads
@@ -404,11 +423,7 @@ class PGAT(nn.Module):
         ws1 = torch.einsum("kdi,dk->ki", Wh, self.attention[:d])
         ws2 = torch.einsum("kdi,dk->ki", Wh, self.attention[d:])
         ZS = _pgcn._LinearNoBias.apply(H, torch.cat([W, ws2, ws1], 0))     # n x (F + 2K) = [Z | z2 | z1]
-        # the buffers that live from forward to backward belong to ONE forward: a second forward of this layer
-        # before the first one's backward (evaluation pass in between, shared weights, two graphs) gets its own
-        st = self._state
-        if st is None or st.busy or (st.heads, st.d) != (K, d):
-            st = self._state = self.A.new_layer_state(K, d)
+        st = self._layer_state(K, d)
         if self._attn_drop is not None:                                 # (a layer without the option never touches the field)
             st.drop = self._attn_drop if self.training else None
         out = _gat.GatAggregatePacked.apply(self.A, st, ZS)             # :144-149 on the stored entries
@@ -697,18 +712,9 @@ def run(rank, size, nlayers, nfeatures, path_A, path_partvec, backend, epochs=No
             raise ValueError("attn_dropout takes a probability in [0, 1), got %r" % (data["attn_dropout"],))
     if data.get("attention") not in (None,) + ATTENTIONS:
         raise ValueError("attention takes %s, got %r" % (" | ".join(ATTENTIONS), data.get("attention")))
-    if data.get("share_weights") and data.get("attention") == "dot":
-        raise ValueError("share_weights needs attention='v2': the dot layer keeps its query, key and value projections apart")
-    if data.get("share_weights") and data.get("attention") != "v2":
-        raise ValueError("share_weights needs attention='v2': the v1 layer has one projection")
-    if data.get("attention") == "dot" and mode == "reference":
-        raise ValueError("the reference layer has the static score only: attention='dot' needs standard mode")
-    if data.get("attention") == "dot" and float(data.get("attn_dropout") or 0.0) > 0.0:
-        raise ValueError("attention='dot' with attn_dropout is not implemented: use attention='v1', or attn_dropout=0")
-    if data.get("attention") == "v2" and mode == "reference":
-        raise ValueError("the reference layer has the static score only: attention='v2' needs standard mode")
-    if data.get("attention") == "v2" and float(data.get("attn_dropout") or 0.0) > 0.0:
-        raise ValueError("attention='v2' with attn_dropout is not implemented: use attention='v1', or attn_dropout=0")
+    conflict = _score_conflict("run", data.get("attention"), data.get("share_weights"), mode == "reference", data.get("attn_dropout"))
+    if conflict:
+        raise ValueError(conflict)
     control = {k: data.pop(k) for k in list(data) if k in _nodeloss.CONTROL}
     control = {k: v for k, v in control.items() if v is not None}
     if control:            # each value, what goes together, the horizon against the warm-up: before any collective
@@ -910,18 +916,9 @@ def main(argv):
             mode = arg
         elif opt == '--heads':
             heads = int(arg)
-    if score.get("share_weights") and score.get("attention") == "dot":
-        refuse("--share-weights needs --attention v2: the dot layer keeps its query, key and value projections apart")
-    if score.get("share_weights") and score.get("attention") != "v2":
-        refuse("--share-weights needs --attention v2: the v1 layer has one projection")
-    if score.get("attention") == "dot" and mode == "reference":
-        refuse("--mode reference has the static score only: --attention dot needs --mode standard")
-    if score.get("attention") == "dot" and data.get("attn_dropout", 0.0) > 0.0:
-        refuse("--attention dot with --attn-dropout is not implemented: use --attention v1, or leave --attn-dropout out")
-    if score.get("attention") == "v2" and mode == "reference":
-        refuse("--mode reference has the static score only: --attention v2 needs --mode standard")
-    if score.get("attention") == "v2" and data.get("attn_dropout", 0.0) > 0.0:
-        refuse("--attention v2 with --attn-dropout is not implemented: use --attention v1, or leave --attn-dropout out")
+    conflict = _score_conflict("flags", score.get("attention"), score.get("share_weights"), mode == "reference", data.get("attn_dropout"))
+    if conflict:
+        refuse(conflict)
     if score.get("attention") == "v1":
         score.pop("attention")                          # (the default: the call of before)
     files = [k for k in ("features", "labels", "split") if k in data]

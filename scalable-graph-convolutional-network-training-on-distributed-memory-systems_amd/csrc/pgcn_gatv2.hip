@@ -21,20 +21,13 @@
 // adds in slot order; da is summed wave -> workgroup (LDS, wave order) -> work-space row per workgroup -> two passes in index order.
 // Fixed summation order everywhere, no atomics: two runs give the same bits.  Plain vector loads and stores.
 //
-// The row pass is TWO passes over the forward structure.  Mathematically sum_j de_ij = 0 for every row and head, and dZt and da
-// multiply de by quantities of one sign and size along a row: an error that all entries of a row SHARE -- the rounding of t_i, or of
-// out_i -- does not cancel but comes back times sum_j alpha_ij LReLU(x_ij).  Where a row's softmax is nearly one-hot (scores of
-// magnitude ~150) that shared error is the result: measured on such rows, da was 3.4e-3 from float64 with t = <dOut_i, out_i> from a
-// separate dot and 2.3e-3 with de = alpha <dOut_i, Zs_j - out_i>, where the float32 statement of the definition is at 1.1e-3
-// (tests/test_gatv2_gpu.py).  So pass 1 (gatv2_dalpha_kernel) writes q_ij = <dOut_i, Zs_j - out_i> into the de planes and
-// T_i = sum_j alpha_ij q_ij (slots and fix-up for cut rows), and pass 2 forms de_ij = alpha_ij (q_ij - T_i) from THE SAME q: the rows
-// of de then sum to zero to rounding, as in torch's own softmax backward.  One more gather of Zs (it is the pass's second touch of
-// the same rows) buys that.
+// The row pass is TWO passes over the forward structure: pass 1 (attn_dalpha_kernel, shared with pgcn_gatdot.hip) writes q_ij into the
+// de planes and T_i, pass 2 forms de_ij = alpha_ij (q_ij - T_i) from the same q.  pgcn_gat_tasks.h has the kernel and the reason.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
 
-#include "pgcn_gat_tasks.h"      // Plan / Task / pick_task, Lane / pick_lane: shared with pgcn_gatdot.hip
+#include "pgcn_gat_tasks.h"      // Plan / Task / Lane, put_row, attn_dalpha_kernel, check_plan / bad_rows: shared with pgcn_gatdot.hip
 
 namespace {
 
@@ -50,24 +43,6 @@ __device__ __forceinline__ void load_a(float (&av)[4], const float *__restrict__
 __device__ __forceinline__ float head_sum(float v, int hl) {
     for (int o = hl >> 1; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
     return v;
-}
-
-// the output row of a task: straight into C (its row's only task) or into its slot
-__device__ __forceinline__ void put_row(const Task &t, const Lane &l, float (&acc)[4], float *__restrict__ C, int64_t ldc,
-                                        float *__restrict__ partial, int32_t F, uint32_t flags) {
-    if (!t.act || !l.fact) return;
-    if (t.dst >= 0) {
-        vstore<4>(partial + (int64_t)t.dst * F + l.fcol, acc);
-    } else {
-        float *cp = C + t.row * ldc + l.fcol;
-        if (flags & PGCN_SPMM_ACCUMULATE) {
-            float old[4];
-            vload<4>(old, cp);
-#pragma unroll
-            for (int v = 0; v < 4; ++v) acc[v] += old[v];
-        }
-        vstore<4>(cp, acc);
-    }
 }
 
 // ---- e = a . LeakyReLU(Zt_i + Zs_j) --------------------------------------------------------------------------------------------------
@@ -168,60 +143,6 @@ __global__ __launch_bounds__(kThreads) void gatv2_softmax_kernel(const int64_t *
     }
     s = group_reduce<TPR, false>(s, red);  // >= 1: the entry of the maximum contributes exp(0)
     for (int64_t q = b + lane; q < e; q += TPR) p[q] = p[q] / s;
-}
-
-// ---- pass 1 over the forward structure: q_ij = <dOut_i, Zs_j - out_i> into the de planes, T_i = sum_j alpha_ij q_ij --------------------
-__global__ __launch_bounds__(kThreads) void gatv2_dalpha_kernel(Plan pl, const float *__restrict__ Zs, int64_t lds,
-                                                                const float *__restrict__ alpha, int64_t stride_a,
-                                                                const float *__restrict__ dOut, int64_t ldo, const float *__restrict__ out,
-                                                                int64_t ldout, int32_t heads, int32_t d, int32_t F, float *__restrict__ de,
-                                                                int64_t stride_de, float *__restrict__ T, float *__restrict__ partial) {
-    const Task t = pick_task(pl);
-    if (!t.act) return;                        // (wave-uniform; no workgroup barrier below)
-    const int lane = threadIdx.x & 63;
-    const Lane l = pick_lane(F, d);
-    const int hl = d >> 2;
-    float g0[4] = {0.f, 0.f, 0.f, 0.f}, o4[4] = {0.f, 0.f, 0.f, 0.f};
-    if (l.fact) {
-        vload<4>(g0, dOut + t.row * ldo + l.fcol);
-        vload<4>(o4, out + t.row * ldout + l.fcol);
-    }
-    const float *ak = alpha + (int64_t)l.head * stride_a + t.kbeg;
-    float *dk = de + (int64_t)l.head * stride_de + t.kbeg;
-    float tacc = 0.f;                          // (the same on every lane of a head)
-    const int last = t.len > 0 ? t.len - 1 : 0;
-    for (int base = 0; base < t.len; base += 64) {
-        const int el = base + lane < last ? base + lane : last;
-        const int32_t cl = pl.col[t.kbeg + el];
-        const int cnt = min(64, t.len - base);
-        for (int e0 = 0; e0 < cnt; e0 += kBatch) {
-            float x[kBatch][4], al[kBatch];
-#pragma unroll
-            for (int u = 0; u < kBatch; ++u) {
-                const int e = e0 + u < cnt ? e0 + u : cnt - 1;
-                const int32_t c = __shfl(cl, e, 64);
-                vload<4>(x[u], Zs + (int64_t)c * lds + l.fsafe);
-                al[u] = ak[base + e];
-            }
-            float p[kBatch];
-#pragma unroll
-            for (int u = 0; u < kBatch; ++u)
-                p[u] = (g0[0] * (x[u][0] - o4[0]) + g0[1] * (x[u][1] - o4[1])) + (g0[2] * (x[u][2] - o4[2]) + g0[3] * (x[u][3] - o4[3]));
-            for (int o = hl >> 1; o > 0; o >>= 1) {
-#pragma unroll
-                for (int u = 0; u < kBatch; ++u) p[u] += __shfl_xor(p[u], o, 64);
-            }
-            float pm = p[0];
-#pragma unroll
-            for (int u = 0; u < kBatch; ++u) {
-                tacc += e0 + u < cnt ? al[u] * p[u] : 0.f;
-                pm = l.sub == u ? p[u] : pm;
-            }
-            const int e = e0 + l.sub;
-            if (l.fact && l.sub < kBatch && e < cnt) dk[base + e] = pm;
-        }
-    }
-    if (l.fact && l.sub == 0) (t.dst >= 0 ? partial + (int64_t)t.dst * heads : T + t.row * heads)[l.head] = tacc;
 }
 
 // ---- pass 2: de = alpha (q - T) in place, dZt and da (row i owns the work) ------------------------------------------------------------
@@ -354,39 +275,9 @@ __global__ __launch_bounds__(kThreads) void gatv2_grad_cols_kernel(Plan pl, cons
     put_row(t, l, acc, dZs, ldz, partial, F, flags);
 }
 
-// ---- host side ---------------------------------------------------------------------------------------------------------------------
-int64_t plan_grid(bool has_tasks, int64_t nrows, int64_t ntasks, const int64_t *seg, int32_t nslices) {
-    if (nslices > 1) {
-        int64_t longest = 0;
-        for (int i = 0; i < nslices; ++i) longest = seg[i + 1] - seg[i] > longest ? seg[i + 1] - seg[i] : longest;
-        return ((longest + kWaves - 1) / kWaves) * nslices;
-    }
-    const int64_t nt = has_tasks ? ntasks : nrows;
-    return (nt + kWaves - 1) / kWaves;
-}
-
-// sizes and shape limits shared by the three task kernels; PGCN_OK, or the code to return
-int check_plan(const char *who, int32_t heads, int32_t d, int64_t nrows, const int32_t *tasks, int64_t ntasks, const int64_t *seg,
-               int32_t nslices, Plan *pl, int64_t *grid) {
-    if (heads <= 0 || d <= 0 || nrows < 0 || ntasks < 0 || nslices < 1 || nslices > PGCN_MAX_SLICES || (nslices > 1 && (!seg || !tasks)))
-        return pgcn_set_error2(PGCN_EINVAL, who, "bad sizes");
-    const int hl = d / 4;
-    if (heads > kMaxHeads || (int64_t)heads * d > 256 || d % 4 || hl < kBatch || (hl & (hl - 1)))
-        return pgcn_set_error2(PGCN_EUNSUPPORTED, who, "needs heads <= 8, d = 32, 64, 128 or 256 and heads * d <= 256");
-    if (nslices > 1 && (seg[0] != 0 || seg[nslices] != ntasks)) return pgcn_set_error2(PGCN_EINVAL, who, "seg does not cover the task list");
-    pl->tasks = reinterpret_cast<const int4 *>(tasks);
-    pl->ntasks = tasks ? ntasks : nrows;
-    pl->nrows = nrows;
-    pl->nslices = nslices;
-    for (int i = 0; i <= PGCN_MAX_SLICES; ++i) pl->seg.v[i] = (nslices > 1 && i <= nslices) ? seg[i] : 0;
-    *grid = plan_grid(tasks != nullptr, nrows, ntasks, seg, nslices);
-    if (*grid > 0x7fffffffLL) return pgcn_set_error2(PGCN_EINVAL, who, "too many tasks for one launch");
-    return PGCN_OK;
-}
-
-bool bad_rows(const float *p, int64_t ld) { return ld % 4 || (uintptr_t)p % 16; }
-
 }  // namespace
+
+// ---- host side (plan_grid, check_plan, bad_rows: pgcn_gat_tasks.h) -------------------------------------------------------------------
 
 extern "C" int pgcn_gatv2_scores_f32(const int64_t *rowptr, const int32_t *col, int64_t nrows, const int32_t *tasks, int64_t ntasks,
                                      const int64_t *seg, int32_t nslices, const float *Zt, int64_t ldt, const float *Zs, int64_t lds,
@@ -466,7 +357,7 @@ extern "C" int pgcn_gatv2_grad_rows_f32(const int64_t *rowptr, const int32_t *co
     const int64_t groups = (grid + kDaGroup - 1) / kDaGroup;
     if (partial_ws_elems < nslots * F || da_ws_elems < (grid + groups) * F)
         return pgcn_set_error2(PGCN_ENOMEM, who, "work-space too small (pgcn_gatv2_da_ws_elems)");
-    hipLaunchKernelGGL(gatv2_dalpha_kernel, dim3((unsigned)grid), dim3(kThreads), 0, s, pl, Zs, lds, alpha, alpha_stride, dOut, ldo, out, ldout,
+    hipLaunchKernelGGL(attn_dalpha_kernel, dim3((unsigned)grid), dim3(kThreads), 0, s, pl, Zs, lds, alpha, alpha_stride, dOut, ldo, out, ldout,
                        heads, d, (int32_t)F, de, de_stride, t_ws, partial_ws);
     PGCN_HIP_CHECK(hipGetLastError());
     if (nfix > 0) {                            // T of the cut rows, in slot order, before pass 2 takes the slots for dZt

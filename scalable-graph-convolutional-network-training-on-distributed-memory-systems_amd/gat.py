@@ -45,8 +45,8 @@ order of ``fwd`` (csrc/pgcn_gatv2.hip).
     backward  over fwd, two passes: q = <dOut_i, Zs_j - out_i> and T_i = sum_j alpha q, then de = alpha (q - T), dZt, da (pgcn_gatv2_grad_rows_f32); alpha and de into the
               transposed order (pgcn_csr_permute_f32); over bwd: dZs (pgcn_gatv2_grad_cols_f32); halo rows of dZs travel home and are
               ADDED (the reverse all-to-all-v of the v1 path).  da is this rank's partial sum, like any weight gradient.
-The unsplit structures only: the pass waits for the halo rows.  CPU tensors, providers without the four methods and shapes the kernels
-refuse take the same arithmetic as tensor operations over the entry list (``_v2_forward`` / ``_v2_backward``).
+The unsplit structures only: the pass waits for the halo rows.  CPU tensors, providers without the methods and shapes the kernels
+refuse take the same arithmetic as tensor operations over the entry list (``_scored_forward_entries`` / ``_scored_backward_entries``).
 
 Scaled dot-product attention (``GatEngine.forward_dot`` / ``backward_dot``, ``GatDotAggregate``; standard mode): the score of the graph
 transformers, e_ijk = <Zq[i,k,:], Zk[j,k,:]> / sqrt(d), with separate values: out_i = sum_j alpha_ij Zv_j (csrc/pgcn_gatdot.hip;
@@ -58,7 +58,8 @@ DESIGN.md section 4).  The planes, the softmax and the multi-head product are th
               over bwd: dZk and dZv in ONE walk that reads the forward-order planes through the entry permutation
               (pgcn_gatdot_grad_cols_f32; nothing is permuted) into one gradient panel of the forward panel's layout, whose halo rows
               travel home and are ADDED (the reverse all-to-all-v, at width 2 Fp).
-CPU tensors, providers without the three methods and shapes the kernels refuse take ``_dot_forward`` / ``_dot_backward``.
+The composed route is GATv2's.  Both layers run ONE path, ``_scored_forward`` / ``_scored_backward``; what differs -- the panel's
+parts, the row's own operand, the kernels, the score and the chain from de to the inputs -- is a ``_Scored`` each (``_V2``, ``_DOT``).
 """
 from __future__ import annotations
 
@@ -263,7 +264,7 @@ class GatEngine(BoundaryExchange):
         self._scratch = {}
         self._gid_cache = {}
         self._entry_cache = None
-        self._v2_entries = None
+        self._entries = None               # (rows, cols) of the forward structure's entries (built on demand)
         self.sliced_grad = _T.gat_sliced   # XCD-sliced edge gradient where the shape allows
         # the edge gradient over the balanced tasks of the SpMM plan (pgcn_gat_edge_grad_tasks_f32)
         self.task_grad = _T.gat_task_grad and hasattr(kernels, "gat_edge_grad_tasks")
@@ -607,269 +608,171 @@ class GatEngine(BoundaryExchange):
         dZc[:, F:F + K].index_add_(0, cols, de)
         return self._finish_backward(st, dOut, dZc, ds1, pack)
 
-    # -- GATv2: the dynamic score (csrc/pgcn_gatv2.hip) ---------------------------------------------------------------------------------
-    def _v2_kernels(self, K: int, d: int) -> bool:
-        return all(hasattr(self.k, m) for m in ("gatv2_scores", "gatv2_softmax", "gatv2_grad_rows", "gatv2_grad_cols", "csr_permute",
-                                                "spmm_heads")) and self.covers(K, d)
-
-    def _v2_entry_list(self):
-        if self._v2_entries is None:
-            rp = self.graph.fwd.rowptr.to(torch.int64).cpu()
-            rows = torch.repeat_interleave(torch.arange(self.n_local, dtype=torch.int64), rp[1:] - rp[:-1])
-            self._v2_entries = (rows.to(self.device), self.graph.fwd.col.to(torch.int64).to(self.device))
-        return self._v2_entries
-
+    # -- scores that need both ends' rows: GATv2 and the scaled dot product.  The path is stated once; a ``_Scored`` (below: _V2, _DOT) has
+    # -- what differs (csrc/pgcn_gatv2.hip, csrc/pgcn_gatdot.hip, csrc/pgcn_gat_tasks.h) ------------------------------------------------
     def forward_v2(self, st: GatLayerState, Zt: torch.Tensor, Zs: torch.Tensor, a: torch.Tensor) -> torch.Tensor:
         """out_i = sum_j alpha_ij Zs_j with alpha the softmax over row i of e_ijk = sum_c a[c,k] LeakyReLU(Zt[i,k,c] + Zs[j,k,c]).
         Zt, Zs: [n_local, heads * d] of the owned rows (column slices of one projection are fine); a: [d, heads]."""
-        K, d = st.heads, st.d
-        F = K * d
-        n_p, n_h = self.n_local, self.n_halo
-        if self.mode_id != 0:
-            raise ValueError("GATv2 needs mode='standard': the reference layer has the static score only")
-        if st.drop is not None and st.drop.on:
-            raise ValueError("GATv2 with attention dropout is not implemented: use attention='v1' with attn_dropout, or attn_dropout=0")
-        if Zt.shape != (n_p, F) or Zs.shape != (n_p, F) or tuple(a.shape) != (d, K):
-            raise ValueError("expected Zt / Zs %s and a %s" % ((n_p, F), (d, K)))
-        Zt, a = Zt.detach(), a.detach().contiguous()
-        Fp = (F + 3) // 4 * 4
-        # ONE rank only: the projection itself is the gather panel (never written through).  A rank of several without halo rows still
-        # has its part in the all-to-all-v below -- its peers wait for it -- so it takes the copy-in branch like every other rank
-        if self.size == 1 and n_h == 0 and Zs.stride(1) == 1 and Zs.stride(0) % 4 == 0 and Zs.data_ptr() % 16 == 0 \
-                and Zs.dtype is torch.float32 and n_p > 0:
-            st.Zc = Zc = Zs.detach()
-            st.Zc_borrowed = True
-        else:
-            if st.Zc is None or st.Zc_borrowed or st.Zc.shape != (n_p + n_h, Fp):
-                st.Zc = torch.zeros((n_p + n_h, Fp), dtype=torch.float32, device=self.device)
-                st.Zc_borrowed = False
-            Zc = st.Zc
-            Zc[:n_p, :F].copy_(Zs)
-            if self.size > 1:                    # the rows of Zs only: Zt is row i's own
-                send = self._slab("gat_send", self.n_send, Fp)
-                self.k.gather_rows(Zc[:n_p], self.send_idx, send)
-                for w in self._exchange_all(send, self.round_send_off, Zc[n_p:], self.round_recv_off, Fp):
-                    w()
-        if Zt.stride(1) != 1:
-            Zt = Zt.contiguous()
-        out = torch.empty((n_p, F), dtype=torch.float32, device=self.device)
-        st.Zt, st.att, st.alpha_e, st.dropped, st.entries, st.fused = Zt, a, None, None, None, False
-        done = False
-        if self._v2_kernels(K, d):
-            if st.alpha is None or st.alpha.shape != (K, max(self.nnz, 1)):
-                st.alpha = torch.zeros((K, max(self.nnz, 1)), dtype=torch.float32, device=self.device)
-                st.fwd_heads = None
-            if self.k.gatv2_scores(self.fwd, Zt, Zc, a, self.slope, st.alpha, K, d):
-                self.k.gatv2_softmax(self.fwd, st.alpha, K)
-                if self.nnz == 0:
-                    out.zero_()
-                elif not self.k.spmm_heads(self.fwd, st.alpha, Zc, out, K, d):
-                    raise RuntimeError("the multi-head product refused a shape the GATv2 score kernel took")
-                done = True
-        if not done:
-            self._v2_forward(st, Zt, Zc, a, out)
-        st.out = out
-        return out
+        self._scored_refuse(_V2, st)
+        if Zt.shape != (self.n_local, st.heads * st.d) or Zs.shape != Zt.shape or tuple(a.shape) != (st.d, st.heads):
+            raise ValueError("expected Zt / Zs %s and a %s" % ((self.n_local, st.heads * st.d), (st.d, st.heads)))
+        return self._scored_forward(_V2, st, Zt, (Zs,), a.detach().contiguous())
 
     def backward_v2(self, st: GatLayerState, dOut: torch.Tensor):
         """(dZt, dZs, da) of the last ``forward_v2`` for the owned rows; da [d, heads] is THIS rank's partial sum."""
-        K, d = st.heads, st.d
-        F = K * d
-        n_p, n_h = self.n_local, self.n_halo
-        Fp = (F + 3) // 4 * 4
-        dOut = dOut.contiguous()
-        dZc = self._slab("gat_dzs", n_p + n_h, Fp)[:n_p + n_h]
-        dZt = None
-        if st.alpha_e is None:
-            de = self._plane_scratch("v2_de", K)
-            dZt = torch.empty((n_p, F), dtype=torch.float32, device=self.device)
-            da = torch.empty((d, K), dtype=torch.float32, device=self.device)
-            if self.k.gatv2_grad_rows(self.fwd, st.Zt, st.Zc, st.att, st.alpha, dOut, st.out, self.slope, de, dZt, da, K, d):
-                alpha_t, de_t = self._plane_scratch("v2_alpha_t", K), self._plane_scratch("v2_de_t", K)
-                self.k.csr_permute(st.alpha, self.perm, alpha_t)
-                self.k.csr_permute(de, self.perm, de_t)
-                if not self.k.gatv2_grad_cols(self.bwd, st.Zc, st.Zt, dOut, st.att, alpha_t, de_t, self.slope, dZc, K, d):
-                    dZt = None
-            else:
-                dZt = None
-        if dZt is None:                          # the composed route, or a kernel refused operands its forward twin took
-            dZt, da = self._v2_backward(st, dOut, dZc)
-        if Fp > F:
-            dZc[:, F:].zero_()
-        if self.size > 1:                        # partial rows of dZs back to their owners, ADDED
-            back = self._slab("gat_send", self.n_send, Fp)
-            waits = self._exchange_all(dZc[n_p:], self.round_recv_off, back, self.round_send_off, Fp, tag="backward")
-            for r in range(self.rounds):
-                waits[r]()
-                self.k.spmm(self.unpack[r], back, dZc[:n_p], accumulate=True)
-        return dZt, dZc[:n_p, :F].clone(), da
-
-    # -- ... as tensor operations over the entry list (CPU tensors, other providers, shapes the kernels refuse) ------------------------
-    def _v2_forward(self, st: GatLayerState, Zt: torch.Tensor, Zc: torch.Tensor, a: torch.Tensor, out: torch.Tensor):
-        """The definition over the entry list, formed in DOUBLE and rounded once per output: this route is the fall-back and not the
-        hot path, and its sums over a row's entries (and, for da, over all entries) then add nothing to the layer's float32 error."""
-        K, d = st.heads, st.d
-        F, n_p = K * d, self.n_local
-        rows, cols = self._v2_entry_list()
-        f64 = torch.float64
-        Zj = Zc[:, :F].reshape(-1, K, d)[cols].to(f64)
-        x = Zt.reshape(n_p, K, d)[rows].to(f64) + Zj
-        e = (torch.where(x > 0, x, x * self.slope) * a.to(f64).t().unsqueeze(0)).sum(-1)
-        m = torch.full((n_p, K), -float("inf"), dtype=f64, device=e.device).scatter_reduce(0, rows.unsqueeze(1).expand(-1, K), e, "amax",
-                                                                                           include_self=True)
-        ex = torch.exp(e - m[rows])
-        D = torch.zeros((n_p, K), dtype=f64, device=e.device).index_add_(0, rows, ex)
-        st.alpha_e = ex / D[rows]                                              # (kept in double for the backward)
-        out.copy_(torch.zeros((n_p, K, d), dtype=f64, device=e.device).index_add_(0, rows, st.alpha_e.unsqueeze(-1) * Zj).view(n_p, F))
-
-    def _v2_backward(self, st: GatLayerState, dOut: torch.Tensor, dZc: torch.Tensor):
-        K, d = st.heads, st.d
-        F, n_p, n_h = K * d, self.n_local, self.n_halo
-        rows, cols = self._v2_entry_list()
-        f64 = torch.float64
-        alpha = st.alpha_e if st.alpha_e is not None else st.alpha[:, :self.nnz].t().to(f64)
-        G = dOut.view(n_p, K, d).to(f64)
-        Gi, Zj = G[rows], st.Zc[:, :F].reshape(-1, K, d)[cols].to(f64)
-        q = (Gi * (Zj - st.out.view(n_p, K, d)[rows].to(f64))).sum(-1)        # = <dOut_i, Zs_j> - t_i, and de as the kernels form it:
-        de = alpha * (q - torch.zeros((n_p, K), dtype=f64, device=q.device).index_add_(0, rows, alpha * q)[rows])
-        x = st.Zt.reshape(n_p, K, d)[rows].to(f64) + Zj
-        pos = x > 0
-        w = de.unsqueeze(-1) * st.att.to(f64).t().unsqueeze(0)
-        w = torch.where(pos, w, w * self.slope)
-        dZt = torch.zeros((n_p, K, d), dtype=f64, device=self.device).index_add_(0, rows, w).view(n_p, F).to(torch.float32)
-        dZs = torch.zeros((n_p + n_h, K, d), dtype=f64, device=self.device).index_add_(0, cols, w + alpha.unsqueeze(-1) * Gi)
-        dZc[:, :F].copy_(dZs.view(n_p + n_h, F))
-        da = (de.unsqueeze(-1) * torch.where(pos, x, x * self.slope)).sum(0).t().contiguous().to(torch.float32)
-        return dZt, da
-
-    # -- scaled dot-product attention: separate queries, keys and values (csrc/pgcn_gatdot.hip) -----------------------------------------
-    def _dot_kernels(self, K: int, d: int) -> bool:
-        return all(hasattr(self.k, m) for m in ("gatdot_scores", "gatv2_softmax", "gatdot_grad_rows", "gatdot_grad_cols",
-                                                "spmm_heads")) and self.covers(K, d)
+        (dZt, da), (dZs,) = self._scored_backward(_V2, st, dOut)
+        return dZt, dZs, da
 
     def forward_dot(self, st: GatLayerState, Zq: torch.Tensor, Zk: torch.Tensor, Zv: torch.Tensor) -> torch.Tensor:
         """out_i = sum_j alpha_ij Zv_j with alpha the softmax over row i of e_ijk = <Zq[i,k,:], Zk[j,k,:]> / sqrt(d).  Zq, Zk, Zv:
         [n_local, heads * d] of the owned rows (column slices of one projection are fine)."""
-        K, d = st.heads, st.d
-        F = K * d
-        n_p, n_h = self.n_local, self.n_halo
-        if self.mode_id != 0:
-            raise ValueError("dot-product attention needs mode='standard': the reference layer has the static score only")
-        if st.drop is not None and st.drop.on:
-            raise ValueError("dot-product attention with attention dropout is not implemented: use attention='v1' with attn_dropout, "
-                             "or attn_dropout=0")
-        if Zq.shape != (n_p, F) or Zk.shape != (n_p, F) or Zv.shape != (n_p, F):
-            raise ValueError("expected Zq / Zk / Zv %s" % ((n_p, F),))
-        Zq, Zk, Zv = Zq.detach(), Zk.detach(), Zv.detach()
-        Fp = (F + 3) // 4 * 4
-        # ONE rank only, and [Zk | Zv] adjacent column slices of one aligned projection: they ARE the gather panel (never written
-        # through).  A rank of several without halo rows still has its part in the all-to-all-v below -- its peers wait for it
-        if self.size == 1 and n_h == 0 and n_p > 0 and Fp == F and Zk.dtype is torch.float32 and Zv.dtype is torch.float32 \
-                and Zk.stride(1) == 1 and Zv.stride(1) == 1 and Zk.stride(0) == Zv.stride(0) >= 2 * F and Zk.stride(0) % 4 == 0 \
-                and Zk.data_ptr() % 16 == 0 and Zv.data_ptr() == Zk.data_ptr() + 4 * F \
-                and Zk.untyped_storage().data_ptr() == Zv.untyped_storage().data_ptr():
-            st.Zc = Zc = Zk.as_strided((n_p, 2 * F), (Zk.stride(0), 1))
-            st.Zc_borrowed = True
-        else:
-            if st.Zc is None or st.Zc_borrowed or st.Zc.shape != (n_p + n_h, 2 * Fp):
-                st.Zc = torch.zeros((n_p + n_h, 2 * Fp), dtype=torch.float32, device=self.device)
-                st.Zc_borrowed = False
-            Zc = st.Zc
-            Zc[:n_p, :F].copy_(Zk)
-            Zc[:n_p, Fp:Fp + F].copy_(Zv)
-            if self.size > 1:                    # keys and values of the boundary rows in one exchange; Zq is row i's own
-                send = self._slab("gat_send", self.n_send, 2 * Fp)
-                self.k.gather_rows(Zc[:n_p], self.send_idx, send)
-                for w in self._exchange_all(send, self.round_send_off, Zc[n_p:], self.round_recv_off, 2 * Fp):
-                    w()
-        if Zq.stride(1) != 1:
-            Zq = Zq.contiguous()
-        out = torch.empty((n_p, F), dtype=torch.float32, device=self.device)
-        st.Zq, st.alpha_e, st.dropped, st.entries, st.fused = Zq, None, None, None, False
-        done = False
-        if self._dot_kernels(K, d):
-            if st.alpha is None or st.alpha.shape != (K, max(self.nnz, 1)):
-                st.alpha = torch.zeros((K, max(self.nnz, 1)), dtype=torch.float32, device=self.device)
-                st.fwd_heads = None
-            if self.k.gatdot_scores(self.fwd, Zq, Zc[:, :F], st.alpha, K, d):
-                self.k.gatv2_softmax(self.fwd, st.alpha, K)
-                if self.nnz == 0:
-                    out.zero_()
-                elif not self.k.spmm_heads(self.fwd, st.alpha, Zc[:, Fp:Fp + F], out, K, d):
-                    raise RuntimeError("the multi-head product refused a shape the dot-product score kernel took")
-                done = True
-        if not done:
-            self._dot_forward(st, Zq, Zc, out)
-        st.out = out
-        return out
+        self._scored_refuse(_DOT, st)
+        if Zq.shape != (self.n_local, st.heads * st.d) or Zk.shape != Zq.shape or Zv.shape != Zq.shape:
+            raise ValueError("expected Zq / Zk / Zv %s" % ((self.n_local, st.heads * st.d),))
+        return self._scored_forward(_DOT, st, Zq, (Zk, Zv))
 
     def backward_dot(self, st: GatLayerState, dOut: torch.Tensor):
         """(dZq, dZk, dZv) of the last ``forward_dot`` for the owned rows."""
+        (dZq,), (dZk, dZv) = self._scored_backward(_DOT, st, dOut)
+        return dZq, dZk, dZv
+
+    def _scored_refuse(self, sc: "_Scored", st: GatLayerState) -> None:
+        if self.mode_id != 0:
+            raise ValueError("%s needs mode='standard': the reference layer has the static score only" % sc.layer)
+        if st.drop is not None and st.drop.on:
+            raise ValueError("%s with attention dropout is not implemented: use attention='v1' with attn_dropout, or attn_dropout=0"
+                             % sc.layer)
+
+    def _scored_forward(self, sc: "_Scored", st: GatLayerState, own: torch.Tensor, parts, att: Optional[torch.Tensor] = None):
+        """``parts``: the operands of the other end, one Fp-wide part of the gather panel each (Fp = F padded to 4; part i in columns
+        [i Fp, i Fp + F)): the scores gather the first, the aggregation the last.  ``own``, the row's own operand, never leaves its rank."""
+        K, d = st.heads, st.d
+        F = K * d
+        n_p, n_h = self.n_local, self.n_halo
+        Fp = (F + 3) // 4 * 4
+        W = len(parts) * Fp
+        own, parts = own.detach(), [Z.detach() for Z in parts]
+        # ONE rank only: the projection itself is the gather panel (never written through) where ``sc.borrow`` finds it fit.  A rank of
+        # several without halo rows still has its part in the all-to-all-v below -- its peers wait for it -- so it takes the copy-in
+        # branch like every other rank
+        Zc = sc.borrow(parts, F, Fp) if self.size == 1 and n_h == 0 and n_p > 0 else None
+        if Zc is not None:
+            st.Zc, st.Zc_borrowed = Zc, True
+        else:
+            if st.Zc is None or st.Zc_borrowed or st.Zc.shape != (n_p + n_h, W):
+                st.Zc = torch.zeros((n_p + n_h, W), dtype=torch.float32, device=self.device)
+                st.Zc_borrowed = False
+            Zc = st.Zc
+            for Z, part in zip(parts, _panel_parts(Zc[:n_p], len(parts), F, Fp)):
+                part.copy_(Z)
+            if self.size > 1:                    # the boundary rows of every part in ONE exchange
+                send = self._slab("gat_send", self.n_send, W)
+                self.k.gather_rows(Zc[:n_p], self.send_idx, send)
+                for w in self._exchange_all(send, self.round_send_off, Zc[n_p:], self.round_recv_off, W):
+                    w()
+        if own.stride(1) != 1:
+            own = own.contiguous()
+        out = torch.empty((n_p, F), dtype=torch.float32, device=self.device)
+        setattr(st, sc.own, own)
+        if att is not None:
+            st.att = att
+        st.alpha_e, st.dropped, st.entries, st.fused = None, None, None, False
+        P = _panel_parts(Zc, len(parts), F, Fp)
+        done = False
+        if all(hasattr(self.k, m) for m in sc.kernels) and self.covers(K, d):
+            if st.alpha is None or st.alpha.shape != (K, max(self.nnz, 1)):
+                st.alpha = torch.zeros((K, max(self.nnz, 1)), dtype=torch.float32, device=self.device)
+                st.fwd_heads = None
+            if sc.scores(self, st, P, st.alpha):
+                self.k.gatv2_softmax(self.fwd, st.alpha, K)
+                if self.nnz == 0:
+                    out.zero_()
+                elif not self.k.spmm_heads(self.fwd, st.alpha, P[-1], out, K, d):
+                    raise RuntimeError("the multi-head product refused a shape the %s score kernel took" % sc.name)
+                done = True
+        if not done:
+            self._scored_forward_entries(sc, st, P, out)
+        st.out = out
+        return out
+
+    def _scored_backward(self, sc: "_Scored", st: GatLayerState, dOut: torch.Tensor):
+        """(the gradients ``sc`` forms itself: the own operand's first; the gradient of every panel part for the owned rows)."""
         K, d = st.heads, st.d
         F = K * d
         n_p, n_h = self.n_local, self.n_halo
         Fp = (F + 3) // 4 * 4
         dOut = dOut.contiguous()
-        dZc = self._slab("gat_dkv", n_p + n_h, 2 * Fp)[:n_p + n_h]       # the gradient panel: [dZk | dZv] in the forward panel's layout
-        Zc = st.Zc
-        dZq = None
+        dZc = self._slab(sc.slab, n_p + n_h, sc.parts * Fp)[:n_p + n_h]      # the gradient panel, in the forward panel's layout
+        P, dP = _panel_parts(st.Zc, sc.parts, F, Fp), _panel_parts(dZc, sc.parts, F, Fp)
+        grads = None
         if st.alpha_e is None:
-            de = self._plane_scratch("dot_de", K)
-            dZq = torch.empty((n_p, F), dtype=torch.float32, device=self.device)
-            if not (self.k.gatdot_grad_rows(self.fwd, Zc[:, :F], Zc[:, Fp:Fp + F], st.alpha, dOut, st.out, de, dZq, K, d)
-                    and self.k.gatdot_grad_cols(self.bwd, self.perm, st.Zq, dOut, st.alpha, de, dZc[:, :F], dZc[:, Fp:Fp + F], K, d)):
-                dZq = None
-        if dZq is None:                          # the composed route, or a kernel refused operands its forward twin took
-            dZq = self._dot_backward(st, dOut, dZc)
+            grads = sc.grads(self, st, P, dOut, self._plane_scratch(sc.tag + "_de", K), dP)
+        if grads is None:                        # the composed route, or a kernel refused operands its forward twin took
+            grads = self._scored_backward_entries(sc, st, dOut, P, dP)
         if Fp > F:
-            dZc[:, F:Fp].zero_()
-            dZc[:, Fp + F:].zero_()
-        if self.size > 1:                        # partial rows of [dZk | dZv] back to their owners, ADDED
-            back = self._slab("gat_send", self.n_send, 2 * Fp)
-            waits = self._exchange_all(dZc[n_p:], self.round_recv_off, back, self.round_send_off, 2 * Fp, tag="backward")
-            for r in range(self.rounds):
-                waits[r]()
-                self.k.spmm(self.unpack[r], back, dZc[:n_p], accumulate=True)
-        return dZq, dZc[:n_p, :F].clone(), dZc[:n_p, Fp:Fp + F].clone()
+            for i in range(sc.parts):
+                dZc[:, i * Fp + F:(i + 1) * Fp].zero_()
+        self._return_rows(dZc, sc.parts * Fp)
+        return grads, [g[:n_p].clone() for g in dP]
 
     # -- ... as tensor operations over the entry list (CPU tensors, other providers, shapes the kernels refuse) ------------------------
-    def _dot_forward(self, st: GatLayerState, Zq: torch.Tensor, Zc: torch.Tensor, out: torch.Tensor):
-        """The definition over the entry list, formed in DOUBLE and rounded once per output, like ``_v2_forward``."""
-        K, d = st.heads, st.d
-        F, n_p = K * d, self.n_local
-        Fp = (F + 3) // 4 * 4
-        rows, cols = self._v2_entry_list()
-        f64 = torch.float64
-        Kj = Zc[:, :F].reshape(-1, K, d)[cols].to(f64)
-        e = (Zq.reshape(n_p, K, d)[rows].to(f64) * Kj).sum(-1) / float(d) ** 0.5
-        m = torch.full((n_p, K), -float("inf"), dtype=f64, device=e.device).scatter_reduce(0, rows.unsqueeze(1).expand(-1, K), e, "amax",
-                                                                                           include_self=True)
-        ex = torch.exp(e - m[rows])
-        D = torch.zeros((n_p, K), dtype=f64, device=e.device).index_add_(0, rows, ex)
-        st.alpha_e = ex / D[rows]                                              # (kept in double for the backward)
-        Vj = Zc[:, Fp:Fp + F].reshape(-1, K, d)[cols].to(f64)
-        out.copy_(torch.zeros((n_p, K, d), dtype=f64, device=e.device).index_add_(0, rows, st.alpha_e.unsqueeze(-1) * Vj).view(n_p, F))
+    def _entry_list(self):
+        if self._entries is None:
+            rp = self.graph.fwd.rowptr.to(torch.int64).cpu()
+            rows = torch.repeat_interleave(torch.arange(self.n_local, dtype=torch.int64), rp[1:] - rp[:-1])
+            self._entries = (rows.to(self.device), self.graph.fwd.col.to(torch.int64).to(self.device))
+        return self._entries
 
-    def _dot_backward(self, st: GatLayerState, dOut: torch.Tensor, dZc: torch.Tensor) -> torch.Tensor:
+    def _entry_softmax(self, e: torch.Tensor, rows: torch.Tensor) -> torch.Tensor:
+        """alpha per entry [nnz, K] of the scores ``e``: the softmax over every row's entries, the row's maximum subtracted."""
+        shape = (self.n_local, e.shape[1])
+        m = torch.full(shape, -float("inf"), dtype=e.dtype, device=e.device).scatter_reduce(0, rows.unsqueeze(1).expand(-1, shape[1]), e,
+                                                                                            "amax", include_self=True)
+        ex = torch.exp(e - m[rows])
+        D = torch.zeros(shape, dtype=e.dtype, device=e.device).index_add_(0, rows, ex)
+        return ex / D[rows]
+
+    def _entry_de(self, alpha: torch.Tensor, q: torch.Tensor, rows: torch.Tensor) -> torch.Tensor:
+        """de = alpha (q - T), T_i = sum_j alpha_ij q_ij: as the kernels form it, q and T from the same products."""
+        return alpha * (q - torch.zeros((self.n_local, q.shape[1]), dtype=q.dtype, device=q.device).index_add_(0, rows, alpha * q)[rows])
+
+    def _scored_forward_entries(self, sc: "_Scored", st: GatLayerState, P, out: torch.Tensor):
+        """The definition over the entry list, formed in DOUBLE and rounded once per output: this route is the fall-back and not the
+        hot path, and its sums over a row's entries (and, for da, over all entries) then add nothing to the layer's float32 error."""
         K, d = st.heads, st.d
-        F, n_p, n_h = K * d, self.n_local, self.n_halo
-        Fp = (F + 3) // 4 * 4
-        rows, cols = self._v2_entry_list()
+        n_p = self.n_local
+        rows, cols = self._entry_list()
+        Pj = [Z.reshape(-1, K, d)[cols].to(torch.float64) for Z in P]
+        st.alpha_e = self._entry_softmax(sc.entry_scores(self, st, rows, Pj[0]), rows)     # (kept in double for the backward)
+        out.copy_(torch.zeros((n_p, K, d), dtype=torch.float64, device=self.device)
+                  .index_add_(0, rows, st.alpha_e.unsqueeze(-1) * Pj[-1]).view(n_p, K * d))
+
+    def _scored_backward_entries(self, sc: "_Scored", st: GatLayerState, dOut: torch.Tensor, P, dP):
+        K, d = st.heads, st.d
+        n_p = self.n_local
+        rows, cols = self._entry_list()
         f64 = torch.float64
-        s = 1.0 / float(d) ** 0.5
         alpha = st.alpha_e if st.alpha_e is not None else st.alpha[:, :self.nnz].t().to(f64)
-        G = dOut.view(n_p, K, d).to(f64)
-        Gi = G[rows]
-        Kj, Vj = (st.Zc[:, c0:c0 + F].reshape(-1, K, d)[cols].to(f64) for c0 in (0, Fp))
-        q = (Gi * (Vj - st.out.view(n_p, K, d)[rows].to(f64))).sum(-1)          # de as the kernels form it: q and T from the same products
-        de = alpha * (q - torch.zeros((n_p, K), dtype=f64, device=q.device).index_add_(0, rows, alpha * q)[rows])
-        w = de.unsqueeze(-1)
-        dZq = (s * torch.zeros((n_p, K, d), dtype=f64, device=self.device).index_add_(0, rows, w * Kj)).view(n_p, F).to(torch.float32)
-        dZk = s * torch.zeros((n_p + n_h, K, d), dtype=f64, device=self.device).index_add_(0, cols, w * st.Zq.reshape(n_p, K, d)[rows].to(f64))
-        dZv = torch.zeros((n_p + n_h, K, d), dtype=f64, device=self.device).index_add_(0, cols, alpha.unsqueeze(-1) * Gi)
-        dZc[:, :F].copy_(dZk.view(n_p + n_h, F))
-        dZc[:, Fp:Fp + F].copy_(dZv.view(n_p + n_h, F))
-        return dZq
+        Gi = dOut.view(n_p, K, d).to(f64)[rows]
+        Pj = [Z.reshape(-1, K, d)[cols].to(f64) for Z in P]
+        q = (Gi * (Pj[-1] - st.out.view(n_p, K, d)[rows].to(f64))).sum(-1)       # = <dOut_i, Z_j> - t_i
+        grads, dparts = sc.entry_chain(self, st, rows, cols, alpha, self._entry_de(alpha, q, rows), Gi, Pj)
+        for g, dst in zip(dparts, dP):
+            dst.copy_(g.view(-1, K * d))
+        return grads
+
+    def _return_rows(self, dZc: torch.Tensor, width: int, waits=None) -> None:
+        """Partial rows of the gradient panel ``dZc`` back to their owners, ADDED (the reverse all-to-all-v).  ``waits`` = (slab,
+        waiters) of an exchange of the halo rows that is already on its way (the split backward)."""
+        if self.size > 1:
+            if waits is not None:
+                back, waits = waits
+            else:
+                back = self._slab("gat_send", self.n_send, width)
+                waits = self._exchange_all(dZc[self.n_local:], self.round_recv_off, back, self.round_send_off, width, tag="backward")
+            for r in range(self.rounds):
+                waits[r]()
+                self.k.spmm(self.unpack[r], back, dZc[:self.n_local], accumulate=True)
 
     def _finish_backward(self, st: GatLayerState, dOut: torch.Tensor, dZc: torch.Tensor, ds1: torch.Tensor,
                          pack: Optional[torch.Tensor] = None, waits=None):
@@ -881,15 +784,7 @@ class GatEngine(BoundaryExchange):
         Fp = st.Zc.shape[1]
         if Fp > F + K:
             (dZc[:n_p] if waits is not None else dZc)[:, F + K:].zero_()
-        if self.size > 1:                                   # partial rows of [dZ | ds2] back to their owners, ADDED
-            if waits is not None:
-                back, waits = waits
-            else:
-                back = self._slab("gat_send", self.n_send, Fp)
-                waits = self._exchange_all(dZc[n_p:], self.round_recv_off, back, self.round_send_off, Fp, tag="backward")
-            for r in range(self.rounds):
-                waits[r]()
-                self.k.spmm(self.unpack[r], back, dZc[:n_p], accumulate=True)
+        self._return_rows(dZc, Fp, waits)                   # partial rows of [dZ | ds2] back to their owners, ADDED
         if pack is not None:                                # one copy of [dZ | ds2] out of the slab + the K columns of ds1
             if dZc.data_ptr() != pack.data_ptr():
                 pack[:, :F + K].copy_(dZc[:n_p, :F + K])
@@ -904,16 +799,122 @@ class GatEngine(BoundaryExchange):
         return pack if pack is not None else (dZ, ds1, ds2)
 
 
+def _panel_parts(Zc: torch.Tensor, n: int, F: int, Fp: int):
+    return [Zc[:, i * Fp:i * Fp + F] for i in range(n)]
+
+
+@dataclass(frozen=True)
+class _Scored:
+    """What the two layers whose score needs both ends' rows do differently (``GatEngine._scored_forward`` / ``_scored_backward``).
+    P / dP: the parts of the gather panel / of the gradient panel, Pj: P gathered per entry, in double."""
+    name: str                    # in messages: the kernels ...
+    layer: str                   # ... and the layer
+    tag: str                     # prefix of its plane scratch
+    slab: str                    # its gradient panel
+    parts: int                   # Fp-wide parts of the gather panel
+    own: str                     # the GatLayerState attribute that keeps the row's own operand
+    kernels: tuple               # provider methods the kernel route needs
+    borrow: object               # (parts, F, Fp) -> the caller's projection as the gather panel of ONE rank, or None
+    scores: object               # (eng, st, P, E) -> bool: the score planes E
+    grads: object                # (eng, st, P, dOut, de, dP) -> its gradients and dP written, or None (refused)
+    entry_scores: object         # (eng, st, rows, Pj[0]) -> e [nnz, K], double
+    entry_chain: object          # (eng, st, rows, cols, alpha, de, Gi, Pj) -> (its gradients, the gradient of every part [n, K, d])
+
+
+def _v2_borrow(parts, F, Fp):
+    Zs, = parts
+    fit = Zs.stride(1) == 1 and Zs.stride(0) % 4 == 0 and Zs.data_ptr() % 16 == 0 and Zs.dtype is torch.float32
+    return Zs if fit else None
+
+
+def _v2_grads(eng, st, P, dOut, de, dP):
+    K, d = st.heads, st.d
+    dZt = torch.empty((eng.n_local, K * d), dtype=torch.float32, device=eng.device)
+    da = torch.empty((d, K), dtype=torch.float32, device=eng.device)
+    if not eng.k.gatv2_grad_rows(eng.fwd, st.Zt, P[0], st.att, st.alpha, dOut, st.out, eng.slope, de, dZt, da, K, d):
+        return None
+    alpha_t, de_t = eng._plane_scratch("v2_alpha_t", K), eng._plane_scratch("v2_de_t", K)
+    eng.k.csr_permute(st.alpha, eng.perm, alpha_t)
+    eng.k.csr_permute(de, eng.perm, de_t)
+    if not eng.k.gatv2_grad_cols(eng.bwd, P[0], st.Zt, dOut, st.att, alpha_t, de_t, eng.slope, dP[0], K, d):
+        return None
+    return dZt, da
+
+
+def _v2_entry_scores(eng, st, rows, Zj):
+    x = st.Zt.reshape(-1, st.heads, st.d)[rows].to(torch.float64) + Zj
+    return (torch.where(x > 0, x, x * eng.slope) * st.att.to(torch.float64).t().unsqueeze(0)).sum(-1)
+
+
+def _v2_entry_chain(eng, st, rows, cols, alpha, de, Gi, Pj):
+    K, d, n_p, f64 = st.heads, st.d, eng.n_local, torch.float64
+    x = st.Zt.reshape(n_p, K, d)[rows].to(f64) + Pj[0]
+    pos = x > 0
+    w = de.unsqueeze(-1) * st.att.to(f64).t().unsqueeze(0)
+    w = torch.where(pos, w, w * eng.slope)
+    dZt = torch.zeros((n_p, K, d), dtype=f64, device=eng.device).index_add_(0, rows, w).view(n_p, K * d).to(torch.float32)
+    dZs = torch.zeros((n_p + eng.n_halo, K, d), dtype=f64, device=eng.device).index_add_(0, cols, w + alpha.unsqueeze(-1) * Gi)
+    da = (de.unsqueeze(-1) * torch.where(pos, x, x * eng.slope)).sum(0).t().contiguous().to(torch.float32)
+    return (dZt, da), (dZs,)
+
+
+def _dot_borrow(parts, F, Fp):
+    Zk, Zv = parts               # [Zk | Zv] adjacent column slices of one aligned projection: they ARE the gather panel
+    fit = Fp == F and Zk.dtype is torch.float32 and Zv.dtype is torch.float32 \
+        and Zk.stride(1) == 1 and Zv.stride(1) == 1 and Zk.stride(0) == Zv.stride(0) >= 2 * F and Zk.stride(0) % 4 == 0 \
+        and Zk.data_ptr() % 16 == 0 and Zv.data_ptr() == Zk.data_ptr() + 4 * F \
+        and Zk.untyped_storage().data_ptr() == Zv.untyped_storage().data_ptr()
+    return Zk.as_strided((Zk.shape[0], 2 * F), (Zk.stride(0), 1)) if fit else None
+
+
+def _dot_grads(eng, st, P, dOut, de, dP):
+    K, d = st.heads, st.d
+    dZq = torch.empty((eng.n_local, K * d), dtype=torch.float32, device=eng.device)
+    if not (eng.k.gatdot_grad_rows(eng.fwd, P[0], P[1], st.alpha, dOut, st.out, de, dZq, K, d)
+            and eng.k.gatdot_grad_cols(eng.bwd, eng.perm, st.Zq, dOut, st.alpha, de, dP[0], dP[1], K, d)):
+        return None
+    return dZq,
+
+
+def _dot_entry_scores(eng, st, rows, Kj):
+    return (st.Zq.reshape(-1, st.heads, st.d)[rows].to(torch.float64) * Kj).sum(-1) / float(st.d) ** 0.5
+
+
+def _dot_entry_chain(eng, st, rows, cols, alpha, de, Gi, Pj):
+    K, d, n_p, f64 = st.heads, st.d, eng.n_local, torch.float64
+    s = 1.0 / float(d) ** 0.5
+    w = de.unsqueeze(-1)
+    dZq = (s * torch.zeros((n_p, K, d), dtype=f64, device=eng.device).index_add_(0, rows, w * Pj[0])).view(n_p, K * d).to(torch.float32)
+    dZk = s * torch.zeros((n_p + eng.n_halo, K, d), dtype=f64, device=eng.device).index_add_(0, cols, w * st.Zq.reshape(n_p, K, d)[rows].to(f64))
+    dZv = torch.zeros((n_p + eng.n_halo, K, d), dtype=f64, device=eng.device).index_add_(0, cols, alpha.unsqueeze(-1) * Gi)
+    return (dZq,), (dZk, dZv)
+
+
+_V2 = _Scored("GATv2", "GATv2", "v2", "gat_dzs", 1, "Zt",
+              ("gatv2_scores", "gatv2_softmax", "gatv2_grad_rows", "gatv2_grad_cols", "csr_permute", "spmm_heads"), _v2_borrow,
+              lambda eng, st, P, E: eng.k.gatv2_scores(eng.fwd, st.Zt, P[0], st.att, eng.slope, E, st.heads, st.d),
+              _v2_grads, _v2_entry_scores, _v2_entry_chain)
+_DOT = _Scored("dot-product", "dot-product attention", "dot", "gat_dkv", 2, "Zq",
+               ("gatdot_scores", "gatv2_softmax", "gatdot_grad_rows", "gatdot_grad_cols", "spmm_heads"), _dot_borrow,
+               lambda eng, st, P, E: eng.k.gatdot_scores(eng.fwd, st.Zq, P[0], E, st.heads, st.d),
+               _dot_grads, _dot_entry_scores, _dot_entry_chain)
+
+
+def _claim(ctx, engine, state: GatLayerState) -> None:
+    """The forward of an autograd Function takes ``state``'s buffers until its backward has run."""
+    if state.busy:
+        raise RuntimeError("GAT layer state is still owned by a forward whose backward has not run; "
+                           "use a fresh state (GatEngine.new_layer_state) for a second forward")
+    ctx.engine, ctx.state = engine, state
+    state.busy = any(ctx.needs_input_grad)
+
+
 class GatAggregate(torch.autograd.Function):
     """out = GAT aggregation of (Z, s1, s2) on ``engine`` with ``state``'s buffers."""
 
     @staticmethod
     def forward(ctx, engine: GatEngine, state: GatLayerState, Z, s1, s2):
-        if state.busy:
-            raise RuntimeError("GAT layer state is still owned by a forward whose backward has not run; "
-                               "use a fresh state (GatEngine.new_layer_state) for a second forward")
-        ctx.engine, ctx.state = engine, state
-        state.busy = any(ctx.needs_input_grad)
+        _claim(ctx, engine, state)
         return engine.forward(state, Z, s1, s2)           # (Z may be a column slice: it is copied into the panel [Z | s2] anyway)
 
     @staticmethod
@@ -928,11 +929,7 @@ class GatV2Aggregate(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, engine: GatEngine, state: GatLayerState, Zt, Zs, a):
-        if state.busy:
-            raise RuntimeError("GAT layer state is still owned by a forward whose backward has not run; "
-                               "use a fresh state (GatEngine.new_layer_state) for a second forward")
-        ctx.engine, ctx.state = engine, state
-        state.busy = any(ctx.needs_input_grad)
+        _claim(ctx, engine, state)
         return engine.forward_v2(state, Zt, Zs, a)
 
     @staticmethod
@@ -947,11 +944,7 @@ class GatDotAggregate(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, engine: GatEngine, state: GatLayerState, Zq, Zk, Zv):
-        if state.busy:
-            raise RuntimeError("GAT layer state is still owned by a forward whose backward has not run; "
-                               "use a fresh state (GatEngine.new_layer_state) for a second forward")
-        ctx.engine, ctx.state = engine, state
-        state.busy = any(ctx.needs_input_grad)
+        _claim(ctx, engine, state)
         return engine.forward_dot(state, Zq, Zk, Zv)
 
     @staticmethod
@@ -968,14 +961,10 @@ class GatAggregatePacked(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, engine: GatEngine, state: GatLayerState, ZS):
-        if state.busy:
-            raise RuntimeError("GAT layer state is still owned by a forward whose backward has not run; "
-                               "use a fresh state (GatEngine.new_layer_state) for a second forward")
         K, F = state.heads, state.heads * state.d
         if ZS.dim() != 2 or ZS.shape[1] != F + 2 * K:
             raise ValueError("packed projection must be n x (F + 2K)")
-        ctx.engine, ctx.state = engine, state
-        state.busy = any(ctx.needs_input_grad)
+        _claim(ctx, engine, state)
         if "panel" in __import__("inspect").signature(engine.forward).parameters:
             return engine.forward(state, ZS[:, :F], ZS[:, F + K:F + 2 * K], ZS[:, F:F + K], panel=ZS)
         return engine.forward(state, ZS[:, :F], ZS[:, F + K:F + 2 * K], ZS[:, F:F + K])

@@ -1366,29 +1366,52 @@ class HipKernels:
         if not (a.is_cuda and a.dtype is torch.float32 and tuple(a.shape) == (d, heads) and a.is_contiguous()):
             raise _lib.PgcnError("a must be a contiguous fp32 [d, heads] CUDA tensor")
 
+    def _attn_rows(self, F: int, A: DeviceCSR, **mats) -> None:
+        """Every named matrix is a row-major fp32 CUDA matrix of enough rows (its value: (tensor, rows)) and at least F columns."""
+        for what, (t, rows) in mats.items():
+            self._check_dense(t, rows, what)
+            if t.shape[1] < F:
+                raise _lib.PgcnError("%s is narrower than heads * d" % what)
+        if A.row_map is not None:
+            raise _lib.PgcnError("a compact-row structure")
+
+    def _attn_slot_ws(self, A: DeviceCSR, need: int) -> None:
+        if need and (A.ws is None or A.ws.numel() < need):
+            A.ws = torch.empty(need, dtype=torch.float32, device=self.device)
+            A.launch_cache.clear()
+
+    def _t_ws(self, A: DeviceCSR, heads: int) -> torch.Tensor:
+        # T_i = sum_j alpha_ij q_ij of pass 1 of a row gradient belongs to the PROVIDER: one for every engine and layer that uses it,
+        # written and read within one call -- good for one stream, which is how the engines call (the comm stream never runs these
+        # kernels); two streams on one provider would need one each
+        tws = getattr(self, "_attn_t_ws", None)
+        if tws is None or tws.numel() < max(A.nrows, 1) * heads:
+            tws = self._attn_t_ws = torch.empty(max(A.nrows, 1) * heads, dtype=torch.float32, device=self.device)
+        return tws
+
+    @staticmethod
+    def _attn_done(rc: int, what: str) -> bool:
+        """How every attention wrapper ends: False = the entry point does not cover the shape, an error raised, or True."""
+        if rc == _lib.PGCN_EUNSUPPORTED:
+            return False
+        _lib.check(rc, what)
+        return True
+
     def gatv2_scores(self, A: DeviceCSR, Zt: torch.Tensor, Zs: torch.Tensor, a: torch.Tensor, slope: float, E: torch.Tensor,
                      heads: int, d: int) -> bool:
         """E[k, p] = sum_c a[c, k] LeakyReLU(Zt[i, k d + c] + Zs[j, k d + c]) for every stored entry p = (i, j) of ``A``, storage order
         (pgcn_gatv2_scores_f32).  Zt: the rows of A, Zs: its columns.  False = shape not covered (heads 1-8, d 32 / 64 / 128 / 256,
         heads * d <= 256, 16-byte rows)."""
-        F = heads * d
         if not self._v2_shape(heads, d):
             return False
-        self._check_dense(Zt, A.nrows, "Zt")
-        self._check_dense(Zs, A.ncols, "Zs")
+        self._attn_rows(heads * d, A, Zt=(Zt, A.nrows), Zs=(Zs, A.ncols))
         self._v2_attention(a, heads, d)
         self._v2_planes(A, heads, E)
-        if Zt.shape[1] < F or Zs.shape[1] < F or A.row_map is not None:
-            raise _lib.PgcnError("Zt / Zs narrower than heads * d, or a compact-row structure")
         if A.col.numel() == 0:
             return True
-        rc = self.lib.pgcn_gatv2_scores_f32(
+        return self._attn_done(self.lib.pgcn_gatv2_scores_f32(
             A.rowptr.data_ptr(), A.col.data_ptr(), A.nrows, _ptr(A.tasks), A.ntasks, A.seg, A.nslices, Zt.data_ptr(), Zt.stride(0),
-            Zs.data_ptr(), Zs.stride(0), a.data_ptr(), heads, d, slope, E.data_ptr(), E.stride(0), self._stream())
-        if rc == _lib.PGCN_EUNSUPPORTED:
-            return False
-        _lib.check(rc, "pgcn_gatv2_scores_f32")
-        return True
+            Zs.data_ptr(), Zs.stride(0), a.data_ptr(), heads, d, slope, E.data_ptr(), E.stride(0), self._stream()), "pgcn_gatv2_scores_f32")
 
     def gatv2_softmax(self, A: DeviceCSR, E: torch.Tensor, heads: int) -> None:
         """The score planes of ``gatv2_scores`` become the alpha planes, in place: the softmax over every row's stored entries, the
@@ -1408,47 +1431,30 @@ class HipKernels:
         F = heads * d
         if not self._v2_shape(heads, d):
             return False
-        self._check_dense(Zt, A.nrows, "Zt")
-        self._check_dense(Zs, A.ncols, "Zs")
-        self._check_dense(dOut, A.nrows, "dOut")
-        self._check_dense(dZt, A.nrows, "dZt")
-        self._check_dense(out, A.nrows, "out")
+        self._attn_rows(F, A, Zt=(Zt, A.nrows), Zs=(Zs, A.ncols), dOut=(dOut, A.nrows), dZt=(dZt, A.nrows), out=(out, A.nrows))
         self._v2_attention(a, heads, d)
         self._v2_attention(da, heads, d)
         self._v2_planes(A, heads, alpha, de)
-        if min(Zt.shape[1], Zs.shape[1], dOut.shape[1], dZt.shape[1], out.shape[1]) < F or A.row_map is not None:
-            raise _lib.PgcnError("Zt / Zs / dOut / out / dZt narrower than heads * d, or a compact-row structure")
         if A.col.numel() == 0:
             da.zero_()
             if not accumulate:
                 dZt[:A.nrows, :F].zero_()
             return True
-        need = A.nslots * F
-        if need and (A.ws is None or A.ws.numel() < need):
-            A.ws = torch.empty(need, dtype=torch.float32, device=self.device)
-            A.launch_cache.clear()
+        self._attn_slot_ws(A, A.nslots * F)
         nda = int(self.lib.pgcn_gatv2_da_ws_elems(A.nrows, _ptr(A.tasks), A.ntasks, A.seg, A.nslices, heads, d))
         if nda < 0:
             raise _lib.PgcnError("pgcn_gatv2_da_ws_elems refused the plan")
-        # the two scratch buffers of the call (the da partial rows; T_i = sum_j alpha_ij q_ij of pass 1) belong to the PROVIDER: one of
-        # each for every engine and layer that uses it, written and read within this call -- good for one stream, which is how the
-        # engines call (the comm stream never runs these kernels); two streams on one provider would need a pair each
-        ws = getattr(self, "_v2_da_ws", None)
+        ws = getattr(self, "_v2_da_ws", None)          # the da partial rows: the provider's, like _t_ws
         if ws is None or ws.numel() < nda:
             ws = self._v2_da_ws = torch.empty(max(nda, 1), dtype=torch.float32, device=self.device)
-        tws = getattr(self, "_v2_t_ws", None)
-        if tws is None or tws.numel() < max(A.nrows, 1) * heads:
-            tws = self._v2_t_ws = torch.empty(max(A.nrows, 1) * heads, dtype=torch.float32, device=self.device)
+        tws = self._t_ws(A, heads)
         flags = _lib.SPMM_ACCUMULATE if accumulate else 0
-        rc = self.lib.pgcn_gatv2_grad_rows_f32(
+        return self._attn_done(self.lib.pgcn_gatv2_grad_rows_f32(
             A.rowptr.data_ptr(), A.col.data_ptr(), A.nrows, _ptr(A.tasks), A.ntasks, A.seg, A.nslices, _ptr(A.fix), A.nfix,
             Zt.data_ptr(), Zt.stride(0), Zs.data_ptr(), Zs.stride(0), a.data_ptr(), alpha.data_ptr(), alpha.stride(0), dOut.data_ptr(),
             dOut.stride(0), out.data_ptr(), out.stride(0), tws.data_ptr(), heads, d, slope, de.data_ptr(), de.stride(0), dZt.data_ptr(), dZt.stride(0), da.data_ptr(),
-            _ptr(A.ws), 0 if A.ws is None else A.ws.numel(), A.nslots, ws.data_ptr(), ws.numel(), flags, self._stream())
-        if rc == _lib.PGCN_EUNSUPPORTED:
-            return False
-        _lib.check(rc, "pgcn_gatv2_grad_rows_f32")
-        return True
+            _ptr(A.ws), 0 if A.ws is None else A.ws.numel(), A.nslots, ws.data_ptr(), ws.numel(), flags, self._stream()),
+            "pgcn_gatv2_grad_rows_f32")
 
     def gatv2_grad_cols(self, AT: DeviceCSR, Zs: torch.Tensor, Zt: torch.Tensor, dOut: torch.Tensor, a: torch.Tensor,
                         alpha_t: torch.Tensor, de_t: torch.Tensor, slope: float, dZs: torch.Tensor, heads: int, d: int,
@@ -1459,65 +1465,35 @@ class HipKernels:
         F = heads * d
         if not self._v2_shape(heads, d):
             return False
-        self._check_dense(Zs, AT.nrows, "Zs")
-        self._check_dense(Zt, AT.ncols, "Zt")
-        self._check_dense(dOut, AT.ncols, "dOut")
-        self._check_dense(dZs, AT.nrows, "dZs")
+        self._attn_rows(F, AT, Zs=(Zs, AT.nrows), Zt=(Zt, AT.ncols), dOut=(dOut, AT.ncols), dZs=(dZs, AT.nrows))
         self._v2_attention(a, heads, d)
         self._v2_planes(AT, heads, alpha_t, de_t)
-        if min(Zt.shape[1], Zs.shape[1], dOut.shape[1], dZs.shape[1]) < F or AT.row_map is not None:
-            raise _lib.PgcnError("Zs / Zt / dOut / dZs narrower than heads * d, or a compact-row structure")
         if AT.col.numel() == 0:
             if not accumulate:
                 dZs[:AT.nrows, :F].zero_()
             return True
-        need = AT.nslots * F
-        if need and (AT.ws is None or AT.ws.numel() < need):
-            AT.ws = torch.empty(need, dtype=torch.float32, device=self.device)
-            AT.launch_cache.clear()
+        self._attn_slot_ws(AT, AT.nslots * F)
         flags = _lib.SPMM_ACCUMULATE if accumulate else 0
-        rc = self.lib.pgcn_gatv2_grad_cols_f32(
+        return self._attn_done(self.lib.pgcn_gatv2_grad_cols_f32(
             AT.rowptr.data_ptr(), AT.col.data_ptr(), AT.nrows, _ptr(AT.tasks), AT.ntasks, AT.seg, AT.nslices, _ptr(AT.fix), AT.nfix,
             Zs.data_ptr(), Zs.stride(0), Zt.data_ptr(), Zt.stride(0), dOut.data_ptr(), dOut.stride(0), a.data_ptr(), alpha_t.data_ptr(),
             alpha_t.stride(0), de_t.data_ptr(), de_t.stride(0), heads, d, slope, dZs.data_ptr(), dZs.stride(0), _ptr(AT.ws),
-            0 if AT.ws is None else AT.ws.numel(), AT.nslots, flags, self._stream())
-        if rc == _lib.PGCN_EUNSUPPORTED:
-            return False
-        _lib.check(rc, "pgcn_gatv2_grad_cols_f32")
-        return True
+            0 if AT.ws is None else AT.ws.numel(), AT.nslots, flags, self._stream()), "pgcn_gatv2_grad_cols_f32")
 
     # -- scaled dot-product attention (pgcn_gatdot.hip) ----------------------------------------------------------------
-    def _dot_rows(self, F: int, A: DeviceCSR, **mats) -> None:
-        """Every named matrix is a row-major fp32 CUDA matrix of enough rows (its value: (tensor, rows)) and at least F columns."""
-        for what, (t, rows) in mats.items():
-            self._check_dense(t, rows, what)
-            if t.shape[1] < F:
-                raise _lib.PgcnError("%s is narrower than heads * d" % what)
-        if A.row_map is not None:
-            raise _lib.PgcnError("a compact-row structure")
-
     def gatdot_scores(self, A: DeviceCSR, Zq: torch.Tensor, Zk: torch.Tensor, E: torch.Tensor, heads: int, d: int) -> bool:
         """E[k, p] = <Zq[i, k d ..], Zk[j, k d ..]> / sqrt(d) for every stored entry p = (i, j) of ``A``, storage order
         (pgcn_gatdot_scores_f32).  Zq: the rows of A, Zk: its columns.  False = shape not covered (heads 1-8, d 32 / 64 / 128 / 256,
         heads * d <= 256, 16-byte rows, leading dimensions % 4 == 0)."""
         if not self._v2_shape(heads, d):
             return False
-        self._dot_rows(heads * d, A, Zq=(Zq, A.nrows), Zk=(Zk, A.ncols))
+        self._attn_rows(heads * d, A, Zq=(Zq, A.nrows), Zk=(Zk, A.ncols))
         self._v2_planes(A, heads, E)
         if A.col.numel() == 0:
             return True
-        rc = self.lib.pgcn_gatdot_scores_f32(
+        return self._attn_done(self.lib.pgcn_gatdot_scores_f32(
             A.rowptr.data_ptr(), A.col.data_ptr(), A.nrows, _ptr(A.tasks), A.ntasks, A.seg, A.nslices, Zq.data_ptr(), Zq.stride(0),
-            Zk.data_ptr(), Zk.stride(0), heads, d, E.data_ptr(), E.stride(0), self._stream())
-        if rc == _lib.PGCN_EUNSUPPORTED:
-            return False
-        _lib.check(rc, "pgcn_gatdot_scores_f32")
-        return True
-
-    def _slot_ws(self, A: DeviceCSR, need: int) -> None:
-        if need and (A.ws is None or A.ws.numel() < need):
-            A.ws = torch.empty(need, dtype=torch.float32, device=self.device)
-            A.launch_cache.clear()
+            Zk.data_ptr(), Zk.stride(0), heads, d, E.data_ptr(), E.stride(0), self._stream()), "pgcn_gatdot_scores_f32")
 
     def gatdot_grad_rows(self, A: DeviceCSR, Zk: torch.Tensor, Zv: torch.Tensor, alpha: torch.Tensor, dOut: torch.Tensor,
                          out: torch.Tensor, de: torch.Tensor, dZq: torch.Tensor, heads: int, d: int, accumulate: bool = False) -> bool:
@@ -1527,26 +1503,20 @@ class HipKernels:
         F = heads * d
         if not self._v2_shape(heads, d):
             return False
-        self._dot_rows(F, A, Zk=(Zk, A.ncols), Zv=(Zv, A.ncols), dOut=(dOut, A.nrows), out=(out, A.nrows), dZq=(dZq, A.nrows))
+        self._attn_rows(F, A, Zk=(Zk, A.ncols), Zv=(Zv, A.ncols), dOut=(dOut, A.nrows), out=(out, A.nrows), dZq=(dZq, A.nrows))
         self._v2_planes(A, heads, alpha, de)
         if A.col.numel() == 0:
             if not accumulate:
                 dZq[:A.nrows, :F].zero_()
             return True
-        self._slot_ws(A, A.nslots * F)
-        # T_i = sum_j alpha_ij q_ij of pass 1 belongs to the PROVIDER, like the scratch of gatv2_grad_rows: written and read within this call
-        tws = getattr(self, "_v2_t_ws", None)
-        if tws is None or tws.numel() < max(A.nrows, 1) * heads:
-            tws = self._v2_t_ws = torch.empty(max(A.nrows, 1) * heads, dtype=torch.float32, device=self.device)
-        rc = self.lib.pgcn_gatdot_grad_rows_f32(
+        self._attn_slot_ws(A, A.nslots * F)
+        tws = self._t_ws(A, heads)
+        return self._attn_done(self.lib.pgcn_gatdot_grad_rows_f32(
             A.rowptr.data_ptr(), A.col.data_ptr(), A.nrows, _ptr(A.tasks), A.ntasks, A.seg, A.nslices, _ptr(A.fix), A.nfix,
             Zk.data_ptr(), Zk.stride(0), Zv.data_ptr(), Zv.stride(0), alpha.data_ptr(), alpha.stride(0), dOut.data_ptr(), dOut.stride(0),
             out.data_ptr(), out.stride(0), tws.data_ptr(), heads, d, de.data_ptr(), de.stride(0), dZq.data_ptr(), dZq.stride(0),
-            _ptr(A.ws), 0 if A.ws is None else A.ws.numel(), A.nslots, _lib.SPMM_ACCUMULATE if accumulate else 0, self._stream())
-        if rc == _lib.PGCN_EUNSUPPORTED:
-            return False
-        _lib.check(rc, "pgcn_gatdot_grad_rows_f32")
-        return True
+            _ptr(A.ws), 0 if A.ws is None else A.ws.numel(), A.nslots, _lib.SPMM_ACCUMULATE if accumulate else 0, self._stream()),
+            "pgcn_gatdot_grad_rows_f32")
 
     def gatdot_grad_cols(self, AT: DeviceCSR, perm: torch.Tensor, Zq: torch.Tensor, dOut: torch.Tensor, alpha: torch.Tensor,
                          de: torch.Tensor, dZk: torch.Tensor, dZv: torch.Tensor, heads: int, d: int, accumulate: bool = False) -> bool:
@@ -1556,7 +1526,7 @@ class HipKernels:
         F = heads * d
         if not self._v2_shape(heads, d):
             return False
-        self._dot_rows(F, AT, Zq=(Zq, AT.ncols), dOut=(dOut, AT.ncols), dZk=(dZk, AT.nrows), dZv=(dZv, AT.nrows))
+        self._attn_rows(F, AT, Zq=(Zq, AT.ncols), dOut=(dOut, AT.ncols), dZk=(dZk, AT.nrows), dZv=(dZv, AT.nrows))
         self._v2_planes(AT, heads, alpha, de)
         nnz = AT.col.numel()
         if not (perm.is_cuda and perm.dtype is torch.int64 and perm.dim() == 1 and perm.numel() == nnz and perm.is_contiguous()):
@@ -1566,16 +1536,13 @@ class HipKernels:
                 dZk[:AT.nrows, :F].zero_()
                 dZv[:AT.nrows, :F].zero_()
             return True
-        self._slot_ws(AT, 2 * AT.nslots * F)
-        rc = self.lib.pgcn_gatdot_grad_cols_f32(
+        self._attn_slot_ws(AT, 2 * AT.nslots * F)
+        return self._attn_done(self.lib.pgcn_gatdot_grad_cols_f32(
             AT.rowptr.data_ptr(), AT.col.data_ptr(), AT.nrows, _ptr(AT.tasks), AT.ntasks, AT.seg, AT.nslices, _ptr(AT.fix), AT.nfix,
             perm.data_ptr(), Zq.data_ptr(), Zq.stride(0), dOut.data_ptr(), dOut.stride(0), alpha.data_ptr(), alpha.stride(0),
             de.data_ptr(), de.stride(0), heads, d, dZk.data_ptr(), dZk.stride(0), dZv.data_ptr(), dZv.stride(0), _ptr(AT.ws),
-            0 if AT.ws is None else AT.ws.numel(), AT.nslots, _lib.SPMM_ACCUMULATE if accumulate else 0, self._stream())
-        if rc == _lib.PGCN_EUNSUPPORTED:
-            return False
-        _lib.check(rc, "pgcn_gatdot_grad_cols_f32")
-        return True
+            0 if AT.ws is None else AT.ws.numel(), AT.nslots, _lib.SPMM_ACCUMULATE if accumulate else 0, self._stream()),
+            "pgcn_gatdot_grad_cols_f32")
 
     # -- the dense blocks of an attention pattern (pgcn_gat_blocks.hip, r06) ------------------------------------------
     @staticmethod
