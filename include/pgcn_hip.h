@@ -242,6 +242,15 @@ int pgcn_spmm_strip_f32(const int32_t *work, int64_t nwork, const int32_t *recs,
                         const float *B, int64_t ldb, int64_t ncols, int32_t f, float *partial_ws,
                         int64_t partial_ws_elems, int64_t nslots_total, pgcn_stream_t stream);
 
+/* The same records, work list, panels and slots in 8-WAVE workgroups (512 threads, 176 registers, 153 KB of LDS instead of 1 024
+ * threads that fill the CU): for a caller that launches the strips on one stream and its gather part on another, so that gather
+ * workgroups run on the same CUs beside a strip workgroup instead of waiting for it to retire.  Every row adds the same entries
+ * in the same order: the partial rows are those of pgcn_spmm_strip_f32 bit for bit.  Same arguments, checks (their messages
+ * carry this name), ldb bound and plain kernel for odd widths / alignments.  Alone on a device it is the slower of the two. */
+int pgcn_spmm_strip_w8_f32(const int32_t *work, int64_t nwork, const int32_t *recs, const int32_t *pairs,
+                           const float *B, int64_t ldb, int64_t ncols, int32_t f, float *partial_ws,
+                           int64_t partial_ws_elems, int64_t nslots_total, pgcn_stream_t stream);
+
 /* Value-free strip records (structures with no values: diag(row_scale) P diag(col_scale), P a 0/1 pattern).  offs: int32
  * [nrec][1024], the offset slots of pgcn_spmm_strip_f32's pairs without the values (4 KB per record), 16-byte aligned.  The
  * staged panel row j is multiplied by col_scale[j] once (NULL = ones) and every partial row i by row_scale[i] at its slot write
@@ -327,6 +336,9 @@ int pgcn_spmm_core_if_f32(const int32_t *work, int64_t nwork, const int32_t *til
 int pgcn_spmm_strip_if_f32(const int32_t *work, int64_t nwork, const int32_t *recs, const int32_t *pairs, const float *B, int64_t ldb,
                            int64_t ncols, int32_t f, float *partial_ws, int64_t partial_ws_elems, int64_t nslots_total,
                            const int32_t *run_if, pgcn_stream_t stream);
+int pgcn_spmm_strip_w8_if_f32(const int32_t *work, int64_t nwork, const int32_t *recs, const int32_t *pairs, const float *B, int64_t ldb,
+                              int64_t ncols, int32_t f, float *partial_ws, int64_t partial_ws_elems, int64_t nslots_total,
+                              const int32_t *run_if, pgcn_stream_t stream);
 int pgcn_spmm_dense_bf16x3_if_f32(const int32_t *work, int64_t nwork, const int32_t *blk_img, const float *vals3,
                                   const int32_t *panel_list, int64_t npanels, const float *B, int64_t ldb, int64_t ncols, int32_t f,
                                   void *image_ws, int64_t image_ws_bytes, float *partial_ws, int64_t partial_ws_elems,

@@ -55,6 +55,7 @@ SIGNATURES = {
     "pgcn_spmm_core_if_f32": (ctypes.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _vp,
                                              _i64, _i64, _vp, _vp]),
     "pgcn_spmm_strip_if_f32": (ctypes.c_int, [_vp, _i64, _vp, _vp, _vp, _i64, _i64, _i32, _vp, _i64, _i64, _vp, _vp]),
+    "pgcn_spmm_strip_w8_if_f32": (ctypes.c_int, [_vp, _i64, _vp, _vp, _vp, _i64, _i64, _i32, _vp, _i64, _i64, _vp, _vp]),
     "pgcn_spmm_dense_bf16x3_if_f32": (ctypes.c_int, [_vp, _i64, _vp, _vp, _vp, _i64, _vp, _i64, _i64, _i32, _vp, _i64, _vp, _i64, _i64,
                                                      _vp, _vp]),
     "pgcn_spmm_fixup_if_f32": (ctypes.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _i64, _i32, _u32, _vp, _vp]),
@@ -65,6 +66,7 @@ SIGNATURES = {
     "pgcn_spmm_core_f32": (ctypes.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _vp,
                                           _i64, _i64, _vp]),
     "pgcn_spmm_strip_f32": (ctypes.c_int, [_vp, _i64, _vp, _vp, _vp, _i64, _i64, _i32, _vp, _i64, _i64, _vp]),
+    "pgcn_spmm_strip_w8_f32": (ctypes.c_int, [_vp, _i64, _vp, _vp, _vp, _i64, _i64, _i32, _vp, _i64, _i64, _vp]),
     "pgcn_spmm_strip_vf_f32": (ctypes.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _vp, _i64, _i64, _vp]),
     "pgcn_spmm_heads_f32": (ctypes.c_int, [_vp, _vp, _vp, _i64, _i32, _i32, _i64, _vp, _i64, _vp, _i32, _vp, _i64, _vp, _i64,
                                            _vp, _i64, _vp, _i64, _i64, _u32, _vp]),

@@ -602,6 +602,12 @@ class HipKernels:
             self.sides.append(torch.cuda.Stream(self.device))
         sides = self.sides
         dev, nside = self.device, len(lanes) - 1
+        # tuning.strip_waves = 8: stored strip records of a group that really runs on lanes go through the 8-wave workgroups, beside which
+        # the other lane's gather workgroups fit on a CU (the same bits); alone on the device the 16-wave kernel is the faster one
+        strip_fn, strip_if_fn, strip_name = lib.pgcn_spmm_strip_f32, lib.pgcn_spmm_strip_if_f32, "pgcn_spmm_strip_f32"
+        other = [lane for lane in lanes if "strip" not in lane]      # (no gather tasks, or gather queued on the strips' own lane: nothing shares the CU)
+        if _T.strip_waves == 8 and st is not None and soffs is None and any("gather" in lane for lane in other):
+            strip_fn, strip_if_fn, strip_name = lib.pgcn_spmm_strip_w8_f32, lib.pgcn_spmm_strip_w8_if_f32, "pgcn_spmm_strip_w8_f32"
 
         def launch(name, b, c, s):
             if name == "gather" and csc is not None:
@@ -614,7 +620,7 @@ class HipKernels:
                 check(lib.pgcn_spmm_strip_vf_f32(sw, sn, srec, soffs, srs, scs, b, ldb, ncols, f, ws, ws_n, nst, s),
                       "pgcn_spmm_strip_vf_f32")
             elif name == "strip":
-                check(lib.pgcn_spmm_strip_f32(sw, sn, srec, spairs, b, ldb, ncols, f, ws, ws_n, nst, s), "pgcn_spmm_strip_f32")
+                check(strip_fn(sw, sn, srec, spairs, b, ldb, ncols, f, ws, ws_n, nst, s), strip_name)
             elif pat3 is not None:
                 check(lib.pgcn_spmm_dense_pat_bf16x3_f32(w3, n3, bi3, pat3, pr3, rs3, cs3, pl3, np3, b, ldb, ncols, f, img3, imgb3, ws,
                                                          ws_n, nst, s), "pgcn_spmm_dense_pat_bf16x3_f32")
@@ -627,7 +633,7 @@ class HipKernels:
                 check(lib.pgcn_spmm_csr_plan_if_f32(rowptr, col, val, tasks, ntasks, seg, nslices, None, 0, rmap, b, ldb,
                                                     c, ldc, f, ws, ws_n, nslots, gflags, pred, s), "pgcn_spmm_csr_plan_if_f32")
             elif name == "strip":
-                check(lib.pgcn_spmm_strip_if_f32(sw, sn, srec, spairs, b, ldb, ncols, f, ws, ws_n, nst, pred, s), "pgcn_spmm_strip_if_f32")
+                check(strip_if_fn(sw, sn, srec, spairs, b, ldb, ncols, f, ws, ws_n, nst, pred, s), strip_name)
             else:
                 check(lib.pgcn_spmm_dense_bf16x3_if_f32(w3, n3, bi3, v3, pl3, np3, b, ldb, ncols, f, img3, imgb3, ws, ws_n, nst, pred, s),
                       "pgcn_spmm_dense_bf16x3_if_f32")

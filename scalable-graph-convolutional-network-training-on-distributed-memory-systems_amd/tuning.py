@@ -74,10 +74,25 @@ class Tuning:
                                      # 8-way run: 1.1 k records lose, 4.9 k break even, 8.6 k and 14.9 k win 9-15 %)
     strip_pieces: int = 1024         # upper bound of the strip work pieces (records / 64, in multiples of 256 CUs)
     strip_stage_cost: float = 1.0    # staging a panel ~ this many records of work (piece balancing)
-    lanes: str = "strip/gather+dense3"  # launch lanes of the producers of one product: the LDS-bound strips on a second stream beside the gather
-                                     # part and the bf16 blocks (r04, Reddit shape: one stream 1.610 ms, this 1.545; strips + dense3 beside the
-                                     # gather 1.572, three streams 1.57-1.58; lanes confined to disjoint CU ranges 2.9-5.8 ms: profiles/r04_lanes.txt)
+    lanes: str = "gather+dense3/strip"  # launch lanes of the producers of one product ("/" separates lanes, launched in the order written, the
+                                     # last one is the current stream): the gather part and then the bf16 blocks on a side stream, the strips on
+                                     # the current one.  r04, 16-wave strips, Reddit shape: one stream 1.610 ms, strip/gather+dense3 1.545,
+                                     # strips + dense3 beside the gather 1.572, three streams 1.57-1.58; lanes confined to disjoint CU ranges
+                                     # 2.9-5.8 ms (profiles/r04_lanes.txt).  With the 8-wave strips (strip_waves) the gather grid must be
+                                     # launched FIRST: ms per epoch gather+dense3/strip 7.97-8.00, strip/dense3/gather 8.24-8.28,
+                                     # strip/gather+dense3 8.81-8.83 (the 16-wave kernel: 8.54-8.59 under either order, two runs each: inside the
+                                     # spread).  The order also holds for groups that keep 16 waves on lanes: strip_waves=16 as just said;
+                                     # value-free strip records under this order were NOT measured (no benchmark line puts them on lanes)
     lanes_min_nnz: int = 20000000    # smaller matrices keep one stream
+    strip_waves: int = 8             # waves per strip workgroup, 16 | 8, of launch groups that really run on lanes (stored records only): 16 waves at
+                                     # 120 registers and 154 KB fill a CU, so gather workgroups wait until a strip workgroup retires; 8 waves on
+                                     # the same records (176 registers, 153 KB, pgcn_spmm_strip_w8_f32; the same bits) leave room for two gather
+                                     # workgroups per CU, which pull rows through the L1 while the strips are bound by LDS reads.  Alone the
+                                     # 8-wave kernel is 2 % slower by the mean of six launches (6 318 against 6 200 clk per record) and 13 % by
+                                     # the best (0.599 against 0.531 ms), so single-lane groups, shards, groups with no gather grid on another
+                                     # lane and the value-free records keep 16.  One MI355X, four alternating runs: parent 8.555-8.583 ms per epoch, this
+                                     # 7.968-8.001; launch group 1.543 -> 1.414 ms; strip_waves=16 8.54-8.59; products 42.0 -> 41.0, SBM 14.30 -> 14.23,
+                                     # rank 0 of 8 (lanes off) 2.72 -> 2.72 (profiles/strip_w8_bench.txt, strip_w8_trace.txt)
     # ---- reuse of an unchanged operand's aggregation ------------------------------------------------------------
     reuse_operand: int = 1           # single-rank engines keep A . H of a graph-leaf operand (the input features: the same matrix every epoch) and,
                                      # from its third sighting on, skip the launch group while a device-side bitwise compare of H against a kept
@@ -158,6 +173,8 @@ def _parse(spec: str, base: Tuning) -> Tuning:
         setattr(out, k, val)
     if out.dense3_values not in DENSE3_VALUES:
         raise ValueError("PGCN_TUNING: dense3_values must be one of %s, got %r" % ("|".join(DENSE3_VALUES), out.dense3_values))
+    if out.strip_waves not in (8, 16):
+        raise ValueError("PGCN_TUNING: strip_waves must be 8 or 16, got %r" % (out.strip_waves,))
     return out
 
 

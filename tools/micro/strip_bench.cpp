@@ -4,6 +4,8 @@
 // loop, and with PGCN_STRIP_PROBE=4 the per-wave phase timers.  A pure HIP binary: a gpurun call costs ~30 s.
 // The second-generation kernel was developed on it next to the first one (both built in, records in both
 // layouts): bit-identical partial sums, 6 560 -> 5 100 clk per record; profiles/r02_strip_bench.txt.
+// The 8-wave form of the kernel (pgcn_spmm_strip_w8_f32) runs next to it on the same records: clk per record alone and
+// "N differing values of M" against the 16-wave kernel, which must read 0 (profiles/strip_w8_bench.txt).
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstdlib>
@@ -24,6 +26,8 @@ extern "C" int pgcn_spmm_strip3_f32(const int32_t *, int64_t, const int32_t *, c
 #endif
 extern "C" int pgcn_spmm_strip_f32(const int32_t *, int64_t, const int32_t *, const int32_t *, const float *, int64_t, int64_t,
                                     int32_t, float *, int64_t, int64_t, void *);
+extern "C" int pgcn_spmm_strip_w8_f32(const int32_t *, int64_t, const int32_t *, const int32_t *, const float *, int64_t, int64_t,
+                                       int32_t, float *, int64_t, int64_t, void *);
 extern "C" const char *pgcn_last_error(void);
 
 #define CHECK(x) do { hipError_t e = (x); if (e != hipSuccess) { printf("HIP error %s at %d\n", hipGetErrorString(e), __LINE__); exit(1); } } while (0)
@@ -85,7 +89,8 @@ int main(int argc, char **argv) {
         }
     std::vector<float> hB((size_t)n * f);
     for (auto &x : hB) x = (float)(rng() % 2001) / 1000.f - 1.f;
-    int32_t *dwork, *drecs, *dpn, *dpx; float *dB, *dws_n, *dws_x;
+    int32_t *dwork, *drecs, *dpn, *dpx; float *dB, *dws_n, *dws_x, *dws_8;
+    bool w8_bad = false;
     const int64_t nslots = (int64_t)npieces * 512;
     CHECK(hipMalloc(&dwork, work.size() * 4)); CHECK(hipMemcpy(dwork, work.data(), work.size() * 4, hipMemcpyHostToDevice));
     CHECK(hipMalloc(&drecs, recs.size() * 4)); CHECK(hipMemcpy(drecs, recs.data(), recs.size() * 4, hipMemcpyHostToDevice));
@@ -94,6 +99,7 @@ int main(int argc, char **argv) {
     CHECK(hipMalloc(&dws_n, nslots * f * 4)); CHECK(hipMalloc(&dws_x, nslots * f * 4)); CHECK(hipMemset(dws_x, 0xdd, nslots * f * 4));
     CHECK(hipMalloc(&dpx, pairs_next.size() * 4)); CHECK(hipMemcpy(dpx, pairs_next.data(), pairs_next.size() * 4, hipMemcpyHostToDevice));
     CHECK(hipMemset(dws_n, 0xee, nslots * f * 4));
+    CHECK(hipMalloc(&dws_8, nslots * f * 4)); CHECK(hipMemset(dws_8, 0xcc, nslots * f * 4));
     hipEvent_t e0, e1; CHECK(hipEventCreate(&e0)); CHECK(hipEventCreate(&e1));
     auto timeit = [&](const char *name, int which) {
         float best = 1e9f, sum = 0.f;
@@ -109,6 +115,8 @@ int main(int argc, char **argv) {
             if (which == 2) rc = pgcn_spmm_strip3_f32(dwork, npieces, drecs, dpx, dB, f, n, f, dws_x, nslots * f, nslots, nullptr);
             else
 #endif
+            if (which == 8) rc = pgcn_spmm_strip_w8_f32(dwork, npieces, drecs, dpn, dB, f, n, f, dws_8, nslots * f, nslots, nullptr);
+            else
             rc = pgcn_spmm_strip_f32(dwork, npieces, drecs, dpn, dB, f, n, f, dws_n, nslots * f, nslots, nullptr);
             if (rc) { printf("%s failed: %s\n", name, pgcn_last_error()); exit(1); }
             CHECK(hipEventRecord(e1)); CHECK(hipEventSynchronize(e1));
@@ -120,6 +128,17 @@ int main(int argc, char **argv) {
                (long long)nrec, sum / reps, best, clk);
     };
     timeit("strip", 1);
+    timeit("strip w8", 8);
+    if (!(getenv("PGCN_STRIP_PROBE") && atoi(getenv("PGCN_STRIP_PROBE")))) {
+        std::vector<float> ha((size_t)nslots * f), hb((size_t)nslots * f);
+        CHECK(hipMemcpy(ha.data(), dws_n, ha.size() * 4, hipMemcpyDeviceToHost));
+        CHECK(hipMemcpy(hb.data(), dws_8, hb.size() * 4, hipMemcpyDeviceToHost));
+        size_t nd = 0;
+        for (size_t i = 0; i < ha.size(); ++i)
+            if (memcmp(&ha[i], &hb[i], 4)) { if (nd < 5) printf("  mismatch at slot %zu col %zu: %g vs %g\n", i / f, i % f, ha[i], hb[i]); ++nd; }
+        printf("strip vs strip w8: %zu differing values of %zu\n", nd, ha.size());
+        if (nd) w8_bad = true;
+    }
 #ifdef WITH_HALF
     timeit("strip half", 3);
 #endif
@@ -184,5 +203,5 @@ int main(int argc, char **argv) {
             }
     }
     printf("kernel vs plain loop (sample): %zu differing values, max |diff| %g\n", bad, maxref);
-    return bad ? 2 : 0;
+    return bad || w8_bad ? 2 : 0;
 }
