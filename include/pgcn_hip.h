@@ -970,6 +970,41 @@ int pgcn_ppr_step_backward_f32(const float *G, int64_t ldg, const float *T, int6
                                int32_t f, float alpha, int32_t last, float *Gout, int64_t ldgo, float *Dout, int64_t lddo,
                                pgcn_stream_t stream);
 
+/* ---- generalised-PageRank propagation with learned hop weights (GPR-GNN; PGCN.py: PGpr; no counterpart in the reference) ----
+ * OUT = sum_{k=0..K} g_k A^k H with g = gamma, K + 1 floats in DEVICE memory that the kernels read (an optimiser step needs no
+ * rebinding; the host never reads them).  The aggregations are the engine's; these kernels are the element-wise half of a step and
+ * of the adjoint's.  Every operation below is rounded to fp32 on its own (no fma), fl() marks one rounding.
+ *
+ * pgcn_gpr_step_f32:  Y[i,j] = Yin ? fl(Yin[i,j] + fl(g_k X[i,j])) : fl(g_k X[i,j])  (Yin NULL: step 0, nothing is added).  Y may be
+ *   Yin (or X) itself, with equal leading dimensions.
+ * pgcn_gpr_step_backward_f32:  Dout[i,j] = Din ? fl(Din[i,j] + fl(g_k T[i,j])) : fl(g_k T[i,j]), T = T^k the k-th backward
+ *   aggregation of dOUT; Dout NULL: not written (H needs no gradient; Din is ignored); Dout may be Din (or T) itself, with equal leading
+ *   dimensions.  In the same pass the partial sums of sum_{i,j} (double)T[i,j] (double)H[i,j] go to region k of the work-space: every
+ *   product is exact in double, a block adds those of a band of 512 rows in a fixed order and leaves one double.
+ * pgcn_gpr_dot_finish_f32:  one launch after the last step; dgamma[k] = float(sum of region k's records, in ascending order through
+ *   a fixed tree) for k = 0 .. K, rounded once.  nrows == 0: zeros.  No floating-point atomics: the same input gives the same bits.
+ * pgcn_gpr_ws_bytes:  bytes of the work-space of one backward pass (all K + 1 regions; each holds its record count, written by the
+ *   step, and one double per band); -1: not covered.  Its contents are the steps' own: nothing needs clearing.  Every call of one
+ *   pass takes the same nrows, f and K.
+ *
+ * All: the layout of the row-band kernels (256 threads, four consecutive columns per thread, 64-bit row addresses); f from 1 to 1024
+ * (PGCN_EUNSUPPORTED above); float4 when f % 4 == 0 and every base and leading dimension keeps rows 16-byte aligned, four guarded
+ * scalars otherwise, the same bits either way.  Contiguous operands (every leading dimension == f) of a width that is no multiple of
+ * 4 run as rows of 128 columns and one short last row: the same bits of Y and D, float4 traffic, two launches (dgamma then adds in
+ * another fixed order).  A NaN or inf stays in its own element and in its own dgamma[k].  nrows == 0: no launch of a step.
+ * PGCN_EINVAL, nothing launched: a null required pointer (gamma and ws always; the matrices when nrows > 0), nrows < 0, f < 1, a
+ * leading dimension below f, K < 0 or above 65534, k outside 0 .. K, in place with differing leading dimensions, a work-space that
+ * is not 8-byte aligned; PGCN_ENOMEM: a work-space below pgcn_gpr_ws_bytes.  Raw pointers + a stream, no allocation, no
+ * synchronisation (graph-capturable).                                                                                        */
+int64_t pgcn_gpr_ws_bytes(int64_t nrows, int32_t f, int32_t K);
+int pgcn_gpr_step_f32(const float *X, int64_t ldx, const float *Yin, int64_t ldyin, const float *gamma, int32_t k, int32_t K,
+                      int64_t nrows, int32_t f, float *Y, int64_t ldy, pgcn_stream_t stream);
+int pgcn_gpr_step_backward_f32(const float *T, int64_t ldt, const float *H, int64_t ldh, const float *Din, int64_t lddin,
+                               const float *gamma, int32_t k, int32_t K, int64_t nrows, int32_t f, float *Dout, int64_t lddo, void *ws,
+                               int64_t ws_bytes, pgcn_stream_t stream);
+int pgcn_gpr_dot_finish_f32(const void *ws, int64_t ws_bytes, int64_t nrows, int32_t f, int32_t K, float *dgamma,
+                            pgcn_stream_t stream);
+
 /* ---- the tail of a GAT layer: head mean, bias, ELU and dropout (PGAT.py: _GatTail) ------------------------------------
  * A GAT layer ends with drop(act(reduce_heads(X) + b)); X is the nrows x heads * d output of the aggregation on OWNED rows, the
  * heads side by side.  The output width is fout = mean ? d : heads * d.

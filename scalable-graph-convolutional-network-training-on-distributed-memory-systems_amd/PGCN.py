@@ -322,6 +322,69 @@ class Propagate(nn.Module):
         return PPropagate.apply(self.A, H, self.K, self.alpha)
 
 
+class PGpr(torch.autograd.Function):
+    """Generalised-PageRank propagation of the logits with LEARNED hop weights (GPR-GNN, Chien et al., ICLR 2021; csrc/pgcn_gpr.hip):
+    OUT = sum_{k=0..K} gamma_k A^k H -- forward ``A.gpr`` (K aggregations at the width of H, each with the halo exchange, each followed
+    by one element-wise pass), backward ``A.gpr_backward``: the exact adjoint, and dgamma_k = <A^T^k dOUT, H> over this rank's rows
+    (a partial sum: it joins the gradient all-reduce like every weight gradient).  The map is linear in H and in gamma: H and gamma are
+    all that is saved.  An input that needs no gradient gets none; dgamma is formed either way."""
+
+    @staticmethod
+    def forward(ctx, A, H, gamma):
+        ctx.A = A
+        ctx.save_for_backward(H, gamma)
+        return A.gpr(H, gamma)
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        H, gamma = ctx.saved_tensors
+        dH, dgamma = ctx.A.gpr_backward(grad_output, H, gamma, ctx.needs_input_grad[1])
+        join = getattr(ctx.A, "join_wgrad", None)        # (as PSpMM.backward: a weight gradient parked on the engine's side stream)
+        if join is not None:
+            join()
+        return None, dH, dgamma if ctx.needs_input_grad[2] else None
+
+
+GPR_INITS = ("ppr", "uniform")         # --gpr-init / run(gpr_init=...)
+GPR_ALPHA = 0.1                        # --gpr-alpha / run(gpr_alpha=...): the alpha of the "ppr" initialisation when none is given
+
+
+def gpr_initial(K, init="ppr", alpha=GPR_ALPHA):
+    """The K + 1 initial hop weights as a fp32 tensor.  "ppr": gamma_k = alpha (1 - alpha)^k for k < K and gamma_K = (1 - alpha)^K,
+    computed in Python doubles and rounded to fp32 once (APPNP's weights: the model starts as ``Propagate(K, alpha)``); "uniform":
+    1 / (K + 1).  A function of its arguments alone: the same on every rank."""
+    if init == "uniform":
+        values = [1.0 / (K + 1)] * (K + 1)
+    else:
+        values = [alpha * (1.0 - alpha) ** k for k in range(K)] + [(1.0 - alpha) ** K]
+    return torch.tensor(values, dtype=torch.float64).to(torch.float32)
+
+
+class Gpr(nn.Module):
+    """``PGpr`` as the last module of a model: OUT = sum_k gamma_k A^k H over the engine's stored matrix (meant for a normalised one),
+    ``gamma`` an ``nn.Parameter`` of K + 1 fp32 values trained with the rest of the model (they may turn negative) and initialised by
+    ``gpr_initial(K, init, alpha)``.  gamma takes the model's ONE weight decay like every other parameter: the optimisers here have no
+    per-parameter groups.  The same in ``train()`` and ``eval()``.  In a model with DropEdge (``PGCN(drop_edge=...)``) it keeps using
+    the UNDROPPED matrix, as ``Propagate`` does."""
+
+    def __init__(self, A, K, init="ppr", alpha=GPR_ALPHA):
+        super(Gpr, self).__init__()
+        if isinstance(K, bool) or not isinstance(K, int) or K < 1:
+            raise ValueError("gpr takes an integer K >= 1, got %r" % (K,))
+        if init not in GPR_INITS:
+            raise ValueError("gpr_init takes %s, got %r" % (" | ".join(GPR_INITS), init))
+        if isinstance(alpha, bool) or not isinstance(alpha, (int, float)) or not 0.0 <= float(alpha) <= 1.0:
+            raise ValueError("gpr_alpha takes a number with 0 <= alpha <= 1, got %r" % (alpha,))
+        self.A, self.K, self.init, self.alpha = A, K, init, float(alpha)
+        self.gamma = nn.Parameter(gpr_initial(K, init, self.alpha))
+
+    def extra_repr(self):
+        return "K=%d, init=%s" % (self.K, "ppr(alpha=%g)" % self.alpha if self.init == "ppr" else self.init)
+
+    def forward(self, H):
+        return PGpr.apply(self.A, H, self.gamma)
+
+
 def _no_aggregation(A, H):
     """``PGCN(aggregate=False)``: the layer's input is its own 'aggregation' (a dense layer, the MLP in front of ``Propagate``)."""
     return H
@@ -1722,7 +1785,8 @@ def _barrier():
 
 
 def _architecture(fin, classes, nlayers, nfeatures, hidden, multilabel, dropout, dropout_seed, norm, root_weight, bias, residual, aggr=None,
-                  propagate=None, ppr_alpha=None, dense_layers=None, drop_edge=None, softmax_beta=None):
+                  propagate=None, ppr_alpha=None, dense_layers=None, drop_edge=None, softmax_beta=None, gpr=None, gpr_init=None,
+                  gpr_alpha=None):
     """checkpoint.architecture of the model ``_train_on_data`` builds from these arguments (``drop_edge``: recorded only when it is
     positive, so that earlier checkpoints compare as before)."""
     widths = [int(fin)] + [int(nfeatures if hidden is None else hidden)] * (nlayers - 1) + [int(classes)]
@@ -1731,7 +1795,9 @@ def _architecture(fin, classes, nlayers, nfeatures, hidden, multilabel, dropout,
                                     **({"propagate": (propagate, PPR_ALPHA if ppr_alpha is None else ppr_alpha)} if propagate is not None else {}),
                                     **({"dense_layers": True} if dense_layers else {}),
                                     **({"drop_edge": float(drop_edge)} if drop_edge else {}),
-                                    **({"softmax_beta": float(softmax_beta)} if softmax_beta is not None else {}))
+                                    **({"softmax_beta": float(softmax_beta)} if softmax_beta is not None else {}),
+                                    **({"gpr": (gpr, gpr_init or GPR_INITS[0], GPR_ALPHA if gpr_alpha is None else gpr_alpha)}
+                                       if gpr is not None else {}))
 
 
 def _check_softmax_beta(softmax_beta, aggr=None, dense_layers=None, drop_edge=None):
@@ -1782,6 +1848,21 @@ def _check_propagate(propagate, ppr_alpha, dense_layers, aggr=None, root_weight=
         raise ValueError("dense_layers does not go with %s" % ('aggr="max"' if aggr == "max" else "root_weight"))
 
 
+def _check_gpr(gpr, gpr_init, gpr_alpha, propagate=None):
+    """ValueError for values of run's ``gpr`` / ``gpr_init`` / ``gpr_alpha`` that no model can be built from."""
+    if gpr is not None and (isinstance(gpr, bool) or not isinstance(gpr, int) or gpr < 1):
+        raise ValueError("gpr takes an integer >= 1, got %r" % (gpr,))
+    if gpr is not None and propagate is not None:
+        raise ValueError("gpr does not go with propagate: the hop weights are either learned or fixed")
+    if gpr is None and (gpr_init is not None or gpr_alpha is not None):
+        raise ValueError("gpr_init and gpr_alpha need gpr")
+    if gpr_init is not None and gpr_init not in GPR_INITS:
+        raise ValueError("gpr_init takes %s, got %r" % (" | ".join(GPR_INITS), gpr_init))
+    if gpr_alpha is not None and (isinstance(gpr_alpha, bool) or not isinstance(gpr_alpha, (int, float))
+                                  or not 0.0 <= float(gpr_alpha) <= 1.0):
+        raise ValueError("gpr_alpha takes a number with 0 <= alpha <= 1, got %r" % (gpr_alpha,))
+
+
 TASKS = tuple(_nodeloss.TASKS)         # --task / run(task=...): "single", one class per vertex (the default), or "multilabel"
 OPTIMIZERS = _nodeloss.OPTIMIZERS      # --optimizer / run(optimizer=...): "torch" (the default) or "fused"
 
@@ -1789,7 +1870,7 @@ OPTIMIZERS = _nodeloss.OPTIMIZERS      # --optimizer / run(optimizer=...): "torc
 def _train_on_data(A, n, nlayers, nfeatures, features, labels, split, hidden, epochs, lr, eval_every, dropout, dropout_seed,
                    multilabel=False, weight_decay=0.0, decoupled_decay=False, optimizer="torch", norm=None, root_weight=None, bias=None,
                    residual=None, save=None, load=None, predict=None, proba=None, control=None, aggr=None, propagate=None, ppr_alpha=None,
-                   dense_layers=None, drop_edge=None, softmax_beta=None):
+                   dense_layers=None, drop_edge=None, softmax_beta=None, gpr=None, gpr_init=None, gpr_alpha=None):
     """The loop of ``run`` on real inputs: widths fin -> hidden -> ... -> C, no ReLU on the last layer, constant features (the
     first layer's backward aggregation is skipped), Adam, the masked loss over the train rows.  Reports every ``eval_every``
     epochs: without dropout from the record of the training step's own pass (the logits BEFORE that step's update), with
@@ -1817,8 +1898,11 @@ def _train_on_data(A, n, nlayers, nfeatures, features, labels, split, hidden, ep
     pattern that survive the step, renormalised (class PGCN, ``PSpMMDrop``; ``A`` built with ``normalize="sym"``); the mask's seed and
     step are the dropout state's, which then exists even with ``dropout`` = 0, and the reporting rule is dropout's: ``evaluate`` in
     eval mode after the update.  ``Propagate`` keeps the undropped matrix.  ``softmax_beta=B``: every layer aggregates by the softmax
-    aggregation (class PGCN, ``PAggSoftmax``); ``Propagate`` keeps ``PSpMM``.  None: the model of before."""
+    aggregation (class PGCN, ``PAggSoftmax``); ``Propagate`` keeps ``PSpMM``.  None: the model of before.  ``gpr=K`` (``gpr_init``,
+    ``gpr_alpha``): the module ``Gpr`` follows the last layer instead -- the K + 1 hop weights are a parameter, reduced, decayed and
+    stepped with the rest; rank 0 prints them after the last report."""
     _check_propagate(propagate, ppr_alpha, dense_layers, aggr, root_weight)
+    _check_gpr(gpr, gpr_init, gpr_alpha, propagate)
     _check_drop_edge(drop_edge, getattr(A.part, "normalize", None), aggr, dense_layers)
     _check_softmax_beta(softmax_beta, aggr, dense_layers, drop_edge)
     drop_edge = float(drop_edge or 0.0)
@@ -1847,6 +1931,8 @@ def _train_on_data(A, n, nlayers, nfeatures, features, labels, split, hidden, ep
     if softmax_beta is not None:
         extra["softmax_beta"] = softmax_beta
     tail = [Propagate(A, propagate, PPR_ALPHA if ppr_alpha is None else float(ppr_alpha))] if propagate is not None else []
+    if gpr is not None:
+        tail = [Gpr(A, gpr, gpr_init or GPR_INITS[0], GPR_ALPHA if gpr_alpha is None else float(gpr_alpha))]
     model = nn.Sequential(*[PGCN(A, widths[i], widths[i + 1], dropout=dropout if i < nlayers - 1 else 0.0, layer=i, state=state,
                                  relu=i < nlayers - 1, **({"norm": norm} if norm not in (None, "none") and i < nlayers - 1 else {}),
                                  **extra, **({"residual": True} if residual and i < nlayers - 1 and widths[i] == widths[i + 1] else {}))
@@ -1859,7 +1945,8 @@ def _train_on_data(A, n, nlayers, nfeatures, features, labels, split, hidden, ep
     first, history, best, hooks = 0, [], None, None
     if save is not None or load is not None or predict is not None or proba:
         arch = _architecture(data.fin, data.classes, nlayers, nfeatures, hidden, multilabel, dropout, dropout_seed, norm, root_weight,
-                             bias, residual, aggr, propagate, ppr_alpha, dense_layers, drop_edge, softmax_beta)
+                             bias, residual, aggr, propagate, ppr_alpha, dense_layers, drop_edge, softmax_beta,
+                             **({"gpr": gpr, "gpr_init": gpr_init, "gpr_alpha": gpr_alpha} if gpr is not None else {}))
         hooks = _checkpoint.Hooks("PGCN", arch, model, fused, opt, state, save, load, predict, proba, myrank, _barrier)
         first, history, best = hooks.resume()
     last = first + epochs - 1
@@ -1908,6 +1995,8 @@ def _train_on_data(A, n, nlayers, nfeatures, features, labels, split, hidden, ep
                      lambda want_prob: (_predict(model, H, kind, True, want_prob), A.part.owned, n, data.classes))
         model.best_state = hooks.best_state
     best = _nodeloss.close(task, elapsed.item(), epochs, best, myrank == 0)
+    if gpr is not None and myrank == 0:
+        print("gamma " + " ".join("%.6g" % v for v in model[-1].gamma.detach().cpu().tolist()), flush=True)
     model.history, model.best, model.widths = history, best, widths
     return model
 
@@ -1916,7 +2005,7 @@ def run(rank, size, nlayers, nfeatures, path_A, path_partvec, backend, normalize
         features=None, labels=None, split=None, hidden=None, epochs=None, lr=None, eval_every=None, task=None,
         weight_decay=None, decoupled_decay=None, optimizer=None, norm=None, root_weight=None, bias=None, residual=None,
         save=None, load=None, predict=None, proba=None, aggr=None, propagate=None, ppr_alpha=None, dense_layers=None, drop_edge=None,
-        softmax_beta=None, **control):
+        softmax_beta=None, gpr=None, gpr_init=None, gpr_alpha=None, **control):
     """PGCN.py:162-238.  ``normalize="sym"``: train on D_r^-1/2 (A + I) D_c^-1/2 of the pattern of ``path_A``, built on the fly
     (partition.build_partition) instead of by the offline pass preprocess/GrB-GNN-IDG.py.  ``dropout`` > 0: the output of every
     layer but the last is dropped with that probability (class PGCN), masks from (``dropout_seed``, step, layer, global row,
@@ -1962,7 +2051,12 @@ def run(rank, size, nlayers, nfeatures, path_A, path_partvec, backend, normalize
     (``PAggSoftmax``, csrc/pgcn_aggsoftmax.hip): per feature the softmax(beta x)-weighted mean of a vertex's stored neighbourhood --
     0 its mean, large values its max; the stored values are ignored, with ``normalize="sym"`` a vertex is its own neighbour.  Not
     with ``aggr="max"``, ``dense_layers`` or a positive ``drop_edge``.  A checkpoint records it: loading one under another value, or
-    without it, raises ValueError naming ``softmax_beta``."""
+    without it, raises ValueError naming ``softmax_beta``.
+    ``gpr`` (an integer K >= 1; needs the three files; not with ``propagate``): the logits of the last layer are propagated with
+    LEARNED hop weights, OUT = sum_{k=0..K} gamma_k A^k H (GPR-GNN; ``Gpr``, csrc/pgcn_gpr.hip); ``gpr_init`` ("ppr", the default: APPNP's
+    weights for ``gpr_alpha``, 0 <= alpha <= 1, default 0.1 -- the model starts as ``propagate=K``; or "uniform": 1 / (K + 1)); both need
+    ``gpr``.  gamma is a parameter like the weights: it takes ``weight_decay`` too (no per-parameter groups).  A checkpoint records
+    K, the initialisation and alpha, and carries gamma; rank 0 prints the final gamma after the last report."""
     global myrank, world_size, send_map, recv_map, device, X, recv_buffers, send_buffers, stats
     for name in control:
         if name not in _nodeloss.CONTROL:
@@ -1999,6 +2093,9 @@ def run(rank, size, nlayers, nfeatures, path_A, path_partvec, backend, normalize
     _check_propagate(propagate, ppr_alpha, dense_layers, aggr, root_weight)
     if (propagate is not None or ppr_alpha is not None or dense_layers is not None) and not all(given):
         raise ValueError("propagate, ppr_alpha and dense_layers need features, labels and split")
+    _check_gpr(gpr, gpr_init, gpr_alpha, propagate)
+    if gpr is not None and not all(given):
+        raise ValueError("gpr needs features, labels and split")
     _check_drop_edge(drop_edge, normalize, aggr, dense_layers)
     if drop_edge is not None and not all(given):
         raise ValueError("drop_edge needs features, labels and split")
@@ -2029,7 +2126,8 @@ def run(rank, size, nlayers, nfeatures, path_A, path_partvec, backend, normalize
         opened = _nodeloss.TASKS[task or "single"].open_checked(features, labels, split, len(partvec))
         if load is not None:
             arch = _architecture(opened[3], opened[4], nlayers, nfeatures, hidden, multilabel, dropout, dropout_seed, norm, root_weight,
-                                 bias, residual, aggr, propagate, ppr_alpha, dense_layers, drop_edge, softmax_beta)
+                                 bias, residual, aggr, propagate, ppr_alpha, dense_layers, drop_edge, softmax_beta,
+                                 **({"gpr": gpr, "gpr_init": gpr_init, "gpr_alpha": gpr_alpha} if gpr is not None else {}))
             load = _checkpoint.load(load, "PGCN", arch, optimizer or "torch")
         del opened
         if control and load is not None:        # (the horizon against the warm-up, from the epoch the checkpoint stands at)
@@ -2083,7 +2181,8 @@ def run(rank, size, nlayers, nfeatures, path_A, path_partvec, backend, normalize
                               **{k: v for k, v in (("propagate", propagate), ("ppr_alpha", ppr_alpha)) if v is not None},
                               **({"dense_layers": True} if dense_layers else {}),
                               **({"drop_edge": float(drop_edge)} if drop_edge else {}),
-                              **({"softmax_beta": float(softmax_beta)} if softmax_beta is not None else {}))
+                              **({"softmax_beta": float(softmax_beta)} if softmax_beta is not None else {}),
+                              **{k: v for k, v in (("gpr", gpr), ("gpr_init", gpr_init), ("gpr_alpha", gpr_alpha)) if v is not None})
 
     owned = A.part.owned.to(device)
     # PGCN.py:186-188 synthetic features H[i,:] = i, owned rows only
@@ -2160,9 +2259,9 @@ def init_process(rank, size, fn, nlayers, nfeatures, path_A, path_partvec, backe
                  features=None, labels=None, split=None, hidden=None, epochs=None, lr=None, eval_every=None, task=None,
                  weight_decay=None, decoupled_decay=None, optimizer=None, norm=None, root_weight=None, bias=None, residual=None,
                  save=None, load=None, predict=None, proba=None, control=None, aggr=None, propagate=None, ppr_alpha=None, dense_layers=None,
-                 drop_edge=None, softmax_beta=None):
+                 drop_edge=None, softmax_beta=None, gpr=None, gpr_init=None, gpr_alpha=None):
     """PGCN.py:241-253.  ``control``: the given options of nodeloss.CONTROL as one dict (None: today's call).  ``aggr``, ``propagate``,
-    ``ppr_alpha``, ``dense_layers``, ``drop_edge``, ``softmax_beta``: run's."""
+    ``ppr_alpha``, ``dense_layers``, ``drop_edge``, ``softmax_beta``, ``gpr``, ``gpr_init``, ``gpr_alpha``: run's."""
     global _exchanger
     dist.init_process_group(backend, rank=rank, world_size=size)
 
@@ -2184,7 +2283,7 @@ def init_process(rank, size, fn, nlayers, nfeatures, path_A, path_partvec, backe
                     ("optimizer", optimizer), ("norm", norm), ("root_weight", root_weight), ("bias", bias),
                     ("residual", residual), ("save", save), ("load", load), ("predict", predict), ("proba", proba), ("aggr", aggr),
                     ("propagate", propagate), ("ppr_alpha", ppr_alpha), ("dense_layers", dense_layers),
-                    ("softmax_beta", softmax_beta)):
+                    ("softmax_beta", softmax_beta), ("gpr", gpr), ("gpr_init", gpr_init), ("gpr_alpha", gpr_alpha)):
         if v is not None:
             kw[name] = v
     kw.update(control or {})
@@ -2211,7 +2310,7 @@ def main(argv):
         opts, args = getopt.getopt(argv, "a:p:b:s:l:f:", ["normalize=", "dropout=", "dropout-seed=", "features=", "labels=", "split=",
                                                           "hidden=", "epochs=", "lr=", "eval-every=", "task=", "weight-decay=", "adamw",
                                                           "optimizer=", "norm=", "root-weight", "bias", "residual", "save=", "load=",
-                                                          "predict=", "proba", "aggr=", "propagate=", "ppr-alpha=", "dense-layers", "drop-edge=", "softmax-aggr="] + [f[2:] + "=" for f in _nodeloss.CONTROL_FLAGS.split(", ")])
+                                                          "predict=", "proba", "aggr=", "propagate=", "ppr-alpha=", "dense-layers", "drop-edge=", "softmax-aggr=", "gpr=", "gpr-init=", "gpr-alpha="] + [f[2:] + "=" for f in _nodeloss.CONTROL_FLAGS.split(", ")])
     except getopt.GetoptError:
         print("a:p:b:", flush=True)
         sys.exit(2)
@@ -2299,6 +2398,27 @@ def main(argv):
             except ValueError:
                 print("--ppr-alpha takes a number >= 0 and < 1, got %r" % arg, flush=True)
                 sys.exit(2)
+        elif opt == '--gpr':           # K hops with LEARNED weights over the logits of the last layer (GPR-GNN: class Gpr)
+            try:
+                data["gpr"] = int(arg)
+                if data["gpr"] < 1:
+                    raise ValueError
+            except ValueError:
+                print("--gpr takes an integer >= 1, got %r" % arg, flush=True)
+                sys.exit(2)
+        elif opt == '--gpr-init':      # ppr (APPNP's weights for --gpr-alpha, the default) | uniform (1 / (K + 1))
+            if arg not in GPR_INITS:
+                print("--gpr-init takes %s, got %r" % ("|".join(GPR_INITS), arg), flush=True)
+                sys.exit(2)
+            data["gpr_init"] = arg
+        elif opt == '--gpr-alpha':     # the alpha of --gpr-init ppr (0.1)
+            try:
+                data["gpr_alpha"] = float(arg)
+                if not 0.0 <= data["gpr_alpha"] <= 1.0:
+                    raise ValueError
+            except ValueError:
+                print("--gpr-alpha takes a number >= 0 and <= 1, got %r" % arg, flush=True)
+                sys.exit(2)
         elif opt == '--dense-layers':  # no layer aggregates (PGCN(aggregate=False)): with --propagate, predict then propagate
             data["dense_layers"] = True
         elif opt == '--drop-edge':     # DropEdge: drop every off-diagonal entry of the pattern with this probability at every training
@@ -2350,7 +2470,7 @@ def main(argv):
     os.environ.setdefault("WORLD_SIZE", str(size))
     files = [k for k in ("features", "labels", "split") if k in data]
     if data and len(files) != 3:
-        print("--features, --labels and --split go together (and --hidden, --epochs, --lr, --eval-every, --task, --weight-decay, --adamw, --optimizer, --save, --load, --predict, --proba, --aggr, --propagate, --ppr-alpha, --dense-layers, --drop-edge, --softmax-aggr, %s, --norm, --residual, --root-weight, --bias need them); got %%s"
+        print("--features, --labels and --split go together (and --hidden, --epochs, --lr, --eval-every, --task, --weight-decay, --adamw, --optimizer, --save, --load, --predict, --proba, --aggr, --propagate, --ppr-alpha, --dense-layers, --drop-edge, --softmax-aggr, --gpr, --gpr-init, --gpr-alpha, %s, --norm, --residual, --root-weight, --bias need them); got %%s"
               % _nodeloss.CONTROL_FLAGS % ", ".join("--" + {"decoupled_decay": "adamw"}.get(k, k.replace("_", "-")) for k in sorted(data)), flush=True)
         sys.exit(2)
     for k in files:
@@ -2362,6 +2482,12 @@ def main(argv):
         sys.exit(2)
     if "ppr_alpha" in data and "propagate" not in data:
         print("--ppr-alpha needs --propagate", flush=True)
+        sys.exit(2)
+    if "gpr" in data and "propagate" in data:
+        print("--gpr does not go with --propagate: the hop weights are either learned or fixed", flush=True)
+        sys.exit(2)
+    if ("gpr_init" in data or "gpr_alpha" in data) and "gpr" not in data:
+        print("--gpr-init and --gpr-alpha need --gpr", flush=True)
         sys.exit(2)
     if "dense_layers" in data and (data.get("aggr") == "max" or "root_weight" in data):
         print("--dense-layers does not go with %s" % ("--aggr max" if data.get("aggr") == "max" else "--root-weight"), flush=True)
@@ -2416,7 +2542,7 @@ def main(argv):
                 args += layer_opts
             if has_residual:                   # (the tuple grows only when --residual is given)
                 args += (True,)
-    named = {k: data[k] for k in ("aggr", "propagate", "ppr_alpha", "dense_layers", "drop_edge", "softmax_beta") if k in data}      # (by name, only when given)
+    named = {k: data[k] for k in ("aggr", "propagate", "ppr_alpha", "dense_layers", "drop_edge", "softmax_beta", "gpr", "gpr_init", "gpr_alpha") if k in data}      # (by name, only when given)
     p = mp.Process(target=init_process, args=args, **({"kwargs": named} if named else {}))
     p.start()
     p.join()

@@ -172,6 +172,11 @@ SIGNATURES = {
     "pgcn_ppr_step_f32": (ctypes.c_int, [_vp, _i64, _vp, _i64, _i64, _i32, ctypes.c_float, _vp, _i64, _vp]),
     "pgcn_ppr_step_backward_f32": (ctypes.c_int, [_vp, _i64, _vp, _i64, _vp, _i64, _i64, _i32, ctypes.c_float, _i32, _vp, _i64, _vp, _i64,
                                                   _vp]),
+    "pgcn_gpr_ws_bytes": (_i64, [_i64, _i32, _i32]),
+    "pgcn_gpr_step_f32": (ctypes.c_int, [_vp, _i64, _vp, _i64, _vp, _i32, _i32, _i64, _i32, _vp, _i64, _vp]),
+    "pgcn_gpr_step_backward_f32": (ctypes.c_int, [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _i32, _i32, _i64, _i32, _vp, _i64, _vp, _i64,
+                                                  _vp]),
+    "pgcn_gpr_dot_finish_f32": (ctypes.c_int, [_vp, _i64, _i64, _i32, _i32, _vp, _vp]),
     "pgcn_gat_tail_ws_bytes": (_i64, [_i64, _i32]),
     "pgcn_gat_tail_forward_f32": (ctypes.c_int, [_vp, _i64, _i64, _i32, _i32, _i32, _vp, _i32, _vp, ctypes.c_uint64, _vp, _u32, _u32, _vp,
                                                  _i64, _vp]),

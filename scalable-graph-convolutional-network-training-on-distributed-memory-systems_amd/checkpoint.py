@@ -38,12 +38,12 @@ from . import nodedata as _nodedata
 
 FORMAT_VERSION = 1
 ARCH_FIELDS = ("task", "layers", "widths", "norm", "root_weight", "bias", "residual", "heads", "out_heads", "dropout", "attn_dropout", "attention", "share_weights", "dropout_seed", "aggr",
-               "drop_edge", "softmax_beta", "propagate", "dense_layers")
+               "drop_edge", "gpr", "softmax_beta", "propagate", "dense_layers")
 
 
 def architecture(widths, task, dropout=0.0, dropout_seed=0, norm=None, root_weight=None, bias=None, residual=None, heads=None,
                  out_heads=None, aggr=None, propagate=None, dense_layers=None, drop_edge=None, softmax_beta=None, attn_dropout=None, attention=None,
-                 share_weights=None):
+                 share_weights=None, gpr=None):
     """The plain-value record of what a model was built from; two models of equal records have state dicts of equal keys and shapes,
     and draw the same dropout masks.  ``aggr``: the key exists only for "max" -- a record of the weighted sum is the record of before,
     and compares equal to every checkpoint written without the key.  Likewise ``propagate`` ((K, alpha): the key holds [K, alpha]
@@ -55,7 +55,9 @@ def architecture(widths, task, dropout=0.0, dropout_seed=0, norm=None, root_weig
     checkpoint loaded under another value is refused in its name.  ``attention`` / ``share_weights``: the keys exist only for the GATv2
     layers ("v2", and whether the two projections are one); a record without them is a v1 model, so a v1 checkpoint under a v2 command
     line, or the reverse, is refused in the name of ``attention``.  The dot-product layers record ``attention: "dot"`` the same way
-    (``share_weights`` stays False there), so every pair of v1, v2 and dot is told apart by that field."""
+    (``share_weights`` stays False there), so every pair of v1, v2 and dot is told apart by that field.  ``gpr`` ((K, init, alpha)):
+    the key holds [K, init, alpha] only when the model ends with the learned-hop-weight propagation (``PGCN.Gpr``; gamma itself is a
+    parameter in the model's state)."""
     arch = {"widths": [int(w) for w in widths], "layers": len(widths) - 1, "task": str(task or "single"),
             "norm": "none" if norm in (None, "none") else str(norm), "root_weight": bool(root_weight), "bias": bool(bias),
             "residual": bool(residual), "heads": None if heads is None else int(heads),
@@ -76,6 +78,8 @@ def architecture(widths, task, dropout=0.0, dropout_seed=0, norm=None, root_weig
         arch["attn_dropout"] = float(attn_dropout)
     if attention not in (None, "v1"):
         arch["attention"], arch["share_weights"] = str(attention), bool(share_weights)
+    if gpr is not None:
+        arch["gpr"] = [int(gpr[0]), str(gpr[1]), float(gpr[2])]
     return arch
 
 

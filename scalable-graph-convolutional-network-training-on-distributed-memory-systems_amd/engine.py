@@ -693,6 +693,31 @@ def ppr_step_backward_composed(G: torch.Tensor, T: torch.Tensor, D: Optional[tor
     return gout, dout
 
 
+# --------------------------------------------------------------------------
+# generalised-PageRank propagation with learned hop weights: the composed route (framework operations; the definitions of
+# csrc/pgcn_gpr.hip)
+
+
+def gpr_step_composed(X: torch.Tensor, Yin: Optional[torch.Tensor], gamma: torch.Tensor, k: int,
+                      out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Y of ``HipKernels.gpr_step`` from framework operations, bit for bit: Yin + (gamma[k] X), the product and the sum rounded to
+    fp32 on their own; gamma[k] is read where gamma lives.  ``out`` may be Yin itself."""
+    gx = X.detach() * gamma.detach()[k]
+    if Yin is None:
+        return gx if out is None else out.copy_(gx)
+    return torch.add(Yin, gx, out=out)
+
+
+def gpr_step_backward_composed(T: torch.Tensor, H: torch.Tensor, Din: Optional[torch.Tensor], gamma: torch.Tensor, k: int, dots: list,
+                               need_d: bool = True, dout: Optional[torch.Tensor] = None):
+    """(Dout,) of ``HipKernels.gpr_step_backward`` from framework operations, the same bits of Dout; the dot of step k is appended
+    to ``dots`` as one float64 value: exact products, a double sum in the framework's order."""
+    dots.append((T.detach().to(torch.float64) * H.detach().to(torch.float64)).sum())
+    if not need_d:
+        return (None,)
+    return (gpr_step_composed(T, Din, gamma, k, out=dout),)
+
+
 @dataclasses.dataclass
 class ReuseRecord:
     """What ``AggregationEngine.forward_reusing`` knows about the one operand it follows.  The identity is the host's filter (an operand
@@ -953,6 +978,63 @@ class AggregationEngine(BoundaryExchange):
             # (the last step of K = 1 has no D yet: its sum is written over T)
             G, D = step_backward(G, T, D, alpha, last, gout=None if last else T, dout=D if D is not None else (T if last else None))
         return D
+
+    # ------------------------------------------------------------------
+    # generalised-PageRank propagation with learned hop weights (GPR-GNN; csrc/pgcn_gpr.hip):
+    # OUT = sum_{k=0..K} gamma_k A^k H.  Linear in H and in gamma: the adjoint needs H alone.  K aggregations with ``forward``'s
+    # exchange and overlap, each followed by one element-wise pass; two n_local x f buffers take turns for Z^k (T^k) beside the
+    # accumulator, whatever K is.  gamma stays in device memory and is read by the kernels.
+    def _gpr_route(self, gamma):
+        """(K, composed) of the route, chosen before the first launch: the provider's kernels on a HIP device, else the composed
+        framework route with the same arithmetic (CPU tensors, providers without the kernels).  Nothing is built or kept."""
+        if not isinstance(gamma, torch.Tensor) or gamma.dim() != 1 or gamma.numel() < 2 or gamma.dtype is not torch.float32:
+            raise ValueError("gpr takes gamma as K + 1 >= 2 fp32 values, got %r" % (gamma,))
+        names = ("gpr_step", "gpr_step_backward", "gpr_dot_finish", "gpr_workspace")
+        return gamma.numel() - 1, not (self.on_gpu and all(hasattr(self.k, m) for m in names))
+
+    def gpr(self, H: torch.Tensor, gamma: torch.Tensor) -> torch.Tensor:
+        """OUT^K of OUT^0 = fl(g_0 H), OUT^k = fl(OUT^{k-1} + fl(g_k A^k H))  (H: n_local x f, owned rows; g = gamma, K + 1 fp32)."""
+        K, composed = self._gpr_route(gamma)
+        if H.shape[0] != self.n_local:
+            raise ValueError("H must hold exactly the %d owned rows" % self.n_local)
+        step = gpr_step_composed if composed else self._ppr_kernel(self.k.gpr_step)
+        H, gamma = H.detach().contiguous(), gamma.detach().contiguous()
+        OUT = step(H, None, gamma, 0)
+        bufs = [torch.empty((self.n_local, H.shape[1]), dtype=torch.float32, device=self.device) for _ in range(min(K, 2))]
+        Z = H
+        for k in range(1, K + 1):
+            Z = self._forward_into(Z, bufs[(k - 1) % 2])
+            step(Z, OUT, gamma, k, out=OUT)
+        return OUT
+
+    def gpr_backward(self, G: torch.Tensor, H: torch.Tensor, gamma: torch.Tensor, need_dH: bool = True):
+        """(dH | None, dgamma) of ``gpr``: T^0 = G, T^k = A^T T^{k-1}, dH = sum_k g_k T^k accumulated as D^k = fl(D^{k-1} +
+        fl(g_k T^k)), dgamma[k] = fl32(sum T^k * H in double) over THIS rank's rows (a partial sum, like every weight gradient).
+        ``need_dH`` False: the D chain is skipped, dgamma is still formed."""
+        K, composed = self._gpr_route(gamma)
+        if self.A_loc_T is None:
+            raise RuntimeError("partition was built without the transposed pieces")
+        if G.shape[0] != self.n_local or H.shape != G.shape:
+            raise ValueError("G and H must hold exactly the %d owned rows" % self.n_local)
+        G, H, gamma = G.detach().contiguous(), H.detach().contiguous(), gamma.detach().contiguous()
+        f = G.shape[1]
+        if composed:
+            step, acc = gpr_step_backward_composed, []
+        else:
+            step, acc = self._ppr_kernel(self.k.gpr_step_backward), self.k.gpr_workspace(self.n_local, f, K)
+            if acc is None:
+                raise ValueError("gpr_workspace does not cover this operand (at most %d columns)" % 1024)
+        bufs = [torch.empty((self.n_local, f), dtype=torch.float32, device=self.device) for _ in range(min(K, 2))]
+        T = G
+        (D,) = step(T, H, None, gamma, 0, acc, need_d=need_dH)
+        for k in range(1, K + 1):
+            T = self._backward_into(T, bufs[(k - 1) % 2])
+            (D,) = step(T, H, D, gamma, k, acc, need_d=need_dH, dout=D)
+        if composed:
+            dgamma = torch.stack(acc).to(torch.float32)
+        else:
+            dgamma = self._ppr_kernel(self.k.gpr_dot_finish)(acc, self.n_local, f, K)
+        return D, dgamma
 
     # ------------------------------------------------------------------
     # max aggregation (csrc/pgcn_aggmax.hip; DESIGN.md section 4): OUT[i, c] = max over the stored columns j of row i of H[j, c], ARG the

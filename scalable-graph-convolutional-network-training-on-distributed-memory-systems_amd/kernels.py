@@ -2192,6 +2192,58 @@ class HipKernels:
                                                        self._ld(Dout), self._stream()), "pgcn_ppr_step_backward_f32")
         return Gout, Dout
 
+    # -- generalised-PageRank propagation with learned hop weights: a step, an adjoint step with its dot, the finish (csrc/pgcn_gpr.hip) --
+    def _gpr_gamma_ok(self, gamma: torch.Tensor, k: int) -> bool:
+        return gamma.dim() == 1 and gamma.numel() >= 1 and self._bn_vec_ok(1, torch.float32, gamma) and 0 <= int(k) < gamma.numel()
+
+    def gpr_step(self, X: torch.Tensor, Yin: Optional[torch.Tensor], gamma: torch.Tensor, k: int, out: Optional[torch.Tensor] = None):
+        """Y = fl(Yin + fl(gamma[k] X)) (``Yin`` None: fl(gamma[k] X) alone) in one pass (pgcn_gpr_step_f32); ``gamma``: K + 1 fp32
+        values on the device, read by the kernel.  ``out`` may be Yin itself.  None when the operands are not covered."""
+        if not self._bn_mat_ok(X, Yin, out) or not self._gpr_gamma_ok(gamma, k):
+            return None
+        n, f = X.shape
+        Y = out if out is not None else torch.empty((n, f), dtype=torch.float32, device=self.device)
+        _lib.check(self.lib.pgcn_gpr_step_f32(X.data_ptr(), self._ld(X), _ptr(Yin), self._ld(Yin) if Yin is not None else 0,
+                                              gamma.data_ptr(), int(k), gamma.numel() - 1, n, f, Y.data_ptr(), self._ld(Y), self._stream()),
+                   "pgcn_gpr_step_f32")
+        return Y
+
+    def gpr_workspace(self, n: int, f: int, K: int):
+        """The float64 work-space of one backward pass of K + 1 steps on n x f operands (pgcn_gpr_ws_bytes).  None: not covered."""
+        ws_bytes = int(self.lib.pgcn_gpr_ws_bytes(int(n), int(f), int(K)))
+        return None if ws_bytes < 0 else torch.empty(ws_bytes // 8, dtype=torch.float64, device=self.device)
+
+    def gpr_step_backward(self, T: torch.Tensor, H: torch.Tensor, Din: Optional[torch.Tensor], gamma: torch.Tensor, k: int,
+                          ws: torch.Tensor, need_d: bool = True, dout: Optional[torch.Tensor] = None):
+        """(Dout,) of step k of the adjoint from T = T^k: Dout = fl(Din + fl(gamma[k] T)) (``Din`` None: the product alone; ``need_d``
+        False: Dout is None, nothing but the dot is written), and region k of ``ws`` (``gpr_workspace``) takes the partial sums of
+        sum T * H in double (pgcn_gpr_step_backward_f32).  ``dout`` may be Din itself.  None when the operands are not covered."""
+        if not self._bn_mat_ok(T, H, Din if need_d else None, dout if need_d else None) or not self._gpr_gamma_ok(gamma, k) or \
+                not self._bn_vec_ok(1, torch.float64, ws):
+            return None
+        n, f = T.shape
+        Dout = None
+        if need_d:
+            Dout = dout if dout is not None else torch.empty((n, f), dtype=torch.float32, device=self.device)
+        else:
+            Din = None
+        _lib.check(self.lib.pgcn_gpr_step_backward_f32(T.data_ptr(), self._ld(T), H.data_ptr(), self._ld(H), _ptr(Din),
+                                                       self._ld(Din) if Din is not None else 0, gamma.data_ptr(), int(k),
+                                                       gamma.numel() - 1, n, f, _ptr(Dout), self._ld(Dout) if Dout is not None else 0,
+                                                       ws.data_ptr(), ws.numel() * 8, self._stream()), "pgcn_gpr_step_backward_f32")
+        return (Dout,)
+
+    def gpr_dot_finish(self, ws: torch.Tensor, n: int, f: int, K: int, out: Optional[torch.Tensor] = None):
+        """dgamma, fp32 [K + 1]: every region of ``ws`` summed in a fixed order and rounded once, one launch after the last
+        ``gpr_step_backward`` (pgcn_gpr_dot_finish_f32).  None when the operands are not covered."""
+        if not self._bn_vec_ok(1, torch.float64, ws) or not self._bn_vec_ok(int(K) + 1, torch.float32, out) or \
+                not 0 < int(f) <= ROWBAND_MAX_F or int(K) < 0 or int(n) < 0:
+            return None
+        dgamma = out if out is not None else torch.empty(int(K) + 1, dtype=torch.float32, device=self.device)
+        _lib.check(self.lib.pgcn_gpr_dot_finish_f32(ws.data_ptr(), ws.numel() * 8, int(n), int(f), int(K), dgamma.data_ptr(),
+                                                    self._stream()), "pgcn_gpr_dot_finish_f32")
+        return dgamma
+
     # -- the tail of a GAT layer: head mean, bias, ELU and dropout (csrc/pgcn_gat_tail.hip) -------------------------------
     def gat_tail_forward(self, X: torch.Tensor, heads: int, d: int, mean: bool, bias: Optional[torch.Tensor], act: int,
                          row_ids: Optional[torch.Tensor] = None, seed: int = 0, step: Optional[torch.Tensor] = None, layer: int = 0,
