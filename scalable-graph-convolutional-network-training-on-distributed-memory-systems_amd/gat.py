@@ -395,8 +395,11 @@ class GatEngine(BoundaryExchange):
             st.s2c = torch.zeros((n_p + n_h, K), dtype=torch.float32, device=self.device)
         out = torch.empty((n_p, F), dtype=torch.float32, device=self.device)
         st.fused = False
-        split = (self.size > 1 and self.overlap and n_h > 0 and self.fwd_halo is not None and self.fused_fwd and self.covers(K, d)
-                 and self.mode_id == 0 and (drop is None or self._drop_kernels(K, d)))
+        # what every rank decides alike: ranks with halo rows exchange the s2 rows first.  The exchange is a collective, so a rank of
+        # several WITHOUT halo rows (one that owns nothing, one without an edge to a peer) takes its part in that exchange too, below
+        splits = (self.size > 1 and self.overlap and self.fused_fwd and self.covers(K, d) and self.mode_id == 0
+                  and (drop is None or self._drop_kernels(K, d)))
+        split = splits and n_h > 0 and self.fwd_halo is not None
         if split:
             # N > 1 (r06): the statistics of the edge softmax need s2 only -- its halo rows (16 bytes each) are exchanged FIRST, the 1 KB
             # rows of [Z | s2] follow on the comm stream under the statistics pass and the product over the LOCAL columns; the product
@@ -424,6 +427,12 @@ class GatEngine(BoundaryExchange):
             st.fused = True
             st.out = out
             return out
+        if splits:                                          # no halo rows here, but the peers' first all-to-all-v waits for this rank
+            st.s2c[:n_p].copy_(s2)
+            send2 = self._slab("gat_send_s2", self.n_send, K)
+            self.k.gather_rows(st.s2c[:n_p], self.send_idx, send2)
+            for w in self._exchange_all(send2, self.round_send_off, st.s2c[n_p:], self.round_recv_off, K, tag="forward_s2"):
+                w()
         if self.size > 1:                                   # PGAT.py:139 `Comm.apply(H)`: here the rows of [Z | s2]
             send = self._slab("gat_send", self.n_send, Fp)
             self.k.gather_rows(Zc[:n_p], self.send_idx, send)

@@ -356,11 +356,11 @@ def model_worker(rank, P, port, paths, gpu, q, jobs=()):
             if c["dropout"] > 0.0:
                 kw.update(dropout=c["dropout"], dropout_seed=DROPOUT_SEED)
             with redirect_stdout(io.StringIO()):
-                M.run(r, size, c["nlayers"], c["hidden"], path_A, path_partvec, "gloo", normalize="sym", **kw)
+                model = M.run(r, size, c["nlayers"], c["hidden"], path_A, path_partvec, "gloo", normalize="sym", **kw)
             eng = M._engine_current
             results.append(dict(tag=tag(c), names=cur["names"], grads=cur["grads"], logits=cur["logits"], loss=cur["loss"],
                                 own=eng.part.owned.cpu().numpy(), composed=eng._max.composed, hip=type(eng.k).__name__,
-                                kinds=cur["kinds"]))
+                                kinds=cur["kinds"], eval_logits=GG.eval_logits(M, model, paths)))
 
     M.init_process(rank, P, fn, 3, HIDDEN, paths["A"], paths["pv%d" % P], "gloo", "sym")
     q.put({"rank": rank, "results": results})

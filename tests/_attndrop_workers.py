@@ -273,8 +273,7 @@ def model64(data, params, o, step, training=True, dtype=torch.float64):
             keep = D.keep_mask(seed, step, l, np.arange(n), fout, thr)
             t = torch.where(keep, t * scale, torch.zeros((), dtype=dtype))
         h = t
-    train = torch.from_numpy(data["split"] == 1)
-    loss = F.cross_entropy(logits[train], torch.from_numpy(data["labels"])[train])
+    loss = GT.train_loss(logits, data, o)
     grads = {}
     if training:
         names = list(p)
@@ -322,7 +321,8 @@ def grad_worker(rank, P, port, paths, gpu, q, jobs=(), n=None, steps=2, provider
     for job in jobs:
         o = job["opts"]
         t = paths[o["task"]]
-        data = M._nodedata.load(t["features"], t["labels"], t["split"], eng.part.owned, n, device=M.device)
+        load, masked = GT.task_pieces(M, o)
+        data = load(t["features"], t["labels"], t["split"], eng.part.owned, n, device=M.device)
         state = D.DropoutState(o.get("seed", SEED), M.device) if o["dropout"] > 0 or o["attn"] > 0 else None
         extra = {"attn_dropout": o["attn"]} if o["attn"] > 0 else {}
         widths = [data.fin] + [o["hidden"]] * (o["nlayers"] - 1)
@@ -341,7 +341,7 @@ def grad_worker(rank, P, port, paths, gpu, q, jobs=(), n=None, steps=2, provider
             model.zero_grad()
             del launches[:]
             logits = model(data.features)
-            loss, _ = M.masked_loss(logits, data.labels, data.split, data.counts[1])
+            loss, _ = masked(logits, data.labels, data.split, data.counts[1])
             loss.backward()
             M.sum_gradients(model)
             rec["launches"].append(list(launches))

@@ -2,8 +2,9 @@
 lists and the groups of tests/test_degenerate.py and tests/test_degenerate_gpu.py.
 
 Nothing is restated here.  The data, the float64 models, the seed rule, the workers and every held comparison are those of
-_gradgrid_workers (GG), _optgrid_workers (OX) and _gat_tail_workers (GT): the double models know no partition, so their references and
-weight seeds are the balanced tests'.  A group hands those files' own runners a copy of ``paths`` whose one key "pv<P>" names the
+_gradgrid_workers (GG), _optgrid_workers (OX) and _gat_tail_workers (GT), and for the options merged after those of
+_aggsoftmax_workers (SM), _gpr_workers (GP), _attndrop_workers (AD), _gatv2_workers (V2) and _gatdot_workers (DT): the double models
+know no partition, so their references and weight seeds are the balanced tests'.  A group hands those files' own runners a copy of ``paths`` whose one key "pv<P>" names the
 vector written here, looks at what the workers answered BEFORE the runner compares it (``_watch``) -- the vector is what its row of
 VECTORS says, an empty rank reports losses of exactly 0.0 and logits of no rows -- and then lets the runner hold loss, logits, every
 rank's reduced gradients, the buffers and the eval logits through conftest.held_to_fixture as it does under a balanced vector."""
@@ -18,7 +19,12 @@ for p in (ROOT, HERE):
     if p not in sys.path:
         sys.path.insert(0, p)
 
+import _aggsoftmax_workers as SM  # noqa: E402
+import _attndrop_workers as AD  # noqa: E402
 import _gat_tail_workers as GT  # noqa: E402
+import _gatdot_workers as DT  # noqa: E402
+import _gatv2_workers as V2  # noqa: E402
+import _gpr_workers as GP  # noqa: E402
 import _gradgrid_workers as GG  # noqa: E402
 import _optgrid_workers as OX  # noqa: E402
 
@@ -40,17 +46,29 @@ def degrees(data):
     return np.bincount(A.row[A.row != A.col], minlength=A.shape[0])
 
 
+def neighbours(data, v):
+    """The vertices that share a stored entry off the diagonal with vertex ``v``."""
+    A = data["A"].tocsr()
+    return np.setdiff1d(np.union1d(A[v].indices, A[:, v].tocoo().row), [v])
+
+
 def part_vector(name, data):
-    """The vector ``name`` for the task whose arrays ``data`` are, as an int array of n entries."""
+    """The vector ``name`` for the data set whose arrays ``data`` are (any of the planted problems: n is the matrix's), as an int
+    array of n entries.  A data set without 37 set-less vertices, or without a train vertex that has a neighbour, fails here."""
     rng = np.random.default_rng(VECTOR_SEED)
     n = data["A"].shape[0]
+    assert data["split"].shape == (n,), (name, data["split"].shape, n)
     pv = np.zeros(n, np.int64)
     if name == "E3":
         pv = 1 + rng.integers(0, 2, n)
     elif name == "S2":
-        pv[np.flatnonzero(data["split"] == 0)[:SET_LESS_ROWS]] = 1
+        free = np.flatnonzero(data["split"] == 0)
+        assert free.size >= SET_LESS_ROWS, "S2 needs %d vertices in no set, this data set has %d" % (SET_LESS_ROWS, free.size)
+        pv[free[:SET_LESS_ROWS]] = 1
     elif name == "O2":
-        pv[np.flatnonzero((data["split"] == 1) & (degrees(data) >= 1))[:1]] = 1
+        first = np.flatnonzero((data["split"] == 1) & (degrees(data) >= 1))[:1]
+        assert first.size == 1, "O2 needs a train vertex with a neighbour, this data set has none"
+        pv[first] = 1
     else:
         assert name == "E2", name
     return pv
@@ -68,16 +86,21 @@ def with_vector(paths, name, data, dirname, task):
 def check_vector(name, owns, data):
     """Conditions on the INPUT, from the ranks' reported ``own`` arrays and the split: the vector is what its row says."""
     P, who = VECTORS[name]
-    assert len(owns) == P and sorted(np.concatenate(owns).tolist()) == list(range(N)), name
+    n = data["A"].shape[0]
+    assert len(owns) == P and sorted(np.concatenate(owns).tolist()) == list(range(n)), name
     split = data["split"]
     if name in ("E2", "E3"):
         assert owns[who].size == 0, (name, owns[who].size)
     if name == "E3":
-        assert all(owns[r].size >= BAND + 1 for r in (1, 2)), (name, [o.size for o in owns])
+        assert all(owns[r].size >= BAND + 1 for r in (1, 2)), \
+            "E3 needs %d rows on each of ranks 1 and 2, this data set of %d vertices gives %s" % (BAND + 1, n, [o.size for o in owns])
     if name == "S2":
         assert owns[who].size == SET_LESS_ROWS and (split[owns[who]] == 0).all(), (name, owns[who].size)
     if name == "O2":
         assert owns[who].size == 1 and split[owns[who][0]] == 1 and degrees(data)[owns[who][0]] >= 1, (name, owns[who])
+        # the premise of the one-row groups: every neighbour of the row is a halo row of its rank (it follows from the vector)
+        nb = neighbours(data, int(owns[who][0]))
+        assert nb.size >= 1 and not np.isin(nb, owns[who]).any() and np.isin(nb, np.concatenate(owns[:who] + owns[who + 1:])).all(), (name, nb)
 
 
 def check_empty_rank(name, answers, classes, epochs, where):
@@ -132,6 +155,29 @@ def newer_cases():
     labels, a double reference under the recorded selection per max configuration).  Those run as two worker groups of three."""
     return [(v, task, half) for v, task in cases("newer")
             for half in ((0, 1) if task == "multilabel" and VECTORS[v][0] == 2 else (None,))]
+
+
+# The options merged after that table was written, each under every vector: option -> vector -> task, 20 groups, the same on the CPU
+# and on the device.  Softmax aggregation and GPR-GNN are single-label (their workers know no other task); the three attention options
+# alternate as GROUPS does: multi-label under E3 and S2.
+_ALTERNATING = {"E2": "single", "E3": "multilabel", "S2": "multilabel", "O2": "single"}
+OPTION_GROUPS = {"softmax": dict.fromkeys(VECTORS, "single"), "gpr": dict.fromkeys(VECTORS, "single"),
+                 "attndrop": _ALTERNATING, "gatv2": _ALTERNATING, "gatdot": _ALTERNATING}
+
+
+def option_cases(kind):
+    return [(v, OPTION_GROUPS[kind][v]) for v in VECTORS]
+
+
+def attention_configs(kind, task):
+    """The grids of the balanced whole-model tests on the device (test_<kind>_gpu.test_whole_model_on_processes_against_the_float64_model):
+    hidden 64 on 2 heads, so that the first layer (d = 32) takes the kernels and the last (d = the classes) the composition."""
+    if kind == "attndrop":
+        return [AD.options(K=2, hidden=64, dropout=dr, attn=AD.ATTN, task=task) for dr in (0.0, GT.DROPOUT)]
+    if kind == "gatv2":
+        return [V2.options(K=2, hidden=64, Ko=2, bias=True, dropout=GT.DROPOUT, share=sh, task=task) for sh in (False, True)]
+    assert kind == "gatdot", kind
+    return [DT.options(K=2, hidden=64, Ko=2, bias=True, dropout=GT.DROPOUT, task=task)]
 
 
 # ---- the groups ---------------------------------------------------------------------------------------------------------------------------
@@ -217,36 +263,52 @@ def newer_group(datasets, dirname, name, task, gpu, half=None):
     return _grid_group("newer", OX, OX.run_group_x, newer_configs(half), datasets, dirname, name, task, gpu, lanes=(0,))
 
 
-def gat_group(gat_datasets, dirname, name, task, gpu):
-    """GT.grad_worker on the eight GAT configurations under the vector ``name``, held exactly as
-    test_gat_tail.test_whole_model_gradients_of_every_option holds its grid: GT.hold_steps, the dropout / no-dropout comparison of the
-    two steps' logits, the eval logits."""
+# option: (its worker module, the checker-backed provider with numpy stand-ins of its kernels, for the CPU)
+ATTENTION = {"gat": (GT, None), "attndrop": (AD, "attn"), "gatv2": (V2, "v2"), "gatdot": (DT, "dot")}
+
+
+def _attention_group(kind, grid, gat_datasets, dirname, name, task, gpu):
+    """W.grad_worker of the worker module W of ``kind`` on ``grid`` under the vector ``name``, held exactly as the balanced
+    whole-model test of that module holds its grid: W.hold_steps, the dropout / no-dropout comparison of the two steps' logits, the
+    eval logits.  On the CPU the newer options run on their stand-in providers, so that the engine walks the kernels' path."""
     import time
     from conftest import held_to_fixture
     t0 = time.time()
+    W, standin = ATTENTION[kind]
     paths, data = gat_datasets
-    P = VECTORS[name][0]
-    grid = gat_configs(task)
-    assert len(grid) == 8
-    refs = [GT.reference(data[task], o, 0, 2, 0.0) for o in grid]
+    P, who = VECTORS[name]
+    refs = [W.reference(data[task], o, 0, 2, 0.0) for o in grid]
     jobs = [{"opts": o, "params": {k: v.numpy() for k, v in r["params"].items()}} for o, r in zip(grid, refs)]
-    res = GT.spawn(GT.grad_worker, P, with_vector(paths, name, data[task], dirname, task), gpu, jobs=jobs, n=N)
+    extra = {} if standin is None else {"provider": None if gpu else standin}
+    res = W.spawn(W.grad_worker, P, with_vector(paths, name, data[task], dirname, task), gpu, jobs=jobs, n=N, **extra)
     answers = [r["results"] for r in res]
     assert all(len(a) == len(grid) for a in answers)
     check_vector(name, [a[0]["own"] for a in answers], data[task])
-    check_empty_rank(name, answers, GT.classes_of(data[task], grid[0]), 2, "gat")
+    check_empty_rank(name, answers, GT.classes_of(data[task], grid[0]), 2, kind)
     if gpu:
         assert all(x["hip"] == "HipKernels" for a in answers for x in a)
+    if standin is not None:
+        # the route of EVERY rank, the one without rows included: d = 32 in the kernels, the last layer (d = the classes) composed.
+        # It is decided from the provider's methods and GatEngine.covers(K, d) alone (gat.GatEngine._scored_forward; with attention
+        # dropout GatEngine.forward: _drop_kernels(K, d), and the masked kernel takes a structure without entries), never from the rows
+        assert all(x["composed"] == [False, True] for a in answers for x in a), (kind, name, [x["composed"] for a in answers for x in a])
+    if kind == "attndrop" and gpu:             # as the balanced test: the masked kernels in every training pass, none in the eval pass
+        for x in (x for a in answers for x in a):
+            for step in x["launches"]:
+                assert "gat_attndrop_forward2" in step and "gat_attndrop_grad" in step and not any(c.startswith("gat_blocks") for c in step)
+            assert not any(c.startswith("gat_attndrop") for c in x["eval_launches"])
+    if kind in ("gatv2", "gatdot") and not gpu:            # every rank made the calls of both passes, the one without rows too
+        assert all({"scores", "softmax", "grad_rows", "grad_cols"} <= {c[0] for c in r["log"]} for r in res), (kind, name)
 
     def hold():
         held = 0
         for j, (o, ref) in enumerate(zip(grid, refs)):
             ranks = [dict(r["results"][j], rank=r["rank"]) for r in res]
-            where = "degenerate%s/gat/%s/%s/P%d" % ("-gpu" if gpu else "", name, GT.tag(o), P)
-            assert all(r["tag"] == GT.tag(o) for r in ranks)
-            held += GT.hold_steps(where, ranks, ref, N, 2)
+            where = "degenerate%s/%s/%s/%s/P%d" % ("-gpu" if gpu else "", kind, name, W.tag(o), P)
+            assert all(r["tag"] == W.tag(o) for r in ranks)
+            held += W.hold_steps(where, ranks, ref, N, 2)
             logits = [GT.rows(ranks, lambda r, s=s: r["logits"][s], N) for s in range(2)]
-            if o["dropout"] > 0:
+            if o["dropout"] > 0 or o.get("attn", 0.0) > 0:
                 assert not np.array_equal(logits[0], logits[1]), where + ": the second step drew the first step's masks"
             else:
                 assert np.array_equal(logits[0], logits[1]), where
@@ -257,5 +319,93 @@ def gat_group(gat_datasets, dirname, name, task, gpu):
 
     held, pairs, worst = _logged(hold)
     assert held > 0
-    _report("gat", name, task, gpu, held, pairs, worst, t0)
+    _report(kind, name, task, gpu, held, pairs, worst, t0)
+    return held
+
+
+def gat_group(gat_datasets, dirname, name, task, gpu):
+    """GT.grad_worker on the eight GAT configurations under the vector ``name``, held exactly as
+    test_gat_tail.test_whole_model_gradients_of_every_option holds its grid: GT.hold_steps, the dropout / no-dropout comparison of the
+    two steps' logits, the eval logits."""
+    grid = gat_configs(task)
+    assert len(grid) == 8
+    return _attention_group("gat", grid, gat_datasets, dirname, name, task, gpu)
+
+
+def attention_group(kind, gat_datasets, dirname, name, task, gpu):
+    """The balanced device grid of attention dropout, GATv2 or dot-product attention (``attention_configs``) under the vector ``name``."""
+    return _attention_group(kind, attention_configs(kind, task), gat_datasets, dirname, name, task, gpu)
+
+
+def softmax_group(dataset, dirname, name, gpu):
+    """SM.rank_subset() -- the four of the balanced two- and three-rank tests, betas 1, 4, 0, 1 -- under the vector ``name``, held by
+    SM.check_models.  Before that: every rank, the one without rows included, aggregates through _aggregate_softmax and reports the
+    route its device decides (engine.AggregationEngine._max_structures: from the device and the provider's methods, not from the rows)."""
+    import time
+    t0 = time.time()
+    paths, data = dataset
+    P = VECTORS[name][0]
+    configs = SM.rank_subset()
+    jobs = SM.make_jobs(configs)
+    res = SM.spawn_model(P, with_vector(paths, name, data, dirname, "softmax"), gpu, SM.strip(jobs))
+    assert all(len(r) == len(configs) for r in res)
+    for j in range(len(configs)):
+        check_vector(name, [r[j]["own"] for r in res], data)
+    check_empty_rank(name, res, SM.CLASSES, SM.EPOCHS, "softmax")
+    for a in (a for r in res for a in r):
+        assert a["kinds"] == ["method:_aggregate_softmax"], ("softmax", name, a["tag"], a["kinds"])
+        assert a["composed"] == (not gpu), ("softmax", name, a["tag"], a["composed"])
+        assert not gpu or a["hip"] == "HipKernels", ("softmax", name, a["hip"])
+    held, pairs, worst = _logged(lambda: SM.check_models(data, configs, jobs, res, "/degenerate%s/%s" % ("-gpu" if gpu else "", name)))
+    assert held > 0
+    _report("softmax", name, "single", gpu, held, pairs, worst, t0)
+    return held
+
+
+def gpr_group(dataset, dirname, name, gpu):
+    """GP.model_configs() under the vector ``name``, held by GP.check_models (gamma's reduced gradient on every rank included).  Before
+    that, on dgamma as gpr_backward returned it: K + 1 fp32 values per step, exact zeros on a rank without rows; gamma's gradient after
+    the all-reduce is the ranks' dgamma ADDED -- the same bits on every rank, and the bits of the fp32 sum of the recorded parts: under
+    each of these vectors at most two parts are not exact zeros, so the sum has one rounding whatever the order."""
+    import time
+    from conftest import held_to_fixture
+    t0 = time.time()
+    paths, data = dataset
+    P, who = VECTORS[name]
+    configs = GP.model_configs()
+    res = GP.spawn_model(P, with_vector(paths, name, data, dirname, "gpr"), gpu, configs, data)
+    assert all(len(r) == len(configs) for r in res)
+    for j, c in enumerate(configs):
+        ranks = [r[j] for r in res]
+        check_vector(name, [r["own"] for r in ranks], data)
+        for s in range(GP.EPOCHS):
+            parts = [r["dgamma"][s] for r in ranks]
+            assert all(len(r["dgamma"]) == GP.EPOCHS for r in ranks), ("gpr", name, [len(r["dgamma"]) for r in ranks])
+            assert all(d.dtype == np.float32 and d.shape == (c["K"] + 1,) for d in parts), ("gpr", name, [d.shape for d in parts])
+            if name in ("E2", "E3"):
+                assert parts[who].tobytes() == np.zeros(c["K"] + 1, np.float32).tobytes(), ("gpr", name, GP.tag(c), s, parts[who])
+            assert sum(bool(d.any()) for d in parts) <= 2, ("gpr", name, parts)
+            total = parts[0].copy()
+            for d in parts[1:]:
+                total = total + d
+            for i, r in enumerate(ranks):
+                got = r["grads"][s][GP.GAMMA]
+                assert GP.bits(got).tobytes() == GP.bits(total).tobytes(), ("gpr", name, GP.tag(c), "step", s, "rank", i, got, total)
+        assert not gpu or all(r["hip"] == "HipKernels" for r in ranks), ("gpr", name)
+    check_empty_rank(name, res, GP.CLASSES, GP.EPOCHS, "gpr")
+
+    def hold():
+        case = "/degenerate%s/%s" % ("-gpu" if gpu else "", name)
+        held = GP.check_models(data, configs, res, case)
+        for j, c in enumerate(configs):
+            if c["dropout"] == 0.0:            # without dropout the eval pass is the training pass: the double model's logits of step 0
+                rec = GP.reference(data, c)["steps"][0]
+                held_to_fixture("gpr%s/%s/P%d" % (case, GP.tag(c), P), "eval logits", GP.rows([r[j] for r in res], lambda r: r["eval_logits"], N),
+                                rec["twin"]["logits"].numpy(), rec["m64"]["logits"].numpy())
+                held += 1
+        return held
+
+    held, pairs, worst = _logged(hold)
+    assert held > 0
+    _report("gpr", name, "single", gpu, held, pairs, worst, t0)
     return held

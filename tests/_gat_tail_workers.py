@@ -159,17 +159,28 @@ def model64(data, params, o, step, training=True, dtype=torch.float64):
             keep = D.keep_mask(o.get("dropout_seed", DROPOUT_SEED), step, l, np.arange(n), fout, thr)
             t = torch.where(keep, t * scale, torch.zeros((), dtype=dtype))
         h = t
-    train = torch.from_numpy(data["split"] == 1)
-    if o["task"] == "multilabel":
-        y = torch.from_numpy(data["labels"] == 1)[train].to(dtype)
-        loss = F.binary_cross_entropy_with_logits(logits[train], y, reduction="sum") / (int(train.sum()) * logits.shape[1])
-    else:
-        loss = F.cross_entropy(logits[train], torch.from_numpy(data["labels"])[train])
+    loss = train_loss(logits, data, o)
     grads = {}
     if training:
         names = list(p)
         grads = dict(zip(names, (g.detach() for g in torch.autograd.grad(loss, [p[k] for k in names]))))
     return loss.detach(), logits.detach(), grads
+
+
+def train_loss(logits, data, o):
+    """The loss of the train rows for the task of ``o``: cross entropy, or the mean binary cross entropy over the rows' elements."""
+    train = torch.from_numpy(data["split"] == 1)
+    if o["task"] == "multilabel":
+        y = torch.from_numpy(data["labels"] == 1)[train].to(logits.dtype)
+        return F.binary_cross_entropy_with_logits(logits[train], y, reduction="sum") / (int(train.sum()) * logits.shape[1])
+    return F.cross_entropy(logits[train], torch.from_numpy(data["labels"])[train])
+
+
+def task_pieces(M, o):
+    """(the loader, the masked loss) of PGAT for the task of ``o``."""
+    if o["task"] == "multilabel":
+        return M._nodedata.load_multilabel, M.masked_bce_loss
+    return M._nodedata.load, M.masked_loss
 
 
 def accuracy(logits, data):
@@ -243,8 +254,7 @@ def grad_worker(rank, P, port, paths, gpu, q, jobs=(), n=None, steps=2):
     results = []
     for job in jobs:
         o = job["opts"]
-        multilabel = o["task"] == "multilabel"
-        load = M._nodedata.load_multilabel if multilabel else M._nodedata.load
+        load, masked = task_pieces(M, o)
         data = load(paths[o["task"]]["features"], paths[o["task"]]["labels"], paths[o["task"]]["split"], eng.part.owned, n, device=M.device)
         state = D.DropoutState(DROPOUT_SEED, M.device) if o["dropout"] > 0 else None
         widths = [data.fin] + [o["hidden"]] * (o["nlayers"] - 1)
@@ -262,7 +272,7 @@ def grad_worker(rank, P, port, paths, gpu, q, jobs=(), n=None, steps=2):
             model.train()
             model.zero_grad()
             logits = model(data.features)
-            loss, _ = (M.masked_bce_loss if multilabel else M.masked_loss)(logits, data.labels, data.split, data.counts[1])
+            loss, _ = masked(logits, data.labels, data.split, data.counts[1])
             loss.backward()
             M.sum_gradients(model)
             rec["loss"].append(float(loss.detach().double().cpu()))

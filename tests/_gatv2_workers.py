@@ -194,8 +194,7 @@ def model64(data, params, o, step, training=True, dtype=torch.float64):
             keep = D.keep_mask(o.get("dropout_seed", GT.DROPOUT_SEED), step, l, np.arange(n), fout, thr)
             t = torch.where(keep, t * scale, torch.zeros((), dtype=dtype))
         h = t
-    train = torch.from_numpy(data["split"] == 1)
-    loss = F.cross_entropy(logits[train], torch.from_numpy(data["labels"])[train])
+    loss = GT.train_loss(logits, data, o)
     grads = {}
     if training:
         names = list(p)
@@ -281,7 +280,8 @@ def grad_worker(rank, P, port, paths, gpu, q, jobs=(), n=None, steps=2, provider
     for job in jobs:
         o = job["opts"]
         t = paths[o["task"]]
-        data = M._nodedata.load(t["features"], t["labels"], t["split"], eng.part.owned, n, device=M.device)
+        load, masked = GT.task_pieces(M, o)
+        data = load(t["features"], t["labels"], t["split"], eng.part.owned, n, device=M.device)
         state = D.DropoutState(GT.DROPOUT_SEED, M.device) if o["dropout"] > 0 else None
         v2 = {"attention": "v2", "share_weights": o["share"]}
         widths = [data.fin] + [o["hidden"]] * (o["nlayers"] - 1)
@@ -299,7 +299,7 @@ def grad_worker(rank, P, port, paths, gpu, q, jobs=(), n=None, steps=2, provider
             model.train()
             model.zero_grad()
             logits = model(data.features)
-            loss, _ = M.masked_loss(logits, data.labels, data.split, data.counts[1])
+            loss, _ = masked(logits, data.labels, data.split, data.counts[1])
             loss.backward()
             M.sum_gradients(model)
             rec["loss"].append(float(loss.detach().double().cpu()))

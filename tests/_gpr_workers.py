@@ -338,15 +338,24 @@ def model_worker(rank, P, port, paths, gpu, q, jobs=()):
         cur["loss"].append(float(out[0].detach().double().cpu()))
         return out
 
+    E = pkg("engine")
+    gpr_backward = E.AggregationEngine.gpr_backward
+
+    def recorded(self, *a, **kw):              # dgamma as the engine returned it: this rank's partial sum, before the ranks' sum
+        out = gpr_backward(self, *a, **kw)
+        cur["dgamma"].append(out[1].detach().cpu().numpy().copy())
+        return out
+
     M.initiliaze_parameters = initialise
     torch.optim.Adam.step = step
     M.masked_loss = with_loss
+    E.AggregationEngine.gpr_backward = recorded
     results = []
 
     def fn(r, size, nlayers, nfeatures, path_A, path_partvec, backend, *rest, **_):
         for job in jobs:
             c = job["config"]
-            cur.update(job=job, grads=[], logits=[], loss=[])
+            cur.update(job=job, grads=[], logits=[], loss=[], dgamma=[])
             torch.manual_seed(job["seed"])
             kw = dict(features=paths["features"], labels=paths["labels"], split=paths["split"], hidden=c["hidden"], epochs=EPOCHS, lr=0.0,
                       optimizer="torch", gpr=c["K"], gpr_alpha=c["alpha"])
@@ -357,11 +366,11 @@ def model_worker(rank, P, port, paths, gpu, q, jobs=()):
             if c["dropout"] > 0.0:
                 kw.update(dropout=c["dropout"], dropout_seed=DROPOUT_SEED)
             with redirect_stdout(io.StringIO()):
-                M.run(r, size, NLAYERS, c["hidden"], path_A, path_partvec, "gloo", normalize="sym", **kw)
+                model = M.run(r, size, NLAYERS, c["hidden"], path_A, path_partvec, "gloo", normalize="sym", **kw)
             eng = M._engine_current
             results.append(dict(tag=tag(c), names=cur["names"], modules=cur["modules"], grads=cur["grads"], logits=cur["logits"],
                                 loss=cur["loss"], own=eng.part.owned.cpu().numpy(), hip=type(eng.k).__name__, drawn=cur["drawn"],
-                                stats=dict(eng.stats)))
+                                stats=dict(eng.stats), dgamma=cur["dgamma"], eval_logits=GG.eval_logits(M, model, paths)))
 
     M.init_process(rank, P, fn, NLAYERS, HIDDEN, paths["A"], paths["pv%d" % P], "gloo", "sym")
     q.put({"rank": rank, "results": results})

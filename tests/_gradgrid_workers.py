@@ -308,6 +308,15 @@ def pick_seed(data, task, c):
 
 # ---- the workers ------------------------------------------------------------------------------------------------------------------------
 
+def eval_logits(M, model, paths, task=None):
+    """This rank's rows of the logits of ``model`` in eval mode, on the features of ``paths``, after a run() on the current engine."""
+    load = M._nodedata.load_multilabel if task == "multilabel" else M._nodedata.load
+    data = load(paths["features"], paths["labels"], paths["split"], M._engine_current.part.owned, N, device=M.device)
+    model.eval()
+    with torch.no_grad():
+        return model(data.features).cpu().numpy()
+
+
 def run_worker(rank, P, port, paths, gpu, q, task=None, jobs=()):
     """Rank `rank` of `P` over gloo (gpu false: the checker-backed kernels on the CPU; true: the real provider): inside ONE process
     group, PGCN.run(epochs=2, lr=0.0, optimizer="torch", normalize="sym", nlayers=4, ...) once per job and lane.  A job:
@@ -357,7 +366,6 @@ def run_worker(rank, P, port, paths, gpu, q, task=None, jobs=()):
     M.initiliaze_parameters = initialise
     torch.optim.Adam.step = step
     M.masked_loss, M.masked_bce_loss = with_loss(M.masked_loss), with_loss(M.masked_bce_loss)
-    load = M._nodedata.load_multilabel if task == "multilabel" else M._nodedata.load
     results = []
 
     def fn(r, size, nlayers, nfeatures, path_A, path_partvec, backend, **_):
@@ -380,10 +388,7 @@ def run_worker(rank, P, port, paths, gpu, q, task=None, jobs=()):
                         kw.update(dropout=c["dropout"], dropout_seed=DROPOUT_SEED)
                     with redirect_stdout(io.StringIO()):
                         model = M.run(r, size, NLAYERS, c["hidden"], path_A, path_partvec, "gloo", normalize="sym", **kw)
-                    data = load(paths["features"], paths["labels"], paths["split"], M._engine_current.part.owned, N, device=M.device)
-                    model.eval()
-                    with torch.no_grad():
-                        ev = model(data.features).cpu().numpy()
+                    ev = eval_logits(M, model, paths, task)
                     results.append(dict(tag=tag(c), lane=lane, init=cur["init"], drawn=cur["drawn"], grads=cur["grads"], logits=cur["logits"], loss=cur["loss"],
                                         eval_logits=ev, buffers={k: v.detach().cpu().numpy().copy() for k, v in model.named_buffers()},
                                         history=model.history, own=M._engine_current.part.owned.cpu().numpy(),

@@ -6,7 +6,14 @@ after the all-reduce on EVERY rank, the batch-norm buffers and the eval logits, 
 twin as the fixture -- no new tolerance, no element excused.  Here the wiring is held: zero-row tensors through the autograd nodes,
 the masked losses' global divisor, batch norm's column sums from a rank without rows, empty exchange rounds;
 tests/test_degenerate_gpu.py runs the same groups on the kernels (14, two of them as two worker groups each:
-_degenerate_workers.newer_cases)."""
+_degenerate_workers.newer_cases).
+
+The options merged since -- softmax aggregation, GPR-GNN, attention dropout, GATv2 and dot-product attention -- run under every vector
+too (_degenerate_workers.OPTION_GROUPS: 20 groups), through their own balanced runners and references; the three attention options on
+the numpy stand-ins of their kernels, so that the engine's kernel path is walked here: a row structure without rows or entries that
+still takes part in the exchange of the other end's rows, one owned row whose every neighbour is a halo row, masks drawn from the
+global ids of such a row, the LSE merge of a row that receives every candidate from its peer, dgamma of a rank without rows."""
+import numpy as np
 import pytest
 import torch
 
@@ -25,11 +32,21 @@ def gat_datasets(tmp_path_factory):
 
 
 @pytest.fixture(scope="module")
+def softmax_dataset(tmp_path_factory):
+    return W.SM.make_dataset(str(tmp_path_factory.mktemp("degenerate_softmax")))
+
+
+@pytest.fixture(scope="module")
+def gpr_dataset(tmp_path_factory):
+    return W.GP.make_dataset(str(tmp_path_factory.mktemp("degenerate_gpr")))
+
+
+@pytest.fixture(scope="module")
 def vectors(tmp_path_factory):
     return str(tmp_path_factory.mktemp("degenerate_vectors"))
 
 
-def test_the_lists_and_the_vectors(datasets):
+def test_the_lists_and_the_vectors(datasets, gat_datasets, softmax_dataset, gpr_dataset):
     assert len(W.cases("pgcn")) + len(W.cases("newer")) + len(W.cases("gat")) == 14
     assert len(W.newer_cases()) == len(W.cases("newer")) + 2 and {v for v, _, _ in W.newer_cases()} == set(W.VECTORS)
     assert W.newer_configs(0) + W.newer_configs(1) == W.newer_configs()
@@ -42,6 +59,31 @@ def test_the_lists_and_the_vectors(datasets):
         for name, (P, who) in W.VECTORS.items():
             pv = W.part_vector(name, data)
             W.check_vector(name, [(pv == r).nonzero()[0] for r in range(P)], data)
+    # the options merged since: five options, each under every vector -- 20 groups -- on the data sets of their own workers
+    assert set(W.OPTION_GROUPS) == {"softmax", "gpr", "attndrop", "gatv2", "gatdot"}
+    assert all([v for v, _ in W.option_cases(kind)] == list(W.VECTORS) for kind in W.OPTION_GROUPS)
+    assert sum(len(W.option_cases(kind)) for kind in W.OPTION_GROUPS) == 20
+    assert all(W.OPTION_GROUPS[kind] == dict.fromkeys(W.VECTORS, "single") for kind in ("softmax", "gpr"))
+    assert all(W.OPTION_GROUPS[kind] == {"E2": "single", "E3": "multilabel", "S2": "multilabel", "O2": "single"}
+               for kind in ("attndrop", "gatv2", "gatdot"))
+    assert [W.SM.tag(c) for c in W.SM.rank_subset()] == ["none-h32-b1-l3", "none+drop-h32-b4-l2", "node+res-h32-b0-l3", "none+root+bias-h32-b1-l2"]
+    assert [c["K"] for c in W.GP.model_configs()] == [10, 3]
+    for kind, count in (("attndrop", 2), ("gatv2", 2), ("gatdot", 1)):
+        for task in W.GG.TASKS:
+            grid = W.attention_configs(kind, task)
+            assert len({W.ATTENTION[kind][0].tag(o) for o in grid}) == count and all(o["hidden"] == 64 and o["K"] == 2 and o["task"] == task for o in grid)
+    assert [o["share"] for o in W.attention_configs("gatv2", "single")] == [False, True]
+    for data in (softmax_dataset[1], gpr_dataset[1], gat_datasets[1]["single"], gat_datasets[1]["multilabel"]):
+        for name, (P, who) in W.VECTORS.items():
+            pv = W.part_vector(name, data)
+            W.check_vector(name, [(pv == r).nonzero()[0] for r in range(P)], data)
+    small = dict(softmax_dataset[1], split=np.ones(softmax_dataset[1]["split"].shape[0], np.uint8))
+    with pytest.raises(AssertionError, match="S2 needs 37 vertices in no set"):
+        W.part_vector("S2", small)
+    few = W.part_vector("E3", softmax_dataset[1])
+    few[:] = np.where(np.arange(few.size) < 600, 1, 2)
+    with pytest.raises(AssertionError, match="E3 needs 513 rows"):
+        W.check_vector("E3", [(few == r).nonzero()[0] for r in range(3)], softmax_dataset[1])
 
 
 def test_unpack_sign_mask_of_no_rows():
@@ -75,3 +117,28 @@ def test_newer_options(datasets, vectors, vector, task, half):
 @pytest.mark.parametrize("vector,task", W.cases("gat"))
 def test_gat_options(gat_datasets, vectors, vector, task):
     assert W.gat_group(gat_datasets, vectors, vector, task, False) > 8 * 2 * 2
+
+
+@pytest.mark.parametrize("vector,task", W.option_cases("softmax"))
+def test_softmax_aggregation(softmax_dataset, vectors, vector, task):
+    assert W.softmax_group(softmax_dataset, vectors, vector, False) > 4 * 2 * 2
+
+
+@pytest.mark.parametrize("vector,task", W.option_cases("gpr"))
+def test_gpr(gpr_dataset, vectors, vector, task):
+    assert W.gpr_group(gpr_dataset, vectors, vector, False) > 2 * 2 * 2
+
+
+@pytest.mark.parametrize("vector,task", W.option_cases("attndrop"))
+def test_attention_dropout(gat_datasets, vectors, vector, task):
+    assert W.attention_group("attndrop", gat_datasets, vectors, vector, task, False) > 2 * 2 * 2
+
+
+@pytest.mark.parametrize("vector,task", W.option_cases("gatv2"))
+def test_gatv2(gat_datasets, vectors, vector, task):
+    assert W.attention_group("gatv2", gat_datasets, vectors, vector, task, False) > 2 * 2 * 2
+
+
+@pytest.mark.parametrize("vector,task", W.option_cases("gatdot"))
+def test_dot_product_attention(gat_datasets, vectors, vector, task):
+    assert W.attention_group("gatdot", gat_datasets, vectors, vector, task, False) > 2 * 2
