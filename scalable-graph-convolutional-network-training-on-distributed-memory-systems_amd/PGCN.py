@@ -544,6 +544,26 @@ def bind_dense_library(path):
             L.pgcn_dropout_keep_words_u32.restype = ctypes.c_int
             L.pgcn_dropout_keep_words_u32.argtypes = [ptr, i64, i32, u64, ptr, u32, u32, ptr, ptr]
             L.pgcn_has_dropout = True
+    # the same three products for widths above 128 (include/pgcn_dense_wide.h): only a library that vouches for them
+    L.pgcn_has_dense_wide = False
+    if hasattr(L, "pgcn_dense_wide_abi_version"):
+        L.pgcn_dense_wide_abi_version.restype = ctypes.c_int
+        L.pgcn_dense_wide_abi_version.argtypes = []
+        if L.pgcn_dense_wide_abi_version() == 1:
+            u32, u64, f32 = ctypes.c_uint32, ctypes.c_uint64, ctypes.c_float
+            L.pgcn_dense_wide_last_error.restype = ctypes.c_char_p
+            L.pgcn_dense_wide_last_error.argtypes = []
+            L.pgcn_wide_image_ws_bytes.restype = ctypes.c_int64
+            L.pgcn_wide_image_ws_bytes.argtypes = [i32, i32]
+            L.pgcn_wide_linear_relu_f32.restype = ctypes.c_int
+            L.pgcn_wide_linear_relu_f32.argtypes = [ptr, i64, i64, i32, ptr, i64, i32, ptr, i64, i32, ptr, ptr, u64, ptr, u32, u32, ptr, i64, ptr]
+            L.pgcn_wide_grad_input_f32.restype = ctypes.c_int
+            L.pgcn_wide_grad_input_f32.argtypes = [ptr, i64, ptr, f32, ptr, i64, i64, i32, ptr, i64, i32, ptr, i64, ptr, i64, ptr]
+            L.pgcn_wide_weight_grad_ws_elems.restype = ctypes.c_int64
+            L.pgcn_wide_weight_grad_ws_elems.argtypes = [i64, i32, i32]
+            L.pgcn_wide_weight_grad_f32.restype = ctypes.c_int
+            L.pgcn_wide_weight_grad_f32.argtypes = [ptr, i64, ptr, f32, ptr, i64, i64, i32, i32, ptr, i64, ptr, i64, ptr]
+            L.pgcn_has_dense_wide = True
     return L
 
 
@@ -779,6 +799,136 @@ def weight_grad_fused(gm, x):
     return weight_grad_call(_dense_lib(), gm, x, _dense_stream(gm))
 
 
+# ---- the same products for widths above 128 (gemm/pgcn_dense_wide.hip, include/pgcn_dense_wide.h) ----------------------------------
+def _wide_shape_ok(fin, fout):
+    """The shapes the wide kernels own: multiples of 4 in 4 .. 1024 with one width above 128 (the library answers -2 otherwise; asked
+    here first so that a refused shape costs no work-space)."""
+    return fin % 4 == 0 and fout % 4 == 0 and 4 <= fin <= 1024 and 4 <= fout <= 1024 and max(fin, fout) > 128
+
+
+def _wide_mask_ok(mask, g):
+    return mask is None or (mask.shape == (g.shape[0], mask_words(g.shape[1])) and mask.dtype is torch.int32 and
+                            mask.is_contiguous() and mask.device == g.device)
+
+
+def _wide_image_ws(L, K, N, device):
+    # (from PyTorch's caching allocator at each call: safe under graph capture, freed in stream order, no global dictionary)
+    return torch.empty(int(L.pgcn_wide_image_ws_bytes(K, N)), dtype=torch.uint8, device=device)
+
+
+def wide_linear_relu_call(L, x, weight, relu, want_mask, stream, dropout=None):
+    """[dropout] [relu](x . weight^T) through pgcn_wide_linear_relu_f32 of `L` on `stream`, or None when the library has no wide entry
+    points / refuses the operands (-2).  dropout: None or (row_ids, seed, step, layer, thr) as dropout_linear_relu_call takes them.
+    Returns y, or (y, mask words) with want_mask."""
+    if not getattr(L, "pgcn_has_dense_wide", False) or x.dim() != 2 or weight.dim() != 2 or x.shape[1] != weight.shape[1] or \
+            x.stride(1) != 1 or weight.stride(1) != 1 or not (x.dtype is weight.dtype is torch.float32) or \
+            not _wide_shape_ok(x.shape[1], weight.shape[0]):
+        return None
+    row_ids = seed = step = None
+    layer = thr = 0
+    if dropout is not None:
+        row_ids, seed, step, layer, thr = dropout
+        if not _row_ids_ok(row_ids, x.shape[0]) or step.dtype is not torch.int64 or step.numel() != 1:
+            return None
+    n, fin, fout = x.shape[0], x.shape[1], weight.shape[0]
+    y = torch.empty((n, fout), dtype=torch.float32, device=x.device)
+    mask = torch.empty((n, mask_words(fout)), dtype=torch.int32, device=x.device) if want_mask else None
+    ws = _wide_image_ws(L, fin, fout, x.device)
+    rc = L.pgcn_wide_linear_relu_f32(x.data_ptr(), x.stride(0), n, fin, weight.data_ptr(), weight.stride(0), fout, y.data_ptr(),
+                                     y.stride(0), 1 if relu else 0, mask.data_ptr() if want_mask else None,
+                                     row_ids.data_ptr() if row_ids is not None else None, int(seed or 0),
+                                     step.data_ptr() if step is not None else None, int(layer), int(thr), ws.data_ptr(), ws.numel(), stream)
+    if rc == -2:
+        return None
+    if rc != 0:
+        raise RuntimeError("pgcn_wide_linear_relu_f32: %s" % L.pgcn_dense_wide_last_error().decode())
+    return (y, mask) if want_mask else y
+
+
+def wide_grad_input_call(L, g, mask, scale, weight, want_gm, stream):
+    """(gm, gx) = (mask ? g * scale : 0 -- None unless want_gm --, gm . weight) through pgcn_wide_grad_input_f32 of `L`, or None."""
+    if not getattr(L, "pgcn_has_dense_wide", False) or g.dim() != 2 or weight.dim() != 2 or g.shape[1] != weight.shape[0] or \
+            g.stride(1) != 1 or weight.stride(1) != 1 or not (g.dtype is weight.dtype is torch.float32) or \
+            not _wide_shape_ok(weight.shape[1], weight.shape[0]) or not _wide_mask_ok(mask, g):
+        return None
+    n, fout, fin = g.shape[0], g.shape[1], weight.shape[1]
+    gm = torch.empty((n, fout), dtype=torch.float32, device=g.device) if want_gm else None
+    gx = torch.empty((n, fin), dtype=torch.float32, device=g.device)
+    ws = _wide_image_ws(L, fout, fin, g.device)
+    rc = L.pgcn_wide_grad_input_f32(g.data_ptr(), g.stride(0), mask.data_ptr() if mask is not None else None, float(scale),
+                                    gm.data_ptr() if want_gm else None, gm.stride(0) if want_gm else 0, n, fout, weight.data_ptr(),
+                                    weight.stride(0), fin, gx.data_ptr(), gx.stride(0), ws.data_ptr(), ws.numel(), stream)
+    if rc == -2:
+        return None
+    if rc != 0:
+        raise RuntimeError("pgcn_wide_grad_input_f32: %s" % L.pgcn_dense_wide_last_error().decode())
+    return gm, gx
+
+
+def wide_weight_grad_masked_call(L, g, mask, scale, x, stream):
+    """(mask ? g * scale : 0)^T . x (fout x fin) through pgcn_wide_weight_grad_f32 of `L`, that matrix formed in registers, or None."""
+    if not getattr(L, "pgcn_has_dense_wide", False) or g.dim() != 2 or x.dim() != 2 or g.shape[0] != x.shape[0] or \
+            g.stride(1) != 1 or x.stride(1) != 1 or not (g.dtype is x.dtype is torch.float32) or \
+            not _wide_shape_ok(x.shape[1], g.shape[1]) or not _wide_mask_ok(mask, g):
+        return None
+    n, fout, fin = g.shape[0], g.shape[1], x.shape[1]
+    if n == 0:                                   # (an empty sum: the entry point launches nothing)
+        return torch.zeros((fout, fin), dtype=torch.float32, device=g.device)
+    ws = torch.empty(int(L.pgcn_wide_weight_grad_ws_elems(n, fout, fin)), dtype=torch.float32, device=g.device)
+    dw = torch.empty((fout, fin), dtype=torch.float32, device=g.device)
+    rc = L.pgcn_wide_weight_grad_f32(g.data_ptr(), g.stride(0), mask.data_ptr() if mask is not None else None, float(scale), x.data_ptr(),
+                                     x.stride(0), n, fout, fin, dw.data_ptr(), dw.stride(0), ws.data_ptr(), ws.numel(), stream)
+    if rc == -2:
+        return None
+    if rc != 0:
+        raise RuntimeError("pgcn_wide_weight_grad_f32: %s" % L.pgcn_dense_wide_last_error().decode())
+    return dw
+
+
+def wide_linear_relu_fused(x, weight, relu, want_mask, dropout=None):
+    """[dropout] [relu](x . weight^T) for widths above 128 by the package's K-blocked matrix-core kernel on the current stream, or None
+    (CPU tensors, refused operands): the caller runs the library product."""
+    if not _dense_operand_ok(x, weight):
+        return None
+    return wide_linear_relu_call(_dense_lib(), x, weight, relu, want_mask, _dense_stream(x), dropout)
+
+
+def wide_grad_input_fused(g, mask, scale, weight, want_gm):
+    """(mask ? g * scale : 0, that . weight) for widths above 128 in one pass, or None."""
+    if not _dense_operand_ok(g, weight):
+        return None
+    return wide_grad_input_call(_dense_lib(), g, mask, scale, weight, want_gm, _dense_stream(g))
+
+
+def wide_weight_grad_masked_fused(g, mask, scale, x):
+    """(mask ? g * scale : 0)^T . x for widths above 128 on the current stream, or None."""
+    if not _dense_operand_ok(g, x):
+        return None
+    return wide_weight_grad_masked_call(_dense_lib(), g, mask, scale, x, _dense_stream(g))
+
+
+def _dense_wide_on():
+    from .tuning import T as _T
+    return int(_T.dense_wide) != 0
+
+
+def _wide_backward(g, mask, scale, x, weight, need_gx, need_gw):
+    """The backward of a layer whose forward took the wide kernel: (gx, gw), each None where not asked for -- or None when a kernel
+    refuses (the caller then takes the library route from the mask).  Gm is never written; the weight gradient runs on the current
+    stream; a first layer (need_gx false) launches no input-gradient kernel."""
+    gx = gw = None
+    if need_gx:
+        both = wide_grad_input_fused(g, mask, scale, weight, False)
+        if both is None:
+            return None
+        gx = both[1]
+    if need_gw:
+        gw = wide_weight_grad_masked_fused(g, mask, scale, x)
+        if gw is None:
+            return None
+    return gx, gw
+
+
 def _dense_fused_level():
     from .tuning import T as _T
     return int(_T.dense_fused)
@@ -857,7 +1007,8 @@ class _LinearReluNoBias(torch.autograd.Function):
     """relu(x . W^T) as one autograd node (PGCN.py:146-147).  With the package's own kernels (tuning.dense_fused; default 3) the
     forward is ONE kernel that also leaves the sign mask of its output (1 bit per element), the backward two: the mask applied to
     the gradient + the input gradient, and the weight gradient.  Levels: 0 library GEMMs + clamp / threshold passes; 1 forward
-    only; 2 + input gradient; 3 + weight gradient.  Same arithmetic class, relu'(0) = 0."""
+    only; 2 + input gradient; 3 + weight gradient.  Same arithmetic class, relu'(0) = 0.  Widths above 128 (level 3,
+    tuning.dense_wide): the K-blocked kernels of gemm/pgcn_dense_wide.hip, asked after the narrow ones and before the library."""
 
     @staticmethod
     def forward(ctx, x, weight, eng=None):
@@ -866,6 +1017,10 @@ class _LinearReluNoBias(torch.autograd.Function):
         level = _dense_fused_level()
         out = linear_relu_fused(x, weight, True, want_mask=level >= 2) if level >= 1 else None   # (None: not CUDA / not its shapes)
         mask = None
+        ctx.wide = False
+        if out is None and level >= 3 and _dense_wide_on():   # (widths above 128: the K-blocked kernels, all three products or none)
+            out = wide_linear_relu_fused(x, weight, True, True)
+            ctx.wide = out is not None
         if out is None:
             y = mm_nt(x, weight).clamp_min_(0.0)
         elif level >= 2:
@@ -885,6 +1040,10 @@ class _LinearReluNoBias(torch.autograd.Function):
         gx = gw = None
         both = None
         level = _dense_fused_level()
+        if ctx.has_mask and ctx.wide and _dense_wide_on():
+            out = _wide_backward(g.contiguous(), ym, 1.0, x, weight, ctx.needs_input_grad[0], ctx.needs_input_grad[1])
+            if out is not None:
+                return out[0], out[1], None
         if ctx.has_mask and level >= 2:
             g = g.contiguous()
             # (the weight gradient masks g in its registers: Gm, whose only reader it was, is not written)
@@ -923,7 +1082,8 @@ class _LinearReluDropoutNoBias(torch.autograd.Function):
     """dropout(relu(x . W^T)) as one autograd node: y = keep ? relu(x . W^T) / (1 - p) : 0 with keep a pure function of
     (seed, step, layer, GLOBAL row id, column) (dropout.py, gemm/pgcn_dropout.h).  Fused (tuning.dropout_fused, tuning.dense_fused >= 2):
     ONE forward kernel that leaves y and the words sign AND keep, the backward reads nothing but those words.  Otherwise (CPU
-    tensors, widths above 128, unaligned rows, a library without the entry points): the library product + clamp + the keep words
+    tensors, widths the narrow and the wide kernels (tuning.dense_wide) both refuse, unaligned rows, a library without the entry
+    points): the library product + clamp + the keep words
     (kernel on the GPU, dropout.keep_mask on the CPU) + torch.where -- the same results up to the product's rounding."""
 
     @staticmethod
@@ -934,6 +1094,10 @@ class _LinearReluDropoutNoBias(torch.autograd.Function):
         out = None
         if int(_T.dropout_fused) and level >= 2:
             out = dropout_linear_relu_fused(x, weight, row_ids, state.seed, state.step, layer, thr)
+        ctx.wide = False
+        if out is None and int(_T.dropout_fused) and level >= 3 and _dense_wide_on():
+            out = wide_linear_relu_fused(x, weight, True, True, dropout=(row_ids, state.seed, state.step, layer, thr))
+            ctx.wide = out is not None
         if out is not None:
             y, mask = out
         else:
@@ -959,6 +1123,10 @@ class _LinearReluDropoutNoBias(torch.autograd.Function):
         gx = gw = None
         level = _dense_fused_level()
         both = None
+        if ctx.wide and _dense_wide_on():
+            out = _wide_backward(g.contiguous(), mask, ctx.scale, x, weight, ctx.needs_input_grad[0], ctx.needs_input_grad[1])
+            if out is not None:
+                return out[0], out[1], None, None, None, None, None, None
         if int(_T.dropout_fused) and level >= 2:
             g = g.contiguous()
             masked = ctx.needs_input_grad[1] and _wgrad_masked_route(g, mask, x, level)     # (as _LinearReluNoBias: Gm is not written)

@@ -3,7 +3,8 @@
 #   pgcn_gemm.cpp   host code, rocBLAS calls by solution index;
 #   pgcn_dense.hip  relu(X.W^T) and its input gradient on the bf16 matrix cores (gfx950; index arithmetic: pgcn_dense_tile.h;
 #                   dropout fused into both: pgcn_dropout.h);
-#   pgcn_wgrad.hip  the weight gradient Gm^T.X on the same cores.
+#   pgcn_wgrad.hip  the weight gradient Gm^T.X on the same cores;
+#   pgcn_dense_wide.hip  the same three products for widths above 128, up to 1024 (K- and column-blocked; include/pgcn_dense_wide.h).
 # Links librocblas.so.5 / libamdhip64 by SONAME: inside a PyTorch process the loader re-uses the copies PyTorch mapped.
 set -euo pipefail
 HERE="$(cd "$(dirname "${BASH_SOURCE[0]}")" && pwd)"
@@ -12,11 +13,13 @@ ROCM="${ROCM_PATH:-/opt/rocm}"
 HIPCC="${HIPCC:-$ROCM/bin/hipcc}"
 # (-fno-slp-vectorize: packed fp32 VALU beside MFMAs costs the matrix pipe ~12 cycles per instruction -- the bf16 split stays scalar)
 # (a failed compile must not link against an object of an earlier build: the old ones go first, every compile is waited for by pid)
-rm -f "$OUT/pgcn_dense.o" "$OUT/pgcn_wgrad.o" "$OUT/pgcn_gemm.o"
+rm -f "$OUT/pgcn_dense.o" "$OUT/pgcn_wgrad.o" "$OUT/pgcn_dense_wide.o" "$OUT/pgcn_gemm.o"
 pids=()
 "$HIPCC" -O3 -std=c++17 -fPIC --offload-arch=gfx950 -fno-slp-vectorize -Wall -c "$HERE/pgcn_dense.hip" -o "$OUT/pgcn_dense.o" ${PGCN_EXTRA_FLAGS:-} & pids+=($!)
 "$HIPCC" -O3 -std=c++17 -fPIC --offload-arch=gfx950 -fno-slp-vectorize -Wall -c "$HERE/pgcn_wgrad.hip" -o "$OUT/pgcn_wgrad.o" ${PGCN_EXTRA_FLAGS:-} & pids+=($!)
+# (the new file also keeps the compiler from forming packed fp32 VALU of its own accord: -packed-fp32-ops)
+"$HIPCC" -O3 -std=c++17 -fPIC --offload-arch=gfx950 -fno-slp-vectorize -Wall -Wno-inline-asm -Xclang -target-feature -Xclang -packed-fp32-ops -c "$HERE/pgcn_dense_wide.hip" -o "$OUT/pgcn_dense_wide.o" ${PGCN_EXTRA_FLAGS:-} & pids+=($!)
 "$HIPCC" -O2 -std=c++17 -fPIC -Wall -I"$ROCM/include" -c "$HERE/pgcn_gemm.cpp" -o "$OUT/pgcn_gemm.o" & pids+=($!)
 for p in "${pids[@]}"; do wait "$p"; done
-"$HIPCC" -shared -fPIC "$OUT/pgcn_gemm.o" "$OUT/pgcn_dense.o" "$OUT/pgcn_wgrad.o" -o "$OUT/libpgcn_gemm.so" -L"$ROCM/lib" -lrocblas -lamdhip64 -lpthread
+"$HIPCC" -shared -fPIC "$OUT/pgcn_gemm.o" "$OUT/pgcn_dense.o" "$OUT/pgcn_wgrad.o" "$OUT/pgcn_dense_wide.o" -o "$OUT/libpgcn_gemm.so" -L"$ROCM/lib" -lrocblas -lamdhip64 -lpthread
 echo "built $OUT/libpgcn_gemm.so"

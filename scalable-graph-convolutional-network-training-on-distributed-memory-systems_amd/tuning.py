@@ -134,6 +134,12 @@ class Tuning:
                                      # + element-wise passes; 0 = always the unfused route (same masks, same results up to the product's rounding)
                                      # MI355X, n = 232 965, f = 128: forward 82 us fused against 63 plain and 856 unfused, input gradient 84 / 86 / 368
                                      # (profiles/dropout_dense_times.json, HISTORY.md section 14)
+    dense_wide: int = 1              # layers with a width above 128 (up to 1024, multiples of 4): the K- and column-blocked kernels of
+                                     # gemm/pgcn_dense_wide.hip for all three products (with dense_fused 3; dropout in the epilogue with
+                                     # dropout_fused) instead of library GEMM + clamp / keep-words / where passes + the 64-slab bmm; 0 = those
+                                     # layers take the library route, the behaviour of before, bit for bit.  DESIGN.md section 4,
+                                     # HISTORY.md section 40: every product at 256 x 256 and 512 x 256 beats the library route
+                                     # by more than the spread, 1.7x (forward) to 9x (forward + dropout); profiles/dense_wide_times.json
     # ---- GAT path -------------------------------------------------------------------------------------------
     gat_long_row: int = 1024         # rows above this get a 256-thread workgroup in the attention kernels
     gat_small_row: int = 192         # gather plan of the attention structures (r05): a partial row there is heads x d = 1 KB wide, twice the GCN
