@@ -409,6 +409,69 @@ int pgcn_aggsoftmax_backward_csr_plan_f32(const int64_t *rowptr, const int32_t *
                                           float *partial_ws, int64_t partial_ws_elems, int64_t nslots, uint32_t flags,
                                           pgcn_stream_t stream);
 
+/* ---- Principal Neighbourhood Aggregation (Corso et al., NeurIPS 2020; PyG's PNAConv; no counterpart in the reference): mean, max,
+ * min and standard deviation over the neighbourhood in ONE gather, their backward, and the degree scalers.  cand(i) = the stored
+ * columns of row i (stored values are ignored), d_i = |cand(i)| over ALL the structures that hold a piece of row i, x_j = B[j, c]:
+ *   MEAN[i, c] = (1 / d_i) sum_j x_j
+ *   MAX, AMAX    pgcn_aggmax_csr_plan_f32's definition and tie rule (the smallest GLOBAL id among the maxima, fp32 ==)
+ *   MIN, AMIN    the mirror image: (v, g) replaces (cur, a) when a < 0 || v < cur || (v == cur && g < a)
+ *   VAR[i, c]  = (1 / d_i) sum_j (x_j - MEAN[i, c])^2  (population variance),   STD = sqrt(VAR + 1e-5f)
+ *   d_i = 0: all four 0.0f, AMAX = AMIN = -1.          S[i, :] = [MEAN | MAX | MIN | STD]: n x 4 f, leading dimension lds >= 4 f
+ * MAX, MIN, AMAX and AMIN are the same bits under any plan, any cut of a row and any split over several calls; MEAN and STD depend on
+ * the order of the additions, as the sum does.  The variance is never formed as E[x^2] - E[x]^2: a group of candidates is the state
+ * (cnt, mean, M2 = sum (x - mean)^2); a task accumulates s1 = sum (x - K), s2 = sum (x - K)^2 around its first value K and closes with
+ * mean = K + s1 / cnt, M2 = max(s2 - s1 s1 / cnt, 0); groups merge by Chan's rule
+ *   dl = m_b - m_a,   mean = m_a + dl n_b / n,   M2 = M2_a + M2_b + dl^2 n_a n_b / n
+ * -- the pieces of a cut row in slot order, and, with PGCN_SPMM_ACCUMULATE, the row's current state with this call's result.  Equal
+ * values give M2 = 0 exactly.
+ *
+ * pgcn_aggpna_csr_plan_f32: pairs / tasks / seg / nslices / fix / nslots and the flags (PGCN_SPMM_ACCUMULATE, _XCD_SWIZZLE, _OFFSETS32,
+ * _FPASS64) as pgcn_aggmax_csr_plan_f32 takes them, the pairs of every task in ascending global id.  It leaves M2 in the fourth block of
+ * S; pgcn_aggpna_finish_f32 turns it into STD after the last structure.  cnt_prior[rows] (int32; read with PGCN_SPMM_ACCUMULATE only,
+ * NULL otherwise): the candidates ALREADY merged into every row's state -- one count per row, not per feature; this call's own count of
+ * a row is its stored length.  Without the flag the outputs are written, whatever they held.  ws: six planes of nslots x f words
+ * (mean, M2, max, min as floats, amax, amin as int32) followed by nslots int32 counts: ws_bytes >= nslots (24 f + 4).  Any f >= 1; a
+ * float4 / int4 body when f % 4 == 0 with 16-byte aligned operands and leading dimensions % 4 == 0, a guarded scalar body otherwise
+ * with the same bits for MAX, MIN, AMAX, AMIN.
+ *
+ * pgcn_aggpna_finish_f32 (row-band kernel, f <= 1024), deg[rows]: d_i as int32.
+ *   dS == NULL: S's fourth block M2 -> STD = d > 0 ? sqrtf(M2 / d + 1e-5f) : 0, in place; the other arguments are not read.
+ *   dS = [dMEAN | dMAX | dMIN | dSTD] (leading dimension ldds >= 4 f): S is read only; Q = dSTD / (d STD), P = dMEAN / d - Q MEAN (0
+ *   where d = 0) and the PANEL of the backward is written: row i holds six planes of fp = 4 ceil(f / 4) words each,
+ *   {P | Q | dMAX | dMIN | AMAX | AMIN} at panel[i * ldp + k fp] (the ids as their int32 bits), ldp >= 6 fp = 24 ceil(f / 4), ldp % 4
+ *   == 0, panel 16-byte aligned; features beyond f hold 0 and id -1.  The operands of one stored entry of the backward are one
+ *   contiguous region; it reads P, Q, AMAX, AMIN, and dMAX / dMIN only where an id matches.
+ *
+ * pgcn_aggpna_backward_csr_plan_f32: over the TRANSPOSED structure (col, rowgid, slot_row as pgcn_aggmax_backward_csr_plan_f32 takes
+ * them), X the rows of this structure:
+ *   D[r, c] = sum over the stored entries i of row r of ( P[i, c] + (AMAX[i, c] == rowgid[r] ? dMAX[i, c] : 0)
+ *             + (AMIN[i, c] == rowgid[r] ? dMIN[i, c] : 0) )  +  X[r, c] sum_i Q[i, c]
+ * -- gather form, entries in storage order, the X sum Q term applied per piece, the pieces of a cut row added in slot order
+ * (pgcn_spmm_fixup_f32): deterministic, no atomics.  D is written, never accumulated into.  PGCN_SPMM_OFFSETS32: every byte offset into
+ * the panel fits 32 bits.  partial_ws: nslots x f floats.
+ *
+ * pgcn_pna_scale_forward_f32 / _backward_f32 (row-band kernels, fout <= 1024): the identity, amplification and attenuation scalers on
+ * the product Y = [Y0 | Y1 | Y2] (n x 3 fout):  Z[i, c] = Y0[i, c] + a[i] Y1[i, c] + b[i] Y2[i, c] (two FMAs);  dY = [G | a G | b G].
+ *
+ * All five: PGCN_EINVAL without touching a device on null pointers, f < 1 or a leading dimension below its width; a structure
+ * (operand) without rows returns at once.  Inputs are finite by contract.  Vector stores only.                                  */
+int pgcn_aggpna_csr_plan_f32(const int64_t *rowptr, const int32_t *pairs, const int32_t *tasks, int64_t ntasks, const int64_t *seg,
+                             int32_t nslices, const int32_t *fix, int64_t nfix, const float *B, int64_t ldb, float *S, int64_t lds,
+                             int32_t *AMAX, int64_t ldx, int32_t *AMIN, int64_t ldn, const int32_t *cnt_prior, int32_t f, void *ws,
+                             int64_t ws_bytes, int64_t nslots, uint32_t flags, pgcn_stream_t stream);
+int pgcn_aggpna_finish_f32(float *S, int64_t lds, const int32_t *deg, int64_t nrows, int32_t f, const float *dS, int64_t ldds,
+                           const int32_t *AMAX, int64_t ldx, const int32_t *AMIN, int64_t ldn, float *panel, int64_t ldp,
+                           pgcn_stream_t stream);
+int pgcn_aggpna_backward_csr_plan_f32(const int64_t *rowptr, const int32_t *col, const int32_t *rowgid, const int32_t *slot_row,
+                                      const int32_t *tasks, int64_t ntasks, const int64_t *seg, int32_t nslices, const int32_t *fix,
+                                      int64_t nfix, const float *X, int64_t ldx, const float *panel, int64_t ldp, float *D, int64_t ldd,
+                                      int32_t f, float *partial_ws, int64_t partial_ws_elems, int64_t nslots, uint32_t flags,
+                                      pgcn_stream_t stream);
+int pgcn_pna_scale_forward_f32(const float *Y, int64_t ldy, const float *a, const float *b, float *Z, int64_t ldz, int64_t nrows,
+                               int32_t fout, pgcn_stream_t stream);
+int pgcn_pna_scale_backward_f32(const float *G, int64_t ldg, const float *a, const float *b, float *dY, int64_t ldy, int64_t nrows,
+                                int32_t fout, pgcn_stream_t stream);
+
 /* ---- DropEdge (Rong et al., ICLR 2020; no counterpart in the reference): the aggregation over a pattern whose entries are dropped
  * anew at every training step and renormalised.  csrc/pgcn_dropedge.h states the keep function:
  *   keep(gi, gj) = gi == gj || u(seed, step[0], min(gi, gj), max(gi, gj)) >= thr      (GLOBAL ids below 2^31; thr: dropout's threshold)

@@ -198,7 +198,9 @@ class PSpMM(torch.autograd.Function):
         return None, dH
 
 
-AGGRS = ("sum", "max")          # --aggr / run(aggr=...) / PGCN(aggr=...): the weighted sum A . H (the default) or the element-wise max
+ALL_AGGRS = ("sum", "max", "pna")   # what --aggr / run(aggr=...) / PGCN(aggr=...) take: the weighted sum A . H (the default), the
+                                    # element-wise max, or the four aggregators and three degree scalers of PNA
+AGGRS = ALL_AGGRS[:2]               # COMPATIBILITY ONLY: the tuple earlier releases exported; nothing in the package reads it
 
 
 class PAggMax(torch.autograd.Function):
@@ -221,6 +223,49 @@ class PAggMax(torch.autograd.Function):
         if join is not None:
             join()
         return None, dH
+
+
+class PAggPna(torch.autograd.Function):
+    """The four aggregators of Principal Neighbourhood Aggregation (Corso et al., 2020) in place of ``PSpMM``'s weighted sum
+    (csrc/pgcn_aggpna.hip; the stored values are ignored, under ``normalize="sym"`` a vertex is its own neighbour): S = [MEAN | MAX | MIN |
+    STD] of the neighbourhood, n x 4 f, from ONE gather -- forward ``A.forward_pna`` with the halo exchange, backward ``A.backward_pna``.
+    Saved: S (the output the next node keeps anyway), AMAX, AMIN, H and the received halo rows.  The constant feature matrix of the first
+    layer needs no gradient: nothing is saved, nothing is aggregated."""
+
+    @staticmethod
+    def forward(ctx, A, H):
+        ctx.A = A
+        S, AMAX, AMIN, halo = A.forward_pna(H)
+        if ctx.needs_input_grad[1]:
+            ctx.has_halo = halo is not None
+            ctx.save_for_backward(S, AMAX, AMIN, H, *([halo] if halo is not None else []))
+        return S
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        dH = None
+        if ctx.needs_input_grad[1]:
+            S, AMAX, AMIN, H = ctx.saved_tensors[:4]
+            dH = ctx.A.backward_pna(grad_output, H, ctx.saved_tensors[4] if ctx.has_halo else None, S, AMAX, AMIN)
+        join = getattr(ctx.A, "join_wgrad", None)        # (as PSpMM.backward: the weight gradient parked on the engine's side stream)
+        if join is not None:
+            join()
+        return None, dH
+
+
+class _PnaScale(torch.autograd.Function):
+    """Z = Y0 + a Y1 + b Y2 over the PNA layer's product Y = [Y0 | Y1 | Y2] (n x 3 fout): the identity, amplification and attenuation
+    scalers a_i = log(max(d_i, 1) + 1) / delta, b_i = 1 / a_i of the engine (``A.pna_scale``; pgcn_pna_scale_forward_f32 on a HIP
+    device).  Backward dY = [G | a G | b G].  Nothing is saved: the scalers are the engine's constants."""
+
+    @staticmethod
+    def forward(ctx, A, Y):
+        ctx.A = A
+        return A.pna_scale(Y)
+
+    @staticmethod
+    def backward(ctx, G):
+        return None, ctx.A.pna_scale_backward(G)
 
 
 def _softmax_beta(value, what="softmax_beta"):
@@ -1655,6 +1700,12 @@ class PGCN(nn.Module):
     ignored -- instead of ``PSpMM``; every other option composes unchanged and the layer owns the same parameters.  None or "sum":
     the branches of before.
 
+    ``aggr="pna"`` (opt-in): Principal Neighbourhood Aggregation (Corso et al., 2020; PyG's ``PNAConv`` without towers and pre-layers) --
+    ``PAggPna`` forms S = [MEAN | MAX | MIN | STD] of the stored neighbourhood in one gather (csrc/pgcn_aggpna.hip), the layer owns
+    ``linear = nn.Linear(12 fin, fout, bias=False)`` with its columns in PyG's order (scaler-major: identity, amplification, attenuation;
+    then aggregator; then feature) and computes it as ONE product S W'^T of width 4 fin -> 3 fout followed by the degree scalers
+    (``_PnaScale``); the result enters ``_forward_combined`` as Z1, so ``root_weight``, ``bias``, ``norm``, ``residual``, dropout and
+    ``relu=False`` compose as they do for max.  Refused with ``aggregate=False``, an active ``drop_edge`` and ``softmax_beta``.
     ``aggregate=False`` (opt-in): the layer does not aggregate -- act(H W^T ...), a dense layer over the vertices' own rows (the MLP
     in front of ``Propagate``); no exchange, no engine call.  Every other option composes through the same nodes, and the layer owns
     the same parameters under the same state-dict keys.  Refused with ``aggr="max"`` (nothing to take a max over) and with
@@ -1673,9 +1724,15 @@ class PGCN(nn.Module):
     def __init__(self, A, in_features, out_features, dropout=0.0, layer=0, state=None, relu=True, norm=None, root_weight=False, bias=False,
                  residual=False, aggr=None, aggregate=True, drop_edge=None, softmax_beta=None):
         super(PGCN, self).__init__()
-        if aggr not in AGGRS + (None,):
-            raise ValueError("aggr takes %s, got %r" % (" | ".join(AGGRS), aggr))
+        if aggr not in ALL_AGGRS + (None,):
+            raise ValueError("aggr takes %s, got %r" % (" | ".join(ALL_AGGRS), aggr))
         self.aggregate = bool(aggregate)
+        self.pna = aggr == "pna"
+        if self.pna:
+            clash = ("aggregate=False" if not self.aggregate else "softmax_beta" if softmax_beta is not None
+                     else "drop_edge" if drop_edge is not None and drop_edge.on else None)
+            if clash is not None:
+                raise ValueError('aggr="pna" does not go with %s' % clash)
         if softmax_beta is not None:
             softmax_beta = _softmax_beta(softmax_beta)
             if aggr == "max" or not self.aggregate or (drop_edge is not None and drop_edge.on):
@@ -1693,7 +1750,8 @@ class PGCN(nn.Module):
         if softmax_beta is not None:
             self.softmax_beta = softmax_beta
             self._aggregate = self._aggregate_softmax
-        self.linear = nn.Linear(in_features, out_features, bias=False)
+        # (PNA: 3 scalers x 4 aggregators x fin columns in PyG's order -- scaler-major, then aggregator, then feature)
+        self.linear = nn.Linear(12 * in_features if self.pna else in_features, out_features, bias=False)
         self.A = A
         self.send_map = send_map
         self.recv_map = recv_map
@@ -1737,6 +1795,14 @@ class PGCN(nn.Module):
     def _aggregate_softmax(self, A, H):
         return PAggSoftmax.apply(A, H, self.softmax_beta)
 
+    def _pna_product(self, H):
+        """The neighbour product of a PNA layer: the n x 12 fin operand [S | a S | b S] is never formed.  Y = S W'^T with W' the weight
+        viewed as (3 fout) x (4 fin) -- one ``_LinearNoBias``, so the narrow, wide and library routes choose themselves -- then the
+        scalers act on the three fout-wide blocks of Y (``_PnaScale``)."""
+        fout, fin4 = self.linear.weight.shape[0], self.linear.weight.shape[1] // 3
+        W = self.linear.weight.view(fout, 3, fin4).permute(1, 0, 2).reshape(3 * fout, fin4)
+        return _PnaScale.apply(self.A, _LinearNoBias.apply(PAggPna.apply(self.A, H), W))
+
     def _global_row_ids(self, H):
         if self._row_ids is None or self._row_ids.device != H.device:      # global ids in local row order, once
             self._row_ids = self.A.part.owned.to(device=H.device, dtype=torch.int64).contiguous()
@@ -1753,7 +1819,7 @@ class PGCN(nn.Module):
 
     def _forward_combined(self, H, AH, R=None):
         """The layer with a root weight and / or a bias: H the layer's input (owned rows), AH its aggregation."""
-        Z1 = _LinearNoBias.apply(AH, self.linear.weight)
+        Z1 = self._pna_product(H) if self.pna else _LinearNoBias.apply(AH, self.linear.weight)
         Z2 = _LinearNoBias.apply(H, self.root.weight) if self.root_weight else None
         drop = self.relu and self.training and self.dropout > 0.0
         if drop and self.state is None:
@@ -1776,6 +1842,8 @@ class PGCN(nn.Module):
         return self._layer(H)
 
     def _layer(self, H, R=None):
+        if self.pna:            # (always the combined route: Z1 is the scaled product, the tail is the one of before)
+            return self._forward_combined(H, None, R)
         if self.root_weight or self.has_bias:
             return self._forward_combined(H, self._aggregate(self.A, H), R)
         if self.norm == "node":
@@ -1959,7 +2027,7 @@ def _architecture(fin, classes, nlayers, nfeatures, hidden, multilabel, dropout,
     positive, so that earlier checkpoints compare as before)."""
     widths = [int(fin)] + [int(nfeatures if hidden is None else hidden)] * (nlayers - 1) + [int(classes)]
     return _checkpoint.architecture(widths, "multilabel" if multilabel else "single", dropout, dropout_seed, norm, root_weight, bias,
-                                    residual, **({"aggr": aggr} if aggr == "max" else {}),
+                                    residual, **({"aggr": aggr} if aggr in ("max", "pna") else {}),
                                     **({"propagate": (propagate, PPR_ALPHA if ppr_alpha is None else ppr_alpha)} if propagate is not None else {}),
                                     **({"dense_layers": True} if dense_layers else {}),
                                     **({"drop_edge": float(drop_edge)} if drop_edge else {}),
@@ -1974,8 +2042,8 @@ def _check_softmax_beta(softmax_beta, aggr=None, dense_layers=None, drop_edge=No
     if softmax_beta is None:
         return
     _softmax_beta(softmax_beta)
-    if aggr == "max":
-        raise ValueError('softmax_beta does not go with aggr="max"')
+    if aggr in ("max", "pna"):
+        raise ValueError('softmax_beta does not go with aggr="%s"' % aggr)
     if dense_layers:
         raise ValueError("softmax_beta does not go with dense_layers: nothing is aggregated")
     if drop_edge:
@@ -1994,8 +2062,8 @@ def _check_drop_edge(drop_edge, normalize=None, aggr=None, dense_layers=None, ch
         if check_normalize and normalize != "sym":
             raise ValueError("drop_edge needs normalize='sym': DropEdge renormalises the pattern of A + I, a weighted or pre-normalised "
                              "matrix cannot be renormalised")
-        if aggr == "max":
-            raise ValueError('drop_edge does not go with aggr="max"')
+        if aggr in ("max", "pna"):
+            raise ValueError('drop_edge does not go with aggr="%s"' % aggr)
         if dense_layers:
             raise ValueError("drop_edge does not go with dense_layers: nothing is aggregated")
 
@@ -2012,8 +2080,8 @@ def _check_propagate(propagate, ppr_alpha, dense_layers, aggr=None, root_weight=
             raise ValueError("ppr_alpha needs propagate")
         if isinstance(ppr_alpha, bool) or not isinstance(ppr_alpha, (int, float)) or not 0.0 <= float(ppr_alpha) < 1.0:
             raise ValueError("ppr_alpha takes a finite number with 0 <= alpha < 1, got %r" % (ppr_alpha,))
-    if dense_layers and (aggr == "max" or root_weight):
-        raise ValueError("dense_layers does not go with %s" % ('aggr="max"' if aggr == "max" else "root_weight"))
+    if dense_layers and (aggr in ("max", "pna") or root_weight):
+        raise ValueError("dense_layers does not go with %s" % ('aggr="%s"' % aggr if aggr in ("max", "pna") else "root_weight"))
 
 
 def _check_gpr(gpr, gpr_init, gpr_alpha, propagate=None):
@@ -2090,8 +2158,8 @@ def _train_on_data(A, n, nlayers, nfeatures, features, labels, split, hidden, ep
     _dropout.threshold(dropout)
     state = _dropout.DropoutState(dropout_seed, device) if dropout > 0.0 or drop_edge > 0.0 else None
     extra = dict(({"root_weight": True} if root_weight else {}), **({"bias": True} if bias else {}))       # (neither: the call of before)
-    if aggr == "max":
-        extra["aggr"] = "max"
+    if aggr in ("max", "pna"):
+        extra["aggr"] = aggr
     if dense_layers:
         extra["aggregate"] = False
     if drop_edge > 0.0:
@@ -2254,8 +2322,8 @@ def run(rank, size, nlayers, nfeatures, path_A, path_partvec, backend, normalize
         raise ValueError("root_weight and bias need features, labels and split")
     if residual is not None and not all(given):
         raise ValueError("residual needs features, labels and split")
-    if aggr not in AGGRS + (None,):
-        raise ValueError("aggr takes %s, got %r" % (" | ".join(AGGRS), aggr))
+    if aggr not in ALL_AGGRS + (None,):
+        raise ValueError("aggr takes %s, got %r" % (" | ".join(ALL_AGGRS), aggr))
     if aggr is not None and not all(given):
         raise ValueError("aggr=%r needs features, labels and split" % (aggr,))
     _check_propagate(propagate, ppr_alpha, dense_layers, aggr, root_weight)
@@ -2345,7 +2413,7 @@ def run(rank, size, nlayers, nfeatures, path_A, path_partvec, backend, normalize
                               **({"root_weight": True} if root_weight else {}), **({"bias": True} if bias else {}),
                               **({"residual": True} if residual else {}),
                               **{k: v for k, v in (("save", save), ("load", load), ("predict", predict), ("proba", proba)) if v is not None},
-                              **({"control": control} if control else {}), **({"aggr": "max"} if aggr == "max" else {}),
+                              **({"control": control} if control else {}), **({"aggr": aggr} if aggr in ("max", "pna") else {}),
                               **{k: v for k, v in (("propagate", propagate), ("ppr_alpha", ppr_alpha)) if v is not None},
                               **({"dense_layers": True} if dense_layers else {}),
                               **({"drop_edge": float(drop_edge)} if drop_edge else {}),
@@ -2544,9 +2612,10 @@ def main(argv):
                 sys.exit(2)
             if arg != "none" or "norm" in data:
                 data["norm"] = arg
-        elif opt == '--aggr':          # sum (the default) | max (the element-wise max over the neighbourhood: PAggMax) -- every layer
-            if arg not in AGGRS:
-                print("--aggr takes %s, got %r" % ("|".join(AGGRS), arg), flush=True)
+        elif opt == '--aggr':          # sum (the default) | max (the element-wise max over the neighbourhood: PAggMax) | pna (mean, max, min
+                                       # and std with the three degree scalers: PAggPna) -- every layer
+            if arg not in ALL_AGGRS:
+                print("--aggr takes %s, got %r" % ("|".join(ALL_AGGRS), arg), flush=True)
                 sys.exit(2)
             if arg != "sum" or "aggr" in data:
                 data["aggr"] = arg
@@ -2657,19 +2726,19 @@ def main(argv):
     if ("gpr_init" in data or "gpr_alpha" in data) and "gpr" not in data:
         print("--gpr-init and --gpr-alpha need --gpr", flush=True)
         sys.exit(2)
-    if "dense_layers" in data and (data.get("aggr") == "max" or "root_weight" in data):
-        print("--dense-layers does not go with %s" % ("--aggr max" if data.get("aggr") == "max" else "--root-weight"), flush=True)
+    if "dense_layers" in data and (data.get("aggr") in ("max", "pna") or "root_weight" in data):
+        print("--dense-layers does not go with %s" % ("--aggr %s" % data["aggr"] if data.get("aggr") in ("max", "pna") else "--root-weight"), flush=True)
         sys.exit(2)
     if data.get("drop_edge", 0.0) > 0.0:
         if normalize != "sym":
             print("--drop-edge needs --normalize sym: DropEdge renormalises the pattern of A + I, a weighted or pre-normalised matrix "
                   "cannot be renormalised", flush=True)
             sys.exit(2)
-        if data.get("aggr") == "max" or "dense_layers" in data:
-            print("--drop-edge does not go with %s" % ("--aggr max" if data.get("aggr") == "max" else "--dense-layers"), flush=True)
+        if data.get("aggr") in ("max", "pna") or "dense_layers" in data:
+            print("--drop-edge does not go with %s" % ("--aggr %s" % data["aggr"] if data.get("aggr") in ("max", "pna") else "--dense-layers"), flush=True)
             sys.exit(2)
     if "softmax_beta" in data:
-        clash = ("--aggr max" if data.get("aggr") == "max" else "--dense-layers" if "dense_layers" in data
+        clash = ("--aggr %s" % data["aggr"] if data.get("aggr") in ("max", "pna") else "--dense-layers" if "dense_layers" in data
                  else "--drop-edge" if data.get("drop_edge", 0.0) > 0.0 else None)
         if clash:
             print("--softmax-aggr does not go with %s" % clash, flush=True)

@@ -569,6 +569,138 @@ def aggsoftmax_backward_composed(AT: ComposedMaxCSR, X: torch.Tensor, G: torch.T
     return D
 
 
+# --------------------------------------------------------------------------
+# PNA aggregators: the composed route (framework operations; the definitions of csrc/pgcn_aggpna.hip)
+
+PNA_EPS = 1e-5
+
+
+def pna_merge_var(na, ma, Ma, nb, mb, Mb):
+    """Chan's rule: the group (nb, mb, Mb) joins the state (na, ma, Ma) -- counts n x 1, means and M2 = sum (x - mean)^2 n x f.  A
+    count of 0 is an absent group.  Returns (mean, M2) of the union."""
+    n = na + nb
+    r = nb / torch.where(n > 0, n, torch.ones_like(n))
+    dl = mb - ma
+    mean = torch.where(nb == 0, ma, torch.where(na == 0, mb, ma + dl * r))
+    M2 = torch.where(nb == 0, Ma, torch.where(na == 0, Mb, Ma + Mb + dl * dl * (na * r)))
+    return mean, M2
+
+
+def _min_better(v, g, cur, a):
+    """The update rule of the min: candidate (v, g) replaces the state (cur, a)."""
+    return (g >= 0) & ((a < 0) | (v < cur) | ((v == cur) & (g < a)))
+
+
+def aggpna_composed(A: ComposedMaxCSR, B: torch.Tensor, S: torch.Tensor, AMAX: torch.Tensor, AMIN: torch.Tensor, cnt_prior=None,
+                    accumulate: bool = False):
+    """(S, AMAX, AMIN) of ``HipKernels.aggpna`` from framework operations: S = [MEAN | MAX | MIN | M2].  MAX, MIN and their args
+    bit for bit (``aggmax_composed``; the min is the max of -B, negation is exact); the mean and M2 from sums shifted by every row's
+    first value, never from E[x^2] - E[x]^2.  ``accumulate``: the rows' current state joins by the merge rules, ``cnt_prior`` the
+    candidates it holds.  nnz x f temporaries: the route of CPU tensors and of providers without the kernels."""
+    n, f = A.nrows, B.shape[1]
+    B = B.detach()
+    mx, amx = aggmax_composed(A, B, torch.empty((n, f), dtype=B.dtype, device=B.device),
+                              torch.empty((n, f), dtype=torch.int32, device=B.device))
+    mn, amn = aggmax_composed(A, -B, torch.empty((n, f), dtype=B.dtype, device=B.device),
+                              torch.empty((n, f), dtype=torch.int32, device=B.device))
+    mn = torch.where(amn >= 0, -mn, mn)                                                # (a row without entries keeps +0.0)
+    cnt = torch.zeros(n, dtype=torch.int64, device=B.device)
+    mean = torch.zeros((n, f), dtype=B.dtype, device=B.device)
+    M2 = torch.zeros((n, f), dtype=B.dtype, device=B.device)
+    if A.nnz:
+        X = B[A.col]
+        cnt = torch.bincount(A.row, minlength=n)
+        e = torch.arange(A.nnz, dtype=torch.int64, device=B.device)
+        first = torch.full((n,), A.nnz - 1, dtype=torch.int64, device=B.device).scatter_reduce(0, A.row, e, "amin", include_self=True)
+        K = X[first]                                                                   # every row's first value (any row of X where it has none)
+        dl = X - K[A.row]
+        c = cnt.clamp(min=1).to(B.dtype).unsqueeze(1)
+        s1 = torch.zeros((n, f), dtype=B.dtype, device=B.device).index_add_(0, A.row, dl)
+        s2 = torch.zeros((n, f), dtype=B.dtype, device=B.device).index_add_(0, A.row, dl * dl)
+        has = (cnt > 0).unsqueeze(1)
+        mean = torch.where(has, K + s1 / c, mean)
+        M2 = torch.where(has, (s2 - s1 * (s1 / c)).clamp(min=0), M2)
+    if accumulate:
+        cur = S[:n]
+        na = cnt_prior[:n].to(B.dtype).unsqueeze(1)
+        mean, M2 = pna_merge_var(na, cur[:, :f], cur[:, 3 * f:], cnt.to(B.dtype).unsqueeze(1), mean, M2)
+        cx, cax, cn, can = cur[:, f:2 * f], AMAX[:n], cur[:, 2 * f:3 * f], AMIN[:n]
+        take = _max_better(mx, amx, cx, cax)
+        mx, amx = torch.where(take, mx, cx), torch.where(take, amx, cax)
+        take = _min_better(mn, amn, cn, can)
+        mn, amn = torch.where(take, mn, cn), torch.where(take, amn, can)
+    S[:n] = torch.cat([mean, mx, mn, M2], 1)
+    AMAX[:n] = amx
+    AMIN[:n] = amn
+    return S, AMAX, AMIN
+
+
+def aggpna_finish_composed(S: torch.Tensor, deg: torch.Tensor, dS=None, AMAX=None, AMIN=None):
+    """``HipKernels.aggpna_finish`` from framework operations.  Without ``dS``: M2 -> STD in S's fourth block, in place.  With it: the
+    operands of the backward (P, Q, dMAX, dMIN, AMAX, AMIN) as a tuple -- what the kernels' route interleaves into one panel."""
+    f = S.shape[1] // 4
+    d = deg[:S.shape[0]].to(S.dtype).unsqueeze(1)
+    has, d1 = d > 0, d.clamp(min=1)
+    if dS is None:
+        S[:, 3 * f:] = torch.where(has, torch.sqrt(S[:, 3 * f:] / d1 + PNA_EPS), torch.zeros_like(d))
+        return S
+    dS = dS.detach()
+    Q = torch.where(has, dS[:, 3 * f:] / (d1 * torch.where(has, S[:, 3 * f:], torch.ones_like(d))), torch.zeros_like(d))
+    P = torch.where(has, dS[:, :f] / d1 - Q * S[:, :f], torch.zeros_like(d))
+    return P, Q, dS[:, f:2 * f], dS[:, 2 * f:3 * f], AMAX, AMIN
+
+
+def aggpna_backward_composed(AT: ComposedMaxCSR, row_gid: torch.Tensor, X: torch.Tensor, panel, D: torch.Tensor):
+    """D of ``HipKernels.aggpna_backward`` from framework operations: D[r] = sum over the stored entries i of row r of the transposed
+    structure of (P[i] + (AMAX[i] == row_gid[r] ? dMAX[i] : 0) + (AMIN[i] == row_gid[r] ? dMIN[i] : 0)) + X[r] sum_i Q[i].  The same
+    definition; only the order of the fp32 additions is the framework's."""
+    P, Q, gmax, gmin, AMAX, AMIN = panel
+    n = AT.nrows
+    D[:n] = 0
+    if AT.nnz:
+        g = row_gid.to(AMAX.dtype)[AT.row].unsqueeze(1)
+        zero = torch.zeros((), dtype=P.dtype, device=P.device)
+        term = P[AT.col] + torch.where(AMAX[AT.col] == g, gmax[AT.col], zero) + torch.where(AMIN[AT.col] == g, gmin[AT.col], zero)
+        D[:n].index_add_(0, AT.row, term)
+        qs = torch.zeros_like(D[:n]).index_add_(0, AT.row, Q[AT.col])
+        D[:n] += X.detach()[:n] * qs
+    return D
+
+
+def pna_scale_composed(Y: torch.Tensor, a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
+    """``HipKernels.pna_scale`` from framework operations: Y0 + a Y1 + b Y2 over Y = [Y0 | Y1 | Y2]."""
+    fo = Y.shape[1] // 3
+    return Y[:, :fo] + a.unsqueeze(1) * Y[:, fo:2 * fo] + b.unsqueeze(1) * Y[:, 2 * fo:]
+
+
+def pna_scale_backward_composed(G: torch.Tensor, a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
+    return torch.cat([G, a.unsqueeze(1) * G, b.unsqueeze(1) * G], 1)
+
+
+def pna_delta(hist) -> float:
+    """delta of the PNA scalers: the mean over all vertices of log(d + 1), from the integer degree histogram (hist[d] = vertices of
+    degree d) -- a float64 sum in ascending degree, so the same bits under any part vector and rank count."""
+    import numpy as np
+    hist = np.asarray(hist, dtype=np.int64)
+    n = int(hist.sum())
+    if n == 0:
+        return 0.0
+    terms = hist.astype(np.float64) * np.log(np.arange(hist.shape[0], dtype=np.float64) + 1.0)
+    return float(np.cumsum(terms)[-1] / n)
+
+
+@dataclasses.dataclass
+class PnaDegrees:
+    """What ``forward_pna`` / ``backward_pna`` need beside ``MaxStructures``, built once: the whole row's stored length d (int32, the
+    local and every halo structure together), per halo round the count the row's state holds before that round joins, and the
+    scalers a = log(max(d, 1) + 1) / delta, b = 1 / a (fp32, rounded from float64) with delta = mean over ALL vertices of log(d + 1)."""
+    deg: torch.Tensor
+    prior: list
+    delta: float
+    a: torch.Tensor
+    b: torch.Tensor
+
+
 @dataclasses.dataclass
 class MaxStructures:
     """What ``AggregationEngine.forward_max`` / ``backward_max`` run on, built at the first max call: the whole pattern of every
@@ -751,6 +883,7 @@ class AggregationEngine(BoundaryExchange):
         self._wgrad_stream = None       # side stream of the weight gradients (tuning.wgrad_lane), made on first use
         self._wgrad_parked = []         # [(event after a weight gradient on that stream, tensors it reads)] not yet joined
         self._max: Optional[MaxStructures] = None      # the max aggregation's structures, built at the first forward_max / backward_max
+        self._pna: Optional[PnaDegrees] = None         # PNA's degrees and scalers, built at the first pna_degrees
         self._drop: Optional[DropEdgeStructures] = None    # DropEdge's structures, built at the first forward_drop / drop_refresh
         self.reuse_operand = bool(_T.reuse_operand)     # forward_reusing may keep the aggregation of an unchanged operand ...
         self.reuse_max_bytes = int(_T.reuse_max_bytes)  # ... whose copy and result fit in this
@@ -1175,6 +1308,134 @@ class AggregationEngine(BoundaryExchange):
             waits[r]()
             self.k.spmm(self.unpack[r], back, dH, accumulate=True)      # returned rows are sums: backward's unpack
         return dH
+
+    # ------------------------------------------------------------------
+    # PNA aggregators (csrc/pgcn_aggpna.hip): S = [MEAN | MAX | MIN | STD] of H over the stored columns of every
+    # row in one gather, AMAX / AMIN the smallest GLOBAL ids that attain the extremes.  On ``_max_structures()``: nothing new is prepared.
+    PNA_KERNELS = ("aggpna", "aggpna_finish", "aggpna_backward")
+
+    def pna_degrees(self) -> PnaDegrees:
+        """Built once, at the first PNA call: the degrees (stored row lengths over the local and all halo structures, int32 on the
+        device), the per-round prior counts and the scalers.  delta comes from the integer degree histogram: the counts are summed over
+        the ranks (exact), the float64 sum runs in ascending degree on every rank.  COLLECTIVE on a multi-rank partition."""
+        if self._pna is None:
+            m = self._max_structures(self.PNA_KERNELS)
+            n = self.n_local
+
+            def lengths(a):
+                if m.composed:
+                    lens = torch.bincount(a.row, minlength=a.nrows) if a.nnz else torch.zeros(a.nrows, dtype=torch.int64, device=self.device)
+                else:
+                    lens = a.rowptr[1:] - a.rowptr[:-1]
+                out = torch.zeros(n, dtype=torch.int64, device=self.device)
+                out[:lens.numel()] = lens[:n]
+                return out
+            run, prior = lengths(m.loc), []
+            for a in (m.halo if self.size > 1 else []):
+                prior.append(run.to(torch.int32).contiguous())
+                run = run + lengths(a)
+            if n and int(run.max()) >= 2 ** 31:
+                raise ValueError("PNA keeps a vertex's degree as int32: a degree >= 2^31 is not supported")
+            top = torch.tensor([int(run.max()) if n else 0], dtype=torch.int64)
+            top = self._reduce_host(top, dist.ReduceOp.MAX)
+            hist = torch.bincount(run.cpu(), minlength=int(top[0]) + 1)
+            hist = self._reduce_host(hist, dist.ReduceOp.SUM)
+            delta = pna_delta(hist.numpy())
+            if not delta > 0.0:
+                raise ValueError("aggr=\"pna\": the degree scalers divide by delta = mean log(d + 1), which is 0 here (no vertex has a "
+                                 "stored neighbour)")
+            lg = torch.log(run.clamp(min=1).to(torch.float64) + 1.0)
+            self._pna = PnaDegrees(run.to(torch.int32).contiguous(), prior, delta, (lg / delta).to(torch.float32).contiguous(),
+                                   (delta / lg).to(torch.float32).contiguous())
+        return self._pna
+
+    def _reduce_host(self, t: torch.Tensor, op) -> torch.Tensor:
+        """An integer all-reduce of a small host tensor over torch.distributed (through the device where the backend takes no host
+        tensors); the identity on one rank."""
+        if self.size == 1:
+            return t
+        if dist.get_backend() == "gloo" or not self.on_gpu:
+            dist.all_reduce(t, op=op)
+            return t
+        d = t.to(self.device)
+        dist.all_reduce(d, op=op)
+        return d.cpu()
+
+    def forward_pna(self, H: torch.Tensor):
+        """(S, AMAX, AMIN, halo): S = [MEAN | MAX | MIN | STD] (n_local x 4 f) of H over every owned vertex's stored neighbourhood
+        (stored values ignored; all 0.0 and -1 for a vertex without neighbours), the global ids that attain the extremes (int32), and
+        the received boundary rows as a tensor of its own (None at size 1) for the backward.  The exchange and its overlap are
+        ``forward_softmax``'s; every round's halo structure joins the state by the merge rules, STD is formed once at the end."""
+        if H.shape[0] != self.n_local:
+            raise ValueError("H must hold exactly the %d owned rows" % self.n_local)
+        m = self._max_structures(self.PNA_KERNELS)
+        dg = self.pna_degrees()
+        run = aggpna_composed if m.composed else self.k.aggpna
+        finish = aggpna_finish_composed if m.composed else self.k.aggpna_finish
+        H = H.contiguous()
+        f = H.shape[1]
+        S = torch.empty((self.n_local, 4 * f), dtype=torch.float32, device=self.device)
+        AMAX = torch.empty((self.n_local, f), dtype=torch.int32, device=self.device)
+        AMIN = torch.empty((self.n_local, f), dtype=torch.int32, device=self.device)
+        if self.size == 1:
+            run(m.loc, H, S, AMAX, AMIN)
+            return finish(S, dg.deg), AMAX, AMIN, None
+        send = self._slab("send", self.n_send, f)
+        halo = torch.empty((max(self.n_halo, 1), f), dtype=torch.float32, device=self.device)      # kept for the backward (forward_softmax)
+        self.k.gather_rows(H, self.send_idx, send)
+        waits = self._exchange_all(send, self.round_send_off, halo, self.round_recv_off, f, tag="forward")
+        run(m.loc, H, S, AMAX, AMIN)             # overlaps the exchange
+        for r in range(self.rounds):
+            waits[r]()
+            run(m.halo[r], halo, S, AMAX, AMIN, dg.prior[r], accumulate=True)      # round r's group joins; overlaps round r+1
+        return finish(S, dg.deg), AMAX, AMIN, halo
+
+    def backward_pna(self, dS: torch.Tensor, H: torch.Tensor, halo, S: torch.Tensor, AMAX: torch.Tensor, AMIN: torch.Tensor) -> torch.Tensor:
+        """dH of ``forward_pna``: dH[j] = sum over the vertices i that hold j of (P[i] + (AMAX[i] == j ? dMAX[i] : 0) + (AMIN[i] == j ?
+        dMIN[i] : 0)) + H[j] sum_i Q[i], with Q = dSTD / (d STD), P = dMEAN / d - Q MEAN formed once per call.  Partial sums for rows
+        owned by peers travel home like ``backward``'s (f wide) and are ADDED."""
+        m = self._max_structures(self.PNA_KERNELS)
+        if m.loc_T is None:
+            raise RuntimeError("partition was built without the transposed pieces")
+        dg = self.pna_degrees()
+        run = aggpna_backward_composed if m.composed else self.k.aggpna_backward
+        finish = aggpna_finish_composed if m.composed else self.k.aggpna_finish
+        dS, H = dS.contiguous(), H.contiguous()
+        f = H.shape[1]
+        panel = finish(S, dg.deg, dS, AMAX, AMIN)
+        dH = torch.empty((self.n_local, f), dtype=torch.float32, device=self.device)
+        if self.size == 1:
+            return run(m.loc_T, m.owned, H, panel, dH)
+        partial = self._slab("halo", self.n_halo, f)
+        back = self._slab("send", self.n_send, f)
+        ready = []
+        for r in range(self.rounds):
+            b0, b1 = self.round_recv_off[r][0], self.round_recv_off[r][-1]
+            run(m.halo_T[r], m.halo_global[b0:b1], halo[b0:b1], panel, partial[b0:b1])
+            if self.overlap:
+                ev = torch.cuda.Event()
+                ev.record(torch.cuda.current_stream(self.device))
+                ready.append(ev)
+        waits = self._exchange_all(partial, self.round_recv_off, back, self.round_send_off, f,
+                                   ready if self.overlap else None, tag="backward")
+        run(m.loc_T, m.owned, H, panel, dH)
+        for r in range(self.rounds):
+            waits[r]()
+            self.k.spmm(self.unpack[r], back, dH, accumulate=True)      # returned rows are sums: backward's unpack
+        return dH
+
+    def pna_scale(self, Y: torch.Tensor) -> torch.Tensor:
+        """Z = Y0 + a Y1 + b Y2 over Y = [Y0 | Y1 | Y2]: the identity, amplification and attenuation scalers of this rank's rows."""
+        dg = self.pna_degrees()
+        if self.on_gpu and hasattr(self.k, "pna_scale"):
+            return self.k.pna_scale(Y.contiguous(), dg.a, dg.b)
+        return pna_scale_composed(Y, dg.a, dg.b)
+
+    def pna_scale_backward(self, G: torch.Tensor) -> torch.Tensor:
+        dg = self.pna_degrees()
+        if self.on_gpu and hasattr(self.k, "pna_scale_backward"):
+            return self.k.pna_scale_backward(G.contiguous(), dg.a, dg.b)
+        return pna_scale_backward_composed(G, dg.a, dg.b)
 
     # ------------------------------------------------------------------
     # DropEdge (csrc/pgcn_dropedge.hip; DESIGN.md section 4): the aggregation over the stored pattern minus the entries dropped in this

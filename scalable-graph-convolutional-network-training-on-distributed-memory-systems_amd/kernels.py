@@ -956,6 +956,165 @@ class HipKernels:
         fn(X, G, OUT, LSE, D)
         return D
 
+    # -- PNA aggregators and scalers (pgcn_aggpna.hip) -------------------------
+    @staticmethod
+    def pna_panel_ld(f: int) -> int:
+        """Words of a row of the backward's panel: six planes of 4 ceil(f / 4) words (include/pgcn_hip.h)."""
+        return 24 * ((int(f) + 3) // 4)
+
+    def _pna_counts(self, t, rows: int, what: str):
+        if not (t.is_cuda and t.dtype is torch.int32 and t.dim() == 1 and t.is_contiguous() and t.numel() >= rows):
+            raise _lib.PgcnError("%s must be a contiguous int32 CUDA vector of at least %d entries" % (what, rows))
+
+    def aggpna(self, A: DeviceMaxCSR, B: torch.Tensor, S: torch.Tensor, AMAX: torch.Tensor, AMIN: torch.Tensor,
+               cnt_prior: Optional[torch.Tensor] = None, accumulate: bool = False):
+        """(S, AMAX, AMIN) of the four PNA aggregators over the stored columns of every row of ``A`` (include/pgcn_hip.h,
+        pgcn_aggpna_csr_plan_f32; a ``prepare_max(csr, col_gid)`` structure) on the current stream: S = [MEAN | MAX | MIN | M2], n x 4 f
+        -- ``aggpna_finish`` turns M2 into STD after the last structure.  ``accumulate``: the rows' current state joins under the merge
+        rules, ``cnt_prior`` (int32 per row) the candidates it already holds.  Rows beyond ``A.nrows`` are not touched."""
+        if A.pairs is None:
+            raise _lib.PgcnError("aggpna needs a structure made by prepare_max(csr, col_gid)")
+        if accumulate:
+            if cnt_prior is None:
+                raise _lib.PgcnError("aggpna: accumulate needs cnt_prior, the candidates already merged into every row")
+            self._pna_counts(cnt_prior, A.nrows, "cnt_prior")
+        key = ("pna", B.stride(0), S.stride(0), AMAX.stride(0), AMIN.stride(0), B.shape[1], bool(accumulate))
+        fn = A.launch_cache.get(key)
+        if fn is None:
+            f = B.shape[1]
+            self._max_operand(B, A.ncols, torch.float32, "B")
+            self._max_operand(S, A.nrows, torch.float32, "S")
+            self._max_operand(AMAX, A.nrows, torch.int32, "AMAX")
+            self._max_operand(AMIN, A.nrows, torch.int32, "AMIN")
+            if S.shape[1] != 4 * f or AMAX.shape[1] != f or AMIN.shape[1] != f:
+                raise _lib.PgcnError("S must be 4 f wide, AMAX and AMIN f wide (f = %d)" % f)
+            ldb, lds, ldx, ldn = max(B.stride(0), f), max(S.stride(0), 4 * f), max(AMAX.stride(0), f), max(AMIN.stride(0), f)
+            nrows = A.nrows
+            if nrows == 0 or (A.nnz == 0 and accumulate):
+                fn = lambda B, S, AMAX, AMIN, cnt: None
+            elif A.nnz == 0:            # nothing to launch: every row is empty (memsets, plumbing)
+                def fn(B, S, AMAX, AMIN, cnt):
+                    S[:nrows].zero_()
+                    AMAX[:nrows].fill_(-1)
+                    AMIN[:nrows].fill_(-1)
+            else:
+                flags = self.base_flags | (_lib.SPMM_ACCUMULATE if accumulate else 0) | self._max_fpass(A, f)
+                if (A.ncols + 1) * ldb * 4 < 2 ** 32:
+                    flags |= _lib.SPMM_OFFSETS32
+                ws, ws_n = self._max_ws(A, A.nslots * (24 * f + 4))
+                lib, check, stream = self.lib, _lib.check, self._stream
+                rowptr, pairs, tasks, ntasks, fix, nfix, nslots = (A.rowptr.data_ptr(), A.pairs.data_ptr(), _ptr(A.tasks), A.ntasks,
+                                                                   _ptr(A.fix), A.nfix, A.nslots)
+                seg, nslices = A.seg, A.nslices
+
+                def fn(B, S, AMAX, AMIN, cnt):
+                    check(lib.pgcn_aggpna_csr_plan_f32(rowptr, pairs, tasks, ntasks, seg, nslices, fix, nfix, B.data_ptr(), ldb, S.data_ptr(),
+                                                       lds, AMAX.data_ptr(), ldx, AMIN.data_ptr(), ldn, _ptr(cnt), f, ws, ws_n, nslots,
+                                                       flags, stream()), "pgcn_aggpna_csr_plan_f32")
+            A.launch_cache[key] = fn
+        fn(B, S, AMAX, AMIN, cnt_prior if accumulate else None)
+        return S, AMAX, AMIN
+
+    def aggpna_finish(self, S: torch.Tensor, deg: torch.Tensor, dS: Optional[torch.Tensor] = None, AMAX: Optional[torch.Tensor] = None,
+                      AMIN: Optional[torch.Tensor] = None):
+        """Without ``dS``: the fourth block of S, M2 -> STD = sqrt(M2 / d + 1e-5) in place (0 where d = 0); returns S.  With ``dS`` = [dMEAN |
+        dMAX | dMIN | dSTD]: the panel of the backward, n x 24 ceil(f / 4) words, six planes {P | Q | dMAX | dMIN | AMAX | AMIN} per row
+        (pgcn_aggpna_finish_f32), a new tensor.  ``deg``: int32 per row, the whole row's stored length."""
+        n, f = S.shape[0], S.shape[1] // 4
+        if S.shape[1] != 4 * f or f < 1 or f > ROWBAND_MAX_F:
+            raise _lib.PgcnError("aggpna_finish: S must be 4 f wide with 1 <= f <= %d, got %d columns" % (ROWBAND_MAX_F, S.shape[1]))
+        self._max_operand(S, n, torch.float32, "S")
+        self._pna_counts(deg, n, "deg")
+        lib, check = self.lib, _lib.check
+        if dS is None:
+            check(lib.pgcn_aggpna_finish_f32(_ptr(S), max(S.stride(0), 4 * f), _ptr(deg), n, f, None, 0, None, 0, None, 0, None, 0,
+                                             self._stream()), "pgcn_aggpna_finish_f32")
+            return S
+        self._max_operand(dS, n, torch.float32, "dS")
+        self._max_operand(AMAX, n, torch.int32, "AMAX")
+        self._max_operand(AMIN, n, torch.int32, "AMIN")
+        if dS.shape[1] != 4 * f or AMAX.shape[1] != f or AMIN.shape[1] != f:
+            raise _lib.PgcnError("aggpna_finish: dS must be 4 f wide, AMAX and AMIN f wide (f = %d)" % f)
+        ldp = self.pna_panel_ld(f)
+        panel = torch.empty((max(n, 1), ldp), dtype=torch.float32, device=self.device)
+        check(lib.pgcn_aggpna_finish_f32(_ptr(S), max(S.stride(0), 4 * f), _ptr(deg), n, f, _ptr(dS), max(dS.stride(0), 4 * f), _ptr(AMAX),
+                                         max(AMAX.stride(0), f), _ptr(AMIN), max(AMIN.stride(0), f), panel.data_ptr(), ldp,
+                                         self._stream()), "pgcn_aggpna_finish_f32")
+        return panel
+
+    def aggpna_backward(self, AT: DeviceMaxCSR, row_gid: torch.Tensor, X: torch.Tensor, panel: torch.Tensor, D: torch.Tensor):
+        """D[r] = sum over the stored entries i of row r of the transposed structure of (P[i] + (AMAX[i] == row_gid[r] ? dMAX[i] : 0) +
+        (AMIN[i] == row_gid[r] ? dMIN[i] : 0)) + X[r] sum_i Q[i], element-wise (pgcn_aggpna_backward_csr_plan_f32): deterministic, D is
+        written.  ``panel``: ``aggpna_finish``'s, one row per column of ``AT``; ``X``: the rows of ``AT``."""
+        if AT.col is None:
+            raise _lib.PgcnError("aggpna_backward needs a structure made by prepare_max(csr) without col_gid")
+        self._pna_counts(row_gid, AT.nrows, "row_gid")
+        key = ("pna", X.stride(0), panel.stride(0), D.stride(0), D.shape[1])
+        fn = AT.launch_cache.get(key)
+        if fn is None:
+            f = D.shape[1]
+            ldp = self.pna_panel_ld(f)
+            self._max_operand(X, AT.nrows, torch.float32, "X")
+            self._max_operand(D, AT.nrows, torch.float32, "D")
+            if not (panel.is_cuda and panel.dtype is torch.float32 and panel.dim() == 2 and panel.is_contiguous() and
+                    panel.shape[1] == ldp and panel.shape[0] >= AT.ncols):
+                raise _lib.PgcnError("panel must be aggpna_finish's: contiguous, %d x %d floats" % (AT.ncols, ldp))
+            if X.shape[1] != f:
+                raise _lib.PgcnError("X and D widths differ")
+            ldx, ldd = max(X.stride(0), f), max(D.stride(0), f)
+            nrows = AT.nrows
+            if nrows == 0:
+                fn = lambda gid, X, panel, D: None
+            elif AT.nnz == 0:
+                fn = lambda gid, X, panel, D: D[:nrows].zero_()
+            else:
+                flags = self.base_flags | self._max_fpass(AT, f)
+                if (AT.ncols + 1) * ldp * 4 < 2 ** 32:
+                    flags |= _lib.SPMM_OFFSETS32
+                ws, ws_n = self._max_ws(AT, AT.nslots * f * 4)
+                lib, check, stream = self.lib, _lib.check, self._stream
+                rowptr, col, srow, tasks, ntasks, fix, nfix, nslots = (AT.rowptr.data_ptr(), AT.col.data_ptr(), _ptr(AT.slot_row),
+                                                                       _ptr(AT.tasks), AT.ntasks, _ptr(AT.fix), AT.nfix, AT.nslots)
+                seg, nslices = AT.seg, AT.nslices
+
+                def fn(gid, X, panel, D):
+                    check(lib.pgcn_aggpna_backward_csr_plan_f32(rowptr, col, gid.data_ptr(), srow, tasks, ntasks, seg, nslices, fix, nfix,
+                                                                X.data_ptr(), ldx, panel.data_ptr(), ldp, D.data_ptr(), ldd, f, ws,
+                                                                ws_n // 4, nslots, flags, stream()), "pgcn_aggpna_backward_csr_plan_f32")
+            AT.launch_cache[key] = fn
+        fn(row_gid, X, panel, D)
+        return D
+
+    def _pna_scalers(self, a, b, n):
+        for t, what in ((a, "a"), (b, "b")):
+            if not (t.is_cuda and t.dtype is torch.float32 and t.dim() == 1 and t.is_contiguous() and t.numel() >= n):
+                raise _lib.PgcnError("%s must be a contiguous float32 CUDA vector of at least %d entries" % (what, n))
+
+    def pna_scale(self, Y: torch.Tensor, a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
+        """Z[i] = Y[i, 0:fo] + a[i] Y[i, fo:2 fo] + b[i] Y[i, 2 fo:3 fo] (pgcn_pna_scale_forward_f32): the identity, amplification and
+        attenuation scalers applied to the layer's product."""
+        n, fo = Y.shape[0], Y.shape[1] // 3
+        if Y.shape[1] != 3 * fo or fo < 1 or fo > ROWBAND_MAX_F:
+            raise _lib.PgcnError("pna_scale: Y must be 3 fout wide with 1 <= fout <= %d, got %d columns" % (ROWBAND_MAX_F, Y.shape[1]))
+        self._max_operand(Y, n, torch.float32, "Y")
+        self._pna_scalers(a, b, n)
+        Z = torch.empty((n, fo), dtype=torch.float32, device=self.device)
+        _lib.check(self.lib.pgcn_pna_scale_forward_f32(_ptr(Y), max(Y.stride(0), 3 * fo), _ptr(a), _ptr(b), _ptr(Z), fo, n, fo,
+                                                       self._stream()), "pgcn_pna_scale_forward_f32")
+        return Z
+
+    def pna_scale_backward(self, G: torch.Tensor, a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
+        """dY = [G | a G | b G] (pgcn_pna_scale_backward_f32): the adjoint of ``pna_scale``."""
+        n, fo = G.shape
+        if fo < 1 or fo > ROWBAND_MAX_F:
+            raise _lib.PgcnError("pna_scale_backward: 1 <= fout <= %d, got %d" % (ROWBAND_MAX_F, fo))
+        self._max_operand(G, n, torch.float32, "G")
+        self._pna_scalers(a, b, n)
+        dY = torch.empty((n, 3 * fo), dtype=torch.float32, device=self.device)
+        _lib.check(self.lib.pgcn_pna_scale_backward_f32(_ptr(G), max(G.stride(0), fo), _ptr(a), _ptr(b), _ptr(dY), 3 * fo, n, fo,
+                                                        self._stream()), "pgcn_pna_scale_backward_f32")
+        return dY
+
     # -- DropEdge (pgcn_dropedge.hip) -----------------------------------------
     def _drop_structure(self, A: DeviceMaxCSR, row_gid: torch.Tensor, what: str):
         """What the drop kernels need of a ``prepare_max(csr, col_gid)`` structure: the pairs, and the row of every slot of a cut row
