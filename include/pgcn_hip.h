@@ -1179,6 +1179,32 @@ int pgcn_scatter_rows_f32(float *H, int64_t ldh, const int32_t *idx, int64_t nid
                           const float *in, int64_t ldi, int32_t f, int32_t accumulate,
                           pgcn_stream_t stream);
 
+/* ---- bf16 operands for the weighted-sum aggregation (csrc/pgcn_bf16.hip) ----
+ * C (+)= A . bf16(H) replaces torch.sparse.mm(A, H) at GPU/PGCN.py:127 and, with the CSR of A^T and bf16(G), torch.sparse.mm(A.t(), grad) at
+ * GPU/PGCN.py:132, for a caller that opts into a bf16 operand: stored values, sums, partial slots and C stay fp32.  bf16(.) is round to
+ * nearest even of the fp32 value in integer arithmetic, the bits of torch.Tensor.to(torch.bfloat16): a NaN becomes 0x7fc0, +-inf and +-0
+ * stay, a finite value above the largest bf16 becomes inf.  A bf16 matrix is uint16 words, row-major, 16-byte aligned, with a leading
+ * dimension that is a multiple of 8 (every row starts on 16 bytes) and at most 2^30.
+ * pgcn_cast_rows_bf16:   Y[r, c] = bf16(X[r, c]) for c < f, 0 for f <= c < ldy.  X: nrows x f fp32, leading dimension ldx >= f (float4
+ *   loads where X is 16-byte aligned and ldx % 4 == 0, words otherwise: the same bits); one 16-byte store per 8 columns.
+ * pgcn_gather_rows_bf16: out[r, .] = bf16(H[idx[r], .]), the same conversion for an index list (repeated and unordered indices allowed):
+ *   the boundary rows of fp32 H packed into a bf16 send slab in one pass (replaces H[indices], GPU/PGCN.py:104, under this option).
+ * pgcn_spmm_csr_plan_bf16: the arguments of pgcn_spmm_csr_plan_f32, except that B is bf16 (ldb in ELEMENTS) and the entries arrive as
+ *   pairs[nnz] of {col, fp32 bits of the value} (8-byte aligned; one load per entry).  tasks NULL: one task per row (ntasks = rows,
+ *   nslices = 1, no slots).  row_map, PGCN_SPMM_ACCUMULATE / _XCD_SWIZZLE / _OFFSETS32 (here: (max col + 1) * ldb * 2 < 2^32) / _NO_FIXUP /
+ *   _FPASS64, the XCD-sliced segments and the partial slots as there; cut rows are combined by pgcn_spmm_fixup_f32 in slot order.  Entries
+ *   are added in storage order with fp32 FMAs, no atomics: two calls give the same bits.  Any f >= 1; C and the work-space take float4
+ *   stores where they are 16-byte aligned with ldc % 4 == 0 and f % 4 == 0, guarded words otherwise (the same bits); nothing is written at
+ *   or beyond column f.  PGCN_EINVAL before any launch, the message naming the entry point: ldb % 8 != 0, ldb > 2^30, B not 16-byte
+ *   aligned, pairs not 8-byte aligned, bad sizes, null pointers.  Raw pointers + a stream, no allocation, no synchronisation.          */
+int pgcn_cast_rows_bf16(const float *X, int64_t ldx, int64_t nrows, int32_t f, uint16_t *Y, int64_t ldy, pgcn_stream_t stream);
+int pgcn_gather_rows_bf16(const float *H, int64_t ldh, const int32_t *idx, int64_t nidx, uint16_t *out, int64_t ldo, int32_t f,
+                          pgcn_stream_t stream);
+int pgcn_spmm_csr_plan_bf16(const int64_t *rowptr, const int32_t *pairs, const int32_t *tasks, int64_t ntasks, const int64_t *seg,
+                            int32_t nslices, const int32_t *fix, int64_t nfix, const int32_t *row_map, const uint16_t *B, int64_t ldb,
+                            float *C, int64_t ldc, int32_t f, float *partial_ws, int64_t partial_ws_elems, int64_t nslots, uint32_t flags,
+                            pgcn_stream_t stream);
+
 /* ---- boundary-row exchange over RCCL (xGMI) --------------------------------
  * One all-to-all-v: ncclGroupStart; ncclSend/ncclRecv per peer; ncclGroupEnd.
  * replaces the 2.(P-1) blocking dist.send / dist.recv of GPU/PGCN.py:99-115

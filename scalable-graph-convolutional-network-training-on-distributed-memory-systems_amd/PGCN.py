@@ -198,6 +198,40 @@ class PSpMM(torch.autograd.Function):
         return None, dH
 
 
+OPERANDS = ("fp32", "bf16")         # what --operand / run(operand=...) / PGCN(operand=...) take: the data type of the aggregation's operand
+
+
+class PSpMMBf16(torch.autograd.Function):
+    """``PSpMM`` with a bf16 operand (csrc/pgcn_bf16.hip): forward A_p . bf16(H), backward A_p^T . bf16(grad) -- the straight-through
+    adjoint, no gradient flows through the rounding.  Stored values, sums and results are fp32; the forward halo rows travel in bf16."""
+
+    @staticmethod
+    def forward(ctx, A, H):
+        ctx.A = A
+        return A.forward_bf16(H)
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        dH = ctx.A.backward_bf16(grad_output)
+        join = getattr(ctx.A, "join_wgrad", None)      # (the weight gradient parked on the side stream: PSpMM.backward's hand-over)
+        if join is not None:
+            join()
+        return None, dH
+
+
+def _check_operand(operand, aggr=None, softmax_beta=None, drop_edge=None, propagate=None, gpr=None):
+    """ValueError for an ``operand`` that no model can be built from: not one of OPERANDS, or "bf16" together with another aggregation
+    (``aggr`` max | pna, ``softmax_beta``, a positive ``drop_edge``) or a propagation of the logits (``propagate``, ``gpr``)."""
+    if operand not in OPERANDS + (None,):
+        raise ValueError("operand takes %s, got %r" % (" | ".join(OPERANDS), operand))
+    if operand != "bf16":
+        return
+    clash = ('aggr="%s"' % aggr if aggr in ("max", "pna") else "softmax_beta" if softmax_beta is not None
+             else "drop_edge" if drop_edge else "propagate" if propagate is not None else "gpr" if gpr is not None else None)
+    if clash is not None:
+        raise ValueError('operand="bf16" does not go with %s' % clash)
+
+
 ALL_AGGRS = ("sum", "max", "pna")   # what --aggr / run(aggr=...) / PGCN(aggr=...) take: the weighted sum A . H (the default), the
                                     # element-wise max, or the four aggregators and three degree scalers of PNA
 AGGRS = ALL_AGGRS[:2]               # COMPATIBILITY ONLY: the tuple earlier releases exported; nothing in the package reads it
@@ -1719,13 +1753,19 @@ class PGCN(nn.Module):
     ``softmax_beta=B`` (opt-in; a finite number >= 0, 0 included, no bool): the aggregation is ``PAggSoftmax`` -- per feature the
     softmax(B x)-weighted mean of the stored neighbourhood, stored values ignored -- instead of ``PSpMM``; every other option
     composes through the same nodes and the layer owns the same parameters under the same keys.  Refused with ``aggr="max"``,
-    ``aggregate=False`` and an active ``drop_edge``.  None: the branches of before."""
+    ``aggregate=False`` and an active ``drop_edge``.  None: the branches of before.
+
+    ``operand="bf16"`` (opt-in; OPERANDS): the aggregation is ``PSpMMBf16`` -- A . bf16(H) forward, A^T . bf16(G) backward, the gathered
+    rows and the forward halo exchange in bf16, everything else fp32 (csrc/pgcn_bf16.hip).  Not an architecture field: the layer owns
+    the same parameters, a checkpoint written under one operand type loads under the other.  Refused with ``aggr="max"`` / "pna",
+    ``softmax_beta`` and an active ``drop_edge``.  None or "fp32": the branches of before, call for call."""
 
     def __init__(self, A, in_features, out_features, dropout=0.0, layer=0, state=None, relu=True, norm=None, root_weight=False, bias=False,
-                 residual=False, aggr=None, aggregate=True, drop_edge=None, softmax_beta=None):
+                 residual=False, aggr=None, aggregate=True, drop_edge=None, softmax_beta=None, operand=None):
         super(PGCN, self).__init__()
         if aggr not in ALL_AGGRS + (None,):
             raise ValueError("aggr takes %s, got %r" % (" | ".join(ALL_AGGRS), aggr))
+        _check_operand(operand, aggr, softmax_beta, drop_edge is not None and drop_edge.on)
         self.aggregate = bool(aggregate)
         self.pna = aggr == "pna"
         if self.pna:
@@ -1750,6 +1790,8 @@ class PGCN(nn.Module):
         if softmax_beta is not None:
             self.softmax_beta = softmax_beta
             self._aggregate = self._aggregate_softmax
+        if operand == "bf16" and self.aggregate:       # (not an architecture field: the same parameters under the same keys)
+            self._aggregate = PSpMMBf16.apply
         # (PNA: 3 scalers x 4 aggregators x fin columns in PyG's order -- scaler-major, then aggregator, then feature)
         self.linear = nn.Linear(12 * in_features if self.pna else in_features, out_features, bias=False)
         self.A = A
@@ -2106,7 +2148,7 @@ OPTIMIZERS = _nodeloss.OPTIMIZERS      # --optimizer / run(optimizer=...): "torc
 def _train_on_data(A, n, nlayers, nfeatures, features, labels, split, hidden, epochs, lr, eval_every, dropout, dropout_seed,
                    multilabel=False, weight_decay=0.0, decoupled_decay=False, optimizer="torch", norm=None, root_weight=None, bias=None,
                    residual=None, save=None, load=None, predict=None, proba=None, control=None, aggr=None, propagate=None, ppr_alpha=None,
-                   dense_layers=None, drop_edge=None, softmax_beta=None, gpr=None, gpr_init=None, gpr_alpha=None):
+                   dense_layers=None, drop_edge=None, softmax_beta=None, gpr=None, gpr_init=None, gpr_alpha=None, operand=None):
     """The loop of ``run`` on real inputs: widths fin -> hidden -> ... -> C, no ReLU on the last layer, constant features (the
     first layer's backward aggregation is skipped), Adam, the masked loss over the train rows.  Reports every ``eval_every``
     epochs: without dropout from the record of the training step's own pass (the logits BEFORE that step's update), with
@@ -2136,7 +2178,9 @@ def _train_on_data(A, n, nlayers, nfeatures, features, labels, split, hidden, ep
     eval mode after the update.  ``Propagate`` keeps the undropped matrix.  ``softmax_beta=B``: every layer aggregates by the softmax
     aggregation (class PGCN, ``PAggSoftmax``); ``Propagate`` keeps ``PSpMM``.  None: the model of before.  ``gpr=K`` (``gpr_init``,
     ``gpr_alpha``): the module ``Gpr`` follows the last layer instead -- the K + 1 hop weights are a parameter, reduced, decayed and
-    stepped with the rest; rank 0 prints them after the last report."""
+    stepped with the rest; rank 0 prints them after the last report.  ``operand="bf16"``: every layer aggregates a bf16 operand (class
+    PGCN, ``PSpMMBf16``); not recorded in a checkpoint -- the weights are the same objects."""
+    _check_operand(operand, aggr, softmax_beta, drop_edge, propagate, gpr)
     _check_propagate(propagate, ppr_alpha, dense_layers, aggr, root_weight)
     _check_gpr(gpr, gpr_init, gpr_alpha, propagate)
     _check_drop_edge(drop_edge, getattr(A.part, "normalize", None), aggr, dense_layers)
@@ -2166,6 +2210,8 @@ def _train_on_data(A, n, nlayers, nfeatures, features, labels, split, hidden, ep
         extra["drop_edge"] = _dropout.EdgeDrop(drop_edge, state)       # one context: the layers of a step share the mask and its scales
     if softmax_beta is not None:
         extra["softmax_beta"] = softmax_beta
+    if operand == "bf16":
+        extra["operand"] = operand
     tail = [Propagate(A, propagate, PPR_ALPHA if ppr_alpha is None else float(ppr_alpha))] if propagate is not None else []
     if gpr is not None:
         tail = [Gpr(A, gpr, gpr_init or GPR_INITS[0], GPR_ALPHA if gpr_alpha is None else float(gpr_alpha))]
@@ -2241,7 +2287,7 @@ def run(rank, size, nlayers, nfeatures, path_A, path_partvec, backend, normalize
         features=None, labels=None, split=None, hidden=None, epochs=None, lr=None, eval_every=None, task=None,
         weight_decay=None, decoupled_decay=None, optimizer=None, norm=None, root_weight=None, bias=None, residual=None,
         save=None, load=None, predict=None, proba=None, aggr=None, propagate=None, ppr_alpha=None, dense_layers=None, drop_edge=None,
-        softmax_beta=None, gpr=None, gpr_init=None, gpr_alpha=None, **control):
+        softmax_beta=None, gpr=None, gpr_init=None, gpr_alpha=None, operand=None, **control):
     """PGCN.py:162-238.  ``normalize="sym"``: train on D_r^-1/2 (A + I) D_c^-1/2 of the pattern of ``path_A``, built on the fly
     (partition.build_partition) instead of by the offline pass preprocess/GrB-GNN-IDG.py.  ``dropout`` > 0: the output of every
     layer but the last is dropped with that probability (class PGCN), masks from (``dropout_seed``, step, layer, global row,
@@ -2292,7 +2338,11 @@ def run(rank, size, nlayers, nfeatures, path_A, path_partvec, backend, normalize
     LEARNED hop weights, OUT = sum_{k=0..K} gamma_k A^k H (GPR-GNN; ``Gpr``, csrc/pgcn_gpr.hip); ``gpr_init`` ("ppr", the default: APPNP's
     weights for ``gpr_alpha``, 0 <= alpha <= 1, default 0.1 -- the model starts as ``propagate=K``; or "uniform": 1 / (K + 1)); both need
     ``gpr``.  gamma is a parameter like the weights: it takes ``weight_decay`` too (no per-parameter groups).  A checkpoint records
-    K, the initialisation and alpha, and carries gamma; rank 0 prints the final gamma after the last report."""
+    K, the initialisation and alpha, and carries gamma; rank 0 prints the final gamma after the last report.
+    ``operand`` ("fp32", the default, or "bf16"; with or without the three files): every layer's aggregation reads its operand in bf16
+    -- A . bf16(H) forward, A^T . bf16(G) backward, the forward halo rows exchanged in bf16; stored values, sums, results and the dense
+    side stay fp32 (``PSpMMBf16``, csrc/pgcn_bf16.hip).  Not with ``aggr`` "max" / "pna", ``softmax_beta``, a positive ``drop_edge``,
+    ``propagate`` or ``gpr``.  A checkpoint does not record it: one written under either operand type loads under the other."""
     global myrank, world_size, send_map, recv_map, device, X, recv_buffers, send_buffers, stats
     for name in control:
         if name not in _nodeloss.CONTROL:
@@ -2326,6 +2376,7 @@ def run(rank, size, nlayers, nfeatures, path_A, path_partvec, backend, normalize
         raise ValueError("aggr takes %s, got %r" % (" | ".join(ALL_AGGRS), aggr))
     if aggr is not None and not all(given):
         raise ValueError("aggr=%r needs features, labels and split" % (aggr,))
+    _check_operand(operand, aggr, softmax_beta, drop_edge, propagate, gpr)
     _check_propagate(propagate, ppr_alpha, dense_layers, aggr, root_weight)
     if (propagate is not None or ppr_alpha is not None or dense_layers is not None) and not all(given):
         raise ValueError("propagate, ppr_alpha and dense_layers need features, labels and split")
@@ -2418,7 +2469,8 @@ def run(rank, size, nlayers, nfeatures, path_A, path_partvec, backend, normalize
                               **({"dense_layers": True} if dense_layers else {}),
                               **({"drop_edge": float(drop_edge)} if drop_edge else {}),
                               **({"softmax_beta": float(softmax_beta)} if softmax_beta is not None else {}),
-                              **{k: v for k, v in (("gpr", gpr), ("gpr_init", gpr_init), ("gpr_alpha", gpr_alpha)) if v is not None})
+                              **{k: v for k, v in (("gpr", gpr), ("gpr_init", gpr_init), ("gpr_alpha", gpr_alpha)) if v is not None},
+                              **({"operand": operand} if operand == "bf16" else {}))
 
     owned = A.part.owned.to(device)
     # PGCN.py:186-188 synthetic features H[i,:] = i, owned rows only
@@ -2428,13 +2480,14 @@ def run(rank, size, nlayers, nfeatures, path_A, path_partvec, backend, normalize
 
     tune_dense_gemms(A.part.n_local, nfeatures, device)
     _dropout.threshold(dropout)
+    op = {"operand": operand} if operand == "bf16" else {}      # (not given: the calls of before)
     if dropout > 0.0:
         state = _dropout.DropoutState(dropout_seed, device)
-        model = nn.Sequential(*[PGCN(A, nfeatures, nfeatures, dropout=dropout if i < nlayers - 1 else 0.0, layer=i, state=state)
+        model = nn.Sequential(*[PGCN(A, nfeatures, nfeatures, dropout=dropout if i < nlayers - 1 else 0.0, layer=i, state=state, **op)
                                 for i in range(nlayers)])
     else:
         state = None
-        model = nn.Sequential(*[PGCN(A, nfeatures, nfeatures) for _ in range(nlayers)])
+        model = nn.Sequential(*[PGCN(A, nfeatures, nfeatures, **op) for _ in range(nlayers)])
     model = model.to(device)
     initiliaze_parameters(model)
     optimizer = torch.optim.Adam(model.parameters(), lr=1e-3)
@@ -2495,9 +2548,9 @@ def init_process(rank, size, fn, nlayers, nfeatures, path_A, path_partvec, backe
                  features=None, labels=None, split=None, hidden=None, epochs=None, lr=None, eval_every=None, task=None,
                  weight_decay=None, decoupled_decay=None, optimizer=None, norm=None, root_weight=None, bias=None, residual=None,
                  save=None, load=None, predict=None, proba=None, control=None, aggr=None, propagate=None, ppr_alpha=None, dense_layers=None,
-                 drop_edge=None, softmax_beta=None, gpr=None, gpr_init=None, gpr_alpha=None):
+                 drop_edge=None, softmax_beta=None, gpr=None, gpr_init=None, gpr_alpha=None, operand=None):
     """PGCN.py:241-253.  ``control``: the given options of nodeloss.CONTROL as one dict (None: today's call).  ``aggr``, ``propagate``,
-    ``ppr_alpha``, ``dense_layers``, ``drop_edge``, ``softmax_beta``, ``gpr``, ``gpr_init``, ``gpr_alpha``: run's."""
+    ``ppr_alpha``, ``dense_layers``, ``drop_edge``, ``softmax_beta``, ``gpr``, ``gpr_init``, ``gpr_alpha``, ``operand``: run's."""
     global _exchanger
     dist.init_process_group(backend, rank=rank, world_size=size)
 
@@ -2519,7 +2572,8 @@ def init_process(rank, size, fn, nlayers, nfeatures, path_A, path_partvec, backe
                     ("optimizer", optimizer), ("norm", norm), ("root_weight", root_weight), ("bias", bias),
                     ("residual", residual), ("save", save), ("load", load), ("predict", predict), ("proba", proba), ("aggr", aggr),
                     ("propagate", propagate), ("ppr_alpha", ppr_alpha), ("dense_layers", dense_layers),
-                    ("softmax_beta", softmax_beta), ("gpr", gpr), ("gpr_init", gpr_init), ("gpr_alpha", gpr_alpha)):
+                    ("softmax_beta", softmax_beta), ("gpr", gpr), ("gpr_init", gpr_init), ("gpr_alpha", gpr_alpha),
+                    ("operand", operand)):
         if v is not None:
             kw[name] = v
     kw.update(control or {})
@@ -2541,12 +2595,13 @@ def main(argv):
     os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
     os.environ.setdefault("MASTER_PORT", "29500")
     backend, nlayers, nfeatures, normalize, dropout, dropout_seed = "nccl", 3, 128, None, 0.0, 0
+    operand = None     # --operand bf16 (it needs no data files: kept beside ``data``)
     data = {}          # the node-classification options that were given (run's keyword arguments)
     try:
         opts, args = getopt.getopt(argv, "a:p:b:s:l:f:", ["normalize=", "dropout=", "dropout-seed=", "features=", "labels=", "split=",
                                                           "hidden=", "epochs=", "lr=", "eval-every=", "task=", "weight-decay=", "adamw",
                                                           "optimizer=", "norm=", "root-weight", "bias", "residual", "save=", "load=",
-                                                          "predict=", "proba", "aggr=", "propagate=", "ppr-alpha=", "dense-layers", "drop-edge=", "softmax-aggr=", "gpr=", "gpr-init=", "gpr-alpha="] + [f[2:] + "=" for f in _nodeloss.CONTROL_FLAGS.split(", ")])
+                                                          "predict=", "proba", "aggr=", "propagate=", "ppr-alpha=", "dense-layers", "drop-edge=", "softmax-aggr=", "gpr=", "gpr-init=", "gpr-alpha=", "operand="] + [f[2:] + "=" for f in _nodeloss.CONTROL_FLAGS.split(", ")])
     except getopt.GetoptError:
         print("a:p:b:", flush=True)
         sys.exit(2)
@@ -2674,6 +2729,11 @@ def main(argv):
             except ValueError:
                 print("--softmax-aggr takes a finite number >= 0, got %r" % arg, flush=True)
                 sys.exit(2)
+        elif opt == '--operand':       # fp32 (the default) | bf16 (the aggregation reads its operand in bf16: PSpMMBf16) -- every layer
+            if arg not in OPERANDS:
+                print("--operand takes %s, got %r" % ("|".join(OPERANDS), arg), flush=True)
+                sys.exit(2)
+            operand = arg if arg != "fp32" else None
         elif opt == '--root-weight':   # every layer adds H . W_r^T: a vertex's own features get their own weights (class PGCN)
             data["root_weight"] = True
         elif opt == '--bias':          # every layer adds a bias (a normalised layer keeps bn_bias alone)
@@ -2743,6 +2803,13 @@ def main(argv):
         if clash:
             print("--softmax-aggr does not go with %s" % clash, flush=True)
             sys.exit(2)
+    if operand == "bf16":
+        clash = ("--aggr %s" % data["aggr"] if data.get("aggr") in ("max", "pna") else "--softmax-aggr" if "softmax_beta" in data
+                 else "--drop-edge" if data.get("drop_edge", 0.0) > 0.0 else "--propagate" if "propagate" in data
+                 else "--gpr" if "gpr" in data else None)
+        if clash:
+            print("--operand bf16 does not go with %s" % clash, flush=True)
+            sys.exit(2)
     if "load" in data and not os.path.exists(data["load"]):
         print("--load: no such file %r" % (data["load"],), flush=True)
         sys.exit(2)
@@ -2780,6 +2847,8 @@ def main(argv):
             if has_residual:                   # (the tuple grows only when --residual is given)
                 args += (True,)
     named = {k: data[k] for k in ("aggr", "propagate", "ppr_alpha", "dense_layers", "drop_edge", "softmax_beta", "gpr", "gpr_init", "gpr_alpha") if k in data}      # (by name, only when given)
+    if operand is not None:
+        named["operand"] = operand
     p = mp.Process(target=init_process, args=args, **({"kwargs": named} if named else {}))
     p.start()
     p.join()

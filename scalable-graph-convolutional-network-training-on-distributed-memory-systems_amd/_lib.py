@@ -197,6 +197,11 @@ SIGNATURES = {
     "pgcn_predict_f32": (ctypes.c_int, [_vp, _i64, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _i64, _vp]),
     "pgcn_gather_rows_f32": (ctypes.c_int, [_vp, _i64, _vp, _i64, _vp, _i64, _i32, _vp]),
     "pgcn_scatter_rows_f32": (ctypes.c_int, [_vp, _i64, _vp, _i64, _vp, _i64, _i32, _i32, _vp]),
+    # bf16 operands (csrc/pgcn_bf16.hip): the cast, the boundary-row pack and the gather kernel over {col, value bits} pairs
+    "pgcn_cast_rows_bf16": (ctypes.c_int, [_vp, _i64, _i64, _i32, _vp, _i64, _vp]),
+    "pgcn_gather_rows_bf16": (ctypes.c_int, [_vp, _i64, _vp, _i64, _vp, _i64, _i32, _vp]),
+    "pgcn_spmm_csr_plan_bf16": (ctypes.c_int, [_vp, _vp, _vp, _i64, _vp, _i32, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _i32, _vp, _i64,
+                                               _i64, _u32, _vp]),
     "pgcn_comm_unique_id": (ctypes.c_int, [_vp]),
     "pgcn_comm_init": (ctypes.c_int, [ctypes.POINTER(_vp), _vp, _i32, _i32]),
     "pgcn_comm_destroy": (ctypes.c_int, [_vp]),

@@ -714,6 +714,22 @@ class MaxStructures:
     halo_global: torch.Tensor
 
 
+@dataclasses.dataclass
+class Bf16Structures:
+    """What ``AggregationEngine.forward_bf16`` / ``backward_bf16`` run on, built at the first call: the whole of every block as
+    kernels.DeviceBf16CSR -- or nothing on the composed route, which rounds the operand and calls ``forward`` / ``backward``."""
+    composed: bool
+    loc: object = None
+    halo: list = dataclasses.field(default_factory=list)
+    loc_T: object = None
+    halo_T: list = dataclasses.field(default_factory=list)
+
+
+def round_bf16(X: torch.Tensor) -> torch.Tensor:
+    """bf16(X) as fp32: round to nearest even, the definition the kernels of csrc/pgcn_bf16.hip match bit for bit."""
+    return X.to(torch.bfloat16).to(torch.float32)
+
+
 # --------------------------------------------------------------------------
 # DropEdge: the composed route (framework operations + the numpy keep function; the definitions of csrc/pgcn_dropedge.hip)
 
@@ -885,6 +901,7 @@ class AggregationEngine(BoundaryExchange):
         self._max: Optional[MaxStructures] = None      # the max aggregation's structures, built at the first forward_max / backward_max
         self._pna: Optional[PnaDegrees] = None         # PNA's degrees and scalers, built at the first pna_degrees
         self._drop: Optional[DropEdgeStructures] = None    # DropEdge's structures, built at the first forward_drop / drop_refresh
+        self._bf16: Optional[Bf16Structures] = None        # the bf16-operand structures, built at the first forward_bf16 / backward_bf16
         self.reuse_operand = bool(_T.reuse_operand)     # forward_reusing may keep the aggregation of an unchanged operand ...
         self.reuse_max_bytes = int(_T.reuse_max_bytes)  # ... whose copy and result fit in this
         self._reuse: Optional[ReuseRecord] = None       # the operand forward_reusing follows: a candidate, or armed (ref and C kept)
@@ -1047,6 +1064,94 @@ class AggregationEngine(BoundaryExchange):
             # dH[row] += the partial rows that came back for it in this round: one pattern SpMM
             # (deterministic; the reference ASSIGNS here and loses partials for P >= 3, quirk Q3)
             self.k.spmm(self.unpack[r], back, dH, accumulate=True)
+        return dH
+
+    # ------------------------------------------------------------------
+    # bf16 operands (csrc/pgcn_bf16.hip): AH = A . bf16(H), dH = A^T . bf16(G) -- the gathered rows and the forward
+    # halo exchange in bf16, stored values, sums, the partial rows that travel home and every result in fp32
+    BF16_KERNELS = ("prepare_bf16", "cast_rows_bf16", "gather_rows_bf16", "spmm_bf16")
+
+    def _bf16_structures(self) -> Bf16Structures:
+        """Built once, at the first bf16 call: an engine that never uses the option holds nothing new.  The route is chosen here, before
+        the first launch: the provider's kernels on a HIP device, else the composed route -- the operand rounded by the framework, then
+        ``forward`` / ``backward`` (the same definition; what CPU and gloo runs compute)."""
+        if self._bf16 is None:
+            part, k = self.part, self.k
+            if not (self.on_gpu and all(hasattr(k, m) for m in self.BF16_KERNELS)):
+                self._bf16 = Bf16Structures(True)
+            else:
+                loc_T = None if part.A_loc_T is None else k.prepare_bf16(part.A_loc_T)
+                self._bf16 = Bf16Structures(False, k.prepare_bf16(part.A_loc), [k.prepare_bf16(a) for a in part.A_halo], loc_T,
+                                            [k.prepare_bf16(a) for a in part.A_halo_T])
+        return self._bf16
+
+    def _slab_bf16(self, name: str, rows: int, ld: int) -> torch.Tensor:
+        key = (name, ld, "bf16")
+        t = self._buf.get(key)
+        if t is None or t.shape[0] < rows:
+            t = torch.zeros((max(rows, 1), ld), dtype=torch.bfloat16, device=self.device)
+            self._buf[key] = t
+        return t
+
+    def forward_bf16(self, H: torch.Tensor) -> torch.Tensor:
+        """AH = A_p . bf16([H ; halo])   (H: n_local x f fp32, owned rows only; the result is fp32)."""
+        if H.shape[0] != self.n_local:
+            raise ValueError("H must hold exactly the %d owned rows" % self.n_local)
+        m = self._bf16_structures()
+        if m.composed:
+            return self.forward(round_bf16(H))
+        k = self.k
+        H = H.contiguous()
+        f = H.shape[1]
+        C = torch.empty((self.n_local, f), dtype=torch.float32, device=self.device)
+        if self.size == 1:
+            return k.spmm_bf16(m.loc, k.cast_rows_bf16(H), C)
+        ld = (f + 7) // 8 * 8
+        send = self._slab_bf16("send", self.n_send, ld)
+        halo = self._slab_bf16("halo", self.n_halo, ld)
+        k.gather_rows_bf16(H, self.send_idx, send)      # one pass over fp32 H: cast and pack
+        # the slabs travel as float32 rows of width ld / 2: the same bytes, the exchange of before
+        waits = self._exchange_all(send.view(torch.float32), self.round_send_off, halo.view(torch.float32), self.round_recv_off, ld // 2,
+                                   tag="forward")
+        k.spmm_bf16(m.loc, k.cast_rows_bf16(H), C)      # the cast of the owned rows and the local gather overlap the exchange
+        for r in range(self.rounds):
+            waits[r]()
+            k.spmm_bf16(m.halo[r], halo[:, :f], C, accumulate=True)
+        return C
+
+    def backward_bf16(self, G: torch.Tensor) -> torch.Tensor:
+        """dH = (A^T . bf16(G))[owned rows]: the straight-through adjoint of ``forward_bf16``.  The partial rows for peers are fp32 sums:
+        they travel home and are ADDED as in ``backward``."""
+        if self.A_loc_T is None:
+            raise RuntimeError("partition was built without the transposed pieces")
+        if G.shape[0] != self.n_local:
+            raise ValueError("G must hold exactly the %d owned rows" % self.n_local)
+        m = self._bf16_structures()
+        if m.composed:
+            return self.backward(round_bf16(G))
+        k = self.k
+        G = G.contiguous()
+        f = G.shape[1]
+        dH = torch.empty((self.n_local, f), dtype=torch.float32, device=self.device)
+        Gb = k.cast_rows_bf16(G)
+        if self.size == 1:
+            return k.spmm_bf16(m.loc_T, Gb, dH)
+        partial = self._slab("halo", self.n_halo, f)
+        back = self._slab("send", self.n_send, f)
+        ready = []
+        for r in range(self.rounds):
+            b0, b1 = self.round_recv_off[r][0], self.round_recv_off[r][-1]
+            k.spmm_bf16(m.halo_T[r], Gb, partial[b0:b1])
+            if self.overlap:
+                ev = torch.cuda.Event()
+                ev.record(torch.cuda.current_stream(self.device))
+                ready.append(ev)
+        waits = self._exchange_all(partial, self.round_recv_off, back, self.round_send_off, f,
+                                   ready if self.overlap else None, tag="backward")
+        k.spmm_bf16(m.loc_T, Gb, dH)
+        for r in range(self.rounds):
+            waits[r]()
+            k.spmm(self.unpack[r], back, dH, accumulate=True)      # returned rows are sums: backward's unpack
         return dH
 
     def forward_symmetric_backward(self, G: torch.Tensor) -> torch.Tensor:
@@ -1584,4 +1689,16 @@ class AggregationEngine(BoundaryExchange):
         if self.size > 1:
             b += sum(8 * a.nnz + 8 * (a.nrows + 1) for a in self.A_halo) + 4 * f * self.n_halo
             b += 2 * 4 * f * self.n_send   # pack: read rows + write slab
+        return b
+
+    def alg_bytes_forward_bf16(self, f: int) -> int:
+        """Compulsory HBM bytes of one ``forward_bf16`` gather on this rank: 8.nnz + 8.(nrows+1) + 2.ld.(cols) + 4.f.(rows) with ld the
+        16-byte padded width -- the cast that produces the bf16 operand is a pass of its own and not counted, as the fp32 figure counts
+        no producer of H."""
+        ld = (f + 7) // 8 * 8
+        a = self.part.A_loc
+        b = 8 * a.nnz + 8 * (self.n_local + 1) + 2 * ld * a.ncols + 4 * f * self.n_local
+        if self.size > 1:
+            b += sum(8 * h.nnz + 8 * (h.nrows + 1) for h in self.part.A_halo) + 2 * ld * self.n_halo
+            b += (4 * f + 2 * ld) * self.n_send   # pack: read fp32 rows + write the bf16 slab
         return b

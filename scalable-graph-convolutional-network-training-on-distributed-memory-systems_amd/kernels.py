@@ -170,6 +170,40 @@ class DeviceMaxCSR:
         return 8 * self.nnz + 8 * (self.nrows + 1) + 4 * f * self.ncols + 2 * 4 * f * self.nrows
 
 
+@dataclass
+class DeviceBf16CSR:
+    """The WHOLE block as plain CSR with stored values for a bf16 operand (pgcn_bf16.hip; ``HipKernels.prepare_bf16``): the entries as
+    interleaved {col, fp32 bits of the value} pairs, and its plan -- unsliced, or XCD-sliced with every row's entries grouped by
+    col % nslices.  One more 8 B-per-entry copy of the structure beside the sum path's."""
+    nrows: int
+    ncols: int
+    nnz: int
+    rowptr: torch.Tensor                    # int64 [nrows + 1]
+    pairs: torch.Tensor                     # int32 [nnz, 2] {col, value bits}
+    row_map: Optional[torch.Tensor] = None  # int32 [nrows] output row of every CSR row (None: the row itself)
+    out_rows: int = 0                       # rows C must hold: nrows, or the largest mapped row + 1
+    tasks: Optional[torch.Tensor] = None    # int32 [ntasks, 4] (None: one task per row)
+    fix: Optional[torch.Tensor] = None      # int32 [nfix, 4]
+    ntasks: int = 0
+    nfix: int = 0
+    nslots: int = 0
+    nslices: int = 1
+    seg: Optional[object] = None            # ctypes int64[nslices + 1] (host): task segment bounds of a sliced plan
+    ws: Optional[torch.Tensor] = None       # fp32 work-space of the cut rows (grown on demand)
+    retired_ws: list = field(default_factory=list)
+    launch_cache: dict = field(default_factory=dict)
+
+    def alg_bytes(self, f: int) -> int:
+        """Compulsory HBM bytes of one launch: 8 B per entry, the row pointers, every bf16 operand row once (16-byte padded), the
+        fp32 rows written."""
+        return 8 * self.nnz + 8 * (self.nrows + 1) + 2 * bf16_ld(f) * self.ncols + 4 * f * self.nrows
+
+
+def bf16_ld(f: int) -> int:
+    """Leading dimension of a bf16 matrix of width f: every row starts on 16 bytes."""
+    return (int(f) + 7) // 8 * 8
+
+
 def build_plan(rowptr_host: np.ndarray, chunk: int, slice_cnt: Optional[np.ndarray] = None,
                small_row: int = DEFAULT_SMALL_ROW, force: bool = False,
                row_flags: Optional[np.ndarray] = None, ngroups: int = 1,
@@ -861,6 +895,128 @@ class HipKernels:
             AT.launch_cache[key] = fn
         fn(row_gid, G, ARG, D)
         return D
+
+    # -- bf16 operands of the weighted sum (pgcn_bf16.hip) ---------------------
+    def prepare_bf16(self, csr: HostCSR, chunk: Optional[int] = None, nslices: Optional[int] = None) -> DeviceBf16CSR:
+        """The whole block of ``csr`` (partition.full_csr: the strips, core tiles and bf16x3 blocks read fp32 operands and take no part)
+        as plain CSR with stored values -- a value-free structure's are the ones ``full_csr`` materialises -- in {col, value bits}
+        pairs.  A structure with a ``row_map`` keeps exactly its rows, compact, with the map.  ``chunk``: entries per task of a long row
+        (tuning.bf16_chunk); ``nslices``: 1 = unsliced, 8 = XCD-sliced (entries of a row grouped by col % nslices, columns ascending
+        inside a group); None: partition.pick_nslices."""
+        from .partition import full_csr, pick_nslices
+        dev = self.device
+        rowptr, col, val = full_csr(csr)
+        S = pick_nslices(csr.ncols) if nslices is None else int(nslices)
+        if not 1 <= S <= _lib.MAX_SLICES:
+            raise _lib.PgcnError("prepare_bf16: nslices must lie in 1 .. %d, got %d" % (_lib.MAX_SLICES, S))
+        lens = rowptr[1:] - rowptr[:-1]
+        row_map = None
+        if csr.row_map is not None:             # (entries stay in place: only rows outside the map, all empty, leave the row pointers)
+            rows = torch.unique(csr.row_map.to(rowptr.device, torch.int64))
+            lens, row_map = lens[rows], rows.to(torch.int32)
+            rowptr = torch.cat([torch.zeros(1, dtype=torch.int64, device=lens.device), torch.cumsum(lens, 0)])
+        nrows, nnz = int(lens.numel()), int(col.numel())
+        slice_cnt = None
+        if nrows and nnz and S > 1:
+            key = torch.repeat_interleave(torch.arange(nrows, device=col.device), lens) * S + col.to(torch.int64) % S
+            slice_cnt = torch.bincount(key, minlength=nrows * S).view(nrows, S).to(torch.int32).cpu().numpy()
+            order = torch.argsort(key, stable=True)
+            col, val = col[order], val[order]
+            del key, order
+        top = _T.bf16_chunk if chunk is None else int(chunk)
+        if top < 1:
+            raise _lib.PgcnError("prepare_bf16: chunk must be >= 1, got %d" % top)
+        chunk = top
+        if self.adaptive_chunk:
+            e = max(nnz, 1) // 8192
+            chunk = min(top, max(64, 1 << max(e.bit_length() - 1, 0)))
+        rowptr = rowptr.cpu()
+        tasks, fix, nslots, seg = None, None, 0, None
+        if nrows:
+            tasks, fix, nslots, seg = build_plan(rowptr.numpy(), chunk, slice_cnt, self.small_row)
+        pairs = torch.stack([col.cpu().to(torch.int32), val.cpu().to(torch.float32).contiguous().view(torch.int32)], 1).contiguous()
+        d = DeviceBf16CSR(nrows=nrows, ncols=csr.ncols, nnz=nnz, rowptr=rowptr.to(dev, torch.int64).contiguous(), pairs=pairs.to(dev),
+                          row_map=None if row_map is None else row_map.to(dev).contiguous(), ntasks=nrows,
+                          out_rows=nrows if row_map is None else (int(row_map.max()) + 1 if nrows else 0))
+        if tasks is not None:
+            d.tasks = torch.from_numpy(tasks).to(dev)
+            d.fix = torch.from_numpy(np.ascontiguousarray(fix)).to(dev) if fix.shape[0] else None
+            d.ntasks, d.nfix, d.nslots = tasks.shape[0], fix.shape[0], nslots
+            if slice_cnt is not None:
+                d.nslices, d.seg = S, seg
+        return d
+
+    def _bf16_out(self, out: Optional[torch.Tensor], rows: int, f: int, what: str) -> torch.Tensor:
+        """The bf16 matrix a cast writes: ``out`` (rows padded to a multiple of 8 columns, 16-byte aligned), or a new one."""
+        if out is None:
+            return torch.empty((rows, bf16_ld(f)), dtype=torch.bfloat16, device=self.device)
+        self._max_operand(out, rows, torch.bfloat16, what)
+        if out.shape[1] < f or out.stride(0) % 8 or out.stride(0) < bf16_ld(f) or out.data_ptr() % 16:
+            raise _lib.PgcnError("%s must be a 16-byte aligned bf16 matrix of at least %d columns whose rows start 16 bytes apart" % (what, f))
+        return out
+
+    def cast_rows_bf16(self, X: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """bf16(X) (pgcn_cast_rows_bf16) as an n x f view of a matrix whose rows are padded with zeros to a multiple of 8 columns."""
+        self._max_operand(X, 0, torch.float32, "X")
+        n, f = X.shape
+        Y = self._bf16_out(out, n, f, "out")
+        _lib.check(self.lib.pgcn_cast_rows_bf16(X.data_ptr() if n else None, max(X.stride(0), f), n, f, Y.data_ptr() if n else None,
+                                                max(Y.stride(0), bf16_ld(f)), self._stream()), "pgcn_cast_rows_bf16")
+        return Y[:n, :f]
+
+    def gather_rows_bf16(self, H: torch.Tensor, idx: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
+        """out[r] = bf16(H[idx[r]]) (pgcn_gather_rows_bf16): the boundary rows of fp32 H packed into a bf16 slab in one pass."""
+        self._max_operand(H, 0, torch.float32, "H")
+        if not (idx.is_cuda and idx.dtype is torch.int32 and idx.dim() == 1 and idx.is_contiguous()):
+            raise _lib.PgcnError("idx must be a contiguous int32 CUDA vector")
+        n, f = idx.numel(), H.shape[1]
+        Y = self._bf16_out(out, n, f, "out")
+        _lib.check(self.lib.pgcn_gather_rows_bf16(H.data_ptr() if H.shape[0] else None, max(H.stride(0), f), idx.data_ptr() if n else None, n,
+                                                  Y.data_ptr() if n else None, max(Y.stride(0), bf16_ld(f)), f, self._stream()),
+                   "pgcn_gather_rows_bf16")
+        return Y[:n, :f]
+
+    def spmm_bf16(self, A: DeviceBf16CSR, Bb: torch.Tensor, C: torch.Tensor, accumulate: bool = False) -> torch.Tensor:
+        """C (+)= A . Bb with Bb a bf16 matrix (what ``cast_rows_bf16`` returns) and everything else fp32 (pgcn_spmm_csr_plan_bf16) on the
+        current stream; C rows are addressed through A.row_map if set.  Bound once per shape like ``spmm``."""
+        key = (Bb.stride(0), C.stride(0), Bb.shape[1], bool(accumulate))
+        fn = A.launch_cache.get(key)
+        if fn is None:
+            f = Bb.shape[1]
+            self._max_operand(Bb, A.ncols, torch.bfloat16, "Bb")
+            self._max_operand(C, A.out_rows, torch.float32, "C")
+            if C.shape[1] != f:
+                raise _lib.PgcnError("Bb and C widths differ")
+            ldb = Bb.stride(0) if Bb.shape[0] > 1 else bf16_ld(f)       # (the row stride of a single row is never used)
+            ldc = max(C.stride(0), f)
+            nrows, rmap = A.nrows, A.row_map
+            if nrows == 0 or (A.nnz == 0 and accumulate):
+                fn = lambda Bb, C: None
+            elif A.nnz == 0:            # nothing to launch: every row is empty (a memset, plumbing)
+                rows = None if rmap is None else rmap.long()
+                fn = (lambda Bb, C: C[:nrows].zero_()) if rows is None else (lambda Bb, C: C.index_fill_(0, rows, 0.0))
+            else:
+                flags = self.base_flags | (_lib.SPMM_ACCUMULATE if accumulate else 0) | self._max_fpass(A, f)
+                if (A.ncols + 1) * ldb * 2 < 2 ** 32:
+                    flags |= _lib.SPMM_OFFSETS32
+                need = A.nslots * f
+                if need and (A.ws is None or A.ws.numel() < need):
+                    if A.ws is not None:
+                        A.retired_ws.append(A.ws)           # (a binding made earlier still launches into it)
+                    A.ws = torch.empty(need, dtype=torch.float32, device=self.device)
+                    A.launch_cache.clear()
+                ws, ws_n = _ptr(A.ws), (0 if A.ws is None else A.ws.numel())
+                lib, check, stream = self.lib, _lib.check, self._stream
+                rowptr, pairs, tasks, ntasks, fix, nfix, nslots = (A.rowptr.data_ptr(), A.pairs.data_ptr(), _ptr(A.tasks), A.ntasks,
+                                                                   _ptr(A.fix), A.nfix, A.nslots)
+                seg, nslices, rm = A.seg, A.nslices, _ptr(rmap)
+
+                def fn(Bb, C):
+                    check(lib.pgcn_spmm_csr_plan_bf16(rowptr, pairs, tasks, ntasks, seg, nslices, fix, nfix, rm, Bb.data_ptr(), ldb,
+                                                      C.data_ptr(), ldc, f, ws, ws_n, nslots, flags, stream()), "pgcn_spmm_csr_plan_bf16")
+            A.launch_cache[key] = fn
+        fn(Bb, C)
+        return C
 
     # -- softmax aggregation (pgcn_aggsoftmax.hip) ----------------------------
     @staticmethod

@@ -31,6 +31,8 @@ class Tuning:
     xcd_swizzle: bool = True         # unsliced plans: one contiguous row range per XCD
     aggmax_chunk: int = 1024         # max aggregation (pgcn_aggmax.hip): entries per task of a long row of its plain, unsliced plans (forward and
                                      # transposed), shrunk on small blocks like spmm_chunk; not swept yet: the sum path's value
+    bf16_chunk: int = 1024           # bf16 operands (pgcn_bf16.hip): entries per task of a long row of the whole-block plans, shrunk on small
+                                     # blocks like spmm_chunk; not swept yet: the sum path's value
     # ---- XCD-sliced storage ---------------------------------------------------------------------------------
     slices: int = 8                  # = XCDs of an MI355X
     slice_min_cols: int = 16384      # narrower operands fit one L2: stored unsliced
