@@ -472,6 +472,47 @@ int pgcn_pna_scale_forward_f32(const float *Y, int64_t ldy, const float *a, cons
 int pgcn_pna_scale_backward_f32(const float *G, int64_t ldg, const float *a, const float *b, float *dY, int64_t ldy, int64_t nrows,
                                 int32_t fout, pgcn_stream_t stream);
 
+/* ---- GATED aggregation (GatedGCN, Bresson & Laurent 2017; Dwivedi et al., "Benchmarking GNNs"; PyG's ResGatedGraphConv is the
+ * un-normalised form; no counterpart in the reference): a gate per FEATURE that depends on both ends of a stored entry (i, j), stored
+ * values ignored.  K / Q / V: the key, query and value projections (K of the structure's rows, QV = [Q | V] of its columns, 2 f wide):
+ *   g_ij,c = 1 / (1 + exp(-(K[i, c] + Q[j, c])))        (the argument clamped to [-80, 80]; 1 - g is formed as exp(-x) g)
+ *   NUM[i, c] = sum_j g_ij,c V[j, c]    DEN[i, c] = sum_j g_ij,c    Z1 = NUM / (DEN + 1e-6f)    a row without entries: 0.0f
+ *   backward, G = dZ1, P = G / (DEN + 1e-6f), O = Z1:   t_ij = P_i (V_j - O_i) g_ij (1 - g_ij)
+ *   dK_i = sum_j t_ij        dQ_j = sum_i t_ij        dV_j = sum_i g_ij P_i
+ * The gates are recomputed inside the gathers, never stored.  Every sum is fp32 in storage order, the pieces of a cut row added in slot
+ * order (pgcn_spmm_fixup_f32): no atomics, two calls give the same bits.  rowptr / tasks / seg / nslices / fix / nslots: a structure and
+ * plan as pgcn_aggmax_csr_plan_f32 takes them; slot_row[nslots]: the row of every slot (required when nslots > 0); ncols: the rows of
+ * the gathered operand.  flags: PGCN_SPMM_ACCUMULATE (rows kernels), _XCD_SWIZZLE, _OFFSETS32 (every row offset ncols x ld x 4 of the
+ * gathered operand fits 32 bits), _FPASS64.  Any f >= 1; a float4 body when f % 4 == 0 with 16-byte aligned bases and leading dimensions
+ * % 4 == 0, a guarded scalar body otherwise, the same bits.  PGCN_EINVAL before any launch on null pointers, f < 1, a leading dimension
+ * below the width read, or offsets beyond 32 bits under _OFFSETS32; a structure without rows returns at once.
+ *
+ * pgcn_agggated_csr_plan_f32 (FORWARD structure, pairs): NUM and DEN -- written, or added to under PGCN_SPMM_ACCUMULATE (the state is
+ * additive: that is how several structures join).  K (ldk >= f), QV (ldqv >= 2 f), NUM, DEN take a leading dimension each: K and QV may
+ * be column slices of one n x 3 f product.  ws: 2 x nslots x f floats.
+ * pgcn_agggated_finish_f32 (row-band kernel, f <= 1024).  G == NULL: Z = Z / (DEN + 1e-6f) in place (NUM -> Z1).  G = dZ1: Z holds Z1,
+ *   read only; the PANEL of the backward is written: row i holds three planes of fp = 4 ceil(f / 4) words, {K | P | O} at
+ *   panel[i * ldp + k fp], ldp >= 3 fp, ldp % 4 == 0, panel 16-byte aligned; features beyond f hold 0.
+ * pgcn_agggated_grad_rows_f32 (FORWARD structure, pairs; panel of the structure's rows): dK (+)= sum_j t_ij; ws: nslots x f floats.
+ * pgcn_agggated_grad_cols_f32 (TRANSPOSED structure, col; QV of the structure's rows, the panel indexed by the stored entries):
+ *   D = [dQ | dV] (ldd >= 2 f), written, never accumulated into; ws: 2 x nslots x f floats.
+ * Inputs are finite by contract.  Plain vector loads and stores only.                                                                */
+int pgcn_agggated_csr_plan_f32(const int64_t *rowptr, const int32_t *pairs, const int32_t *slot_row, const int32_t *tasks,
+                               int64_t ntasks, const int64_t *seg, int32_t nslices, const int32_t *fix, int64_t nfix, int64_t ncols,
+                               const float *K, int64_t ldk, const float *QV, int64_t ldqv, float *NUM, int64_t ldn, float *DEN,
+                               int64_t ldd, int32_t f, void *ws, int64_t ws_bytes, int64_t nslots, uint32_t flags,
+                               pgcn_stream_t stream);
+int pgcn_agggated_finish_f32(float *Z, int64_t ldz, const float *DEN, int64_t ldd, int64_t nrows, int32_t f, const float *G,
+                             int64_t ldg, const float *K, int64_t ldk, float *panel, int64_t ldp, pgcn_stream_t stream);
+int pgcn_agggated_grad_rows_f32(const int64_t *rowptr, const int32_t *pairs, const int32_t *slot_row, const int32_t *tasks,
+                                int64_t ntasks, const int64_t *seg, int32_t nslices, const int32_t *fix, int64_t nfix, int64_t ncols,
+                                const float *panel, int64_t ldp, const float *QV, int64_t ldqv, float *dK, int64_t lddk, int32_t f,
+                                float *partial_ws, int64_t partial_ws_elems, int64_t nslots, uint32_t flags, pgcn_stream_t stream);
+int pgcn_agggated_grad_cols_f32(const int64_t *rowptr, const int32_t *col, const int32_t *slot_row, const int32_t *tasks,
+                                int64_t ntasks, const int64_t *seg, int32_t nslices, const int32_t *fix, int64_t nfix, int64_t ncols,
+                                const float *QV, int64_t ldqv, const float *panel, int64_t ldp, float *D, int64_t ldd, int32_t f,
+                                void *ws, int64_t ws_bytes, int64_t nslots, uint32_t flags, pgcn_stream_t stream);
+
 /* ---- DropEdge (Rong et al., ICLR 2020; no counterpart in the reference): the aggregation over a pattern whose entries are dropped
  * anew at every training step and renormalised.  csrc/pgcn_dropedge.h states the keep function:
  *   keep(gi, gj) = gi == gj || u(seed, step[0], min(gi, gj), max(gi, gj)) >= thr      (GLOBAL ids below 2^31; thr: dropout's threshold)

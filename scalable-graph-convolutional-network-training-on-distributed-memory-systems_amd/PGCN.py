@@ -226,14 +226,15 @@ def _check_operand(operand, aggr=None, softmax_beta=None, drop_edge=None, propag
         raise ValueError("operand takes %s, got %r" % (" | ".join(OPERANDS), operand))
     if operand != "bf16":
         return
-    clash = ('aggr="%s"' % aggr if aggr in ("max", "pna") else "softmax_beta" if softmax_beta is not None
+    clash = ('aggr="%s"' % aggr if aggr in ALL_AGGRS[1:] else "softmax_beta" if softmax_beta is not None
              else "drop_edge" if drop_edge else "propagate" if propagate is not None else "gpr" if gpr is not None else None)
     if clash is not None:
         raise ValueError('operand="bf16" does not go with %s' % clash)
 
 
-ALL_AGGRS = ("sum", "max", "pna")   # what --aggr / run(aggr=...) / PGCN(aggr=...) take: the weighted sum A . H (the default), the
-                                    # element-wise max, or the four aggregators and three degree scalers of PNA
+ALL_AGGRS = ("sum", "max", "pna", "gated")   # what --aggr / run(aggr=...) / PGCN(aggr=...) take: the weighted sum A . H (the default), the
+                                    # element-wise max, the four aggregators and three degree scalers of PNA, or GatedGCN's
+                                    # per-feature gates; ALL_AGGRS[1:] are the ones that replace the sum
 AGGRS = ALL_AGGRS[:2]               # COMPATIBILITY ONLY: the tuple earlier releases exported; nothing in the package reads it
 
 
@@ -285,6 +286,34 @@ class PAggPna(torch.autograd.Function):
         if join is not None:
             join()
         return None, dH
+
+
+class PAggGated(torch.autograd.Function):
+    """The gated aggregation of GatedGCN (Bresson & Laurent, 2017; csrc/pgcn_agggated.hip) over the layer's ONE product Y = [K | Q | V]
+    (n x 3 f, stored values of the matrix ignored): Z1_i = sum_j g_ij V_j / (sum_j g_ij + 1e-6), g_ij = sigmoid(K_i + Q_j) per feature --
+    forward ``A.forward_gated`` (the boundary rows of [Q | V] cross ranks once, 2 f wide), backward ``A.backward_gated``, which writes
+    dK | dQ | dV straight into one n x 3 f gradient.  The nnz x f gates are recomputed in the kernels, never stored.  Saved: Y, Z1, DEN
+    and the received halo rows."""
+
+    @staticmethod
+    def forward(ctx, A, Y):
+        ctx.A = A
+        f = Y.shape[1] // 3
+        Z1, DEN, halo = A.forward_gated(Y[:, :f], Y[:, f:])
+        ctx.has_halo = halo is not None
+        ctx.save_for_backward(Y, Z1, DEN, *([halo] if halo is not None else []))
+        return Z1
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        Y, Z1, DEN = ctx.saved_tensors[:3]
+        f = Y.shape[1] // 3
+        dY = torch.empty_like(Y, memory_format=torch.contiguous_format)
+        ctx.A.backward_gated(grad_output, Y[:, :f], Y[:, f:], ctx.saved_tensors[3] if ctx.has_halo else None, Z1, DEN, out=dY)
+        join = getattr(ctx.A, "join_wgrad", None)        # (as PSpMM.backward: the weight gradient parked on the engine's side stream)
+        if join is not None:
+            join()
+        return None, dY
 
 
 class _PnaScale(torch.autograd.Function):
@@ -1740,6 +1769,13 @@ class PGCN(nn.Module):
     then aggregator; then feature) and computes it as ONE product S W'^T of width 4 fin -> 3 fout followed by the degree scalers
     (``_PnaScale``); the result enters ``_forward_combined`` as Z1, so ``root_weight``, ``bias``, ``norm``, ``residual``, dropout and
     ``relu=False`` compose as they do for max.  Refused with ``aggregate=False``, an active ``drop_edge`` and ``softmax_beta``.
+
+    ``aggr="gated"`` (opt-in): the GatedGCN layer (Bresson & Laurent, 2017; PyG's ``ResGatedGraphConv`` is the un-normalised form) -- the
+    layer owns ``linear = nn.Linear(fin, 3 fout, bias=False)``, rows in the order key, query, value, computes ONE product [K | Q | V] and
+    ``PAggGated`` forms Z1_i = sum_j sigmoid(K_i + Q_j) V_j / (sum_j sigmoid(K_i + Q_j) + 1e-6) per feature over the stored neighbourhood
+    (csrc/pgcn_agggated.hip); the result enters ``_forward_combined`` as Z1, exactly as PNA's does.  No biases inside the three
+    projections (``bias=True`` adds the output bias).  Refused where PNA is.  On a HIP device ``fout <= 1024`` (the finishing kernel's
+    row-band shape; wider layers raise there).
     ``aggregate=False`` (opt-in): the layer does not aggregate -- act(H W^T ...), a dense layer over the vertices' own rows (the MLP
     in front of ``Propagate``); no exchange, no engine call.  Every other option composes through the same nodes, and the layer owns
     the same parameters under the same state-dict keys.  Refused with ``aggr="max"`` (nothing to take a max over) and with
@@ -1768,11 +1804,12 @@ class PGCN(nn.Module):
         _check_operand(operand, aggr, softmax_beta, drop_edge is not None and drop_edge.on)
         self.aggregate = bool(aggregate)
         self.pna = aggr == "pna"
-        if self.pna:
+        self.gated = aggr == "gated"
+        if self.pna or self.gated:
             clash = ("aggregate=False" if not self.aggregate else "softmax_beta" if softmax_beta is not None
                      else "drop_edge" if drop_edge is not None and drop_edge.on else None)
             if clash is not None:
-                raise ValueError('aggr="pna" does not go with %s' % clash)
+                raise ValueError('aggr="%s" does not go with %s' % (aggr, clash))
         if softmax_beta is not None:
             softmax_beta = _softmax_beta(softmax_beta)
             if aggr == "max" or not self.aggregate or (drop_edge is not None and drop_edge.on):
@@ -1793,7 +1830,8 @@ class PGCN(nn.Module):
         if operand == "bf16" and self.aggregate:       # (not an architecture field: the same parameters under the same keys)
             self._aggregate = PSpMMBf16.apply
         # (PNA: 3 scalers x 4 aggregators x fin columns in PyG's order -- scaler-major, then aggregator, then feature)
-        self.linear = nn.Linear(12 * in_features if self.pna else in_features, out_features, bias=False)
+        # (gated: the rows of the weight in the order key, query, value -- one product [K | Q | V], no biases inside)
+        self.linear = nn.Linear(12 * in_features if self.pna else in_features, 3 * out_features if self.gated else out_features, bias=False)
         self.A = A
         self.send_map = send_map
         self.recv_map = recv_map
@@ -1861,7 +1899,10 @@ class PGCN(nn.Module):
 
     def _forward_combined(self, H, AH, R=None):
         """The layer with a root weight and / or a bias: H the layer's input (owned rows), AH its aggregation."""
-        Z1 = self._pna_product(H) if self.pna else _LinearNoBias.apply(AH, self.linear.weight)
+        if self.gated:          # ONE product [K | Q | V] = H W^T (the narrow, wide and library routes choose themselves), then the gather
+            Z1 = PAggGated.apply(self.A, _LinearNoBias.apply(H, self.linear.weight))
+        else:
+            Z1 = self._pna_product(H) if self.pna else _LinearNoBias.apply(AH, self.linear.weight)
         Z2 = _LinearNoBias.apply(H, self.root.weight) if self.root_weight else None
         drop = self.relu and self.training and self.dropout > 0.0
         if drop and self.state is None:
@@ -1884,7 +1925,7 @@ class PGCN(nn.Module):
         return self._layer(H)
 
     def _layer(self, H, R=None):
-        if self.pna:            # (always the combined route: Z1 is the scaled product, the tail is the one of before)
+        if self.pna or self.gated:      # (always the combined route: Z1 is the scaled / gated product, the tail is the one of before)
             return self._forward_combined(H, None, R)
         if self.root_weight or self.has_bias:
             return self._forward_combined(H, self._aggregate(self.A, H), R)
@@ -2069,7 +2110,7 @@ def _architecture(fin, classes, nlayers, nfeatures, hidden, multilabel, dropout,
     positive, so that earlier checkpoints compare as before)."""
     widths = [int(fin)] + [int(nfeatures if hidden is None else hidden)] * (nlayers - 1) + [int(classes)]
     return _checkpoint.architecture(widths, "multilabel" if multilabel else "single", dropout, dropout_seed, norm, root_weight, bias,
-                                    residual, **({"aggr": aggr} if aggr in ("max", "pna") else {}),
+                                    residual, **({"aggr": aggr} if aggr in ALL_AGGRS[1:] else {}),
                                     **({"propagate": (propagate, PPR_ALPHA if ppr_alpha is None else ppr_alpha)} if propagate is not None else {}),
                                     **({"dense_layers": True} if dense_layers else {}),
                                     **({"drop_edge": float(drop_edge)} if drop_edge else {}),
@@ -2084,7 +2125,7 @@ def _check_softmax_beta(softmax_beta, aggr=None, dense_layers=None, drop_edge=No
     if softmax_beta is None:
         return
     _softmax_beta(softmax_beta)
-    if aggr in ("max", "pna"):
+    if aggr in ALL_AGGRS[1:]:
         raise ValueError('softmax_beta does not go with aggr="%s"' % aggr)
     if dense_layers:
         raise ValueError("softmax_beta does not go with dense_layers: nothing is aggregated")
@@ -2104,7 +2145,7 @@ def _check_drop_edge(drop_edge, normalize=None, aggr=None, dense_layers=None, ch
         if check_normalize and normalize != "sym":
             raise ValueError("drop_edge needs normalize='sym': DropEdge renormalises the pattern of A + I, a weighted or pre-normalised "
                              "matrix cannot be renormalised")
-        if aggr in ("max", "pna"):
+        if aggr in ALL_AGGRS[1:]:
             raise ValueError('drop_edge does not go with aggr="%s"' % aggr)
         if dense_layers:
             raise ValueError("drop_edge does not go with dense_layers: nothing is aggregated")
@@ -2122,8 +2163,8 @@ def _check_propagate(propagate, ppr_alpha, dense_layers, aggr=None, root_weight=
             raise ValueError("ppr_alpha needs propagate")
         if isinstance(ppr_alpha, bool) or not isinstance(ppr_alpha, (int, float)) or not 0.0 <= float(ppr_alpha) < 1.0:
             raise ValueError("ppr_alpha takes a finite number with 0 <= alpha < 1, got %r" % (ppr_alpha,))
-    if dense_layers and (aggr in ("max", "pna") or root_weight):
-        raise ValueError("dense_layers does not go with %s" % ('aggr="%s"' % aggr if aggr in ("max", "pna") else "root_weight"))
+    if dense_layers and (aggr in ALL_AGGRS[1:] or root_weight):
+        raise ValueError("dense_layers does not go with %s" % ('aggr="%s"' % aggr if aggr in ALL_AGGRS[1:] else "root_weight"))
 
 
 def _check_gpr(gpr, gpr_init, gpr_alpha, propagate=None):
@@ -2202,7 +2243,7 @@ def _train_on_data(A, n, nlayers, nfeatures, features, labels, split, hidden, ep
     _dropout.threshold(dropout)
     state = _dropout.DropoutState(dropout_seed, device) if dropout > 0.0 or drop_edge > 0.0 else None
     extra = dict(({"root_weight": True} if root_weight else {}), **({"bias": True} if bias else {}))       # (neither: the call of before)
-    if aggr in ("max", "pna"):
+    if aggr in ALL_AGGRS[1:]:
         extra["aggr"] = aggr
     if dense_layers:
         extra["aggregate"] = False
@@ -2464,7 +2505,7 @@ def run(rank, size, nlayers, nfeatures, path_A, path_partvec, backend, normalize
                               **({"root_weight": True} if root_weight else {}), **({"bias": True} if bias else {}),
                               **({"residual": True} if residual else {}),
                               **{k: v for k, v in (("save", save), ("load", load), ("predict", predict), ("proba", proba)) if v is not None},
-                              **({"control": control} if control else {}), **({"aggr": aggr} if aggr in ("max", "pna") else {}),
+                              **({"control": control} if control else {}), **({"aggr": aggr} if aggr in ALL_AGGRS[1:] else {}),
                               **{k: v for k, v in (("propagate", propagate), ("ppr_alpha", ppr_alpha)) if v is not None},
                               **({"dense_layers": True} if dense_layers else {}),
                               **({"drop_edge": float(drop_edge)} if drop_edge else {}),
@@ -2786,25 +2827,25 @@ def main(argv):
     if ("gpr_init" in data or "gpr_alpha" in data) and "gpr" not in data:
         print("--gpr-init and --gpr-alpha need --gpr", flush=True)
         sys.exit(2)
-    if "dense_layers" in data and (data.get("aggr") in ("max", "pna") or "root_weight" in data):
-        print("--dense-layers does not go with %s" % ("--aggr %s" % data["aggr"] if data.get("aggr") in ("max", "pna") else "--root-weight"), flush=True)
+    if "dense_layers" in data and (data.get("aggr") in ALL_AGGRS[1:] or "root_weight" in data):
+        print("--dense-layers does not go with %s" % ("--aggr %s" % data["aggr"] if data.get("aggr") in ALL_AGGRS[1:] else "--root-weight"), flush=True)
         sys.exit(2)
     if data.get("drop_edge", 0.0) > 0.0:
         if normalize != "sym":
             print("--drop-edge needs --normalize sym: DropEdge renormalises the pattern of A + I, a weighted or pre-normalised matrix "
                   "cannot be renormalised", flush=True)
             sys.exit(2)
-        if data.get("aggr") in ("max", "pna") or "dense_layers" in data:
-            print("--drop-edge does not go with %s" % ("--aggr %s" % data["aggr"] if data.get("aggr") in ("max", "pna") else "--dense-layers"), flush=True)
+        if data.get("aggr") in ALL_AGGRS[1:] or "dense_layers" in data:
+            print("--drop-edge does not go with %s" % ("--aggr %s" % data["aggr"] if data.get("aggr") in ALL_AGGRS[1:] else "--dense-layers"), flush=True)
             sys.exit(2)
     if "softmax_beta" in data:
-        clash = ("--aggr %s" % data["aggr"] if data.get("aggr") in ("max", "pna") else "--dense-layers" if "dense_layers" in data
+        clash = ("--aggr %s" % data["aggr"] if data.get("aggr") in ALL_AGGRS[1:] else "--dense-layers" if "dense_layers" in data
                  else "--drop-edge" if data.get("drop_edge", 0.0) > 0.0 else None)
         if clash:
             print("--softmax-aggr does not go with %s" % clash, flush=True)
             sys.exit(2)
     if operand == "bf16":
-        clash = ("--aggr %s" % data["aggr"] if data.get("aggr") in ("max", "pna") else "--softmax-aggr" if "softmax_beta" in data
+        clash = ("--aggr %s" % data["aggr"] if data.get("aggr") in ALL_AGGRS[1:] else "--softmax-aggr" if "softmax_beta" in data
                  else "--drop-edge" if data.get("drop_edge", 0.0) > 0.0 else "--propagate" if "propagate" in data
                  else "--gpr" if "gpr" in data else None)
         if clash:

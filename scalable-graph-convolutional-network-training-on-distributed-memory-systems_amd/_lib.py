@@ -120,6 +120,13 @@ SIGNATURES = {
     "pgcn_aggpna_finish_f32": (ctypes.c_int, [_vp, _i64, _vp, _i64, _i32, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp]),
     "pgcn_aggpna_backward_csr_plan_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _i32, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64,
                                                          _i32, _vp, _i64, _i64, _u32, _vp]),
+    "pgcn_agggated_csr_plan_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _vp, _i32, _vp, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp,
+                                                  _i64, _i32, _vp, _i64, _i64, _u32, _vp]),
+    "pgcn_agggated_finish_f32": (ctypes.c_int, [_vp, _i64, _vp, _i64, _i64, _i32, _vp, _i64, _vp, _i64, _vp, _i64, _vp]),
+    "pgcn_agggated_grad_rows_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _vp, _i32, _vp, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _i64,
+                                                   _i32, _vp, _i64, _i64, _u32, _vp]),
+    "pgcn_agggated_grad_cols_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _vp, _i32, _vp, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _i64,
+                                                   _i32, _vp, _i64, _i64, _u32, _vp]),
     "pgcn_pna_scale_forward_f32": (ctypes.c_int, [_vp, _i64, _vp, _vp, _vp, _i64, _i64, _i32, _vp]),
     "pgcn_pna_scale_backward_f32": (ctypes.c_int, [_vp, _i64, _vp, _vp, _vp, _i64, _i64, _i32, _vp]),
     "pgcn_dropedge_sum_csr_plan_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _i32, _vp, _i64, _vp, _i64, _vp, _i64, _i32, _vp,

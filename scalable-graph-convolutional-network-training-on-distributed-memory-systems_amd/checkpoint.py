@@ -45,7 +45,7 @@ def architecture(widths, task, dropout=0.0, dropout_seed=0, norm=None, root_weig
                  out_heads=None, aggr=None, propagate=None, dense_layers=None, drop_edge=None, softmax_beta=None, attn_dropout=None, attention=None,
                  share_weights=None, gpr=None):
     """The plain-value record of what a model was built from; two models of equal records have state dicts of equal keys and shapes,
-    and draw the same dropout masks.  ``aggr``: the key exists only for "max" and "pna" -- a record of the weighted sum is the record of before,
+    and draw the same dropout masks.  ``aggr``: the key exists only for "max", "pna" and "gated" -- a record of the weighted sum is the record of before,
     and compares equal to every checkpoint written without the key.  Likewise ``propagate`` ((K, alpha): the key holds [K, alpha]
     only when the model ends with the personalised-PageRank propagation) and ``dense_layers`` (True only when the layers do not
     aggregate): without them the record is the record of before.  ``drop_edge``: the key holds the DropEdge probability only when it is
@@ -64,7 +64,7 @@ def architecture(widths, task, dropout=0.0, dropout_seed=0, norm=None, root_weig
             "out_heads": None if out_heads is None else int(out_heads), "dropout": float(dropout),
             "dropout_seed": int(dropout_seed) if float(dropout) > 0.0 or float(drop_edge or 0.0) > 0.0
             or float(attn_dropout or 0.0) > 0.0 else 0}
-    if aggr in ("max", "pna"):
+    if aggr in ("max", "pna", "gated"):
         arch["aggr"] = str(aggr)
     if propagate is not None:
         arch["propagate"] = [int(propagate[0]), float(propagate[1])]

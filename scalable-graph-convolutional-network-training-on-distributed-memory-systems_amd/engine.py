@@ -677,6 +677,76 @@ def pna_scale_backward_composed(G: torch.Tensor, a: torch.Tensor, b: torch.Tenso
     return torch.cat([G, a.unsqueeze(1) * G, b.unsqueeze(1) * G], 1)
 
 
+# --------------------------------------------------------------------------
+# gated aggregation: the composed route (framework operations; the definitions of csrc/pgcn_agggated.hip).  Row block by row block:
+# never more than a block's entries x f at once -- the nnz x f gates of the whole structure are what the kernels exist to avoid.
+
+GATED_EPS = 1e-6
+GATED_BLOCK_ROWS = 4096
+
+
+def _gated_blocks(A: ComposedMaxCSR):
+    """(rows, cols) of the stored entries of GATED_BLOCK_ROWS consecutive rows at a time (``A.row`` ascends)."""
+    if A.nnz:
+        cuts = torch.searchsorted(A.row, torch.arange(0, A.nrows + GATED_BLOCK_ROWS, GATED_BLOCK_ROWS, device=A.row.device)).tolist()
+        for e0, e1 in zip(cuts, cuts[1:]):
+            if e1 > e0:
+                yield A.row[e0:e1], A.col[e0:e1]
+
+
+def agggated_composed(A: ComposedMaxCSR, K: torch.Tensor, QV: torch.Tensor, NUM: torch.Tensor, DEN: torch.Tensor, accumulate: bool = False):
+    """(NUM, DEN) of ``HipKernels.agggated`` from framework operations: NUM[i] = sum_j g_ij V[j], DEN[i] = sum_j g_ij over the stored
+    entries, g_ij = sigmoid(K[i] + Q[j]) per feature, QV = [Q | V].  ``accumulate``: added to what the rows hold.  The same definition;
+    only the order of the fp32 additions is the framework's."""
+    n, f = A.nrows, K.shape[1]
+    K, QV = K.detach(), QV.detach()
+    if not accumulate:
+        NUM[:n] = 0
+        DEN[:n] = 0
+    for r, c in _gated_blocks(A):
+        g = torch.sigmoid(K[r] + QV[c, :f])
+        NUM[:n].index_add_(0, r, g * QV[c, f:])
+        DEN[:n].index_add_(0, r, g)
+    return NUM, DEN
+
+
+def agggated_finish_composed(Z: torch.Tensor, DEN: torch.Tensor, G=None, K=None):
+    """``HipKernels.agggated_finish`` from framework operations.  Without ``G``: Z = Z / (DEN + eps) in place.  With it: the operands
+    of the backward (K, P = G / (DEN + eps), O = Z) as a tuple -- what the kernels' route writes as one panel."""
+    if G is None:
+        Z /= DEN + GATED_EPS
+        return Z
+    return K.detach(), G.detach() / (DEN + GATED_EPS), Z
+
+
+def agggated_grad_rows_composed(A: ComposedMaxCSR, panel, QV: torch.Tensor, dK: torch.Tensor, accumulate: bool = False):
+    """dK of ``HipKernels.agggated_grad_rows`` from framework operations: dK[i] (+)= sum_j P[i] (V[j] - O[i]) g_ij (1 - g_ij)."""
+    K, P, O = panel
+    n, f = A.nrows, dK.shape[1]
+    QV = QV.detach()
+    if not accumulate:
+        dK[:n] = 0
+    for r, c in _gated_blocks(A):
+        x = K[r] + QV[c, :f]
+        dK[:n].index_add_(0, r, P[r] * (QV[c, f:] - O[r]) * (torch.sigmoid(x) * torch.sigmoid(-x)))
+    return dK
+
+
+def agggated_grad_cols_composed(AT: ComposedMaxCSR, QV: torch.Tensor, panel, D: torch.Tensor):
+    """D = [dQ | dV] of ``HipKernels.agggated_grad_cols`` from framework operations: over the stored entries i of row r of the
+    transposed structure, dQ[r] = sum_i P[i] (V[r] - O[i]) g (1 - g), dV[r] = sum_i g P[i], g = sigmoid(K[i] + Q[r]).  D is written."""
+    K, P, O = panel
+    n, f = AT.nrows, D.shape[1] // 2
+    QV = QV.detach()
+    D[:n] = 0
+    for r, c in _gated_blocks(AT):
+        x = K[c] + QV[r, :f]
+        g = torch.sigmoid(x)
+        D[:n, :f].index_add_(0, r, P[c] * (QV[r, f:] - O[c]) * (g * torch.sigmoid(-x)))
+        D[:n, f:].index_add_(0, r, g * P[c])
+    return D
+
+
 def pna_delta(hist) -> float:
     """delta of the PNA scalers: the mean over all vertices of log(d + 1), from the integer degree histogram (hist[d] = vertices of
     degree d) -- a float64 sum in ascending degree, so the same bits under any part vector and rank count."""
@@ -1541,6 +1611,79 @@ class AggregationEngine(BoundaryExchange):
         if self.on_gpu and hasattr(self.k, "pna_scale_backward"):
             return self.k.pna_scale_backward(G.contiguous(), dg.a, dg.b)
         return pna_scale_backward_composed(G, dg.a, dg.b)
+
+    # ------------------------------------------------------------------
+    # gated aggregation (csrc/pgcn_agggated.hip): Z1[i] = sum_j g_ij V[j] / (sum_j g_ij + 1e-6) over the stored
+    # columns j of row i, g_ij = sigmoid(K[i] + Q[j]) per feature.  (NUM, DEN) is additive: every structure joins by accumulation.  On
+    # ``_max_structures()``: nothing new is prepared.
+    GATED_KERNELS = ("agggated", "agggated_finish", "agggated_grad_rows", "agggated_grad_cols")
+
+    def _gated_routes(self):
+        m = self._max_structures(self.GATED_KERNELS)
+        if m.composed:
+            return m, agggated_composed, agggated_finish_composed, agggated_grad_rows_composed, agggated_grad_cols_composed
+        return m, self.k.agggated, self.k.agggated_finish, self.k.agggated_grad_rows, self.k.agggated_grad_cols
+
+    def forward_gated(self, K: torch.Tensor, QV: torch.Tensor):
+        """(Z1, DEN, halo): the gated aggregation over every owned vertex's stored neighbourhood (stored values ignored; 0.0 for a
+        vertex without neighbours), the gates' sums, and the received boundary rows of [Q | V] as a tensor of its own (None at size 1)
+        for the backward.  ``K`` (n_local x f) and ``QV`` (n_local x 2 f) may be column slices of one product: nothing is copied.  The
+        boundary rows cross ranks once, 2 f wide; the local structure's pass overlaps the exchange, every round joins by accumulation."""
+        f = K.shape[1]
+        if K.shape[0] != self.n_local or QV.shape[0] != self.n_local or QV.shape[1] != 2 * f:
+            raise ValueError("K and QV must hold exactly the %d owned rows, f and 2 f wide" % self.n_local)
+        m, run, finish, _, _ = self._gated_routes()
+        Z = torch.empty((self.n_local, f), dtype=torch.float32, device=self.device)
+        DEN = torch.empty((self.n_local, f), dtype=torch.float32, device=self.device)
+        if self.size == 1:
+            run(m.loc, K, QV, Z, DEN)
+            return finish(Z, DEN), DEN, None
+        send = self._slab("send", self.n_send, 2 * f)
+        halo = torch.empty((max(self.n_halo, 1), 2 * f), dtype=torch.float32, device=self.device)      # kept for the backward (forward_softmax)
+        self.k.gather_rows(QV, self.send_idx, send)
+        waits = self._exchange_all(send, self.round_send_off, halo, self.round_recv_off, 2 * f, tag="forward")
+        run(m.loc, K, QV, Z, DEN)                # overlaps the exchange
+        for r in range(self.rounds):
+            waits[r]()
+            run(m.halo[r], K, halo, Z, DEN, accumulate=True)      # round r's sums join the local result; overlaps round r+1
+        return finish(Z, DEN), DEN, halo
+
+    def backward_gated(self, G: torch.Tensor, K: torch.Tensor, QV: torch.Tensor, halo, Z1: torch.Tensor, DEN: torch.Tensor, out=None):
+        """(dK, dQV) of ``forward_gated``, column slices of ONE n_local x 3 f gradient [dK | dQ | dV] (``out``, or a new tensor): with
+        P = G / (DEN + 1e-6), O = Z1 and t_ij = P_i (V_j - O_i) g_ij (1 - g_ij):  dK_i = sum_j t_ij over the forward structures, dQ_j =
+        sum_i t_ij and dV_j = sum_i g_ij P_i over the transposed ones.  The halo structures' [dQ | dV] partial rows are formed first and
+        travel home 2 f wide like ``backward``'s while the local passes run; they are ADDED."""
+        m, _, finish, rows, cols = self._gated_routes()
+        if m.loc_T is None:
+            raise RuntimeError("partition was built without the transposed pieces")
+        f = K.shape[1]
+        panel = finish(Z1, DEN, G.contiguous(), K)
+        dY = torch.empty((self.n_local, 3 * f), dtype=torch.float32, device=self.device) if out is None else out
+        dK, dQV = dY[:, :f], dY[:, f:]
+        if self.size == 1:
+            rows(m.loc, panel, QV, dK)
+            cols(m.loc_T, QV, panel, dQV)
+            return dK, dQV
+        partial = self._slab("halo", self.n_halo, 2 * f)
+        back = self._slab("send", self.n_send, 2 * f)
+        ready = []
+        for r in range(self.rounds):
+            b0, b1 = self.round_recv_off[r][0], self.round_recv_off[r][-1]
+            cols(m.halo_T[r], halo[b0:b1], panel, partial[b0:b1])
+            if self.overlap:
+                ev = torch.cuda.Event()
+                ev.record(torch.cuda.current_stream(self.device))
+                ready.append(ev)
+        waits = self._exchange_all(partial, self.round_recv_off, back, self.round_send_off, 2 * f,
+                                   ready if self.overlap else None, tag="backward")
+        cols(m.loc_T, QV, panel, dQV)
+        rows(m.loc, panel, QV, dK)
+        for r in range(self.rounds):
+            rows(m.halo[r], panel, halo, dK, accumulate=True)
+        for r in range(self.rounds):
+            waits[r]()
+            self.k.spmm(self.unpack[r], back, dQV, accumulate=True)      # returned rows are sums: backward's unpack
+        return dK, dQV
 
     # ------------------------------------------------------------------
     # DropEdge (csrc/pgcn_dropedge.hip; DESIGN.md section 4): the aggregation over the stored pattern minus the entries dropped in this

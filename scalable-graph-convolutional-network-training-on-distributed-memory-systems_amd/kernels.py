@@ -1271,6 +1271,124 @@ class HipKernels:
                                                         self._stream()), "pgcn_pna_scale_backward_f32")
         return dY
 
+    # -- gated aggregation (pgcn_agggated.hip) ---------------------------------
+    @staticmethod
+    def gated_panel_ld(f: int) -> int:
+        """Words of a row of the gated backward's panel: three planes [K | P | O] of 4 ceil(f / 4) words (include/pgcn_hip.h)."""
+        return 12 * ((int(f) + 3) // 4)
+
+    def _gated_bind(self, A: DeviceMaxCSR, key, operands, widths, gathered: int, ws_words: int, accumulate: bool, empty, call):
+        """The binding the four gated entry points share, made once per ``key`` in ``A.launch_cache``.  ``operands``: (tensor, rows,
+        name) in the order ``call`` takes their (pointer, leading dimension) pairs; ``widths``: the columns each must hold;
+        ``gathered``: the position of the operand whose rows the stored entries index; ``ws_words``: work-space floats per slot and
+        feature; ``empty``: what a structure without entries does instead of a launch."""
+        f = key[-1]
+        for (t, rows, name), w in zip(operands, widths):       # on every call: the key holds strides, not row counts or widths
+            self._max_operand(t, rows, torch.float32, name)
+            if t.shape[1] != w:
+                raise _lib.PgcnError("%s must be %d columns wide (f = %d), got %d" % (name, w, f, t.shape[1]))
+        fn = A.launch_cache.get(key)
+        if fn is None:
+            lds = [max(t.stride(0), w) for (t, _, _), w in zip(operands, widths)]
+            if A.nrows == 0 or (A.nnz == 0 and accumulate):
+                fn = lambda *ts: None
+            elif A.nnz == 0:
+                fn = empty
+            else:
+                flags = self.base_flags | (_lib.SPMM_ACCUMULATE if accumulate else 0) | self._max_fpass(A, f)
+                if (A.ncols + 1) * lds[gathered] * 4 < 2 ** 32:
+                    flags |= _lib.SPMM_OFFSETS32
+                self._slot_rows(A)
+                ws, ws_n = self._max_ws(A, A.nslots * f * 4 * ws_words)
+                check, stream = _lib.check, self._stream
+                plan = (A.rowptr.data_ptr(), _ptr(A.pairs if A.pairs is not None else A.col), _ptr(A.slot_row), _ptr(A.tasks), A.ntasks,
+                        A.seg, A.nslices, _ptr(A.fix), A.nfix, A.ncols)
+                tail = (f, ws, ws_n if ws_words == 2 else ws_n // 4, A.nslots, flags)
+                name = call.__name__
+
+                def fn(*ts):
+                    args = []
+                    for t, ld in zip(ts, lds):
+                        args += [t.data_ptr(), ld]
+                    check(call(*plan, *args, *tail, stream()), name)
+            A.launch_cache[key] = fn
+        return fn
+
+    def agggated(self, A: DeviceMaxCSR, K: torch.Tensor, QV: torch.Tensor, NUM: torch.Tensor, DEN: torch.Tensor, accumulate: bool = False):
+        """(NUM, DEN) of the gated aggregation over the stored entries (i, j) of ``A`` (include/pgcn_hip.h, pgcn_agggated_csr_plan_f32; a
+        ``prepare_max(csr, col_gid)`` structure, nothing else is prepared) on the current stream: NUM[i] = sum_j g_ij V[j], DEN[i] =
+        sum_j g_ij with g_ij = sigmoid(K[i] + Q[j]) per feature, ``QV`` = [Q | V] of the columns (2 f wide).  ``accumulate``: the sums
+        are added to what the rows hold.  Every operand takes its own row stride: K and QV may be column slices of one product."""
+        if A.pairs is None:
+            raise _lib.PgcnError("agggated needs a structure made by prepare_max(csr, col_gid)")
+        f = K.shape[1]
+        nrows = A.nrows
+
+        def empty(K, QV, NUM, DEN):
+            NUM[:nrows].zero_()
+            DEN[:nrows].zero_()
+        key = ("gated", K.stride(0), QV.stride(0), NUM.stride(0), DEN.stride(0), bool(accumulate), f)
+        self._gated_bind(A, key, ((K, nrows, "K"), (QV, A.ncols, "QV"), (NUM, nrows, "NUM"), (DEN, nrows, "DEN")), (f, 2 * f, f, f), 1, 2,
+                         accumulate, empty, self.lib.pgcn_agggated_csr_plan_f32)(K, QV, NUM, DEN)
+        return NUM, DEN
+
+    def agggated_finish(self, Z: torch.Tensor, DEN: torch.Tensor, G: Optional[torch.Tensor] = None, K: Optional[torch.Tensor] = None):
+        """Without ``G``: Z = Z / (DEN + 1e-6) in place (NUM becomes Z1); returns Z.  With ``G`` = dZ1 and ``K``: the panel of the
+        backward, n x 12 ceil(f / 4) words, three planes {K | P = G / (DEN + 1e-6) | O = Z} per row (pgcn_agggated_finish_f32), a new
+        tensor."""
+        n, f = Z.shape
+        if f < 1 or f > ROWBAND_MAX_F:
+            raise _lib.PgcnError("agggated_finish: 1 <= f <= %d, got %d" % (ROWBAND_MAX_F, f))
+        ops = [(Z, "Z"), (DEN, "DEN")] + ([] if G is None else [(G, "G"), (K, "K")])
+        for t, name in ops:
+            self._max_operand(t, n, torch.float32, name)
+            if t.shape[1] != f:
+                raise _lib.PgcnError("agggated_finish: %s must be %d columns wide, got %d" % (name, f, t.shape[1]))
+        ld = lambda t: max(t.stride(0), f)
+        if G is None:
+            _lib.check(self.lib.pgcn_agggated_finish_f32(_ptr(Z), ld(Z), _ptr(DEN), ld(DEN), n, f, None, 0, None, 0, None, 0, self._stream()),
+                       "pgcn_agggated_finish_f32")
+            return Z
+        ldp = self.gated_panel_ld(f)
+        panel = torch.empty((max(n, 1), ldp), dtype=torch.float32, device=self.device)
+        _lib.check(self.lib.pgcn_agggated_finish_f32(_ptr(Z), ld(Z), _ptr(DEN), ld(DEN), n, f, _ptr(G), ld(G), _ptr(K), ld(K), panel.data_ptr(),
+                                                     ldp, self._stream()), "pgcn_agggated_finish_f32")
+        return panel
+
+    def _gated_panel(self, panel: torch.Tensor, rows: int, f: int):
+        ldp = self.gated_panel_ld(f)
+        if not (panel.is_cuda and panel.dtype is torch.float32 and panel.dim() == 2 and panel.is_contiguous() and panel.shape[1] == ldp
+                and panel.shape[0] >= rows):
+            raise _lib.PgcnError("panel must be agggated_finish's: contiguous, at least %d x %d floats" % (rows, ldp))
+
+    def agggated_grad_rows(self, A: DeviceMaxCSR, panel: torch.Tensor, QV: torch.Tensor, dK: torch.Tensor, accumulate: bool = False):
+        """dK[i] (+)= sum over the stored entries (i, j) of ``A`` of P[i] (V[j] - O[i]) g_ij (1 - g_ij), element-wise
+        (pgcn_agggated_grad_rows_f32; the FORWARD structure of ``agggated``): ``panel``: ``agggated_finish``'s, one row per row of
+        ``A``; ``QV`` = [Q | V] of the columns."""
+        if A.pairs is None:
+            raise _lib.PgcnError("agggated_grad_rows needs a structure made by prepare_max(csr, col_gid)")
+        f = dK.shape[1]
+        nrows = A.nrows
+        self._gated_panel(panel, nrows, f)
+        key = ("gated_rows", panel.stride(0), QV.stride(0), dK.stride(0), bool(accumulate), f)
+        self._gated_bind(A, key, ((panel, nrows, "panel"), (QV, A.ncols, "QV"), (dK, nrows, "dK")), (panel.shape[1], 2 * f, f), 1, 1, accumulate,
+                         lambda panel, QV, dK: dK[:nrows].zero_(), self.lib.pgcn_agggated_grad_rows_f32)(panel, QV, dK)
+        return dK
+
+    def agggated_grad_cols(self, AT: DeviceMaxCSR, QV: torch.Tensor, panel: torch.Tensor, D: torch.Tensor):
+        """D[r] = [dQ | dV] of row r of the transposed structure: sums over its stored entries i of P[i] (V[r] - O[i]) g (1 - g) and of
+        g P[i], g = sigmoid(K[i] + Q[r]) (pgcn_agggated_grad_cols_f32): deterministic, D is written.  ``QV``: the rows of ``AT``;
+        ``panel``: ``agggated_finish``'s, one row per column of ``AT``."""
+        if AT.col is None:
+            raise _lib.PgcnError("agggated_grad_cols needs a structure made by prepare_max(csr) without col_gid")
+        f = D.shape[1] // 2
+        nrows = AT.nrows
+        self._gated_panel(panel, AT.ncols, max(f, 1))
+        key = ("gated_cols", QV.stride(0), panel.stride(0), D.stride(0), f)
+        self._gated_bind(AT, key, ((QV, nrows, "QV"), (panel, AT.ncols, "panel"), (D, nrows, "D")), (2 * f, panel.shape[1], 2 * f), 1, 2, False,
+                         lambda QV, panel, D: D[:nrows].zero_(), self.lib.pgcn_agggated_grad_cols_f32)(QV, panel, D)
+        return D
+
     # -- DropEdge (pgcn_dropedge.hip) -----------------------------------------
     def _drop_structure(self, A: DeviceMaxCSR, row_gid: torch.Tensor, what: str):
         """What the drop kernels need of a ``prepare_max(csr, col_gid)`` structure: the pairs, and the row of every slot of a cut row
@@ -1280,6 +1398,10 @@ class HipKernels:
         if not (row_gid.is_cuda and row_gid.dtype is torch.int32 and row_gid.dim() == 1 and row_gid.is_contiguous()
                 and row_gid.numel() >= A.nrows):
             raise _lib.PgcnError("row_gid must be a contiguous int32 CUDA vector of at least %d entries" % A.nrows)
+        self._slot_rows(A)
+
+    def _slot_rows(self, A: DeviceMaxCSR) -> None:
+        """The row of every slot of a cut row, made once, on the device, from the fix list."""
         if A.nslots > 0 and A.slot_row is None:
             cnt = A.fix[:, 2].to(torch.int64)                 # the slots of a row are consecutive from fix[:, 1] on
             first = torch.cumsum(cnt, 0) - cnt
