@@ -1145,6 +1145,50 @@ int pgcn_gat_tail_backward_f32(const float *G, int64_t ldg, const float *Y, int6
                                uint32_t layer, uint32_t thr, float *dX, int64_t lddx, float *dbias, void *ws, int64_t ws_bytes,
                                pgcn_stream_t stream);
 
+/* ---- the tail of a GAT layer with a per-vertex layer norm and a residual link (PGAT.py: _GatTailNorm) -----------------------------
+ * Y = R + drop(act(LN(reduce_heads(X) + b))): the tail above with a layer normalisation of each vertex over its fout output columns
+ * between the bias and the activation, and the layer's input added at the end.  Row-local: no collective, and a row's results depend
+ * on that row alone -- not on its position, the block that met it, nrows or the rank.  fout = mean ? d : heads * d.
+ * pgcn_gat_tail_ln_forward_f32:  r and t = r + bias[j] exactly as pgcn_gat_tail_forward_f32 forms them (heads in index order, one
+ *   product with 1.0f / heads, none for one head; bias == NULL: the term is absent).  mean_i = sum_j t / fout;  var_i = sum_j
+ *   (t - mean_i)^2 / fout (biased, a true second pass in registers, never E[t^2] - mean^2);  rstd_i = 1 / sqrt(var_i + float(eps)) --
+ *   fp32 sums: a thread adds its four columns in a fixed order, then a fixed tree of depth <= log2(TPR) + 1 over the TPR threads of
+ *   the row.  xh = (t - mean_i) rstd_i;  u = fma(gamma[j], xh, beta[j]);  a = act ? (u > 0 ? u : expm1f(u)) : u;  dd = keep ?
+ *   a * scale : 0;  Y[i,j] = R ? R[i,j] + dd : dd.  keep / scale: those of pgcn_gat_tail_forward_f32, the key (seed, *step, layer,
+ *   row_ids[i] (NULL: i), OUTPUT column j); step == NULL or thr == 0: keep is true and scale 1.  mean_out, rstd_out: nrows floats, the
+ *   fp32 values the kernel itself used; both may be NULL (inference).  Y == R with ldy == ldr is allowed (in place); Y == X is not
+ *   (the backward reads X).  One launch; nrows == 0: none.
+ * pgcn_gat_tail_ln_backward_f32:  t, xh and u are formed AGAIN from X, bias, mean and rstd: nothing of size nrows x fout is saved
+ *   -- no Y (with R added it no longer tells the sign), no mask (the keep bits come from the key, the sign from u).
+ *   deriv = (act && u <= 0) ? expf(u) : 1;  g' = keep ? (G[i,j] * scale) * deriv : 0;  gh = g' gamma[j];  c1 = sum_j gh / fout,
+ *   c2 = sum_j gh xh / fout (one tree for both);  dT = rstd_i ((gh - c1) - xh c2);  dX[i, k d + j] = mean ? dT * (1.0f / heads) : dT
+ *   for every head k.  In the same pass dbias[j] = float(sum_i dT), dgamma[j] = float(sum_i g' xh), dbeta[j] = float(sum_i g'),
+ *   added in double (a dropped element adds exact zeros to the last two whatever its x): a block owns 512 consecutive rows, folds its
+ *   row groups through LDS by a fixed tree and writes one partial record [3][fout] of doubles to `ws` (pgcn_gat_tail_ln_ws_bytes(nrows,
+ *   fout) bytes, 8-byte aligned, at least one record; -1 for sizes the kernels refuse); a second launch, 32 of the 3 fout outputs per
+ *   block, adds the records in a fixed order -- no floating-point atomics, the same input gives the same bits.  The sums are
+ *   RANK-LOCAL.  dX == NULL: sums only.  All three sum pointers NULL: no sums, ws is not read, one launch; only some of them:
+ *   PGCN_EINVAL.  dX == G or dX == X is allowed when mean == 0 and the leading dimensions agree.  nrows == 0: the sums are zeroed,
+ *   nothing else is written.  The residual's gradient is G itself: no kernel.
+ * Both: row-major with leading dimensions in elements, 64-bit row offsets; every fout from 1 to 1024 and heads * d <= 8192
+ * (PGCN_EUNSUPPORTED above); a thread owns four consecutive OUTPUT columns -- one float4 when fout % 4 == 0 and every base and leading
+ * dimension keeps rows 16-byte aligned, four guarded scalars otherwise, the same bits either way (the file is built with
+ * -ffp-contract=off: the one fused operation is the written fma).  PGCN_EINVAL, nothing launched: a null required pointer (gamma and
+ * beta always; X, Y / G, X, mean, rstd with nrows > 0), nrows < 0, heads < 1, d < 1, act other than 0 / 1, a leading dimension below
+ * its width, eps non-finite or <= 0 (as a double or as a float), a misaligned ws / step / row_ids, only one of mean_out / rstd_out, a
+ * refused in-place case; PGCN_ENOMEM: ws_bytes too small.  A NaN or inf in a row stays in that row's outputs, and in the columns of
+ * the three sums that row touches.  Raw pointers + a stream, no allocation, no synchronisation (graph-capturable).          */
+int64_t pgcn_gat_tail_ln_ws_bytes(int64_t nrows, int32_t fout);
+int pgcn_gat_tail_ln_forward_f32(const float *X, int64_t ldx, int64_t nrows, int32_t heads, int32_t d, int32_t mean,
+                                 const float *bias, const float *gamma, const float *beta, double eps, int32_t act, const float *R,
+                                 int64_t ldr, const int64_t *row_ids, uint64_t seed, const int64_t *step, uint32_t layer,
+                                 uint32_t thr, float *Y, int64_t ldy, float *mean_out, float *rstd_out, pgcn_stream_t stream);
+int pgcn_gat_tail_ln_backward_f32(const float *G, int64_t ldg, const float *X, int64_t ldx, int64_t nrows, int32_t heads, int32_t d,
+                                  int32_t mean, const float *bias, const float *gamma, const float *beta, const float *mean_in,
+                                  const float *rstd_in, int32_t act, const int64_t *row_ids, uint64_t seed, const int64_t *step,
+                                  uint32_t layer, uint32_t thr, float *dX, int64_t lddx, float *dbias, float *dgamma, float *dbeta,
+                                  void *ws, int64_t ws_bytes, pgcn_stream_t stream);
+
 /* ---- layer normalisation of a vertex over its features + residual link, fused with ReLU and dropout (PGCN.py: _LayerNormReluDropout)
  * The layer y = R + drop(relu(LN(x))) of an nrows x f block of OWNED rows.  Row-local: no collective, and a row's results depend on
  * that row alone -- not on its position, the block that met it, nrows or the rank.

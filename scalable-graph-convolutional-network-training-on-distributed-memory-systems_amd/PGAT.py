@@ -170,12 +170,8 @@ def _f32_inv(x):
     return float(np.float32(1.0) / np.float32(x))
 
 
-def gat_tail_composed(X, heads, d, mean=False, bias=None, act=0, row_ids=None, state=None, layer=0, thr=0, scale=1.0):
-    """Y of the layer tail from framework operations, the definitions of csrc/pgcn_gat_tail.hip: ``mean`` -- the heads added in index
-    order, then one product with 1.0f / heads (none for one head); t = r + bias (None: absent); ``act`` 1: ELU, t > 0 ? t : expm1(t);
-    Y = keep ? a * scale : 0 -- keep the bits of dropout.py under (seed, step, layer, global row id, OUTPUT column); ``state`` None
-    or ``thr`` 0: no dropout.  For CPU tensors, the checker-backed provider of the tests and widths the kernels refuse."""
-    X = X.detach()
+def _tail_t(X, heads, d, mean, bias):
+    """t = reduce_heads(X) + bias, as both tails form it."""
     r = X
     if mean:
         r = X[:, :d]
@@ -183,7 +179,16 @@ def gat_tail_composed(X, heads, d, mean=False, bias=None, act=0, row_ids=None, s
             r = r + X[:, k * d:(k + 1) * d]
         if heads > 1:
             r = r * _f32_inv(heads)
-    t = r + bias.detach() if bias is not None else r
+    return r + bias.detach() if bias is not None else r
+
+
+def gat_tail_composed(X, heads, d, mean=False, bias=None, act=0, row_ids=None, state=None, layer=0, thr=0, scale=1.0):
+    """Y of the layer tail from framework operations, the definitions of csrc/pgcn_gat_tail.hip: ``mean`` -- the heads added in index
+    order, then one product with 1.0f / heads (none for one head); t = r + bias (None: absent); ``act`` 1: ELU, t > 0 ? t : expm1(t);
+    Y = keep ? a * scale : 0 -- keep the bits of dropout.py under (seed, step, layer, global row id, OUTPUT column); ``state`` None
+    or ``thr`` 0: no dropout.  For CPU tensors, the checker-backed provider of the tests and widths the kernels refuse."""
+    X = X.detach()
+    t = _tail_t(X, heads, d, mean, bias)
     a = torch.where(t > 0, t, torch.expm1(t)) if act else t
     if state is not None and thr > 0:
         a = torch.where(_pgcn._bn_keep(a, row_ids, state, layer, thr).to(a.device), a * scale, torch.zeros((), dtype=a.dtype, device=a.device))
@@ -255,6 +260,129 @@ class _GatTail(torch.autograd.Function):
         return (dX if want_dx else None, dbias) + (None,) * 9
 
 
+# ---- the same tail with a per-vertex layer norm and a residual link (csrc/pgcn_gat_tail_ln.hip) -------------------------------------
+def gat_tail_ln_composed(X, heads, d, mean=False, bias=None, gamma=None, beta=None, eps=1e-5, act=0, R=None, row_ids=None, state=None,
+                         layer=0, thr=0, scale=1.0):
+    """(Y, mean, rstd) of R + drop(act(LN(reduce_heads(X) + bias))) from framework operations, the definitions of
+    csrc/pgcn_gat_tail_ln.hip: t as ``gat_tail_composed`` forms it; per ROW mean = sum t / fout, var = sum (t - mean)^2 / fout (biased,
+    two passes), rstd = 1 / sqrt(var + eps); u = gamma (t - mean) rstd + beta; a = u > 0 ? u : expm1(u) with ``act``;
+    Y = R + (keep ? a * scale : 0) -- keep the bits of dropout.py under (seed, step, layer, global row id, OUTPUT column); ``state``
+    None or ``thr`` 0: no dropout; ``R`` None: nothing is added.  For CPU tensors, the checker-backed provider of the tests and widths
+    the kernels refuse."""
+    t = _tail_t(X.detach(), heads, d, mean, bias)
+    f = t.shape[1]
+    mu = t.sum(1) / f
+    e = t - mu.unsqueeze(1)
+    rstd = 1.0 / torch.sqrt((e * e).sum(1) / f + eps)
+    u = torch.addcmul(beta.detach(), gamma.detach(), e * rstd.unsqueeze(1))
+    Y = torch.where(u > 0, u, torch.expm1(u)) if act else u
+    if state is not None and thr > 0:
+        Y = torch.where(_pgcn._bn_keep(Y, row_ids, state, layer, thr).to(Y.device), Y * scale, torch.zeros((), dtype=Y.dtype, device=Y.device))
+    if R is not None:
+        Y = R.detach() + Y
+    return Y, mu, rstd
+
+
+def gat_tail_ln_backward_composed(G, X, heads, d, mean=False, bias=None, gamma=None, beta=None, mu=None, rstd=None, act=0, row_ids=None,
+                                  state=None, layer=0, thr=0, scale=1.0, want_sums=True):
+    """(dX, dbias, dgamma, dbeta) of the same tail from G, X and the saved row statistics: t, xh = (t - mean) rstd and
+    u = gamma xh + beta are formed again; deriv = u <= 0 ? exp(u) : 1 with ``act``; g' = keep ? (G * scale) * deriv : 0 with the keep
+    bits formed again (``state`` at the step of the forward); gh = g' gamma, c1 = sum_j gh / fout, c2 = sum_j gh xh / fout,
+    dT = rstd ((gh - c1) - xh c2); dX = dT (times 1.0f / heads with ``mean``) for every head.  dbias = sum_i dT, dgamma = sum_i g' xh,
+    dbeta = sum_i g': THIS rank's column sums, added in float64 and rounded once (a dropped element adds exact zeros; None unless
+    ``want_sums``).  The residual's gradient is G itself."""
+    drop = state is not None and thr > 0
+    zero = torch.zeros((), dtype=G.dtype, device=G.device)
+    t = _tail_t(X.detach(), heads, d, mean, bias)
+    f = t.shape[1]
+    xh = (t - mu.unsqueeze(1)) * rstd.unsqueeze(1)
+    gm = G * scale if drop else G
+    if act:
+        u = torch.addcmul(beta.detach(), gamma.detach(), xh)
+        gm = torch.where(u <= 0, gm * torch.exp(u), gm)
+    keep = None
+    if drop:
+        keep = _pgcn._bn_keep(G, row_ids, state, layer, thr).to(G.device)
+        gm = torch.where(keep, gm, zero)
+    gh = gm * gamma.detach()
+    c1, c2 = gh.sum(1, keepdim=True) / f, (gh * xh).sum(1, keepdim=True) / f
+    dT = rstd.unsqueeze(1) * ((gh - c1) - xh * c2)
+    dX = dT
+    if mean:
+        dX = (dT * _f32_inv(heads) if heads > 1 else dT).repeat(1, heads)
+    if not want_sums:
+        return dX, None, None, None
+    gx = gm.double() * xh.double()
+    if keep is not None:
+        gx = torch.where(keep, gx, torch.zeros((), dtype=torch.float64, device=G.device))
+    return dX, dT.double().sum(0).to(G.dtype), gx.sum(0).to(G.dtype), gm.double().sum(0).to(G.dtype)
+
+
+def _tail_ln_kernels(X, width, vectors, R=None, row_ids=None, G=None):
+    """The provider whose normalising tail kernels take X (heads * d columns) for an output of ``width`` columns, the per-column
+    vectors and R / G (n x width), or None: PGCN._rowband_kernels."""
+    k = _pgcn._rowband_kernels(_kernel_provider if _kernel_provider is not None else getattr(_engine_current, "k", None),
+                               ("gat_tail_ln_forward", "gat_tail_ln_backward"), (X,), vectors, row_ids, width=width,
+                               max_in=_kernels.GAT_TAIL_MAX_IN)
+    for t in (R, G):                                    # (n x width on X's device, in a layout the kernels take; else the composed twin)
+        if k is not None and t is not None:
+            k = _pgcn._rowband_kernels(k, (), (t,)) if tuple(t.shape) == (X.shape[0], width) and t.device == X.device else None
+    return k
+
+
+class _GatTailNorm(torch.autograd.Function):
+    """R + drop(act(LN(reduce_heads(X) + bias))) as ONE autograd node, LN over each vertex's own output columns: no collective, the
+    same results under any part vector.  On a HIP device one launch forward (pgcn_gat_tail_ln_forward_f32) and one pass backward
+    (pgcn_gat_tail_ln_backward_f32; dbias, dgamma and dbeta summed in double in the same pass).  Saved: X (the engine keeps it alive
+    anyway), the row statistics mean and rstd, and the parameters -- no Y, no mask: u and the keep bits are formed again, so the step
+    must not advance between forward and backward.  R's gradient is G itself.  The sums are THIS rank's.  Anything the kernels do not
+    cover takes ``gat_tail_ln_composed``."""
+
+    @staticmethod
+    def forward(ctx, X, bias, gamma, beta, R, heads, d, mean, act, eps, row_ids, state, layer, thr, scale):
+        drop = bool(state is not None and thr > 0)
+        fout = d if mean else heads * d
+        save = any(ctx.needs_input_grad[:4])               # (only R wants a gradient: that is G itself, nothing to save)
+        k = _tail_ln_kernels(X, fout, (bias, gamma, beta), R, row_ids if drop else None)
+        b = bias.detach() if bias is not None else None
+        if k is not None:
+            Y, mu, rstd = _pgcn._bn_must(k.gat_tail_ln_forward(X, heads, d, mean, b, gamma.detach(), beta.detach(), eps, act,
+                                                               R.detach() if R is not None else None, row_ids if drop else None,
+                                                               state.seed if drop else 0, state.step if drop else None, layer,
+                                                               thr if drop else 0, save=save), "gat_tail_ln_forward", "_tail_ln_kernels")
+        else:
+            Y, mu, rstd = gat_tail_ln_composed(X, heads, d, mean, b, gamma, beta, eps, act, R, row_ids, state if drop else None, layer,
+                                               thr if drop else 0, scale)
+        ctx.cfg = (int(heads), int(d), bool(mean), int(act), row_ids if drop else None, state if drop else None, int(layer),
+                   int(thr) if drop else 0, float(scale) if drop else 1.0, bias is not None, save)
+        if save:
+            ctx.save_for_backward(X, gamma, beta, mu, rstd, *((bias,) if bias is not None else ()))
+        return Y
+
+    @staticmethod
+    def backward(ctx, G):
+        heads, d, mean, act, row_ids, state, layer, thr, scale, has_bias, saved = ctx.cfg
+        Gr = G if ctx.needs_input_grad[4] else None                                   # (the residual's gradient: G itself, no kernel)
+        if not saved:
+            return (None, None, None, None, Gr) + (None,) * 10
+        X, gamma, beta, mu, rstd = ctx.saved_tensors[:5]
+        b = ctx.saved_tensors[5].detach() if has_bias else None
+        want_dx, want_sums = ctx.needs_input_grad[0], any(ctx.needs_input_grad[1:4])
+        if G.stride(1) != 1 or (G.shape[0] > 1 and G.stride(0) < G.shape[1]):
+            G = G.contiguous()
+        k = _tail_ln_kernels(X, G.shape[1], (b, gamma, beta), None, row_ids, G)
+        if k is not None:
+            out = _pgcn._bn_must(k.gat_tail_ln_backward(G, X, heads, d, mean, b, gamma.detach(), beta.detach(), mu, rstd, act, row_ids,
+                                                        state.seed if state is not None else 0,
+                                                        state.step if state is not None else None, layer, thr, want_dx=want_dx,
+                                                        want_sums=want_sums), "gat_tail_ln_backward", "_tail_ln_kernels")
+        else:
+            out = gat_tail_ln_backward_composed(G, X, heads, d, mean, b, gamma, beta, mu, rstd, act, row_ids, state, layer, thr, scale,
+                                                want_sums)
+        dX, dbias, dgamma, dbeta = out
+        return (dX if want_dx else None, dbias if has_bias else None, dgamma, dbeta, Gr) + (None,) * 10
+
+
 # The conflicts among the score options (attention, share_weights, the reference mode, attn_dropout), stated once; the constructor of
 # PGAT ("layer"), run() and the command line ("flags") each render one in their own spelling (%s: the attention, or why no sharing)
 _NO_SHARING = {"v1": "the v1 layer has one projection", "dot": "the dot layer keeps its query, key and value projections apart"}
@@ -292,7 +420,14 @@ class PGAT(nn.Module):
     (``_GatTail``).  ``attn_dropout`` drops the NORMALISED attention coefficients in training mode, per entry and head and after the
     softmax over the whole row (the GAT paper's p = 0.6): alpha' = keep ? alpha / (1 - p) : 0, keep a pure function of (seed, step,
     layer, head, the two GLOBAL vertex ids) -- csrc/pgcn_attndrop.h, ``gat.GatEngine``; it needs ``state`` like ``dropout``, and an
-    evaluation pass makes exactly the calls of a layer without it.  Not here: norms, residual links.
+    evaluation pass makes exactly the calls of a layer without it.
+
+    ``norm="node"`` (opt-in; None | "none" | "node"): layer normalisation of each vertex over its own output columns, between the bias
+    and the activation (``eps``); the layer then owns ``ln_weight`` (ones) and ``ln_bias`` (zeros).  Row-local: no collective, the same
+    results under any part vector.  ``residual=True`` (opt-in; needs ``in_features`` equal to the OUTPUT width): the output is
+    H + tail(...), the GCN layers' order -- convolution, norm, activation, dropout, plus the input.  With the norm both are ONE kernel
+    each way (``_GatTailNorm``, csrc/pgcn_gat_tail_ln.hip); a residual without a norm keeps ``_GatTail`` and adds H as a tensor
+    operation.  The batch norm over all vertices belongs to ``PGCN``.
 
     ``attention="v2"``: the DYNAMIC score of GATv2 (Brody, Alon, Yahav, ICLR 2022), e_ijk = sum_c a[c,k] LeakyReLU(Zt[i,k,c] +
     Zs[j,k,c]) with Zs = H Ws^T (``linear``: the messages and the neighbour's side of the score) and Zt = H Wt^T (``linear_t``: the
@@ -306,7 +441,7 @@ class PGAT(nn.Module):
     ``attn_dropout``."""
 
     def __init__(self, A, in_features, out_features, heads=None, bias=False, activation=None, concat=True, dropout=0.0, layer=0,
-                 state=None, attn_dropout=0.0, attention="v1", share_weights=False):
+                 state=None, attn_dropout=0.0, attention="v1", share_weights=False, norm=None, residual=False, eps=1e-5):
         super(PGAT, self).__init__()
         K = globals()["heads"] if heads is None else heads
         if out_features % K:
@@ -346,11 +481,24 @@ class PGAT(nn.Module):
         self.layer, self.state, self._row_ids = int(layer), state, None
         if self.dropout > 0.0 and state is None:
             raise ValueError("dropout=%r needs state=dropout.DropoutState(...) shared by the model's layers" % (dropout,))
-        self._has_tail = self.has_bias or activation is not None or not self.concat or self.dropout > 0.0
+        if norm == "batch":
+            raise ValueError("norm='batch' (batch normalisation over all vertices) belongs to PGCN: PGAT takes None | 'none' | 'node'")
+        if norm not in (None, "none", "node"):
+            raise ValueError("norm takes None | 'none' | 'node', got %r" % (norm,))
+        self.norm, self.residual, self.ln_eps = (None if norm in (None, "none") else norm), bool(residual), float(eps)
+        fout = out_features if self.concat else out_features // K
+        if self.residual and int(in_features) != fout:
+            raise ValueError("residual=True needs in_features equal to the layer's output width, got %d -> %d" % (in_features, fout))
+        self._has_tail = self.has_bias or activation is not None or not self.concat or self.dropout > 0.0 or self.norm is not None
+        if (self.norm is not None or self.residual) and A is not None and getattr(A, "mode", "standard") == "reference":
+            raise ValueError("the reference layer has no norm and no residual link (norm, residual need mode='standard')")
         if self._has_tail and A is not None and getattr(A, "mode", "standard") == "reference":
             raise ValueError("the reference layer has no bias, activation, head mean or dropout")
         if self.has_bias:
-            self.bias = nn.Parameter(torch.zeros(out_features if self.concat else out_features // K))
+            self.bias = nn.Parameter(torch.zeros(fout))
+        if self.norm is not None:
+            self.ln_weight = nn.Parameter(torch.ones(fout))
+            self.ln_bias = nn.Parameter(torch.zeros(fout))
         self.attn_dropout = float(attn_dropout)
         _dropout.threshold(attn_dropout)
         self._attn_drop = None
@@ -411,9 +559,9 @@ class PGAT(nn.Module):
     def forward(self, H):
         K, d = self.heads, self.out_features // self.heads
         if self.version == "v2":
-            return self._tail(self._forward_v2(H), K, d)
+            return self._tail(self._forward_v2(H), K, d, H)
         if self.version == "dot":
-            return self._tail(self._forward_dot(H), K, d)
+            return self._tail(self._forward_dot(H), K, d, H)
         # Z = self.linear(H) (:140), z1 = Z a1 (:141), z2 = Z a2 (:142) as ONE product: z_k = Z_k a_k = H (W_k^T a_k), so the 2K
         # projection columns ride along as 2K more rows of the weight (K x in each, a tiny product of their own; autograd carries
         # their gradients back to W and the attention vectors).  The per-head einsums they replace ran as skinny batched GEMMs:
@@ -427,18 +575,23 @@ class PGAT(nn.Module):
         if self._attn_drop is not None:                                 # (a layer without the option never touches the field)
             st.drop = self._attn_drop if self.training else None
         out = _gat.GatAggregatePacked.apply(self.A, st, ZS)             # :144-149 on the stored entries
-        return self._tail(out, K, d)
+        return self._tail(out, K, d, H)
 
-    def _tail(self, out, K, d):
+    def _tail(self, out, K, d, H):
         if not self._has_tail:
-            return out
+            return H + out if self.residual else out
         # (its own output: GatEngine.backward reads the state's `out` buffer, so the tail never runs in place here)
         drop = self.training and self.dropout > 0.0
         if drop and (self._row_ids is None or self._row_ids.device != out.device):      # global ids in local row order, once
             self._row_ids = self.A.part.owned.to(device=out.device, dtype=torch.int64).contiguous()
-        return _GatTail.apply(out, self.bias if self.has_bias else None, K, d, not self.concat, 1 if self.activation == "elu" else 0,
-                              self._row_ids if drop else None, self.state if drop else None, self.layer,
-                              self.dropout_thr if drop else 0, self.dropout_scale if drop else 1.0)
+        args = (self._row_ids if drop else None, self.state if drop else None, self.layer, self.dropout_thr if drop else 0,
+                self.dropout_scale if drop else 1.0)
+        bias, act = self.bias if self.has_bias else None, 1 if self.activation == "elu" else 0
+        if self.norm is not None:
+            return _GatTailNorm.apply(out, bias, self.ln_weight, self.ln_bias, H if self.residual else None, K, d, not self.concat, act,
+                                      self.ln_eps, *args)
+        Y = _GatTail.apply(out, bias, K, d, not self.concat, act, *args)
+        return H + Y if self.residual else Y
 
 
 _all_reduce = _pgcn._all_reduce
@@ -547,7 +700,7 @@ def _barrier():
 
 
 def _architecture(fin, classes, nlayers, task=None, hidden=None, out_heads=None, dropout=0.0, dropout_seed=0, bias=None,
-                  attn_dropout=0.0, attention=None, share_weights=None, **_):
+                  attn_dropout=0.0, attention=None, share_weights=None, norm=None, residual=None, **_):
     """checkpoint.architecture of the model ``_train_on_data`` builds from these arguments (and this module's ``heads``)."""
     widths = [int(fin)] + [int(8 * heads if hidden is None else hidden)] * (nlayers - 1) + [int(classes)]
     # (the initial parameters are drawn under dropout_seed, with or without dropout: the record keeps it in the dropout case only,
@@ -555,6 +708,10 @@ def _architecture(fin, classes, nlayers, task=None, hidden=None, out_heads=None,
     extra = {"attn_dropout": float(attn_dropout)} if attn_dropout and float(attn_dropout) > 0.0 else {}
     if attention not in (None, "v1"):                    # (v1: the record of before)
         extra.update(attention=str(attention), share_weights=bool(share_weights))
+    if norm not in (None, "none"):                       # (unset: the record of before, whose norm is "none" and residual False)
+        extra["norm"] = str(norm)
+    if residual:
+        extra["residual"] = True
     return _checkpoint.architecture(widths, task, dropout, dropout_seed, bias=bias, heads=heads,
                                     out_heads=1 if out_heads is None else out_heads, **extra)
 
@@ -563,11 +720,12 @@ TASKS, OPTIMIZERS = _pgcn.TASKS, _pgcn.OPTIMIZERS
 
 
 def build_classifier(A, fin, classes, nlayers, hidden, K, out_heads=1, dropout=0.0, bias=False, state=None, attn_dropout=0.0,
-                     attention="v1", share_weights=False):
+                     attention="v1", share_weights=False, norm=None, residual=False):
     """The model of the GAT paper on the engine ``A``: layers 0 .. L-2 are K concatenated heads of hidden / K columns, ELU, dropout
     on their output; the last layer averages ``out_heads`` heads of ``classes`` columns.  ``attn_dropout``: dropout on the attention
     coefficients of EVERY layer, the last one included, as in the paper.  ``attention="v2"`` (and ``share_weights``): every layer takes
-    the dynamic score of GATv2, ``attention="dot"``: the scaled dot-product score with separate queries, keys and values (class PGAT).  ``widths``: the layers' input widths and the class count."""
+    the dynamic score of GATv2, ``attention="dot"``: the scaled dot-product score with separate queries, keys and values (class PGAT).  ``norm="node"``: every layer but the last normalises each vertex over its own columns; ``residual``: every layer but
+    the last whose input width equals ``hidden`` adds its input to its output (the GCN side's rule).  ``widths``: the layers' input widths and the class count."""
     if hidden % K:
         raise ValueError("hidden (%d) must be divisible by the number of heads (%d)" % (hidden, K))
     widths = [fin] + [hidden] * (nlayers - 1) + [classes]
@@ -578,7 +736,9 @@ def build_classifier(A, fin, classes, nlayers, hidden, K, out_heads=1, dropout=0
         last = {"layer": nlayers - 1, "state": state}
     if attention != "v1" or share_weights:               # (absent: the constructor calls of before)
         extra.update(attention=attention, share_weights=bool(share_weights))
-    layers = [PGAT(A, widths[i], hidden, heads=K, activation="elu", dropout=dropout, layer=i, state=state, **extra)
+    normed = {"norm": norm} if norm not in (None, "none") else {}      # (absent: the constructor calls of before)
+    layers = [PGAT(A, widths[i], hidden, heads=K, activation="elu", dropout=dropout, layer=i, state=state, **extra, **normed,
+                   **({"residual": True} if residual and widths[i] == hidden else {}))
               for i in range(nlayers - 1)]
     layers.append(PGAT(A, widths[nlayers - 1], out_heads * classes, heads=out_heads, concat=False, **extra, **last))
     return nn.Sequential(*layers), widths
@@ -586,7 +746,8 @@ def build_classifier(A, fin, classes, nlayers, hidden, K, out_heads=1, dropout=0
 
 def _train_on_data(A, n, nlayers, features, labels, split, task=None, hidden=None, out_heads=None, epochs=None, lr=None,
                    eval_every=None, dropout=0.0, dropout_seed=0, bias=None, weight_decay=None, decoupled_decay=None, optimizer=None,
-                   save=None, load=None, predict=None, proba=None, control=None, attn_dropout=0.0, attention=None, share_weights=None):
+                   save=None, load=None, predict=None, proba=None, control=None, attn_dropout=0.0, attention=None, share_weights=None,
+                   norm=None, residual=None):
     """The loop of ``run`` on real inputs, the scheme of PGCN._train_on_data (``control``: ``nodeloss.Control``, as there):
     constant features, Adam, the masked loss over the train
     rows (``task="multilabel"``: the masked binary cross entropy and micro-F1).  Reports every ``eval_every`` epochs: without
@@ -618,7 +779,9 @@ def _train_on_data(A, n, nlayers, features, labels, split, task=None, hidden=Non
         model, widths = build_classifier(A, data.fin, data.classes, nlayers, hidden, K, out_heads, dropout, bool(bias), state,
                                          **({"attn_dropout": attn_dropout} if attn_dropout > 0.0 else {}),
                                          **({"attention": attention, "share_weights": bool(share_weights)}
-                                            if attention not in (None, "v1") or share_weights else {}))
+                                            if attention not in (None, "v1") or share_weights else {}),
+                                         **({"norm": norm} if norm not in (None, "none") else {}),
+                                         **({"residual": True} if residual else {}))
     for i, m in enumerate(model):
         _pgcn.tune_dense_gemms(A.part.n_local, widths[i], device, m.projected_width)
     model = model.to(device)
@@ -631,7 +794,7 @@ def _train_on_data(A, n, nlayers, features, labels, split, task=None, hidden=Non
     first, history, best, hooks = 0, [], None, None
     if save is not None or load is not None or predict is not None or proba:
         arch = _architecture(data.fin, data.classes, nlayers, kind, hidden, out_heads, dropout, dropout_seed, bias, attn_dropout,
-                             attention, share_weights)
+                             attention, share_weights, norm, residual)
         hooks = _checkpoint.Hooks("PGAT", arch, model, fused, opt, state, save, load, predict, proba, myrank, _barrier)
         first, history, best = hooks.resume()
     last = first + epochs - 1
@@ -686,7 +849,7 @@ def _train_on_data(A, n, nlayers, features, labels, split, task=None, hidden=Non
 def run(rank, size, nlayers, nfeatures, path_A, path_partvec, backend, epochs=None, features=None, labels=None, split=None, **data):
     """PGAT.py:165-233.  ``features`` / ``labels`` / ``split`` (.npy files in global vertex order, nodedata.py; all three or none):
     train the classifier of ``build_classifier`` on them instead of the synthetic loop (``_train_on_data`` takes the other keyword
-    arguments: task, hidden, out_heads, lr, eval_every, dropout, dropout_seed, attn_dropout, attention, share_weights, bias, weight_decay, decoupled_decay, optimizer, and
+    arguments: task, hidden, out_heads, lr, eval_every, dropout, dropout_seed, attn_dropout, attention, share_weights, norm, residual, bias, weight_decay, decoupled_decay, optimizer, and
     save, load, predict, proba -- checkpoint.py, as in PGCN.run -- and the options of nodeloss.CONTROL: clip_norm, lr_schedule,
     lr_warmup, lr_min, lr_step, lr_gamma, lr_horizon, patience, as in PGCN.run); the returned model carries ``history``, ``best`` and
     ``widths``."""
@@ -712,6 +875,10 @@ def run(rank, size, nlayers, nfeatures, path_A, path_partvec, backend, epochs=No
             raise ValueError("attn_dropout takes a probability in [0, 1), got %r" % (data["attn_dropout"],))
     if data.get("attention") not in (None,) + ATTENTIONS:
         raise ValueError("attention takes %s, got %r" % (" | ".join(ATTENTIONS), data.get("attention")))
+    if data.get("norm") == "batch":
+        raise ValueError("norm='batch' (batch normalisation over all vertices) belongs to PGCN: PGAT takes none | node")
+    if data.get("norm") not in (None, "none", "node"):
+        raise ValueError("norm takes none | node, got %r" % (data.get("norm"),))
     conflict = _score_conflict("run", data.get("attention"), data.get("share_weights"), mode == "reference", data.get("attn_dropout"))
     if conflict:
         raise ValueError(conflict)
@@ -828,7 +995,7 @@ def main(argv):
         opts, args = getopt.getopt(argv, "a:p:b:s:l:f:", ["mode=", "heads=", "features=", "labels=", "split=", "task=", "hidden=",
                                                           "out-heads=", "epochs=", "lr=", "eval-every=", "dropout=", "dropout-seed=", "attn-dropout=",
                                                           "bias", "weight-decay=", "adamw", "optimizer=", "save=", "load=", "predict=",
-                                                          "proba", "attention=", "share-weights"] + [f[2:] + "=" for f in _nodeloss.CONTROL_FLAGS.split(", ")])
+                                                          "proba", "attention=", "share-weights", "norm=", "residual"] + [f[2:] + "=" for f in _nodeloss.CONTROL_FLAGS.split(", ")])
     except getopt.GetoptError:
         print("a:p:b:", flush=True)
         sys.exit(2)
@@ -876,6 +1043,14 @@ def main(argv):
                 refuse("--dropout-seed takes an integer, got %r" % arg)
         elif opt == '--bias':          # every layer adds a bias
             data["bias"] = True
+        elif opt == '--norm':          # node: every layer but the last normalises each vertex over its own columns (class PGAT)
+            if arg == "batch":
+                refuse("--norm batch (batch normalisation over all vertices) belongs to PGCN.py: PGAT.py takes --norm none|node")
+            if arg not in ("none", "node"):
+                refuse("--norm takes none|node, got %r" % arg)
+            data["norm"] = arg
+        elif opt == '--residual':      # every layer but the last whose input is as wide as its output returns H + layer(H) (class PGAT)
+            data["residual"] = True
         elif opt == '--weight-decay':  # Adam's L2 term; with --adamw the decoupled decay of AdamW
             try:
                 data["weight_decay"] = float(arg)
@@ -924,7 +1099,7 @@ def main(argv):
     files = [k for k in ("features", "labels", "split") if k in data]
     if data and len(files) != 3:
         refuse("--features, --labels and --split go together (and --task, --hidden, --out-heads, --epochs, --lr, --eval-every, --dropout, "
-               "--dropout-seed, --attn-dropout, --bias, --weight-decay, --adamw, --save, --load, --predict, --proba, --optimizer, %s need them); got %%s"
+               "--dropout-seed, --attn-dropout, --bias, --norm, --residual, --weight-decay, --adamw, --save, --load, --predict, --proba, --optimizer, %s need them); got %%s"
                % _nodeloss.CONTROL_FLAGS % ", ".join("--" + {"decoupled_decay": "adamw"}.get(k, k.replace("_", "-")) for k in sorted(data)))
     for k in files:
         if not os.path.exists(data[k]):

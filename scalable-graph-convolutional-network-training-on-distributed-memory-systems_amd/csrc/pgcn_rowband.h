@@ -141,7 +141,7 @@ __device__ __forceinline__ bool drop_keep(const DropCols &c, const DropRow &r, i
 }
 
 // ---- column sums ----
-// Folds the 256 / TPR row groups of `acc` (N = 4 or 8 doubles per thread) through `sm` (N x 256 doubles of LDS), k-major so that
+// Folds the 256 / TPR row groups of `acc` (N = 4, 8 or 12 doubles per thread) through `sm` (N x 256 doubles of LDS), k-major so that
 // neighbouring threads touch neighbouring doubles; on return the threads of row group 0 hold the band's sums.
 template <int N>
 __device__ __forceinline__ void fold_row_groups(double (&acc)[N], double *sm, int log2_tpr) {

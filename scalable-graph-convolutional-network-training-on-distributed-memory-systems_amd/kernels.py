@@ -2734,6 +2734,73 @@ class HipKernels:
                                                        _ptr(dbias), _ptr(ws), ws_bytes, self._stream()), "pgcn_gat_tail_backward_f32")
         return dX, dbias
 
+    # -- the same tail with a per-vertex layer norm and a residual link (csrc/pgcn_gat_tail_ln.hip) -----------------------
+    def _gat_tail_ln_ok(self, X, n, heads, d, mean, act, bias, gamma, beta, row_ids, step) -> bool:
+        fin = heads * d
+        fout = d if mean else fin
+        return (heads >= 1 and d >= 1 and act in (0, 1) and fout <= GAT_TAIL_MAX_F and fin <= GAT_TAIL_MAX_IN and
+                self._mat_ok(X, n, fin) and gamma is not None and beta is not None and
+                self._bn_vec_ok(fout, torch.float32, bias, gamma, beta) and self._bn_vec_ok(n, torch.int64, row_ids) and
+                self._bn_vec_ok(1, torch.int64, step))
+
+    def gat_tail_ln_forward(self, X: torch.Tensor, heads: int, d: int, mean: bool, bias: Optional[torch.Tensor], gamma: torch.Tensor,
+                            beta: torch.Tensor, eps: float, act: int, R: Optional[torch.Tensor] = None,
+                            row_ids: Optional[torch.Tensor] = None, seed: int = 0, step: Optional[torch.Tensor] = None, layer: int = 0,
+                            thr: int = 0, save: bool = True, out: Optional[torch.Tensor] = None):
+        """(Y, mean, rstd) of Y = R + drop(act(LN(reduce_heads(X) + bias))) in one launch (pgcn_gat_tail_ln_forward_f32): X is
+        n x heads * d, Y and R n x fout with fout = d (``mean``: the heads averaged) or heads * d; mean / rstd fp32 [n], the row
+        statistics the kernel used (``save`` False, inference: both None and not written).  ``bias`` None: absent; ``act`` 0: none,
+        1: ELU; ``R`` None: nothing is added, ``out`` may be R itself.  The dropout's operands are ``gat_tail_forward``'s.  None when
+        the shape is not covered."""
+        heads, d = int(heads), int(d)
+        if X.dim() != 2 or X.shape[1] != heads * d:
+            return None
+        n, fout = X.shape[0], (d if mean else heads * d)
+        if not self._gat_tail_ln_ok(X, n, heads, d, mean, act, bias, gamma, beta, row_ids, step) or not self._mat_ok(R, n, fout) or \
+                not self._mat_ok(out, n, fout):
+            return None
+        Y = out if out is not None else torch.empty((n, fout), dtype=torch.float32, device=self.device)
+        mu = rstd = None
+        if save:
+            mu = torch.empty(n, dtype=torch.float32, device=self.device)
+            rstd = torch.empty(n, dtype=torch.float32, device=self.device)
+        _lib.check(self.lib.pgcn_gat_tail_ln_forward_f32(X.data_ptr(), self._ld(X), n, heads, d, 1 if mean else 0, _ptr(bias),
+                                                         gamma.data_ptr(), beta.data_ptr(), float(eps), int(act), _ptr(R),
+                                                         self._ld(R) if R is not None else 0, _ptr(row_ids), int(seed) & ((1 << 64) - 1),
+                                                         _ptr(step), int(layer), int(thr), Y.data_ptr(), self._ld(Y), _ptr(mu), _ptr(rstd),
+                                                         self._stream()), "pgcn_gat_tail_ln_forward_f32")
+        return Y, mu, rstd
+
+    def gat_tail_ln_backward(self, G: torch.Tensor, X: torch.Tensor, heads: int, d: int, mean: bool, bias: Optional[torch.Tensor],
+                             gamma: torch.Tensor, beta: torch.Tensor, mu: torch.Tensor, rstd: torch.Tensor, act: int,
+                             row_ids: Optional[torch.Tensor] = None, seed: int = 0, step: Optional[torch.Tensor] = None, layer: int = 0,
+                             thr: int = 0, want_dx: bool = True, want_sums: bool = True, out: Optional[torch.Tensor] = None):
+        """(dX, dbias, dgamma, dbeta) of the same tail from G, X and the forward's row statistics; t, xh, u and the keep bits are
+        formed again (pgcn_gat_tail_ln_backward_f32; one pass + the second level of the sums).  dX is n x heads * d; the three sums
+        fp32 [fout], THIS rank's column sums added in double.  ``want_dx`` False: dX is None (sums only); ``want_sums`` False: the
+        three are None (one launch).  None when the shape is not covered."""
+        heads, d = int(heads), int(d)
+        if G.dim() != 2 or X.dim() != 2 or X.shape[1] != heads * d or mu is None or rstd is None:
+            return None
+        n, fin = X.shape
+        fout = d if mean else fin
+        if not self._gat_tail_ln_ok(X, n, heads, d, mean, act, bias, gamma, beta, row_ids, step) or not self._mat_ok(G, n, fout) or \
+                not self._mat_ok(out, n, fin) or not self._bn_vec_ok(n, torch.float32, mu, rstd):
+            return None
+        dX = dbias = dgamma = dbeta = ws = None
+        ws_bytes = 0
+        if want_dx:
+            dX = out if out is not None else torch.empty((n, fin), dtype=torch.float32, device=self.device)
+        if want_sums:
+            ws, ws_bytes, dbias, dgamma, dbeta = self._sums_ws(self.lib.pgcn_gat_tail_ln_ws_bytes, n, fout, 3)
+        _lib.check(self.lib.pgcn_gat_tail_ln_backward_f32(G.data_ptr(), self._ld(G), X.data_ptr(), self._ld(X), n, heads, d,
+                                                          1 if mean else 0, _ptr(bias), gamma.data_ptr(), beta.data_ptr(), mu.data_ptr(),
+                                                          rstd.data_ptr(), int(act), _ptr(row_ids), int(seed) & ((1 << 64) - 1),
+                                                          _ptr(step), int(layer), int(thr), _ptr(dX), self._ld(dX) if want_dx else 0,
+                                                          _ptr(dbias), _ptr(dgamma), _ptr(dbeta), _ptr(ws), ws_bytes, self._stream()),
+                   "pgcn_gat_tail_ln_backward_f32")
+        return dX, dbias, dgamma, dbeta
+
     # -- layer normalisation of a vertex over its features + residual link, fused with ReLU and dropout (csrc/pgcn_layernorm.hip)
     def ln_relu_forward(self, X: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: float, R: Optional[torch.Tensor] = None,
                         row_ids: Optional[torch.Tensor] = None, seed: int = 0, step: Optional[torch.Tensor] = None, layer: int = 0,
