@@ -594,6 +594,33 @@ int pgcn_spmm_heads_forward2_f32(const int64_t *rowptr, const int32_t *col, cons
                                  float *C2, int64_t ldc2, float *partial_ws, int64_t partial_ws_elems, int64_t nslots,
                                  uint32_t flags, pgcn_stream_t stream);
 
+/* The two recomputing passes above for rows of 257 to 1024 columns (pgcn_spmm_heads_wide.hip): heads <= 8, d = 64, 128 or 256 and
+ * 256 < F = heads * d <= 1024 -- 8 x 64, 4 x 128, 4 x 256, 8 x 128 and everything between.  One wave per task of the plan as there; a
+ * lane owns ceil(F / 256) float4 segments at columns 256 r + 4 lane, and everything that does not depend on the column (the index, the
+ * statistics, the `heads` weights) is formed once per entry for the whole row.
+ *   pgcn_spmm_heads_wide_forward2_f32: the contract of pgcn_spmm_heads_forward2_f32 -- C[:, 0 .. F) (+)= A_alpha . B, C2 = [V | C | 0]
+ *     up to F + heads rounded up to 4, both modes, slope, PGCN_SPMM_ACCUMULATE; work-space nslots x (2 F + heads rounded up to 4).
+ *   pgcn_spmm_heads_wide_grad_f32: the contract of pgcn_spmm_heads_grad_f32 with de == NULL on the transposed structure --
+ *     C = [dZ | ds2 | 0], F + heads rounded up to 4 columns (ldc at least that; a slot row is that wide).  The per-entry gradient
+ *     is not kept at these widths: a non-NULL de answers PGCN_EUNSUPPORTED.
+ * Both: tasks / seg / nslices / fix / slots of the sliced plan, cut rows combined in slot order by pgcn_spmm_fixup_f32, no atomics,
+ * every sum in a fixed order (two calls give the same bits); the arithmetic per entry is that of the narrow kernels.  Nothing is
+ * launched before every check has passed: PGCN_EINVAL for bad sizes, null pointers, a C / C2 / Z too narrow; PGCN_EUNSUPPORTED for a
+ * shape outside the range above, for B / C / the work-space not 16-byte aligned or ldb / ldc not a multiple of 4; PGCN_ENOMEM for
+ * partial_ws_elems below nslots x the slot width.                                                                                    */
+int pgcn_spmm_heads_wide_forward2_f32(const int64_t *rowptr, const int32_t *col, const float *rowstat, const float *s2,
+                                      int64_t lds2, float slope, int32_t mode, int32_t heads, int32_t d, int64_t nrows,
+                                      const int32_t *tasks, int64_t ntasks, const int64_t *seg, int32_t nslices,
+                                      const int32_t *fix, int64_t nfix, const float *B, int64_t ldb, float *C, int64_t ldc,
+                                      float *C2, int64_t ldc2, float *partial_ws, int64_t partial_ws_elems, int64_t nslots,
+                                      uint32_t flags, pgcn_stream_t stream);
+int pgcn_spmm_heads_wide_grad_f32(const int64_t *rowptr, const int32_t *col, const float *rowstat, const float *s2,
+                                  int64_t lds2, float slope, int32_t mode, int32_t heads, int32_t d, int64_t nrows,
+                                  const int32_t *tasks, int64_t ntasks, const int64_t *seg, int32_t nslices,
+                                  const int32_t *fix, int64_t nfix, const float *B, int64_t ldb, const float *Z,
+                                  int64_t ldz, const float *t, float *C, int64_t ldc, float *de, float *partial_ws,
+                                  int64_t partial_ws_elems, int64_t nslots, uint32_t flags, pgcn_stream_t stream);
+
 /* ---- ATTENTION DROPOUT (Velickovic et al., ICLR 2018, section 3.3; no counterpart in the reference): the two gather passes above with
  * the normalised coefficients dropped anew at every training step, per entry AND head (pgcn_gat_attndrop.hip).  csrc/pgcn_attndrop.h
  * states the keep function:

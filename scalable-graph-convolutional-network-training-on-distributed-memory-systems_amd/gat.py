@@ -274,6 +274,8 @@ class GatEngine(BoundaryExchange):
         self.fused_grad = _T.gat_fused_grad and self.multi_head and hasattr(kernels, "spmm_heads_grad")
         # ... and the forward product with recomputed weights + the second accumulator that makes de unnecessary
         self.fused_fwd = _T.gat_fused_forward and self.fused_grad and hasattr(kernels, "spmm_heads_forward2")
+        # ... both at 257 to 1024 columns (pgcn_spmm_heads_wide.hip)
+        self.wide = _T.gat_wide and self.fused_fwd
 
     @property
     def inv_perm(self) -> torch.Tensor:
@@ -308,6 +310,12 @@ class GatEngine(BoundaryExchange):
         hl = d // 4
         return d % 4 == 0 and hl >= 8 and hl & (hl - 1) == 0 and heads * d <= 256 and heads <= 8
 
+    def _wide(self, heads: int, d: int) -> bool:
+        """Shapes beyond ``covers`` that the v1 route takes through the same two passes (pgcn_spmm_heads_wide_forward2_f32 / _grad_f32):
+        257 to 1024 columns.  The whole structure goes through the gather kernels there: no blocks, no ``gat_row_dots``."""
+        shapes = getattr(self.k, "_heads_wide", None)      # (the provider states the shapes once; one without the kernels has none)
+        return bool(self.wide and shapes is not None and shapes(heads, d))
+
     @staticmethod
     def padded_width(F: int, heads: int) -> int:
         return (F + heads + 3) // 4 * 4
@@ -340,7 +348,7 @@ class GatEngine(BoundaryExchange):
             rg, cg = self._gids(name)
             return self.k.gat_attndrop_forward2(A, st.rowstat, s2, self.slope, B, out, st.V, K, d, rg, cg, drop.state.seed,
                                                 drop.state.step, drop.layer, drop.thr, accumulate=accumulate)
-        part = self.parts.get(name) if d == 64 else None
+        part = self.parts.get(name) if d == 64 and K * d <= 256 else None     # (wider rows: the whole structure in the gather kernel)
         if not self.k.spmm_heads_forward2(part[0] if part else A, st.rowstat, s2, self.slope, self.mode_id, B, out, st.V, K, d,
                                           accumulate=accumulate):
             return False
@@ -354,7 +362,7 @@ class GatEngine(BoundaryExchange):
             rg, cg = self._gids(name)      # (rows of the transposed structure: the neighbours gj; its columns: the attending gi)
             return self.k.gat_attndrop_grad(AT, st.rowstat, s2, self.slope, dOut, Z, t, dZc, K, d, rg, cg, drop.state.seed,
                                             drop.state.step, drop.layer, drop.thr)
-        part = self.parts.get(name) if d == 64 else None
+        part = self.parts.get(name) if d == 64 and K * d <= 256 else None
         if not self.k.spmm_heads_grad(part[0] if part else AT, st.rowstat, s2, self.slope, self.mode_id, dOut, Z, t, dZc, None, K, d):
             return False
         if part and not self.k.gat_blocks_backward(part[1], st.rowstat, s2, self.slope, dOut, Z, t, dZc, K, d):
@@ -397,7 +405,7 @@ class GatEngine(BoundaryExchange):
         st.fused = False
         # what every rank decides alike: ranks with halo rows exchange the s2 rows first.  The exchange is a collective, so a rank of
         # several WITHOUT halo rows (one that owns nothing, one without an edge to a peer) takes its part in that exchange too, below
-        splits = (self.size > 1 and self.overlap and self.fused_fwd and self.covers(K, d) and self.mode_id == 0
+        splits = (self.size > 1 and self.overlap and self.fused_fwd and (self.covers(K, d) or self._wide(K, d)) and self.mode_id == 0
                   and (drop is None or self._drop_kernels(K, d)))
         split = splits and n_h > 0 and self.fwd_halo is not None
         if split:
@@ -423,7 +431,8 @@ class GatEngine(BoundaryExchange):
             if ok:
                 ok = self._forward2("fwd_halo", st, st.s2c[n_p:], Zc[n_p:], out, K, d, accumulate=True, drop=drop)
             if not ok:
-                raise RuntimeError("the split GAT forward was refused by a kernel whose shape `covers` accepted")
+                raise RuntimeError("the split GAT forward was refused by a kernel whose shape `covers` or `_wide` accepted (%d x %d: "
+                                   "an alignment or leading dimension the shape predicates do not model)" % (K, d))
             st.fused = True
             st.out = out
             return out
@@ -450,7 +459,7 @@ class GatEngine(BoundaryExchange):
             st.fused = True
             st.out = out
             return out
-        if self.fused_fwd and self.covers(K, d):
+        if self.fused_fwd and (self.covers(K, d) or self._wide(K, d)):
             # statistics only, then ONE gather pass: out, and V | C for the backward's ds1 (no alpha planes, no de)
             self.k.gat_edge_softmax(self.fwd, st.s1, st.s2c, K, self.slope, self.mode_id, self.n_global,
                                     None, st.beta, st.rowstat)
@@ -501,7 +510,8 @@ class GatEngine(BoundaryExchange):
                 back = self._slab("gat_send", self.n_send, Fp)
                 waits = self._exchange_all(dZc[n_p:], self.round_recv_off, back, self.round_send_off, Fp, tag="backward")
                 if not self._grad("bwd_local", st, st.s2c[:n_p], dOut, st.Zc[:n_p], t, dZc[:n_p], K, d, drop=drop):
-                    raise RuntimeError("the local part of the fused GAT backward was refused after its halo part was taken")
+                    raise RuntimeError("the local part of the fused GAT backward was refused after its halo part was taken (%d x %d, "
+                                       "%s kernels)" % (K, d, "wide" if self._wide(K, d) else "narrow"))
                 ds1 = dots[1] if dots is not None and dots[1] is not None else \
                     (dOut.view(n_p, K, d) * st.V[:, :F].view(n_p, K, d)).sum(-1) - t * st.V[:, F:F + K]
                 return self._finish_backward(st, dOut, dZc, ds1, pack, waits=(back, waits))

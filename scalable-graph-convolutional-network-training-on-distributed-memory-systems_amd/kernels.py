@@ -1611,10 +1611,12 @@ class HipKernels:
         accumulator (pgcn_spmm_heads_forward2_f32): C[:, :F] (+)= A_alpha . B; C2[:, :F] (+)= V = sum_j c_ij B_j and
         C2[:, F:F+heads] (+)= sum_j c_ij with c = alpha x LeakyReLU' (standard) or alpha + beta (reference), from
         which the backward pass gets ds1 = <dOut, V> - t C without a per-entry gradient.  rowstat: [A.nrows, heads, 4];
-        s2: [A.ncols, heads].  False = shape not covered (d must be 32, 64, 128 or 256)."""
+        s2: [A.ncols, heads].  False = shape not covered (d must be 32, 64, 128 or 256).  Rows of 257 to 1024 columns
+        (d = 64, 128 or 256) run pgcn_spmm_heads_wide_forward2_f32, the same contract."""
         F = heads * d
         hl = d // 4
-        if d % 4 or hl < 8 or hl & (hl - 1) or F > 256 or heads > 8:
+        wide = self._heads_wide(heads, d)
+        if not wide and (d % 4 or hl < 8 or hl & (hl - 1) or F > 256 or heads > 8):
             return False
         pw2 = F + (heads + 3) // 4 * 4
         self._check_rows(s2, A.ncols, heads, "s2")
@@ -1637,15 +1639,21 @@ class HipKernels:
             A.ws = torch.empty(need, dtype=torch.float32, device=self.device)
             A.launch_cache.clear()
         flags = _lib.SPMM_ACCUMULATE if accumulate else 0
-        rc = self.lib.pgcn_spmm_heads_forward2_f32(
+        name = "pgcn_spmm_heads_wide_forward2_f32" if wide else "pgcn_spmm_heads_forward2_f32"
+        rc = getattr(self.lib, name)(
             A.rowptr.data_ptr(), A.col.data_ptr(), rowstat.data_ptr(), s2.data_ptr(), s2.stride(0), slope, mode, heads, d,
             A.nrows, _ptr(A.tasks), A.ntasks, A.seg, A.nslices, _ptr(A.fix), A.nfix, B.data_ptr(), B.stride(0),
             C.data_ptr(), C.stride(0), C2.data_ptr(), C2.stride(0), _ptr(A.ws), 0 if A.ws is None else A.ws.numel(),
             A.nslots, flags, self._stream())
         if rc == _lib.PGCN_EUNSUPPORTED:
             return False
-        _lib.check(rc, "pgcn_spmm_heads_forward2_f32")
+        _lib.check(rc, name)
         return True
+
+    @staticmethod
+    def _heads_wide(heads: int, d: int) -> bool:
+        """Shapes of pgcn_spmm_heads_wide.hip: rows of 257 to 1024 columns, a head of 16, 32 or 64 lanes."""
+        return d in (64, 128, 256) and 1 <= heads <= 8 and 256 < heads * d <= 1024
 
     def spmm_heads_grad(self, AT: DeviceCSR, rowstat: torch.Tensor, s2: torch.Tensor, slope: float, mode: int,
                         B: torch.Tensor, Z: torch.Tensor, t: torch.Tensor, C: torch.Tensor, de: Optional[torch.Tensor],
@@ -1654,11 +1662,15 @@ class HipKernels:
         gather pass (pgcn_spmm_heads_grad_f32): C[:, :F] (+)= A_alpha^T . B, de[q] = the edge gradient of entry q of
         ``AT`` (entry-major [nnz, heads]), C[:, F:F+heads] (+)= its row sums (ds2).  Z: rows of AT ([>= AT.nrows, >= F]),
         t: [AT.ncols, heads].  de = None: the per-entry gradient is not kept (ds1 then comes from the forward pass's
-        second accumulator, ``spmm_heads_forward2``).  False = shape not covered (d must be 32, 64, 128 or 256)."""
+        second accumulator, ``spmm_heads_forward2``).  False = shape not covered (d must be 32, 64, 128 or 256).  Rows of
+        257 to 1024 columns (d = 64, 128 or 256) run pgcn_spmm_heads_wide_grad_f32, which keeps no ``de``: False with one."""
         F = heads * d
         hl = d // 4
-        if d % 4 or hl < 8 or hl & (hl - 1) or F > 256 or heads > 8:
-            return False                   # (the C entry point answers PGCN_EUNSUPPORTED for these too)
+        wide = self._heads_wide(heads, d)
+        if wide and de is not None:
+            return False
+        if not wide and (d % 4 or hl < 8 or hl & (hl - 1) or F > 256 or heads > 8):
+            return False                   # (the C entry points answer PGCN_EUNSUPPORTED for these too)
         pw = F + (heads + 3) // 4 * 4
         nnz = AT.col.numel()
         self._check_rows(s2, AT.nrows, heads, "s2")
@@ -1684,14 +1696,15 @@ class HipKernels:
             AT.ws = torch.empty(need, dtype=torch.float32, device=self.device)
             AT.launch_cache.clear()
         flags = _lib.SPMM_ACCUMULATE if accumulate else 0
-        rc = self.lib.pgcn_spmm_heads_grad_f32(
+        name = "pgcn_spmm_heads_wide_grad_f32" if wide else "pgcn_spmm_heads_grad_f32"
+        rc = getattr(self.lib, name)(
             AT.rowptr.data_ptr(), AT.col.data_ptr(), rowstat.data_ptr(), s2.data_ptr(), s2.stride(0), slope, mode, heads, d,
             AT.nrows, _ptr(AT.tasks), AT.ntasks, AT.seg, AT.nslices, _ptr(AT.fix), AT.nfix, B.data_ptr(), B.stride(0),
             Z.data_ptr(), Z.stride(0), t.data_ptr(), C.data_ptr(), C.stride(0), _ptr(de), _ptr(AT.ws),
             0 if AT.ws is None else AT.ws.numel(), AT.nslots, flags, self._stream())
         if rc == _lib.PGCN_EUNSUPPORTED:
             return False
-        _lib.check(rc, "pgcn_spmm_heads_grad_f32")
+        _lib.check(rc, name)
         return True
 
     # -- attention dropout (pgcn_gat_attndrop.hip): the masked twins of the two calls above ------------------------------

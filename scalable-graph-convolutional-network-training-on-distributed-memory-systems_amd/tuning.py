@@ -158,6 +158,9 @@ class Tuning:
     gat_multihead: bool = True       # all heads of attention @ Z in one launch
     gat_fused_grad: bool = True      # edge gradient inside the transposed product's gather pass (one pass fewer)
     gat_fused_forward: bool = True   # forward product with recomputed weights + second accumulator (no alpha / de arrays)
+    gat_wide: bool = True            # v1 layers of 257 to 1024 columns (d = 64, 128, 256) on the two recomputing passes of pgcn_spmm_heads_wide.hip;
+                                     # off = the route of before (alpha planes, one SpMM per head, stored edge gradient): the A/B switch of
+                                     # tools/gat_wide_probe.py
 
 
 def _parse(spec: str, base: Tuning) -> Tuning:
